@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the ACE Zero hot path on MI355X (contract: see the round prompt / DESIGN.md).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher's environment: re-executes itself under
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                                                               (N > 1 without a launcher's environment: re-executes itself under
                                                                 torch.distributed.run with N ranks, one per GPU)
+
+K is the number of timed headline steps (one window after W warm-up steps); `ms_per_step` on the line = that window / K. With
+--dump-outputs the state the last timed step left (head parameters, AdamW moments, the batch's scene coordinates, the step's scalars) is
+written to DIR/<name>.npy; every input is seeded, so two builds run with the same arguments can be compared output for output.
 
 A "step" is one training iteration of the scene-coordinate head (ace_trainer.py:499-679) on 5120 patches per
 GPU drawn from an 8M-patch synthetic feature buffer resident in HBM (BASELINE config[1]: full ace_zero.py
@@ -39,7 +44,8 @@ MFMA_PEAK_TFLOPS = 2500.0         # MI355X dense bf16 (MI355X_MICROARCH.md)
 CSRC = os.path.join(ROOT, "acezero_amd", "csrc")
 STEP_SOURCES = ("head_api.hip", "head_kernels.hip", "head_kernels.h", "gemm_common.h", "pose_kernels.hip", "pose_small.hip", "pose_fused.hip")
 RANSAC_SOURCES = ("ransac_api.hip", "ransac_math.h", "det_math.h")
-WINDOWS = 5                       # timed windows of --steps steps each: `value` = mean over all of them, ms_per_step = their median
+WINDOWS = 5                       # timed windows of the auxiliary legs (100 steps each); the headline leg times exactly --steps steps in one window
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: the arrays written stay below this in all
 
 
 def src_digest(files):
@@ -130,6 +136,9 @@ def parse():
     ap.add_argument("--smoke-same-device", action="store_true")
     # internal: the one-rank RCCL legs as a child process of the default run (dp_world1_legs)
     ap.add_argument("--dp-world1-legs", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (head parameters, AdamW moments, the batch's scene "
+                         "coordinates, loss / lr / inliers) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared array by array")
     return ap.parse_args()
 
 
@@ -152,8 +161,26 @@ def make_buffer(n_patches, device, seed, n_images=1000, grid=(80, 60), feature_d
     return prob, feats, target_px, view_idx
 
 
+def dump_outputs(tr, dump_dir, rows):
+    """What a caller of HeadTrainer.step holds after the last timed step: the updated fp32 head parameters and AdamW moments, the pose
+    network's parameters (pose refinement only), the scene coordinates the step predicted for its `rows` batch rows, and the step's
+    scalars. float32 / float64 .npy files, DUMP_LIMIT_BYTES in all at most."""
+    st = tr.state()
+    arrays = {"head_params": tr.params, "adam_m": tr.adam_m, "adam_v": tr.adam_v}
+    if tr.pose_params is not None:
+        arrays["pose_params"] = tr.pose_params
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    arrays["scene_coords"] = tr.last_scene_coords(rows)
+    arrays["step_state"] = np.array([st["iteration"], st["loss"], st["batch_inliers"], st["lr"], st["focal_scale"]], np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit"
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), a)
+
+
 def bench_training(args, rank, world, device, pose_refinement=None, steps=None, buffer_patches=None, strong=False, windows=WINDOWS,
-                   n_images=1000, grid=(80, 60), dtype="bf16"):
+                   n_images=1000, grid=(80, 60), dtype="bf16", dump_dir=None):
     """pose_refinement None -> args.pose_refinement (the headline leg); 'mlp' -> ace_zero's non-seed mapping iterations
     (--pose_refinement mlp --refine_calibration True, ace_zero.py:86,97,262-264).
     strong=True: the REFERENCE's step on N GPUs -- the global batch stays 5120, every rank draws the same permutation of the global
@@ -206,8 +233,7 @@ def bench_training(args, rank, world, device, pose_refinement=None, steps=None, 
 
     for i in range(args.warmup):
         step(i)
-    # `windows` timed windows of exactly `steps` steps, each bracketed by barrier + synchronize (the first one is the contract's
-    # timed region; a 20-step window lasts 3 ms, so one window alone moves by several percent from box to box and run to run)
+    # `windows` timed windows of exactly `steps` steps, each bracketed by barrier + synchronize (the headline leg: one window of --steps)
     wins = []
     for w in range(windows):
         if dist is not None:
@@ -221,6 +247,8 @@ def bench_training(args, rank, world, device, pose_refinement=None, steps=None, 
         torch.cuda.synchronize()
         wins.append(time.perf_counter() - t0)
     dt = sum(wins) / windows          # mean time of a window of `steps` steps
+    if dump_dir is not None and rank == 0:   # outside the timed region, before the profiled steps below move the state on
+        dump_outputs(tr, dump_dir, len(batches[(args.warmup + windows * steps - 1) % len(batches)]))
     st = tr.state()
     assert st["iteration"] == args.warmup + windows * steps and not st["nan"], st
     st["window_ms_per_step"] = [w / steps * 1e3 for w in wins]
@@ -513,20 +541,6 @@ def cpu_baseline():
         steps += 1
     t_train = (time.perf_counter() - t0) / max(steps, 1)
     kind, train_what = "port", f"{steps} steps of 5120 patches, oracle/head_oracle.py fp32 on torch-CPU with {tcores} of {cores} host threads"
-    if os.path.isdir("/root/reference"):
-        # the reference itself (build container only: /root/reference does not exist on the GPU box): the unmodified
-        # TrainerACE.training_step through the stub-import recipe of tests/golden/make_head_golden.py
-        try:
-            import importlib.util
-            spec = importlib.util.spec_from_file_location("make_head_golden", os.path.join(ROOT, "tests", "golden", "make_head_golden.py"))
-            mk = importlib.util.module_from_spec(spec)
-            spec.loader.exec_module(mk)
-            t_ref, n_ref = mk.time_reference_step(batch=BATCH, budget_s=12.0, max_steps=40, threads=tcores)
-            t_train, kind = t_ref, "reference"
-            train_what = (f"{n_ref} calls of the reference's TrainerACE.training_step (ace_trainer.py:499-679) at 5120 patches, CPU PyTorch fp32, "
-                          f"{tcores} of {cores} host threads (the reference pins them to 1 at import, ace_trainer.py:5-8: overridden)")
-        except Exception as e:   # noqa: BLE001 -- a broken reference import must not take the bench down
-            train_what += f" (reference import failed: {type(e).__name__})"
     fr = synth.make_registration_frames(seed=5, n_frames=16)
     dsac_oracle.lib()
 
@@ -569,9 +583,9 @@ def cpu_baseline():
     except (OSError, ValueError, KeyError):
         pass
     return {"value": BATCH / t_train, "unit": "patches/s", "cores": tcores, "kind": kind, "reference_stored": ref_stored,
-            "kind_note": "reference = the reference's own training_step (only where /root/reference exists); port = oracle/ restatement "
-                         "(the GPU box has no reference checkout). The registration figures are always the oracle port: the reference's "
-                         "dsacstar needs OpenCV 4.4.0, which is not available.",
+            "kind_note": "port = oracle/ restatement (the benchmark reads nothing outside the repository; the reference's own figure is "
+                         "reference_stored). The registration figures are the oracle port too: the reference's dsacstar needs OpenCV 4.4.0, "
+                         "which is not available.",
             "registration_images_per_s_12_threads": 1.0 / t_reg12,
             "point_cloud_frames_per_s": 1.0 / t_cloud,
             "sample": train_what + f"; registration: {nfr} frames, oracle/dsac_oracle.cpp, {cores} threads (and with the reference's 12)",
@@ -678,7 +692,9 @@ def main():
         rccl_ranks = world if torch.distributed.get_backend() == "nccl" else 0
     assert world == args.gpus, (world, args.gpus)
 
-    dt, st, prof = bench_training(args, rank, world, device, dtype=args.dtype if args.headline_only else "bf16")
+    # the headline leg: exactly --steps timed steps (one window), ms_per_step = that window / --steps
+    dt, st, prof = bench_training(args, rank, world, device, dtype=args.dtype if args.headline_only else "bf16", windows=1,
+                                  dump_dir=args.dump_outputs)
     dev_state = device_state(device) if rank == 0 else None
     if args.headline_only:
         if world > 1:
@@ -689,7 +705,7 @@ def main():
             torch.distributed.destroy_process_group()
         if rank == 0:
             print(json.dumps({"metric": "ACE patches/sec", "value": BATCH * world * args.steps / dt, "unit": "patches/s", "n_gpus": world,
-                              "rccl_ranks": rccl_ranks, "steps": args.steps, "warmup": args.warmup, "ms_per_step": float(np.median(st["window_ms_per_step"])),
+                              "rccl_ranks": rccl_ranks, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
                               "ms_per_step_mean": dt / args.steps * 1e3, "window_ms_per_step": st["window_ms_per_step"], "headline_only": True,
                               "pose_refinement": args.pose_refinement, "dtype": args.dtype,
                               "per_class_us_per_step": {k: v[0] / 20 * 1e3 for k, v in prof.items()}, "final_loss": st["loss"], "device_state": dev_state}),
@@ -804,8 +820,8 @@ def main():
                         "session_1000_registered": (ss or {}).get("registered"), "session_1000_source": ss_why or "profiles/%s_session_1000_frames.json" % PROFILE_TAG})
         out = {
             "metric": "ACE patches/sec", "value": patches_per_s, "unit": "patches/s", "n_gpus": world, "rccl_ranks": rccl_ranks, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": float(np.median(st["window_ms_per_step"])), "ms_per_step_mean": dt / args.steps * 1e3,
-            "window_ms_per_step": st["window_ms_per_step"], "windows": WINDOWS, "higher_is_better": True, "scaling": "weak",
+            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "ms_per_step_mean": dt / args.steps * 1e3,
+            "window_ms_per_step": st["window_ms_per_step"], "windows": 1, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
             "config": {"workload": "7-Scenes-chess-like ace_zero mapping step: 8M-patch bf16 feature buffer in HBM, batch 5120 per GPU, "
                                    "default head (1 block, 2 103 300 params), tanh loss, 1cyclepoly AdamW, pose_refinement " + args.pose_refinement,

@@ -17,7 +17,17 @@ import types
 from unittest.mock import MagicMock
 
 import numpy as np
-import torch
+
+# --compatible-sgemm (the fixtures of test_head_oracle.py::test_oracle_fp32_matches_reference_golden, which runs the oracle on the same
+# arithmetic in a child process): MKL's COMPATIBLE branch, which computes the same sgemm bits on every x86-64 host and thread count, and
+# the reference's 1x1 convolutions lowered to that sgemm (oneDNN off: its kernels and blocking depend on the host). Without the flag the
+# host's default paths run (the long trajectories of test_focal_drift.py / test_trajectory.py and the B = 5120 fixtures).
+COMPATIBLE_SGEMM = "--compatible-sgemm" in sys.argv
+if COMPATIBLE_SGEMM:
+    os.environ["MKL_CBWR"] = "COMPATIBLE"
+import torch  # noqa: E402
+if COMPATIBLE_SGEMM:
+    torch.backends.mkldnn.enabled = False
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -204,40 +214,9 @@ def run_reference(cfg, prob, flat0, batches):
     return rec, snaps, coords0
 
 
-def time_reference_step(batch=5120, budget_s=12.0, max_steps=40, threads=None):
-    """Seconds per TrainerACE.training_step of the REFERENCE on this host's cores (CPU PyTorch fp32) at `batch` patches: bench.py's
-    cpu_baseline, kind "reference", when /root/reference is present (the reference pins BLAS / OpenMP to one thread at import,
-    ace_trainer.py:5-8; overridden here and stated with the number)."""
-    global B
-    if threads:
-        torch.set_num_threads(threads)
-    cfg = full_cfg(CONFIGS["head_tanh_1cyclepoly"])
-    cfg.update(global_batch=batch, lr_min=0.0005, lr_max=0.003, warmup_iterations=1000, warmup_lr=0.0005, cooldown_iterations=5000,
-               cooldown_trigger_percent=0.7, iterations=25000)
-    prob = synth.make_training_problem(seed=3, n_images=20, views_per_image=2, patches_per_view=128)
-    flat0 = head_oracle.init_params(1)
-    rng = np.random.default_rng(0)
-    idx = rng.integers(0, prob["features"].shape[0], batch)
-    old_B, B = B, batch
-    try:
-        t_steps = []
-        run_reference(cfg, prob, flat0, [idx])                     # warm-up (allocations, thread pools)
-        t0 = time.perf_counter()
-        n = 0
-        while time.perf_counter() - t0 < budget_s and n < max_steps:
-            t1 = time.perf_counter()
-            run_reference(cfg, prob, flat0, [idx, idx][:1])
-            t_steps.append(time.perf_counter() - t1)
-            n += 1
-    finally:
-        B = old_B
-    # run_reference rebuilds the head and the optimiser for every call; the step itself is the bulk (0.2-0.4 s of a call)
-    return float(np.median(t_steps)), n
-
-
 def main():
     out_dir = os.path.dirname(os.path.abspath(__file__))
-    only = sys.argv[1:]   # optional: names of the configurations to (re)generate
+    only = [a for a in sys.argv[1:] if not a.startswith("--")]   # optional: names of the configurations to (re)generate
     from tests import helpers   # the "trained regime" configurations and their problem live next to the tests that consume them
     global B
     for name, c in (list(CONFIGS.items()) + list(helpers.TRAINED_CONFIGS.items()) + [("head_focal_drift", helpers.FOCAL_DRIFT), ("head_trajectory", helpers.TRAJECTORY)] +

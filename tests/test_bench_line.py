@@ -17,9 +17,16 @@ def test_bench_json_line_contract(monkeypatch, seq):
     monkeypatch.setenv("ACEZ_SEQ", seq)
     monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
     monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
-    wins = [0.1551, 0.1549, 0.1550, 0.1620, 0.1548]             # five timed windows: the median is quoted, the mean gives `value`
-    monkeypatch.setattr(bench, "bench_training", lambda *a, **k: (300 * sum(wins) / 5 * 1e-3 if not k.get("steps") else k["steps"] * 240e-6,
-                                                                  {"loss": 22.3, "focal_scale": 1.01, "window_ms_per_step": list(wins)}, prof))
+    win = 0.1553                                                 # the headline leg: ONE timed window of exactly --steps steps
+    wins = [0.2401, 0.2399, 0.2400, 0.2470, 0.2398]             # the auxiliary legs: five windows of 100 steps
+    headline_calls = []
+
+    def training(*a, **k):
+        if k.get("steps"):
+            return k["steps"] * 240e-6, {"loss": 22.3, "focal_scale": 1.01, "window_ms_per_step": list(wins)}, prof
+        headline_calls.append(k)
+        return 300 * win * 1e-3, {"loss": 22.3, "focal_scale": 1.01, "window_ms_per_step": [win]}, prof
+    monkeypatch.setattr(bench, "bench_training", training)
     monkeypatch.setattr(bench, "bench_registration", lambda *a, **k: (2048, 2048 / 340e3, 1.0))
     monkeypatch.setattr(bench, "bench_dp_rank_proxy", lambda args, device, rows, **k: 0.150 if rows == 5120 else 0.110)
     monkeypatch.setattr(bench, "dp_world1_legs", lambda args: ({"allreduce_rccl": 0.150, "sharded_skipped": 0.150, "sharded_rccl": 0.150,
@@ -37,8 +44,11 @@ def test_bench_json_line_contract(monkeypatch, seq):
     d = json.loads(lines[0])
     assert d["metric"] == "ACE patches/sec" and d["unit"] == "patches/s" and d["n_gpus"] == 1 and d["higher_is_better"] is True
     assert d["steps"] == 300 and d["warmup"] == 30 and d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "bf16"
-    assert abs(d["value"] - 5120 / (sum(wins) / 5 * 1e-3)) < 1 and abs(d["ms_per_step"] - 0.1550) < 1e-9 and "workload" in d["config"]
-    assert d["windows"] == 5 and d["window_ms_per_step"] == wins and abs(d["ms_per_step_mean"] - sum(wins) / 5) < 1e-9
+    assert abs(d["value"] - 5120 / (win * 1e-3)) < 1 and abs(d["ms_per_step"] - win) < 1e-9 and "workload" in d["config"]
+    assert d["windows"] == 1 and d["window_ms_per_step"] == [win] and abs(d["ms_per_step_mean"] - win) < 1e-9
+    # --steps is the number of timed steps: the headline leg is one window of args.steps, and no dump unless asked for
+    assert len(headline_calls) == 1 and headline_calls[0]["windows"] == 1 and headline_calls[0]["dump_dir"] is None
+    assert abs(d["summary"]["refinement_ms_per_step"] - 0.2400) < 1e-9
     assert d["garden_like"]["training"]["n_images"] == 185 and d["garden_like"]["registration"]["map"] == "60x93"
     assert d["refinement_step"]["ms_per_step"] > 0 and "mfma_busy_frac" in d["roofline"] and d["dtype_fp16"]["ms_per_step"] > 0
     r = d["roofline"]

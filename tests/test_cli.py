@@ -59,8 +59,9 @@ def test_pose_line_format_roundtrip(tmp_path):
     assert float(tok[8]) == 525.0 and float(tok[9]) == 1234
 
 
-def test_missing_feature_file_is_a_clear_error():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "train_ace.py"), "x/*.png", "/tmp/out.pt"], capture_output=True, text=True, cwd=ROOT)
+def test_missing_feature_file_is_a_clear_error(tmp_path):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "train_ace.py"), "x/*.png", str(tmp_path / "out.pt")], capture_output=True, text=True,
+                       cwd=ROOT)
     assert r.returncode != 0 and "no files match" in (r.stderr + r.stdout)
 
 

@@ -1,5 +1,7 @@
 """CPU: the head oracle (fp32 mode) against the golden vectors produced by the reference's own training_step."""
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -8,9 +10,23 @@ import torch
 from oracle import head_oracle
 from tests import helpers
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
 
 @pytest.mark.parametrize("name", list(helpers.HEAD_CONFIGS) + list(helpers.TRAINED_CONFIGS))
 def test_oracle_fp32_matches_reference_golden(name, golden_dir):
+    """The first steps are compared at tolerances that a different sgemm code path or thread count exceeds, and MKL picks its kernels by
+    CPU vendor and model. So the comparison runs in a child process on MKL's COMPATIBLE branch, which computes the same sgemm bits on every
+    x86-64 host, and on a fixed number of threads (the split of the reductions); the fixtures were made on that branch
+    (tests/golden/make_head_golden.py --compatible-sgemm)."""
+    code = "import sys; sys.path.insert(0, %r); from tests.test_head_oracle import check_against_golden; check_against_golden(%r, %r)" % (
+        ROOT, name, golden_dir)
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MKL_CBWR="COMPATIBLE", OMP_NUM_THREADS="8", MKL_NUM_THREADS="8"), capture_output=True, text=True,
+                       timeout=900)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
+
+
+def check_against_golden(name, golden_dir):
     g = np.load(os.path.join(golden_dir, name + ".npz"))
     prob, flat0, cfg = helpers.problem_for(name)
     batches = helpers.golden_batches(prob, cfg["steps"])
