@@ -93,6 +93,10 @@ SYMBOLS = {
     "acez_trainer_import_weights16_all": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "acez_train_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "acez_train_step_next": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "acez_train_group_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int]),
+    "acez_train_group_destroy": (None, [C.c_void_p]),
+    "acez_train_group_step": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_int32), C.c_void_p]),
     "acez_trainer_get_state": (C.c_int, [C.c_void_p, C.POINTER(TrainState), C.c_void_p]),
     "acez_trainer_get_log": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acez_trainer_last_scene_coords": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

@@ -132,7 +132,9 @@ ACE_ZERO_FLAGS = [
     (("--refit_iterations",), int, 25000, None, ""),
     (("--registration_confidence",), int, 500, None, "inlier count above which an image counts as registered"),
     (("--try_seeds",), int, 5, None, "number of seed images to try"),
-    (("--seed_parallel_workers",), int, 3, None, "accepted; seeds run back to back in one process"),
+    (("--seed_parallel_workers",), int, 3, None, "accepted; the seed trials are mapped one after the other: trained side by side "
+                                                 "(ReconstructionSession.reconstruct(seed_parallel_workers=...), one head group) they give the "
+                                                 "same result and measured no faster on one MI355X"),
     (("--seed_iterations",), int, 10000, None, ""),
     (("--seed_network",), Path, None, None, "pre-trained head to start from"),
     (("--warmstart",), _strtobool, True, None, ""),
@@ -641,7 +643,7 @@ def ace_zero_main(argv=None):
     if opt.seed_network is not None:
         over["seed_network"] = torch.load(opt.seed_network, map_location="cpu")
     ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, opt=default_options(**over), depth=depth)
-    res = ses.reconstruct()
+    res = ses.reconstruct()   # (seed trials one after the other: side by side is not faster here)
     if rank != 0:                                                       # every rank holds the same result; rank 0 writes it
         import torch.distributed as dist
         dist.barrier()

@@ -135,7 +135,7 @@ enum { KC_SCHED = 0, KC_GATHER, KC_GEMM_FWD, KC_LOSS, KC_GEMM_DGRAD, KC_WGRAD, K
 struct ProfScope {
   acez_trainer* tr; hipStream_t s; int cls; int i0 = -1;
   ProfScope(acez_trainer* t, hipStream_t st, int c) : tr(t), s(st), cls(c) {
-    if (!tr->profiling) return;
+    if (!tr->profiling || c < 0) return;   // (c < 0: nothing is launched in this scope)
     if (tr->ev_next + 2 > tr->ev_pool.size()) {
       for (int i = 0; i < 64; ++i) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; tr->ev_pool.push_back(e); }
     }
@@ -548,10 +548,12 @@ static void launch_rowseq(acez_trainer* tr, const std::vector<SeqLayer>& layers,
   }
 }
 
-static uint16_t* launch_forward(acez_trainer* tr, const uint16_t* in0, int n, const TrainState* st, hipStream_t s) {
-  ProfScope chain_scope(tr, s, KC_GEMM_FWD);  // one event pair around the whole chain of dependent GEMM launches
+// collect != null: nothing is launched; the layer table of the one-launch chain goes to *collect (head_group.hip builds its tables so)
+static uint16_t* launch_forward(acez_trainer* tr, const uint16_t* in0, int n, const TrainState* st, hipStream_t s,
+                                std::vector<SeqLayer>* collect = nullptr) {
+  ProfScope chain_scope(tr, s, collect ? -1 : KC_GEMM_FWD);  // one event pair around the whole chain of dependent GEMM launches
   const float* P = tr->pb.d_params;
-  const bool seq = seq_usable(tr, n);
+  const bool seq = collect || seq_usable(tr, n);
   std::vector<SeqLayer> sq;
   // a training forward (st != null) leaves every layer's ReLU mask as bits for the input-gradient chain; fc2's mask is applied by the loss kernel
   auto mask_out = [&](int l) -> uint2* { return (st && tr->maskbits && l != 3 * (tr->nb + 1) + 1) ? tr->maskbits + (size_t)l * tr->mask_stride : nullptr; };
@@ -583,7 +585,8 @@ static uint16_t* launch_forward(acez_trainer* tr, const uint16_t* in0, int n, co
   const int f1 = 3 * (tr->nb + 1), f2 = f1 + 1;
   gemm(f1, r, tr->out[f1], nullptr, nullptr);
   gemm(f2, tr->out[f1], tr->out[f2], nullptr, nullptr);
-  if (seq) launch_rowseq<false>(tr, sq, n, st, s);
+  if (collect) *collect = sq;
+  else if (seq) launch_rowseq<false>(tr, sq, n, st, s);
   return tr->out[f2];
 }
 
@@ -741,44 +744,11 @@ static void fill_wgrad_args(acez_trainer* tr, WgradArgs& a, int n, const TrainSt
   a.slabs = tr->slabs; a.slab_stride = tr->n_wide; a.M = n; a.nslabs = tr->nslabs; a.n_layers = tr->L; a.st = st; a.zeros = tr->zeros; a.dbg = 0;
 }
 
-static int train_backward_impl(acez_trainer* tr, const int64_t* d_indices, int n, void* stream, bool fused, const int64_t* d_next = nullptr,
-                               int n_next = 0) {
-  ACEZ_REQUIRE(tr && d_indices, "null pointer");
-  ACEZ_REQUIRE(!tr->inference_only, "an inference-only context (acez_train_config.inference_only) cannot train");
-  ACEZ_REQUIRE(tr->have_buf, "acez_trainer_set_buffer has not been called");
-  ACEZ_REQUIRE(n > 0 && n <= tr->max_batch, "n must be in [1, max_batch]");
-  ACEZ_HIP_CHECK(hipSetDevice(tr->device));
-  hipStream_t s = (hipStream_t)stream;
-  const TrainState* st = tr->st;   // (re-read below: the launch that closes the previous step moves the state to the other slot)
-  tr->last_n = n;
-
-  const bool pose_naive = tr->cfg.pose_refinement == 1;
-  const bool pose_mlp = tr->cfg.pose_refinement == 2 || pose_naive;   // both need the refined-pose table and per-row pose gradients
-  // Pose refinement on its own stream: the refined poses are needed by the loss phase only, so their launches run beside the
-  // head's forward chain; the pose-gradient launches run beside the input-gradient chain and wgrad.
-  hipStream_t ps = (pose_mlp && tr->pose_stream) ? tr->pose_stream : s;
-  // mlp refinement folded into the step's own launches (pose_fused.hip): forward beside the gather, backward beside / behind the optimiser
+// The launch that opens a step: the gather of its batch (unless acez_train_step_next of the step before has gathered it), with the schedule
+// bookkeeping of the previous step and, when the pose network is folded in, its forward. Afterwards tr->st is the slot the step reads.
+static void begin_batch(acez_trainer* tr, const int64_t* d_indices, int n, hipStream_t s) {
   const bool pf = tr->pose_fused;
-  const int f1 = 3 * (tr->nb + 1), f2 = f1 + 1;
-  const int nblk = (n + 4 * tr->loss_rows - 1) / (4 * tr->loss_rows);
-  auto pose_fwd_launches = [&](hipStream_t q) {
-    if (tr->cfg.pose_refinement == 2) pose_forward(tr, &tr->st->active, q);
-    if (pose_naive)   // refine_poses.py:224-234: the poses themselves are the parameters; P = 0 + 1 * params, then Gram-Schmidt
-      hipLaunchKernelGGL(pose_compose_kernel, dim3((tr->buf.n_images + 255) / 256), dim3(256), 0, q, (const float*)tr->pa1,
-                         (const float*)tr->pb.d_pose_params, 1.0f, tr->pose_cur, tr->buf.n_images, (const int*)&tr->st->active, tr->cfg.pose_refinement_ortho);
-  };
-  auto pose_bwd_launches = [&](hipStream_t q) {
-    if (tr->cfg.pose_refinement == 2) pose_backward(tr, n, &tr->st->active, q);
-    if (pose_naive) {
-      const int I = tr->buf.n_images;
-      launch_pose_grad_reduce(tr, n, (const int*)&tr->st->active, q);
-      hipLaunchKernelGGL(pose_compose_bwd_kernel, dim3((I + 255) / 256), dim3(256), 0, q, (const float*)tr->pa1, (const float*)tr->pb.d_pose_params, 1.0f,
-                         (const float*)tr->pdT, tr->pb.d_grad + tr->n_params + 4, I, (const int*)&tr->st->active, tr->cfg.pose_refinement_ortho);
-    }
-  };
-
-  uint16_t* act = nullptr;
-  {
+  const TrainState* st = tr->st;
   // (pose refinement folded into the step's launches: the batch may have been gathered ahead too -- beside the loss kernel of the step
   // before, round 5 -- but the launch below still runs: the pose network's forward and the schedule wave ride in it, with no gather blocks)
   const bool pre_ok = tr->pre_idx == d_indices && tr->pre_n == n;
@@ -812,47 +782,35 @@ static int train_backward_impl(acez_trainer* tr, const int64_t* d_indices, int n
   }
   delete psg;
   }
-  }
-  st = tr->st;   // the slot the bookkeeping (if any rode with the gather) has just written
-  if (ps != s) {   // after the schedule bookkeeping of step_begin (the pose kernels read st->active / pose_enable)
-    ACEZ_HIP_CHECK(hipEventRecord(tr->ev_begin, s));
-    ACEZ_HIP_CHECK(hipStreamWaitEvent(ps, tr->ev_begin, 0));
-  }
-  if (!pf) pose_fwd_launches(ps);
-  if (ps != s) ACEZ_HIP_CHECK(hipEventRecord(tr->ev_pose_fwd, ps));
-  act = launch_forward(tr, tr->R[0], n, st, s);
-  if (ps != s) ACEZ_HIP_CHECK(hipStreamWaitEvent(s, tr->ev_pose_fwd, 0));   // the loss kernel projects with the refined poses
+}
 
-  {
-    LossArgs a{};
-    fill_loss_train(tr, a, act, d_indices, n, pose_mlp);
-    tr->last_nblk = nblk;   // (after this step's step_begin, whose schedule wave closed the step BEFORE with that step's count)
-    ProfScope ps(tr, s, KC_LOSS);
-    tr->next_gathered = false;
-    if (fused && d_next && n_next > 0 && (wgrad_opt_usable(tr) || pf) && tr->loss_rows == 4 && tr->R0_alt) {
-      // the next batch's gather as extra workgroups of the loss launch (this path has no optimiser launch to carry it): 32 rows per
-      // workgroup and pass, as many workgroups as the loss kernel leaves free (two of these workgroups fit a CU)
-      const int want = (n_next + 31) / 32, room = std::max(32, 2 * tr->n_cus - nblk);
-      const int gblocks = std::min(want, room);
-      GatherMeta gm = gather_meta(tr);
-      gm.dst = tr->batch_meta_alt;
-      if (tr->f16) hipLaunchKernelGGL((loss_gather_kernel<EltF16, 4>), dim3(nblk + gblocks), dim3(256), 0, s, a, nblk, (const uint16_t*)tr->buf.d_features, d_next, tr->R0_alt, n_next, gm);
-      else hipLaunchKernelGGL((loss_gather_kernel<EltBf16, 4>), dim3(nblk + gblocks), dim3(256), 0, s, a, nblk, (const uint16_t*)tr->buf.d_features, d_next, tr->R0_alt, n_next, gm);
-      tr->next_gathered = true; tr->next_idx = d_next; tr->next_n = n_next;
-    } else {
-      launch_loss(tr, nblk, s, a);
-    }
+// The loss launch of a training step (+ the next batch's gather beside it, when announced on a path that has no optimiser launch to carry it)
+static void launch_train_loss(acez_trainer* tr, const uint16_t* act, const int64_t* d_indices, int n, int nblk, hipStream_t s, bool fused,
+                              const int64_t* d_next, int n_next, bool pose_tables) {
+  LossArgs a{};
+  fill_loss_train(tr, a, act, d_indices, n, pose_tables);
+  tr->last_nblk = nblk;   // (after this step's step_begin, whose schedule wave closed the step BEFORE with that step's count)
+  ProfScope ps(tr, s, KC_LOSS);
+  tr->next_gathered = false;
+  if (fused && d_next && n_next > 0 && (wgrad_opt_usable(tr) || tr->pose_fused) && tr->loss_rows == 4 && tr->R0_alt) {
+    // the next batch's gather as extra workgroups of the loss launch (this path has no optimiser launch to carry it): 32 rows per
+    // workgroup and pass, as many workgroups as the loss kernel leaves free (two of these workgroups fit a CU)
+    const int want = (n_next + 31) / 32, room = std::max(32, 2 * tr->n_cus - nblk);
+    const int gblocks = std::min(want, room);
+    GatherMeta gm = gather_meta(tr);
+    gm.dst = tr->batch_meta_alt;
+    if (tr->f16) hipLaunchKernelGGL((loss_gather_kernel<EltF16, 4>), dim3(nblk + gblocks), dim3(256), 0, s, a, nblk, (const uint16_t*)tr->buf.d_features, d_next, tr->R0_alt, n_next, gm);
+    else hipLaunchKernelGGL((loss_gather_kernel<EltBf16, 4>), dim3(nblk + gblocks), dim3(256), 0, s, a, nblk, (const uint16_t*)tr->buf.d_features, d_next, tr->R0_alt, n_next, gm);
+    tr->next_gathered = true; tr->next_idx = d_next; tr->next_n = n_next;
+  } else {
+    launch_loss(tr, nblk, s, a);
   }
+}
 
-  if (ps != s) {   // the pose gradients start from the per-row pose gradients the loss kernel has just written
-    ACEZ_HIP_CHECK(hipEventRecord(tr->ev_loss, s));
-    ACEZ_HIP_CHECK(hipStreamWaitEvent(ps, tr->ev_loss, 0));
-  }
-  if (!pf) pose_bwd_launches(ps);
-  if (ps != s) ACEZ_HIP_CHECK(hipEventRecord(tr->ev_pose_bwd, ps));
-
-  // input-gradient chain
-  const bool seq = seq_usable(tr, n);
+// The input-gradient chain of a training step (collect != null: nothing is launched, the one-launch chain's layer table goes to *collect)
+static void launch_dgrad(acez_trainer* tr, int n, const TrainState* st, hipStream_t s, std::vector<SeqLayer>* collect = nullptr) {
+  const int f1 = 3 * (tr->nb + 1), f2 = f1 + 1;
+  const bool seq = collect || seq_usable(tr, n);
   std::vector<SeqLayer> sq;
   auto dgrad = [&](int l, int l_out, const uint16_t* add, uint16_t* out_main, uint16_t* out_aux) {
     const uint2* mask = tr->maskbits + (size_t)l_out * tr->mask_stride;   // the bits forward layer l_out left (RowGemmArgs::mask_in)
@@ -873,7 +831,7 @@ static int train_backward_impl(acez_trainer* tr, const int64_t* d_indices, int n
     launch_rowgemm(g, s, tr->f16);
     ++tr->prof_launches;
   };
-  ProfScope* dchain = new ProfScope(tr, s, KC_GEMM_DGRAD);
+  ProfScope dchain(tr, s, collect ? -1 : KC_GEMM_DGRAD);
   dgrad(f2, f1, nullptr, tr->dZ[f1], nullptr);
   int cur = 0;
   dgrad(f1, 3 * tr->nb + 2, nullptr, tr->dZ[3 * tr->nb + 2], tr->dR[cur]);
@@ -885,9 +843,14 @@ static int train_backward_impl(acez_trainer* tr, const int64_t* d_indices, int n
       cur ^= 1;
     }
   }
-  if (seq) launch_rowseq<true>(tr, sq, n, st, s);
+  if (collect) *collect = sq;
+  else if (seq) launch_rowseq<true>(tr, sq, n, st, s);
+}
 
-  delete dchain;
+// The partial buffers of a step and its weight-gradient launch (fused: wgrad_opt_kernel where usable); the split flow's gradient reduction
+static void launch_weight_grads(acez_trainer* tr, int n, int nblk, const TrainState* st, hipStream_t s, bool fused) {
+  const bool pf = tr->pose_fused;
+  const int f2 = 3 * (tr->nb + 1) + 1;
   // the partial buffers of this step (reduced by grad_reduce_kernel in the split flow, by the optimiser launches in the fused step)
   {
     GradReduceArgs a{};
@@ -955,6 +918,65 @@ static int train_backward_impl(acez_trainer* tr, const int64_t* d_indices, int n
       hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(wide_blocks + tail_blocks)), dim3(256), 0, s, tr->last_reduce);
     }
   }
+}
+
+static int train_backward_impl(acez_trainer* tr, const int64_t* d_indices, int n, void* stream, bool fused, const int64_t* d_next = nullptr,
+                               int n_next = 0) {
+  ACEZ_REQUIRE(tr && d_indices, "null pointer");
+  ACEZ_REQUIRE(!tr->inference_only, "an inference-only context (acez_train_config.inference_only) cannot train");
+  ACEZ_REQUIRE(tr->have_buf, "acez_trainer_set_buffer has not been called");
+  ACEZ_REQUIRE(n > 0 && n <= tr->max_batch, "n must be in [1, max_batch]");
+  ACEZ_HIP_CHECK(hipSetDevice(tr->device));
+  hipStream_t s = (hipStream_t)stream;
+  const TrainState* st = tr->st;   // (re-read below: the launch that closes the previous step moves the state to the other slot)
+  tr->last_n = n;
+
+  const bool pose_naive = tr->cfg.pose_refinement == 1;
+  const bool pose_mlp = tr->cfg.pose_refinement == 2 || pose_naive;   // both need the refined-pose table and per-row pose gradients
+  // Pose refinement on its own stream: the refined poses are needed by the loss phase only, so their launches run beside the
+  // head's forward chain; the pose-gradient launches run beside the input-gradient chain and wgrad.
+  hipStream_t ps = (pose_mlp && tr->pose_stream) ? tr->pose_stream : s;
+  // mlp refinement folded into the step's own launches (pose_fused.hip): forward beside the gather, backward beside / behind the optimiser
+  const bool pf = tr->pose_fused;
+  const int nblk = (n + 4 * tr->loss_rows - 1) / (4 * tr->loss_rows);
+  auto pose_fwd_launches = [&](hipStream_t q) {
+    if (tr->cfg.pose_refinement == 2) pose_forward(tr, &tr->st->active, q);
+    if (pose_naive)   // refine_poses.py:224-234: the poses themselves are the parameters; P = 0 + 1 * params, then Gram-Schmidt
+      hipLaunchKernelGGL(pose_compose_kernel, dim3((tr->buf.n_images + 255) / 256), dim3(256), 0, q, (const float*)tr->pa1,
+                         (const float*)tr->pb.d_pose_params, 1.0f, tr->pose_cur, tr->buf.n_images, (const int*)&tr->st->active, tr->cfg.pose_refinement_ortho);
+  };
+  auto pose_bwd_launches = [&](hipStream_t q) {
+    if (tr->cfg.pose_refinement == 2) pose_backward(tr, n, &tr->st->active, q);
+    if (pose_naive) {
+      const int I = tr->buf.n_images;
+      launch_pose_grad_reduce(tr, n, (const int*)&tr->st->active, q);
+      hipLaunchKernelGGL(pose_compose_bwd_kernel, dim3((I + 255) / 256), dim3(256), 0, q, (const float*)tr->pa1, (const float*)tr->pb.d_pose_params, 1.0f,
+                         (const float*)tr->pdT, tr->pb.d_grad + tr->n_params + 4, I, (const int*)&tr->st->active, tr->cfg.pose_refinement_ortho);
+    }
+  };
+
+  begin_batch(tr, d_indices, n, s);
+  st = tr->st;   // the slot the bookkeeping (if any rode with the gather) has just written
+  if (ps != s) {   // after the schedule bookkeeping of step_begin (the pose kernels read st->active / pose_enable)
+    ACEZ_HIP_CHECK(hipEventRecord(tr->ev_begin, s));
+    ACEZ_HIP_CHECK(hipStreamWaitEvent(ps, tr->ev_begin, 0));
+  }
+  if (!pf) pose_fwd_launches(ps);
+  if (ps != s) ACEZ_HIP_CHECK(hipEventRecord(tr->ev_pose_fwd, ps));
+  const uint16_t* act = launch_forward(tr, tr->R[0], n, st, s);
+  if (ps != s) ACEZ_HIP_CHECK(hipStreamWaitEvent(s, tr->ev_pose_fwd, 0));   // the loss kernel projects with the refined poses
+
+  launch_train_loss(tr, act, d_indices, n, nblk, s, fused, d_next, n_next, pose_mlp);
+
+  if (ps != s) {   // the pose gradients start from the per-row pose gradients the loss kernel has just written
+    ACEZ_HIP_CHECK(hipEventRecord(tr->ev_loss, s));
+    ACEZ_HIP_CHECK(hipStreamWaitEvent(ps, tr->ev_loss, 0));
+  }
+  if (!pf) pose_bwd_launches(ps);
+  if (ps != s) ACEZ_HIP_CHECK(hipEventRecord(tr->ev_pose_bwd, ps));
+
+  launch_dgrad(tr, n, st, s);
+  launch_weight_grads(tr, n, nblk, st, s, fused);
   if (ps != s) ACEZ_HIP_CHECK(hipStreamWaitEvent(s, tr->ev_pose_bwd, 0));   // d_grad's pose tail: read by the all-reduce and by the pose AdamW
   if (pf && !fused) launch_pose_wgrad(tr, &tr->st->active, false, s);
   ACEZ_HIP_CHECK(hipGetLastError());
@@ -1362,3 +1384,5 @@ extern "C" int acez_trainer_get_poses(acez_trainer* tr, float* h_poses34, void* 
   ACEZ_HIP_CHECK(hipStreamSynchronize(s));
   return ACEZ_OK;
 }
+
+#include "head_group.hip"   // acez_train_group_*: several trainers stepped in one launch sequence

@@ -1,0 +1,244 @@
+// head_group.hip -- several independent trainers stepped in one launch sequence (include/acez.h, acez_train_group_*).
+// Included by head_api.hip (it drives the trainers' own step phases). A group step advances every member by exactly one
+// acez_train_step / acez_train_step_next: each member's gather, loss, weight-gradient / optimiser and schedule launches are the ones
+// its own step issues, and the two dependent GEMM chains of all members run as ONE launch each (rowseq_group_kernel), whose bodies are
+// rowseq_kernel's (rowgemm80_body<..., SEQ>): bitwise the members' own steps, in any order mixed with their single steps.
+//
+// Why: a workgroup of rowseq_kernel spends most of a layer filling its ring and waiting at the seam for its three siblings (~1.1 us of
+// MFMA work in a 5.2-5.8 us layer). In the group chain a workgroup runs layer l of head 0, 1, ..., H-1 before layer l + 1 of head 0: the
+// seam it waits on was closed while it worked on the other heads' tiles, and the next body's first W stages are requested behind the
+// current epilogue exactly as between two layers of one head. Measured: 0.96 x the members' own steps at H = 3 --
+// the members' activations together no longer fit the Infinity Cache -- so the session does not use it by default.
+
+constexpr int GROUP_MAX = 8;
+
+// one member's chain layer tables (device memory, written once by acez_train_group_create)
+struct GroupHead {
+  SeqLayer fwd[2][MAX_LAYERS];   // [which of the trainer's two input buffers is R[0] this step][layer] (acez_train_step_next swaps them)
+  SeqLayer bwd[MAX_LAYERS];
+  uint32_t* flags;               // the trainer's hand-off counters + sticky fault word (RowSeqArgs::flags)
+  uint32_t spin_limit;
+  int pad;
+};
+
+// per-step arguments (kernel argument block: no host-to-device copy per step)
+struct RowSeqGroupArgs {
+  const GroupHead* heads;
+  const TrainState* st[GROUP_MAX];
+  int M[GROUP_MAX];
+  int variant[GROUP_MAX];              // GroupHead::fwd index
+  uint32_t base[GROUP_MAX][64];        // per member and row tile: seams completed by earlier launches (RowSeqArgs::base)
+  int H, layer0, n_layers, mtiles;     // layers [layer0, layer0 + n_layers) of every member's table; mtiles = the largest member's
+};
+
+template <bool BWD, class E = EltBf16>
+__global__ __launch_bounds__(512) void rowseq_group_kernel(RowSeqGroupArgs a) {
+  __shared__ __attribute__((aligned(16))) uint16_t smem[RG80_SMEM_SEQ];
+  __shared__ uint32_t run_mask;
+  // rowseq_kernel's decode over the largest member's row tiles: the four column tiles of row tile mt of EVERY member share one XCD
+  const int per_xcd = (a.mtiles + 7) >> 3;
+  const int jx = blockIdx.x >> 3;
+  const int mt = (blockIdx.x & 7) * per_xcd + (jx >> 2);
+  if (mt >= a.mtiles) return;
+  const int n0 = (jx & 3) * 128;
+  if (threadIdx.x == 0) {
+    // which members this workgroup runs, decided once for the whole workgroup: row tile mt inside the member's batch, its schedule
+    // active and its fault word down (rowseq_kernel's entry test, per member). A member that does not run keeps its counters in step with
+    // the host's bases exactly as rowseq_kernel's early return does; row tiles past a member's batch are not counted (launch_rowseq).
+    uint32_t run = 0;
+    for (int h = 0; h < a.H; ++h) {
+      if (mt >= (a.M[h] + 79) / 80) continue;
+      uint32_t* flags = a.heads[h].flags;
+      if ((a.st[h] && !a.st[h]->active) || flags[64 * 32]) {
+        const uint32_t inc = 8u * (uint32_t)(a.n_layers - 1);
+        asm volatile("global_atomic_add %0, %1, off" ::"v"(flags + mt * 32), "v"(inc) : "memory");
+        continue;
+      }
+      run |= 1u << h;
+    }
+    run_mask = run;
+  }
+  __syncthreads();
+  const uint32_t run = __builtin_amdgcn_readfirstlane(run_mask);
+  if (!run) return;
+  auto table = [&](int h, int layer) -> const SeqLayer& {
+    const GroupHead& g = a.heads[h];
+    return BWD ? g.bwd[a.layer0 + layer] : g.fwd[a.variant[h]][a.layer0 + layer];
+  };
+  bool first = true;
+  for (int layer = 0; layer < a.n_layers; ++layer) {
+    for (int h = 0; h < a.H; ++h) {
+      if (!((run >> h) & 1u)) continue;
+      const SeqLayer& y = table(h, layer);
+      // the body this workgroup runs next: the next member of this layer, else the first member of the next layer
+      const uint32_t later = run & ~((2u << h) - 1u);
+      const uint16_t* next_W = nullptr;
+      if (later) next_W = table(__builtin_ctz(later), layer).W;
+      else if (layer + 1 < a.n_layers) next_W = table(__builtin_ctz(run), layer + 1).W;
+      const TrainState* st = a.st[h];
+      RowGemmArgs g;
+      g.In = y.In; g.W = y.W; g.bias = y.bias; g.add = y.add; g.mask_out = y.mask_out; g.mask_in = y.mask_in; g.res = y.res; g.out_main = y.out_main; g.out_aux = y.out_aux;
+      g.bias_partials = y.bias_partials; g.M = a.M[h]; g.N = 512; g.K = 512; g.relu = BWD ? 0 : 1; g.aux_mode = y.aux_mode; g.st = st; g.dbg = 0;
+      g.absmax = (BWD && st) ? const_cast<uint32_t*>(st->dz_absmax_slots) : nullptr;
+      SeqLink q;
+      // (target and budget are scalar operands of the poll: the table lives in global memory, so say that they are uniform)
+      q.flag = a.heads[h].flags + mt * 32;
+      q.target = (uint32_t)__builtin_amdgcn_readfirstlane((int)((a.base[h][mt] + (uint32_t)layer) * 32u));
+      q.first = first; q.wait = layer > 0; q.signal = layer + 1 < a.n_layers;
+      q.next_W = next_W;
+      q.flag_index = (uint32_t)(mt * 32); q.limit = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.heads[h].spin_limit);
+      first = false;
+      if (!BWD) {
+        if (y.aux_mode == AUX_RESIDUAL) rowgemm80_body<true, false, false, AUX_RESIDUAL, true, E>(g, smem, 1, mt, n0, q);
+        else rowgemm80_body<true, false, false, AUX_NONE, true, E>(g, smem, 1, mt, n0, q);
+      } else {
+        if (y.add) rowgemm80_body<false, true, true, AUX_UNMASKED, true, E>(g, smem, 1, mt, n0, q);
+        else if (y.aux_mode == AUX_UNMASKED) rowgemm80_body<false, false, true, AUX_UNMASKED, true, E>(g, smem, 1, mt, n0, q);
+        else rowgemm80_body<false, false, true, AUX_NONE, true, E>(g, smem, 1, mt, n0, q);
+      }
+    }
+  }
+}
+
+struct acez_train_group {
+  std::vector<acez_trainer*> m;
+  std::vector<const uint16_t*> in0;   // the buffer GroupHead::fwd[0] was built on (R[0] at creation)
+  GroupHead* d_heads = nullptr;
+  int n_fwd = 0, n_bwd = 0;
+};
+
+extern "C" void acez_train_group_destroy(acez_train_group* g) {
+  if (!g) return;
+  if (g->d_heads) (void)hipFree(g->d_heads);
+  delete g;
+}
+
+extern "C" int acez_train_group_create(acez_train_group** out, acez_trainer* const* members, int h) {
+  ACEZ_REQUIRE(out && members, "null pointer");
+  ACEZ_REQUIRE(h >= 1 && h <= GROUP_MAX, "a group has 1 to 8 members");
+  for (int i = 0; i < h; ++i) {
+    const acez_trainer* t = members[i];
+    ACEZ_REQUIRE(t, "null member");
+    ACEZ_REQUIRE(!t->inference_only, "an inference-only context cannot be a group member");
+    ACEZ_REQUIRE(t->cfg.pose_refinement == 0, "group members train without pose refinement");
+    ACEZ_REQUIRE(t->cfg.refine_calibration == 0, "group members train without calibration refinement");
+    for (int j = 0; j < i; ++j) ACEZ_REQUIRE(members[j] != t, "the same trainer is listed twice");
+    const acez_trainer* t0 = members[0];
+    ACEZ_REQUIRE(t->device == t0->device, "group members must be on one device");
+    ACEZ_REQUIRE(t->f16 == t0->f16, "group members must have the same compute_dtype");
+    ACEZ_REQUIRE(t->nb == t0->nb, "group members must have the same num_head_blocks");
+    ACEZ_REQUIRE(t->cfg.head.use_homogeneous == t0->cfg.head.use_homogeneous, "group members must have the same use_homogeneous");
+  }
+  ACEZ_HIP_CHECK(hipSetDevice(members[0]->device));
+  acez_train_group* g = new (std::nothrow) acez_train_group();
+  ACEZ_REQUIRE(g, "out of host memory");
+  std::vector<GroupHead> heads(h);
+  for (int i = 0; i < h; ++i) {
+    acez_trainer* t = members[i];
+    GroupHead& gh = heads[i];
+    memset(&gh, 0, sizeof(gh));
+    // the members' own chain tables: what launch_forward / launch_dgrad hand to rowseq_kernel (a training forward: st != null)
+    std::vector<SeqLayer> f0, f1, b;
+    launch_forward(t, t->R[0], t->max_batch, t->st, nullptr, &f0);
+    launch_forward(t, t->R0_alt, t->max_batch, t->st, nullptr, &f1);
+    launch_dgrad(t, t->max_batch, t->st, nullptr, &b);
+    for (size_t l = 0; l < f0.size(); ++l) { gh.fwd[0][l] = f0[l]; gh.fwd[1][l] = f1[l]; }
+    for (size_t l = 0; l < b.size(); ++l) gh.bwd[l] = b[l];
+    gh.flags = t->seq_flags; gh.spin_limit = t->seq_spin_limit;
+    g->m.push_back(t);
+    g->in0.push_back(t->R[0]);
+    g->n_fwd = (int)f0.size(); g->n_bwd = (int)b.size();
+  }
+  if (hipMalloc((void**)&g->d_heads, sizeof(GroupHead) * h) != hipSuccess ||
+      hipMemcpy(g->d_heads, heads.data(), sizeof(GroupHead) * h, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    acez_train_group_destroy(g);
+    set_error("acez_train_group_create: device allocation failed");
+    return ACEZ_ERR_HIP;
+  }
+  *out = g;
+  return ACEZ_OK;
+}
+
+// one of the two GEMM chains of the members listed in `idx` (all of them seq_usable for their batch) as one launch per SEQ_MAX_LAYERS
+// layers, with launch_rowseq's host bookkeeping per member
+template <bool BWD>
+static void launch_rowseq_group(acez_train_group* g, const std::vector<int>& idx, const int* n, const TrainState* const* st, hipStream_t s) {
+  const int total = BWD ? g->n_bwd : g->n_fwd;
+  const bool f16 = g->m[0]->f16;
+  for (int i0 = 0; i0 < total; i0 += SEQ_MAX_LAYERS) {
+    const int cnt = std::min(SEQ_MAX_LAYERS, total - i0);
+    RowSeqGroupArgs a{};
+    a.heads = g->d_heads; a.H = GROUP_MAX; a.layer0 = i0; a.n_layers = cnt; a.mtiles = 0;
+    // members that sit this chain out (per-layer launches) get M = 0: no row tile of theirs exists in the launch
+    for (int k = 0; k < GROUP_MAX; ++k) { a.M[k] = 0; a.st[k] = nullptr; }
+    a.H = (int)g->m.size();
+    for (int i : idx) {
+      acez_trainer* tr = g->m[i];
+      a.st[i] = st[i]; a.M[i] = n[i]; a.variant[i] = tr->R[0] == g->in0[i] ? 0 : 1;
+      a.mtiles = std::max(a.mtiles, (n[i] + 79) / 80);
+      for (int mt = 0; mt < 64; ++mt) a.base[i][mt] = tr->seq_base[mt];
+      if (cnt > 1 && tr->seq_launches == tr->seq_fault_at)   // tests (ACEZ_SEQ_FAULT_AT): as launch_rowseq
+        for (int mt = 0; mt < 64; ++mt) a.base[i][mt] += 1u << 20;
+      ++tr->seq_launches;
+    }
+    const dim3 grid(32 * ((a.mtiles + 7) / 8));
+    if (f16) hipLaunchKernelGGL((rowseq_group_kernel<BWD, EltF16>), grid, dim3(512), 0, s, a);
+    else hipLaunchKernelGGL((rowseq_group_kernel<BWD, EltBf16>), grid, dim3(512), 0, s, a);
+    for (int i : idx) {
+      acez_trainer* tr = g->m[i];
+      for (int mt = 0; mt < (n[i] + 79) / 80; ++mt) tr->seq_base[mt] += (uint32_t)(cnt - 1);
+    }
+  }
+}
+
+extern "C" int acez_train_group_step(acez_train_group* g, const int64_t* const* d_indices, const int32_t* n, const int64_t* const* d_next,
+                                     const int32_t* n_next, void* stream) {
+  ACEZ_REQUIRE(g && d_indices && n, "null pointer");
+  const int H = (int)g->m.size();
+  // every argument is checked before anything is launched: a refused step changes no member
+  for (int i = 0; i < H; ++i) {
+    const acez_trainer* tr = g->m[i];
+    ACEZ_REQUIRE(d_indices[i], "null indices");
+    ACEZ_REQUIRE(tr->have_buf, "acez_trainer_set_buffer has not been called on a member");
+    ACEZ_REQUIRE(n[i] > 0 && n[i] <= tr->max_batch, "n must be in [1, max_batch]");
+    const int nn = (d_next && d_next[i] && n_next) ? n_next[i] : 0;
+    ACEZ_REQUIRE(nn >= 0 && nn <= tr->max_batch, "n_next must be in [0, max_batch]");
+  }
+  ACEZ_HIP_CHECK(hipSetDevice(g->m[0]->device));
+  hipStream_t s = (hipStream_t)stream;
+  const TrainState* st[GROUP_MAX];
+  int nblk[GROUP_MAX];
+  const int64_t* nx[GROUP_MAX];
+  int nn[GROUP_MAX];
+  std::vector<int> chained;   // members whose chains can run as one-launch chains (seq_usable); the others take per-layer launches
+  for (int i = 0; i < H; ++i) {
+    acez_trainer* tr = g->m[i];
+    nx[i] = (d_next && d_next[i] && n_next) ? d_next[i] : nullptr;
+    nn[i] = nx[i] ? n_next[i] : 0;
+    nblk[i] = (n[i] + 4 * tr->loss_rows - 1) / (4 * tr->loss_rows);
+    tr->last_n = n[i];
+    begin_batch(tr, d_indices[i], n[i], s);
+    st[i] = tr->st;
+    if (seq_usable(tr, n[i])) chained.push_back(i);
+  }
+  // forward chains
+  if (!chained.empty()) launch_rowseq_group<false>(g, chained, n, st, s);
+  for (int i = 0; i < H; ++i)
+    if (!seq_usable(g->m[i], n[i])) launch_forward(g->m[i], g->m[i]->R[0], n[i], st[i], s);
+  const int f2 = 3 * (g->m[0]->nb + 1) + 1;
+  for (int i = 0; i < H; ++i) launch_train_loss(g->m[i], g->m[i]->out[f2], d_indices[i], n[i], nblk[i], s, true, nx[i], nn[i], false);
+  // input-gradient chains
+  if (!chained.empty()) launch_rowseq_group<true>(g, chained, n, st, s);
+  for (int i = 0; i < H; ++i)
+    if (!seq_usable(g->m[i], n[i])) launch_dgrad(g->m[i], n[i], st[i], s);
+  // weight gradients + optimiser + schedule: each member's own launches (acez_train_step_next's tail)
+  for (int i = 0; i < H; ++i) {
+    acez_trainer* tr = g->m[i];
+    launch_weight_grads(tr, n[i], nblk[i], st[i], s, true);
+    ACEZ_HIP_CHECK(hipGetLastError());
+    const int rc = train_update_impl(tr, stream, true, 0, -1, nx[i], nn[i]);
+    if (rc != ACEZ_OK) return rc;
+  }
+  return ACEZ_OK;
+}

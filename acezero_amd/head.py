@@ -412,3 +412,63 @@ class HeadTrainer:
         out = torch.empty(f.shape[0], 3, dtype=torch.float32, device=self.device)
         N.check(self.lib.acez_head_forward(self._h, _ptr(f), int(f.shape[0]), _ptr(out), _stream()))
         return out
+
+
+class HeadGroup:
+    """Up to 8 HeadTrainers stepped together (acez_train_group_*): step() advances every member by one training step, bitwise what
+    HeadTrainer.step on each of them would do, with the GEMM chains of all members in one launch each. The members stay ordinary
+    HeadTrainers -- state(), log(), state_dict(), current_poses() and their own step() work as before, in any order with group steps --
+    and must not be closed while the group is open."""
+
+    def __init__(self, trainers):
+        self.trainers = list(trainers)
+        if not self.trainers:
+            raise ValueError("a group needs at least one trainer")
+        self.lib = self.trainers[0].lib
+        if any(t.lib is not self.lib for t in self.trainers):
+            raise ValueError("group members must come from one build of the library")
+        h = len(self.trainers)
+        members = (C.c_void_p * h)(*[t._h.value for t in self.trainers])
+        g = C.c_void_p()
+        N.check(self.lib.acez_train_group_create(C.byref(g), members, h))
+        self._g = g
+
+    def __len__(self):
+        return len(self.trainers)
+
+    def step(self, indices_list, next_indices_list=None):
+        """indices_list[i]: int64 CUDA tensor of member i's buffer rows; next_indices_list[i] (optional, entries may be None): the batch of
+        member i's FOLLOWING step, gathered ahead as in HeadTrainer.step -- pass the very same tensor to that call."""
+        h = len(self.trainers)
+        if len(indices_list) != h or (next_indices_list is not None and len(next_indices_list) != h):
+            raise ValueError(f"one batch per member ({h})")
+        for x in indices_list:
+            assert x.dtype == torch.int64 and x.is_cuda and x.is_contiguous()
+        idx = (C.c_void_p * h)(*[x.data_ptr() for x in indices_list])
+        n = (C.c_int32 * h)(*[int(x.numel()) for x in indices_list])
+        nxt = nn = None
+        if next_indices_list is not None:
+            for t, x in zip(self.trainers, next_indices_list):
+                if x is not None:
+                    assert x.dtype == torch.int64 and x.is_cuda and x.is_contiguous()
+                    t._next_keepalive = x     # the device pointer must stay valid until the member's next step has consumed it
+            nxt = (C.c_void_p * h)(*[x.data_ptr() if x is not None else None for x in next_indices_list])
+            nn = (C.c_int32 * h)(*[int(x.numel()) if x is not None else 0 for x in next_indices_list])
+        N.check(self.lib.acez_train_group_step(self._g, idx, n, nxt, nn, _stream()))
+
+    def close(self):
+        if getattr(self, "_g", None):
+            self.lib.acez_train_group_destroy(self._g)
+            self._g = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

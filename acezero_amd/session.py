@@ -33,13 +33,26 @@ from . import dsacstar
 from .encoder import Encoder, output_size
 import torch.distributed as dist
 
-from .head import HeadTrainer, _ptr, _stream, epoch_batches, epoch_permutations
+from .head import HeadGroup, HeadTrainer, _ptr, _stream, epoch_batches, epoch_permutations
 from .parallel import epoch_local_batches, gather_registrations, make_data_parallel, rank_world
 
 _logger = logging.getLogger("acezero_amd.session")
 
 
 MAX_SCENE_COORDINATES = 16384   # per frame: the DSAC* kernel's inlier word (ransac_api.hip MAX_ROWS x 256 threads)
+
+
+SEED_GROUP_MAX = 8   # members of one HeadGroup (acez_train_group_create)
+
+
+def seed_groups(n_seeds, workers):
+    """The seed trials of a rank in training groups (ace_zero.py --seed_parallel_workers; the reference's joblib n_jobs): consecutive
+    seed indices, groups of `workers` (-1: all of them), at most SEED_GROUP_MAX per group. 1 is the one-after-the-other flow."""
+    workers = int(workers)
+    if workers == 0 or workers < -1:
+        raise ValueError(f"seed_parallel_workers must be -1 (all seeds together) or a positive number, not {workers}")
+    size = SEED_GROUP_MAX if workers == -1 else min(workers, SEED_GROUP_MAX)
+    return [list(range(k, min(n_seeds, k + size))) for k in range(0, int(n_seeds), size)]
 
 
 def check_frame_size(h, w):
@@ -399,6 +412,19 @@ class ReconstructionSession:
                             with_depth=with_depth, tag=tag, data_parallel=False) if self.rank == src else None]
             dist.broadcast_object_list(box, src=dist.get_global_rank(self.group, src) if self.group is not None else src, group=self.group)
             return box[0]
+        job = self._map_prepare(image_ids, poses_c2w, focal, iterations=iterations, loss_type=loss_type, schedule=schedule, lr_max=lr_max,
+                                refinement=refinement, pose_wait=pose_wait, refine_calibration=refine_calibration, load_weights=load_weights,
+                                with_depth=with_depth, tag=tag, data_parallel=data_parallel, t0=t0)
+        self._map_loop(job)
+        return self._map_result(job)
+
+    def _map_prepare(self, image_ids, poses_c2w, focal, *, iterations, loss_type, schedule, lr_max, refinement="none", pose_wait=0,
+                     refine_calibration=False, load_weights=None, with_depth=False, tag="map", data_parallel=None, t0=None):
+        """First part of map(): the training buffer and the trainer, ready to step. Returns the job map()'s other two parts work on."""
+        o = self.opt
+        t0 = time.time() if t0 is None else t0
+        image_ids = [int(i) for i in image_ids]
+        m = len(image_ids)
         poses_c2w = torch.as_tensor(poses_c2w, dtype=torch.float32).reshape(-1, 4, 4)
         dp = (self.world > 1 and m >= self.world) if data_parallel is None else bool(data_parallel and self.world > 1)
         fill = self._fill_buffer_augmented if o.use_aug else self._fill_buffer
@@ -454,11 +480,18 @@ class ReconstructionSession:
             tr.load_flat((torch.rand(tr.n_params, generator=g) * 2 - 1) / math.sqrt(512.0))
         tr.set_buffer(**buf)
         torch.cuda.synchronize(self.dev)
-        t_loop0 = time.time()
+        return SimpleNamespace(tr=tr, n=n, n_local=n_local, shard_lo=shard_lo, dp=dp, m=m, focal=focal, refine_calibration=refine_calibration,
+                               tag=tag, t0=t0, t_fill=t_fill, t_loop0=None, t_loop=None, dpt=None)
+
+    def _map_loop(self, job):
+        """Second part of map(): the training loop of one trainer."""
+        o, tr, n, dp = self.opt, job.tr, job.n, job.dp
+        shard_lo, n_local = job.shard_lo, job.n_local
+        job.t_loop0 = time.time()
         launched, done = 0, False
         perms = epoch_permutations(n, o.base_seed + 8191, self.dev) if dp else None       # ace_trainer.py:79-80 seed of the training generator
         pairs = None if dp else epoch_batches(n, o.batch_size, o.base_seed + 8191, self.dev)  # (rows, next rows): the next batch is gathered ahead
-        dpt = make_data_parallel(tr, self.group) if dp else None          # one all-reduce of the gradient bucket per step (parallel.py)
+        job.dpt = dpt = make_data_parallel(tr, self.group) if dp else None          # one all-reduce of the gradient bucket per step (parallel.py)
         while not done:                                                  # TrainerACE.train / run_epoch (ace_trainer.py:454-497)
             if dp:
                 perm = next(perms)
@@ -479,11 +512,39 @@ class ReconstructionSession:
                     if st["iteration"] >= st["max_iterations"]:
                         done = True
                         break
+
+    def _map_loop_group(self, jobs):
+        """_map_loop for several single-GPU jobs trained side by side (HeadGroup): every member walks its own epoch_batches stream, one
+        group step advances each by one step, the state is read every 64 group steps and the loop ends when every member has finished.
+        A group step is bitwise the members' own steps, so every job ends exactly where _map_loop would have left it."""
+        o = self.opt
+        t_loop0 = time.time()
+        streams = [epoch_batches(j.n, o.batch_size, o.base_seed + 8191, self.dev) for j in jobs]
+        launched = 0
+        with HeadGroup([j.tr for j in jobs]) as grp:
+            while True:
+                pairs = [next(p) for p in streams]
+                grp.step([p[0] for p in pairs], [p[1] for p in pairs])
+                launched += 1
+                if launched % 64 == 0:                                   # the only host synchronisation of the loop
+                    states = [j.tr.state() for j in jobs]
+                    if any(st["nan"] for st in states):
+                        raise RuntimeError("Aborting because of NaN loss")   # ace_trainer.py:615-617
+                    if all(st["iteration"] >= st["max_iterations"] for st in states):
+                        break
+        share = (time.time() - t_loop0) / len(jobs)                     # (the loop's wall-clock, split evenly for the timings)
+        for j in jobs:
+            j.t_loop0, j.t_loop = t_loop0, share
+
+    def _map_result(self, job):
+        """Third part of map(): the result dict (the trainer is closed)."""
+        o, tr, n, dp, dpt, m, focal, tag = self.opt, job.tr, job.n, job.dp, job.dpt, job.m, job.focal, job.tag
+        refine_calibration, t0, t_fill, t_loop0 = job.refine_calibration, job.t0, job.t_fill, job.t_loop0
         st = tr.state()
         if dpt is not None:
             dpt.gather_masters()                                         # the fp32 masters of the other ranks' layers, for the checkpoint
         dt = time.time() - t0
-        t_loop = time.time() - t_loop0
+        t_loop = time.time() - t_loop0 if job.t_loop is None else job.t_loop
         self.timings["buffer_s"] += t_fill
         self.timings["loop_s"] += t_loop
         out = {"head": {k: v.detach().cpu().half() for k, v in tr.state_dict().items()},      # save_model (ace_trainer.py:681-694)
@@ -558,8 +619,8 @@ class ReconstructionSession:
         return poses, inl
 
     # --------------------------------------------------------------------------------------------------- the loop (ace_zero.py)
-    def map_seed(self, seed_idx, seed):
-        """ace_zero_util.map_seed: one image, identity pose, depth-supervised, scored on (at most) 1000 frames."""
+    def _seed_map_args(self, seed_idx, seed):
+        """map() arguments of a seed trial (ace_zero_util.map_seed): one image, identity pose, depth-supervised."""
         o = self.opt
         img = int(seed * self.n)                                         # dataset.py:112
         if self.depth is None:
@@ -567,17 +628,47 @@ class ReconstructionSession:
         rows = self.opt.max_dataset_passes * self.opt.samples_per_image
         if rows < self.opt.batch_size:                                   # one image gives passes x samples rows (10 240 by default = two batches)
             raise ValueError(f"a seed image yields {rows} buffer rows, fewer than one batch of {self.opt.batch_size}: raise --max_dataset_passes")
-        return self.map([img], torch.eye(4).unsqueeze(0), self.focal0, iterations=o.seed_iterations, loss_type=o.repro_loss_type,
-                        schedule=o.learning_rate_schedule, lr_max=o.learning_rate_max, with_depth=True, tag=f"iteration0_seed{seed_idx}",
-                        data_parallel=False)
+        return ([img], torch.eye(4).unsqueeze(0), self.focal0), dict(iterations=o.seed_iterations, loss_type=o.repro_loss_type,
+                                                                    schedule=o.learning_rate_schedule, lr_max=o.learning_rate_max, with_depth=True,
+                                                                    tag=f"iteration0_seed{seed_idx}", data_parallel=False)
+
+    def map_seed(self, seed_idx, seed):
+        """ace_zero_util.map_seed: one image, identity pose, depth-supervised, scored on (at most) 1000 frames."""
+        args, kw = self._seed_map_args(seed_idx, seed)
+        return self.map(*args, **kw)
+
+    def map_seeds(self, seed_idx, seeds):
+        """map_seed for several seed trials trained side by side (ace_zero.py --seed_parallel_workers): the buffers are filled in seed order
+        (the augmentation / sampling streams advance exactly as in the one-after-the-other flow), the trainers step as one HeadGroup, the
+        results come back in seed order -- identical to map_seed on each seed in turn, timings aside."""
+        if len(seed_idx) == 1:
+            return [self.map_seed(seed_idx[0], seeds[0])]
+        jobs = []
+        for i, sd_ in zip(seed_idx, seeds):
+            args, kw = self._seed_map_args(i, sd_)
+            jobs.append(self._map_prepare(*args, **kw))
+        self._map_loop_group(jobs)
+        return [self._map_result(j) for j in jobs]
+
+    def run_seed_trials(self, seed_idx, seeds, workers=1):
+        """Map the given seed trials in groups of `workers` (seed_groups; seed order) and score each: [(map result, rate)] in seed order,
+        the same for every `workers`."""
+        trials = []
+        for grp in seed_groups(len(seed_idx), workers):
+            maps = self.map_seeds([seed_idx[k] for k in grp], [seeds[k] for k in grp])
+            trials += [(mp_, self.score_seed(seed_idx[k], mp_)) for k, mp_ in zip(grp, maps)]
+        return trials
 
     def score_seed(self, seed_idx, m):
         _, inl = self.register(m["head"], self.focal0, max_estimates=self.opt.max_estimates_seed_scoring, tag=f"iteration0_seed{seed_idx}_fastcheck")
         return float((inl > self.opt.registration_confidence).mean())
 
-    def reconstruct(self):
+    def reconstruct(self, seed_parallel_workers=1):
+        """ace_zero.py's loop. seed_parallel_workers: seed trials trained side by side per group (seed_groups; ace_zero.py
+        --seed_parallel_workers); 1 maps and scores the seeds one after the other. The result is the same for every value."""
         o = self.opt
         t_start = time.time()
+        seed_groups(o.try_seeds, seed_parallel_workers)                  # a bad --seed_parallel_workers fails before any work
         focal = self.focal0
         if o.seed_network is not None:                                   # ace_zero.py:176-178: a pre-trained head (state_dict) as the seed
             current, first_id, seed_rates = {"head": o.seed_network}, "seed_network", []
@@ -585,16 +676,19 @@ class ReconstructionSession:
             np.random.seed(o.random_seed)                                # ace_zero.py:181-183
             seeds = np.random.uniform(size=o.try_seeds)
             if self.world == 1:
-                trials = []
-                for i, sd_ in enumerate(seeds):                          # ace_zero.py:185-215: map, then score, seed after seed
-                    mp_ = self.map_seed(i, sd_)
-                    trials.append((mp_, self.score_seed(i, mp_)))
+                # ace_zero.py:185-215: map, then score; seed_parallel_workers seeds at a time train side by side (one HeadGroup)
+                trials = self.run_seed_trials(list(range(len(seeds))), list(seeds), seed_parallel_workers)
             else:
                 # a seed trial maps ONE image (nothing to shard): trial i runs on rank i % world, side by side with the others; its
                 # head is then handed to every rank and scored by all of them together (sharded registration)
                 # (without augmentation the buffer is filled from the cached feature maps, which only the frame's owner holds)
                 runner = [(i if o.use_aug else int(sd_ * self.n)) % self.world for i, sd_ in enumerate(seeds)]
-                maps = [self.map_seed(i, sd_) if runner[i] == self.rank else None for i, sd_ in enumerate(seeds)]
+                # (the trials a rank owns are grouped like a single process's)
+                mine = [i for i in range(len(seeds)) if runner[i] == self.rank]
+                maps = [None] * len(seeds)
+                for grp in seed_groups(len(mine), seed_parallel_workers):
+                    for i, mp_ in zip([mine[k] for k in grp], self.map_seeds([mine[k] for k in grp], [seeds[mine[k]] for k in grp])):
+                        maps[i] = mp_
                 for i in range(len(maps)):
                     box = [maps[i]]
                     dist.broadcast_object_list(box, src=dist.get_global_rank(self.group, runner[i]) if self.group is not None else runner[i],

@@ -289,6 +289,24 @@ int acez_train_step(acez_trainer* tr, const int64_t* d_indices, int n, void* str
  * not be rewritten, nor their memory freed and reused, between this call and the next step call -- acez_trainer_set_buffer and
  * acez_trainer_sync_weights drop the rows gathered ahead. NULL = acez_train_step. */
 int acez_train_step_next(acez_trainer* tr, const int64_t* d_indices, int n, const int64_t* d_indices_next, int n_next, void* stream);
+
+/* Training group: h (1..8) independent trainers stepped together (ace_zero.py --seed_parallel_workers: the seed trials side by side).
+ * One acez_train_group_step advances every member by exactly one step, bitwise what acez_train_step (or acez_train_step_next with the
+ * same announcement) on each member, one after the other, produces; single steps and group steps may be mixed in any order. The two
+ * dependent GEMM chains of all members run as one launch each (rowseq_group_kernel: layer l of every member before layer l + 1); every
+ * other launch is the member's own. Each member keeps its weights, optimiser and schedule state, buffer and loss settings; state, log and
+ * diagnostics are read from the members as before. Members must outlive the group.
+ * acez_train_group_create returns ACEZ_ERR_INVALID (and creates nothing) for: h outside [1, 8], a member listed twice, members on
+ * different devices or with different compute_dtype / num_head_blocks / use_homogeneous, a member with pose_refinement,
+ * refine_calibration or inference_only.
+ * acez_train_group_step: d_indices[i] / n[i] as acez_train_step for member i; d_next[i] / n_next[i] as acez_train_step_next (d_next ==
+ * NULL or d_next[i] == NULL: no announcement for that member). Arguments are checked before anything is launched. */
+typedef struct acez_train_group acez_train_group;
+int acez_train_group_create(acez_train_group** out, acez_trainer* const* members, int h);
+void acez_train_group_destroy(acez_train_group* g);
+int acez_train_group_step(acez_train_group* g, const int64_t* const* d_indices, const int32_t* n, const int64_t* const* d_next,
+                          const int32_t* n_next, void* stream);
+
 /* Synchronises `stream` and copies the schedule state. */
 int acez_trainer_get_state(acez_trainer* tr, acez_train_state* h_out, void* stream);
 /* Per-iteration log kept on the device: loss and batch_inliers of iterations [first, first+count). */
