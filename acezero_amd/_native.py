@@ -65,6 +65,13 @@ class TrainState(C.Structure):
                 ("grad_scale", C.c_float), ("opt_steps", C.c_int32)]
 
 
+class AlignParams(C.Structure):
+    _fields_ = [("threshold_t", C.c_double), ("threshold_r", C.c_double), ("confidence_threshold", C.c_double),
+                ("estimate_alignment", C.c_int32), ("estimate_scale", C.c_int32), ("min_confident_estimates", C.c_int32),
+                ("ransac_iterations", C.c_int32), ("refinement_max_hyp", C.c_int32), ("refinement_max_it", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
 # every symbol include/acez.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "acez_last_error": (C.c_char_p, []),
@@ -119,6 +126,11 @@ SYMBOLS = {
     "acez_point_cloud_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                           C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "acez_align_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
+    "acez_align_destroy": (None, [C.c_void_p]),
+    "acez_align_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(AlignParams), C.c_void_p,
+                                      C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.POINTER(C.c_int32)]),
 }
 
 

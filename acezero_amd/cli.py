@@ -361,19 +361,24 @@ def train_with_options(opt):
     return 0
 
 
+def quat_wxyz_to_matrix(q_wxyz):
+    """Rotation matrix of a pose file's (qw, qx, qy, qz) (dataset_io.py:130-134, eval_poses.py:77)."""
+    from scipy.spatial.transform import Rotation
+    q = list(q_wxyz)
+    return Rotation.from_quat(q[1:] + [q[0]]).as_matrix()
+
+
 def read_ace_pose_file(path, confidence_threshold):
     """dataset_io.load_dataset_ace (:96-156): (files, cam->world 4x4 float64 [k,4,4], focal lengths) of the entries whose confidence
     is not below the threshold."""
-    from scipy.spatial.transform import Rotation
     files, poses, focals = [], [], []
     for line in open(path).read().splitlines():
         tok = line.split()
         assert len(tok) == 10, f"Expected 10 tokens per line in pose file, got {len(tok)}"
         if float(tok[-1]) < confidence_threshold:
             continue
-        q = [float(t) for t in tok[1:5]]
         T = np.eye(4)
-        T[:3, :3] = Rotation.from_quat(q[1:] + [q[0]]).as_matrix()
+        T[:3, :3] = quat_wxyz_to_matrix([float(t) for t in tok[1:5]])
         T[:3, 3] = [float(t) for t in tok[5:8]]
         files.append(tok[0]); poses.append(np.linalg.inv(T)); focals.append(float(tok[-2]))
     return files, np.stack(poses) if poses else np.zeros((0, 4, 4)), focals
@@ -713,4 +718,60 @@ def export_point_cloud_main(argv=None):
         clr = source_colours(rgb, sel[f], p, ses.ow)
     write_point_cloud(opt.output_file, xyz, clr)
     _logger.info(f"Done. Wrote point cloud to: {opt.output_file}")
+    return 0
+
+
+# ------------------------------------------------------------------------------------------------------------ eval_poses
+def eval_parser():
+    """eval_poses.py:28-54: the same positional arguments, flags, defaults and help."""
+    from .evaluate import DEFAULT_SEED
+    p = argparse.ArgumentParser(description='Compute pose error metrics for an ACE pose file using (pseudo) ground truth pose files.',
+                                formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument('ace_pose_file', type=Path, help='Path to an ACE pose file with one line per image.')
+    p.add_argument('gt_pose_files', type=str,
+                   help="Glob pattern for pose files, e.g. 'datasets/scene/*.txt', each file is assumed to "
+                        "contain a 4x4 pose matrix, cam2world, correspondence with rgb files in the ACE pose "
+                        "file is assumed by alphabetical order")
+    p.add_argument('--estimate_alignment', type=_strtobool, default=True,
+                   help='Estimate rigid body transformation between estimates and ground truth.')
+    p.add_argument('--estimate_alignment_scale', type=_strtobool, default=True,
+                   help='Estimate similarity transformation when estimating alignment')
+    p.add_argument('--estimate_alignment_conf_threshold', type=float, default=500,
+                   help='Only consider pose estimates with higher confidence when estimates the alignment.')
+    p.add_argument('--pose_error_thresh_t', type=float, default=0.05, help='Pose threshold (translation) for evaluation and alignment')
+    p.add_argument('--pose_error_thresh_r', type=float, default=5, help='Pose threshold (rotation) for evaluation and alignment')
+    p.add_argument('--seed', type=int, default=DEFAULT_SEED,
+                   help="[additive] key of the device's counter-based stream of RANSAC samples (the reference uses Python's random)")
+    return p
+
+
+def eval_poses_main(argv=None):
+    """eval_poses.py: read the ACE pose file (every line) and the GT pose files, align, log per-frame errors, accuracy and medians."""
+    from .evaluate import evaluate_poses, load_gt_pose_files, log_lines, read_pose_file_with_confidence
+    logging.basicConfig(level=logging.INFO)
+    opt = eval_parser().parse_args(argv)
+    log = logging.getLogger("eval_poses")
+    log.info("Reading ACE pose file.")
+    ace_estimates = read_pose_file_with_confidence(opt.ace_pose_file)
+    log.info(f"Read {len(ace_estimates)} poses from: {opt.ace_pose_file}")
+    sorted_ace_poses = [ace_estimates[key] for key in sorted(ace_estimates.keys())]
+    sorted_gt_poses = load_gt_pose_files(opt.gt_pose_files)
+    log.info(f"Loaded {len(sorted_gt_poses)} ground truth poses.")
+    pairs = list(zip(sorted_ace_poses, sorted_gt_poses))            # zip semantics: the shorter list decides
+    if not pairs:
+        raise SystemExit("no (estimate, ground truth) pairs to evaluate")
+    res = evaluate_poses(np.stack([p[0][0] for p in pairs]), np.stack([p[1] for p in pairs]), np.array([p[0][1] for p in pairs]),
+                         estimate_alignment=opt.estimate_alignment, estimate_alignment_scale=opt.estimate_alignment_scale,
+                         estimate_alignment_conf_threshold=opt.estimate_alignment_conf_threshold, pose_error_thresh_t=opt.pose_error_thresh_t,
+                         pose_error_thresh_r=opt.pose_error_thresh_r, seed=opt.seed)
+    if opt.estimate_alignment and res["T"] is None:
+        log.info(f"Alignment requested but failed. Setting all pose errors to {math.inf}.")
+    for r_err, t_err in zip(res["r_err"], res["t_err"]):
+        log.info(f"Rotation Error: {r_err:.2f}deg, Translation Error: {t_err * 100:.1f}cm")
+    total_frames = len(res["t_err"])
+    assert total_frames == len(ace_estimates)
+    log.info("===================================================")
+    log.info("Test complete.")
+    for line in log_lines(res):
+        log.info(line)
     return 0

@@ -465,6 +465,45 @@ int acez_point_cloud_filter(const float* d_scene_coords, const float* d_poses_in
                             uint8_t* d_keep, int32_t* d_counts, int32_t* d_offsets, float* d_out_xyz, int32_t* d_out_source,
                             void* stream);
 
+/* =====================================================================================================
+ * G. Pose evaluation against ground truth (eval_poses.py, eval_poses_util.py of the reference)
+ * =====================================================================================================
+ * estimate_alignment (eval_poses_util.py:70-180) and the per-frame errors of eval_poses.py:140-170 in fp64 on the device:
+ * RANSAC over similarity transforms fitted to three camera centres (Kabsch, eval_poses_util.py:20-45), the inlier test of
+ * get_inliers (translation in the aligned frame AND rotation angle), stable top-k shortlist, refinement on the inlier sets,
+ * then t_err = |(T G).t - E.t| / scale and r_err = angle(R_est (T G)_R^T) in degrees for every frame.  Host pointers in and
+ * out; one synchronisation per call.  DESIGN.md section 4d lists the declared deviations from the reference.
+ * Without a device acez_align_create returns ACEZ_ERR_NODEVICE; there is no CPU path. */
+typedef struct acez_align acez_align;
+
+typedef struct {
+  double threshold_t;              /* metres: inlier test and accuracy (--pose_error_thresh_t, 0.05)            */
+  double threshold_r;              /* degrees: inlier test and accuracy (--pose_error_thresh_r, 5)             */
+  double confidence_threshold;     /* frames with confidence strictly above it (and finite GT) take part        */
+  int32_t estimate_alignment;      /* 0: T = I, scale = 1 (--estimate_alignment False)                         */
+  int32_t estimate_scale;          /* similarity (1) or rigid (0) Kabsch                                        */
+  int32_t min_confident_estimates; /* fewer confident frames: status "failed" (10)                             */
+  int32_t ransac_iterations;       /* hypotheses H, <= max_hyp (10000)                                          */
+  int32_t refinement_max_hyp;      /* shortlist length, 1..64 (12)                                              */
+  int32_t refinement_max_it;       /* refinement iterations per shortlisted hypothesis (8)                     */
+  uint64_t seed;                   /* key of the counter-based sample stream (unused with a sample table)       */
+} acez_align_params;
+
+int acez_align_create(acez_align** out, int max_frames, int max_hyp, int device);
+void acez_align_destroy(acez_align* ctx);
+
+/* gt_c2w, est_c2w  double [n_frames][4][4] cam -> world; confidence double [n_frames]
+ * samples          int32 [ransac_iterations][3] indices into the confident frames (in frame order), or NULL: own stream
+ * out_T            double [16] row-major alignment (zeros if failed); out_scale (1 if failed); out_status 0 ok, 1 failed
+ * out_scores       int32 [ransac_iterations] inlier count per hypothesis, out_valid int32 [same] 1 if its sample passed
+ *                  the sample test; both optional (NULL), all zero when RANSAC did not run
+ * out_t_err        double [n_frames] metres; out_r_err double [n_frames] degrees (inf if failed, NaN for non-finite GT)
+ * out_accurate     frames with r_err < threshold_r and t_err < threshold_t */
+int acez_align_evaluate(acez_align* ctx, const double* gt_c2w, const double* est_c2w, const double* confidence, int n_frames,
+                        const acez_align_params* params, const int32_t* samples, double* out_T, double* out_scale,
+                        int32_t* out_status, int32_t* out_scores, int32_t* out_valid, double* out_t_err, double* out_r_err,
+                        int32_t* out_accurate);
+
 #ifdef __cplusplus
 }
 #endif
