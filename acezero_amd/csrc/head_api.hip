@@ -14,6 +14,24 @@
 
 using namespace acez;
 
+// What a training step leaves for the next one. A step's schedule wave (sched_post_wave: the bookkeeping that closes it, reading one
+// TrainState slot and writing the other) and the gather of the next batch can ride in several launches; the host keeps their outcome here.
+// Invariants (kept by plan_step, begin_step, close_step, flush_post and wave_ran below):
+//  - exactly one launch runs each step's schedule wave -- wgrad_opt_kernel's epilogue, adamw_next_kernel, or, while wave_pending, the
+//    next step's begin launch (step_begin / step_begin_pose) or flush_post -- and it is enqueued before anything reads the next slot;
+//  - the host flips to the slot a wave writes (wave_ran) exactly once per wave, right behind the launch that carries it;
+//  - a step gathers its own batch unless the record names exactly that batch (pointer and count) in R[0];
+//  - every read of the schedule state or the log flushes a pending wave (flush_post);
+//  - whatever makes a batch gathered ahead unusable (another patch buffer, a restart point, a fault that held the gathers back) calls drop_batch.
+struct StepCarry {
+  bool wave_pending = false;       // the wave of the last step has not run yet
+  const int64_t* idx = nullptr;    // the batch gathered ahead for the next step (null: none), and its row count
+  int n = 0;
+  bool in_alt = false;             // it sits in R0_alt / batch_meta_alt (gathered beside the loss kernel), swapped in when the step closes
+  void hold(const int64_t* i, int k, bool alt) { idx = i; n = k; in_alt = alt; }
+  void drop_batch() { hold(nullptr, 0, false); }
+};
+
 struct acez_trainer {
   char* arena_base = nullptr;   // current arena of dmalloc (all arenas are in `allocs`)
   size_t arena_size = 0, arena_cursor = 0;
@@ -55,10 +73,7 @@ struct acez_trainer {
   hipStream_t pose_stream = nullptr;
   hipEvent_t ev_begin = nullptr, ev_pose_fwd = nullptr, ev_loss = nullptr, ev_pose_bwd = nullptr;
   GradReduceArgs last_reduce{};   // partial buffers of the last backward (input of the fused update)
-  bool post_pending = false;   // acez_train_update has run; its schedule bookkeeping rides with the next step's gather (flush_post)
-  // acez_train_step_next: the batch of the NEXT step was gathered (and this step's bookkeeping done) inside the optimiser's launch
-  const int64_t* pre_idx = nullptr;
-  int pre_n = 0;
+  StepCarry carry;
   SchedConfig sc;
   std::vector<void*> allocs;
   // pose refinement (mlp): per-image activations and gradients, allocated by set_buffer (needs n_images)
@@ -68,9 +83,8 @@ struct acez_trainer {
   float* pose_wt = nullptr;     // [4][128][128] transposed pose-network weights (forward)
   // mlp refinement folded into the step's own launches (pose_fused.hip); ACEZ_POSE_FUSED=0 = the separate launches of round 2
   bool pose_fused = true;
-  // images per pose workgroup of the fused path: 16 (pose_kernels.hip), 8 or 4 (pose_small.hip); ACEZ_POSE_TILE sets both, ACEZ_POSE_TILE_FWD
-  // the forward alone (the global layouts do not depend on the tile size)
-  int pose_tile = 4, pose_tile_fwd = 4;
+  // images per pose workgroup of the fused path: 4 (pose_small.hip); ACEZ_POSE_TILE=16 (diagnostics build): pose_kernels.hip's tiles
+  int pose_tile = 4;
   bool pose_wt_valid = false;   // pose_wt matches the parameters (kept up to date by the fused optimiser epilogue of pose_mlp_wgrad_kernel)
   float* row_dT = nullptr;
   int* row_image = nullptr;
@@ -87,7 +101,6 @@ struct acez_trainer {
   // 16-bit operand format of the GEMM chains (acez_train_config.compute_dtype): bf16, or fp16 with the gradient chain scaled by
   // grad_scale (fp16's smallest normal is 6e-5; the reference uses a GradScaler for the same reason, ace_schedule.py:70,107-113)
   bool f16 = false;
-  int loss_rows = 4;   // rows per wavefront of loss_kernel (4 waves per workgroup): 4 = 16-row workgroups; ACEZ_LOSS_ROWS=8 (diagnostics build): 8
   int last_nblk = 0;   // loss workgroups of the last backward (the schedule wave scans their |ds| maxima in fp16 mode)
   int n_cus = 0;
   uint32_t* seq_flags = nullptr;  // [64 row tiles][32] hand-off counters, monotonically increasing
@@ -109,15 +122,10 @@ struct acez_trainer {
   float* wg_xch = nullptr;        // [L * 16 tiles][2][64][128] fp32 exchange tiles
   uint32_t* wg_flags = nullptr;   // [L * 16 tiles][2][32] hand-off counters
   uint32_t wg_epoch = 0;          // wgrad_opt launches so far (a counter reaches 2 * epoch in each of them)
-  bool wide_done = false;         // this step's backward has already applied the optimiser to the wide layers' weights AND the small parameters
-  bool post_done = false;         // ... and run the schedule wave that closes the step (no pose refinement)
-  // acez_train_step_next on this path: the next batch is gathered beside the loss kernel (loss_gather_kernel) into the OTHER input
-  // buffer / metadata table (the weight-gradient launch of the running step still reads the current ones); swapped when the step ends
+  // the next batch gathered beside the loss kernel (loss_gather_kernel) goes to the OTHER input buffer / metadata table (the weight-
+  // gradient launch of the running step still reads the current ones); swapped when the step closes (StepCarry::in_alt)
   uint16_t* R0_alt = nullptr;
   int4* batch_meta_alt = nullptr;
-  bool next_gathered = false;
-  const int64_t* next_idx = nullptr;
-  int next_n = 0;
   long wgo_fault_at = -1;         // tests: ACEZ_WGO_FAULT_AT=<n> makes the n-th wgrad_opt launch time out
   int wgo_fault_mod = 0;          // tests: ACEZ_WGO_FAULT_MOD=<m>: ... only in the workgroups with b % m == 1 (a partially applied step)
   uint32_t* wg_status = nullptr;  // [workgroups][8 loader waves] WgradOptArgs::status
@@ -131,6 +139,17 @@ struct acez_trainer {
 };
 
 enum { KC_SCHED = 0, KC_GATHER, KC_GEMM_FWD, KC_LOSS, KC_GEMM_DGRAD, KC_WGRAD, KC_REDUCE, KC_ADAMW, KC_COUNT };
+
+// loss_kernel's workgroups for n rows (4 waves of 4 rows); the gather's for n rows (4 rows per workgroup and pass, at most 1024)
+static int loss_blocks(int n) { return (n + 15) / 16; }
+static int gather_blocks(int n) { return (n + 3) / 4 < 1024 ? (n + 3) / 4 : 1024; }
+
+// the pose tile (images per workgroup) as a template argument: f(std::integral_constant<int, T>, workgroups for n_images)
+template <class F>
+static void with_pose_tile(const acez_trainer* tr, int n_images, F f) {
+  if (tr->pose_tile == 16) f(std::integral_constant<int, 16>{}, (n_images + 15) / 16);
+  else f(std::integral_constant<int, 4>{}, (n_images + 3) / 4);
+}
 
 struct ProfScope {
   acez_trainer* tr; hipStream_t s; int cls; int i0 = -1;
@@ -261,7 +280,7 @@ static int seq_fault_check(acez_trainer* tr, hipStream_t s) {
   if (hipMemcpyAsync(&err, tr->seq_err, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return 0;
   if (!err) return 0;
   wgo_recover(tr, s);   // (before the fault word comes down: nothing else may run on this trainer's buffers in between)
-  tr->pre_idx = nullptr; tr->pre_n = 0; tr->next_gathered = false;   // batches "gathered ahead" since the fault were held back
+  tr->carry.drop_batch();   // batches "gathered ahead" since the fault were held back
   (void)hipMemsetAsync(tr->seq_flags, 0, (64 * 32 + 1) * sizeof(uint32_t), s);   // counters + fault word (the poll budget behind them stays)
   hipLaunchKernelGGL(sched_reactivate_kernel, dim3(1), dim3(64), 0, s, tr->st);
   const int one = 1;
@@ -309,12 +328,10 @@ extern "C" int acez_trainer_create(acez_trainer** out, const acez_train_config* 
   ACEZ_HIP_CHECK(hipGetDevice(&tr->device));
   tr->cfg = *cfg;
   tr->f16 = cfg->compute_dtype == ACEZ_DTYPE_FP16;
-  if (const char* e = ACEZ_DIAG_ENV("ACEZ_LOSS_ROWS")) tr->loss_rows = (atoi(e) == 8) ? 8 : 4;
   if (const char* e = ACEZ_DIAG_ENV("ACEZ_POSE_FUSED")) tr->pose_fused = atoi(e) != 0;
-  if (const char* e = ACEZ_DIAG_ENV("ACEZ_POSE_TILE")) { const int v = atoi(e); tr->pose_tile = tr->pose_tile_fwd = (v == 4 || v == 16) ? v : 8; }
-  if (const char* e = ACEZ_DIAG_ENV("ACEZ_POSE_TILE_FWD")) { const int v = atoi(e); tr->pose_tile_fwd = (v == 4 || v == 16) ? v : 8; }
+  if (const char* e = ACEZ_DIAG_ENV("ACEZ_POSE_TILE")) tr->pose_tile = atoi(e) == 16 ? 16 : 4;
   if (cfg->pose_refinement != 2) tr->pose_fused = false;
-  if (cfg->pose_refinement != 0 && !tr->pose_fused && !(ACEZ_DIAG_ENV("ACEZ_POSE_STREAM") && atoi(ACEZ_DIAG_ENV("ACEZ_POSE_STREAM")) == 0)) {
+  if (cfg->pose_refinement != 0 && !tr->pose_fused) {
     ACEZ_HIP_CHECK(hipStreamCreateWithFlags(&tr->pose_stream, hipStreamNonBlocking));
     for (hipEvent_t* e : {&tr->ev_begin, &tr->ev_pose_fwd, &tr->ev_loss, &tr->ev_pose_bwd}) ACEZ_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
   }
@@ -356,7 +373,7 @@ extern "C" int acez_trainer_create(acez_trainer** out, const acez_train_config* 
   tr->R.resize(tr->nb + 2, nullptr);
   for (int l = 0; l < tr->L; ++l) { A((void**)&tr->out[l], act_bytes); if (trains) A((void**)&tr->dZ[l], act_bytes); }
   for (int b = 0; b < tr->nb + 2; ++b) A((void**)&tr->R[b], act_bytes);
-  const int max_loss_blocks = (tr->max_batch + 4 * tr->loss_rows - 1) / (4 * tr->loss_rows);
+  const int max_loss_blocks = loss_blocks(tr->max_batch);
   tr->bias_layer_stride = (int64_t)max_loss_blocks * 512;
   if (trains) {
     A((void**)&tr->dR[0], act_bytes);
@@ -445,7 +462,7 @@ extern "C" int acez_trainer_set_buffer(acez_trainer* tr, const acez_train_buffer
   ACEZ_REQUIRE(buf->d_image_pose_inv && buf->n_images > 0, "empty pose table");
   tr->buf = *buf;
   tr->have_buf = true;
-  tr->pre_idx = nullptr; tr->pre_n = 0;   // rows gathered ahead (acez_train_step_next) came from the buffer before
+  tr->carry.drop_batch();   // rows gathered ahead (acez_train_step_next) came from the buffer before
   if (tr->cfg.pose_refinement == 1) {
     ACEZ_REQUIRE(tr->pb.n_pose_params == (int64_t)buf->n_images * 12, "naive pose refinement: n_pose_params != 12 * n_images");
     if (tr->pose_images < buf->n_images) {
@@ -506,7 +523,7 @@ extern "C" int acez_trainer_sync_weights(acez_trainer* tr, void* stream) {
   hipLaunchKernelGGL(recast_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, a);
   ACEZ_HIP_CHECK(hipGetLastError());
   tr->pose_wt_valid = false;   // the caller may have rewritten the pose parameters as well
-  tr->pre_idx = nullptr; tr->pre_n = 0;   // a restart point: the next step gathers its own batch
+  tr->carry.drop_batch();   // a restart point: the next step gathers its own batch
   return ACEZ_OK;
 }
 
@@ -599,13 +616,8 @@ static void fill_loss_head(acez_trainer* tr, LossArgs& a) {
 
 
 static void launch_loss(acez_trainer* tr, int nblk, hipStream_t s, const LossArgs& a) {
-  if (tr->loss_rows == 4) {
-    if (tr->f16) hipLaunchKernelGGL((loss_kernel<EltF16, 4>), dim3(nblk), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((loss_kernel<EltBf16, 4>), dim3(nblk), dim3(256), 0, s, a);
-  } else {
-    if (tr->f16) hipLaunchKernelGGL((loss_kernel<EltF16, 8>), dim3(nblk), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((loss_kernel<EltBf16, 8>), dim3(nblk), dim3(256), 0, s, a);
-  }
+  if (tr->f16) hipLaunchKernelGGL((loss_kernel<EltF16, 4>), dim3(nblk), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((loss_kernel<EltBf16, 4>), dim3(nblk), dim3(256), 0, s, a);
 }
 
 // training-mode arguments of the loss kernel
@@ -689,45 +701,12 @@ static void launch_pose_wgrad(acez_trainer* tr, const int* active, bool fuse, hi
   else hipLaunchKernelGGL((pose_mlp_wgrad_kernel<32, 8>), dim3(jobs), dim3(512), 0, s, w);
 }
 
-static void launch_pose_grad_reduce(acez_trainer* tr, int n, const int* active, hipStream_t s) {
-  const int I = tr->buf.n_images;
-  hipLaunchKernelGGL(pose_grad_reduce2_kernel, dim3((I + 15) / 16), dim3(256), 0, s, (const float*)tr->row_dT, (const int*)tr->row_image, n,
-                     tr->pdT, I, active);
-}
-
-// gradient of the pose network from the per-row pose gradients of the loss kernel -> d_grad tail (4 launches)
-static void pose_backward(acez_trainer* tr, int n, const int* active, hipStream_t s) {
-  const int I = tr->buf.n_images;
-  launch_pose_grad_reduce(tr, n, active, s);
-  const PoseNetArgs a = pose_net_args(tr, active);
-  hipLaunchKernelGGL(pose_mlp_bwd_kernel, dim3((I + PN_IMG - 1) / PN_IMG), dim3(256), 0, s, a);
-  launch_pose_wgrad(tr, active, false, s);
-}
-
-// after a launch that ran the schedule bookkeeping (it wrote the other slot): every later launch reads that slot
-static void st_flip(acez_trainer* tr) {
-  tr->st_cur ^= 1;
-  tr->st = tr->st_slot[tr->st_cur];
-}
-
 static PostArgs post_args(acez_trainer* tr) {
   PostArgs p;
   p.src = tr->st; p.st = tr->st_slot[tr->st_cur ^ 1]; p.c = tr->sc; p.grad_stats = (const float*)(tr->pb.d_grad + tr->n_params);
   p.inv_global_batch = 1.0f / (float)tr->cfg.global_batch; p.log_loss = tr->log_loss; p.log_inl = tr->log_inl; p.log_cap = tr->log_cap;
   p.fault = tr->seq_err; p.stat_partials = tr->stat_partials; p.n_loss_blocks = tr->last_nblk;
   return p;
-}
-
-// The schedule bookkeeping that closes a step (sched_post) is deferred: normally it is executed by an extra workgroup of
-// the next step's gather launch. Every entry point that reads the schedule state or the log flushes it first.
-static void flush_post(acez_trainer* tr, hipStream_t s) {
-  if (!tr->post_pending) return;
-  tr->post_pending = false;
-  ProfScope ps(tr, s, KC_SCHED);
-  const PostArgs p = post_args(tr);
-  hipLaunchKernelGGL(sched_post_kernel, dim3(1), dim3(64), 0, s, p.src, p.st, p.c, p.grad_stats, p.inv_global_batch, p.log_loss, p.log_inl, p.log_cap, p.fault,
-                     p.stat_partials, p.n_loss_blocks);
-  st_flip(tr);
 }
 
 // operands of the weight-gradient launch of a step on n rows (wgrad_kernel / wgrad_opt_kernel; wgo_recover runs it again on a faulted step)
@@ -744,67 +723,131 @@ static void fill_wgrad_args(acez_trainer* tr, WgradArgs& a, int n, const TrainSt
   a.slabs = tr->slabs; a.slab_stride = tr->n_wide; a.M = n; a.nslabs = tr->nslabs; a.n_layers = tr->L; a.st = st; a.zeros = tr->zeros; a.dbg = 0;
 }
 
-// The launch that opens a step: the gather of its batch (unless acez_train_step_next of the step before has gathered it), with the schedule
-// bookkeeping of the previous step and, when the pose network is folded in, its forward. Afterwards tr->st is the slot the step reads.
-static void begin_batch(acez_trainer* tr, const int64_t* d_indices, int n, hipStream_t s) {
-  const bool pf = tr->pose_fused;
-  const TrainState* st = tr->st;
-  // (pose refinement folded into the step's launches: the batch may have been gathered ahead too -- beside the loss kernel of the step
-  // before, round 5 -- but the launch below still runs: the pose network's forward and the schedule wave ride in it, with no gather blocks)
-  const bool pre_ok = tr->pre_idx == d_indices && tr->pre_n == n;
-  const bool pregathered = !pf && pre_ok && !tr->post_pending;
-  tr->pre_idx = nullptr; tr->pre_n = 0;
-  if (pregathered) {
-    // acez_train_step_next of the step before has gathered exactly this batch into R[0] and closed that step's bookkeeping
-  } else {
-  if (pf && !tr->pose_wt_valid) {   // first step / after acez_trainer_sync_weights / after a split (backward + update) step
+// ---- The step protocol: which launch of a step gathers its batch, which gathers the next one, which runs the step's schedule wave
+// (StepCarry's invariants). plan_step decides it for one call; begin_step, close_step and flush_post apply and keep the record.
+
+enum class Flow { Fused, Backward, Update };   // acez_train_step(_next) / acez_train_backward / acez_train_update(_next, _layers)
+// the optimiser's form: wgrad_opt_kernel (inside the weight-gradient launch, with the step's wave), adamw_pose_kernel + pose_mlp_wgrad_kernel
+// (mlp refinement folded in), adamw_next_kernel (+ the next batch's gather and the step's wave), adamw_split_pose_kernel (pose refinement
+// otherwise, + the next batch's gather when folded in), adamw_kernel
+enum class Opt { None, WgradOpt, AdamwPose, AdamwNext, AdamwSplitPose, Adamw };
+enum class NextAt { None, Loss, Optimiser };   // the launch that gathers the announced next batch
+
+struct StepPlan {
+  Flow flow;
+  // the launch that opens the step: made at all (it also carries a pending wave) / gathers the batch / carries the pose network's forward
+  bool begin_launch = false, begin_gathers = false, begin_pose = false;
+  NextAt next_at = NextAt::None;
+  Opt opt = Opt::None;   // (None: the split flow's backward call)
+};
+
+// one trainer's step (or backward call) in flight
+struct StepRun {
+  acez_trainer* tr;
+  StepPlan plan;
+  const int64_t* idx; int n;
+  const int64_t* next; int n_next;   // the announced next batch (none: null or no rows)
+  int nblk;
+  hipStream_t s, ps;     // ps: the stream of the pose launches the step does not carry (beside the head's chains; else = s)
+  const TrainState* st;  // the slot the step reads (known after its begin launch)
+};
+
+// Every choice of one call, from the trainer (its configuration and record) and the batches; the phases read them and derive nothing again.
+// idx / n: the step's own batch (not for an update).
+static StepPlan plan_step(const acez_trainer* tr, Flow flow, const int64_t* idx, int n, const int64_t* next, int n_next) {
+  StepPlan p{flow};
+  const bool pf = tr->pose_fused, announced = next && n_next > 0;
+  if (flow != Flow::Update) {
+    const StepCarry& c = tr->carry;
+    const bool have = !c.in_alt && c.idx == idx && c.n == n;
+    // without the pose network folded in, a pending wave needs step_begin_kernel, whose gather then runs too
+    p.begin_gathers = !have || (!pf && c.wave_pending);
+    p.begin_pose = pf;
+    p.begin_launch = p.begin_gathers || pf;
+    if (flow == Flow::Backward) return p;
+  }
+  if (flow == Flow::Fused && wgrad_opt_usable(tr)) p.opt = Opt::WgradOpt;
+  else if (flow == Flow::Fused && pf) p.opt = Opt::AdamwPose;
+  else if (announced && tr->cfg.pose_refinement == 0 && tr->have_buf) p.opt = Opt::AdamwNext;
+  else if (tr->cfg.pose_refinement != 0) p.opt = Opt::AdamwSplitPose;
+  else p.opt = Opt::Adamw;
+  // wgrad_opt / adamw_pose: no launch after the loss kernel is free to gather, so the gather runs beside it into the other input buffer
+  if (announced && (p.opt == Opt::WgradOpt || p.opt == Opt::AdamwPose)) p.next_at = NextAt::Loss;
+  else if (p.opt == Opt::AdamwNext || (announced && p.opt == Opt::AdamwSplitPose && pf && tr->have_buf)) p.next_at = NextAt::Optimiser;
+  return p;
+}
+
+// the launch just enqueued runs the pending schedule wave: every later launch reads the slot it writes
+static void wave_ran(acez_trainer* tr) {
+  tr->st_cur ^= 1;
+  tr->st = tr->st_slot[tr->st_cur];
+  tr->carry.wave_pending = false;
+}
+
+// A pending wave as a launch of its own: before a state or log read, and before an update that follows an update (a data-parallel rank
+// whose shard holds no row of a batch zeroes its gradient and only takes part in the all-reduce).
+static void flush_post(acez_trainer* tr, hipStream_t s) {
+  if (!tr->carry.wave_pending) return;
+  ProfScope ps(tr, s, KC_SCHED);
+  const PostArgs p = post_args(tr);
+  hipLaunchKernelGGL(sched_post_kernel, dim3(1), dim3(64), 0, s, p.src, p.st, p.c, p.grad_stats, p.inv_global_batch, p.log_loss, p.log_inl, p.log_cap, p.fault,
+                     p.stat_partials, p.n_loss_blocks);
+  wave_ran(tr);
+}
+
+// The launch that opens a step: the gather of its batch, the pending wave of the step before and, with the pose network folded in, its
+// forward for all images. The record's batch is used up either way. Afterwards tr->st is the slot the step reads.
+static void begin_step(acez_trainer* tr, const StepPlan& p, const int64_t* d_indices, int n, hipStream_t s) {
+  tr->carry.drop_batch();
+  if (!p.begin_launch) return;   // the batch was gathered ahead, the wave of the step before has run
+  if (p.begin_pose && !tr->pose_wt_valid) {   // first step / after acez_trainer_sync_weights / after a split (backward + update) step
     hipLaunchKernelGGL(pose_transpose_kernel, dim3(4, 4, 4), dim3(256), 0, s, (const float*)tr->pb.d_pose_params, tr->pose_wt, (const int*)nullptr);
     tr->pose_wt_valid = true;
   }
-  ProfScope* psg = new ProfScope(tr, s, KC_GATHER);
-  const int gblocks = (pf && pre_ok) ? 0 : ((n + 3) / 4 < 1024 ? (n + 3) / 4 : 1024);
-  if (pf) {   // + the pose network's forward for all images, as the first workgroups of the same launch
-    const int T = tr->pose_tile_fwd, np = (tr->buf.n_images + T - 1) / T;
-    const int do_post = tr->post_pending ? 1 : 0;
-    tr->post_pending = false;
-#define ACEZ_SBP(TT) hipLaunchKernelGGL(step_begin_pose_kernel<TT>, dim3(np + gblocks + 1), dim3(pose_fwd_threads<TT>()), 0, s, (const uint16_t*)tr->buf.d_features, \
-                                        d_indices, tr->R[0], n, post_args(tr), do_post, pose_net_args(tr, nullptr), np, gather_meta(tr))
-    if (T == 16) ACEZ_SBP(16); else if (T == 4) ACEZ_SBP(4); else ACEZ_SBP(8);
-#undef ACEZ_SBP
-    if (do_post) st_flip(tr);
-  } else if (tr->post_pending) {   // gather of this step + the schedule bookkeeping of the previous one, in one launch
-    tr->post_pending = false;
+  ProfScope psg(tr, s, KC_GATHER);
+  const int gblocks = p.begin_gathers ? gather_blocks(n) : 0;
+  const bool wave = tr->carry.wave_pending;
+  if (p.begin_pose)   // the pose forward as the first workgroups of the launch (with no gather workgroups when the batch is there)
+    with_pose_tile(tr, tr->buf.n_images, [&](auto tile, int np) {
+      constexpr int T = decltype(tile)::value;
+      hipLaunchKernelGGL(step_begin_pose_kernel<T>, dim3(np + gblocks + 1), dim3(pose_fwd_threads<T>()), 0, s, (const uint16_t*)tr->buf.d_features,
+                         d_indices, tr->R[0], n, post_args(tr), wave ? 1 : 0, pose_net_args(tr, nullptr), np, gather_meta(tr));
+    });
+  else if (wave)
     hipLaunchKernelGGL(step_begin_kernel, dim3(gblocks + 1), dim3(256), 0, s, (const uint16_t*)tr->buf.d_features, d_indices, tr->R[0], n,
                        post_args(tr), gather_meta(tr));
-    st_flip(tr);
-  } else {
-    hipLaunchKernelGGL(gather_kernel, dim3(gblocks), dim3(256), 0, s, (const uint16_t*)tr->buf.d_features, d_indices, tr->R[0], n, st, gather_meta(tr));
-  }
-  delete psg;
-  }
+  else
+    hipLaunchKernelGGL(gather_kernel, dim3(gblocks), dim3(256), 0, s, (const uint16_t*)tr->buf.d_features, d_indices, tr->R[0], n, (const TrainState*)tr->st,
+                       gather_meta(tr));
+  if (wave) wave_ran(tr);
 }
 
-// The loss launch of a training step (+ the next batch's gather beside it, when announced on a path that has no optimiser launch to carry it)
-static void launch_train_loss(acez_trainer* tr, const uint16_t* act, const int64_t* d_indices, int n, int nblk, hipStream_t s, bool fused,
-                              const int64_t* d_next, int n_next, bool pose_tables) {
-  LossArgs a{};
-  fill_loss_train(tr, a, act, d_indices, n, pose_tables);
-  tr->last_nblk = nblk;   // (after this step's step_begin, whose schedule wave closed the step BEFORE with that step's count)
-  ProfScope ps(tr, s, KC_LOSS);
-  tr->next_gathered = false;
-  if (fused && d_next && n_next > 0 && (wgrad_opt_usable(tr) || tr->pose_fused) && tr->loss_rows == 4 && tr->R0_alt) {
-    // the next batch's gather as extra workgroups of the loss launch (this path has no optimiser launch to carry it): 32 rows per
-    // workgroup and pass, as many workgroups as the loss kernel leaves free (two of these workgroups fit a CU)
-    const int want = (n_next + 31) / 32, room = std::max(32, 2 * tr->n_cus - nblk);
-    const int gblocks = std::min(want, room);
-    GatherMeta gm = gather_meta(tr);
-    gm.dst = tr->batch_meta_alt;
-    if (tr->f16) hipLaunchKernelGGL((loss_gather_kernel<EltF16, 4>), dim3(nblk + gblocks), dim3(256), 0, s, a, nblk, (const uint16_t*)tr->buf.d_features, d_next, tr->R0_alt, n_next, gm);
-    else hipLaunchKernelGGL((loss_gather_kernel<EltBf16, 4>), dim3(nblk + gblocks), dim3(256), 0, s, a, nblk, (const uint16_t*)tr->buf.d_features, d_next, tr->R0_alt, n_next, gm);
-    tr->next_gathered = true; tr->next_idx = d_next; tr->next_n = n_next;
-  } else {
-    launch_loss(tr, nblk, s, a);
+// The end of a step: a next batch gathered beside its loss kernel moves to R[0]; unless one of the step's own launches ran its wave, the
+// wave is left to the next step's begin launch or to flush_post.
+static void close_step(acez_trainer* tr, const StepPlan& p) {
+  if (tr->carry.in_alt) {
+    std::swap(tr->R[0], tr->R0_alt);
+    std::swap(tr->batch_meta, tr->batch_meta_alt);
+    tr->carry.in_alt = false;
   }
+  if (p.opt != Opt::WgradOpt && p.opt != Opt::AdamwNext) tr->carry.wave_pending = true;
+}
+
+// The loss launch of a training step (+ the next batch's gather beside it: NextAt::Loss)
+static void launch_train_loss(const StepRun& r) {
+  acez_trainer* tr = r.tr;
+  LossArgs a{};
+  fill_loss_train(tr, a, tr->out[3 * (tr->nb + 1) + 1], r.idx, r.n, tr->cfg.pose_refinement != 0);
+  tr->last_nblk = r.nblk;   // (after this step's begin launch, whose schedule wave closed the step BEFORE with that step's count)
+  ProfScope ps(tr, r.s, KC_LOSS);
+  if (r.plan.next_at != NextAt::Loss) return launch_loss(tr, r.nblk, r.s, a);
+  // 32 rows per gather workgroup and pass, as many workgroups as the loss kernel leaves free (two of these workgroups fit a CU)
+  const int gblocks = std::min((r.n_next + 31) / 32, std::max(32, 2 * tr->n_cus - r.nblk));
+  GatherMeta gm = gather_meta(tr);
+  gm.dst = tr->batch_meta_alt;
+  if (tr->f16) hipLaunchKernelGGL((loss_gather_kernel<EltF16, 4>), dim3(r.nblk + gblocks), dim3(256), 0, r.s, a, r.nblk, (const uint16_t*)tr->buf.d_features, r.next, tr->R0_alt, r.n_next, gm);
+  else hipLaunchKernelGGL((loss_gather_kernel<EltBf16, 4>), dim3(r.nblk + gblocks), dim3(256), 0, r.s, a, r.nblk, (const uint16_t*)tr->buf.d_features, r.next, tr->R0_alt, r.n_next, gm);
+  tr->carry.hold(r.next, r.n_next, true);
 }
 
 // The input-gradient chain of a training step (collect != null: nothing is launched, the one-launch chain's layer table goes to *collect)
@@ -847,9 +890,9 @@ static void launch_dgrad(acez_trainer* tr, int n, const TrainState* st, hipStrea
   else if (seq) launch_rowseq<true>(tr, sq, n, st, s);
 }
 
-// The partial buffers of a step and its weight-gradient launch (fused: wgrad_opt_kernel where usable); the split flow's gradient reduction
-static void launch_weight_grads(acez_trainer* tr, int n, int nblk, const TrainState* st, hipStream_t s, bool fused) {
-  const bool pf = tr->pose_fused;
+// The partial buffers of a step and its weight-gradient launch (wgrad_opt_kernel: Opt::WgradOpt); the split flow's gradient reduction
+static void launch_weight_grads(acez_trainer* tr, const StepPlan& p, int n, int nblk, const TrainState* st, hipStream_t s) {
+  const bool fused = p.flow == Flow::Fused;
   const int f2 = 3 * (tr->nb + 1) + 1;
   // the partial buffers of this step (reduced by grad_reduce_kernel in the split flow, by the optimiser launches in the fused step)
   {
@@ -865,16 +908,15 @@ static void launch_weight_grads(acez_trainer* tr, int n, int nblk, const TrainSt
     tr->last_reduce = a;   // the fused update reduces the partials itself
   }
   // weight gradients of all wide layers in one launch
-  tr->wide_done = false;
   {
     WgradArgs a{};
     fill_wgrad_args(tr, a, n, st);
     if (const char* e = ACEZ_DIAG_ENV("ACEZ_WGO_DBG")) a.dbg = atoi(e);   // timing experiments (wgrad_opt_kernel's ablation bits)
     ProfScope ps(tr, s, KC_WGRAD);
     const int groups = tr->L * tr->nslabs;
-    if (fused && wgrad_opt_usable(tr)) {
+    if (p.opt == Opt::WgradOpt) {
       // single-GPU fused step: the launch applies the optimiser to the wide layers' weights itself (wgrad_opt_kernel); the update that
-      // follows (train_update_impl) only has the small parameters, the statistics and the schedule left
+      // follows has nothing left to launch
       WgradOptArgs o{};
       fill_adam_args(tr, o.ad);
       o.ad.tail = tr->last_reduce;
@@ -889,14 +931,12 @@ static void launch_weight_grads(acez_trainer* tr, int n, int nblk, const TrainSt
       // the small parameters ride in the multiplier waves of the first workgroups, the schedule wave that closes the step in the last one
       o.nsmall = small_cols_blocks(tr->L, (int64_t)tr->no * 513, 8);
       o.do_post = 1;
-      if (const char* e = ACEZ_DIAG_ENV("ACEZ_WGO_POST")) o.do_post = o.do_post && atoi(e) != 0;   // timing experiments: the schedule wave as its own launch
       const dim3 grid(256 * ((tr->L + 7) / 8));
       if ((int)grid.x < o.nsmall) abort();
       const PostArgs post = post_args(tr);
       if (tr->f16) hipLaunchKernelGGL(wgrad_opt_kernel<EltF16>, grid, dim3(WGRAD_THREADS), 0, s, a, o, post);
       else hipLaunchKernelGGL(wgrad_opt_kernel<EltBf16>, grid, dim3(WGRAD_THREADS), 0, s, a, o, post);
-      tr->wide_done = true;
-          tr->post_done = o.do_post != 0;
+      wave_ran(tr);
     }
     else if (tr->f16) hipLaunchKernelGGL(wgrad_kernel<EltF16>, dim3(128 * ((groups + 7) / 8)), dim3(WGRAD_THREADS), 0, s, a);
     else hipLaunchKernelGGL(wgrad_kernel<EltBf16>, dim3(128 * ((groups + 7) / 8)), dim3(WGRAD_THREADS), 0, s, a);
@@ -905,203 +945,189 @@ static void launch_weight_grads(acez_trainer* tr, int n, int nblk, const TrainSt
     const int64_t wide_blocks = (tr->n_wide / 4 + 255) / 256;
     const int64_t tail_blocks = grad_reduce_tail_blocks(tr->L, tr->n_params - tr->n_wide);
     ProfScope ps(tr, s, KC_REDUCE);
-    if (pf) {
-      // split flow with the pose network folded in (a data-parallel host all-reduces d_grad next, so the pose gradients must be complete
-      // now): the reduce + backward chain (S1) rides at the front of the gradient-reduction launch, the weight gradients (S2) follow
-      const PoseNetArgs a = pose_net_args(tr, &tr->st->active);
-      const int T = tr->pose_tile, np = (tr->buf.n_images + T - 1) / T;
-#define ACEZ_GRP(TT) hipLaunchKernelGGL(grad_reduce_pose_kernel<TT>, dim3((unsigned)(np + wide_blocks + tail_blocks)), dim3(256), 0, s, tr->last_reduce, a, \
-                                        (const float*)tr->row_dT, (const int*)tr->row_image, n, np)
-      if (T == 16) ACEZ_GRP(16); else if (T == 4) ACEZ_GRP(4); else ACEZ_GRP(8);
-#undef ACEZ_GRP
-    } else {
+    // split flow with the pose network folded in (a data-parallel host all-reduces d_grad next, so the pose gradients must be complete
+    // now): the reduce + backward chain (S1) rides at the front of the gradient-reduction launch, the weight gradients (S2) follow
+    if (tr->pose_fused)
+      with_pose_tile(tr, tr->buf.n_images, [&](auto tile, int np) {
+        hipLaunchKernelGGL(grad_reduce_pose_kernel<decltype(tile)::value>, dim3((unsigned)(np + wide_blocks + tail_blocks)), dim3(256), 0, s, tr->last_reduce,
+                           pose_net_args(tr, &tr->st->active), (const float*)tr->row_dT, (const int*)tr->row_image, n, np);
+      });
+    else
       hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(wide_blocks + tail_blocks)), dim3(256), 0, s, tr->last_reduce);
-    }
   }
 }
 
-static int train_backward_impl(acez_trainer* tr, const int64_t* d_indices, int n, void* stream, bool fused, const int64_t* d_next = nullptr,
-                               int n_next = 0) {
-  ACEZ_REQUIRE(tr && d_indices, "null pointer");
-  ACEZ_REQUIRE(!tr->inference_only, "an inference-only context (acez_train_config.inference_only) cannot train");
-  ACEZ_REQUIRE(tr->have_buf, "acez_trainer_set_buffer has not been called");
-  ACEZ_REQUIRE(n > 0 && n <= tr->max_batch, "n must be in [1, max_batch]");
-  ACEZ_HIP_CHECK(hipSetDevice(tr->device));
-  hipStream_t s = (hipStream_t)stream;
-  const TrainState* st = tr->st;   // (re-read below: the launch that closes the previous step moves the state to the other slot)
-  tr->last_n = n;
-
-  const bool pose_naive = tr->cfg.pose_refinement == 1;
-  const bool pose_mlp = tr->cfg.pose_refinement == 2 || pose_naive;   // both need the refined-pose table and per-row pose gradients
-  // Pose refinement on its own stream: the refined poses are needed by the loss phase only, so their launches run beside the
-  // head's forward chain; the pose-gradient launches run beside the input-gradient chain and wgrad.
-  hipStream_t ps = (pose_mlp && tr->pose_stream) ? tr->pose_stream : s;
-  // mlp refinement folded into the step's own launches (pose_fused.hip): forward beside the gather, backward beside / behind the optimiser
-  const bool pf = tr->pose_fused;
-  const int nblk = (n + 4 * tr->loss_rows - 1) / (4 * tr->loss_rows);
-  auto pose_fwd_launches = [&](hipStream_t q) {
-    if (tr->cfg.pose_refinement == 2) pose_forward(tr, &tr->st->active, q);
-    if (pose_naive)   // refine_poses.py:224-234: the poses themselves are the parameters; P = 0 + 1 * params, then Gram-Schmidt
-      hipLaunchKernelGGL(pose_compose_kernel, dim3((tr->buf.n_images + 255) / 256), dim3(256), 0, q, (const float*)tr->pa1,
-                         (const float*)tr->pb.d_pose_params, 1.0f, tr->pose_cur, tr->buf.n_images, (const int*)&tr->st->active, tr->cfg.pose_refinement_ortho);
-  };
-  auto pose_bwd_launches = [&](hipStream_t q) {
-    if (tr->cfg.pose_refinement == 2) pose_backward(tr, n, &tr->st->active, q);
-    if (pose_naive) {
-      const int I = tr->buf.n_images;
-      launch_pose_grad_reduce(tr, n, (const int*)&tr->st->active, q);
-      hipLaunchKernelGGL(pose_compose_bwd_kernel, dim3((I + 255) / 256), dim3(256), 0, q, (const float*)tr->pa1, (const float*)tr->pb.d_pose_params, 1.0f,
-                         (const float*)tr->pdT, tr->pb.d_grad + tr->n_params + 4, I, (const int*)&tr->st->active, tr->cfg.pose_refinement_ortho);
-    }
-  };
-
-  begin_batch(tr, d_indices, n, s);
-  st = tr->st;   // the slot the bookkeeping (if any rode with the gather) has just written
-  if (ps != s) {   // after the schedule bookkeeping of step_begin (the pose kernels read st->active / pose_enable)
-    ACEZ_HIP_CHECK(hipEventRecord(tr->ev_begin, s));
-    ACEZ_HIP_CHECK(hipStreamWaitEvent(ps, tr->ev_begin, 0));
-  }
-  if (!pf) pose_fwd_launches(ps);
-  if (ps != s) ACEZ_HIP_CHECK(hipEventRecord(tr->ev_pose_fwd, ps));
-  const uint16_t* act = launch_forward(tr, tr->R[0], n, st, s);
-  if (ps != s) ACEZ_HIP_CHECK(hipStreamWaitEvent(s, tr->ev_pose_fwd, 0));   // the loss kernel projects with the refined poses
-
-  launch_train_loss(tr, act, d_indices, n, nblk, s, fused, d_next, n_next, pose_mlp);
-
-  if (ps != s) {   // the pose gradients start from the per-row pose gradients the loss kernel has just written
-    ACEZ_HIP_CHECK(hipEventRecord(tr->ev_loss, s));
-    ACEZ_HIP_CHECK(hipStreamWaitEvent(ps, tr->ev_loss, 0));
-  }
-  if (!pf) pose_bwd_launches(ps);
-  if (ps != s) ACEZ_HIP_CHECK(hipEventRecord(tr->ev_pose_bwd, ps));
-
-  launch_dgrad(tr, n, st, s);
-  launch_weight_grads(tr, n, nblk, st, s, fused);
-  if (ps != s) ACEZ_HIP_CHECK(hipStreamWaitEvent(s, tr->ev_pose_bwd, 0));   // d_grad's pose tail: read by the all-reduce and by the pose AdamW
-  if (pf && !fused) launch_pose_wgrad(tr, &tr->st->active, false, s);
-  ACEZ_HIP_CHECK(hipGetLastError());
-  return ACEZ_OK;
-}
-
-extern "C" int acez_train_backward(acez_trainer* tr, const int64_t* d_indices, int n, void* stream) {
-  return train_backward_impl(tr, d_indices, n, stream, false);
-}
-
-static int train_update_impl(acez_trainer* tr, void* stream, bool fused, int layer_lo = 0, int layer_hi = -1, const int64_t* d_next = nullptr,
-                             int n_next = 0) {
-  ACEZ_REQUIRE(tr, "null trainer");
-  ACEZ_REQUIRE(!tr->inference_only, "an inference-only context (acez_train_config.inference_only) cannot train");
-  if (layer_hi < 0) layer_hi = tr->L;
-  ACEZ_REQUIRE(layer_lo >= 0 && layer_lo <= layer_hi && layer_hi <= tr->L, "layer range out of bounds");
-  ACEZ_REQUIRE(!fused || (layer_lo == 0 && layer_hi == tr->L), "the fused step updates every layer");
-  ACEZ_HIP_CHECK(hipSetDevice(tr->device));
-  hipStream_t s = (hipStream_t)stream;
-  // two updates without a backward in between (a data-parallel rank whose shard holds no row of a batch zeroes its gradient and
-  // only takes part in the all-reduce): the schedule bookkeeping of the previous step must not be lost
+// The optimiser launch(es) of a step in the form plan_step chose (a pending wave flushed first), then close_step
+static int launch_update(acez_trainer* tr, const StepPlan& p, hipStream_t s, int layer_lo, int layer_hi, const int64_t* d_next, int n_next) {
   flush_post(tr, s);
+  const bool fused = p.flow == Flow::Fused;
   AdamArgs a;
   fill_adam_args(tr, a);
   if (fused) { a.slabs = tr->slabs; a.nslabs = tr->nslabs; a.slab_stride = tr->n_wide; a.tail = tr->last_reduce; }
+  a.layer_lo = layer_lo; a.layer_hi = layer_hi;
   const int nsmall = adamw_small_blocks(tr->L, (int64_t)tr->no * 513, fused);   // small-parameter workgroups come first in the grid
-  // wgrad_opt_kernel of this step's backward has already updated the wide layers' weights and the small parameters: no optimiser
-  // workgroups for the head are left
-  const bool wide_done = fused && tr->wide_done;
-  tr->wide_done = false;
-  if (wide_done) {
-    // ... and it has closed the step; the next batch (acez_train_step_next) was gathered beside the loss kernel into the other buffers
-    if (tr->post_done) { st_flip(tr); tr->post_pending = false; } else { tr->post_pending = true; }
-    tr->post_done = false;
-    if (tr->next_gathered) {
-      std::swap(tr->R[0], tr->R0_alt);
-      std::swap(tr->batch_meta, tr->batch_meta_alt);
-      tr->pre_idx = tr->next_idx; tr->pre_n = tr->next_n;
-      tr->next_gathered = false;
-    }
-    return ACEZ_OK;
-  }
-  const bool pf = tr->pose_fused;
-  if (pf && fused) {
+  const int n_adam = (layer_hi - layer_lo) * 64 + nsmall;
+  switch (p.opt) {
+  case Opt::WgradOpt: break;   // wgrad_opt_kernel has updated the wide layers' weights and the small parameters, and run the step's wave
+  case Opt::AdamwPose:
     // the head's AdamW with the pose network's reduce + backward chain (S1) as the first workgroups of the same launch, then the
     // pose weight gradients with AdamW in their epilogue (S2: needs S1 of every image tile)
-    const int T = tr->pose_tile, np = (tr->buf.n_images + T - 1) / T;
-    { ProfScope ps(tr, s, KC_ADAMW);
-#define ACEZ_AP(TT) hipLaunchKernelGGL(adamw_pose_kernel<TT>, dim3(np + tr->L * 64 + nsmall), dim3(pose_threads<TT>()), 0, s, a, pose_net_args(tr, &tr->st->active, 1), \
-                                       (const float*)tr->row_dT, (const int*)tr->row_image, tr->last_n, np)
-      if (T == 16) ACEZ_AP(16); else if (T == 4) ACEZ_AP(4); else ACEZ_AP(8);
-#undef ACEZ_AP
-    }
+    with_pose_tile(tr, tr->buf.n_images, [&](auto tile, int np) {
+      constexpr int T = decltype(tile)::value;
+      ProfScope ps(tr, s, KC_ADAMW);
+      hipLaunchKernelGGL(adamw_pose_kernel<T>, dim3(np + n_adam), dim3(pose_threads<T>()), 0, s, a, pose_net_args(tr, &tr->st->active, 1),
+                         (const float*)tr->row_dT, (const int*)tr->row_image, tr->last_n, np);
+    });
     launch_pose_wgrad(tr, &tr->st->active, true, s);
-    tr->post_pending = true;
-    if (tr->next_gathered) {   // the next batch was gathered beside this step's loss kernel into the other input buffer (this step's wgrad read the current one)
-      std::swap(tr->R[0], tr->R0_alt);
-      std::swap(tr->batch_meta, tr->batch_meta_alt);
-      tr->pre_idx = tr->next_idx; tr->pre_n = tr->next_n;
-      tr->next_gathered = false;
-    }
-    ACEZ_HIP_CHECK(hipGetLastError());
-    return ACEZ_OK;
-  }
-  a.layer_lo = layer_lo; a.layer_hi = layer_hi;
-  if (d_next && n_next > 0 && tr->cfg.pose_refinement == 0 && tr->have_buf && layer_lo == 0 && layer_hi == tr->L) {
-    // the next batch is known: its gather and this step's schedule bookkeeping ride in the optimiser's launch (adamw_next_kernel).
-    // fused: the optimiser sums the weight-gradient slabs itself; else (acez_train_update_next: a data-parallel rank) it reads the
-    // all-reduced bucket like adamw_kernel, and the schedule wave takes the statistics from the bucket too (a.tail is null)
-    int n_adam = tr->L * 64 + nsmall;
-    // timing experiments (diagnostics build; results wrong by construction): 1 = no optimiser workgroups at all, 2 = no gather
-    const int tail_abl = ACEZ_DIAG_ENV("ACEZ_TAIL_ABL") ? atoi(ACEZ_DIAG_ENV("ACEZ_TAIL_ABL")) : 0;
-    if (tail_abl & 1) n_adam = 0;
-    if (tail_abl & 2) n_next = 0;
-    // every workgroup of the launch resident at once (4 of these 256-thread workgroups per CU): gather workgroups that had to wait for a
-    // free slot started when the optimiser's tiles were done and ran their three load levels as the launch's tail. ACEZ_NEXT_GBLOCKS
-    // overrides the count (timing experiments).
-    int gcap = 4 * tr->n_cus - n_adam - 1;
-    if (gcap < 64) gcap = 64;
-    if (const char* e = ACEZ_DIAG_ENV("ACEZ_NEXT_GBLOCKS")) gcap = std::max(1, atoi(e));
-    const int gwant = (n_next + 3) / 4 < 1024 ? (n_next + 3) / 4 : 1024;
-    const int gblocks = gwant < gcap ? gwant : gcap;
+    break;
+  case Opt::AdamwNext: {
+    // the next batch's gather and this step's wave ride in the optimiser's launch (split flow: the wave takes the statistics from the
+    // all-reduced bucket, a.tail is null). Every workgroup resident at once (4 per CU): gather workgroups that had to wait for a free slot
+    // started when the optimiser's tiles were done and ran their three load levels as the launch's tail.
+    const int gblocks = std::min(gather_blocks(n_next), std::max(64, 4 * tr->n_cus - n_adam - 1));
     { ProfScope ps(tr, s, KC_ADAMW);
       // (+ 1: the launch's last workgroup is the schedule wave, as in step_begin_kernel -- gblocks gather workgroups remain)
       hipLaunchKernelGGL(adamw_next_kernel, dim3(n_adam + gblocks + 1), dim3(256), 0, s, a, n_adam, (const uint16_t*)tr->buf.d_features, d_next, tr->R[0], n_next,
                          post_args(tr), gather_meta(tr)); }
-    st_flip(tr);
-    tr->pre_idx = d_next; tr->pre_n = n_next;
-    tr->post_pending = false;
-    ACEZ_HIP_CHECK(hipGetLastError());
-    return ACEZ_OK;
+    wave_ran(tr);
+    tr->carry.hold(d_next, n_next, false);
+    break;
   }
-  if (tr->cfg.pose_refinement != 0) {
-    // the pose parameters' AdamW (and, for the network, the refresh of its four transposed copies) at the front of the head's optimiser launch
+  case Opt::AdamwSplitPose: {
+    // the pose parameters' AdamW (and, for the network, the refresh of its four transposed copies) at the front of the head's optimiser
+    // launch; NextAt::Optimiser: the next batch's rows are gathered here, the next backward's first launch keeps the pose forward and the
+    // schedule wave (step_begin_pose_kernel without gather workgroups)
     float* wt = (tr->cfg.pose_refinement == 2 && tr->pose_fused) ? tr->pose_wt : nullptr;
     const int npb = (int)((tr->pb.n_pose_params + 255) / 256);
-    const int n_adam = (layer_hi - layer_lo) * 64 + nsmall;
-    // the next batch announced (acez_train_update_next) and the pose network folded into the step's launches: its rows are gathered here,
-    // the next backward's first launch keeps the pose forward and the schedule wave (step_begin_pose_kernel without gather workgroups)
-    const bool ahead = d_next && n_next > 0 && tr->pose_fused && tr->have_buf && layer_lo == 0 && layer_hi == tr->L;
-    int gblocks = 0;
-    if (ahead) {
-      const int gwant = (n_next + 3) / 4 < 1024 ? (n_next + 3) / 4 : 1024;
-      gblocks = std::max(64, std::min(gwant, 4 * tr->n_cus - n_adam - npb));
-    }
+    const bool ahead = p.next_at == NextAt::Optimiser;
+    const int gblocks = ahead ? std::max(64, std::min(gather_blocks(n_next), 4 * tr->n_cus - n_adam - npb)) : 0;
     { ProfScope ps(tr, s, KC_ADAMW);
       hipLaunchKernelGGL(adamw_split_pose_kernel, dim3(npb + n_adam + gblocks), dim3(256), 0, s, a, npb, tr->pb.d_pose_params, tr->pb.d_pose_m,
                          tr->pb.d_pose_v, (const float*)(tr->pb.d_grad + tr->n_params + 4), (int64_t)tr->pb.n_pose_params,
                          (const AdamScalars*)&tr->st->pose_adam, (const int*)&tr->st->pose_enable, (const int*)&tr->st->active, (const int*)tr->seq_err, wt,
                          n_adam, (const uint16_t*)tr->buf.d_features, d_next, tr->R[0], ahead ? n_next : 0, gather_meta(tr)); }
-    if (ahead) { tr->pre_idx = d_next; tr->pre_n = n_next; }
+    if (ahead) tr->carry.hold(d_next, n_next, false);
     if (!wt) tr->pose_wt_valid = false;   // no transposed copies kept here: the next folded forward rebuilds them
-  } else {
-    ProfScope ps(tr, s, KC_ADAMW);
-    hipLaunchKernelGGL(adamw_kernel, dim3((layer_hi - layer_lo) * 64 + nsmall), dim3(256), 0, s, a);
+    break;
   }
-  tr->post_pending = true;   // sched_post: with the next step's gather, or at the next state read-out (flush_post)
+  default: {   // Opt::Adamw
+    ProfScope ps(tr, s, KC_ADAMW);
+    hipLaunchKernelGGL(adamw_kernel, dim3(n_adam), dim3(256), 0, s, a);
+    break;
+  }
+  }
+  close_step(tr, p);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
 }
 
-extern "C" int acez_train_update(acez_trainer* tr, void* stream) { return train_update_impl(tr, stream, false); }
+// pose refinement of the launches the head's step does not carry (naive; mlp with ACEZ_POSE_FUSED=0): forward, and the gradients from the
+// loss kernel's per-row pose gradients
+static void pose_fwd_launches(acez_trainer* tr, hipStream_t q) {
+  if (tr->cfg.pose_refinement == 2) pose_forward(tr, &tr->st->active, q);
+  if (tr->cfg.pose_refinement == 1)   // refine_poses.py:224-234: the poses themselves are the parameters; P = 0 + 1 * params, then Gram-Schmidt
+    hipLaunchKernelGGL(pose_compose_kernel, dim3((tr->buf.n_images + 255) / 256), dim3(256), 0, q, (const float*)tr->pa1,
+                       (const float*)tr->pb.d_pose_params, 1.0f, tr->pose_cur, tr->buf.n_images, (const int*)&tr->st->active, tr->cfg.pose_refinement_ortho);
+}
+static void pose_bwd_launches(acez_trainer* tr, int n, hipStream_t q) {
+  if (tr->cfg.pose_refinement == 0) return;
+  const int I = tr->buf.n_images;
+  const int* active = &tr->st->active;
+  hipLaunchKernelGGL(pose_grad_reduce2_kernel, dim3((I + 15) / 16), dim3(256), 0, q, (const float*)tr->row_dT, (const int*)tr->row_image, n, tr->pdT, I, active);
+  if (tr->cfg.pose_refinement == 2) {   // the network's input-gradient chain and weight gradients -> d_grad tail
+    hipLaunchKernelGGL(pose_mlp_bwd_kernel, dim3((I + PN_IMG - 1) / PN_IMG), dim3(256), 0, q, pose_net_args(tr, active));
+    launch_pose_wgrad(tr, active, false, q);
+  } else {
+    hipLaunchKernelGGL(pose_compose_bwd_kernel, dim3((I + 255) / 256), dim3(256), 0, q, (const float*)tr->pa1, (const float*)tr->pb.d_pose_params, 1.0f,
+                       (const float*)tr->pdT, tr->pb.d_grad + tr->n_params + 4, I, active, tr->cfg.pose_refinement_ortho);
+  }
+}
+
+static StepRun start_run(acez_trainer* tr, Flow flow, const int64_t* idx, int n, const int64_t* next, int n_next, hipStream_t s) {
+  return StepRun{tr, plan_step(tr, flow, idx, n, next, n_next), idx, n, next, n_next, loss_blocks(n), s, tr->pose_stream ? tr->pose_stream : s, nullptr};
+}
+
+// a run's GEMM chain on per-layer launches or rowseq_kernel: forward (bwd = false) or input gradients
+static void launch_chain(const StepRun& r, bool bwd) {
+  if (bwd) launch_dgrad(r.tr, r.n, r.st, r.s);
+  else launch_forward(r.tr, r.tr->R[0], r.n, r.st, r.s);
+}
+
+// The phases of a training step around its two GEMM chains, for one trainer or for the members of a group side by side (head_group.hip);
+// chains(bwd) enqueues the forward (false) / input-gradient (true) chains of all runs. A fused step ends with its update.
+// Pose refinement on its own stream (r.ps): the refined poses are needed by the loss phase only, so their launches run beside the head's
+// forward chain; the pose-gradient launches run beside the input-gradient chain and wgrad.
+template <class Chains>
+static int run_steps(StepRun* runs, int count, Chains chains) {
+  for (int i = 0; i < count; ++i) {
+    StepRun& r = runs[i];
+    acez_trainer* tr = r.tr;
+    tr->last_n = r.n;
+    begin_step(tr, r.plan, r.idx, r.n, r.s);
+    r.st = tr->st;
+    if (r.ps != r.s) {   // after the schedule wave of the begin launch (the pose kernels read st->active / pose_enable)
+      ACEZ_HIP_CHECK(hipEventRecord(tr->ev_begin, r.s));
+      ACEZ_HIP_CHECK(hipStreamWaitEvent(r.ps, tr->ev_begin, 0));
+    }
+    if (!tr->pose_fused) pose_fwd_launches(tr, r.ps);
+    if (r.ps != r.s) ACEZ_HIP_CHECK(hipEventRecord(tr->ev_pose_fwd, r.ps));
+  }
+  chains(false);
+  for (int i = 0; i < count; ++i) {
+    StepRun& r = runs[i];
+    acez_trainer* tr = r.tr;
+    if (r.ps != r.s) ACEZ_HIP_CHECK(hipStreamWaitEvent(r.s, tr->ev_pose_fwd, 0));   // the loss kernel projects with the refined poses
+    launch_train_loss(r);
+    if (r.ps != r.s) {   // the pose gradients start from the per-row pose gradients the loss kernel has just written
+      ACEZ_HIP_CHECK(hipEventRecord(tr->ev_loss, r.s));
+      ACEZ_HIP_CHECK(hipStreamWaitEvent(r.ps, tr->ev_loss, 0));
+    }
+    if (!tr->pose_fused) pose_bwd_launches(tr, r.n, r.ps);
+    if (r.ps != r.s) ACEZ_HIP_CHECK(hipEventRecord(tr->ev_pose_bwd, r.ps));
+  }
+  chains(true);
+  for (int i = 0; i < count; ++i) {
+    StepRun& r = runs[i];
+    acez_trainer* tr = r.tr;
+    launch_weight_grads(tr, r.plan, r.n, r.nblk, r.st, r.s);
+    if (r.ps != r.s) ACEZ_HIP_CHECK(hipStreamWaitEvent(r.s, tr->ev_pose_bwd, 0));   // d_grad's pose tail: read by the all-reduce and by the pose AdamW
+    if (tr->pose_fused && r.plan.flow == Flow::Backward) launch_pose_wgrad(tr, &tr->st->active, false, r.s);
+    ACEZ_HIP_CHECK(hipGetLastError());
+    if (r.plan.flow == Flow::Fused) {
+      const int rc = launch_update(tr, r.plan, r.s, 0, tr->L, r.next, r.n_next);
+      if (rc != ACEZ_OK) return rc;
+    }
+  }
+  return ACEZ_OK;
+}
+
+static int train_step_impl(acez_trainer* tr, Flow flow, const int64_t* d_indices, int n, void* stream, const int64_t* d_next = nullptr, int n_next = 0) {
+  ACEZ_REQUIRE(tr && d_indices, "null pointer");
+  ACEZ_REQUIRE(!tr->inference_only, "an inference-only context (acez_train_config.inference_only) cannot train");
+  ACEZ_REQUIRE(tr->have_buf, "acez_trainer_set_buffer has not been called");
+  ACEZ_REQUIRE(n > 0 && n <= tr->max_batch, "n must be in [1, max_batch]");
+  ACEZ_HIP_CHECK(hipSetDevice(tr->device));
+  StepRun r = start_run(tr, flow, d_indices, n, d_next, n_next, (hipStream_t)stream);
+  return run_steps(&r, 1, [&](bool bwd) { launch_chain(r, bwd); });
+}
+
+extern "C" int acez_train_backward(acez_trainer* tr, const int64_t* d_indices, int n, void* stream) {
+  return train_step_impl(tr, Flow::Backward, d_indices, n, stream);
+}
+
+static int train_update_impl(acez_trainer* tr, void* stream, int layer_lo, int layer_hi, const int64_t* d_next = nullptr, int n_next = 0) {
+  ACEZ_REQUIRE(tr, "null trainer");
+  ACEZ_REQUIRE(!tr->inference_only, "an inference-only context (acez_train_config.inference_only) cannot train");
+  if (layer_hi < 0) layer_hi = tr->L;
+  ACEZ_REQUIRE(layer_lo >= 0 && layer_lo <= layer_hi && layer_hi <= tr->L, "layer range out of bounds");
+  ACEZ_HIP_CHECK(hipSetDevice(tr->device));
+  return launch_update(tr, plan_step(tr, Flow::Update, nullptr, 0, d_next, n_next), (hipStream_t)stream, layer_lo, layer_hi, d_next, n_next);
+}
+
+extern "C" int acez_train_update(acez_trainer* tr, void* stream) { return train_update_impl(tr, stream, 0, -1); }
 extern "C" int acez_train_update_next(acez_trainer* tr, const int64_t* d_indices_next, int n_next, void* stream) {
   ACEZ_REQUIRE(n_next >= 0 && (!tr || n_next <= tr->max_batch), "n_next must be in [0, max_batch]");
-  return train_update_impl(tr, stream, false, 0, -1, d_indices_next, n_next);
+  return train_update_impl(tr, stream, 0, -1, d_indices_next, n_next);
 }
 
 // Sharded data-parallel update (ZeRO-1 by layer): this rank applies AdamW to the weight matrices of wide layers [layer_lo, layer_hi)
@@ -1109,7 +1135,7 @@ extern "C" int acez_train_update_next(acez_trainer* tr, const int64_t* d_indices
 // the update is replicated), then closes the step's schedule bookkeeping like acez_train_update. The fp32 masters / AdamW moments of
 // the other layers' weights go stale on this rank until the owners' values are copied in (host: HeadTrainer.gather_masters).
 extern "C" int acez_train_update_layers(acez_trainer* tr, int layer_lo, int layer_hi, void* stream) {
-  return train_update_impl(tr, stream, false, layer_lo, layer_hi);
+  return train_update_impl(tr, stream, layer_lo, layer_hi);
 }
 
 // 16-bit compute copies W[out][in] of wide layers [layer_lo, layer_hi), 512 x 512 each, to / from a caller buffer (the all-gather
@@ -1147,9 +1173,7 @@ extern "C" int acez_trainer_import_weights16_all(acez_trainer* tr, int own_lo, i
 // optimiser (no flat-gradient round trip through HBM). Bitwise the same parameters as acez_train_backward + acez_train_update;
 // afterwards d_grad holds the bias / fc3 gradients and the statistics, its wide-layer weight part is NOT written.
 extern "C" int acez_train_step(acez_trainer* tr, const int64_t* d_indices, int n, void* stream) {
-  int rc = train_backward_impl(tr, d_indices, n, stream, true);
-  if (rc != ACEZ_OK) return rc;
-  return train_update_impl(tr, stream, true);
+  return train_step_impl(tr, Flow::Fused, d_indices, n, stream);
 }
 
 // acez_train_step with the NEXT step's batch announced: when the following call is acez_train_step / acez_train_step_next with exactly
@@ -1158,9 +1182,7 @@ extern "C" int acez_train_step(acez_trainer* tr, const int64_t* d_indices, int n
 // split backward, a state read) is still correct: it simply gathers again. d_indices_next may be NULL (= acez_train_step).
 extern "C" int acez_train_step_next(acez_trainer* tr, const int64_t* d_indices, int n, const int64_t* d_indices_next, int n_next, void* stream) {
   ACEZ_REQUIRE(n_next >= 0 && n_next <= (tr ? tr->max_batch : 0), "n_next must be in [0, max_batch]");
-  int rc = train_backward_impl(tr, d_indices, n, stream, true, d_indices_next, n_next);
-  if (rc != ACEZ_OK) return rc;
-  return train_update_impl(tr, stream, true, 0, -1, d_indices_next, n_next);
+  return train_step_impl(tr, Flow::Fused, d_indices, n, stream, d_indices_next, n_next);
 }
 
 extern "C" int acez_trainer_get_state(acez_trainer* tr, acez_train_state* h_out, void* stream) {
@@ -1280,7 +1302,7 @@ static int head_forward_impl(acez_trainer* tr, const void* d_features, int n, fl
       a.act = act; a.n = cnt; a.idx = nullptr; a.st = nullptr;
       if (planar_hw > 0) { a.out_xyz = d_out; a.planar_hw = planar_hw; a.row_offset = done; }
       else a.out_xyz = d_out + (size_t)done * 3;
-      launch_loss(tr, (cnt + 4 * tr->loss_rows - 1) / (4 * tr->loss_rows), s, a);
+      launch_loss(tr, loss_blocks(cnt), s, a);
     }
   };
   pass();
@@ -1362,12 +1384,10 @@ extern "C" int acez_trainer_get_poses(acez_trainer* tr, float* h_poses34, void* 
   hipStream_t s = (hipStream_t)stream;
   const int I = tr->buf.n_images;
   const float* src = tr->buf.d_image_pose_inv;
-  if (tr->cfg.pose_refinement == 2 && tr->pose_fused && tr->pose_tile_fwd != 16) {
+  if (tr->cfg.pose_refinement == 2 && tr->pose_fused && tr->pose_tile == 4) {
     const PoseNetArgs a = pose_net_args(tr, nullptr);
-    const int T = tr->pose_tile_fwd, np = (I + T - 1) / T;
     hipLaunchKernelGGL(pose_transpose_kernel, dim3(4, 4, 4), dim3(256), 0, s, a.P, tr->pose_wt, (const int*)nullptr);
-    if (T == 4) hipLaunchKernelGGL(pose_fwd_t_kernel<4>, dim3(np), dim3(pose_fwd_threads<4>()), 0, s, a);
-    else hipLaunchKernelGGL(pose_fwd_t_kernel<8>, dim3(np), dim3(pose_fwd_threads<8>()), 0, s, a);
+    hipLaunchKernelGGL(pose_fwd_t_kernel<4>, dim3((I + 3) / 4), dim3(pose_fwd_threads<4>()), 0, s, a);
     ACEZ_HIP_CHECK(hipGetLastError());
     src = tr->pose_cur;
   } else if (tr->cfg.pose_refinement == 2) {

@@ -163,7 +163,7 @@ extern "C" int acez_train_group_create(acez_train_group** out, acez_trainer* con
 // one of the two GEMM chains of the members listed in `idx` (all of them seq_usable for their batch) as one launch per SEQ_MAX_LAYERS
 // layers, with launch_rowseq's host bookkeeping per member
 template <bool BWD>
-static void launch_rowseq_group(acez_train_group* g, const std::vector<int>& idx, const int* n, const TrainState* const* st, hipStream_t s) {
+static void launch_rowseq_group(acez_train_group* g, const std::vector<int>& idx, const StepRun* runs, hipStream_t s) {
   const int total = BWD ? g->n_bwd : g->n_fwd;
   const bool f16 = g->m[0]->f16;
   for (int i0 = 0; i0 < total; i0 += SEQ_MAX_LAYERS) {
@@ -175,8 +175,8 @@ static void launch_rowseq_group(acez_train_group* g, const std::vector<int>& idx
     a.H = (int)g->m.size();
     for (int i : idx) {
       acez_trainer* tr = g->m[i];
-      a.st[i] = st[i]; a.M[i] = n[i]; a.variant[i] = tr->R[0] == g->in0[i] ? 0 : 1;
-      a.mtiles = std::max(a.mtiles, (n[i] + 79) / 80);
+      a.st[i] = runs[i].st; a.M[i] = runs[i].n; a.variant[i] = tr->R[0] == g->in0[i] ? 0 : 1;
+      a.mtiles = std::max(a.mtiles, (runs[i].n + 79) / 80);
       for (int mt = 0; mt < 64; ++mt) a.base[i][mt] = tr->seq_base[mt];
       if (cnt > 1 && tr->seq_launches == tr->seq_fault_at)   // tests (ACEZ_SEQ_FAULT_AT): as launch_rowseq
         for (int mt = 0; mt < 64; ++mt) a.base[i][mt] += 1u << 20;
@@ -187,7 +187,7 @@ static void launch_rowseq_group(acez_train_group* g, const std::vector<int>& idx
     else hipLaunchKernelGGL((rowseq_group_kernel<BWD, EltBf16>), grid, dim3(512), 0, s, a);
     for (int i : idx) {
       acez_trainer* tr = g->m[i];
-      for (int mt = 0; mt < (n[i] + 79) / 80; ++mt) tr->seq_base[mt] += (uint32_t)(cnt - 1);
+      for (int mt = 0; mt < (runs[i].n + 79) / 80; ++mt) tr->seq_base[mt] += (uint32_t)(cnt - 1);
     }
   }
 }
@@ -207,38 +207,17 @@ extern "C" int acez_train_group_step(acez_train_group* g, const int64_t* const* 
   }
   ACEZ_HIP_CHECK(hipSetDevice(g->m[0]->device));
   hipStream_t s = (hipStream_t)stream;
-  const TrainState* st[GROUP_MAX];
-  int nblk[GROUP_MAX];
-  const int64_t* nx[GROUP_MAX];
-  int nn[GROUP_MAX];
+  StepRun runs[GROUP_MAX];
   std::vector<int> chained;   // members whose chains can run as one-launch chains (seq_usable); the others take per-layer launches
   for (int i = 0; i < H; ++i) {
-    acez_trainer* tr = g->m[i];
-    nx[i] = (d_next && d_next[i] && n_next) ? d_next[i] : nullptr;
-    nn[i] = nx[i] ? n_next[i] : 0;
-    nblk[i] = (n[i] + 4 * tr->loss_rows - 1) / (4 * tr->loss_rows);
-    tr->last_n = n[i];
-    begin_batch(tr, d_indices[i], n[i], s);
-    st[i] = tr->st;
-    if (seq_usable(tr, n[i])) chained.push_back(i);
+    const int64_t* nx = (d_next && d_next[i] && n_next) ? d_next[i] : nullptr;
+    runs[i] = start_run(g->m[i], Flow::Fused, d_indices[i], n[i], nx, nx ? n_next[i] : 0, s);
+    if (seq_usable(g->m[i], n[i])) chained.push_back(i);
   }
-  // forward chains
-  if (!chained.empty()) launch_rowseq_group<false>(g, chained, n, st, s);
-  for (int i = 0; i < H; ++i)
-    if (!seq_usable(g->m[i], n[i])) launch_forward(g->m[i], g->m[i]->R[0], n[i], st[i], s);
-  const int f2 = 3 * (g->m[0]->nb + 1) + 1;
-  for (int i = 0; i < H; ++i) launch_train_loss(g->m[i], g->m[i]->out[f2], d_indices[i], n[i], nblk[i], s, true, nx[i], nn[i], false);
-  // input-gradient chains
-  if (!chained.empty()) launch_rowseq_group<true>(g, chained, n, st, s);
-  for (int i = 0; i < H; ++i)
-    if (!seq_usable(g->m[i], n[i])) launch_dgrad(g->m[i], n[i], st[i], s);
-  // weight gradients + optimiser + schedule: each member's own launches (acez_train_step_next's tail)
-  for (int i = 0; i < H; ++i) {
-    acez_trainer* tr = g->m[i];
-    launch_weight_grads(tr, n[i], nblk[i], st[i], s, true);
-    ACEZ_HIP_CHECK(hipGetLastError());
-    const int rc = train_update_impl(tr, stream, true, 0, -1, nx[i], nn[i]);
-    if (rc != ACEZ_OK) return rc;
-  }
-  return ACEZ_OK;
+  // each member's own step phases; only the GEMM chains of the chained members run as one launch for all of them
+  return run_steps(runs, H, [&](bool bwd) {
+    if (!chained.empty()) (bwd ? launch_rowseq_group<true> : launch_rowseq_group<false>)(g, chained, runs, s);
+    for (int i = 0; i < H; ++i)
+      if (!seq_usable(g->m[i], n[i])) launch_chain(runs[i], bwd);
+  });
 }

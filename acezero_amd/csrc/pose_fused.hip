@@ -18,8 +18,8 @@
 
 namespace acez {
 
-// T = images per pose workgroup: 16 = the v_mfma_f32_16x16x4_f32 bodies of pose_kernels.hip (256 threads), 8 / 4 = the small tiles of
-// pose_small.hip (T / 16 of the matrix time per layer, 16 / T times as many CUs, 512 threads; the default is 4). A launch's workgroups
+// T = images per pose workgroup: 16 = the v_mfma_f32_16x16x4_f32 bodies of pose_kernels.hip (256 threads), 4 = the small tiles of
+// pose_small.hip (a quarter of the matrix time per layer, four times as many CUs, 512 threads; the default). A launch's workgroups
 // all have pose_threads<T>() threads: in the launches shared with the optimiser its workgroups use the first 256 (the other waves
 // return at once), the gather's rows are spread over the waves there are.
 template <int T>
@@ -60,12 +60,6 @@ template <int T>
 __device__ __forceinline__ void pose_s1_tile(const PoseNetArgs& pn, const float* row_dT, const int* row_image, int n, int tile, char* smem) {
   if constexpr (T == 16) pose_s1_body(pn, row_dT, row_image, n, tile, smem);
   else pose4_s1_body<T>(pn, row_dT, row_image, n, tile, smem);
-}
-template <int T>
-__global__ __launch_bounds__(pose_threads<T>()) void pose_s1t_kernel(PoseNetArgs a, const float* row_dT, const int* row_image, int n) {
-  if (a.active && !*a.active) return;
-  __shared__ __attribute__((aligned(16))) char smem[pose_s1_smem_bytes<T>()];
-  pose_s1_tile<T>(a, row_dT, row_image, n, blockIdx.x, smem);
 }
 // stand-alone forward on small tiles (acez_trainer_get_poses, the split flow)
 template <int T>

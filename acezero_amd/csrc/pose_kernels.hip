@@ -755,11 +755,6 @@ __device__ __forceinline__ void pose_s1_body(const PoseNetArgs& a, const float* 
   __syncthreads();   // sDT complete; the hit values are dead, their area becomes the chain's tiles
   pose_mlp_bwd_body(a, tile, sDT, area, area + 12 * PN_IMG, area + (12 + 128) * PN_IMG);
 }
-__global__ __launch_bounds__(256) void pose_s1_kernel(PoseNetArgs a, const float* row_dT, const int* row_image, int n) {
-  if (a.active && !*a.active) return;
-  __shared__ __attribute__((aligned(16))) char smem[PS1_SMEM_BYTES];
-  pose_s1_body(a, row_dT, row_image, n, blockIdx.x, smem);
-}
 
 // torch.optim.AdamW on a small flat parameter vector with its own step counter; the gradient is the fixed-order
 // sum of `nz` partial vectors. Applied only when *enable != 0 (ace_trainer.py:634-636).
