@@ -399,41 +399,54 @@ def _train_from_images(opt):
     from .session import ReconstructionSession
     if opt.use_ace_pose_file is not None:
         files, poses, focals = read_ace_pose_file(opt.use_ace_pose_file, opt.ace_pose_file_conf_threshold)
-        files, frames, fscale = load_frames(None, opt.image_resolution, files=files)
+        files, frames, fscale = load_session_frames(None, opt.image_resolution, files=files)
     else:
-        files, frames, fscale = load_frames(opt.rgb_files, opt.image_resolution)
+        files, frames, fscale = load_session_frames(opt.rgb_files, opt.image_resolution)
         focals = []
         poses = np.stack([np.loadtxt(f) for f in sorted(glob.glob(opt.pose_files))]) if opt.pose_files is not None else None   # dataset_io.load_pose
-    depth = load_depth_maps(opt.depth_files, len(files), frames.shape[2:]) if opt.depth_files is not None else None
+    mixed = not torch.is_tensor(frames)                                  # a folder of several frame sizes: its size classes
     ids = list(range(len(files)))
     if opt.use_pose_seed >= 0:                                           # dataset.py:110-124
         ids, poses = [int(opt.use_pose_seed * len(files))], np.eye(4)[None]
-        if depth is None:
+        if opt.depth_files is None:
             raise SystemExit("--use_pose_seed needs --depth_files here (the reference's ZoeDepth fallback is a network download)")
     elif poses is None or len(poses) != len(files):
         raise SystemExit("need one pose per image: --use_ace_pose_file, --pose_files or --use_pose_seed")
-    H, W = frames.shape[2:]
-    if opt.use_external_focal_length is not None:
-        focal = opt.use_external_focal_length * fscale
-    elif opt.use_heuristic_focal_length or not focals:
-        focal = math.sqrt(W ** 2 + H ** 2) * 0.7
+    frame_focals = None
+    if mixed:                                                            # every frame's focal, converted with its own factor
+        frame_focals = initial_focals(frames, fscale, external=opt.use_external_focal_length, heuristic=opt.use_heuristic_focal_length,
+                                      file_focals=focals)
+        if opt.refine_calibration:
+            check_calibration_focals(frame_focals[ids])                  # before any frame is encoded
+        focal = float(frame_focals[0])
     else:
-        assert np.allclose(focals, focals[0]), "a single focal length is supported"
-        focal = focals[0] * fscale
+        H, W = frames.shape[2:]
+        if opt.use_external_focal_length is not None:
+            focal = opt.use_external_focal_length * fscale
+        elif opt.use_heuristic_focal_length or not focals:
+            focal = math.sqrt(W ** 2 + H ** 2) * 0.7
+        else:
+            assert np.allclose(focals, focals[0]), "a single focal length is supported"
+            focal = focals[0] * fscale
+    hw = frame_shapes(frames, len(files)) if mixed else frames.shape[2:]
+    depth = load_depth_maps(opt.depth_files, len(files), hw) if opt.depth_files is not None else None
     so = _session_options(opt, cooldown_iterations=opt.learning_rate_cooldown_iterations, use_external_focal_length=focal,
                           cooldown_threshold=opt.learning_rate_cooldown_trigger_percent_threshold)
-    ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, opt=so, depth=depth)
-    m = ses.map(ids, torch.from_numpy(np.asarray(poses, np.float64)), focal, iterations=opt.iterations, loss_type=opt.repro_loss_type,
+    ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, opt=so, depth=depth,
+                                focals=frame_focals)
+    m = ses.map(ids, torch.from_numpy(np.asarray(poses, np.float64)), ses.focal0 if mixed else focal, iterations=opt.iterations, loss_type=opt.repro_loss_type,
                 schedule=opt.learning_rate_schedule, lr_max=opt.learning_rate_max, refinement=opt.pose_refinement,
                 pose_wait=opt.pose_refinement_wait, refine_calibration=opt.refine_calibration,
                 load_weights=torch.load(opt.load_weights, map_location="cpu") if opt.load_weights is not None else None,
                 with_depth=opt.use_pose_seed >= 0 or opt.depth_files is not None, tag=opt.output_map_file.stem)
+    # each frame's focal back in its own original units
+    f_out = focals_in_original_units(m["focal"], ses.frel, fscale) if mixed else np.full(len(files), m["focal"] / fscale)
     opt.output_map_file.parent.mkdir(parents=True, exist_ok=True)
     torch.save(m["head"], opt.output_map_file)                           # save_model (ace_trainer.py:681-694)
     pose_file = opt.output_map_file.parent / f"poses_{opt.output_map_file.stem}_preliminary.txt"
     with open(pose_file, "w") as f:                                      # save_poses (ace_trainer.py:696-728)
         for j, i in enumerate(ids):
-            write_pose_line(f, files[i], np.vstack([m["poses_w2c"][j], [0, 0, 0, 1.0]]), float("inf"), m["focal"] / fscale)
+            write_pose_line(f, files[i], np.vstack([m["poses_w2c"][j], [0, 0, 0, 1.0]]), float("inf"), float(f_out[i]))
     _logger.info(f"Done without errors. {m['iterations']} iterations in {m['seconds']:.1f}s ({m['patches_per_s']:.0f} patches/s). "
                  f"Saved trained head weights to: {opt.output_map_file}; refined poses to: {pose_file}")
     return 0
@@ -561,62 +574,136 @@ def register_main(argv=None):
 
 
 # --------------------------------------------------------------------------------------------------------- ace_zero
-def load_frames(rgb_glob, image_resolution=480, files=None, return_rgb=False):
+def load_frames(rgb_glob, image_resolution=480, files=None, return_rgb=False, size_classes=False):
     """Minimal stand-in for CamLocDataset's image path without augmentation (dataset.py:189-195,227-237,146-160): decode,
     resize so that the short side is `image_resolution` (PIL bilinear, as torchvision does for PIL images), grey, normalise.
-    All frames must have one size (the session batches them). Returns (files, float32 [n,1,H,W], resize factor): focal lengths
-    on the command line and in pose files refer to the ORIGINAL image size and are multiplied by that factor (dataset.py:289-290)."""
+    Focal lengths on the command line and in pose files refer to the ORIGINAL image size and are multiplied by the frame's resize
+    factor (dataset.py:289-290). Every size class (frames of one resized shape) passes check_frame_size before any of its frames
+    is decoded.
+
+    Default: all frames must have one size. Returns (files, float32 [n,1,H,W], resize factor[, uint8 rgb [n,H,W,3]]).
+    size_classes=True: any mix of sizes (the reference's batch-size-1 loaders take one, dataset.py:278-417). Returns (files,
+    classes, factors[, rgb]): classes = [(positions in the sorted file list, float32 [k,1,H_c,W_c]), ...] in the order of their
+    first frame, factors = float64 [n] resize factor of every frame, rgb = a list of n uint8 [H_i,W_i,3] arrays -- what
+    ReconstructionSession takes for a folder of mixed sizes."""
     import glob
     import torch
     from PIL import Image
+    from .session import check_frame_size
     if files is None:
         files = sorted(glob.glob(rgb_glob))                             # dataset_io.get_files_from_glob sorts
     if not files:
         raise SystemExit(f"no files match {rgb_glob!r}")
-    frames, size, factor, rgbs = [], None, 1.0, []
-    for f in files:
-        im = Image.open(f).convert("RGB")
+    frames, factors, rgbs, shapes = [], [], [], {}
+    for i, f in enumerate(files):
+        im = Image.open(f)
         w, h = im.size
         sc = image_resolution / min(w, h)
         nw, nh = (image_resolution, int(h * sc)) if w <= h else (int(w * sc), image_resolution)
-        small = im.resize((nw, nh), Image.BILINEAR)
+        if (nh, nw) not in shapes:
+            if shapes and not size_classes:
+                size = next(iter(shapes))
+                raise SystemExit(f"{f}: resized frame is {(nh, nw)}, the first one {size}: frames of ONE size were expected (load_frames("
+                                 "size_classes=True) takes a mix; the entry points do)")
+            try:
+                check_frame_size(nh, nw)                                 # before the class's frames are decoded
+            except RuntimeError as e:
+                raise SystemExit(str(e))
+            shapes[(nh, nw)] = []
+        shapes[(nh, nw)].append(i)
+        small = im.convert("RGB").resize((nw, nh), Image.BILINEAR)
         g = np.asarray(small.convert("L"), np.float32) / 255.0
         if return_rgb:
             rgbs.append(np.asarray(small, np.uint8))
-        if size is None:
-            size = g.shape
-            from .session import check_frame_size
-            try:
-                check_frame_size(*size)                                  # before the other frames are decoded
-            except RuntimeError as e:
-                raise SystemExit(str(e))
-        elif g.shape != size:
-            raise SystemExit(f"{f}: resized frame is {g.shape}, the first one {size}: the in-process mapping session batches frames of ONE "
-                             "size (register_mapping.py handles folders of mixed sizes, one context per size class; the reference's "
-                             "batch-size-1 loaders accept them everywhere): crop or pad the images to a common aspect ratio for mapping")
         frames.append((g - 0.4) / 0.25)
-        factor = sc
-    if return_rgb:
-        return files, torch.from_numpy(np.stack(frames)[:, None]), factor, np.stack(rgbs)
-    return files, torch.from_numpy(np.stack(frames)[:, None]), factor
+        factors.append(sc)
+    if not size_classes:
+        out = (files, torch.from_numpy(np.stack(frames)[:, None]), factors[-1])
+        return out + (np.stack(rgbs),) if return_rgb else out
+    classes = [(np.array(pos, np.int64), torch.from_numpy(np.stack([frames[i] for i in pos])[:, None])) for pos in shapes.values()]
+    out = (files, classes, np.array(factors, np.float64))
+    return out + (rgbs,) if return_rgb else out
+
+
+def load_session_frames(rgb_glob, image_resolution=480, files=None, return_rgb=False):
+    """load_frames for the entry points: a folder of one size comes back exactly as load_frames returns it (files, [n,1,H,W],
+    resize factor[, rgb [n,H,W,3]]), a folder of mixed sizes as load_frames(size_classes=True) returns it (files, classes, per-frame
+    factors[, per-frame rgb list])."""
+    out = load_frames(rgb_glob, image_resolution, files=files, return_rgb=return_rgb, size_classes=True)
+    if len(out[1]) > 1:
+        return out
+    files, classes, factors = out[:3]
+    one = (files, classes[0][1], float(factors[-1]))
+    return one + (np.stack(out[3]),) if return_rgb else one
+
+
+def initial_focals(frames, factors, external=None, heuristic=False, file_focals=None):
+    """Per-frame initial focal lengths in resized pixels of a folder of size classes (`frames`, `factors` as load_frames(size_classes=True)
+    returns them): an external focal or the pose file's focals (original-image pixels) times the frame's factor (dataset.py:289-290),
+    else 70% of the resized frame's diagonal (dataset.py:269-274)."""
+    n = len(factors)
+    out = np.zeros(n, np.float64)
+    for pos, t in frames:
+        h, w = t.shape[2:]
+        for i in pos:
+            if external is not None and external > 0:
+                out[i] = external * factors[i]
+            elif heuristic or file_focals is None or not len(file_focals):
+                out[i] = math.sqrt(w ** 2 + h ** 2) * 0.7
+            else:
+                out[i] = file_focals[i] * factors[i]
+    return out
+
+
+def focals_in_original_units(focal, frel, factors):
+    """Per-frame focal lengths for pose files, in each frame's ORIGINAL-image pixels: the session's nominal focal x the frame's ratio
+    (ReconstructionSession.frel), divided by the frame's resize factor (dataset.py:289-290 the other way round)."""
+    return focal * np.asarray(frel, np.float64) / np.asarray(factors, np.float64)
+
+
+def check_single_focal(focals_original):
+    """ace_zero.py:301-302 hands ONE focal (original-image pixels) from round to round and asserts that every frame has it."""
+    if not np.allclose(focals_original, focals_original[0]):
+        raise SystemExit("ace_zero.py supports a single focal length (ace_zero.py:301-302): the frames' focal lengths differ in original-image "
+                         "pixels (pass --use_external_focal_length, or map the frames of each camera separately)")
+
+
+def check_calibration_focals(focals):
+    """refine_calibration.py:14-15: calibration refinement learns ONE focal; every frame must start from the same one."""
+    if not np.allclose(focals, focals[0]):
+        raise SystemExit("All images must have the same focal length for calibration refinement")
 
 
 def load_depth_maps(depth_glob, n, frame_hw):
     """--depth_files (dataset.py:299-304,333,359): 16-bit millimetres -> metres, nearest resize to the frame, value at the
-    feature-map pixel centres (offset 4, stride 8). Returns float32 [n, ceil(H/8), ceil(W/8)]."""
+    feature-map pixel centres (offset 4, stride 8). frame_hw = (H, W) of every frame: float32 [n, ceil(H/8), ceil(W/8)]; or a list
+    of n per-frame (H_i, W_i) (a folder of mixed sizes): a list of n float32 [ceil(H_i/8), ceil(W_i/8)] maps."""
     import glob
     import torch
     from PIL import Image
     files = sorted(glob.glob(depth_glob))
     if len(files) != n:
         raise SystemExit(f"{len(files)} depth files for {n} images")
-    H, W = frame_hw
-    out = np.zeros((n, (H + 7) // 8, (W + 7) // 8), np.float32)
-    for i, f in enumerate(files):
+
+    def one(f, H, W):
         d = np.asarray(Image.open(f).resize((W, H), Image.NEAREST), np.float32) / 1000.0
         sub = d[4::8, 4::8]
-        out[i, :sub.shape[0], :sub.shape[1]] = sub
-    return torch.from_numpy(out)
+        out = np.zeros(((H + 7) // 8, (W + 7) // 8), np.float32)
+        out[:sub.shape[0], :sub.shape[1]] = sub
+        return out
+    if isinstance(frame_hw, list):
+        return [torch.from_numpy(one(f, int(h), int(w))) for f, (h, w) in zip(files, frame_hw)]
+    H, W = frame_hw
+    return torch.from_numpy(np.stack([one(f, H, W) for f in files]) if n else np.zeros((0, (H + 7) // 8, (W + 7) // 8), np.float32))
+
+
+def frame_shapes(frames, n):
+    """(H, W) of every frame of a folder of size classes."""
+    hw = [None] * n
+    for pos, t in frames:
+        for i in pos:
+            hw[i] = tuple(t.shape[2:])
+    return hw
 
 
 def ace_zero_main(argv=None):
@@ -636,33 +723,43 @@ def ace_zero_main(argv=None):
             raise SystemExit("--export_point_cloud True runs on one GPU: export from the written pose file with export_point_cloud.py")
     logging.basicConfig(level=logging.INFO if rank == 0 else logging.WARNING)
     opt.results_folder.mkdir(parents=True, exist_ok=True)
-    files, frames, fscale, rgb = load_frames(opt.rgb_files, opt.image_resolution, return_rgb=True)
-    depth = load_depth_maps(opt.depth_files, len(files), frames.shape[2:]) if opt.depth_files is not None else None
+    files, frames, fscale, rgb = load_session_frames(opt.rgb_files, opt.image_resolution, return_rgb=True)
+    mixed = not torch.is_tensor(frames)                                  # a folder of several frame sizes: its size classes
+    frame_focals = None
+    if mixed:
+        frame_focals = initial_focals(frames, fscale, external=opt.use_external_focal_length)
+        if opt.refine_calibration:
+            check_calibration_focals(frame_focals)                       # before any frame is encoded
+        check_single_focal(frame_focals / fscale)
+    hw = frame_shapes(frames, len(files)) if mixed else frames.shape[2:]
+    depth = load_depth_maps(opt.depth_files, len(files), hw) if opt.depth_files is not None else None
     if depth is None and opt.seed_network is None:
         raise SystemExit("ace_zero.py (MI355X): seeds need --depth_files (or --seed_network); the reference's ZoeDepth fallback is a "
                          "network download and not part of this package")
     known = vars(default_options())
     over = {k: v for k, v in vars(opt).items() if k in known and k != "seed_network"}
     if opt.use_external_focal_length > 0:
-        over["use_external_focal_length"] = opt.use_external_focal_length * fscale
+        over["use_external_focal_length"] = float(frame_focals[0]) if mixed else opt.use_external_focal_length * fscale
     if opt.seed_network is not None:
         over["seed_network"] = torch.load(opt.seed_network, map_location="cpu")
-    ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, opt=default_options(**over), depth=depth)
+    ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, opt=default_options(**over), depth=depth,
+                                focals=frame_focals)
+    # pose files: every frame's focal in its own original units (one focal, the session's nominal one, goes from round to round)
+    orig = (lambda f: focals_in_original_units(f, ses.frel, fscale)) if mixed else (lambda f: f / fscale)
     res = ses.reconstruct()   # (seed trials one after the other: side by side is not faster here)
     if rank != 0:                                                       # every rank holds the same result; rank 0 writes it
         import torch.distributed as dist
         dist.barrier()
         return 0
     for h in res["history"]:                                            # the files ace_zero.py leaves behind (SURVEY 8b "process/file contract")
-        write_pose_file(opt.results_folder / f"poses_{h['id']}.txt", files, h["poses"], h["confidence"], h["focal"] / fscale)
+        write_pose_file(opt.results_folder / f"poses_{h['id']}.txt", files, h["poses"], h["confidence"], orig(h["focal"]))
         torch.save(h["head"], opt.results_folder / f"{h['id']}.pt")
         _logger.info(f"{h['id']}: registered {h['registration_rate'] * 100:.1f}% of the images")
-    write_pose_file(opt.results_folder / "poses_final.txt", files, res["poses"], res["confidence"], res["focal"] / fscale)
+    write_pose_file(opt.results_folder / "poses_final.txt", files, res["poses"], res["confidence"], orig(res["focal"]))
     if opt.export_point_cloud:
         from .pointcloud import write_point_cloud
         xyz, src, sel = res["point_cloud"]
-        f, p = np.divmod(src.astype(np.int64), ses.hw)
-        write_point_cloud(opt.results_folder / "pc_final.ply", xyz, source_colours(rgb, sel[f], p, ses.ow))
+        write_point_cloud(opt.results_folder / "pc_final.ply", xyz, point_colours(ses, rgb, src, sel))
     rates = [float((res["confidence"] > t).mean()) for t in (500, 1000, 2000, 4000)]
     _logger.info(f"Reconstructed in {res['seconds'] / 60:.1f} minutes, {res['iterations']} iterations; "
                  "registration rate @500/@1000/@2000/@4000: " + " ".join(f"{r * 100:.1f}%" for r in rates))
@@ -675,11 +772,27 @@ def ace_zero_main(argv=None):
 # ------------------------------------------------------------------------------------------------ export_point_cloud
 def source_colours(rgb_nhw3, frame_of_point, pixel_of_point, map_w):
     """Colour of every kept map pixel: the image value at its centre (nearest-neighbour sub-sampling with offset 4, stride 8,
-    ace_vis_util.py:566-570), as 0..255 floats."""
+    ace_vis_util.py:566-570), as 0..255 floats. rgb_nhw3: [n,H,W,3], or a list of n [H_i,W_i,3] frames with map_w per point."""
     y, x = np.divmod(pixel_of_point.astype(np.int64), map_w)
-    yy = np.minimum(y * 8 + 4, rgb_nhw3.shape[1] - 1)
-    xx = np.minimum(x * 8 + 4, rgb_nhw3.shape[2] - 1)
-    return rgb_nhw3[frame_of_point, yy, xx].astype(np.float64)
+    if not isinstance(rgb_nhw3, list):
+        yy = np.minimum(y * 8 + 4, rgb_nhw3.shape[1] - 1)
+        xx = np.minimum(x * 8 + 4, rgb_nhw3.shape[2] - 1)
+        return rgb_nhw3[frame_of_point, yy, xx].astype(np.float64)
+    out = np.zeros((len(frame_of_point), 3), np.float64)
+    for fr in np.unique(frame_of_point):
+        at = np.flatnonzero(frame_of_point == fr)
+        img = rgb_nhw3[int(fr)]
+        out[at] = img[np.minimum(y[at] * 8 + 4, img.shape[0] - 1), np.minimum(x[at] * 8 + 4, img.shape[1] - 1)]
+    return out
+
+
+def point_colours(ses, rgb, src, sel):
+    """source_colours of ReconstructionSession.point_cloud's points."""
+    if len(ses.classes) == 1:
+        f, p = np.divmod(src.astype(np.int64), ses.hw)
+        return source_colours(rgb, sel[f], p, ses.ow)
+    frame, p, ow = ses.source_pixels(src, sel)
+    return source_colours(rgb, frame, p, ow)
 
 
 def export_point_cloud_main(argv=None):
@@ -706,16 +819,21 @@ def export_point_cloud_main(argv=None):
         files, c2w, focals = read_ace_pose_file(opt.pose_file, opt.confidence_threshold)
         if not files:
             raise SystemExit("no pose above the confidence threshold")
-        assert np.allclose(focals, focals[0]), "a single focal length is supported"
-        files, frames, fscale, rgb = load_frames(None, opt.image_resolution, files=files, return_rgb=True)
-        so = default_options(use_external_focal_length=focals[0] * fscale, use_aug=False, registration_confidence=opt.confidence_threshold,
+        files, frames, fscale, rgb = load_session_frames(None, opt.image_resolution, files=files, return_rgb=True)
+        frame_focals = None
+        if torch.is_tensor(frames):
+            assert np.allclose(focals, focals[0]), "a single focal length is supported"
+            f0 = focals[0] * fscale
+        else:                                                            # mixed sizes: every frame's focal with its own factor
+            frame_focals = initial_focals(frames, fscale, file_focals=focals)
+            f0 = float(frame_focals[0])
+        so = default_options(use_external_focal_length=f0, use_aug=False, registration_confidence=opt.confidence_threshold,
                              compute_dtype=opt.compute_dtype)
-        ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, opt=so)
+        ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, opt=so, focals=frame_focals)
         conf = np.full(len(files), np.inf)
         xyz, src, sel = ses.point_cloud(torch.load(opt.network, map_location="cpu"), c2w, conf, ses.focal0, dense=opt.dense_point_cloud,
                                         filter_depth=100, opengl=opt.convention == "opengl")
-        f, p = np.divmod(src.astype(np.int64), ses.hw)
-        clr = source_colours(rgb, sel[f], p, ses.ow)
+        clr = point_colours(ses, rgb, src, sel)
     write_point_cloud(opt.output_file, xyz, clr)
     _logger.info(f"Done. Wrote point cloud to: {opt.output_file}")
     return 0

@@ -1495,14 +1495,13 @@ __device__ __forceinline__ uint32_t sample_draw(uint64_t seed, uint64_t view_id,
 
 constexpr int SAMPLE_MAX_HW = 24576;   // feature-map pixels per view the LDS prefix array holds (e.g. 128 x 192)
 
-__global__ __launch_bounds__(256) void sample_views_kernel(const uint16_t* __restrict__ feat, const uint8_t* __restrict__ mask, int hw, int ow,
-                                                           int channels, int samples, uint64_t seed, uint64_t first_view_id,
-                                                           int view_index_base, uint16_t* __restrict__ out_feat, float* __restrict__ out_px,
-                                                           int32_t* __restrict__ out_view, int32_t* __restrict__ out_pix) {
-  __shared__ uint16_t pref[SAMPLE_MAX_HW];   // inclusive count of valid pixels up to p (hw <= 24576 < 65536)
-  __shared__ int part[256];
-  const int v = blockIdx.x, t = threadIdx.x;
-  const uint8_t* mk = mask ? mask + (size_t)v * hw : nullptr;
+// One view of a sampling launch: `feat` points at the view's first feature row, `mk` at its mask (NULL: every pixel valid), v is
+// the view's position in the launch (keys its draws together with first_view_id and numbers its output rows).
+__device__ __forceinline__ void sample_one_view(uint16_t* pref, int* part, const uint16_t* __restrict__ feat, const uint8_t* __restrict__ mk,
+                                                int hw, int ow, int channels, int samples, uint64_t seed, uint64_t first_view_id, int v,
+                                                int view_index_base, uint16_t* __restrict__ out_feat, float* __restrict__ out_px,
+                                                int32_t* __restrict__ out_view, int32_t* __restrict__ out_pix) {
+  const int t = threadIdx.x;
   const int per = (hw + 255) / 256;
   const int lo = t * per, hi = min(hw, lo + per);
   int cnt = 0;
@@ -1538,7 +1537,7 @@ __global__ __launch_bounds__(256) void sample_views_kernel(const uint16_t* __res
     }
     const int pix = a;
     const size_t dst = (size_t)v * samples + s;
-    const uint16_t* src = feat + ((size_t)v * hw + pix) * channels;
+    const uint16_t* src = feat + (size_t)pix * channels;
     for (int c = lane * 8; c < channels; c += 512)
       *reinterpret_cast<uint4*>(out_feat + dst * channels + c) = *reinterpret_cast<const uint4*>(src + c);
     if (lane == 0) {
@@ -1549,6 +1548,38 @@ __global__ __launch_bounds__(256) void sample_views_kernel(const uint16_t* __res
       if (out_pix) out_pix[dst] = pix;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void sample_views_kernel(const uint16_t* __restrict__ feat, const uint8_t* __restrict__ mask, int hw, int ow,
+                                                           int channels, int samples, uint64_t seed, uint64_t first_view_id,
+                                                           int view_index_base, uint16_t* __restrict__ out_feat, float* __restrict__ out_px,
+                                                           int32_t* __restrict__ out_view, int32_t* __restrict__ out_pix) {
+  __shared__ uint16_t pref[SAMPLE_MAX_HW];   // inclusive count of valid pixels up to p (hw <= 24576 < 65536)
+  __shared__ int part[256];
+  const int v = blockIdx.x;
+  sample_one_view(pref, part, feat + (size_t)v * hw * channels, mask ? mask + (size_t)v * hw : nullptr, hw, ow, channels, samples, seed,
+                  first_view_id, v, view_index_base, out_feat, out_px, out_view, out_pix);
+}
+
+// The same draws for views of any sizes in one launch, read in place from a resident feature store: view v's map starts at row
+// table[v].row of `feat`, is table[v].map_h x table[v].map_w, and its mask starts at byte table[v].mask of `mask` (< 0: no mask).
+// A view whose map would not fit max_hw (<= SAMPLE_MAX_HW), the n_rows of the store or the mask_bytes of the masks is skipped
+// rather than read out of bounds (the host never builds one).
+__global__ __launch_bounds__(256) void sample_views_table_kernel(const uint16_t* __restrict__ feat, int64_t n_rows, const uint8_t* __restrict__ mask,
+                                                                 int64_t mask_bytes, const int64_t* __restrict__ table, int max_hw, int channels, int samples,
+                                                                 uint64_t seed, uint64_t first_view_id, int view_index_base,
+                                                                 uint16_t* __restrict__ out_feat, float* __restrict__ out_px,
+                                                                 int32_t* __restrict__ out_view, int32_t* __restrict__ out_pix) {
+  __shared__ uint16_t pref[SAMPLE_MAX_HW];
+  __shared__ int part[256];
+  const int v = blockIdx.x;
+  const int64_t row = table[v * 4 + 0], mh = table[v * 4 + 1], mw = table[v * 4 + 2], moff = table[v * 4 + 3];
+  // (uniform over the workgroup: no barrier is skipped by part of it)
+  if (row < 0 || mh <= 0 || mw <= 0 || mh * mw > max_hw || row + mh * mw > n_rows) return;
+  if (mask && moff >= 0 && moff + mh * mw > mask_bytes) return;
+  const int hw = (int)(mh * mw);
+  sample_one_view(pref, part, feat + (size_t)row * channels, (mask && moff >= 0) ? mask + moff : nullptr, hw, (int)mw, channels, samples, seed,
+                  first_view_id, v, view_index_base, out_feat, out_px, out_view, out_pix);
 }
 
 }  // namespace acez
@@ -1801,6 +1832,32 @@ extern "C" int acez_buffer_sample_views(const void* d_view_features, const uint8
   hipLaunchKernelGGL(sample_views_kernel, dim3(n_views, split), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)d_view_features, d_masks, hw, map_w,
                      channels, samples_per_view, seed, first_view_id, (int)view_index_base, (uint16_t*)d_out_features, d_out_target_px,
                      d_out_view_idx, d_out_pixel);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}
+
+extern "C" int acez_buffer_sample_views_table(const void* d_features, int64_t n_feature_rows, const uint8_t* d_masks, int64_t mask_bytes,
+                                              const int64_t* d_view_table, int n_views, int max_hw, int channels, int samples_per_view, uint64_t seed, uint64_t first_view_id,
+                                              int32_t view_index_base, void* d_out_features, float* d_out_target_px,
+                                              int32_t* d_out_view_idx, int32_t* d_out_pixel, void* stream) {
+  ACEZ_REQUIRE(d_features && d_view_table && d_out_features && d_out_target_px && d_out_view_idx, "null pointer");
+  ACEZ_REQUIRE(n_views > 0 && max_hw > 0 && samples_per_view > 0 && n_feature_rows > 0, "bad shape");
+  ACEZ_REQUIRE(!d_masks || mask_bytes > 0, "mask_bytes must give the size of d_masks");
+  ACEZ_REQUIRE(max_hw <= SAMPLE_MAX_HW, "feature map too large for the sampling kernel (24576 pixels)");
+  ACEZ_REQUIRE(channels > 0 && channels % 8 == 0, "channels must be a multiple of 8");
+  {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+      (void)hipGetLastError();
+      acez::set_error("no HIP device visible: buffer sampling runs on a gfx950 GPU (there is no CPU fallback)");
+      return ACEZ_ERR_NODEVICE;
+    }
+  }
+  int split = (samples_per_view + 255) / 256;   // as acez_buffer_sample_views: ~256 samples per workgroup
+  if (split > 64) split = 64;
+  hipLaunchKernelGGL(sample_views_table_kernel, dim3(n_views, split), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)d_features, n_feature_rows,
+                     d_masks, mask_bytes, d_view_table, max_hw, channels, samples_per_view, seed, first_view_id, (int)view_index_base, (uint16_t*)d_out_features,
+                     d_out_target_px, d_out_view_idx, d_out_pixel);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
 }

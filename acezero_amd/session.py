@@ -178,9 +178,16 @@ def view_depth(depth_11hw, grid, oh, ow):
 
 
 class ReconstructionSession:
-    def __init__(self, encoder_state_dict, images, opt=None, depth=None, device=None, chunk=64, group=None):
+    def __init__(self, encoder_state_dict, images, opt=None, depth=None, device=None, chunk=64, group=None, focals=None):
         """images [n,1,H,W] float32 normalised (dataset.py:150-153), any device; depth [n,H/8,W/8] camera z at the feature-map
         pixel centres (metres, 0 = invalid) or None -- only the seed images' maps are read.
+
+        A folder of mixed frame sizes (the reference's batch-size-1 loaders take any mix, dataset.py:278-417) comes as its size classes:
+        images = [(positions, [k,1,H_c,W_c]), ...], the positions of every class's frames in the whole list (together 0 .. n-1); depth
+        is then a list of n per-frame maps [H_i/8, W_i/8] (or None). Each class keeps its own output size and principal point, each
+        frame its own focal: focals = per-frame initial focal lengths in resized pixels (default: --use_external_focal_length, else
+        70% of the frame's diagonal). A focal handed to map / register / point_cloud is the NOMINAL one, frame 0's: frame i uses
+        focal * self.frel[i] (all 1 when the frames share one focal, as calibration refinement requires).
 
         Under torch.distributed (one process per GPU, `torchrun ace_zero.py ...`) every rank holds all normalised frames (1.2 MB
         each) but encodes and caches the features of ITS frames only (frame i -> rank i % world, parallel.frames_of_rank):
@@ -190,57 +197,109 @@ class ReconstructionSession:
         if not torch.cuda.is_available():
             raise RuntimeError("ReconstructionSession needs a GPU: every stage is a HIP kernel (no CPU fallback)")
         self.opt = opt or default_options()
-        n, _, H, W = images.shape
-        self.n, self.H, self.W = int(n), int(H), int(W)
-        check_frame_size(int(H), int(W))                                 # before any frame is encoded
+        parts = [(np.arange(images.shape[0]), images)] if torch.is_tensor(images) else [(np.asarray(p, np.int64).reshape(-1), t) for p, t in images]
+        n = sum(len(p) for p, _ in parts)
+        if sorted(int(i) for p, _ in parts for i in p) != list(range(n)):
+            raise ValueError("the size classes' positions must cover 0 .. n-1 once each")
+        for _, t in parts:
+            check_frame_size(int(t.shape[2]), int(t.shape[3]))           # before any frame is encoded
+        self.n = int(n)
+        H, W = max(int(t.shape[2]) for _, t in parts), max(int(t.shape[3]) for _, t in parts)
         amax = float(self.opt.aug_scale) if self.opt.use_aug else 1.0
         self.enc = Encoder.from_state_dict(encoder_state_dict, max_frames=chunk, max_h=int(math.ceil(H * amax)) + 8,
                                            max_w=int(math.ceil(W * amax)) + 8, device=device, dtype=getattr(self.opt, "compute_dtype", None))
         self.dtype = self.enc.dtype                                      # one operand format for the encoder, the cached features and every head
         self.dev = self.enc.device
-        self.images = images.to(self.dev, torch.float32).contiguous()    # 1.2 MB per 480x640 frame: resident for the augmented passes
+        # size classes: frames of one resized shape, with their output size and principal point (dataset.py:411-412)
+        self.classes = []
+        self.frame_class, self.frame_local = np.zeros(self.n, np.int64), np.zeros(self.n, np.int64)
+        for ci, (pos, t) in enumerate(parts):
+            h, w = int(t.shape[2]), int(t.shape[3])
+            oh, ow = output_size(h, w)
+            self.classes.append(SimpleNamespace(ids=pos, H=h, W=w, oh=oh, ow=ow, hw=oh * ow, ppx=w / 2.0, ppy=h / 2.0,
+                                                images=t.to(self.dev, torch.float32).contiguous()))   # 1.2 MB per 480x640 frame: resident for the augmented passes
+            self.frame_class[pos], self.frame_local[pos] = ci, np.arange(len(pos))
+        one = self.classes[0] if len(self.classes) == 1 else None        # a folder of one size: the attributes of that size
+        self.H, self.W, self.oh, self.ow, self.hw = (one.H, one.W, one.oh, one.ow, one.hw) if one else (None,) * 5
+        self.ppx, self.ppy, self.images = (one.ppx, one.ppy, one.images) if one else (None,) * 3
         self._aug_rng = np.random.default_rng(self.opt.base_seed + 77)
-        self.oh, self.ow = output_size(H, W)
-        self.hw = self.oh * self.ow
         self.group = group
         self.rank, self.world = rank_world(group)
         if self.rank:   # data-parallel fills draw their augmentations / sample positions from per-rank streams (rank 0: the single-process one),
             self._aug_rng = np.random.default_rng([self.opt.base_seed + 77, self.rank])   # so the shards' views are not copies of one sequence
-        self.owned = np.arange(self.rank, self.n, self.world)            # parallel.frames_of_rank; local slot of frame g: g // world
-        self.features = torch.empty((len(self.owned), self.hw, self.enc.out_channels), dtype=self.enc.feature_dtype, device=self.dev)
+        self.owned = np.arange(self.rank, self.n, self.world)            # parallel.frames_of_rank
+        # resident features: ONE flat [sum of the owned frames' h*w, C] store, class after class; frame g's map starts at row feat_row[g]
+        self.feat_row = np.full(self.n, -1, np.int64)
+        rows = 0
+        for c in self.classes:
+            c.owned = c.ids[c.ids % self.world == self.rank]
+            c.row0 = rows
+            self.feat_row[c.owned] = rows + np.arange(len(c.owned)) * c.hw
+            rows += len(c.owned) * c.hw
+        C = self.enc.out_channels
+        self.features = torch.empty((rows, C), dtype=self.enc.feature_dtype, device=self.dev)
         t0 = time.time()
-        own = torch.from_numpy(self.owned).to(self.dev)
-        for c0 in range(0, len(self.owned), chunk):
-            c1 = min(len(self.owned), c0 + chunk)
-            self.enc.features_rows(self.images[own[c0:c1]], out=self.features[c0:c1].view(-1, self.enc.out_channels))
+        for c in self.classes:                                           # one encoder pass per class and chunk
+            own = torch.from_numpy(self.frame_local[c.owned]).to(self.dev)
+            for c0 in range(0, len(c.owned), chunk):
+                c1 = min(len(c.owned), c0 + chunk)
+                self.enc.features_rows(c.images[own[c0:c1]], out=self.features[c.row0 + c0 * c.hw:c.row0 + c1 * c.hw])
         torch.cuda.synchronize(self.dev)
-        self.depth = None if depth is None else depth.to(self.dev, torch.float32)
-        f_ext = float(self.opt.use_external_focal_length)
-        self.focal0 = f_ext if f_ext > 0 else math.sqrt(W ** 2 + H ** 2) * 0.7           # dataset.py:269-274
-        self.ppx, self.ppy = W / 2.0, H / 2.0                                            # dataset.py:411-412
+        if depth is None:
+            self.depth = None
+        elif torch.is_tensor(depth):
+            self.depth = depth.to(self.dev, torch.float32)
+        else:                                                            # one map per frame, at its own feature resolution
+            self.depth = [None if d is None else torch.as_tensor(d).to(self.dev, torch.float32) for d in depth]
+        if focals is not None:
+            f0 = np.asarray(focals, np.float64).reshape(-1)
+            if len(f0) != self.n:
+                raise ValueError(f"{len(f0)} focal lengths for {self.n} frames")
+        else:
+            f_ext = float(self.opt.use_external_focal_length)
+            diag = [math.sqrt(c.W ** 2 + c.H ** 2) * 0.7 for c in self.classes]          # dataset.py:269-274
+            f0 = np.array([f_ext if f_ext > 0 else diag[k] for k in self.frame_class], np.float64)
+        self.focal0 = float(f0[0])
+        self.frel = f0 / f0[0]                                           # frame i's focal = nominal focal * frel[i]
         self.history = []
         self._views_sampled = 0
         # where a reconstruction's wall-clock goes (reconstruct() returns it): encoding the frames once, buffer creation / training loop of
         # the mapping rounds, registration passes
         self.timings = {"encode_s": time.time() - t0, "buffer_s": 0.0, "loop_s": 0.0, "register_s": 0.0}
-        _logger.info(f"Encoded {len(self.owned)} of {self.n} frames in {time.time() - t0:.2f}s (rank {self.rank} of {self.world}); "
-                     f"features resident: {self.features.numel() * 2 / 2 ** 30:.2f} GiB")
+        _logger.info(f"Encoded {len(self.owned)} of {self.n} frames ({len(self.classes)} size class{'es' if len(self.classes) > 1 else ''}) "
+                     f"in {time.time() - t0:.2f}s (rank {self.rank} of {self.world}); features resident: {self.features.numel() * 2 / 2 ** 30:.2f} GiB")
 
-    def _slots(self, frame_ids):
-        """Positions in self.features of frames this rank owns."""
+    def _rows(self, frame_ids):
+        """First feature row of each of the given frames (this rank must own them)."""
         ids = np.asarray(frame_ids, np.int64)
         if np.any(ids % self.world != self.rank):
             raise ValueError("frame not owned by this rank")
-        return torch.from_numpy(ids // self.world).to(self.dev)
+        return self.feat_row[ids]
+
+    def source_pixels(self, src, sel):
+        """Decode point_cloud's `src` (row of a point's map pixel in the maps of the frames `sel`, one after the other): (frame ids,
+        map pixels y * ow + x, map widths), one per point."""
+        src = np.asarray(src, np.int64)
+        sel = np.asarray(sel, np.int64)
+        hw = np.array([self.classes[k].hw for k in self.frame_class[sel]], np.int64)
+        off = np.concatenate([[0], np.cumsum(hw)])
+        f = np.searchsorted(off, src, side="right") - 1
+        ow = np.array([self.classes[k].ow for k in self.frame_class[sel]], np.int64)
+        return sel[f], src - off[f], ow[f]
 
     # ------------------------------------------------------------------------------------------------ mapping (train_ace.py)
-    def _K(self, focal):
-        return torch.tensor([[focal, 0, self.ppx], [0, focal, self.ppy], [0, 0, 1.0]], dtype=torch.float32)
+    def _K(self, focal, frame=0):
+        c = self.classes[self.frame_class[frame]]
+        f = float(focal * self.frel[frame])
+        return torch.tensor([[f, 0, c.ppx], [0, f, c.ppy], [0, 0, 1.0]], dtype=torch.float32)
 
     def _fill_buffer(self, image_ids, poses_c2w, focal, with_depth, total=None):
-        """TrainerACE.create_training_buffer (ace_trainer.py:293-452) on cached features, views not augmented."""
+        """TrainerACE.create_training_buffer (ace_trainer.py:293-452) on cached features, views not augmented. The views are sampled
+        in place from the resident store (acez_buffer_sample_views_table: one launch per pass for views of any sizes, no copy of the
+        mapped feature maps)."""
         o = self.opt
-        ids = torch.as_tensor(list(image_ids), dtype=torch.long, device=self.dev)
+        ids_np = np.asarray([int(i) for i in image_ids], np.int64)
+        ids = torch.as_tensor(ids_np, dtype=torch.long, device=self.dev)
         m = len(ids)
         total = total if total is not None else min(o.max_training_buffer_size, o.max_dataset_passes * m * o.samples_per_image)
         C = self.enc.out_channels
@@ -248,11 +307,19 @@ class ReconstructionSession:
         px = torch.empty((total, 2), dtype=torch.float32, device=self.dev)
         vidx = torch.empty((total,), dtype=torch.int32, device=self.dev)
         pix = torch.empty((total,), dtype=torch.int32, device=self.dev)
-        src = self.features[self._slots(ids.cpu().numpy())].reshape(-1, C)   # one copy of the mapped images' feature maps
+        cls = [self.classes[k] for k in self.frame_class[ids_np]]
+        hw = np.array([c.hw for c in cls], np.int64)
+        # per view (view j of a pass = image j): first feature row, map size, mask offset (-1: every pixel valid)
+        table = np.stack([self._rows(ids_np), [c.oh for c in cls], [c.ow for c in cls],
+                          np.concatenate([[0], np.cumsum(hw)[:-1]]) if with_depth else np.full(m, -1)], axis=1).astype(np.int64)
+        table = torch.from_numpy(table).to(self.dev)
         mask = None
         if with_depth:                                                  # pixels without a depth are not sampled (dataset.py:384-386 zero them)
-            d = self.depth[ids]
-            mask = ((d > 0) & (d <= 1000)).to(torch.uint8).reshape(m, self.hw).contiguous()
+            if torch.is_tensor(self.depth):
+                d = self.depth[ids]
+                mask = ((d > 0) & (d <= 1000)).to(torch.uint8).reshape(-1).contiguous()
+            else:
+                mask = torch.cat([((self.depth[i] > 0) & (self.depth[i] <= 1000)).reshape(-1) for i in ids_np]).to(torch.uint8)
         filled, n_views = 0, 0
         while filled < total:
             v = min(m, (total - filled + o.samples_per_image - 1) // o.samples_per_image)
@@ -264,9 +331,10 @@ class ReconstructionSession:
                 ox = torch.empty((v * o.samples_per_image,), dtype=torch.int32, device=self.dev)
             else:
                 of, op, ov, ox = (t[filled:filled + take] for t in (feats, px, vidx, pix))
-            N.check(N.lib().acez_buffer_sample_views(_ptr(src), _ptr(mask) if mask is not None else None, v, self.oh, self.ow, C,
-                                                     o.samples_per_image, o.base_seed + 4095 + 7919 * self.rank, self._views_sampled, n_views, _ptr(of), _ptr(op),
-                                                     _ptr(ov), _ptr(ox), _stream()))
+            N.check(N.lib().acez_buffer_sample_views_table(_ptr(self.features), self.features.shape[0], _ptr(mask) if mask is not None else None,
+                                                           mask.numel() if mask is not None else 0, _ptr(table), v, int(hw[:v].max()), C,
+                                                           o.samples_per_image, o.base_seed + 4095 + 7919 * self.rank, self._views_sampled, n_views,
+                                                           _ptr(of), _ptr(op), _ptr(ov), _ptr(ox), _stream()))
             if take < v * o.samples_per_image:
                 feats[filled:], px[filled:], vidx[filled:], pix[filled:] = of[:take], op[:take], ov[:take], ox[:take]
             filled += take
@@ -275,15 +343,22 @@ class ReconstructionSession:
         view_image = torch.arange(n_views, dtype=torch.int32) % m        # pass p, view j -> image j
         poses_c2w = torch.as_tensor(poses_c2w, dtype=torch.float64).reshape(m, 4, 4)
         pose_inv = torch.linalg.inv(poses_c2w).to(torch.float32)
-        K = self._K(focal)
+        Ks = [self._K(focal, i) for i in ids_np]                        # per image: its class's principal point, its focal
+        Kinvs = [torch.linalg.inv(K) for K in Ks]
         buf = dict(features=feats, target_px=px, view_idx=vidx, view_aug_inv=torch.eye(4)[:3].repeat(n_views, 1, 1),
-                   view_K=K.repeat(n_views, 1, 1), view_Kinv=torch.linalg.inv(K).repeat(n_views, 1, 1), view_image=view_image,
+                   view_K=torch.stack(Ks)[view_image.long()], view_Kinv=torch.stack(Kinvs)[view_image.long()], view_image=view_image,
                    image_pose_inv=pose_inv)
         if with_depth:
             # ground-truth scene coordinates from depth (dataset.py:347-388): eye = ((x*8+4 - W/2) / f * d, (y*8+4 - H/2) / f * d, d)
             img = (vidx.long() % m)
-            d = self.depth[ids].reshape(m, self.hw)[img, pix.long()]
-            eye = torch.stack([(px[:, 0] - self.ppx) / focal * d, (px[:, 1] - self.ppy) / focal * d, d, torch.ones_like(d)], dim=1)
+            if len(self.classes) == 1:
+                d = self.depth[ids].reshape(m, self.hw)[img, pix.long()]
+                eye = torch.stack([(px[:, 0] - self.ppx) / focal * d, (px[:, 1] - self.ppy) / focal * d, d, torch.ones_like(d)], dim=1)
+            else:                                                        # per image: principal point, focal, depth-map offset
+                per = torch.tensor([[c.ppx, c.ppy, focal * self.frel[i]] for c, i in zip(cls, ids_np)], dtype=torch.float32, device=self.dev)[img]
+                doff = torch.from_numpy(np.concatenate([[0], np.cumsum(hw)[:-1]])).to(self.dev)
+                d = torch.cat([self.depth[i].reshape(-1) for i in ids_np])[doff[img] + pix.long()]
+                eye = torch.stack([(px[:, 0] - per[:, 0]) / per[:, 2] * d, (px[:, 1] - per[:, 1]) / per[:, 2] * d, d, torch.ones_like(d)], dim=1)
             buf["target_crds"] = torch.einsum("nij,nj->ni", poses_c2w.to(self.dev, torch.float32)[img][:, :3], eye)
         return buf
 
@@ -313,11 +388,14 @@ class ReconstructionSession:
 
     def _fill_buffer_augmented(self, image_ids, poses_c2w, focal, with_depth, total=None):
         """create_training_buffer with --use_aug True: every pass re-encodes a freshly augmented view of every mapped image and
-        samples it with its validity mask. The views of a pass are grouped by canvas size and processed in batches."""
+        samples it with its validity mask. The views of a pass are grouped by (size class, scale level) -- one canvas size -- and
+        processed in batches."""
         from .buffer import BufferBuilder
         o = self.opt
         ids = torch.as_tensor([int(i) for i in image_ids], dtype=torch.long)
         m = len(ids)
+        cls_of = self.frame_class[ids.numpy()]
+        local = torch.from_numpy(self.frame_local[ids.numpy()])          # positions in the class's frame table
         total = total if total is not None else min(o.max_training_buffer_size, o.max_dataset_passes * m * o.samples_per_image)
         bld = BufferBuilder(self.enc, capacity=total, samples_per_image=o.samples_per_image, seed=o.base_seed + 4095 + 7919 * self.rank + self._views_sampled)
         poses_c2w = torch.as_tensor(poses_c2w, dtype=torch.float64).reshape(m, 4, 4)
@@ -331,28 +409,39 @@ class ReconstructionSession:
         while not bld.full:
             rows_before = bld.n
             levels, scales, angles, jit = self._draw_augmentations(m)
-            for lv in np.unique(levels):
-                sel = np.flatnonzero(levels == lv)
+            for ci, lv in sorted(set(zip(cls_of.tolist(), levels.tolist()))):
+                c = self.classes[ci]
+                sel = np.flatnonzero((levels == lv) & (cls_of == ci))
                 scale = float(scales[sel[0]])
-                hs, ws = int(self.H * scale), int(self.W * scale)
-                f = focal * (hs / self.H)                                # dataset.py:289-290 scales the focal with the short side
-                K = torch.tensor([[f, 0, ws / 2.0], [0, f, hs / 2.0], [0, 0, 1.0]])
-                Kinv = torch.linalg.inv(K)
+                hs, ws = int(c.H * scale), int(c.W * scale)
+                # per view its focal, a Python float (dataset.py:289-290 scales the focal with the short side): K is built in float32 from
+                # it and inverted in float32, as for a folder of one size; per distinct focal of the group: (K, Kinv)
+                view_f = [float(focal * self.frel[int(ids[j])] * (hs / c.H)) for j in sel]
+                Ks = {f: None for f in view_f}
+                for f in Ks:
+                    K = torch.tensor([[f, 0, ws / 2.0], [0, f, hs / 2.0], [0, 0, 1.0]], dtype=torch.float32)
+                    Ks[f] = (K, torch.linalg.inv(K))
                 for c0 in range(0, len(sel), chunk):
                     if bld.full:
                         break
                     js = sel[c0:c0 + chunk]
                     b = len(js)
                     rot_inv = self._rot_inv(angles[js])
+                    fs = view_f[c0:c0 + chunk]
+                    if len(Ks) == 1:
+                        K, Kinv = next(iter(Ks.values()))
+                        Kb, Kinvb = K.repeat(b, 1, 1), Kinv.repeat(b, 1, 1)
+                    else:
+                        Kb, Kinvb = torch.stack([Ks[f][0] for f in fs]), torch.stack([Ks[f][1] for f in fs])
                     if not with_depth:
                         # one launch: warp + colour jitter + the mask at feature resolution (acez_buffer_warp_views); a rotation of at most
                         # aug_rotation degrees never empties the mask: no per-batch host synchronisation
-                        views, mask8 = warp_views_device(self.images, ids[js], scale, angles[js], None if jit is None else (jit[0][js], jit[1][js]),
+                        views, mask8 = warp_views_device(c.images, local[js], scale, angles[js], None if jit is None else (jit[0][js], jit[1][js]),
                                                          mask_hw=output_size(hs, ws))
-                        bld.add_views(views, mask8, rot_inv, pose_inv[js], K.repeat(b, 1, 1), Kinv.repeat(b, 1, 1), [int(j) for j in js],
+                        bld.add_views(views, mask8, rot_inv, pose_inv[js], Kb, Kinvb, [int(j) for j in js],
                                       check_empty=False, mask_at_feature_resolution=True)
                         continue
-                    views, masks, grid = warp_views(self.images[ids[js].to(self.dev)], scale, angles[js], None if jit is None else (jit[0][js], jit[1][js]))
+                    views, masks, grid = warp_views(c.images[local[js].to(self.dev)], scale, angles[js], None if jit is None else (jit[0][js], jit[1][js]))
                     # depth-supervised (seed) views: depth at the feature-map pixel centres through the same warp (dataset.py:331-334, order=0)
                     oh, ow = output_size(hs, ws)
                     for k, j in enumerate(js):
@@ -360,8 +449,9 @@ class ReconstructionSession:
                         dv = view_depth(self.depth[int(ids[j])][None, None], grid[k:k + 1], oh, ow)
                         valid = (dv > 0) & (dv <= 1000)
                         mk = torch.nn.functional.interpolate(masks[k:k + 1].float(), size=(oh, ow), mode="nearest")[0, 0] > 0
-                        took = bld.add_views(views[k:k + 1], (mk & valid).float()[None, None], rot_inv[k:k + 1], pose_inv[j:j + 1], K[None], Kinv[None],
-                                             [int(j)], want_pixels=True, mask_at_feature_resolution=True)
+                        f = fs[k]
+                        took = bld.add_views(views[k:k + 1], (mk & valid).float()[None, None], rot_inv[k:k + 1], pose_inv[j:j + 1], Ks[fs[k]][0][None],
+                                             Ks[fs[k]][1][None], [int(j)], want_pixels=True, mask_at_feature_resolution=True)
                         if took:
                             pix = bld.last_pixels[:took].long()
                             dd = dv[pix // ow, pix % ow]
@@ -425,6 +515,8 @@ class ReconstructionSession:
         t0 = time.time() if t0 is None else t0
         image_ids = [int(i) for i in image_ids]
         m = len(image_ids)
+        if refine_calibration and not np.allclose(self.frel[image_ids], self.frel[image_ids[0]]):
+            raise ValueError("All images must have the same focal length for calibration refinement")   # refine_calibration.py:14-15
         poses_c2w = torch.as_tensor(poses_c2w, dtype=torch.float32).reshape(-1, 4, 4)
         dp = (self.world > 1 and m >= self.world) if data_parallel is None else bool(data_parallel and self.world > 1)
         fill = self._fill_buffer_augmented if o.use_aug else self._fill_buffer
@@ -559,24 +651,30 @@ class ReconstructionSession:
 
     # ---------------------------------------------------------------------------------------- registration (register_mapping.py)
     def scene_coordinates(self, head_sd, frame_ids=None):
-        """Head.forward on the cached features of the given frames (default: every frame this rank owns): float32 [k,3,oh,ow] on
-        the device."""
+        """Head.forward on the cached features of the given frames (default: every frame this rank owns), all of one size class:
+        float32 [k,3,oh,ow] on the device."""
         ids = self.owned if frame_ids is None else np.asarray(frame_ids, np.int64)
         count = len(ids)
-        out = torch.empty((count, 3, self.oh, self.ow), dtype=torch.float32, device=self.dev)
+        if count and len(set(self.frame_class[ids].tolist())) > 1:
+            raise ValueError("scene_coordinates takes frames of one size class")
+        c = self.classes[self.frame_class[ids[0]] if count else 0]
+        out = torch.empty((count, 3, c.oh, c.ow), dtype=torch.float32, device=self.dev)
         if count == 0:
             return out
-        slots = self._slots(ids)
+        rows0 = self._rows(ids)
         nb = sum(1 for k in head_sd if k.endswith("c0.weight"))
         head = HeadTrainer(head_sd["mean"].float().view(3), num_head_blocks=nb, use_homogeneous=head_sd["fc3.weight"].shape[0] == 4,
-                           max_batch=min(count, 64) * self.hw, iterations=1, inference_only=True, device=self.dev.index,
+                           max_batch=min(count, 64) * c.hw, iterations=1, inference_only=True, device=self.dev.index,
                            dtype=self.dtype)   # self.features holds the encoder's 16-bit rows, handed over by raw pointer below
         head.load_state_dict(head_sd)
-        contiguous = bool(np.all(np.diff(slots.cpu().numpy()) == 1)) if count > 1 else True
+        contiguous = bool(np.all(np.diff(rows0) == c.hw)) if count > 1 else True
         for c0 in range(0, count, 64):
             c1 = min(count, c0 + 64)
-            rows = (self.features[int(slots[c0]):int(slots[c0]) + (c1 - c0)] if contiguous else self.features[slots[c0:c1]]).reshape(-1, self.enc.out_channels)
-            N.check(head.lib.acez_head_forward_maps(head._h, _ptr(rows), c1 - c0, self.oh, self.ow, _ptr(out[c0:c1]), _stream()))
+            if contiguous:
+                rows = self.features[int(rows0[c0]):int(rows0[c0]) + (c1 - c0) * c.hw]
+            else:
+                rows = self.features[(torch.from_numpy(rows0[c0:c1])[:, None] + torch.arange(c.hw)).reshape(-1).to(self.dev)]
+            N.check(head.lib.acez_head_forward_maps(head._h, _ptr(rows), c1 - c0, c.oh, c.ow, _ptr(out[c0:c1]), _stream()))
         torch.cuda.synchronize(self.dev)
         head.close()
         return out
@@ -589,9 +687,9 @@ class ReconstructionSession:
         under torch.manual_seed(base_seed) and stops after max_estimates frames (:122-147,256) -- a seeded permutation of the frame
         ids here (a different stream, the same law), NOT the first k frames of the sequence. Frames are sharded over the ranks
         (frame i -> rank i % world); the random stream of a frame is keyed by its id, so the result does not depend on the
-        partition, and one gather returns every frame's result to every rank. rng_ids: the ids that key the random streams, if
-        they are not the positions in this session (register_mapping.py on a folder of mixed frame sizes: one session per size
-        class, streams keyed by the position in the whole file list)."""
+        partition, and one gather returns every frame's result to every rank. Head and RANSAC run once per size class, with that
+        class's principal point and every frame's own focal (`focal` is the nominal one, see __init__). rng_ids: the ids that key
+        the random streams, if they are not the positions in this session."""
         o = self.opt
         if max_estimates <= 0 or max_estimates >= self.n:
             ids = np.arange(self.n)
@@ -601,14 +699,17 @@ class ReconstructionSession:
         self.registered_ids = ids
         t0 = time.time()
         mine = ids[ids % self.world == self.rank]
-        sc = self.scene_coordinates(head_sd, mine)
         prm = dict(hyps=o.ransac_iterations, thr=o.ransac_threshold, alpha=float(o.inlieralpha), max_reproj=float(o.maxpixelerror), sub=8, max_tries=max_tries)
-        if len(mine):
-            keys = [int(i) for i in mine] if rng_ids is None else [int(rng_ids[i]) for i in mine]
-            poses, inl, _ = dsacstar.register_batch(sc, [(focal, self.ppx, self.ppy)] * len(mine), prm, o.register_seed, keys, want_masks=False)
-            poses, inl = poses.cpu(), inl.cpu().to(torch.int32)
-        else:
-            poses, inl = torch.zeros(0, 4, 4), torch.zeros(0, dtype=torch.int32)
+        poses, inl = torch.zeros(len(mine), 4, 4), torch.zeros(len(mine), dtype=torch.int32)
+        for ci, c in enumerate(self.classes):
+            at = np.flatnonzero(self.frame_class[mine] == ci)
+            if len(at) == 0:
+                continue
+            sub = mine[at]
+            sc = self.scene_coordinates(head_sd, sub)
+            keys = [int(i) for i in sub] if rng_ids is None else [int(rng_ids[i]) for i in sub]
+            p_, i_, _ = dsacstar.register_batch(sc, [(focal * self.frel[i], c.ppx, c.ppy) for i in sub], prm, o.register_seed, keys, want_masks=False)
+            poses[at], inl[at] = p_.cpu(), i_.cpu().to(torch.int32)
         if self.world > 1:
             full_p, full_i = gather_registrations([int(i) for i in mine], poses, inl, self.n, self.group, expect=ids)
             poses, inl = full_p[ids], full_i[ids]
@@ -740,22 +841,41 @@ class ReconstructionSession:
 
     def point_cloud(self, head_sd, poses_c2w, confidence, focal, dense=False, filter_depth=100, opengl=False):
         """export_point_cloud.py:66-94 on the cached features of the registered frames (confidence > registration_confidence):
-        (xyz [N,3] float32, source [N] = position in the registered list * hw + map pixel). OpenCV convention by default, as
-        ace_zero.py requests it (--convention opencv, :398)."""
+        (xyz [N,3] float32, source [N] = row of the point's map pixel in the maps of the registered frames one after the other --
+        position * hw + map pixel when all have one size; source_pixels decodes it -- , the registered frame ids). One filter launch
+        per size class. OpenCV convention by default, as ace_zero.py requests it (--convention opencv, :398)."""
         from .pointcloud import filter_scene_coordinates
         sel = np.flatnonzero(np.asarray(confidence) >= self.opt.registration_confidence)   # load_dataset_ace keeps confidence >= threshold
         if self.world > 1:
             raise NotImplementedError("point-cloud export runs on one GPU (python export_point_cloud.py on the written pose file)")
-        sc = self.scene_coordinates(head_sd, sel)
-        pinv = torch.linalg.inv(torch.from_numpy(np.asarray(poses_c2w, np.float64)[sel])).to(torch.float32)
-        K = self._K(focal).repeat(len(sel), 1, 1)
-        xyz, src, _, _ = filter_scene_coordinates(sc, pinv, K, filter_depth, dense, len(sel), seed=self.opt.random_seed, opengl=opengl)
-        return xyz.cpu().numpy(), src.cpu().numpy(), sel
+        pinv_all = torch.linalg.inv(torch.from_numpy(np.asarray(poses_c2w, np.float64)[sel])).to(torch.float32)
+        hw = np.array([self.classes[k].hw for k in self.frame_class[sel]], np.int64)
+        off = np.concatenate([[0], np.cumsum(hw)])
+        xyz, src = [], []
+        for ci, c in enumerate(self.classes):
+            at = np.flatnonzero(self.frame_class[sel] == ci)
+            if len(at) == 0:
+                continue
+            sc = self.scene_coordinates(head_sd, sel[at])
+            K = torch.stack([self._K(focal, i) for i in sel[at]]) if len(self.classes) > 1 else self._K(focal).repeat(len(sel), 1, 1)
+            # the filter keys frame b of a launch by first_frame_id + b: one launch per run of consecutive registered positions, so that a
+            # frame's stream is keyed by its position in `sel` whatever the size classes (one size: one launch, as before)
+            cuts = np.flatnonzero(np.diff(at) != 1) + 1
+            for r0, r1 in zip(np.concatenate([[0], cuts]), np.concatenate([cuts, [len(at)]])):
+                x_, s_, _, _ = filter_scene_coordinates(sc[r0:r1], pinv_all[at[r0:r1]], K[r0:r1], filter_depth, dense, len(sel),
+                                                        seed=self.opt.random_seed, first_frame_id=int(at[r0]), opengl=opengl)
+                f_, p_ = np.divmod(s_.cpu().numpy().astype(np.int64), c.hw)
+                xyz.append(x_.cpu().numpy())
+                src.append(off[at[r0 + f_]] + p_)
+        if not xyz:
+            return np.zeros((0, 3), np.float32), np.zeros((0,), np.int64), sel
+        return np.concatenate(xyz), np.concatenate(src), sel
 
 
 def write_pose_file(path, image_names, poses_c2w, confidences, focal):
-    """poses_<session>.txt (register_mapping.py:261-276): world->camera quaternion + translation, focal, confidence."""
+    """poses_<session>.txt (register_mapping.py:261-276): world->camera quaternion + translation, focal (one, or one per image), confidence."""
     from .cli import write_pose_line
+    focals = np.broadcast_to(np.asarray(focal, np.float64), (len(image_names),))
     with open(path, "w") as f:
-        for name, p, c in zip(image_names, poses_c2w, confidences):
-            write_pose_line(f, name, np.linalg.inv(np.asarray(p, np.float64)), int(c), float(focal))
+        for name, p, c, fl in zip(image_names, poses_c2w, confidences, focals):
+            write_pose_line(f, name, np.linalg.inv(np.asarray(p, np.float64)), int(c), float(fl))

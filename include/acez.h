@@ -416,6 +416,23 @@ int acez_buffer_sample_views(const void* d_view_features, const uint8_t* d_masks
                              int32_t view_index_base, void* d_out_features, float* d_out_target_px,
                              int32_t* d_out_view_idx, int32_t* d_out_pixel, void* stream);
 
+/* acez_buffer_sample_views for views of any sizes in ONE launch, read in place from a resident feature store (no gathered copy of
+ * the mapped frames' feature maps). For each view the draws, rows and outputs equal those of acez_buffer_sample_views with the same
+ * seed, first_view_id and view index, bit for bit.
+ *   d_features       16-bit [n_feature_rows][channels]: the store (e.g. every resident frame's map, one after the other)
+ *   d_masks          uint8 validity bytes of the views (layout as in acez_buffer_sample_views, per view), or NULL
+ *   mask_bytes       size of d_masks in bytes (ignored without masks)
+ *   d_view_table     int64 [n_views][4] on the device: (first feature row, map_h, map_w, byte offset of the mask in d_masks or -1 = every
+ *                    pixel valid). Every view must fit max_hw, the store and the masks; one that does not is skipped (its output rows are
+ *                    left as they were) rather than read out of bounds.
+ *   max_hw           largest map_h * map_w in the table, at most 24576 (checked here, without reading the table)
+ *   other arguments  as acez_buffer_sample_views; view v's samples go to output rows v * samples_per_view + s.
+ * Asynchronous on `stream`; no host synchronisation. */
+int acez_buffer_sample_views_table(const void* d_features, int64_t n_feature_rows, const uint8_t* d_masks, int64_t mask_bytes,
+                                   const int64_t* d_view_table, int n_views, int max_hw, int channels, int samples_per_view,
+                                   uint64_t seed, uint64_t first_view_id, int32_t view_index_base, void* d_out_features,
+                                   float* d_out_target_px, int32_t* d_out_view_idx, int32_t* d_out_pixel, void* stream);
+
 /* Augmented training views of resident frames (dataset.py:283-343: resize by a common factor, rotate about the centre, ColorJitter
  * brightness / contrast on the grey values, a validity mask that goes through the same warp with zero padding), the step in front of the
  * encoder when ace_trainer.py:293-452 fills the buffer with --use_aug True. One launch per batch of views of one canvas size (+ a

@@ -1,0 +1,131 @@
+"""Folders of mixed frame sizes on the host side: size classes from load_frames, per-frame resize factors and focals, depth maps
+at every frame's own feature resolution, the calibration-refinement refusal, per-frame pose-file focals and point colours."""
+import os
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+from acezero_amd import cli, session
+
+# (w, h) of the frames in sorted order: landscape, portrait, and one wider frame (a class of its own)
+SIZES = [(64, 48), (48, 64), (64, 48), (48, 64), (80, 48), (64, 48)]
+
+
+def _folder(tmp_path, sizes=SIZES, scale=1):
+    from PIL import Image
+    rng = np.random.default_rng(5)
+    for i, (w, h) in enumerate(sizes):
+        Image.fromarray(rng.integers(0, 256, size=(h * scale, w * scale, 3), dtype=np.uint8)).save(tmp_path / f"f{i}.png")
+        Image.fromarray(np.full((h * scale, w * scale), 1000 + i, np.uint16)).save(tmp_path / f"d{i}.png")
+    return str(tmp_path / "f*.png")
+
+
+def test_load_frames_returns_size_classes(tmp_path):
+    # the 80 x 48 frame is saved twice as large: its factor differs from the others'
+    from PIL import Image
+    glob_ = _folder(tmp_path)
+    Image.fromarray(np.zeros((96, 160, 3), np.uint8)).save(tmp_path / "f4.png")
+    files, classes, factors = cli.load_frames(glob_, image_resolution=48, size_classes=True)
+    assert [os.path.basename(f) for f in files] == [f"f{i}.png" for i in range(6)]
+    assert [c[0].tolist() for c in classes] == [[0, 2, 5], [1, 3], [4]]
+    assert [tuple(c[1].shape) for c in classes] == [(3, 1, 48, 64), (2, 1, 64, 48), (1, 1, 48, 80)]
+    assert factors.tolist() == [1.0, 1.0, 1.0, 1.0, 0.5, 1.0]
+    # every class holds exactly the frames the single-size loader gives for its files
+    for pos, t in classes:
+        _, one, _ = cli.load_frames(None, 48, files=[files[i] for i in pos])
+        assert torch.equal(one, t)
+    # the default call keeps refusing a mix
+    with pytest.raises(SystemExit):
+        cli.load_frames(glob_, image_resolution=48)
+    # the entry points' loader: a mix as classes, one size exactly as load_frames returns it
+    f2, frames, fs, rgb = cli.load_session_frames(glob_, 48, return_rgb=True)
+    assert isinstance(frames, list) and len(rgb) == 6 and rgb[1].shape == (64, 48, 3) and rgb[4].shape == (48, 80, 3)
+    one = [files[i] for i in (0, 2, 5)]
+    a = cli.load_session_frames(None, 48, files=one)
+    b = cli.load_frames(None, 48, files=one)
+    assert torch.equal(a[1], b[1]) and a[2] == b[2] and a[0] == b[0]
+
+
+def test_per_frame_focals_and_depth(tmp_path):
+    glob_ = _folder(tmp_path, scale=2)
+    files, classes, factors = cli.load_frames(glob_, image_resolution=48, size_classes=True)
+    assert np.allclose(factors, 0.5)
+    f = cli.initial_focals(classes, factors, external=100.0)
+    assert np.allclose(f, 50.0)                                          # original pixels x the frame's factor (dataset.py:289-290)
+    f = cli.initial_focals(classes, factors)
+    assert np.allclose(f[[0, 1, 2, 3, 5]], 0.7 * 80.0) and np.isclose(f[4], 0.7 * np.hypot(80, 48))
+    f = cli.initial_focals(classes, factors, file_focals=[200.0 + i for i in range(6)])
+    assert np.allclose(f, (200.0 + np.arange(6)) * 0.5)
+    depth = cli.load_depth_maps(str(tmp_path / "d*.png"), 6, cli.frame_shapes(classes, 6))
+    assert [tuple(d.shape) for d in depth] == [(6, 8), (8, 6), (6, 8), (8, 6), (6, 10), (6, 8)]
+    assert all(np.allclose(d.numpy(), (1000 + i) / 1000.0) for i, d in enumerate(depth))
+
+
+def test_calibration_refinement_refuses_differing_focals(tmp_path):
+    """refine_calibration.py:14-15: one focal for every frame. Portrait and landscape frames of one camera share the diagonal and
+    pass; the 80 x 48 frame's heuristic focal differs and the run is refused before any frame is encoded."""
+    glob_ = _folder(tmp_path)
+    files, classes, factors = cli.load_frames(glob_, 48, size_classes=True)
+    f = cli.initial_focals(classes, factors)
+    cli.check_calibration_focals(f[[0, 1, 2, 3, 5]])
+    with pytest.raises(SystemExit, match="All images must have the same focal length for calibration refinement"):
+        cli.check_calibration_focals(f)
+    with pytest.raises(SystemExit, match="All images must have the same focal length for calibration refinement"):
+        cli.ace_zero_main([glob_, str(tmp_path / "out"), "--image_resolution", "48", "--depth_files", str(tmp_path / "d*.png")])
+    for i in range(6):
+        np.savetxt(tmp_path / f"p{i}.txt", np.eye(4))
+    with pytest.raises(SystemExit, match="All images must have the same focal length for calibration refinement"):
+        cli.train_main([glob_, str(tmp_path / "m.pt"), "--image_resolution", "48", "--pose_files", str(tmp_path / "p*.txt"),
+                        "--refine_calibration", "True"])
+
+
+def test_pose_file_focal_per_frame(tmp_path):
+    names = ["a.png", "b.png", "c.png"]
+    poses = np.tile(np.eye(4), (3, 1, 1))
+    session.write_pose_file(tmp_path / "p.txt", names, poses, [600, 700, 800], np.array([500.0, 510.5, 520.25]))
+    fl, _, focals = cli.read_ace_pose_file(tmp_path / "p.txt", 0)
+    assert fl == names and focals == [500.0, 510.5, 520.25]
+    session.write_pose_file(tmp_path / "q.txt", names, poses, [600, 700, 800], 512.5)
+    assert cli.read_ace_pose_file(tmp_path / "q.txt", 0)[2] == [512.5] * 3
+
+
+def test_point_sources_of_mixed_frames():
+    """point_cloud's source rows over frames of two sizes decode to (frame, map pixel, map width); colours come from each frame."""
+    fake = SimpleNamespace(classes=[SimpleNamespace(hw=12, ow=4), SimpleNamespace(hw=12, ow=3), SimpleNamespace(hw=20, ow=5)],
+                           frame_class=np.array([0, 1, 0, 2]))
+    sel = np.array([1, 2, 3])
+    src = np.array([0, 11, 12, 23, 24, 43])
+    frame, pix, ow = session.ReconstructionSession.source_pixels(fake, src, sel)
+    assert frame.tolist() == [1, 1, 2, 2, 3, 3] and pix.tolist() == [0, 11, 0, 11, 0, 19] and ow.tolist() == [3, 3, 4, 4, 5, 5]
+    rgb = [np.full((24, 32, 3), 0, np.uint8), np.arange(32 * 24 * 3, dtype=np.uint8).reshape(32, 24, 3) % 200,
+           np.full((24, 32, 3), 7, np.uint8), np.full((32, 40, 3), 9, np.uint8)]
+    clr = cli.source_colours(rgb, frame, pix, ow)
+    assert np.array_equal(clr[0], rgb[1][4, 4]) and np.array_equal(clr[1], rgb[1][28, 20]) and (clr[2:4] == 7).all() and (clr[4:] == 9).all()
+
+
+def test_ace_zero_keeps_a_single_focal(tmp_path):
+    """ace_zero.py:301-302 hands one focal from round to round: without calibration refinement too, a mix whose focals differ in
+    original-image pixels is refused before any frame is encoded. An external focal is one focal for every frame."""
+    glob_ = _folder(tmp_path)
+    with pytest.raises(SystemExit, match="single focal length"):
+        cli.ace_zero_main([glob_, str(tmp_path / "out"), "--image_resolution", "48", "--depth_files", str(tmp_path / "d*.png"),
+                           "--refine_calibration", "False"])
+    files, classes, factors = cli.load_frames(glob_, 48, size_classes=True)
+    cli.check_single_focal(cli.initial_focals(classes, factors, external=60.0) / factors)
+
+
+def test_focals_back_in_original_units_with_differing_factors(tmp_path):
+    """Frames at two original scales: each focal goes to resized pixels with the frame's own factor and comes back with it."""
+    from PIL import Image
+    _folder(tmp_path, sizes=[(64, 48), (48, 64), (64, 48)])
+    Image.fromarray(np.zeros((128, 96, 3), np.uint8)).save(tmp_path / "f1.png")    # frame 1 at twice the size: factor 0.5
+    files, classes, factors = cli.load_frames(str(tmp_path / "f*.png"), 48, size_classes=True)
+    assert factors.tolist() == [1.0, 0.5, 1.0] and len(classes) == 2
+    supplied = np.array([100.0, 200.0, 101.0])                           # original-image pixels
+    f = cli.initial_focals(classes, factors, file_focals=supplied)
+    assert np.allclose(f, [100.0, 100.0, 101.0])
+    frel = f / f[0]                                                      # what ReconstructionSession keeps (focals=f)
+    assert np.allclose(cli.focals_in_original_units(f[0], frel, factors), supplied)
+    assert np.allclose(cli.focals_in_original_units(f[0] * 1.1, frel, factors), supplied * 1.1)   # a refined nominal focal scales them all
