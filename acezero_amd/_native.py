@@ -134,6 +134,10 @@ SYMBOLS = {
     "acez_align_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(AlignParams), C.c_void_p,
                                       C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.POINTER(C.c_int32)]),
+    "acez_render_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_float,
+                                    C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "acez_render_camera": (C.c_int, [C.POINTER(C.c_double), C.c_float, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float)]),
 }
 
 

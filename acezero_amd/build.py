@@ -18,7 +18,7 @@ STAMP = os.path.join(HERE, ".libacez.stamp")
 LIB_DIAG = os.path.join(HERE, "libacez_diag.so")
 STAMP_DIAG = os.path.join(HERE, ".libacez_diag.stamp")
 
-# translation unit -> extra flags.  The RANSAC, point-cloud and pose-evaluation units must not contract a*b+c into fma: their arithmetic
+# translation unit -> extra flags.  The RANSAC, point-cloud, pose-evaluation and rendering units must not contract a*b+c into fma: their arithmetic
 # is compared bit-for-bit with the CPU oracle (DESIGN.md "Determinism").
 UNITS = {
     "acez_common.hip": [],
@@ -27,6 +27,7 @@ UNITS = {
     "ransac_api.hip": ["-ffp-contract=off"],
     "cloud_api.hip": ["-ffp-contract=off"],
     "align_api.hip": ["-ffp-contract=off"],
+    "render_api.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

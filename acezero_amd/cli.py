@@ -80,7 +80,7 @@ TRAIN_FLAGS = [
     (("--use_aug",), _strtobool, True, None, ""),
     (("--aug_rotation",), int, 15, None, ""),
     (("--aug_scale",), float, 1.5, None, ""),
-    (("--render_visualization",), _strtobool, False, None, "accepted; rendering is out of scope"),
+    (("--render_visualization",), _strtobool, False, None, "render the mapping frames and write <map stem>_mapping.pkl"),
     (("--render_target_path",), Path, "renderings", None, ""),
     (("--use_existing_vis_buffer",), Path, None, None, ""),
     (("--render_flipped_portrait",), _strtobool, False, None, ""),
@@ -106,7 +106,7 @@ REGISTER_FLAGS = [
     (("--threshold", "-t"), float, 10, None, "inlier threshold in px"),
     (("--inlieralpha", "-ia"), float, 100, None, "soft inlier count alpha"),
     (("--maxpixelerror", "-maxerrr"), float, 100, None, "reprojection errors are clamped to this value"),
-    (("--render_visualization",), _strtobool, False, None, ""),
+    (("--render_visualization",), _strtobool, False, None, "render one frame per query and write <network stem>_register.pkl"),
     (("--render_target_path",), Path, "renderings", None, ""),
     (("--render_flipped_portrait",), _strtobool, False, None, ""),
     (("--render_pose_conf_threshold",), int, 5000, None, ""),
@@ -161,7 +161,8 @@ ACE_ZERO_FLAGS = [
     (("--training_buffer_cpu",), _strtobool, False, None, "accepted; the buffer lives in HBM"),
     (("--ransac_iterations",), int, 32, None, ""),
     (("--ransac_threshold",), float, 10, None, ""),
-    (("--render_visualization",), _strtobool, False, None, "accepted; rendering is out of scope"),
+    (("--render_visualization",), _strtobool, False, None, "render every round, the final sweep and (ffmpeg on PATH) "
+                                                         "results/reconstruction.mp4 into results/renderings"),
     (("--render_flipped_portrait",), _strtobool, False, None, ""),
     (("--render_marker_size",), float, 0.03, None, ""),
     (("--iterations_output",), int, 500, None, ""),
@@ -316,12 +317,14 @@ def train_with_options(opt):
     start = time.time()
     epoch, launched, done = 0, 0, False
     orig_poses = np.linalg.inv(buf["image_pose_inv"].astype(np.float64))[:, :3, 3]
+    vis = _mapping_visualizer(opt, buf) if opt.render_visualization else None
     with open(log_path, "w", 1) as log:
         from .head import epoch_batches
         pairs = epoch_batches(n, opt.batch_size, opt.base_seed + 8191, tr.device)   # ace_trainer.py:79-80,466 (drawn on the device)
         while not done:
             for _ in range(n // opt.batch_size):
-                tr.step(*next(pairs))                                # (rows, next rows): the next batch is gathered ahead
+                rows, nxt = next(pairs)
+                tr.step(rows, nxt)                                   # (rows, next rows): the next batch is gathered ahead
                 launched += 1
                 if launched % opt.iterations_output == 0 or launched % 64 == 0:
                     st = tr.state()                                  # the only host synchronisation of the loop
@@ -339,12 +342,16 @@ def train_with_options(opt):
                         if opt.refine_calibration:
                             row += f" {st['focal_scale'] * focal}"
                         log.write(row + "\n")
+                        if vis is not None and launched <= st["max_iterations"]:
+                            vis.render_mapping_frame_from_trainer(tr, rows, launched)
                     if st["iteration"] >= st["max_iterations"]:
                         done = True
                         break
             epoch += 1
     st = tr.state()
     elapsed = time.time() - start
+    if vis is not None:
+        _finalize_mapping_visualization(opt, vis, tr, buf, n)
     _logger.info(f"Done without errors. Training time: {elapsed:.1f}s, {st['iteration']} iterations, "
                  f"{st['iteration'] * opt.batch_size / max(elapsed, 1e-9):.0f} patches/s.")
     # save_model (ace_trainer.py:681-694): half-precision head state_dict
@@ -359,6 +366,59 @@ def train_with_options(opt):
             write_pose_line(f, files[i], p34, float("inf"), f_out)
     _logger.info(f"Saved trained head weights to: {opt.output_map_file}; refined poses to: {pose_file}")
     return 0
+
+
+def _mapping_visualizer(opt, buf):
+    """train_ace.py --render_visualization: the mapping phase's visualiser, its pan around the buffer's (original) poses."""
+    vis = _train_visualizer(opt)
+    vis.setup_mapping(list(np.linalg.inv(buf["image_pose_inv"].astype(np.float64))), existing_state=opt.use_existing_vis_buffer)
+    return vis
+
+
+def _train_visualizer(opt, frame_rgb=None):
+    from .render import Visualizer
+    return Visualizer(opt.render_target_path, opt.render_flipped_portrait, opt.render_map_depth_filter,
+                      mapping_error_threshold=opt.render_map_error_threshold, state_file_name=opt.output_map_file.stem + "_mapping.pkl",
+                      marker_size=opt.render_marker_size, camera_z_offset=opt.render_camera_z_offset, every=opt.iterations_output,
+                      existing_state=opt.use_existing_vis_buffer, frame_rgb=frame_rgb)
+
+
+def _register_visualizer(opt):
+    """register_mapping.py --render_visualization: continues from `<network stem>_mapping.pkl` in --render_target_path."""
+    from .render import Visualizer
+    return Visualizer(opt.render_target_path, opt.render_flipped_portrait, opt.render_map_depth_filter,
+                      reloc_conf_threshold=opt.render_pose_conf_threshold, confidence_threshold=opt.confidence_threshold,
+                      state_file_name=Path(opt.network).stem + "_mapping.pkl", marker_size=opt.render_marker_size,
+                      camera_z_offset=opt.render_camera_z_offset)
+
+
+def _finalize_mapping_visualization(opt, vis, tr, buf, n, max_points=1_000_000):
+    """The transition frames and `<map stem>_mapping.pkl`: the trained head on (at most max_points, evenly strided) buffer rows, in
+    buffer order, kept where the reprojection error is below the threshold and the depth within --render_map_depth_filter, coloured by
+    reprojection error (a feature buffer carries no image colours). OpenGL convention."""
+    import torch
+    from .render import errors_to_colors, trainer_batch_errors
+    rows = np.arange(0, n, -(-n // max_points))                     # ceil stride: at most max_points rows
+    feats = buf["features"]                                          # (an NpzFile decodes the array on every access: read it once)
+    poses = tr.current_poses()
+    xyz, err, depth = [], [], []
+    for c0 in range(0, len(rows), 65536):
+        r = torch.from_numpy(rows[c0:c0 + 65536]).to(tr.device)
+        x = tr.get_scene_coordinates(torch.from_numpy(feats[rows[c0:c0 + 65536]].astype(np.float32)).to(tr.device)).cpu().numpy()
+        xyz.append(x)
+        err.append(trainer_batch_errors(tr, r, x, poses))
+        img = tr._buf["view_image"][tr._buf["view_idx"][r].long()].long().cpu().numpy()
+        P = np.asarray(poses, np.float64)[img]
+        depth.append(np.einsum("kj,kj->k", P[:, 2, :3], x.astype(np.float64)) + P[:, 2, 3])
+    del feats
+    xyz = np.concatenate(xyz) if xyz else np.zeros((0, 3), np.float32)
+    err = np.concatenate(err) if err else np.zeros(0)
+    depth = np.concatenate(depth) if depth else np.zeros(0)
+    keep = (err < opt.render_map_error_threshold) & (depth > 0) & (depth < opt.render_map_depth_filter)
+    clr, _ = errors_to_colors(err[keep], opt.render_map_error_threshold, vis.mapping_cmap)
+    xyz = xyz[keep].copy()
+    xyz[:, 1:] *= -1
+    vis.finalize_mapping(xyz, clr, poses, vis.poses_w2c_orig)
 
 
 def quat_wxyz_to_matrix(q_wxyz):
@@ -397,13 +457,15 @@ def _train_from_images(opt):
     import glob
     import torch
     from .session import ReconstructionSession
+    rgb = None
     if opt.use_ace_pose_file is not None:
         files, poses, focals = read_ace_pose_file(opt.use_ace_pose_file, opt.ace_pose_file_conf_threshold)
-        files, frames, fscale = load_session_frames(None, opt.image_resolution, files=files)
+        files, frames, fscale, *rgb = load_session_frames(None, opt.image_resolution, files=files, return_rgb=opt.render_visualization)
     else:
-        files, frames, fscale = load_session_frames(opt.rgb_files, opt.image_resolution)
+        files, frames, fscale, *rgb = load_session_frames(opt.rgb_files, opt.image_resolution, return_rgb=opt.render_visualization)
         focals = []
         poses = np.stack([np.loadtxt(f) for f in sorted(glob.glob(opt.pose_files))]) if opt.pose_files is not None else None   # dataset_io.load_pose
+    rgb = rgb[0] if rgb else None
     mixed = not torch.is_tensor(frames)                                  # a folder of several frame sizes: its size classes
     ids = list(range(len(files)))
     if opt.use_pose_seed >= 0:                                           # dataset.py:110-124
@@ -438,7 +500,8 @@ def _train_from_images(opt):
                 schedule=opt.learning_rate_schedule, lr_max=opt.learning_rate_max, refinement=opt.pose_refinement,
                 pose_wait=opt.pose_refinement_wait, refine_calibration=opt.refine_calibration,
                 load_weights=torch.load(opt.load_weights, map_location="cpu") if opt.load_weights is not None else None,
-                with_depth=opt.use_pose_seed >= 0 or opt.depth_files is not None, tag=opt.output_map_file.stem)
+                with_depth=opt.use_pose_seed >= 0 or opt.depth_files is not None, tag=opt.output_map_file.stem,
+                visualizer=_train_visualizer(opt, rgb) if opt.render_visualization else None)
     # each frame's focal back in its own original units
     f_out = focals_in_original_units(m["focal"], ses.frel, fscale) if mixed else np.full(len(files), m["focal"] / fscale)
     opt.output_map_file.parent.mkdir(parents=True, exist_ok=True)
@@ -479,6 +542,10 @@ def _register_mixed_sizes(opt, files, classes):
     else:
         chosen = np.sort(torch.randperm(n, generator=torch.Generator().manual_seed(int(opt.base_seed)))[:opt.max_estimates].numpy())
     keep = set(int(i) for i in chosen)
+    vis = None
+    if opt.render_visualization:                                         # one video over all size classes, in size-class order
+        vis = _register_visualizer(opt)
+        vis.setup_reloc(len(keep))
     enc_sd = torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu")
     head_sd = torch.load(opt.network, map_location="cpu")
     rows = {}
@@ -491,7 +558,8 @@ def _register_mixed_sizes(opt, files, classes):
                               ransac_iterations=opt.hypotheses, ransac_threshold=opt.threshold, register_seed=opt.base_seed, use_aug=False,
                               registration_confidence=opt.confidence_threshold)
         ses = ReconstructionSession(enc_sd, frames, opt=so)
-        poses, inl = ses.register(head_sd, ses.focal0, max_tries=opt.hypotheses_max_tries, rng_ids=pos, tag=f"register {w}x{h}")
+        poses, inl = ses.register(head_sd, ses.focal0, max_tries=opt.hypotheses_max_tries, rng_ids=pos, tag=f"register {w}x{h}",
+                                  visualizer=vis)
         for k, i in enumerate(pos):
             rows[i] = (poses[k], int(inl[k]), ses.focal0 / fscale)
         del ses
@@ -501,6 +569,8 @@ def _register_mixed_sizes(opt, files, classes):
             p, c, focal = rows[i]
             write_pose_line(f, files[i], np.linalg.inv(np.asarray(p, np.float64)), c, float(focal))
     _logger.info(f"Registered {len(rows)} images of {len(classes)} sizes -> {out}")
+    if vis is not None:
+        vis.save_reloc_state(os.path.join(str(opt.render_target_path), Path(opt.network).stem + "_register.pkl"))
     return 0
 
 
@@ -516,10 +586,17 @@ def _register_from_images(opt):
                           ransac_iterations=opt.hypotheses, ransac_threshold=opt.threshold, register_seed=opt.base_seed, use_aug=False,
                           registration_confidence=opt.confidence_threshold)
     ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, opt=so)
-    poses, inl = ses.register(torch.load(opt.network, map_location="cpu"), ses.focal0, max_estimates=opt.max_estimates, max_tries=opt.hypotheses_max_tries)
+    vis = None
+    if opt.render_visualization:
+        vis = _register_visualizer(opt)
+        vis.setup_reloc(len(files) if opt.max_estimates <= 0 else min(opt.max_estimates, len(files)))
+    poses, inl = ses.register(torch.load(opt.network, map_location="cpu"), ses.focal0, max_estimates=opt.max_estimates, max_tries=opt.hypotheses_max_tries,
+                              visualizer=vis)
     out = Path(opt.network).parent / f"poses_{opt.session}.txt"
     write_pose_file(out, [files[i] for i in ses.registered_ids], poses, inl, ses.focal0 / fscale)
     _logger.info(f"Registered {len(poses)} images -> {out}")
+    if vis is not None:
+        vis.save_reloc_state(os.path.join(str(opt.render_target_path), Path(opt.network).stem + "_register.pkl"))
     return 0
 
 
@@ -570,6 +647,12 @@ def register_main(argv=None):
             write_pose_line(f, files[i], np.linalg.inv(poses[k].astype(np.float64)), int(inl[k]), float(focal[i]))   # :261-276
     dt = time.time() - t0
     _logger.info(f"Registered {n} images in {dt:.2f}s ({n / max(dt, 1e-9):.0f} images/s) -> {pose_log_file}")
+    if opt.render_visualization:
+        vis = _register_visualizer(opt)
+        vis.setup_reloc(n)
+        for k in range(n):
+            vis.render_reloc_frame(poses[k].astype(np.float64), int(inl[k]))
+        vis.save_reloc_state(os.path.join(str(opt.render_target_path), Path(opt.network).stem + "_register.pkl"))
     return 0
 
 
@@ -721,6 +804,8 @@ def ace_zero_main(argv=None):
             dist.init_process_group(os.environ.get("ACEZ_DIST_BACKEND", "nccl"))
         if opt.export_point_cloud:
             raise SystemExit("--export_point_cloud True runs on one GPU: export from the written pose file with export_point_cloud.py")
+        if opt.render_visualization:
+            raise SystemExit("--render_visualization True runs on one GPU")
     logging.basicConfig(level=logging.INFO if rank == 0 else logging.WARNING)
     opt.results_folder.mkdir(parents=True, exist_ok=True)
     files, frames, fscale, rgb = load_session_frames(opt.rgb_files, opt.image_resolution, return_rgb=True)
@@ -746,7 +831,15 @@ def ace_zero_main(argv=None):
                                 focals=frame_focals)
     # pose files: every frame's focal in its own original units (one focal, the session's nominal one, goes from round to round)
     orig = (lambda f: focals_in_original_units(f, ses.frel, fscale)) if mixed else (lambda f: f / fscale)
-    res = ses.reconstruct()   # (seed trials one after the other: side by side is not faster here)
+    render_dir = opt.results_folder / "renderings"                       # ace_zero_util.get_render_path
+    render = None
+    if opt.render_visualization:
+        from .render import Visualizer
+
+        def render(state_name, existing):
+            return Visualizer(render_dir, opt.render_flipped_portrait, 100, state_file_name=state_name, marker_size=opt.render_marker_size,
+                              every=opt.iterations_output, existing_state=existing, frame_rgb=rgb)
+    res = ses.reconstruct(render=render)   # (seed trials one after the other: side by side is not faster here)
     if rank != 0:                                                       # every rank holds the same result; rank 0 writes it
         import torch.distributed as dist
         dist.barrier()
@@ -760,6 +853,8 @@ def ace_zero_main(argv=None):
         from .pointcloud import write_point_cloud
         xyz, src, sel = res["point_cloud"]
         write_point_cloud(opt.results_folder / "pc_final.ply", xyz, point_colours(ses, rgb, src, sel))
+    if opt.render_visualization:
+        _render_video(opt, render_dir)
     rates = [float((res["confidence"] > t).mean()) for t in (500, 1000, 2000, 4000)]
     _logger.info(f"Reconstructed in {res['seconds'] / 60:.1f} minutes, {res['iterations']} iterations; "
                  "registration rate @500/@1000/@2000/@4000: " + " ".join(f"{r * 100:.1f}%" for r in rates))
@@ -767,6 +862,26 @@ def ace_zero_main(argv=None):
         import torch.distributed as dist
         dist.barrier()
     return 0
+
+
+def _render_video(opt, render_dir):
+    """ace_zero.py:341-370: the final sweep over the last round's state, then ffmpeg if it is on PATH (else the command is logged and
+    the PNG frames stay)."""
+    import shlex
+    import shutil
+    import subprocess
+    from .render import render_final_sweep_main
+    _logger.info("Rendering final sweep.")
+    if render_final_sweep_main([str(render_dir), "--render_marker_size", str(opt.render_marker_size)]) != 0:
+        raise SystemExit("the final sweep found no registration state to render from")
+    cmd = ["ffmpeg", "-y", "-framerate", "30", "-pattern_type", "glob", "-i", f"{render_dir}/*.png", "-c:v", "libx264", "-pix_fmt",
+           "yuv420p", str(opt.results_folder / "reconstruction.mp4")]
+    ffmpeg = shutil.which("ffmpeg")
+    if ffmpeg is None:
+        _logger.info("ffmpeg is not on PATH; the frames are in %s. To make the video run: %s", render_dir, shlex.join(cmd))
+        return
+    _logger.info("Converting to video.")
+    subprocess.run([ffmpeg] + cmd[1:], check=True)
 
 
 # ------------------------------------------------------------------------------------------------ export_point_cloud

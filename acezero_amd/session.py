@@ -474,7 +474,7 @@ class ReconstructionSession:
         return buf
 
     def map(self, image_ids, poses_c2w, focal, *, iterations, loss_type, schedule, lr_max, refinement="none", pose_wait=0,
-            refine_calibration=False, load_weights=None, with_depth=False, tag="map", data_parallel=None):
+            refine_calibration=False, load_weights=None, with_depth=False, tag="map", data_parallel=None, visualizer=None):
         """One train_ace.py run (ace_trainer.py:TrainerACE.train): returns {"head": fp16 state_dict, "poses_w2c": [m,3,4] refined,
         "focal": refined focal, "iterations", "seconds", "patches_per_s", "batch_inliers"}.
 
@@ -483,7 +483,11 @@ class ReconstructionSession:
         backward -> all-reduce of the flat gradient bucket -> update with the reference's batch composition: all ranks draw the same
         permutation of the GLOBAL buffer and take the rows of each 5120-slice that live in their shard (parallel.epoch_local_batches;
         the loss is a sum / 5120, ace_trainer.py:612-613, so the summed gradient is the single-GPU gradient of that batch). Replicas
-        stay bit-identical without a weight broadcast, so every rank returns the same result."""
+        stay bit-identical without a weight broadcast, so every rank returns the same result.
+
+        visualizer (acezero_amd.render.Visualizer, one GPU): the mapping phase of the reconstruction video -- a frame every
+        visualizer.every steps from the step's own scene coordinates, then the transition frames over the point cloud of the trained head
+        (point_cloud: the N4 filter) and the visualiser's `_mapping.pkl`. None: nothing is rendered, launched or read."""
         o = self.opt
         t0 = time.time()
         image_ids = [int(i) for i in image_ids]
@@ -502,11 +506,20 @@ class ReconstructionSession:
                             with_depth=with_depth, tag=tag, data_parallel=False) if self.rank == src else None]
             dist.broadcast_object_list(box, src=dist.get_global_rank(self.group, src) if self.group is not None else src, group=self.group)
             return box[0]
+        if visualizer is not None:
+            if self.world > 1:
+                raise RuntimeError("the reconstruction video is rendered by a single-GPU run")
+            visualizer.setup_mapping(np.asarray(torch.as_tensor(poses_c2w, dtype=torch.float64).reshape(-1, 4, 4)),
+                                     existing_state=visualizer.existing_state)
         job = self._map_prepare(image_ids, poses_c2w, focal, iterations=iterations, loss_type=loss_type, schedule=schedule, lr_max=lr_max,
                                 refinement=refinement, pose_wait=pose_wait, refine_calibration=refine_calibration, load_weights=load_weights,
                                 with_depth=with_depth, tag=tag, data_parallel=data_parallel, t0=t0)
+        job.vis = visualizer
         self._map_loop(job)
-        return self._map_result(job)
+        out = self._map_result(job)
+        if visualizer is not None:
+            self._finalize_map_visualization(visualizer, out, image_ids)
+        return out
 
     def _map_prepare(self, image_ids, poses_c2w, focal, *, iterations, loss_type, schedule, lr_max, refinement="none", pose_wait=0,
                      refine_calibration=False, load_weights=None, with_depth=False, tag="map", data_parallel=None, t0=None):
@@ -573,7 +586,7 @@ class ReconstructionSession:
         tr.set_buffer(**buf)
         torch.cuda.synchronize(self.dev)
         return SimpleNamespace(tr=tr, n=n, n_local=n_local, shard_lo=shard_lo, dp=dp, m=m, focal=focal, refine_calibration=refine_calibration,
-                               tag=tag, t0=t0, t_fill=t_fill, t_loop0=None, t_loop=None, dpt=None)
+                               tag=tag, t0=t0, t_fill=t_fill, t_loop0=None, t_loop=None, dpt=None, vis=None, iterations=iterations)
 
     def _map_loop(self, job):
         """Second part of map(): the training loop of one trainer."""
@@ -595,8 +608,11 @@ class ReconstructionSession:
                     # update (gathered inside the optimiser's launch; the first batch of an epoch gathers for itself)
                     dpt.step(local[offs[b]:offs[b + 1]], local[offs[b + 1]:offs[b + 2]] if b + 1 < nb else None)
                 else:
-                    tr.step(*next(pairs))
+                    rows, nxt = next(pairs)
+                    tr.step(rows, nxt)
                 launched += 1
+                if job.vis is not None and launched % job.vis.every == 0 and launched <= job.iterations:
+                    job.vis.render_mapping_frame_from_trainer(tr, rows, launched)   # (a video frame: one read of the step's output)
                 if launched % 64 == 0:                                   # the only host synchronisation of the loop
                     st = tr.state()
                     if st["nan"]:
@@ -649,6 +665,21 @@ class ReconstructionSession:
         tr.close()
         return out
 
+    def _finalize_map_visualization(self, vis, out, image_ids):
+        """The end of a rendered mapping run: the N4 point cloud of the trained head over the mapped frames (refined poses, the
+        visualiser's depth filter, OpenGL convention, the frames' RGB colours), grown over the transition frames; the `_mapping.pkl`."""
+        from .cli import point_colours
+        c2w = np.tile(np.eye(4), (self.n, 1, 1))
+        conf = np.full(self.n, -np.inf)
+        ids = np.asarray(image_ids, np.int64)
+        w2c = np.tile(np.eye(4), (len(ids), 1, 1))
+        w2c[:, :3] = out["poses_w2c"]
+        c2w[ids] = np.linalg.inv(w2c)
+        conf[ids] = np.inf
+        xyz, src, sel = self.point_cloud(out["head"], c2w, conf, out["focal"], filter_depth=vis.map_depth_filter, opengl=True)
+        clr = point_colours(self, vis.frame_rgb, src, sel) if vis.frame_rgb is not None and len(xyz) else np.full((len(xyz), 3), 200.0)
+        vis.finalize_mapping(xyz, clr, out["poses_w2c"], vis.poses_w2c_orig)
+
     # ---------------------------------------------------------------------------------------- registration (register_mapping.py)
     def scene_coordinates(self, head_sd, frame_ids=None):
         """Head.forward on the cached features of the given frames (default: every frame this rank owns), all of one size class:
@@ -679,7 +710,7 @@ class ReconstructionSession:
         head.close()
         return out
 
-    def register(self, head_sd, focal, max_estimates=-1, tag="register", max_tries=16, rng_ids=None):
+    def register(self, head_sd, focal, max_estimates=-1, tag="register", max_tries=16, rng_ids=None, visualizer=None):
         """register_mapping.py:201-276: (poses cam->world [k,4,4] float32, inlier counts [k] int32); the k frame ids they belong to
         are left in self.registered_ids (all frames in order unless max_estimates draws a subset).
 
@@ -689,7 +720,8 @@ class ReconstructionSession:
         (frame i -> rank i % world); the random stream of a frame is keyed by its id, so the result does not depend on the
         partition, and one gather returns every frame's result to every rank. Head and RANSAC run once per size class, with that
         class's principal point and every frame's own focal (`focal` is the nominal one, see __init__). rng_ids: the ids that key
-        the random streams, if they are not the positions in this session."""
+        the random streams, if they are not the positions in this session.
+        visualizer (acezero_amd.render.Visualizer, set up with setup_reloc): one registration frame per registered frame, in order."""
         o = self.opt
         if max_estimates <= 0 or max_estimates >= self.n:
             ids = np.arange(self.n)
@@ -717,6 +749,9 @@ class ReconstructionSession:
         rate = float((inl > o.registration_confidence).mean())
         self.timings["register_s"] += time.time() - t0
         _logger.info(f"[{tag}] {len(ids)} frames in {time.time() - t0:.2f}s, {rate * 100:.1f}% above confidence {o.registration_confidence}")
+        if visualizer is not None:
+            for k in range(len(ids)):
+                visualizer.render_reloc_frame(np.asarray(poses[k], np.float64), int(inl[k]))
         return poses, inl
 
     # --------------------------------------------------------------------------------------------------- the loop (ace_zero.py)
@@ -764,10 +799,29 @@ class ReconstructionSession:
         _, inl = self.register(m["head"], self.focal0, max_estimates=self.opt.max_estimates_seed_scoring, tag=f"iteration0_seed{seed_idx}_fastcheck")
         return float((inl > self.opt.registration_confidence).mean())
 
-    def reconstruct(self, seed_parallel_workers=1):
+    def reconstruct(self, seed_parallel_workers=1, render=None):
         """ace_zero.py's loop. seed_parallel_workers: seed trials trained side by side per group (seed_groups; ace_zero.py
-        --seed_parallel_workers); 1 maps and scores the seeds one after the other. The result is the same for every value."""
+        --seed_parallel_workers); 1 maps and scores the seeds one after the other. The result is the same for every value.
+
+        render (ace_zero.py --render_visualization, one GPU): render(mapping_state_name, existing_state) -> a fresh
+        acezero_amd.render.Visualizer. As the reference does, the best seed is mapped again with the video on, and every round's mapping
+        and registration is rendered: `<id>_mapping.pkl` and `<id>_register.pkl` in the visualiser's folder, each round resuming from
+        the previous round's registration state (render_final_sweep.py continues from the last one)."""
         o = self.opt
+        if render is not None and self.world > 1:
+            raise RuntimeError("the reconstruction video is rendered by a single-GPU run")
+        prev_state = None
+
+        def register_rendered(head, focal, tag):
+            nonlocal prev_state
+            if render is None or (tag == "seed_network"):
+                return self.register(head, focal, tag=tag)
+            vis = render(f"{tag}_mapping.pkl", None)
+            vis.setup_reloc(self.n)
+            out = self.register(head, focal, tag=tag, visualizer=vis)
+            prev_state = f"{tag}_register.pkl"
+            vis.save_reloc_state(os.path.join(vis.target_path, prev_state))
+            return out
         t_start = time.time()
         seed_groups(o.try_seeds, seed_parallel_workers)                  # a bad --seed_parallel_workers fails before any work
         focal = self.focal0
@@ -798,7 +852,10 @@ class ReconstructionSession:
                 trials = [(mp_, self.score_seed(i, mp_)) for i, mp_ in enumerate(maps)]
             best = int(np.argmax([r for _, r in trials]))
             current, first_id, seed_rates = trials[best][0], f"iteration0_seed{best}", [r for _, r in trials]
-        poses, conf = self.register(current["head"], focal, tag=first_id)
+            if render is not None:                                       # ace_zero.py:208-213: re-map the best seed with the video on
+                args, kw = self._seed_map_args(best, seeds[best])
+                current = self.map(*args, **kw, visualizer=render(f"{first_id}_mapping.pkl", None))
+        poses, conf = register_rendered(current["head"], focal, first_id)
         max_rate = float((conf > o.registration_confidence).mean())
         self.history.append({"id": first_id, "registration_rate": max_rate, "focal": focal, "seed_rates": seed_rates, "poses": poses,
                              "confidence": conf, "head": current["head"]})
@@ -815,10 +872,12 @@ class ReconstructionSession:
             else:                                                        # ace_zero_util.get_base_mapping_cmd
                 kw = dict(iterations=o.iterations, loss_type=o.repro_loss_type, schedule=o.learning_rate_schedule, lr_max=o.learning_rate_max,
                           pose_wait=o.pose_refinement_wait)
+            if render is not None:
+                kw["visualizer"] = render(f"iteration{iteration}_mapping.pkl", prev_state)
             current = self.map(sel, torch.from_numpy(poses[sel]), focal, refinement=o.refinement, refine_calibration=o.refine_calibration,
                                load_weights=current["head"] if warm else None, tag=f"iteration{iteration}", **kw)
             focal = current["focal"]                                     # ace_zero.py:297-305: the refined focal goes to the registration
-            poses, conf = self.register(current["head"], focal, tag=f"iteration{iteration}")
+            poses, conf = register_rendered(current["head"], focal, f"iteration{iteration}")
             rate = float((conf > o.registration_confidence).mean())
             self.history.append({"id": f"iteration{iteration}", "registration_rate": rate, "focal": focal, "mapped_images": int(len(sel)),
                                  "iterations": current["iterations"], "map_seconds": current["seconds"], "refit": bool(refit), "poses": poses,

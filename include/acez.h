@@ -521,6 +521,33 @@ int acez_align_evaluate(acez_align* ctx, const double* gt_c2w, const double* est
                         int32_t* out_status, int32_t* out_scores, int32_t* out_valid, double* out_t_err, double* out_r_err,
                         int32_t* out_accurate);
 
+/* =====================================================================================================
+ * H. Rendering the reconstruction video (ace_visualizer.py's pyrender passes, headless)
+ * =====================================================================================================
+ * One frame of two layers on `stream`, written to a device uint8 image:
+ *   points     d_xyz float32 [n_points][3] (world, OpenGL convention), d_rgb uint8 [n_points][3]; each point is a 2 x 2 px square
+ *              (the reference's point_size = 2: the 2 x 2 pixels whose centres are nearest to the projection) with a depth test;
+ *              nearest wins, equal depths go to the lower index. Points with depth outside [znear, zfar] are dropped. Background black.
+ *   triangles  d_tri_xyz float32 [n_tris][3 vertices][3], d_tri_rgba uint8 [n_tris][4]; flat colour, both windings, a depth test
+ *              among themselves only (no test against the points), top-left fill rule on vertices snapped to 1/256 px. Triangles
+ *              that cross the near plane are CLIPPED against it in camera space (the clipped quad is drawn as a fan of two);
+ *              per pixel, depths beyond zfar are dropped; a triangle with a projected vertex 2^21 px or more off the centre is dropped.
+ *              The covered pixels are blended on top of the points as ace_visualizer._blend_images does it: in double,
+ *              rgb * (a / 255) + background * (1 - a / 255), truncated to uint8.
+ *   camera     cam_to_world double [16] row-major, rigid, OpenGL convention (looks down -z); pinhole with yfov = pi/3, square
+ *              pixels, principal point at the frame centre (pyrender.PerspectiveCamera(yfov=pi/3, aspectRatio=W/H)).
+ *   width, height   render size (1280 x 720 by default); flipped_portrait != 0: the render (e.g. 720 x 1280) is rotated by -90 degrees,
+ *              so d_frame is [width][height][3] instead of [height][width][3].
+ *   d_work     uint64 [2 * width * height] scratch (the two per-pixel key planes), owned by the caller.
+ * Asynchronous on `stream`; nothing is allocated. */
+int acez_render_frame(const float* d_xyz, const uint8_t* d_rgb, int64_t n_points, const float* d_tri_xyz, const uint8_t* d_tri_rgba,
+                      int64_t n_tris, const double* cam_to_world, float znear, float zfar, int width, int height, int flipped_portrait,
+                      unsigned long long* d_work, uint8_t* d_frame, void* stream);
+/* Exported for the CPU tests (tests/test_render_cpu.py checks the camera set-up against tests/render_oracle.py without a GPU); the
+ * product calls it only through acez_render_frame. The camera acez_render_frame projects with (host only, no device needed): out_w2c12 float32 [3][4] = [R^T | -R^T t] of the rigid
+ * cam_to_world, computed in double and rounded once; out_focal = (height / 2) * sqrt(3) in pixels. Same argument checks. */
+int acez_render_camera(const double* cam_to_world, float znear, float zfar, int width, int height, float* out_w2c12, float* out_focal);
+
 #ifdef __cplusplus
 }
 #endif
