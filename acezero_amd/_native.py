@@ -72,6 +72,18 @@ class AlignParams(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+RENDER_MAX_TEX_TRIANGLES = 32   # ACEZ_RENDER_MAX_TEX_TRIANGLES
+RENDER_MAX_TEXTURES = 16        # ACEZ_RENDER_MAX_TEXTURES
+
+
+class TexTriangle(C.Structure):
+    _fields_ = [("xyz", (C.c_float * 3) * 3), ("uv", (C.c_float * 2) * 3), ("texture", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Texture(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("width", C.c_int32), ("height", C.c_int32)]
+
+
 # every symbol include/acez.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "acez_last_error": (C.c_char_p, []),
@@ -136,6 +148,11 @@ SYMBOLS = {
                                       C.c_void_p, C.POINTER(C.c_int32)]),
     "acez_render_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_float,
                                     C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "acez_render_texture_size": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "acez_render_texture_build": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "acez_render_frame_tex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(TexTriangle), C.c_int,
+                                        C.POINTER(Texture), C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_float, C.c_float,
+                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acez_render_camera": (C.c_int, [C.POINTER(C.c_double), C.c_float, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float)]),
 }

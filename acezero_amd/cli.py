@@ -553,13 +553,14 @@ def _register_mixed_sizes(opt, files, classes):
         pos = [i for i in pos if i in keep]
         if not pos:
             continue
-        sub_files, frames, fscale = load_frames(None, opt.image_resolution, files=[files[i] for i in pos])
+        sub_files, frames, fscale, *rgb = load_frames(None, opt.image_resolution, files=[files[i] for i in pos],
+                                                      return_rgb=opt.render_visualization)
         so = _session_options(opt, use_external_focal_length=opt.use_external_focal_length * fscale if opt.use_external_focal_length > 0 else -1.0,
                               ransac_iterations=opt.hypotheses, ransac_threshold=opt.threshold, register_seed=opt.base_seed, use_aug=False,
                               registration_confidence=opt.confidence_threshold)
         ses = ReconstructionSession(enc_sd, frames, opt=so)
         poses, inl = ses.register(head_sd, ses.focal0, max_tries=opt.hypotheses_max_tries, rng_ids=pos, tag=f"register {w}x{h}",
-                                  visualizer=vis)
+                                  visualizer=vis, images=rgb[0] if rgb else None)
         for k, i in enumerate(pos):
             rows[i] = (poses[k], int(inl[k]), ses.focal0 / fscale)
         del ses
@@ -581,7 +582,7 @@ def _register_from_images(opt):
     all_files, classes = frame_size_classes(opt.rgb_files)
     if len(classes) > 1:
         return _register_mixed_sizes(opt, all_files, classes)
-    files, frames, fscale = load_frames(opt.rgb_files, opt.image_resolution)
+    files, frames, fscale, *rgb = load_frames(opt.rgb_files, opt.image_resolution, return_rgb=opt.render_visualization)
     so = _session_options(opt, use_external_focal_length=opt.use_external_focal_length * fscale if opt.use_external_focal_length > 0 else -1.0,
                           ransac_iterations=opt.hypotheses, ransac_threshold=opt.threshold, register_seed=opt.base_seed, use_aug=False,
                           registration_confidence=opt.confidence_threshold)
@@ -591,7 +592,7 @@ def _register_from_images(opt):
         vis = _register_visualizer(opt)
         vis.setup_reloc(len(files) if opt.max_estimates <= 0 else min(opt.max_estimates, len(files)))
     poses, inl = ses.register(torch.load(opt.network, map_location="cpu"), ses.focal0, max_estimates=opt.max_estimates, max_tries=opt.hypotheses_max_tries,
-                              visualizer=vis)
+                              visualizer=vis, images=rgb[0] if rgb else None)
     out = Path(opt.network).parent / f"poses_{opt.session}.txt"
     write_pose_file(out, [files[i] for i in ses.registered_ids], poses, inl, ses.focal0 / fscale)
     _logger.info(f"Registered {len(poses)} images -> {out}")
@@ -650,6 +651,7 @@ def register_main(argv=None):
     if opt.render_visualization:
         vis = _register_visualizer(opt)
         vis.setup_reloc(n)
+        _logger.info("--feature_file holds no pixels: the registration frames show the frustums without their images")
         for k in range(n):
             vis.render_reloc_frame(poses[k].astype(np.float64), int(inl[k]))
         vis.save_reloc_state(os.path.join(str(opt.render_target_path), Path(opt.network).stem + "_register.pkl"))

@@ -3,10 +3,9 @@ export_cameras.py): the behaviour of the reference's ace_visualizer.py / ace_vis
 csrc/render_api.hip (acez_render_frame) instead of pyrender on OpenGL.
 
 Every frame is two layers drawn on the device: the point cloud (2 x 2 px points, depth-tested) and the camera geometry (flat RGBA
-triangles, depth-tested among themselves), blended on top of the points. Only the finished frame crosses to the host, where
-histograms and captions are drawn with matplotlib and the PNG is written with PIL as frame_%05d.png.
-
-Frustums are outlines only: the textured image thumbnails of the reference (get_image_box) are not drawn."""
+triangles and, in the registration phase, the query's image as a textured quad inside its frustum, depth-tested among themselves),
+on top of the points. Only the finished frame crosses to the host, where histograms and captions are drawn with matplotlib and the
+PNG is written with PIL as frame_%05d.png."""
 import ctypes as C
 import logging
 import math
@@ -134,6 +133,30 @@ FRUSTUM_VERTS = np.array([(0., 0., 0.), (0.375, -0.375, -1.0), (0.375, 0.375, -1
 FRUSTUM_EDGES = [(0, 1), (0, 2), (0, 3), (0, 4), (1, 2), (2, 3), (3, 4), (4, 1)]
 
 
+def image_box(pose_gl, aspect_ratio, size, flip=True):
+    """The image quad inside a frustum (ace_vis_util.get_image_box's geometry): (xyz float64 [2,3,3] world, uv float64 [2,3,2]).
+
+    In the camera frame (OpenGL) the quad lies at z = -size, 0.75 * size high and 0.75 * aspect_ratio * size wide; with `flip` the
+    width is negated (the reference mirrors the image left/right at the same time). UVs follow the acez_tex_triangle convention: u
+    across the image's columns from the left, v down its rows from the top. The reference's uvs (1,0) (1,1) (0,1) (0,0) at the four
+    corners index the image after its top/bottom flip (and the mirror with `flip`), counted from the bottom left: in the image as it
+    is stored that is the same v, and u = 1 - u with the mirror. Either way the image's top left lands at the camera's upper left."""
+    height = 0.75
+    width = height * aspect_ratio * size
+    height = height * size
+    if flip:
+        width = -width
+    corners = np.array([[width / 2, height / 2, -size], [width / 2, -height / 2, -size], [-width / 2, -height / 2, -size],
+                        [-width / 2, height / 2, -size]], np.float64)
+    uv = np.array([[1.0, 0.0], [1.0, 1.0], [0.0, 1.0], [0.0, 0.0]])
+    if flip:
+        uv[:, 0] = 1.0 - uv[:, 0]
+    hom = np.asarray(pose_gl, np.float64) @ np.concatenate([corners, np.ones((4, 1))], 1).T
+    world = (hom[:3] / hom[3]).T
+    faces = np.array([[0, 1, 2], [2, 3, 0]])
+    return world[faces], uv[faces]
+
+
 def frustum_outline(pose_gl, color=(255, 255, 255), size=0.3, aspect_ratio=4 / 3):
     """Camera frustum drawn as its 8 edges, each a cuboid_from_line: 64 vertices, 96 triangles."""
     v = FRUSTUM_VERTS.copy()
@@ -155,11 +178,13 @@ def box_marker(pose_gl, color=(125, 125, 125), extent=0.015):
 
 class CameraTrajectory:
     """Trajectory geometry: position markers, camera-path segments (a cuboid per step, skipped across jumps of more than 10 x the
-    median step) and frustums placed at least frustum_skip metres apart (unless sparse=False)."""
+    median step) and frustums placed at least frustum_skip metres apart (unless sparse=False); a frustum added with its image also
+    gets the image quad (frustum_images: (xyz [2,3,3], uv [2,3,2], uint8 image [h,w,3]) per frustum, what Renderer takes as
+    `textured`)."""
 
     def __init__(self, frustum_skip=0.0, frustum_scale=0.3):
         self.frustum_skip, self.frustum_scale = frustum_skip, frustum_scale
-        self.trajectory, self.frustums, self.frustum_positions = [], [], []
+        self.trajectory, self.frustums, self.frustum_positions, self.frustum_images = [], [], [], []
         self.previous, self.distances = None, []
         self.color = (255, 255, 255)
         self.aspect_ratio = 4 / 3
@@ -178,15 +203,23 @@ class CameraTrajectory:
     def add_position_marker(self, pose_gl, color, extent=0.015, frustum_marker_=False):
         self.trajectory.append(frustum_marker(pose_gl, color, extent) if frustum_marker_ else box_marker(pose_gl, color, extent))
 
-    def add_camera_frustum(self, pose_gl, sparse=True, color=None):
+    def add_camera_frustum(self, pose_gl, sparse=True, color=None, image=None):
+        """image: the camera's uint8 RGB frame [h,w,3] (numpy or a device tensor), drawn inside the frustum; its w / h becomes the
+        aspect ratio of this frustum and of the ones after it (the reference's aspect_ratio_buffer)."""
         pos = np.asarray(pose_gl, np.float64)[:3, 3]
         near = min((np.linalg.norm(p - pos) for p in self.frustum_positions), default=self.frustum_skip + 1)
         if not sparse or near > self.frustum_skip:
+            if image is not None:
+                h, w = int(image.shape[0]), int(image.shape[1])
+                self.aspect_ratio = w / h
+                xyz, uv = image_box(pose_gl, self.aspect_ratio, self.frustum_scale, flip=True)
+                self.frustum_images.append((xyz, uv, image))
             self.frustums.append(frustum_outline(pose_gl, self.color if color is None else color, self.frustum_scale, self.aspect_ratio))
             self.frustum_positions.append(pos)
 
     def clear_frustums(self):
         self.frustums.clear()
+        self.frustum_images.clear()
 
     def mesh(self):
         return Mesh.concatenate(self.trajectory + self.frustums)
@@ -299,7 +332,8 @@ def _ptr(t):
 
 
 class Renderer:
-    """ctypes wrapper of acez_render_frame: device scratch and output frame are allocated once per frame size."""
+    """ctypes wrapper of acez_render_frame / acez_render_frame_tex: device scratch and output frame are allocated once per frame
+    size; the textures' mip chains share one device block that grows only when a larger set of images arrives."""
 
     def __init__(self, width=WIDTH, height=HEIGHT, flipped_portrait=False, device=None, znear=ZNEAR, zfar=ZFAR):
         if not torch.cuda.is_available():
@@ -312,9 +346,54 @@ class Renderer:
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.work = torch.empty(2 * self.rw * self.rh, dtype=torch.int64, device=self.device)
         self.frame = torch.empty(self.rw * self.rh * 3, dtype=torch.uint8, device=self.device)
+        self.chains = torch.empty(0, dtype=torch.uint8, device=self.device)
 
-    def render_device(self, xyz, rgb, tri=None, tri_rgba=None, cam_to_world=None):
-        """Device tensors in, device frame out: uint8 [H][W][3] (the frame buffer is reused by the next call)."""
+    def _textures(self, textured):
+        """(acez_tex_triangle array, acez_texture array, texture count): every distinct image uploaded (unless it is a device
+        tensor already) and its mip chain built into self.chains, on the current stream."""
+        dev = self.device
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        images, index, tris = [], {}, []
+        for xyz, uv, img in textured:
+            if id(img) not in index:
+                index[id(img)] = len(images)
+                images.append(img)
+            xyz, uv = np.asarray(xyz, np.float32).reshape(-1, 3, 3), np.asarray(uv, np.float32).reshape(-1, 3, 2)
+            if len(xyz) != len(uv):
+                raise ValueError("one uv triple per textured triangle")
+            tris += [(a, b, index[id(img)]) for a, b in zip(xyz, uv)]
+        if len(tris) > N.RENDER_MAX_TEX_TRIANGLES or len(images) > N.RENDER_MAX_TEXTURES:
+            raise ValueError(f"at most {N.RENDER_MAX_TEX_TRIANGLES} textured triangles over {N.RENDER_MAX_TEXTURES} images per frame")
+        dimg, sizes, total = [], [], 0
+        for img in images:
+            t = torch.as_tensor(img)
+            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+                raise ValueError("a texture is a uint8 RGB image [h, w, 3]")
+            dimg.append(t.to(dev).contiguous())
+            levels, nbytes = C.c_int(), C.c_int64()
+            N.check(self.lib.acez_render_texture_size(int(t.shape[1]), int(t.shape[0]), C.byref(levels), C.byref(nbytes)))
+            sizes.append((total, int(t.shape[1]), int(t.shape[0])))
+            total += nbytes.value
+        if total > self.chains.numel():
+            self.chains = torch.empty(total, dtype=torch.uint8, device=dev)
+        table = (N.Texture * max(1, len(images)))()
+        for k, (img, (off, w, h)) in enumerate(zip(dimg, sizes)):
+            N.check(self.lib.acez_render_texture_build(_ptr(img), w, h, C.c_void_p(self.chains.data_ptr() + off), self.chains.numel() - off,
+                                                       stream))
+            table[k].offset, table[k].width, table[k].height = off, w, h
+        arr = (N.TexTriangle * max(1, len(tris)))()
+        for k, (a, b, ti) in enumerate(tris):
+            for i in range(3):
+                arr[k].xyz[i][:] = [float(x) for x in a[i]]
+                arr[k].uv[i][:] = [float(x) for x in b[i]]
+            arr[k].texture = ti
+        self._keep = dimg                                    # the uploads stay alive until the next frame
+        return arr, len(tris), table, len(images)
+
+    def render_device(self, xyz, rgb, tri=None, tri_rgba=None, cam_to_world=None, textured=None):
+        """Device tensors in, device frame out: uint8 [H][W][3] (the frame buffer is reused by the next call). textured: a list of
+        (xyz [k,3,3] world, uv [k,3,2], uint8 RGB image [h,w,3], numpy or device) drawn with acez_render_frame_tex; None or empty:
+        acez_render_frame."""
         dev = self.device
         xyz = torch.as_tensor(xyz, dtype=torch.float32).to(dev).reshape(-1, 3).contiguous()
         rgb = torch.as_tensor(rgb, dtype=torch.uint8).to(dev).reshape(-1, 3).contiguous()
@@ -323,15 +402,22 @@ class Renderer:
         if xyz.shape[0] != rgb.shape[0] or tri.shape[0] != tri_rgba.shape[0]:
             raise ValueError("one colour per point and per triangle")
         cam = (C.c_double * 16)(*np.asarray(cam_to_world, np.float64).reshape(16).tolist())
-        N.check(self.lib.acez_render_frame(_ptr(xyz), _ptr(rgb), int(xyz.shape[0]), _ptr(tri), _ptr(tri_rgba), int(tri.shape[0]), cam,
-                                           self.znear, self.zfar, self.rw, self.rh, int(self.flipped), _ptr(self.work), _ptr(self.frame),
-                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if textured:
+            arr, n_tex_tris, table, n_textures = self._textures(textured)
+            N.check(self.lib.acez_render_frame_tex(_ptr(xyz), _ptr(rgb), int(xyz.shape[0]), _ptr(tri), _ptr(tri_rgba), int(tri.shape[0]), arr,
+                                                   n_tex_tris, table, n_textures, _ptr(self.chains), self.chains.numel(), cam, self.znear,
+                                                   self.zfar, self.rw, self.rh, int(self.flipped), _ptr(self.work), _ptr(self.frame), stream))
+        else:
+            N.check(self.lib.acez_render_frame(_ptr(xyz), _ptr(rgb), int(xyz.shape[0]), _ptr(tri), _ptr(tri_rgba), int(tri.shape[0]), cam,
+                                               self.znear, self.zfar, self.rw, self.rh, int(self.flipped), _ptr(self.work), _ptr(self.frame),
+                                               stream))
         shape = (self.rw, self.rh, 3) if self.flipped else (self.rh, self.rw, 3)
         return self.frame.view(*shape)
 
-    def render(self, xyz, rgb, tri=None, tri_rgba=None, cam_to_world=None):
+    def render(self, xyz, rgb, tri=None, tri_rgba=None, cam_to_world=None, textured=None):
         """The frame on the host: uint8 numpy [H][W][3] (the one device -> host copy of a frame)."""
-        return self.render_device(xyz, rgb, tri, tri_rgba, cam_to_world).cpu().numpy()
+        return self.render_device(xyz, rgb, tri, tri_rgba, cam_to_world, textured).cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------------ overlays and files
@@ -422,7 +508,7 @@ class Visualizer:
     def _render(self):
         xyz, clr, _ = self.cloud.get()
         tri, rgba = self.trajectory.mesh().triangles()
-        return self.renderer.render(xyz, clr, tri, rgba, self.camera.current_view())
+        return self.renderer.render(xyz, clr, tri, rgba, self.camera.current_view(), self.trajectory.frustum_images)
 
     def _save(self, image):
         path = save_frame(self.target_path, self.frame_idx, image)
@@ -532,14 +618,15 @@ class Visualizer:
         self.trajectory = CameraTrajectory(frustum_skip=0, frustum_scale=0.3)
         self.reloc_conf, self.reloc_count, self.reloc_counter, self.reloc_success = [], frame_count, 0, 0
 
-    def render_reloc_frame(self, est_pose_c2w_cv, confidence):
-        """One registration frame: the query's frustum coloured by confidence; earlier registered queries stay as markers. At most
-        RELOC_DURATION frames per run: with more queries every k-th one is rendered (k = count // RELOC_DURATION)."""
+    def render_reloc_frame(self, est_pose_c2w_cv, confidence, image=None):
+        """One registration frame: the query's frustum coloured by confidence, with the query's uint8 RGB frame `image` [h,w,3] inside
+        it (None: the outline alone); earlier registered queries stay as markers. At most RELOC_DURATION frames per run: with more
+        queries every k-th one is rendered (k = count // RELOC_DURATION)."""
         pose = cv_to_gl(est_pose_c2w_cv)
         self.reloc_conf.append(confidence)
         color = self.reloc_cmap[min(int(confidence / self.reloc_conf_threshold * 255), 255)] * 255
         self.trajectory.clear_frustums()
-        self.trajectory.add_camera_frustum(pose, sparse=False, color=color)
+        self.trajectory.add_camera_frustum(pose, sparse=False, color=color, image=image)
         if confidence > self.confidence_threshold:
             self.reloc_success += 1
             if self.reloc_prev is not None:

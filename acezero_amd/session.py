@@ -710,7 +710,7 @@ class ReconstructionSession:
         head.close()
         return out
 
-    def register(self, head_sd, focal, max_estimates=-1, tag="register", max_tries=16, rng_ids=None, visualizer=None):
+    def register(self, head_sd, focal, max_estimates=-1, tag="register", max_tries=16, rng_ids=None, visualizer=None, images=None):
         """register_mapping.py:201-276: (poses cam->world [k,4,4] float32, inlier counts [k] int32); the k frame ids they belong to
         are left in self.registered_ids (all frames in order unless max_estimates draws a subset).
 
@@ -721,7 +721,9 @@ class ReconstructionSession:
         partition, and one gather returns every frame's result to every rank. Head and RANSAC run once per size class, with that
         class's principal point and every frame's own focal (`focal` is the nominal one, see __init__). rng_ids: the ids that key
         the random streams, if they are not the positions in this session.
-        visualizer (acezero_amd.render.Visualizer, set up with setup_reloc): one registration frame per registered frame, in order."""
+        visualizer (acezero_amd.render.Visualizer, set up with setup_reloc): one registration frame per registered frame, in order,
+        each with that frame's uint8 RGB image inside its frustum: images[i] for frame i (default: the visualiser's frame_rgb; none:
+        outlines only)."""
         o = self.opt
         if max_estimates <= 0 or max_estimates >= self.n:
             ids = np.arange(self.n)
@@ -750,8 +752,10 @@ class ReconstructionSession:
         self.timings["register_s"] += time.time() - t0
         _logger.info(f"[{tag}] {len(ids)} frames in {time.time() - t0:.2f}s, {rate * 100:.1f}% above confidence {o.registration_confidence}")
         if visualizer is not None:
+            if images is None:
+                images = visualizer.frame_rgb
             for k in range(len(ids)):
-                visualizer.render_reloc_frame(np.asarray(poses[k], np.float64), int(inl[k]))
+                visualizer.render_reloc_frame(np.asarray(poses[k], np.float64), int(inl[k]), None if images is None else images[int(ids[k])])
         return poses, inl
 
     # --------------------------------------------------------------------------------------------------- the loop (ace_zero.py)

@@ -543,6 +543,45 @@ int acez_align_evaluate(acez_align* ctx, const double* gt_c2w, const double* est
 int acez_render_frame(const float* d_xyz, const uint8_t* d_rgb, int64_t n_points, const float* d_tri_xyz, const uint8_t* d_tri_rgba,
                       int64_t n_tris, const double* cam_to_world, float znear, float zfar, int width, int height, int flipped_portrait,
                       unsigned long long* d_work, uint8_t* d_frame, void* stream);
+/* Textured triangles (the image thumbnails inside the registration frustums, ace_vis_util.get_image_box). A texture is a uint8
+ * [h][w][3] RGB image (row 0 at the top) followed by its mip chain in one device block built by acez_render_texture_build: level
+ * k + 1 is max(1, w_k / 2) x max(1, h_k / 2) (integer halving), level k starts right after level k - 1, and each texel of level k + 1
+ * is (a + b + c + d + 2) >> 2 per channel over the 2 x 2 block at (2x, 2y) of level k, the block's second column / row clamped to the
+ * level's last one (only a level 1 texel wide or high needs it). */
+#define ACEZ_RENDER_MAX_TEX_TRIANGLES 32
+#define ACEZ_RENDER_MAX_TEXTURES 16
+typedef struct acez_tex_triangle {
+  float xyz[3][3];        /* world vertices (OpenGL convention), like a row of d_tri_xyz */
+  float uv[3][2];         /* per-vertex (u, v): u across the image's columns (0 = left edge, 1 = right edge), v down its rows (0 = top) */
+  int32_t texture;        /* index into the texture table */
+  int32_t reserved;       /* 0 */
+} acez_tex_triangle;
+typedef struct acez_texture {
+  int64_t offset;         /* byte offset of level 0 in d_texels */
+  int32_t width, height;  /* level 0 size */
+} acez_texture;
+/* Levels and bytes of the chain of a width x height texture (host only): levels = 1 + floor(log2(max(width, height))). */
+int acez_render_texture_size(int width, int height, int* out_levels, int64_t* out_bytes);
+/* The chain of a device uint8 [height][width][3] image into d_chain (chain_bytes >= acez_render_texture_size's bytes): level 0 is a
+ * copy of the image, then one launch per level. Asynchronous on `stream`. */
+int acez_render_texture_build(const uint8_t* d_image, int width, int height, uint8_t* d_chain, int64_t chain_bytes, void* stream);
+/* acez_render_frame with up to ACEZ_RENDER_MAX_TEX_TRIANGLES textured triangles (host array; they travel to the kernels as launch
+ * arguments, so every index is checked here before anything is launched) over up to ACEZ_RENDER_MAX_TEXTURES textures (host table,
+ * each chain wholly inside d_texels[0, texel_bytes)). Textured triangle t takes triangle id n_tris + t in the SAME key plane as the
+ * flat ones: it is clipped, snapped and filled by the same rules and depth-tests against them. A pixel it wins takes the texel colour
+ * (opaque: alpha 255) instead of the point colour:
+ *   uv        perspective-correct at the pixel centre: the pixel's ray meets the triangle's plane in camera space; barycentrics from
+ *             the three triple products with the unclipped vertices (independent of near-plane clipping);
+ *   lod       rho^2 = max(|d(s,t)/dx|^2, |d(s,t)/dy|^2) from the analytic screen-space derivatives of (s, t) = (u w, v h) in level-0
+ *             texels; lambda = log2(rho^2) / 2 with log2(m 2^e) ~ e + (m - 1) for m in [1, 2) (exact in float: the exponent and the
+ *             mantissa bits). lambda <= 0 (rho^2 <= 1): level 0; otherwise levels floor(lambda) and floor(lambda) + 1 mixed by the
+ *             fraction (GL's LINEAR_MIPMAP_LINEAR), the last level alone from there on, and for a rho^2 that is not finite;
+ *   filter    bilinear per level about texel centres (s - 1/2, t - 1/2), clamp to edge; the mixed float colour + 1/2 truncated.
+ * Every float operation is the one tests/render_texture_oracle.py restates. n_tex_tris == 0 gives acez_render_frame's frame. */
+int acez_render_frame_tex(const float* d_xyz, const uint8_t* d_rgb, int64_t n_points, const float* d_tri_xyz, const uint8_t* d_tri_rgba,
+                          int64_t n_tris, const acez_tex_triangle* tex_tris, int n_tex_tris, const acez_texture* textures, int n_textures,
+                          const uint8_t* d_texels, int64_t texel_bytes, const double* cam_to_world, float znear, float zfar, int width,
+                          int height, int flipped_portrait, unsigned long long* d_work, uint8_t* d_frame, void* stream);
 /* Exported for the CPU tests (tests/test_render_cpu.py checks the camera set-up against tests/render_oracle.py without a GPU); the
  * product calls it only through acez_render_frame. The camera acez_render_frame projects with (host only, no device needed): out_w2c12 float32 [3][4] = [R^T | -R^T t] of the rigid
  * cam_to_world, computed in double and rounded once; out_focal = (height / 2) * sqrt(3) in pixels. Same argument checks. */
