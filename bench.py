@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""bench.py -- throughput of the ACE Zero hot path on MI355X (contract: see the round prompt / DESIGN.md).
+"""bench.py -- throughput of the ACE Zero hot path on MI355X (contract: DESIGN.md section 6).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
                                                                (N > 1 without a launcher's environment: re-executes itself under
                                                                 torch.distributed.run with N ranks, one per GPU)
 
@@ -9,9 +9,13 @@ K is the number of timed headline steps (one window after W warm-up steps); `ms_
 --dump-outputs the state the last timed step left (head parameters, AdamW moments, the batch's scene coordinates, the step's scalars) is
 written to DIR/<name>.npy; every input is seeded, so two builds run with the same arguments can be compared output for output.
 
+A plain run does only that: set-up, warm-up, the K timed steps, the dump if asked for, and the JSON line with the headline figure. Every
+other leg described below (other precisions and configurations, registration, the pipeline and session legs, data-parallel proxies, the
+roofline figures, the device state, the CPU baseline) runs with --full alone, which prints the same headline fields and the rest beside them.
+
 A "step" is one training iteration of the scene-coordinate head (ace_trainer.py:499-679) on 5120 patches per
 GPU drawn from an 8M-patch synthetic feature buffer resident in HBM (BASELINE config[1]: full ace_zero.py
-mapping on one MI355X, default head).  `value` = patches/s of the whole job.  The same run also times the second
+mapping on one MI355X, default head).  `value` = patches/s of the whole job.  With --full the same run also times the second
 half of the metric, DSAC* registration (images/s, scene coordinates resident in HBM, ace_zero's 32 hypotheses /
 16 tries), and reports it under "registration".  With N > 1 the feature buffer is sharded across ranks
 (each rank owns buffer_patches/N rows... here: its own 8M/N-row shard), every rank runs 5120 rows per step and the
@@ -19,7 +23,7 @@ gradient bucket is exchanged over RCCL once per step (reduce-scatter by layer, s
 scaling: global batch = 5120 N);
 registration frames are sharded across ranks with no collective.
 
-Extra objects on the JSON line: "roofline" for the dominant kernel (rowgemm_kernel, bf16 MFMA), measured live
+Extra objects on the --full JSON line: "roofline" for the dominant kernel (rowgemm_kernel, bf16 MFMA), measured live
 with HIP events on the launch stream, and "cpu_baseline": the oracle (a port -- the reference cannot run on the
 GPU box) timed on the host cores on a bounded sample.
 """
@@ -125,16 +129,22 @@ def parse():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--buffer-patches", type=int, default=8_000_000)   # train_ace.py:122
-    ap.add_argument("--reg-frames", type=int, default=2048)
-    ap.add_argument("--e2e-frames", type=int, default=1088)   # 8 passes of 136 frames
+    ap.add_argument("--reg-frames", type=int, default=2048, help="with --full: frames of the registration leg")
+    ap.add_argument("--e2e-frames", type=int, default=1088, help="with --full: frames of the images -> poses leg")   # 8 passes of 136 frames
     ap.add_argument("--pose-refinement", default="none", choices=["none", "mlp"])   # ace_zero.py:86 maps every non-seed iteration with mlp
-    ap.add_argument("--session-frames", type=int, default=120, help="frames of the in-process ACE0 reconstruction leg (N = 1 only; 0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp16"), help="with --headline-only: operand type of the timed step (diagnostics; the default line is bf16 + a dtype_fp16 leg)")
-    ap.add_argument("--headline-only", action="store_true", help="only the timed training steps (the leg rocprofv3 is pointed at: tools/prof_r02.sh)")
+    ap.add_argument("--session-frames", type=int, default=120, help="with --full: frames of the in-process ACE0 reconstruction leg (N = 1 only; 0 = skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp16"), help="with --headline-only: operand type of the timed step (diagnostics; the headline is bf16, --full adds a dtype_fp16 leg)")
+    mode = ap.add_mutually_exclusive_group()
+    mode.add_argument("--full", action="store_true",
+                      help="after the headline leg, run every auxiliary leg (other precisions and configurations, registration, pipeline, session, "
+                           "data-parallel proxies, roofline, device state, CPU baseline) and put their figures on the line")
+    mode.add_argument("--headline-only", action="store_true",
+                      help="the headline leg, then per-kernel-class HIP-event times of 20 more steps and the device state (the leg rocprofv3 is "
+                           "pointed at: tools/prof_r02.sh)")
     # control-flow smoke of the N > 1 path on a ONE-GPU box: every rank on cuda:0, gloo instead of RCCL (not a measurement)
     ap.add_argument("--smoke-same-device", action="store_true")
-    # internal: the one-rank RCCL legs as a child process of the default run (dp_world1_legs)
+    # internal: the one-rank RCCL legs as a child process of the --full run (dp_world1_legs)
     ap.add_argument("--dp-world1-legs", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (head parameters, AdamW moments, the batch's scene "
@@ -180,9 +190,10 @@ def dump_outputs(tr, dump_dir, rows):
 
 
 def bench_training(args, rank, world, device, pose_refinement=None, steps=None, buffer_patches=None, strong=False, windows=WINDOWS,
-                   n_images=1000, grid=(80, 60), dtype="bf16", dump_dir=None):
+                   n_images=1000, grid=(80, 60), dtype="bf16", dump_dir=None, profile=True):
     """pose_refinement None -> args.pose_refinement (the headline leg); 'mlp' -> ace_zero's non-seed mapping iterations
     (--pose_refinement mlp --refine_calibration True, ace_zero.py:86,97,262-264).
+    profile=False: no per-kernel-class leg after the timed windows (the returned profile is None).
     strong=True: the REFERENCE's step on N GPUs -- the global batch stays 5120, every rank draws the same permutation of the global
     buffer and runs the rows of each slice that live in its shard (about 5120 / N), one all-reduce of the gradient bucket per step
     (what `torchrun ace_zero.py` runs inside a mapping round); strong=False: 5120 rows per GPU, global batch 5120 N (weak)."""
@@ -256,12 +267,14 @@ def bench_training(args, rank, world, device, pose_refinement=None, steps=None, 
     # roofline leg: per-kernel-class durations from HIP events on the launch stream (outside the timed region:
     # the events themselves perturb the step time)
     # every rank runs these 20 steps (with N > 1 a step contains an all-reduce: a rank-0-only loop would deadlock)
-    tr.set_profiling(True)
-    for i in range(20):
-        step(args.warmup + windows * steps + i)
-    torch.cuda.synchronize()
-    prof = tr.get_profile()
-    tr.set_profiling(False)
+    prof = None
+    if profile:
+        tr.set_profiling(True)
+        for i in range(20):
+            step(args.warmup + windows * steps + i)
+        torch.cuda.synchronize()
+        prof = tr.get_profile()
+        tr.set_profiling(False)
     if dist is not None:
         dist.barrier()
     return dt, st, prof
@@ -663,6 +676,20 @@ def claim_stdout():
     return os.fdopen(line_fd, "w")
 
 
+def headline_fields(args, world, rccl_ranks, dt, st):
+    """The headline leg's fields, first on the plain and on the --full line alike: dt = the one timed window of --steps steps (the slowest
+    rank's with N > 1)."""
+    return {
+        "metric": "ACE patches/sec", "value": BATCH * world * args.steps / dt, "unit": "patches/s", "n_gpus": world, "rccl_ranks": rccl_ranks,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "ms_per_step_mean": dt / args.steps * 1e3,
+        "window_ms_per_step": st["window_ms_per_step"], "windows": 1, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": "7-Scenes-chess-like ace_zero mapping step: 8M-patch bf16 feature buffer in HBM, batch 5120 per GPU, "
+                               "default head (1 block, 2 103 300 params), tanh loss, 1cyclepoly AdamW, pose_refinement " + args.pose_refinement,
+                   "buffer_patches": args.buffer_patches, "batch_per_gpu": BATCH, "global_batch": BATCH * world,
+                   "parallelism": f"dp{world}" + ("" if world == 1 else " (" + ("one all-reduce of the gradient bucket, replicated AdamW" if dp_mode_name() == "allreduce" else "reduce-scatter of the weight gradients by layer, AdamW on the owned layers, all-gather of the 16-bit weights") + ")")}}
+
+
 def main():
     args = parse()
     if not torch.cuda.is_available():
@@ -694,22 +721,24 @@ def main():
 
     # the headline leg: exactly --steps timed steps (one window), ms_per_step = that window / --steps
     dt, st, prof = bench_training(args, rank, world, device, dtype=args.dtype if args.headline_only else "bf16", windows=1,
-                                  dump_dir=args.dump_outputs)
-    dev_state = device_state(device) if rank == 0 else None
-    if args.headline_only:
+                                  dump_dir=args.dump_outputs, profile=args.full or args.headline_only)
+    dev_state = device_state(device) if rank == 0 and (args.full or args.headline_only) else None
+    if not args.full:
         if world > 1:
-            t = torch.tensor([dt], device=device, dtype=torch.float64)
+            t = torch.tensor([dt] + st["window_ms_per_step"], device=device, dtype=torch.float64)
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-            dt = float(t[0])
+            dt, st["window_ms_per_step"] = float(t[0]), [float(x) for x in t[1:]]
             torch.distributed.barrier()
             torch.distributed.destroy_process_group()
-        if rank == 0:
+        if rank == 0 and args.headline_only:
             print(json.dumps({"metric": "ACE patches/sec", "value": BATCH * world * args.steps / dt, "unit": "patches/s", "n_gpus": world,
                               "rccl_ranks": rccl_ranks, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
                               "ms_per_step_mean": dt / args.steps * 1e3, "window_ms_per_step": st["window_ms_per_step"], "headline_only": True,
                               "pose_refinement": args.pose_refinement, "dtype": args.dtype,
                               "per_class_us_per_step": {k: v[0] / 20 * 1e3 for k, v in prof.items()}, "final_loss": st["loss"], "device_state": dev_state}),
                   file=line_out, flush=True)
+        elif rank == 0:
+            print(json.dumps({**headline_fields(args, world, rccl_ranks, dt, st), "final_loss": st["loss"]}), file=line_out, flush=True)
         return
     # the headline step with fp16 operands (the reference's autocast precision; HeadTrainer(dtype="fp16")): same kernels, same rate
     dt_f16, st_f16, _ = bench_training(args, rank, world, device, steps=100, buffer_patches=min(args.buffer_patches, 2_000_000), dtype="fp16")
@@ -819,14 +848,7 @@ def main():
                         "session_register_frac": (tm.get("register_s") / tot) if tot and tm else None,
                         "session_1000_registered": (ss or {}).get("registered"), "session_1000_source": ss_why or "profiles/%s_session_1000_frames.json" % PROFILE_TAG})
         out = {
-            "metric": "ACE patches/sec", "value": patches_per_s, "unit": "patches/s", "n_gpus": world, "rccl_ranks": rccl_ranks, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "ms_per_step_mean": dt / args.steps * 1e3,
-            "window_ms_per_step": st["window_ms_per_step"], "windows": 1, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": "7-Scenes-chess-like ace_zero mapping step: 8M-patch bf16 feature buffer in HBM, batch 5120 per GPU, "
-                                   "default head (1 block, 2 103 300 params), tanh loss, 1cyclepoly AdamW, pose_refinement " + args.pose_refinement,
-                       "buffer_patches": args.buffer_patches, "batch_per_gpu": BATCH, "global_batch": BATCH * world,
-                       "parallelism": f"dp{world}" + ("" if world == 1 else " (" + ("one all-reduce of the gradient bucket, replicated AdamW" if dp_mode_name() == "allreduce" else "reduce-scatter of the weight gradients by layer, AdamW on the owned layers, all-gather of the 16-bit weights") + ")")},
+            **headline_fields(args, world, rccl_ranks, dt, st),
             "summary": summary,
             "whole_step_flop_frac_of_mfma_peak": patches_per_s / world * FLOP_PER_PATCH / (MFMA_PEAK_TFLOPS * 1e12),
             "strong_scaling": None if dt_strong is None else {

@@ -11,8 +11,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(out_dir, steps, warmup):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--headline-only", "--steps", str(steps), "--warmup", str(warmup),
+def _run(out_dir, steps, warmup, mode=("--headline-only",)):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *mode, "--steps", str(steps), "--warmup", str(warmup),
            "--buffer-patches", "262144", "--dump-outputs", str(out_dir)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
@@ -42,5 +42,19 @@ def test_dump_outputs_hold_the_last_timed_step_and_repeat(tmp_path):
     _run(tmp_path / "b", steps, warmup)
     b = _load(tmp_path / "b")
     assert sorted(b) == sorted(a)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_what_the_headline_leg_dumps(tmp_path):
+    """Without --full or --headline-only the run times the same steps on the same inputs: the same arrays, and a line of the headline
+    fields alone."""
+    line = _run(tmp_path / "plain", 3, 2, mode=())
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    assert not {"summary", "roofline", "registration", "per_class_us_per_step", "device_state", "cpu_baseline"} & set(line)
+    _run(tmp_path / "headline", 3, 2)
+    a, b = _load(tmp_path / "plain"), _load(tmp_path / "headline")
+    assert sorted(a) == sorted(b)
     for k in a:
         assert np.array_equal(a[k], b[k]), k

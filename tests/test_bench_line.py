@@ -3,6 +3,7 @@ the tier framing name is present and consistent; guards the assembly code, which
 import io
 import json
 import sys
+import types
 from contextlib import redirect_stdout
 
 import pytest
@@ -35,7 +36,7 @@ def test_bench_json_line_contract(monkeypatch, seq):
                                                             "cloud_frames": 256, "cloud_s": 1.4e-4, "cloud_points": 256000})
     monkeypatch.setattr(bench, "bench_session", lambda *a: {"frames": 120, "seconds": 5.4})
     monkeypatch.setattr(bench, "cpu_baseline", lambda: {"value": 5.9e4, "unit": "patches/s", "cores": 32, "kind": "port", "sample": "mock"})
-    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
     out = io.StringIO()
     with redirect_stdout(out):
         bench.main()
@@ -85,6 +86,38 @@ def test_bench_json_line_contract(monkeypatch, seq):
     w1 = d["dp_rank_proxy"]["world1_exchange"]
     assert w1["allreduce_rccl_ms"] == 0.150 and w1["sharded_rccl_ms"] == 0.150 and sm["dp_world1_exchange_rccl_ms"] == r["summary_dp_world1_exchange_rccl_ms"] == 0.150
     assert d["dp_rank_proxy"]["mode"] == "allreduce"
+
+
+def test_plain_run_times_the_headline_leg_alone(monkeypatch, tmp_path):
+    """Without --full, bench.py runs set-up, warm-up, the --steps timed steps and the dump, and prints the headline fields the --full line
+    starts with: no auxiliary leg, no per-kernel-class profile, no device probe."""
+    import bench
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    win, calls = 0.1553, []
+
+    def training(*a, **k):
+        calls.append(k)
+        return 7 * win * 1e-3, {"loss": 22.3, "focal_scale": 1.01, "window_ms_per_step": [win]}, None
+    monkeypatch.setattr(bench, "bench_training", training)
+
+    def auxiliary(*a, **k):
+        raise AssertionError("a plain run must not run this leg")
+    for name in ("bench_registration", "bench_pipeline", "bench_session", "bench_dp_rank_proxy", "dp_world1_legs", "cpu_baseline", "device_state"):
+        monkeypatch.setattr(bench, name, auxiliary)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(tmp_path)])
+    out = io.StringIO()
+    with redirect_stdout(out):
+        bench.main()
+    lines = [ln for ln in out.getvalue().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert len(calls) == 1 and calls[0]["windows"] == 1 and calls[0]["profile"] is False and calls[0]["dump_dir"] == str(tmp_path)
+    assert d["metric"] == "ACE patches/sec" and d["unit"] == "patches/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert abs(d["value"] - 5120 / (win * 1e-3)) < 1 and abs(d["ms_per_step"] - win) < 1e-9 and d["window_ms_per_step"] == [win]
+    assert d["steps"] == 7 and d["warmup"] == 3 and d["n_gpus"] == 1 and d["final_loss"] == 22.3
+    args = types.SimpleNamespace(steps=7, warmup=3, buffer_patches=8_000_000, pose_refinement="none")
+    assert list(d) == list(bench.headline_fields(args, 1, 0, 7 * win * 1e-3, {"window_ms_per_step": [win]})) + ["final_loss"]
 
 
 def test_gpus_flag_without_a_launcher_re_executes_under_torchrun(monkeypatch):
