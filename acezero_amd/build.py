@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libacez.so")
 STAMP = os.path.join(HERE, ".libacez.stamp")
-# the diagnostics build (-DACEZ_DIAG): ablation switches, measured-and-rejected kernels, fault-injection hooks. tests/ and tools/ only
+# the diagnostics build (-DACEZ_DIAG): reference-flow switches, device timelines, fault-injection hooks. tests/ and tools/ only
 # (acezero_amd._native.diag_library()); nothing in the product loads it.
 LIB_DIAG = os.path.join(HERE, "libacez_diag.so")
 STAMP_DIAG = os.path.join(HERE, ".libacez_diag.stamp")

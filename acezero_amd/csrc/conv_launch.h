@@ -26,8 +26,6 @@ struct ConvGemmArgs {
   int f16;                // 16-bit operand format of In / W / add / out: 0 = bf16, 1 = fp16 (fp32 accumulation in both)
   int round_before_add;   // 1: the activation is rounded to 16 bits BEFORE the residual is added (the head stores it: ace_network.py:126,133)
   unsigned long long* trace;   // diagnostics build (tools/conv_trace.py): [tiles][8] s_memtime stamps of convgemm512's waves 0 and 8; else null
-  int dbg;   // ablation (ACEZ_CONV_DBG; 0 in production). convgemm256/512: 2 = no MFMA, 4 = no loads. conv3x3p (loader side only):
-             // 32 = weight DMA from 16 hot rows (same bytes into LDS), 64 = every other weight stage not fetched
 };
 
 // tile_mode: 0 = choose by size, 80 / 256 / 512 = force that kernel where the layer shape allows it

@@ -82,9 +82,6 @@ __device__ __forceinline__ void wait_vmcnt_dyn_c12(int n) {   // s_waitcnt vmcnt
     default: ACEZ_VMCNT(0); break;
   }
 }
-#ifndef C12_ABL
-#define C12_ABL 0   // timing-only ablation of conv12p (tools/c12_variants.sh): 1 = no conv1, 2 = no conv2, 4 = no output stores, 8 = no patch writes
-#endif
 template <class E, int TR>
 __global__ __launch_bounds__(512) void conv12p_kernel(Conv12Args a) {
   typedef typename E::frag frag;
@@ -148,7 +145,7 @@ __global__ __launch_bounds__(512) void conv12p_kernel(Conv12Args a) {
       int n_stores = 0;
       if (j + 2 < K && j + 2 > 0) stage_img(j + 2);
       // ---- conv2 of tile j: output row w, pixels x = fr, channels 2 x 32
-      if (j >= 0 && w < TR && !(C12_ABL & 2)) {
+      if (j >= 0 && w < TR) {
         const int tile = tile_of(j);
         const int f = tile / tpf, r = tile - f * tpf;
         const int ty = r / tiles_x, tx = r - ty * tiles_x;
@@ -193,7 +190,7 @@ __global__ __launch_bounds__(512) void conv12p_kernel(Conv12Args a) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         const int oy = TR * ty + w, ox0 = 32 * tx;
-        if (oy < a.H2 && !(C12_ABL & 4)) {
+        if (oy < a.H2) {
           n_stores = min(4, max(0, (a.W2 - ox0 + 7) >> 3));   // store instructions with at least one active lane (the others are branched over)
 #pragma unroll
           for (int it = 0; it < 4; ++it) {
@@ -237,7 +234,7 @@ __global__ __launch_bounds__(512) void conv12p_kernel(Conv12Args a) {
     }
     for (int j = -2; j < K; ++j) {
       const int c = j + 1;
-      if (c >= 0 && c < K && !(C12_ABL & 1)) {
+      if (c >= 0 && c < K) {
         const int tile = tile_of(c);
         const int f = tile / tpf, r = tile - f * tpf;
         const int ty = r / tiles_x, tx = r - ty * tiles_x;
@@ -272,7 +269,7 @@ __global__ __launch_bounds__(512) void conv12p_kernel(Conv12Args a) {
             const int cy = cy0 + f_py[u], cx = cx0 + f_px[u];
             inside = cy >= 0 && cy < a.H && cx >= 0 && cx < a.W;
           }
-          if (f_py[u] >= 0 && !(C12_ABL & 8)) {
+          if (f_py[u] >= 0) {
             uint16_t* dst = sp + f_dst[u];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {   // channels 8g + 4 fh .. +3 = half of logical chunk g
@@ -613,8 +610,7 @@ __global__ __launch_bounds__(1024) void convgemm256_kernel(ConvGemmArgs a) {
         __builtin_amdgcn_global_load_lds((gvoid_t*)g, (lvoid_t*)(slot + 128 * 64 + (lw * 4 + j) * 8 * 64), 16, 0, 0);
       }
     };
-    const bool do_loads = !(ACEZ_DBG(a.dbg) & 4);
-    if (do_loads) for (int kt = 0; kt < 3 && kt < KT; ++kt) issue(kt);
+    for (int kt = 0; kt < 3 && kt < KT; ++kt) issue(kt);
     for (int kt = 0; kt < KT; ++kt) {
       // issued so far: 0..2 at kt = 0, 0..kt+1 afterwards; 6 DMA instructions per stage, in-order completion
       const int later = (kt == 0) ? min(2, KT - 1) : min(1, KT - 1 - kt);
@@ -622,7 +618,7 @@ __global__ __launch_bounds__(1024) void convgemm256_kernel(ConvGemmArgs a) {
       else if (later == 1) ACEZ_VMCNT(6);
       else ACEZ_VMCNT(0);
       __builtin_amdgcn_s_barrier();   // stage kt has landed; the multipliers are done with stage kt - 1
-      if (do_loads && kt >= 1 && kt + 2 < KT) issue(kt + 2);
+      if (kt >= 1 && kt + 2 < KT) issue(kt + 2);
       if (HAS_ADD && kt == KT - 1) {
         // slots 0-1 are free from here on (KT >= 3 for every layer that has a residual input): residual tile -> stO
 #pragma unroll
@@ -649,7 +645,6 @@ __global__ __launch_bounds__(1024) void convgemm256_kernel(ConvGemmArgs a) {
     const int fr = l & 31, fh = l >> 5;
     for (int kt = 0; kt < KT; ++kt) {
       __builtin_amdgcn_s_barrier();
-      if (ACEZ_DBG(a.dbg) & 2) continue;
       const uint16_t* sW = smem + ((kt + rot) % 3) * STAGE;
       const uint16_t* sI = sW + 128 * 64;
 #pragma unroll
@@ -797,8 +792,7 @@ __global__ __launch_bounds__(768) void convgemm512_kernel(ConvGemmArgs a) {
         __builtin_amdgcn_global_load_lds((gvoid_t*)g, (lvoid_t*)(slot + 256 * 32 + (lw * 4 + j) * 16 * 32), 16, 0, 0);
       }
     };
-    const bool do_loads = !(ACEZ_DBG(a.dbg) & 4);
-    if (do_loads) for (int kt = 0; kt < 4 && kt < KT; ++kt) issue(kt);
+    for (int kt = 0; kt < 4 && kt < KT; ++kt) issue(kt);
     for (int kt = 0; kt < KT; ++kt) {
       const int later = (kt == 0) ? min(3, KT - 1) : min(2, KT - 1 - kt);
       if (later >= 3) ACEZ_VMCNT(24);
@@ -807,7 +801,7 @@ __global__ __launch_bounds__(768) void convgemm512_kernel(ConvGemmArgs a) {
       else ACEZ_VMCNT(0);
       __builtin_amdgcn_s_barrier();   // stage kt has landed; the multipliers are done with stage kt - 1
       if (kt == 0) CG_STAMP(1);
-      if (do_loads && kt >= 1 && kt + 3 < KT) issue(kt + 3);
+      if (kt >= 1 && kt + 3 < KT) issue(kt + 3);
     }
     __builtin_amdgcn_s_barrier();     // the multipliers have left the K loop: the ring is free
     CG_STAMP(2);
@@ -835,7 +829,6 @@ __global__ __launch_bounds__(768) void convgemm512_kernel(ConvGemmArgs a) {
     const int fr = l & 31, fh = l >> 5;
     for (int kt = 0; kt < KT; ++kt) {
       __builtin_amdgcn_s_barrier();
-      if (ACEZ_DBG(a.dbg) & 2) continue;
       const uint16_t* sW = smem + (kt & 3) * STAGE;
       const uint16_t* sI = sW + 256 * 32;
 #pragma unroll
@@ -915,7 +908,7 @@ __global__ __launch_bounds__(768) void convgemm512_kernel(ConvGemmArgs a) {
 constexpr int P3_ROWS = 448;
 
 // ---------------------------------------------------------------------------------------------------
-// conv3x3r: the lean stage loop (round 2). Ablation of conv3x3p on MI355X (tools/enc_kstats.sh): with the LDS-DMA AND
+// conv3x3r: the lean stage loop (round 2). Ablation of conv3x3p on MI355X (tools/enc_kstats.sh, git history): with the LDS-DMA AND
 // the MFMAs switched off the 3x3 kernels still take 50 % of their time; loads add 10 %, MFMAs 40 %. The "skeleton" is the stage
 // loop itself: per 32-wide K stage a wave executes ~180 scalar / vector / branch instructions (tap decode, nine-way validity
 // selects, swizzled fragment addresses, the vmcnt switch, slot arithmetic) around its 16 MFMAs -- ~1250 cycles of in-order issue
@@ -1314,10 +1307,7 @@ __global__ __launch_bounds__(512) void conv3x3r_kernel(ConvGemmArgs a) {
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#ifndef ACEZ_B2B_PF
-#define ACEZ_B2B_PF 4
-#endif
-    constexpr int PF = ACEZ_B2B_PF;           // weight fragments requested PF steps ahead
+    constexpr int PF = 4;                     // weight fragments requested PF steps ahead
     frag wa[PF][2];
 #pragma unroll
     for (int k = 0; k < PF; ++k)
@@ -1390,8 +1380,7 @@ void launch_convgemm(const ConvGemmArgs& g_in, bool relu, hipStream_t s, int til
                         g.Ci % 32 == 0 && g.Co % 256 == 0 && g.K == g.Kp;
   // the patch kernel pays from one tile per CU on (16 frames of 480x640 at Co = 256: 0.0925 -> 0.0775 ms per frame against the
   // 80-row / 256 x 128 kernels; 32 frames: 0.0715 -> 0.067); round 1's conv3x3p needed four waves of tiles to win
-  static const int patch_min_tiles = [] { const char* e = ACEZ_DIAG_ENV("ACEZ_PATCH_MIN_TILES"); return e ? atoi(e) : 256; }();
-  const bool use_patch = patch_ok && (tile_mode == 3 || (tile_mode == 0 && (int64_t)((g.M + 255) / 256) * (g.Co / 256) >= patch_min_tiles));
+  const bool use_patch = patch_ok && (tile_mode == 3 || (tile_mode == 0 && (int64_t)((g.M + 255) / 256) * (g.Co / 256) >= 256));
   if (g.W2 && !g.In2) {
     // a pointwise Co -> Co layer behind this one (res1_conv1 + res1_conv2): back to back on conv3x3r's finished tile where the layer runs
     // there and one tile holds a whole output row; else two launches through the scratch map
@@ -1766,7 +1755,6 @@ extern "C" int acez_encoder_forward(acez_encoder* e, const float* d_images, int 
       // fp16 = the reference's arithmetic: relu(conv(x)) is a half tensor BEFORE `res + x` / `skip + x` (ace_network.py:52,58), so the
       // activation is rounded before the residual is added and the sum is rounded again; bf16 keeps its single rounding of the fp32 sum
       g.round_before_add = e->f16 ? 1 : 0;
-      if (const char* d = ACEZ_DIAG_ENV("ACEZ_CONV_DBG")) g.dbg = atoi(d);
       launch_convgemm(g, relu, s, e->tile_mode);
     };
     conv(2, e->a2, h2, w2, e->a3, h4, w4, nullptr, true);

@@ -1,16 +1,8 @@
-// gemm_common.h -- device helpers shared by the GEMM-shaped kernels (head_kernels.hip, encoder_kernels.hip):
+// gemm_common.h -- device helpers shared by the GEMM-shaped kernels (head_kernels.hip, encoder_api.hip, head_maps.hip):
 // bf16 packing, LDS swizzles, LDS-DMA address-space typedefs, counted waits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-// Ablation bits of the argument structs (`dbg` fields; tools/ablate_rowgemm.hip, tools/loss_ablate.py, tools/enc_ablate.sh) are read only in
-// the diagnostics build: in the product library they are the constant 0 and the branches they guard do not exist.
-#ifdef ACEZ_DIAG
-#define ACEZ_DBG(x) (x)
-#else
-#define ACEZ_DBG(x) 0
-#endif
 
 namespace acez {
 

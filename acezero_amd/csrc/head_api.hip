@@ -218,12 +218,11 @@ extern "C" void acez_trainer_destroy(acez_trainer* tr) {
 
 // One launch with rowseq_kernel's geometry (grid of a full 64-row-tile batch, 512 threads, the same LDS) that records which XCD
 // ran each tile. The one-launch chains are enabled only on a gfx950 whose eight XCDs take the workgroups of a launch round-robin,
-// i.e. if the four column tiles of EVERY row tile report one XCD (ACEZ_SEQ_NOPROBE=1 skips the probe: tests of the fault path).
+// i.e. if the four column tiles of EVERY row tile report one XCD.
 static int seq_placement_probe(acez_trainer* tr) {
   hipDeviceProp_t prop;
   ACEZ_HIP_CHECK(hipGetDeviceProperties(&prop, tr->device));
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0 || tr->n_cus < 256) { tr->seq = false; tr->seq_probe = 0; return ACEZ_OK; }
-  if (ACEZ_DIAG_ENV("ACEZ_SEQ_NOPROBE")) return ACEZ_OK;
   uint32_t* d_rec = nullptr;
   ACEZ_HIP_CHECK(hipMalloc((void**)&d_rec, 256 * sizeof(uint32_t)));
   uint32_t h[256];
@@ -586,7 +585,7 @@ static uint16_t* launch_forward(acez_trainer* tr, const uint16_t* in0, int n, co
     RowGemmArgs g{};
     g.In = in; g.W = tr->Wb + (size_t)l * 262144; g.bias = P + (int64_t)l * 262656 + 262144;
     g.add = nullptr; g.mask_out = mask_out(l); g.mask_in = nullptr; g.res = res; g.out_main = out_main; g.out_aux = out_aux;
-    g.M = n; g.N = 512; g.K = 512; g.relu = 1; g.aux_mode = res ? AUX_RESIDUAL : AUX_NONE; g.st = st; g.dbg = 0; g.bias_partials = nullptr;
+    g.M = n; g.N = 512; g.K = 512; g.relu = 1; g.aux_mode = res ? AUX_RESIDUAL : AUX_NONE; g.st = st; g.bias_partials = nullptr;
     launch_rowgemm(g, s, tr->f16);
     ++tr->prof_launches;
   };
@@ -646,10 +645,9 @@ static void fill_loss_train(acez_trainer* tr, LossArgs& a, const uint16_t* act, 
   a.inv_batch = 1.0f / (float)tr->cfg.global_batch; a.focal_init = tr->cfg.focal_init;
   a.st = tr->st; a.out_xyz = tr->xyz; a.dZ = tr->dZ[f2];
   a.fc3_partials = tr->fc3_partials; a.fc3_stride = tr->fc3_stride; a.stat_partials = tr->stat_partials;
-  a.bias_partials = tr->bias_partials + (size_t)f2 * tr->bias_layer_stride; a.dbg = 0;
+  a.bias_partials = tr->bias_partials + (size_t)f2 * tr->bias_layer_stride;
   a.absmax = tr->f16 ? tr->st->dz_absmax_slots : nullptr;
   a.fault = tr->seq_err;
-  if (const char* e = ACEZ_DIAG_ENV("ACEZ_LOSS_DBG")) a.dbg = atoi(e);   // ablation: 1 = stop after phase A, 2 = after phase B (timing only)
 }
 
 // ---- pose refinement (the flat parameter offsets in PoseNetwork.named_parameters() order are PN_* in pose_kernels.hip)
@@ -693,12 +691,7 @@ static void launch_pose_wgrad(acez_trainer* tr, const int* active, bool fuse, hi
   w.fuse = fuse ? 1 : 0; w.p = tr->pb.d_pose_params; w.m = tr->pb.d_pose_m; w.v = tr->pb.d_pose_v; w.Wt = tr->pose_wt;
   w.sc = &tr->st->pose_adam; w.enable = &tr->st->pose_enable; w.fault = tr->seq_err;
   if (tr->pose_trace && jobs <= 1024) w.trace = tr->pose_trace + (size_t)2 * 1024 * 16;
-  static const int wb = ACEZ_DIAG_ENV("ACEZ_POSE_WB") ? atoi(ACEZ_DIAG_ENV("ACEZ_POSE_WB")) : 16;   // operand steps requested per round trip
-  static const int ww = ACEZ_DIAG_ENV("ACEZ_POSE_WW") ? atoi(ACEZ_DIAG_ENV("ACEZ_POSE_WW")) : 8;    // waves per workgroup
-  if (wb == 16 && ww == 4) hipLaunchKernelGGL((pose_mlp_wgrad_kernel<16, 4>), dim3(jobs), dim3(256), 0, s, w);
-  else if (wb == 16) hipLaunchKernelGGL((pose_mlp_wgrad_kernel<16, 8>), dim3(jobs), dim3(512), 0, s, w);
-  else if (ww == 4) hipLaunchKernelGGL((pose_mlp_wgrad_kernel<32, 4>), dim3(jobs), dim3(256), 0, s, w);
-  else hipLaunchKernelGGL((pose_mlp_wgrad_kernel<32, 8>), dim3(jobs), dim3(512), 0, s, w);
+  hipLaunchKernelGGL((pose_mlp_wgrad_kernel<16, 8>), dim3(jobs), dim3(512), 0, s, w);   // 16 operand steps per round trip, 8 waves
 }
 
 static PostArgs post_args(acez_trainer* tr) {
@@ -720,7 +713,7 @@ static void fill_wgrad_args(acez_trainer* tr, WgradArgs& a, int n, const TrainSt
     a.In[3 * b] = tr->R[b]; a.In[3 * b + 1] = tr->out[3 * b]; a.In[3 * b + 2] = tr->out[3 * b + 1];
   }
   a.In[f1] = tr->R[tr->nb + 1]; a.In[f2] = tr->out[f1];
-  a.slabs = tr->slabs; a.slab_stride = tr->n_wide; a.M = n; a.nslabs = tr->nslabs; a.n_layers = tr->L; a.st = st; a.zeros = tr->zeros; a.dbg = 0;
+  a.slabs = tr->slabs; a.slab_stride = tr->n_wide; a.M = n; a.nslabs = tr->nslabs; a.n_layers = tr->L; a.st = st; a.zeros = tr->zeros;
 }
 
 // ---- The step protocol: which launch of a step gathers its batch, which gathers the next one, which runs the step's schedule wave
@@ -869,7 +862,7 @@ static void launch_dgrad(acez_trainer* tr, int n, const TrainState* st, hipStrea
     g.bias_partials = tr->bias_partials + (size_t)l_out * tr->bias_layer_stride;
     g.In = tr->dZ[l]; g.W = tr->WbT + (size_t)l * 262144; g.bias = nullptr; g.add = add; g.mask_in = mask; g.mask_out = nullptr; g.res = nullptr;
     g.out_main = out_main; g.out_aux = out_aux; g.M = n; g.N = 512; g.K = 512; g.relu = 0;
-    g.aux_mode = out_aux ? AUX_UNMASKED : AUX_NONE; g.st = st; g.dbg = 0;
+    g.aux_mode = out_aux ? AUX_UNMASKED : AUX_NONE; g.st = st;
     g.absmax = tr->f16 ? tr->st->dz_absmax_slots : nullptr;
     launch_rowgemm(g, s, tr->f16);
     ++tr->prof_launches;
@@ -911,7 +904,6 @@ static void launch_weight_grads(acez_trainer* tr, const StepPlan& p, int n, int 
   {
     WgradArgs a{};
     fill_wgrad_args(tr, a, n, st);
-    if (const char* e = ACEZ_DIAG_ENV("ACEZ_WGO_DBG")) a.dbg = atoi(e);   // timing experiments (wgrad_opt_kernel's ablation bits)
     ProfScope ps(tr, s, KC_WGRAD);
     const int groups = tr->L * tr->nslabs;
     if (p.opt == Opt::WgradOpt) {
@@ -1232,10 +1224,10 @@ static uint16_t* launch_forward_conv(acez_trainer* tr, const uint16_t* in0, int 
     ConvGemmArgs g{};
     g.In = in; g.W = tr->Wb + (size_t)l * 262144; g.bias = P + (int64_t)l * 262656 + 262144; g.add = add; g.out = out;
     g.zeros = tr->zeros; g.Hi = 1; g.Wi = 1; g.Ci = 512; g.ci_shift = 9; g.Ho = 1; g.Wo = 1; g.Co = 512; g.ksize = 1; g.stride = 1;
-    g.pad = 0; g.K = 512; g.Kp = 512; g.M = n; g.round_before_add = 1; g.dbg = 0; g.f16 = tr->f16 ? 1 : 0;
-    if (const char* e = ACEZ_DIAG_ENV("ACEZ_CONV_DBG")) g.dbg = atoi(e);   // (diagnostics build: convgemm512's ablation / stagger bits)
-    static const int conv_tile = ACEZ_DIAG_ENV("ACEZ_HEAD_CONV_TILE") ? atoi(ACEZ_DIAG_ENV("ACEZ_HEAD_CONV_TILE")) : 0;   // (diagnostics build: 256 / 512 force a tile; round 5: the 256 x 128 tiles, which keep a third more input bytes in flight, are 8 % SLOWER here: 2.54 against 2.35 ms per 64 frames)
-    launch_convgemm(g, true, s, conv_tile);
+    g.pad = 0; g.K = 512; g.Kp = 512; g.M = n; g.round_before_add = 1; g.f16 = tr->f16 ? 1 : 0;
+    // tile chosen by size (round 5: the 256 x 128 tiles, which keep a third more input bytes in flight, are 8 % SLOWER here: 2.54 against
+    // 2.35 ms per 64 frames)
+    launch_convgemm(g, true, s, 0);
   };
   const uint16_t* r = in0;
   for (int b = 0; b <= tr->nb; ++b) {

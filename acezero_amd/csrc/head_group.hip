@@ -78,7 +78,7 @@ __global__ __launch_bounds__(512) void rowseq_group_kernel(RowSeqGroupArgs a) {
       const TrainState* st = a.st[h];
       RowGemmArgs g;
       g.In = y.In; g.W = y.W; g.bias = y.bias; g.add = y.add; g.mask_out = y.mask_out; g.mask_in = y.mask_in; g.res = y.res; g.out_main = y.out_main; g.out_aux = y.out_aux;
-      g.bias_partials = y.bias_partials; g.M = a.M[h]; g.N = 512; g.K = 512; g.relu = BWD ? 0 : 1; g.aux_mode = y.aux_mode; g.st = st; g.dbg = 0;
+      g.bias_partials = y.bias_partials; g.M = a.M[h]; g.N = 512; g.K = 512; g.relu = BWD ? 0 : 1; g.aux_mode = y.aux_mode; g.st = st;
       g.absmax = (BWD && st) ? const_cast<uint32_t*>(st->dz_absmax_slots) : nullptr;
       SeqLink q;
       // (target and budget are scalar operands of the poll: the table lives in global memory, so say that they are uniform)

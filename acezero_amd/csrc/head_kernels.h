@@ -2,7 +2,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "gemm_common.h"   // ACEZ_DBG
+#include "gemm_common.h"
 
 namespace acez {
 
@@ -93,7 +93,6 @@ struct RowGemmArgs {
   float* bias_partials;  // [row tiles * 2][512] column sums of out_main (masked launches) or null
   int M, N, K, relu, aux_mode;
   const TrainState* st;
-  int dbg;  // ablation switches for tools/ablate_rowgemm.hip (0 in production): 1 = no epilogue, 2 = no MFMA, 4 = no loads
   uint32_t* absmax;  // fp16 gradient launches: TrainState::dz_absmax_slots (else null)
 };
 
@@ -105,7 +104,6 @@ struct WgradArgs {
   int64_t slab_stride;
   int M, nslabs, n_layers;
   const TrainState* st;
-  int dbg;                // ablation switches (tools/ablate_rowgemm.hip): 1 = no stores, 2 = no MFMA, 4 = no loads
   const uint16_t* zeros;  // >= 256 bytes of zeros (source of the DMA for rows past the end of a slab)
 };
 
@@ -139,7 +137,6 @@ struct LossArgs {
   int64_t fc3_stride;
   float* stat_partials;  // [blocks][4]
   float* bias_partials;  // [blocks][512] column sums of dZ
-  int dbg;               // ablation (tools/ablate_rowgemm.hip): 1 = stop after phase A, 2 = stop after phase B
   uint32_t* absmax;      // fp16 training: TrainState::dz_absmax_slots (else null)
   const int* fault;      // training: the trainer's sticky fault word (null: none). While it is set the launch is a no-op: the buffers of the
                          // faulted step stay as they are until the host's fall-back has finished that step

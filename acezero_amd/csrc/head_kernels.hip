@@ -123,9 +123,6 @@ __device__ __forceinline__ uint32_t absmax_all(const TrainState* st, int lane) {
 
 // One layer of one workgroup. SEQ = false: the whole of rowgemm80_kernel. SEQ = true: one link of rowseq_kernel (below), where
 // the layers of a dependent chain run in ONE launch and the kernel boundary is replaced by a same-XCD hand-off (SeqLink).
-#ifndef ACEZ_SEQ_SLEEP
-#define ACEZ_SEQ_SLEEP "1"   // s_sleep argument between two polls of a hand-off counter (64 clocks each)
-#endif
 struct SeqLink {
   uint32_t* flag;        // per-row-tile counter in this XCD's L2 (one 128-byte line each), monotonically increasing
   uint32_t target;       // value of *flag when the four column tiles of the layer before have stored their outputs
@@ -157,121 +154,115 @@ __device__ __forceinline__ void rowgemm80_body(const RowGemmArgs& a, uint16_t* s
   if (w >= 4) {
     // ------------------------------------------------------------------ loader waves
     const int lw = w - 4;
-    if (ACEZ_DBG(a.dbg) & 4) {
-      for (int kt = 0; kt < KT + 1; ++kt) __builtin_amdgcn_s_barrier();
+    // W instructions 4lw .. 4lw+3 (8 rows each), In instructions 3lw .. 3lw+2; lane: row + (l>>3), slot l&7
+    const uint16_t* gW[4];
+    const uint16_t* gI[3];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int row = (lw * 4 + j) * 8 + (l >> 3);
+      gW[j] = a.W + (size_t)(n0 + row) * K + ((l & 7) ^ ((row >> 1) & 7)) * 8;
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int row = (lw * 3 + j) * 8 + (l >> 3);
+      gI[j] = a.In + (size_t)min(m0 + row, M - 1) * K + ((l & 7) ^ ((row >> 1) & 7)) * 8;
+    }
+    // (Round 6: K stages started at stage (row tile & 7), so that the eight row tiles an XCD holds of one column tile pull eight different
+    // weight stages at any moment -- the rotation head_maps.hip gains 15 % from -- measured +3.5 us on the forward chain and +1.5 us on the
+    // input-gradient chain (profiles/r06_krot_experiments.log): in lockstep one L2 fill serves every workgroup that shares the stage.)
+    auto issueW = [&](int kt) {
+      uint16_t* slot = smem + (kt & 3) * STAGE;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        __builtin_amdgcn_global_load_lds((gvoid_t*)(gW[j] + kt * 64), (lvoid_t*)(slot + (lw * 4 + j) * 8 * 64), 16, 0, 0);
+    };
+    auto issueI = [&](int kt) {
+      uint16_t* slot = smem + (kt & 3) * STAGE;
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        __builtin_amdgcn_global_load_lds((gvoid_t*)(gI[j] + kt * 64), (lvoid_t*)(slot + 128 * 64 + (lw * 3 + j) * 8 * 64), 16, 0, 0);
+    };
+    auto issue = [&](int kt) { issueW(kt); issueI(kt); };
+    // epilogue inputs: 4-row groups 5lw .. 5lw+4 of the [80][128] tile; lane: row + (l>>4), physical chunk l&15 receives
+    // the logical chunk (l&15) ^ (row & 15)
+    auto issue_tile = [&](const uint16_t* src, uint16_t* dst) {
+#pragma unroll
+      for (int j = 0; j < 5; ++j) {
+        const int row = (lw * 5 + j) * 4 + (l >> 4);
+        const uint16_t* g = src + (size_t)min(m0 + row, M - 1) * N + n0 + (((l & 15) ^ (row & 15)) << 3);
+        __builtin_amdgcn_global_load_lds((gvoid_t*)g, (lvoid_t*)(dst + (lw * 5 + j) * 4 * 128), 16, 0, 0);
+      }
+    };
+    if (!SEQ) {
+      issue(0); issue(1); issue(2); issue(3);
     } else {
-      // W instructions 4lw .. 4lw+3 (8 rows each), In instructions 3lw .. 3lw+2; lane: row + (l>>3), slot l&7
-      const uint16_t* gW[4];
-      const uint16_t* gI[3];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int row = (lw * 4 + j) * 8 + (l >> 3);
-        gW[j] = a.W + (size_t)(n0 + row) * K + ((l & 7) ^ ((row >> 1) & 7)) * 8;
-      }
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int row = (lw * 3 + j) * 8 + (l >> 3);
-        gI[j] = a.In + (size_t)min(m0 + row, M - 1) * K + ((l & 7) ^ ((row >> 1) & 7)) * 8;
-      }
-      // (Round 6: K stages started at stage (row tile & 7), so that the eight row tiles an XCD holds of one column tile pull eight different
-      // weight stages at any moment -- the rotation head_maps.hip gains 15 % from -- measured +3.5 us on the forward chain and +1.5 us on the
-      // input-gradient chain (profiles/r06_krot_experiments.log): in lockstep one L2 fill serves every workgroup that shares the stage.)
-      auto issueW = [&](int kt) {
-        uint16_t* slot = smem + (kt & 3) * STAGE;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          __builtin_amdgcn_global_load_lds((gvoid_t*)(gW[j] + kt * 64), (lvoid_t*)(slot + (lw * 4 + j) * 8 * 64), 16, 0, 0);
-      };
-      auto issueI = [&](int kt) {
-        uint16_t* slot = smem + (kt & 3) * STAGE;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          __builtin_amdgcn_global_load_lds((gvoid_t*)(gI[j] + kt * 64), (lvoid_t*)(slot + 128 * 64 + (lw * 3 + j) * 8 * 64), 16, 0, 0);
-      };
-      auto issue = [&](int kt) { issueW(kt); issueI(kt); };
-      // epilogue inputs: 4-row groups 5lw .. 5lw+4 of the [80][128] tile; lane: row + (l>>4), physical chunk l&15 receives
-      // the logical chunk (l&15) ^ (row & 15)
-      auto issue_tile = [&](const uint16_t* src, uint16_t* dst) {
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-          const int row = (lw * 5 + j) * 4 + (l >> 4);
-          const uint16_t* g = src + (size_t)min(m0 + row, M - 1) * N + n0 + (((l & 15) ^ (row & 15)) << 3);
-          __builtin_amdgcn_global_load_lds((gvoid_t*)g, (lvoid_t*)(dst + (lw * 5 + j) * 4 * 128), 16, 0, 0);
-        }
-      };
-      if (!SEQ) {
-        issue(0); issue(1); issue(2); issue(3);
-      } else {
-        // W stages 0..3 first (requested by the layer before unless this is the first), then -- once the four column tiles
-        // of the producing layer have landed in this XCD's L2 -- the In stages
-        if (q.first) { issueW(0); issueW(1); issueW(2); issueW(3); }
-        if (q.wait) {
-          // Bounded: a sibling that never arrives (workgroups of one row tile on different XCDs -- every L2 then holds its own copy
-          // of the counter and none of them ever reaches the target --, or a sibling that is never dispatched) must not hang the
-          // stream. When the budget expires the wave raises the sticky fault word and goes on with whatever is in memory: the
-          // results of this launch are garbage, the optimiser and schedule kernels of the step see the word and do nothing, and
-          // the host switches the trainer to per-layer launches at its next state read (head_api.hip).
-          // The whole poll is ONE asm statement: written as a C loop with a second exit, the compiler re-scheduled the K loops and
-          // epilogues of the input-gradient instantiation (+3 us per chain, same instruction mix; found by diffing the ISA of a
-          // build without the bound). sc1: past this CU's L1; the counter and the tiles live in the L2 all four workgroups share,
-          // no L2 invalidate. Every lane loads the same word: the loop condition is scalar. The budget is counted in polls
-          // (>= ~0.5 us each: an L2 round trip + the sleep).
-          uint32_t vseen, sseen, spins, timed;
-          asm volatile(
-              "s_mov_b32 %[spins], 0\n\t"
-              "s_mov_b32 %[timed], 0\n"
-              "1:\n\t"
-              "global_load_dword %[vseen], %[flag], off sc1\n\t"
-              "s_waitcnt vmcnt(0)\n\t"
-              "v_readfirstlane_b32 %[sseen], %[vseen]\n\t"
-              "s_sub_i32 %[sseen], %[sseen], %[target]\n\t"
-              "s_cmp_ge_i32 %[sseen], 0\n\t"
-              "s_cbranch_scc1 2f\n\t"
-              "s_sleep " ACEZ_SEQ_SLEEP "\n\t"
-              "s_add_u32 %[spins], %[spins], 1\n\t"
-              "s_cmp_lt_u32 %[spins], %[limit]\n\t"
-              "s_cbranch_scc1 1b\n\t"
-              "s_mov_b32 %[timed], 1\n"
-              "2:"
-              : [vseen] "=&v"(vseen), [sseen] "=&s"(sseen), [spins] "=&s"(spins), [timed] "=&s"(timed)
-              : [flag] "v"(q.flag), [target] "s"(q.target), [limit] "s"(q.limit)
-              : "memory", "scc");
-#ifndef ACEZ_SEQ_UNBOUNDED   // (timing experiments only, tools/lib_variant.sh: what the fault path costs)
-          if (timed && l == 0) {   // the fault word, and the step is switched off: every later kernel of this trainer starts with `if (!st->active) return`
-            __hip_atomic_store(q.flag - q.flag_index + 64 * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (a.st) __hip_atomic_store(const_cast<int*>(&a.st->active), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-#endif
-        }
-        issueI(0); issueI(1); issueI(2); issueI(3);
-      }
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt) {
-        // in-order completion: everything younger than stage kt may still be in flight
-        if (SEQ && kt == 0) ACEZ_VMCNT(9);
-        else if (SEQ && kt == 1) ACEZ_VMCNT(6);
-        else if (SEQ && kt == 2) ACEZ_VMCNT(10);
-        else if (kt == 0) ACEZ_VMCNT(21);
-        else if (kt <= 4) ACEZ_VMCNT(14);
-        else if (kt == 5) ACEZ_VMCNT_C(14 + EPI);
-        else if (kt == 6) ACEZ_VMCNT_C(7 + EPI);
-        else ACEZ_VMCNT_C(EPI);
-        __builtin_amdgcn_s_barrier();   // stage kt has landed; the multipliers are done with stage kt - 1
-        if (kt >= 1 && kt + 3 < KT) issue(kt + 3);
-        if (kt == 4) {
-          if (HAS_ADD) issue_tile(a.add, stA);
-          if (HAS_IN2) issue_tile(a.res, stB);
+      // W stages 0..3 first (requested by the layer before unless this is the first), then -- once the four column tiles
+      // of the producing layer have landed in this XCD's L2 -- the In stages
+      if (q.first) { issueW(0); issueW(1); issueW(2); issueW(3); }
+      if (q.wait) {
+        // Bounded: a sibling that never arrives (workgroups of one row tile on different XCDs -- every L2 then holds its own copy
+        // of the counter and none of them ever reaches the target --, or a sibling that is never dispatched) must not hang the
+        // stream. When the budget expires the wave raises the sticky fault word and goes on with whatever is in memory: the
+        // results of this launch are garbage, the optimiser and schedule kernels of the step see the word and do nothing, and
+        // the host switches the trainer to per-layer launches at its next state read (head_api.hip).
+        // The whole poll is ONE asm statement: written as a C loop with a second exit, the compiler re-scheduled the K loops and
+        // epilogues of the input-gradient instantiation (+3 us per chain, same instruction mix; found by diffing the ISA of a
+        // build without the bound). sc1: past this CU's L1; the counter and the tiles live in the L2 all four workgroups share,
+        // no L2 invalidate. Every lane loads the same word: the loop condition is scalar. The budget is counted in polls
+        // (>= ~0.5 us each: an L2 round trip + the sleep).
+        uint32_t vseen, sseen, spins, timed;
+        asm volatile(
+            "s_mov_b32 %[spins], 0\n\t"
+            "s_mov_b32 %[timed], 0\n"
+            "1:\n\t"
+            "global_load_dword %[vseen], %[flag], off sc1\n\t"
+            "s_waitcnt vmcnt(0)\n\t"
+            "v_readfirstlane_b32 %[sseen], %[vseen]\n\t"
+            "s_sub_i32 %[sseen], %[sseen], %[target]\n\t"
+            "s_cmp_ge_i32 %[sseen], 0\n\t"
+            "s_cbranch_scc1 2f\n\t"
+            "s_sleep 1\n\t"   // 64 clocks between two polls
+            "s_add_u32 %[spins], %[spins], 1\n\t"
+            "s_cmp_lt_u32 %[spins], %[limit]\n\t"
+            "s_cbranch_scc1 1b\n\t"
+            "s_mov_b32 %[timed], 1\n"
+            "2:"
+            : [vseen] "=&v"(vseen), [sseen] "=&s"(sseen), [spins] "=&s"(spins), [timed] "=&s"(timed)
+            : [flag] "v"(q.flag), [target] "s"(q.target), [limit] "s"(q.limit)
+            : "memory", "scc");
+        if (timed && l == 0) {   // the fault word, and the step is switched off: every later kernel of this trainer starts with `if (!st->active) return`
+          __hip_atomic_store(q.flag - q.flag_index + 64 * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (a.st) __hip_atomic_store(const_cast<int*>(&a.st->active), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
-      ACEZ_VMCNT(0);
-      __builtin_amdgcn_s_barrier();     // epilogue inputs have landed; the ring is free
-      if (SEQ && q.next_W) {            // overlaps the epilogue: 64 KiB of the next layer's 208 KiB (requested behind the hand-off
-#pragma unroll                          // instead, so that the loader waves' vmcnt(0) there covers stores only: measured +3 us per chain)
-        for (int j = 0; j < 4; ++j) gW[j] += q.next_W - a.W;
-        issueW(0); issueW(1); issueW(2); issueW(3);
+      issueI(0); issueI(1); issueI(2); issueI(3);
+    }
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) {
+      // in-order completion: everything younger than stage kt may still be in flight
+      if (SEQ && kt == 0) ACEZ_VMCNT(9);
+      else if (SEQ && kt == 1) ACEZ_VMCNT(6);
+      else if (SEQ && kt == 2) ACEZ_VMCNT(10);
+      else if (kt == 0) ACEZ_VMCNT(21);
+      else if (kt <= 4) ACEZ_VMCNT(14);
+      else if (kt == 5) ACEZ_VMCNT_C(14 + EPI);
+      else if (kt == 6) ACEZ_VMCNT_C(7 + EPI);
+      else ACEZ_VMCNT_C(EPI);
+      __builtin_amdgcn_s_barrier();   // stage kt has landed; the multipliers are done with stage kt - 1
+      if (kt >= 1 && kt + 3 < KT) issue(kt + 3);
+      if (kt == 4) {
+        if (HAS_ADD) issue_tile(a.add, stA);
+        if (HAS_IN2) issue_tile(a.res, stB);
       }
     }
-    if (!SEQ && ((ACEZ_DBG(a.dbg) & 1) || !active)) return;
+    ACEZ_VMCNT(0);
+    __builtin_amdgcn_s_barrier();     // epilogue inputs have landed; the ring is free
+    if (SEQ && q.next_W) {            // overlaps the epilogue: 64 KiB of the next layer's 208 KiB (requested behind the hand-off
+#pragma unroll                        // instead, so that the loader waves' vmcnt(0) there covers stores only: measured +3 us per chain)
+      for (int j = 0; j < 4; ++j) gW[j] += q.next_W - a.W;
+      issueW(0); issueW(1); issueW(2); issueW(3);
+    }
+    if (!SEQ && !active) return;
     __builtin_amdgcn_s_barrier();       // the multipliers have written the output tiles
   } else {
     // ------------------------------------------------------------------ multiplier waves
@@ -296,7 +287,7 @@ __device__ __forceinline__ void rowgemm80_body(const RowGemmArgs& a, uint16_t* s
 #pragma unroll
       for (int i = 0; i < 2; ++i) bias[i] = *reinterpret_cast<const float4*>(a.bias + n0 + w * 32 + i * 16 + 4 * fq);
     }
-    // The K loop is straight-line code (the ablation bits are compile-time 0 in the product build): without this the scheduler sinks
+    // The K loop is straight-line code: without this the scheduler sinks
     // the second half's MFMAs below the next s_barrier -- their ds_reads would still be in flight when the loader waves, released by
     // that barrier, refill the slot (only the DMA latency protects them: a rare last-bit corruption under two processes on one GPU,
     // found with tools/seq_stress.py). Keep the fragment reads of a stage complete before the wave arrives at the barrier.
@@ -308,7 +299,6 @@ __device__ __forceinline__ void rowgemm80_body(const RowGemmArgs& a, uint16_t* s
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt) {
       stage_barrier();
-      if (ACEZ_DBG(a.dbg) & 2) continue;
       const uint16_t* sW = smem + (kt & 3) * STAGE;
       const uint16_t* sI = sW + 128 * 64;
       if constexpr (!HAS_MASK) {
@@ -365,7 +355,7 @@ __device__ __forceinline__ void rowgemm80_body(const RowGemmArgs& a, uint16_t* s
       }
     }
     stage_barrier();                    // epilogue inputs have landed
-    if (!SEQ && ((ACEZ_DBG(a.dbg) & 1) || !active)) return;
+    if (!SEQ && !active) return;
     float amax = 0.f;                   // fp16 gradient layers: largest |value| before the conversion (absmax_publish)
     // The epilogue inputs this lane needs from the staging tiles (`add` values in stA, mask / residual values in stB: up to 2 x 10 eight-byte
     // reads), ALL requested before the first is used: written as read-compute-write per fragment the compiler could not move a read above
@@ -610,7 +600,7 @@ __global__ __launch_bounds__(512) void rowseq_kernel(RowSeqArgs a) {
     const SeqLayer& y = a.layer[layer];
     RowGemmArgs g;
     g.In = y.In; g.W = y.W; g.bias = y.bias; g.add = y.add; g.mask_out = y.mask_out; g.mask_in = y.mask_in; g.res = y.res; g.out_main = y.out_main; g.out_aux = y.out_aux;
-    g.bias_partials = y.bias_partials; g.M = a.M; g.N = 512; g.K = 512; g.relu = BWD ? 0 : 1; g.aux_mode = y.aux_mode; g.st = a.st; g.dbg = 0;
+    g.bias_partials = y.bias_partials; g.M = a.M; g.N = 512; g.K = 512; g.relu = BWD ? 0 : 1; g.aux_mode = y.aux_mode; g.st = a.st;
     g.absmax = (BWD && a.st) ? const_cast<uint32_t*>(a.st->dz_absmax_slots) : nullptr;
     SeqLink q;
     q.flag = a.flags + mt * 32; q.target = (a.base[mt] + (uint32_t)layer) * 32u;   // 4 workgroups x 8 waves per seam
@@ -694,9 +684,7 @@ __device__ __forceinline__ typename E::frag tr_frag(const uint16_t* p) {
   return __builtin_bit_cast(typename E::frag, r);
 }
 
-#ifndef ACEZ_WGRAD_RING
-#define ACEZ_WGRAD_RING 4
-#endif
+constexpr int WGRAD_RING = 4;                       // slots of the [dZ | In] stage ring, 32 KiB each (RING - 1 stages in flight per CU)
 constexpr int WGRAD_LOADERS = 8;                    // loader waves per workgroup (beside the 4 multiplier waves)
 constexpr int WGRAD_THREADS = 256 + 64 * WGRAD_LOADERS;
 // s_waitcnt vmcnt(n) for a wave-uniform n that is only known at run time (1 .. 31; anything else waits for everything)
@@ -746,7 +734,7 @@ __device__ __forceinline__ void wait_vmcnt_dyn(int n) {
 template <class E, int PFN, class PF>
 __device__ __forceinline__ bool wgrad_kloop(const WgradArgs& a, uint16_t (*smem)[2][64 * 128], const int layer, const int slab, const int tile,
                                             f32x16 (&acc)[2][2], int& KT_out, PF&& prefetch) {
-  constexpr int RING = ACEZ_WGRAD_RING;   // slots of the [dZ | In] stage ring, 32 KiB each (RING - 1 stages in flight per CU)
+  constexpr int RING = WGRAD_RING;
   static_assert(2 * (16 / WGRAD_LOADERS) * (RING - 1) + PFN <= 31, "wait_vmcnt_dyn covers 1 .. 31");
   const int t = threadIdx.x, l = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -799,11 +787,6 @@ __device__ __forceinline__ bool wgrad_kloop(const WgradArgs& a, uint16_t (*smem)
   // Two separate loops (one per role) with the same number of barriers: sharing one loop body makes the compiler
   // carry the 64 accumulator registers through the loader's control flow (moves on every iteration).
   if (loader) {
-    if (ACEZ_DBG(a.dbg) & 4) {
-      for (int kt = 0; kt < KT; ++kt) __builtin_amdgcn_s_barrier();
-      if (PFN > 0) prefetch();
-      return true;
-    }
     for (int kt = 0; kt < RING && kt < KT; ++kt) issue(kt);
     // stage kt: wait until it has landed, meet the multipliers (they are done with stage kt - 1), refill the slot of stage kt - 1
     auto stage = [&](int kt, int extra) {
@@ -830,7 +813,6 @@ __device__ __forceinline__ bool wgrad_kloop(const WgradArgs& a, uint16_t (*smem)
   const int offB[2] = {tr_base(wc * 64, l), tr_base(wc * 64 + 32, l)};
   for (int kt = 0; kt < KT; ++kt) {
     __builtin_amdgcn_s_barrier();
-    if (ACEZ_DBG(a.dbg) & 2) continue;
     const int slot = kt % RING;
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
@@ -851,7 +833,7 @@ __device__ __forceinline__ bool wgrad_kloop(const WgradArgs& a, uint16_t (*smem)
 template <class E = EltBf16>
 __global__ __launch_bounds__(WGRAD_THREADS) void wgrad_kernel(WgradArgs a) {
   const int active = a.st ? a.st->active : 1;  // tested before the stores only (see rowgemm80_body)
-  __shared__ __attribute__((aligned(16))) uint16_t smem[ACEZ_WGRAD_RING][2][64 * 128];
+  __shared__ __attribute__((aligned(16))) uint16_t smem[WGRAD_RING][2][64 * 128];
   const int l = threadIdx.x & 63;
   const int cw = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 3, wn = cw >> 1, wc = cw & 1;
   // XCD-aware decode: the 16 output tiles of one (layer, slab) group re-read the same dZ / In rows (4x each); they
@@ -867,7 +849,6 @@ __global__ __launch_bounds__(WGRAD_THREADS) void wgrad_kernel(WgradArgs a) {
   int KT;
   if (wgrad_kloop<E, 0>(a, smem, layer, slab, tile, acc, KT, [] {})) return;
 
-  if (ACEZ_DBG(a.dbg) & 1) { if (acc[0][0][0] == 1.2345e30f) a.slabs[0] = 1; return; }
   if (!active) return;
   float* __restrict__ G = a.slabs + (size_t)slab * a.slab_stride;
   const int h = l >> 5;
@@ -1029,7 +1010,6 @@ __device__ __forceinline__ void loss_body(const LossArgs& a, const int block, co
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  if (ACEZ_DBG(a.dbg) == 1) return;
 
   // ---- phase B
   const float gscale = (a.idx && a.st) ? a.st->grad_scale : 1.f;
@@ -1216,7 +1196,6 @@ __device__ __forceinline__ void loss_body(const LossArgs& a, const int block, co
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   if (!a.idx) return;  // inference: no gradients
-  if (ACEZ_DBG(a.dbg) == 2) return;
 
   // ---- the four waves meet once: phase C reads every row's ds and, in the chain kernel, overwrites activations that the other
   // waves' phase A has read
@@ -1548,20 +1527,14 @@ __device__ __forceinline__ void adamw_small_columns(const AdamArgs& a, const int
   sm.finish(a.tail, o, b, s, [] { return false; });
 }
 
-#ifndef GR_LPO
-#define GR_LPO 8   // lanes per output of grad_reduce_kernel's tail (4: 97 workgroups with 80 loads per lane in flight; 8: 193 with 40)
-#endif
-__host__ __device__ inline int grad_reduce_tail_blocks(int n_layers, int64_t n_fc3) { return small_cols_blocks(n_layers, n_fc3, GR_LPO); }
-// Grid: the tail workgroups FIRST (GR_LPO lanes per output: biases, fc3, statistics), then the wide part (split flow only). The tail is the
+constexpr int GR_TAIL_LANES = 8;   // lanes per output of grad_reduce_kernel's tail (4: 97 workgroups with 80 loads per lane in flight; 8: 193 with 40)
+__host__ __device__ inline int grad_reduce_tail_blocks(int n_layers, int64_t n_fc3) { return small_cols_blocks(n_layers, n_fc3, GR_TAIL_LANES); }
+// Grid: the tail workgroups FIRST (GR_TAIL_LANES lanes per output: biases, fc3, statistics), then the wide part (split flow only). The tail is the
 // launch's long pole -- every lane sums up to 80 partials behind two load levels -- and, dispatched behind the 2052 wide workgroups, it
 // started when those were done; every load of a workgroup is requested before the schedule's `active` word is looked at (three dependent
 // round trips per workgroup of a launch that is one wave of workgroups long). Round 6: 18.4 -> see profiles/r06_dp_host_probe.log.
 __device__ __forceinline__ void grad_reduce_body(const GradReduceArgs& a, const int b) {
   const int tail_blocks = grad_reduce_tail_blocks(a.n_layers, a.n_params - a.n_wide);
-#ifdef GR_ABL   // timing-only ablation builds (tools/lib_variant.sh): 1 = no tail, 2 = no wide part
-  if ((GR_ABL & 1) && b < tail_blocks) return;
-  if ((GR_ABL & 2) && b >= tail_blocks) return;
-#endif
   if (b >= tail_blocks) {  // weights: 16-byte loads, slabs summed in slab order
     const int64_t i4 = ((int64_t)(b - tail_blocks) * 256 + threadIdx.x) * 4;
     if (a.skip_wide || i4 >= a.n_wide) return;
@@ -1582,7 +1555,7 @@ __device__ __forceinline__ void grad_reduce_body(const GradReduceArgs& a, const 
   }
   // the tail: 64 outputs per workgroup, four lanes each, coalesced partial-row reads (SmallCols: tail_output's summation order, the same bits;
   // a wavefront per output -- 1538 workgroups whose lanes stride the partial ROWS -- touched 64 cache lines with every load)
-  SmallCols<GR_LPO> sm;
+  SmallCols<GR_TAIL_LANES> sm;
   const SmallOpt none{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
   sm.issue(a, none, b);
   if (a.st && !a.st->active) {
@@ -2228,7 +2201,7 @@ __device__ __forceinline__ void lds_bump(uint32_t* f) {   // after this wave's e
 #endif
 template <class E = EltBf16>
 __global__ __launch_bounds__(WGRAD_THREADS) void wgrad_opt_kernel(WgradArgs a, WgradOptArgs o, PostArgs post) {
-  constexpr int RING = ACEZ_WGRAD_RING;
+  constexpr int RING = WGRAD_RING;
   static_assert(RING >= 3, "two free ring slots are used as staging areas after the K loop");
   __shared__ __attribute__((aligned(16))) uint16_t smem[RING][2][64 * 128];
   __shared__ uint32_t wsync[2];   // [0]: multiplier waves that have staged their accumulators, [1]: loader waves that have written their W^T rows
@@ -2268,7 +2241,7 @@ __global__ __launch_bounds__(WGRAD_THREADS) void wgrad_opt_kernel(WgradArgs a, W
   // eight stages before its end, it bought nothing or stalled the loop on the loaded registers one iteration later: measured, round 4.)
   SmallCols<8> sm;
   float lpm[5];
-  const bool do_small = b < o.nsmall && !(ACEZ_DBG(a.dbg) & 64);
+  const bool do_small = b < o.nsmall;
   auto mprefetch = [&]() {
     if (do_small) {
       sm.issue(ad.tail, small_opt(ad), b);
@@ -2303,20 +2276,18 @@ __global__ __launch_bounds__(WGRAD_THREADS) void wgrad_opt_kernel(WgradArgs a, W
   if (!loader) {
     const int cw = w & 3, wn = cw >> 1, wc = cw & 1, h = l >> 5;
     if (wn != slab) {
-      if (!(ACEZ_DBG(a.dbg) & 32)) {
-        float* __restrict__ X = o.xch + (size_t)(pair * 2 + (1 - slab)) * 8192;
+      float* __restrict__ X = o.xch + (size_t)(pair * 2 + (1 - slab)) * 8192;
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+      for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-              X[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 128 + wc * 64 + j * 32 + (l & 31)] = acc[i][j][r];
-        ACEZ_VMCNT(0);   // acknowledged by the L2 both workgroups share
-        if (l == 0) {
-          const uint32_t one = 1;
-          asm volatile("global_atomic_add %0, %1, off" ::"v"(o.flags + (size_t)(pair * 2 + (1 - slab)) * 32), "v"(one) : "memory");
-        }
+          for (int r = 0; r < 16; ++r)
+            X[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 128 + wc * 64 + j * 32 + (l & 31)] = acc[i][j][r];
+      ACEZ_VMCNT(0);   // acknowledged by the L2 both workgroups share
+      if (l == 0) {
+        const uint32_t one = 1;
+        asm volatile("global_atomic_add %0, %1, off" ::"v"(o.flags + (size_t)(pair * 2 + (1 - slab)) * 32), "v"(one) : "memory");
       }
     } else {
 #pragma unroll
@@ -2343,7 +2314,7 @@ __global__ __launch_bounds__(WGRAD_THREADS) void wgrad_opt_kernel(WgradArgs a, W
       });
     }
     WGO_STAMP(3);   // multipliers: small parameters done
-    if (o.do_post && b == (int)gridDim.x - 1 && w == 0 && !(ACEZ_DBG(a.dbg) & 128))
+    if (o.do_post && b == (int)gridDim.x - 1 && w == 0)
       sched_post_wave(post.src, post.st, post.c, post.grad_stats, post.inv_global_batch, post.log_loss, post.log_inl, post.log_cap, post.fault,
                       post.stat_partials, post.n_loss_blocks, &ad.tail);
     WGO_STAMP(4);   // multipliers: (schedule wave) done
@@ -2355,50 +2326,48 @@ __global__ __launch_bounds__(WGRAD_THREADS) void wgrad_opt_kernel(WgradArgs a, W
   const float inv_scale = st->inv_grad_scale;
   const int fault_now = *ad.fault;
   const float lossv = loss_sum(lp);
-  bool skip = !active || fault_now || lossv != lossv || (ACEZ_DBG(a.dbg) & 8);   // adamw_body's guards
+  bool skip = !active || fault_now || lossv != lossv;   // adamw_body's guards
   if (E::is_f16) skip = skip || f16_overflow(absmax_reduce(amx));
   const bool skip_by_guard = skip;   // (uniform over the launch: every wave evaluates the same words)
-  if (!(ACEZ_DBG(a.dbg) & 48)) {   // (ablation bits of the diagnostics build, timing only: 8 = no final stores, 16 = no poll, 32 = no send, 64 = no small parameters, 128 = no schedule wave)
-    uint32_t vseen, sseen, spins, timed;
-    const uint32_t* flag = o.flags + (size_t)(pair * 2 + slab) * 32;
-    uint32_t wgo_target = o.target;
+  uint32_t vseen, sseen, spins, timed;
+  const uint32_t* flag = o.flags + (size_t)(pair * 2 + slab) * 32;
+  uint32_t wgo_target = o.target;
 #ifdef ACEZ_DIAG   // fault injection in SOME workgroups (ACEZ_WGO_FAULT_MOD): a partially applied step
-    if (o.fault_mod > 0 && b % o.fault_mod == 1) wgo_target += 1u << 20;
+  if (o.fault_mod > 0 && b % o.fault_mod == 1) wgo_target += 1u << 20;
 #endif
-    asm volatile(
-        "s_mov_b32 %[spins], 0\n\t"
-        "s_mov_b32 %[timed], 0\n"
-        "1:\n\t"
-        "global_load_dword %[vseen], %[flag], off sc1\n\t"
-        "s_waitcnt vmcnt(0)\n\t"
-        "v_readfirstlane_b32 %[sseen], %[vseen]\n\t"
-        "s_sub_i32 %[sseen], %[sseen], %[target]\n\t"
-        "s_cmp_ge_i32 %[sseen], 0\n\t"
-        "s_cbranch_scc1 2f\n\t"
-        "s_sleep " ACEZ_SEQ_SLEEP "\n\t"
-        "s_add_u32 %[spins], %[spins], 1\n\t"
-        "s_cmp_lt_u32 %[spins], %[limit]\n\t"
-        "s_cbranch_scc1 1b\n\t"
-        "s_mov_b32 %[timed], 1\n"
-        "2:"
-        : [vseen] "=&v"(vseen), [sseen] "=&s"(sseen), [spins] "=&s"(spins), [timed] "=&s"(timed)
-        : [flag] "v"(flag), [target] "s"(wgo_target), [limit] "s"(o.spin_limit)
-        : "memory", "scc");
-    if (timed) {   // the partner never arrived (the two slabs of a tile are not on one XCD after all): fault word, step switched off
-      skip = true;
-      if (l == 0) {
-        // What the host needs to finish this step (wgo_recover, head_api.hip): which rows were not updated, and with what they would have
-        // been. The small parameters and the schedule wave of this launch read the fault word long before it is raised and DO apply the
-        // step; tiles whose exchange completed are updated too -- so the fall-back completes the step instead of undoing it. Every kernel
-        // of the trainer that writes a step's buffers returns at entry while the word is set: the operands are still there.
-        if (!skip_by_guard && o.status) {
-          o.status[(size_t)b * WGRAD_LOADERS + (w - 4)] = o.epoch * 4u + 3u;
-          o.rec->s = s; o.rec->inv_scale = inv_scale; o.rec->M = a.M; o.rec->in0 = a.In[0];
-          __hip_atomic_store(&o.rec->epoch, o.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __hip_atomic_store(ad.fault, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(const_cast<int*>(&st->active), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile(
+      "s_mov_b32 %[spins], 0\n\t"
+      "s_mov_b32 %[timed], 0\n"
+      "1:\n\t"
+      "global_load_dword %[vseen], %[flag], off sc1\n\t"
+      "s_waitcnt vmcnt(0)\n\t"
+      "v_readfirstlane_b32 %[sseen], %[vseen]\n\t"
+      "s_sub_i32 %[sseen], %[sseen], %[target]\n\t"
+      "s_cmp_ge_i32 %[sseen], 0\n\t"
+      "s_cbranch_scc1 2f\n\t"
+      "s_sleep 1\n\t"
+      "s_add_u32 %[spins], %[spins], 1\n\t"
+      "s_cmp_lt_u32 %[spins], %[limit]\n\t"
+      "s_cbranch_scc1 1b\n\t"
+      "s_mov_b32 %[timed], 1\n"
+      "2:"
+      : [vseen] "=&v"(vseen), [sseen] "=&s"(sseen), [spins] "=&s"(spins), [timed] "=&s"(timed)
+      : [flag] "v"(flag), [target] "s"(wgo_target), [limit] "s"(o.spin_limit)
+      : "memory", "scc");
+  if (timed) {   // the partner never arrived (the two slabs of a tile are not on one XCD after all): fault word, step switched off
+    skip = true;
+    if (l == 0) {
+      // What the host needs to finish this step (wgo_recover, head_api.hip): which rows were not updated, and with what they would have
+      // been. The small parameters and the schedule wave of this launch read the fault word long before it is raised and DO apply the
+      // step; tiles whose exchange completed are updated too -- so the fall-back completes the step instead of undoing it. Every kernel
+      // of the trainer that writes a step's buffers returns at entry while the word is set: the operands are still there.
+      if (!skip_by_guard && o.status) {
+        o.status[(size_t)b * WGRAD_LOADERS + (w - 4)] = o.epoch * 4u + 3u;
+        o.rec->s = s; o.rec->inv_scale = inv_scale; o.rec->M = a.M; o.rec->in0 = a.In[0];
+        __hip_atomic_store(&o.rec->epoch, o.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
+      __hip_atomic_store(ad.fault, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(const_cast<int*>(&st->active), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
   WGO_STAMP(2);   // loaders: guards evaluated, partner's counter seen

@@ -12,10 +12,10 @@
 //     from L2 four K steps ahead and its B fragments (activations) from the tile, 16-byte chunk index XOR row & 31: conflict free;
 //   * every row's dot products run over K in the same order whatever tile, wave or pass the row falls into: a frame's scene coordinates do
 //     not depend on what else is in the batch (tests/test_session_gpu.py registers the same frames in two folder compositions and compares
-//     pose files). The price is 7 %: started at a WORKGROUP-DEPENDENT K step (-DACEZ_HM_ROT=1: rot = (blockIdx >> 3) & 31), the 32
-//     workgroups of an XCD read 32 different weight lines at any moment instead of queueing on one L2 channel -- 3.35 -> 3.13 ms per 136
-//     frames (prototype, fully unrolled loop: 1765 -> 1506 us; with ONE weight panel for all layers, i.e. all CUs on the same 512 KiB: 2182)
-//     -- but fp32 accumulation order would then depend on the tile's workgroup. Not taken;
+//     pose files). The price is 7 %: started at a WORKGROUP-DEPENDENT K step (rot = (blockIdx >> 3) & 31; the variant is in the git
+//     history), the 32 workgroups of an XCD read 32 different weight lines at any moment instead of queueing on one L2 channel -- 3.35 ->
+//     3.13 ms per 136 frames (prototype, fully unrolled loop: 1765 -> 1506 us; with ONE weight panel for all layers, i.e. all CUs on the
+//     same 512 KiB: 2182) -- but fp32 accumulation order would then depend on the tile's workgroup. Not taken;
 //   * residual adds (ace_network.py:126,133: res = res + relu(conv(x)), the activation a 16-bit tensor before the add) as a second,
 //     coalesced pass over the tile: the block input is re-read from global memory (block 0: the features themselves; later blocks: the
 //     tile is copied out to R[b] when it is produced) -- a residual kept in registers would be 64 VGPRs next to 128 accumulators.
@@ -66,10 +66,6 @@ __global__ __launch_bounds__(512) void head_maps_kernel(HeadMapsArgs a) {
   const int fr = l & 31, fh = l >> 5;
   const int n = a.n, ntiles = (n + 127) >> 7;
   const int L = 3 * (a.nb + 1) + 2;
-#ifndef ACEZ_HM_ROT
-#define ACEZ_HM_ROT 0   // 1: timing variant (tools/lib_variant.sh), see the header comment
-#endif
-  const int rot = ACEZ_HM_ROT ? (int)((blockIdx.x >> 3) & 31) : 0;
   constexpr int PF = 4;
   unsigned baddr[4], bx[4];
 #pragma unroll
@@ -116,10 +112,10 @@ __global__ __launch_bounds__(512) void head_maps_kernel(HeadMapsArgs a) {
 #pragma unroll
       for (int k = 0; k < PF; ++k)
 #pragma unroll
-        for (int i = 0; i < 2; ++i) wa[k][i] = *reinterpret_cast<const frag*>(wp[i] + 512 * ((k + rot) & 31));
+        for (int i = 0; i < 2; ++i) wa[k][i] = *reinterpret_cast<const frag*>(wp[i] + 512 * k);
       frag fb[2][4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) fb[0][j] = *(lds_frag*)(lds + baddr[j] + ((((unsigned)(2 * rot)) ^ bx[j]) << 4));
+      for (int j = 0; j < 4; ++j) fb[0][j] = *(lds_frag*)(lds + baddr[j] + (bx[j] << 4));
       // K loop in groups of PF steps; the loop is not unrolled beyond a group and step addresses are computed as they are needed (fully
       // unrolled, the 32 steps kept ~190 address registers alive: 94 dwords of spills, 1506 us instead of 1277 in the prototype)
 #pragma clang loop unroll(disable)
@@ -127,11 +123,11 @@ __global__ __launch_bounds__(512) void head_maps_kernel(HeadMapsArgs a) {
 #pragma unroll
         for (int u = 0; u < PF; ++u) {
           const int kk = k0 + u;
-          const unsigned c2 = 2u * (unsigned)((kk + 1 + rot) & 31);       // (the read past the last step wraps to the first: unused)
+          const unsigned c2 = 2u * (unsigned)((kk + 1) & 31);             // (the read past the last step wraps to the first: unused)
 #pragma unroll
           for (int j = 0; j < 4; ++j) fb[(u + 1) & 1][j] = *(lds_frag*)(lds + baddr[j] + ((c2 ^ bx[j]) << 4));
           frag cur[2] = {wa[u][0], wa[u][1]};
-          const int kn = (kk + PF + rot) & 31;                            // (past the end: early steps again, unused)
+          const int kn = (kk + PF) & 31;                                  // (past the end: early steps again, unused)
 #pragma unroll
           for (int i = 0; i < 2; ++i) wa[u][i] = *reinterpret_cast<const frag*>(wp[i] + 512 * kn);
 #pragma unroll

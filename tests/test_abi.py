@@ -99,9 +99,16 @@ def test_product_library_has_no_ablation_surface():
     # (the measured-and-rejected kernels of rounds 1-5 are in neither build any more: git history + DESIGN_HISTORY.md)
     for kern in (b"chain_kernel", b"headfwd_kernel", b"wgrad256_kernel", b"14rowgemm_kernelI", b"headinfer_kernel", b"conv12_kernel", b"conv3x3p_kernel"):
         assert kern not in prod, kern
+    # one pose weight-gradient form: the code object holds no instantiation that no run can launch
+    pose_wgrad = set(re.findall(rb"(_ZN4acez21pose_mlp_wgrad_kernel\w*)\.kd", prod))
+    assert len(pose_wgrad) == 1, sorted(pose_wgrad)
     diag = open(b.build(diag=True), "rb").read()
     for name in (b"ACEZ_SEQ_FAULT_AT", b"ACEZ_WGO_FAULT_AT", b"ACEZ_CONV_TILE"):
         assert name in diag, name
+    # the timing-only ablation switches are gone from both builds (git history + DESIGN_HISTORY.md keep them)
+    for name in (b"ACEZ_CONV_DBG", b"ACEZ_LOSS_DBG", b"ACEZ_WGO_DBG", b"ACEZ_PATCH_MIN_TILES", b"ACEZ_HEAD_CONV_TILE", b"ACEZ_POSE_WB",
+                 b"ACEZ_POSE_WW", b"ACEZ_SEQ_NOPROBE"):
+        assert name not in prod and name not in diag, name
     # the same C ABI in both builds
     def exported(path):
         out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True).stdout

@@ -1,10 +1,10 @@
 """Stand-alone durations of the pose-refinement kernels (run under rocprofv3 --kernel-trace --stats on the GPU box):
-    [ACEZ_POSE_TILE=16] ACEZ_POSE_WB=32 python tools/pose_kernels_timing.py [n_images] [rows]
+    [ACEZ_POSE_TILE=16] python tools/pose_kernels_timing.py [n_images] [rows]
 Drives the split flow (acez_train_backward / acez_train_update), in which the reduction + backward chain rides at the front of the
 gradient-reduction launch (grad_reduce_pose_kernel) and the weight gradients (pose_mlp_wgrad_kernel) are their own launch, and
 acez_trainer_get_poses (pose_fwd_t_kernel)."""
 import os as _os
-_os.environ.setdefault("ACEZ_LIB", "diag")   # the ACEZ_* ablation switches exist in the diagnostics build only (acezero_amd/build.py --diag)
+_os.environ.setdefault("ACEZ_LIB", "diag")   # ACEZ_POSE_TILE exists in the diagnostics build only (acezero_amd/build.py --diag)
 import os
 import sys
 
