@@ -16,6 +16,10 @@ Three arithmetic modes (same convention as oracle/head_oracle.py):
     sums add two half tensors (the activation is rounded before the add, the sum once more).  PINNED: tests/golden/encoder_small.npz
     also holds the reference Encoder's output under torch.autocast("cpu", dtype=torch.float16) (make_encoder_golden.py); the two agree
     to the last-place flips of oneDNN's accumulation order (tests/test_encoder_oracle.py).
+
+forward(..., fused_skip=True) rounds the last layer as the encoder's fused res2_conv3 + res2_skip form does (conv3x3r with SKIP, which the
+default tiling picks from 7 frames of 480 x 640 on): the skip product is added to relu(res2_conv3 + bias) (rounded first in fp16 only) and
+the sum is rounded once. The default stays the reference's form. forward_variants() returns both from one shared prefix.
 """
 import numpy as np
 import torch
@@ -58,8 +62,8 @@ class EncoderOracle:
         b = self.sd[name + ".bias"]
         return F.conv2d(x, w, fp16_round(b) if self.mode == "fp16" else b, stride=stride, padding=pad)
 
-    def forward(self, image_b1hw):
-        """ace_network.py:42-59.  Returns features [B, C, H/8, W/8] (fp32 container of the 16-bit values in bf16 / fp16 mode)."""
+    def _trunk(self, image_b1hw):
+        """Everything before res2_conv3: (x9 = relu(res2_conv2(...)), res = the first residual block's output)."""
         r = self._r
         x = r(image_b1hw.to(torch.float32))
         x = r(F.relu(self._conv(x, "conv1", 1, 1)))
@@ -73,9 +77,40 @@ class EncoderOracle:
         res = r(res + pre(F.relu(self._conv(x, "res1_conv3", 1, 1))))
         x = r(F.relu(self._conv(res, "res2_conv1", 1, 1)))
         x = r(F.relu(self._conv(x, "res2_conv2", 1, 0)))
-        skip = r(self._conv(res, "res2_skip", 1, 0))
-        x = r(skip + pre(F.relu(self._conv(x, "res2_conv3", 1, 1))))
-        return x
+        return x, res
+
+    def _tail(self, x, res, variants):
+        """res2_skip(res) + relu(res2_conv3(x)) (ace_network.py:57-58) in the rounding of each requested variant (False: unfused, True:
+        fused_skip); relu(res2_conv3(x)) is computed once for both."""
+        r = self._r
+        pre = r if self.mode == "fp16" else (lambda t: t)
+        act = pre(F.relu(self._conv(x, "res2_conv3", 1, 1)))
+        out = []
+        for fused in variants:
+            if not fused:
+                # unfused (two launches): the skip layer's output is a stored 16-bit map, added by res2_conv3's epilogue
+                out.append(r(r(self._conv(res, "res2_skip", 1, 0)) + act))
+            else:
+                # conv3x3r's SKIP epilogue: the skip product goes onto res2_conv3's accumulators after its bias / ReLU (/ fp16 rounding)
+                # pass, then the skip bias is added and the sum rounded once -- the skip product is never rounded on its own
+                b = self.sd["res2_skip.bias"]
+                prod = F.conv2d(res, self._r(self.sd["res2_skip.weight"]), None, stride=1, padding=0)
+                out.append(r((act + prod) + (fp16_round(b) if self.mode == "fp16" else b).view(1, -1, 1, 1)))
+        return out
+
+    def forward(self, image_b1hw, fused_skip=False, frames=None):
+        """ace_network.py:42-59.  Returns features [B, C, H/8, W/8] (fp32 container of the 16-bit values in bf16 / fp16 mode).
+
+        fused_skip: the rounding of the encoder's fused res2_conv3 + res2_skip form (conv3x3r with SKIP) instead of the reference's.
+        frames: encode only these frames of the batch (the encoder is frame-independent)."""
+        return self.forward_variants(image_b1hw, frames, (bool(fused_skip),))[0]
+
+    def forward_variants(self, image_b1hw, frames=None, variants=(False, True)):
+        """Both res2 forms from one shared prefix: [unfused, fused_skip] features of `frames` (all frames by default)."""
+        if frames is not None:
+            image_b1hw = image_b1hw[list(frames)]
+        x, res = self._trunk(image_b1hw)
+        return self._tail(x, res, variants)
 
     def features_rows(self, image_b1hw):
         """[B*h*w, C] rows in pixel order (frame, y, x): the layout of the training buffer and of acez_head_forward."""

@@ -42,6 +42,13 @@ def test_encoder_matches_rounding_matched_oracle(shape, tile, dtype, monkeypatch
     # and against the un-rounded reference arithmetic
     ref32 = encoder_oracle.EncoderOracle(sd, "fp32").forward(img)
     assert _rel(out, ref32) < rel32, _rel(out, ref32)
+    # per pixel against the oracle of the form that ran: tile 3 fuses res2_skip into res2_conv3 (conv3x3r SKIP: the skip product is not
+    # rounded on its own) at every one of these shapes, the other tiles run it as its own launch
+    from tests.pixel_parity import assert_pixel_parity
+    from tests.test_encoder_forms_gpu import PIXEL
+    form = orc.forward(img, fused_skip=True) if tile == "3" else ref
+    pp = assert_pixel_parity(out, form, PIXEL[dtype], "tile %s %s:" % (tile, shape))
+    print("\n[%s] tile %s %s: %s" % (dtype, tile, shape, pp))
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])

@@ -2,6 +2,7 @@
 import os
 
 import numpy as np
+import pytest
 import torch
 
 from acezero_amd import synth
@@ -63,3 +64,48 @@ def test_rows_layout_is_pixel_major():
     rows = o.features_rows(img)
     assert rows.shape == (2 * 8 * 12, 512)
     assert torch.equal(rows[1 * 96 + 3 * 12 + 5], f[1, :, 3, 5])
+
+
+def _ulp(x, mode):
+    """Spacing of the 16-bit format at |x| (normal range)."""
+    mant = 7 if mode == "bf16" else 10
+    e = torch.floor(torch.log2(x.abs().clamp(min=2.0 ** -14)))
+    return 2.0 ** (e - mant)
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16", "fp16"])
+def test_default_form_is_unchanged(mode):
+    """The reference's form stays the default (smoke() and bench.py's CPU baseline use it): forward() is bitwise the unfused variant,
+    and a frame subset is bitwise those frames of the whole batch. The golden checks above pin the default's values."""
+    sd, img = _inputs()
+    o = encoder_oracle.EncoderOracle(sd, mode)
+    full = o.forward(img)
+    u, f = o.forward_variants(img)
+    assert torch.equal(full, u)
+    assert torch.equal(o.forward(img, fused_skip=False), full)
+    assert torch.equal(o.forward(img, frames=[1]), full[1:2])
+    assert torch.equal(o.forward(img, fused_skip=True, frames=[1]), f[1:2])
+
+
+@pytest.mark.parametrize("mode", ["bf16", "fp16"])
+def test_fused_skip_changes_only_the_last_rounding(mode):
+    """fused_skip differs from the reference's form only where res2_skip's output is (not) rounded on its own: per element by at most
+    half an ulp of the skip value plus one ulp of the output, and most elements are bitwise equal."""
+    sd, img = _inputs()
+    o = encoder_oracle.EncoderOracle(sd, mode)
+    x, res = o._trunk(img)
+    u, f = o._tail(x, res, (False, True))
+    skip = torch.nn.functional.conv2d(res, o._r(o.sd["res2_skip.weight"]), o.sd["res2_skip.bias"] if mode == "bf16" else
+                                      encoder_oracle.fp16_round(o.sd["res2_skip.bias"]))
+    assert not torch.equal(u, f)
+    assert torch.equal(f, o._r(f))
+    bound = 0.5 * _ulp(skip, mode) + _ulp(u, mode) + _ulp(f, mode)
+    assert bool(((u - f).abs() <= bound).all())
+    assert float((u == f).double().mean()) > 0.7
+
+
+def test_fused_skip_in_fp32_agrees_to_association():
+    sd, img = _inputs()
+    u, f = encoder_oracle.EncoderOracle(sd, "fp32").forward_variants(img)
+    assert float((u - f).abs().max()) < 1e-5 * float(u.abs().max())
+    assert float((u - f).norm() / u.norm()) < 1e-6
