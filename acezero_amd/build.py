@@ -18,13 +18,14 @@ STAMP = os.path.join(HERE, ".libacez.stamp")
 LIB_DIAG = os.path.join(HERE, "libacez_diag.so")
 STAMP_DIAG = os.path.join(HERE, ".libacez_diag.stamp")
 
-# translation unit -> extra flags.  The RANSAC, point-cloud, pose-evaluation and rendering units must not contract a*b+c into fma: their arithmetic
+# translation unit -> extra flags.  The RANSAC (RGB and RGB-D), point-cloud, pose-evaluation and rendering units must not contract a*b+c into fma: their arithmetic
 # is compared bit-for-bit with the CPU oracle (DESIGN.md "Determinism").
 UNITS = {
     "acez_common.hip": [],
     "head_api.hip": [],
     "encoder_api.hip": [],
     "ransac_api.hip": ["-ffp-contract=off"],
+    "ransac_rgbd.hip": ["-ffp-contract=off"],
     "cloud_api.hip": ["-ffp-contract=off"],
     "align_api.hip": ["-ffp-contract=off"],
     "render_api.hip": ["-ffp-contract=off"],

@@ -211,6 +211,17 @@ def register_parser():
     return p
 
 
+def register_rgbd_parser():
+    """register_mapping_rgbd.py: register_mapping.py's flags plus the depth maps; --threshold / --maxpixelerror are read in centimetres
+    (DSAC*'s RGB-D convention, dsacstar.cpp:498-500)."""
+    p = register_parser()
+    p.description = ("Estimate camera poses for a set of RGB-D images (MI355X DSAC* RGB-D: Kabsch on scene <-> camera coordinates). "
+                     "--threshold and --maxpixelerror are in CENTIMETRES here.")
+    p.add_argument("--depth_files", type=str, required=True, help="glob of the depth maps (16 bit, millimetres), one per image, in the "
+                   "sorted order of the images (the format ace_zero.py --depth_files reads)")
+    return p
+
+
 def ace_zero_parser():
     p = argparse.ArgumentParser(description="Run ACE0 for a scene in ONE process on one MI355X (acezero_amd.session).",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -530,10 +541,11 @@ def frame_size_classes(rgb_glob):
     return files, classes
 
 
-def _register_mixed_sizes(opt, files, classes):
+def _register_mixed_sizes(opt, files, classes, depth_files=None):
     """register_mapping.py on a folder whose frames have several sizes: registration is independent per frame, so every size class
     gets its own encoder / RANSAC context (one ReconstructionSession each); --max_estimates draws its seeded subset over the whole
-    list, the random streams are keyed by the position in the whole list, the pose file keeps the list's order."""
+    list, the random streams are keyed by the position in the whole list, the pose file keeps the list's order. depth_files (one per
+    file, same order): RGB-D registration."""
     import torch
     from .session import ReconstructionSession
     n = len(files)
@@ -558,9 +570,13 @@ def _register_mixed_sizes(opt, files, classes):
         so = _session_options(opt, use_external_focal_length=opt.use_external_focal_length * fscale if opt.use_external_focal_length > 0 else -1.0,
                               ransac_iterations=opt.hypotheses, ransac_threshold=opt.threshold, register_seed=opt.base_seed, use_aug=False,
                               registration_confidence=opt.confidence_threshold)
-        ses = ReconstructionSession(enc_sd, frames, opt=so)
+        depth = None
+        if depth_files is not None:
+            H, W = frames.shape[2:]
+            depth = torch.from_numpy(np.stack([depth_map_at_cells(depth_files[i], H, W) for i in pos]))
+        ses = ReconstructionSession(enc_sd, frames, opt=so, depth=depth)
         poses, inl = ses.register(head_sd, ses.focal0, max_tries=opt.hypotheses_max_tries, rng_ids=pos, tag=f"register {w}x{h}",
-                                  visualizer=vis, images=rgb[0] if rgb else None)
+                                  visualizer=vis, images=rgb[0] if rgb else None, use_depth=depth is not None)
         for k, i in enumerate(pos):
             rows[i] = (poses[k], int(inl[k]), ses.focal0 / fscale)
         del ses
@@ -575,24 +591,29 @@ def _register_mixed_sizes(opt, files, classes):
     return 0
 
 
-def _register_from_images(opt):
-    """register_mapping.py on image files: encoder -> head -> RANSAC for every frame (register_mapping.py:201-276)."""
+def _register_from_images(opt, depth_files=None):
+    """register_mapping.py on image files: encoder -> head -> RANSAC for every frame (register_mapping.py:201-276). depth_files (one
+    per image, in the sorted order of the images): RGB-D registration."""
     import torch
     from .session import ReconstructionSession, write_pose_file
     all_files, classes = frame_size_classes(opt.rgb_files)
     if len(classes) > 1:
-        return _register_mixed_sizes(opt, all_files, classes)
+        return _register_mixed_sizes(opt, all_files, classes, depth_files)
     files, frames, fscale, *rgb = load_frames(opt.rgb_files, opt.image_resolution, return_rgb=opt.render_visualization)
+    depth = None
+    if depth_files is not None:
+        H, W = frames.shape[2:]
+        depth = torch.from_numpy(np.stack([depth_map_at_cells(f, H, W) for f in depth_files]))
     so = _session_options(opt, use_external_focal_length=opt.use_external_focal_length * fscale if opt.use_external_focal_length > 0 else -1.0,
                           ransac_iterations=opt.hypotheses, ransac_threshold=opt.threshold, register_seed=opt.base_seed, use_aug=False,
                           registration_confidence=opt.confidence_threshold)
-    ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, opt=so)
+    ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, opt=so, depth=depth)
     vis = None
     if opt.render_visualization:
         vis = _register_visualizer(opt)
         vis.setup_reloc(len(files) if opt.max_estimates <= 0 else min(opt.max_estimates, len(files)))
     poses, inl = ses.register(torch.load(opt.network, map_location="cpu"), ses.focal0, max_estimates=opt.max_estimates, max_tries=opt.hypotheses_max_tries,
-                              visualizer=vis, images=rgb[0] if rgb else None)
+                              visualizer=vis, images=rgb[0] if rgb else None, use_depth=depth is not None)
     out = Path(opt.network).parent / f"poses_{opt.session}.txt"
     write_pose_file(out, [files[i] for i in ses.registered_ids], poses, inl, ses.focal0 / fscale)
     _logger.info(f"Registered {len(poses)} images -> {out}")
@@ -656,6 +677,26 @@ def register_main(argv=None):
             vis.render_reloc_frame(poses[k].astype(np.float64), int(inl[k]))
         vis.save_reloc_state(os.path.join(str(opt.render_target_path), Path(opt.network).stem + "_register.pkl"))
     return 0
+
+
+def register_rgbd_main(argv=None):
+    """register_mapping_rgbd.py: register_mapping.py's image path with DSAC*'s RGB-D estimator (dsacstar.forward_rgbd): the depth map
+    of every image gives camera coordinates at the feature-map cells, --threshold / --maxpixelerror are centimetres. Writes the same
+    poses_<session>.txt."""
+    import glob
+    opt = register_rgbd_parser().parse_args(argv)
+    logging.basicConfig(level=logging.INFO)
+    if opt.feature_file is not None:
+        raise SystemExit("register_mapping_rgbd.py reads the images and their depth maps; --feature_file holds neither the frames' pixels "
+                         "nor their depth (use register_mapping.py for it)")
+    files = sorted(glob.glob(opt.rgb_files))
+    if not files:
+        raise SystemExit(f"no files match {opt.rgb_files!r}")
+    depth_files = sorted(glob.glob(opt.depth_files))
+    if len(depth_files) != len(files):
+        raise SystemExit(f"--depth_files matches {len(depth_files)} files for {len(files)} images: one depth map per image is needed, "
+                         "paired with the images in sorted order")
+    return _register_from_images(opt, depth_files)
 
 
 # --------------------------------------------------------------------------------------------------------- ace_zero
@@ -765,21 +806,25 @@ def load_depth_maps(depth_glob, n, frame_hw):
     of n per-frame (H_i, W_i) (a folder of mixed sizes): a list of n float32 [ceil(H_i/8), ceil(W_i/8)] maps."""
     import glob
     import torch
-    from PIL import Image
     files = sorted(glob.glob(depth_glob))
     if len(files) != n:
         raise SystemExit(f"{len(files)} depth files for {n} images")
-
-    def one(f, H, W):
-        d = np.asarray(Image.open(f).resize((W, H), Image.NEAREST), np.float32) / 1000.0
-        sub = d[4::8, 4::8]
-        out = np.zeros(((H + 7) // 8, (W + 7) // 8), np.float32)
-        out[:sub.shape[0], :sub.shape[1]] = sub
-        return out
+    one = depth_map_at_cells
     if isinstance(frame_hw, list):
         return [torch.from_numpy(one(f, int(h), int(w))) for f, (h, w) in zip(files, frame_hw)]
     H, W = frame_hw
     return torch.from_numpy(np.stack([one(f, H, W) for f in files]) if n else np.zeros((0, (H + 7) // 8, (W + 7) // 8), np.float32))
+
+
+def depth_map_at_cells(path, H, W):
+    """One depth file (16-bit millimetres) -> metres, nearest resize to the H x W frame, value at the feature-map pixel centres
+    (offset 4, stride 8): float32 [ceil(H/8), ceil(W/8)]."""
+    from PIL import Image
+    d = np.asarray(Image.open(path).resize((W, H), Image.NEAREST), np.float32) / 1000.0
+    sub = d[4::8, 4::8]
+    out = np.zeros(((H + 7) // 8, (W + 7) // 8), np.float32)
+    out[:sub.shape[0], :sub.shape[1]] = sub
+    return out
 
 
 def frame_shapes(frames, n):

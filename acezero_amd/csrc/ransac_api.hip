@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include "ransac_math.h"
 #include "acez_common.h"
+#include "ransac_ctx.h"
 #include <new>
 #include <vector>
 
@@ -30,10 +31,7 @@ namespace {
 using rsm::Cam;
 using rsm::Pose;
 
-struct FrameParam {
-  float focal, ppx, ppy, pad;
-  uint64_t frame_id;
-};
+using acez_rs::FrameParam;
 
 struct RansacArgs {
   const float* sc;  // [n][3][H][W]
@@ -599,36 +597,8 @@ __global__ __launch_bounds__(256, 2) void ransac_kernel(RansacArgs a) {
 // ====================================================================================================
 // C ABI
 // ====================================================================================================
-namespace {
-constexpr int PARAM_SLOTS = 4;
-// One pinned + device copy of the per-frame parameter block per call in flight: acez_register_rgb_device never waits for the
-// stream it launches on (only for the call PARAM_SLOTS launches ago, whose kernel has long finished in any pipelined use).
-struct ParamSlot {
-  FrameParam* h = nullptr;  // pinned
-  FrameParam* d = nullptr;
-  hipEvent_t done = nullptr;
-  bool in_flight = false;
-};
-}  // namespace
-
-struct acez_ransac {
-  int device = 0;
-  int max_frames = 0, max_h = 0, max_w = 0, max_hyps = 0;
-  ParamSlot slot[PARAM_SLOTS];
-  int next_slot = 0;
-  double* d_hyp_poses = nullptr;
-  double* d_scores = nullptr;
-  int* d_best = nullptr;
-  double* d_refined = nullptr;
-  float* d_big = nullptr;      // scan-order copies of frames that do not fit the LDS, allocated on first use
-  size_t big_floats = 0;
-  // staging for the host-buffer entry point
-  float* d_sc = nullptr;
-  float* d_pose = nullptr;
-  int* d_inl = nullptr;
-  uint8_t* d_mask = nullptr;
-  int last_hyps = 0;
-};
+using acez_rs::PARAM_SLOTS;
+using acez_rs::ParamSlot;
 
 static int ensure_hyps(acez_ransac* ctx, int hyps) {
   if (hyps <= ctx->max_hyps) return ACEZ_OK;
@@ -661,6 +631,7 @@ extern "C" void acez_ransac_destroy(acez_ransac* ctx) {
   if (ctx->d_pose) (void)hipFree(ctx->d_pose);
   if (ctx->d_inl) (void)hipFree(ctx->d_inl);
   if (ctx->d_mask) (void)hipFree(ctx->d_mask);
+  acez_rs::rgbd_release(ctx->rgbd);
   delete ctx;
 }
 

@@ -135,3 +135,105 @@ def debug_fetch(n, hyps, device=None):
     N.check(L.acez_ransac_debug_fetch(ctx, n, hyps, hp.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
                                             best.ctypes.data_as(C.c_void_p), ref.ctypes.data_as(C.c_void_p)))
     return {"hyp_poses": hp, "scores": sc, "best": best, "refined": ref}
+
+
+# ---------------------------------------------------------------------------------------------------- RGB-D (forward_rgbd)
+MAX_HYPOTHESES_TRIES = 16  # dsacstar.cpp:48, the tries of the reference's RGB-D sampling
+
+
+def _params_rgbd(hyps, thr, alpha, max_reproj, max_tries=MAX_HYPOTHESES_TRIES, sub=8):
+    """acez_ransac_params of an RGB-D call: thr and max_reproj are centimetres (3D distance), sub is unused."""
+    return N.RansacParams(int(hyps), int(max_tries), float(thr), float(alpha), float(max_reproj), int(sub), MAX_REF_STEPS, 0)
+
+
+def camera_coordinates(depth, focal, ppx, ppy, stride=8):
+    """Camera coordinates at the feature-map cell centres (stride x + stride / 2) from depth [n,h,w] (metres, 0 = none): float32
+    [n,3,h,w] on depth's device. focal / ppx / ppy: one value, or one per frame. The mapping buffer's formula
+    (ReconstructionSession._fill_buffer, dataset.py:347-388): eye = ((px - ppx) / f * d, (py - ppy) / f * d, d) in float32, so that
+    mapping and registration agree on every cell."""
+    d = torch.as_tensor(depth, dtype=torch.float32)
+    if d.dim() == 2:
+        d = d[None]
+    n, h, w = d.shape
+    dev = d.device
+
+    def per_frame(v):
+        return torch.as_tensor(np.broadcast_to(np.asarray(v, np.float32), (n,)).copy()).to(dev).view(n, 1, 1)
+    f, cx, cy = per_frame(focal), per_frame(ppx), per_frame(ppy)
+    px = (torch.arange(w, device=dev, dtype=torch.float32) * stride + stride // 2).view(1, 1, w)
+    py = (torch.arange(h, device=dev, dtype=torch.float32) * stride + stride // 2).view(1, h, 1)
+    return torch.stack([(px - cx) / f * d, (py - cy) / f * d, d], dim=1).contiguous()
+
+
+def forward_rgbd(sceneCoordinates, cameraCoordinates, outPose, ransacHypotheses, inlierThreshold, inlierAlpha, maxDistError):
+    """The reference's commented-out binding (dsacstar.cpp:493-640,901): 1x3xHxW scene and camera coordinates (metres), in-place
+    cam->world `outPose`, inlierThreshold / maxDistError in centimetres; returns the inlier count. As in forward_rgb, the per-process
+    call counter keys the random stream (the reference's ThreadRand::init() continues one stream across calls)."""
+    global _calls
+    sc, cc = sceneCoordinates, cameraCoordinates
+    for name, t in (("sceneCoordinates", sc), ("cameraCoordinates", cc)):
+        if t.dim() != 4 or t.shape[0] != 1 or t.shape[1] != 3 or t.dtype != torch.float32:
+            raise RuntimeError(f"{name} must be a float32 tensor of shape 1x3xHxW")
+    if tuple(sc.shape) != tuple(cc.shape):
+        raise RuntimeError("sceneCoordinates and cameraCoordinates must have the same shape")
+    if outPose.dim() != 2 or tuple(outPose.shape) != (4, 4) or outPose.dtype != torch.float32:
+        raise RuntimeError("outPose must be a float32 tensor of shape 4x4")
+    if not torch.cuda.is_available():
+        raise RuntimeError("dsacstar.forward_rgbd: no GPU visible; the MI355X implementation has no CPU path")
+    H, W = int(sc.shape[2]), int(sc.shape[3])
+    frame_id = _calls
+    _calls += 1
+    prm = _params_rgbd(ransacHypotheses, inlierThreshold, inlierAlpha, maxDistError)
+    if sc.is_cuda or cc.is_cuda:
+        dev = sc.device if sc.is_cuda else cc.device
+        poses, inl, _ = register_batch_rgbd(sc[0][None].to(dev), cc[0][None].to(dev), prm, 0, [frame_id], want_masks=False)
+        outPose.copy_(poses[0].to(outPose.device))
+        return int(inl[0].item())
+    ctx, L = _context(1, H, W, torch.cuda.current_device())
+    pose = np.zeros(16, np.float32)
+    inliers = C.c_int32(0)
+    s1, s2 = sc.stride(), cc.stride()
+    N.check(L.acez_register_rgbd_host(ctx, C.c_void_p(sc.data_ptr()), s1[1], s1[2], s1[3], C.c_void_p(cc.data_ptr()), s2[1], s2[2], s2[3],
+                                      H, W, C.byref(prm), C.c_uint64(0), C.c_uint64(frame_id), pose.ctypes.data_as(C.c_void_p),
+                                      C.byref(inliers), None))
+    outPose.copy_(torch.from_numpy(pose.reshape(4, 4)))
+    return int(inliers.value)
+
+
+def register_batch_rgbd(scene_coords, camera_coords, params, seed, frame_ids=None, want_masks=True):
+    """scene_coords, camera_coords: CUDA float32 [n,3,H,W] (metres); params: N.RansacParams or dict(hyps, thr, alpha, max_reproj
+    [, max_tries]) with thr / max_reproj in centimetres. Returns (poses [n,4,4] f32 cam->world, inliers [n] i32, masks [n,H,W] u8 or
+    None), all CUDA tensors; asynchronous."""
+    for t in (scene_coords, camera_coords):
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] == 3
+    assert tuple(scene_coords.shape) == tuple(camera_coords.shape) and scene_coords.device == camera_coords.device
+    sc, cc = scene_coords.contiguous(), camera_coords.contiguous()
+    n, _, H, W = sc.shape
+    dev = sc.device
+    ctx, L = _context(n, H, W, dev.index)
+    if not isinstance(params, N.RansacParams):
+        params = _params_rgbd(**params)
+    ids = None
+    if frame_ids is not None:
+        ids = (C.c_uint64 * n)(*[int(x) for x in frame_ids])
+    poses = torch.empty(n, 4, 4, dtype=torch.float32, device=dev)
+    inl = torch.empty(n, dtype=torch.int32, device=dev)
+    masks = torch.empty(n, H, W, dtype=torch.uint8, device=dev) if want_masks else None
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        N.check(L.acez_register_rgbd_device(ctx, C.c_void_p(sc.data_ptr()), C.c_void_p(cc.data_ptr()), n, H, W, C.byref(params),
+                                            C.c_uint64(int(seed)), ids, C.c_void_p(poses.data_ptr()), C.c_void_p(inl.data_ptr()),
+                                            C.c_void_p(masks.data_ptr()) if masks is not None else None, stream))
+    return poses, inl, masks
+
+
+def debug_fetch_rgbd(n, hyps, device=None):
+    """Per-hypothesis results of the last RGB-D call: sampled triples (map indices y*W+x), (rvec, tvec), scores, best, refined."""
+    dev = torch.cuda.current_device() if device is None else device
+    L = N.lib()
+    ctx = _ctx[(dev, L._name)]["h_"]
+    smp = np.zeros((n, hyps, 3), np.int32); hp = np.zeros((n, hyps, 6)); sc = np.zeros((n, hyps)); best = np.zeros(n, np.int32)
+    ref = np.zeros((n, 6))
+    N.check(L.acez_ransac_rgbd_debug_fetch(ctx, n, hyps, smp.ctypes.data_as(C.c_void_p), hp.ctypes.data_as(C.c_void_p),
+                                           sc.ctypes.data_as(C.c_void_p), best.ctypes.data_as(C.c_void_p), ref.ctypes.data_as(C.c_void_p)))
+    return {"samples": smp, "hyp_poses": hp, "scores": sc, "best": best, "refined": ref}

@@ -710,7 +710,8 @@ class ReconstructionSession:
         head.close()
         return out
 
-    def register(self, head_sd, focal, max_estimates=-1, tag="register", max_tries=16, rng_ids=None, visualizer=None, images=None):
+    def register(self, head_sd, focal, max_estimates=-1, tag="register", max_tries=16, rng_ids=None, visualizer=None, images=None,
+                 use_depth=False):
         """register_mapping.py:201-276: (poses cam->world [k,4,4] float32, inlier counts [k] int32); the k frame ids they belong to
         are left in self.registered_ids (all frames in order unless max_estimates draws a subset).
 
@@ -723,8 +724,13 @@ class ReconstructionSession:
         the random streams, if they are not the positions in this session.
         visualizer (acezero_amd.render.Visualizer, set up with setup_reloc): one registration frame per registered frame, in order,
         each with that frame's uint8 RGB image inside its frustum: images[i] for frame i (default: the visualiser's frame_rgb; none:
-        outlines only)."""
+        outlines only).
+        use_depth: RGB-D registration (dsacstar.forward_rgbd's estimator) from the session's depth maps: camera coordinates at the cell
+        centres (dsacstar.camera_coordinates, the mapping buffer's formula with each frame's focal and its class's principal point),
+        ransac_threshold and maxpixelerror read as centimetres."""
         o = self.opt
+        if use_depth and self.depth is None:
+            raise RuntimeError("register(use_depth=True) needs the session's depth maps (depth=...)")
         if max_estimates <= 0 or max_estimates >= self.n:
             ids = np.arange(self.n)
         else:
@@ -742,7 +748,12 @@ class ReconstructionSession:
             sub = mine[at]
             sc = self.scene_coordinates(head_sd, sub)
             keys = [int(i) for i in sub] if rng_ids is None else [int(rng_ids[i]) for i in sub]
-            p_, i_, _ = dsacstar.register_batch(sc, [(focal * self.frel[i], c.ppx, c.ppy) for i in sub], prm, o.register_seed, keys, want_masks=False)
+            if use_depth:
+                cc = dsacstar.camera_coordinates(self.frame_depth(sub), [focal * self.frel[i] for i in sub], c.ppx, c.ppy)
+                p_, i_, _ = dsacstar.register_batch_rgbd(sc, cc, prm, o.register_seed, keys, want_masks=False)
+            else:
+                p_, i_, _ = dsacstar.register_batch(sc, [(focal * self.frel[i], c.ppx, c.ppy) for i in sub], prm, o.register_seed, keys,
+                                                    want_masks=False)
             poses[at], inl[at] = p_.cpu(), i_.cpu().to(torch.int32)
         if self.world > 1:
             full_p, full_i = gather_registrations([int(i) for i in mine], poses, inl, self.n, self.group, expect=ids)
@@ -757,6 +768,15 @@ class ReconstructionSession:
             for k in range(len(ids)):
                 visualizer.render_reloc_frame(np.asarray(poses[k], np.float64), int(inl[k]), None if images is None else images[int(ids[k])])
         return poses, inl
+
+    def frame_depth(self, frame_ids):
+        """Depth maps [k, oh, ow] (metres, 0 = none) of the given frames, all of one size class, on the device."""
+        ids = np.asarray(frame_ids, np.int64)
+        c = self.classes[self.frame_class[ids[0]]]
+        d = self.depth[torch.from_numpy(ids).to(self.dev)] if torch.is_tensor(self.depth) else torch.stack([self.depth[int(i)] for i in ids])
+        if tuple(d.shape[1:]) != (c.oh, c.ow):
+            raise ValueError(f"depth maps of {tuple(d.shape[1:])} cells for frames of {c.oh} x {c.ow} scene coordinates")
+        return d
 
     # --------------------------------------------------------------------------------------------------- the loop (ace_zero.py)
     def _seed_map_args(self, seed_idx, seed):

@@ -6,6 +6,7 @@ dsacstar/dsacstar.cpp with OpenCV; here it is the MI355X implementation behind t
                                    inlier_alpha, max_reproj, subsampling, seed, max_hypotheses_tries)
 
 Put the repository root on PYTHONPATH (or copy this directory next to register_mapping.py) and the reference's
-register_mapping.py runs unchanged on this call. Extras (not in the reference): register_batch (device-resident, batched),
+register_mapping.py runs unchanged on this call. forward_rgbd is the reference's commented-out RGB-D binding (dsacstar.cpp:901),
+same arguments. Extras (not in the reference): register_batch / register_batch_rgbd (device-resident, batched),
 set_verbose, reset_call_counter."""
-from acezero_amd.dsacstar import forward_rgb, register_batch, reset_call_counter, set_verbose  # noqa: F401
+from acezero_amd.dsacstar import forward_rgb, forward_rgbd, register_batch, register_batch_rgbd, reset_call_counter, set_verbose  # noqa: F401

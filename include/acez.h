@@ -106,6 +106,44 @@ int acez_register_rgb_host(acez_ransac* ctx, const float* h_scene_coords, int64_
 int acez_ransac_debug_fetch(acez_ransac* ctx, int n_frames, int hypotheses, double* h_hyp_poses,
                             double* h_scores, int32_t* h_best, double* h_refined);
 
+/* RGB-D registration: the reference's commented-out dsacstar.forward_rgbd (dsacstar.cpp:493-640). A pose from 3D-3D
+ * correspondences (Kabsch on three cells per hypothesis, 3D distance scores, Kabsch refinement on the inliers), no PnP.
+ * Same context as the RGB calls; acez_ransac_params keeps its fields with these meanings here:
+ *   hypotheses, max_tries, max_ref_steps   as above
+ *   inlier_threshold   inlierThreshold in CENTIMETRES (3D distance)
+ *   inlier_alpha       inlierAlpha
+ *   max_reproj         maxDistError in CENTIMETRES (distance errors are clamped to it)
+ *   subsampling        unused
+ *   d_scene_coords   float32 [n_frames][3][h][w] scene coordinates, metres (the layout acez_register_rgb_device takes)
+ *   d_camera_coords  float32 [n_frames][3][h][w] camera coordinates back-projected from measured depth, metres; a cell is
+ *                    valid when its coordinate is finite with z != 0
+ *   seed, h_frame_ids  key the random stream as in acez_register_rgb_device
+ *   d_out_poses      float32 [n_frames][4][4] row-major cam->world pose (pose2trans)
+ *   d_out_inliers    int32   [n_frames] inliers of the last accepted refinement step (0 if none was accepted)
+ *   d_out_masks      uint8   [n_frames][h][w] that step's inlier map, or NULL
+ * A frame with fewer than 3 valid cells gives the identity pose and 0 inliers. Asynchronous on `stream`. */
+int acez_register_rgbd_device(acez_ransac* ctx, const float* d_scene_coords, const float* d_camera_coords, int n_frames,
+                              int h, int w, const acez_ransac_params* params, uint64_t seed,
+                              const uint64_t* h_frame_ids, float* d_out_poses, int32_t* d_out_inliers,
+                              uint8_t* d_out_masks, void* stream);
+
+/* Host-buffer variant of dsacstar.forward_rgbd for ONE frame; strides in elements for each tensor. Synchronous. */
+int acez_register_rgbd_host(acez_ransac* ctx, const float* h_scene_coords, int64_t sc_stride_c, int64_t sc_stride_h,
+                            int64_t sc_stride_w, const float* h_camera_coords, int64_t cc_stride_c,
+                            int64_t cc_stride_h, int64_t cc_stride_w, int h, int w,
+                            const acez_ransac_params* params, uint64_t seed, uint64_t frame_id,
+                            float* h_out_pose16, int32_t* out_inliers, uint8_t* h_out_mask /* nullable, h*w */);
+
+/* Diagnostics of the LAST acez_register_rgbd_* call:
+ *   h_samples    int32   [n_frames][hypotheses][3]  map indices y*w+x of the triple each hypothesis was fitted to (-1: none)
+ *   h_hyp_poses  float64 [n_frames][hypotheses][6]  (rvec, tvec) after sampling
+ *   h_scores     float64 [n_frames][hypotheses]     soft inlier scores
+ *   h_best       int32   [n_frames]                 selected hypothesis (the first maximum)
+ *   h_refined    float64 [n_frames][6]              (rvec, tvec) after refinement
+ * Any pointer may be NULL. Synchronous. */
+int acez_ransac_rgbd_debug_fetch(acez_ransac* ctx, int n_frames, int hypotheses, int32_t* h_samples,
+                                 double* h_hyp_poses, double* h_scores, int32_t* h_best, double* h_refined);
+
 /* ------------------------------------------------------------------------------------------------
  * (T) head training / inference
  * ---------------------------------------------------------------------------------------------- */
