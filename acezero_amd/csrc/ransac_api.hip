@@ -19,6 +19,8 @@
 //               wavefronts in a fixed order through LDS; the 6x6 solve runs on wavefront 0.
 // Nothing is written to HBM between stages except the diagnostics (hypothesis poses / scores).
 // Roofline: per frame 57.6 KB in, ~5 KB out; the kernel is fp64-VALU/latency bound.
+// This unit also defines the registration host side that ransac_rgbd.hip shares (ransac_ctx.h): the context, the per-estimator
+// workspaces, the frame-parameter slot ring, the launch geometry, the host-buffer staging and the debug fetch.
 #include <hip/hip_runtime.h>
 #include "ransac_math.h"
 #include "acez_common.h"
@@ -30,6 +32,7 @@ namespace {
 
 using rsm::Cam;
 using rsm::Pose;
+using rsm::div_h;
 
 using acez_rs::FrameParam;
 
@@ -110,9 +113,6 @@ __device__ __forceinline__ void wave_tree28(const double acc[28], double out7[7]
   }
 }
 
-// x = p / H for p < 2^16 (see RansacArgs::h_magic)
-__device__ __forceinline__ int div_h(int p, int H, uint32_t magic) { return H == 1 ? p : (int)__umulhi((uint32_t)p, magic); }
-
 // detm::exp_ with 32-bit integer steps (|x * INV_LN2| < 1100, so the int conversion, k / 2 and the exponent words are the same
 // values as the 64-bit ones of det_math.h; every floating-point operation is identical)
 __device__ __forceinline__ double exp_dev(double x) {
@@ -191,9 +191,8 @@ constexpr int MAX_ROWS = 64;                        // pixels per thread (inlier
 constexpr int RED_DOUBLES = 8 + 2 * 4 * 28;         // step hand-over + reduction scratch
 constexpr int REGION_MIN = RED_DOUBLES + MAX_ROWS * 4 / 2;
 __host__ __device__ inline int region_doubles(int hyps) { return 7 * hyps > REGION_MIN ? 7 * hyps : REGION_MIN; }
-__host__ __device__ inline size_t lds_bytes(int N, int hyps, bool coords_in_hbm) {
-  const size_t Npad = (size_t)((N + 3) & ~3);
-  return (coords_in_hbm ? 0 : 12 * Npad) + 2 * Npad + 8 * (size_t)region_doubles(hyps) + 8 * sizeof(int);
+__host__ __device__ inline size_t lds_bytes(int Npad, int hyps, bool coords_in_hbm) {
+  return (coords_in_hbm ? 0 : 12 * (size_t)Npad) + 2 * (size_t)Npad + 8 * (size_t)region_doubles(hyps) + 8 * sizeof(int);
 }
 
 // GC: the frame does not fit the LDS (more than ~11 400 scene coordinates): its scan-order copy lives in an HBM workspace (L2
@@ -595,43 +594,116 @@ __global__ __launch_bounds__(256, 2) void ransac_kernel(RansacArgs a) {
 }  // namespace
 
 // ====================================================================================================
-// C ABI
+// The registration host side shared with ransac_rgbd.hip (declared in ransac_ctx.h)
 // ====================================================================================================
-using acez_rs::PARAM_SLOTS;
-using acez_rs::ParamSlot;
+namespace acez_rs {
 
-static int ensure_hyps(acez_ransac* ctx, int hyps) {
-  if (hyps <= ctx->max_hyps) return ACEZ_OK;
+int ensure_hyps(Workspace& ws, int hyps, bool samples) {
+  if (!ws.d_best) ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_best, (size_t)ws.frames * sizeof(int)));
+  if (!ws.d_refined) ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_refined, (size_t)ws.frames * 6 * sizeof(double)));
+  if (hyps <= ws.hyps) return ACEZ_OK;
   ACEZ_HIP_CHECK(hipDeviceSynchronize());   // earlier launches may still write the old buffers
-  if (ctx->d_hyp_poses) (void)hipFree(ctx->d_hyp_poses);
-  if (ctx->d_scores) (void)hipFree(ctx->d_scores);
-  ctx->d_hyp_poses = nullptr;
-  ctx->d_scores = nullptr;
-  ACEZ_HIP_CHECK(hipMalloc((void**)&ctx->d_hyp_poses, (size_t)ctx->max_frames * hyps * 6 * sizeof(double)));
-  ACEZ_HIP_CHECK(hipMalloc((void**)&ctx->d_scores, (size_t)ctx->max_frames * hyps * sizeof(double)));
-  ctx->max_hyps = hyps;
+  if (ws.d_hyp_poses) (void)hipFree(ws.d_hyp_poses);
+  if (ws.d_scores) (void)hipFree(ws.d_scores);
+  if (ws.d_samples) (void)hipFree(ws.d_samples);
+  ws.d_hyp_poses = nullptr; ws.d_scores = nullptr; ws.d_samples = nullptr;
+  ws.hyps = 0;
+  ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_hyp_poses, (size_t)ws.frames * hyps * 6 * sizeof(double)));
+  ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_scores, (size_t)ws.frames * hyps * sizeof(double)));
+  if (samples) ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_samples, (size_t)ws.frames * hyps * 3 * sizeof(int)));
+  ws.hyps = hyps;
   return ACEZ_OK;
 }
 
+int ensure_list_floats(Workspace& ws, size_t floats) {
+  if (floats <= ws.list_floats) return ACEZ_OK;
+  ACEZ_HIP_CHECK(hipDeviceSynchronize());
+  if (ws.d_list) (void)hipFree(ws.d_list);
+  ws.d_list = nullptr;
+  ws.list_floats = 0;
+  ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_list, floats * sizeof(float)));
+  ws.list_floats = floats;
+  return ACEZ_OK;
+}
+
+void release(Workspace& ws) {
+  for (void* p : {(void*)ws.d_hyp_poses, (void*)ws.d_scores, (void*)ws.d_samples, (void*)ws.d_best, (void*)ws.d_refined, (void*)ws.d_list})
+    if (p) (void)hipFree(p);
+  ws = Workspace();
+}
+
+int plan_launch(Workspace& ws, int h, int w, int hyps, int list_floats_per_cell, size_t (*lds_bytes)(int, int, bool), Geometry* g) {
+  g->N = h * w;
+  g->Npad = (g->N + 3) & ~3;
+  g->h_magic = h > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)h - 1) / (uint64_t)h) : 0u;
+  g->hbm = lds_bytes(g->Npad, hyps, false) > 160 * 1024;
+  g->lds = lds_bytes(g->Npad, hyps, g->hbm);
+  ACEZ_REQUIRE(g->lds <= 160 * 1024, "too many hypotheses for the 160 KB LDS of a CU");
+  return g->hbm ? ensure_list_floats(ws, (size_t)ws.frames * list_floats_per_cell * g->Npad) : ACEZ_OK;
+}
+
+int stage_params(acez_ransac* ctx, hipStream_t s, int n, const acez_intrinsics* h_intrinsics, const uint64_t* h_frame_ids,
+                 ParamSlot** out) {
+  ParamSlot& slot = ctx->slot[ctx->next_slot];
+  ctx->next_slot = (ctx->next_slot + 1) % PARAM_SLOTS;
+  if (slot.in_flight) ACEZ_HIP_CHECK(hipEventSynchronize(slot.done));
+  for (int i = 0; i < n; ++i) {
+    const acez_intrinsics k = h_intrinsics ? h_intrinsics[i] : acez_intrinsics{0.f, 0.f, 0.f};
+    slot.h[i] = FrameParam{k.focal, k.ppx, k.ppy, 0.f, h_frame_ids ? h_frame_ids[i] : (uint64_t)i};
+  }
+  ACEZ_HIP_CHECK(hipMemcpyAsync(slot.d, slot.h, (size_t)n * sizeof(FrameParam), hipMemcpyHostToDevice, s));
+  *out = &slot;
+  return ACEZ_OK;
+}
+
+int upload_strided(float* d_dst, const float* h_src, int64_t stride_c, int64_t stride_h, int64_t stride_w, int h, int w) {
+  std::vector<float> packed((size_t)3 * h * w);
+  for (int c = 0; c < 3; ++c)
+    for (int y = 0; y < h; ++y)
+      for (int x = 0; x < w; ++x) packed[((size_t)c * h + y) * w + x] = h_src[c * stride_c + y * stride_h + x * stride_w];
+  ACEZ_HIP_CHECK(hipMemcpy(d_dst, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+  return ACEZ_OK;
+}
+
+int download_result(const acez_ransac* ctx, int h, int w, float* h_out_pose16, int32_t* out_inliers, uint8_t* h_out_mask) {
+  ACEZ_HIP_CHECK(hipMemcpy(h_out_pose16, ctx->d_pose, 16 * sizeof(float), hipMemcpyDeviceToHost));
+  ACEZ_HIP_CHECK(hipMemcpy(out_inliers, ctx->d_inl, sizeof(int), hipMemcpyDeviceToHost));
+  if (h_out_mask) ACEZ_HIP_CHECK(hipMemcpy(h_out_mask, ctx->d_mask, (size_t)h * w, hipMemcpyDeviceToHost));
+  return ACEZ_OK;
+}
+
+int debug_fetch(const acez_ransac* ctx, const Workspace& ws, int n_frames, int hypotheses, int32_t* h_samples, double* h_hyp_poses,
+                double* h_scores, int32_t* h_best, double* h_refined) {
+  ACEZ_REQUIRE(n_frames > 0 && n_frames <= ws.frames && hypotheses == ws.last_hyps, "shape does not match the last call");
+  ACEZ_HIP_CHECK(hipSetDevice(ctx->device));
+  ACEZ_HIP_CHECK(hipDeviceSynchronize());
+  const size_t nh = (size_t)n_frames * hypotheses;
+  if (h_samples) ACEZ_HIP_CHECK(hipMemcpy(h_samples, ws.d_samples, nh * 3 * sizeof(int), hipMemcpyDeviceToHost));
+  if (h_hyp_poses) ACEZ_HIP_CHECK(hipMemcpy(h_hyp_poses, ws.d_hyp_poses, nh * 6 * sizeof(double), hipMemcpyDeviceToHost));
+  if (h_scores) ACEZ_HIP_CHECK(hipMemcpy(h_scores, ws.d_scores, nh * sizeof(double), hipMemcpyDeviceToHost));
+  if (h_best) ACEZ_HIP_CHECK(hipMemcpy(h_best, ws.d_best, (size_t)n_frames * sizeof(int), hipMemcpyDeviceToHost));
+  if (h_refined) ACEZ_HIP_CHECK(hipMemcpy(h_refined, ws.d_refined, (size_t)n_frames * 6 * sizeof(double), hipMemcpyDeviceToHost));
+  return ACEZ_OK;
+}
+
+}  // namespace acez_rs
+
+// ====================================================================================================
+// C ABI
+// ====================================================================================================
 extern "C" void acez_ransac_destroy(acez_ransac* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   (void)hipDeviceSynchronize();
-  for (ParamSlot& s : ctx->slot) {
+  for (acez_rs::ParamSlot& s : ctx->slot) {
     if (s.d) (void)hipFree(s.d);
     if (s.h) (void)hipHostFree(s.h);
     if (s.done) (void)hipEventDestroy(s.done);
   }
-  if (ctx->d_hyp_poses) (void)hipFree(ctx->d_hyp_poses);
-  if (ctx->d_scores) (void)hipFree(ctx->d_scores);
-  if (ctx->d_best) (void)hipFree(ctx->d_best);
-  if (ctx->d_refined) (void)hipFree(ctx->d_refined);
-  if (ctx->d_big) (void)hipFree(ctx->d_big);
-  if (ctx->d_sc) (void)hipFree(ctx->d_sc);
-  if (ctx->d_pose) (void)hipFree(ctx->d_pose);
-  if (ctx->d_inl) (void)hipFree(ctx->d_inl);
-  if (ctx->d_mask) (void)hipFree(ctx->d_mask);
-  acez_rs::rgbd_release(ctx->rgbd);
+  acez_rs::release(ctx->rgb);
+  acez_rs::release(ctx->rgbd);
+  for (void* p : {(void*)ctx->d_sc, (void*)ctx->d_cc, (void*)ctx->d_pose, (void*)ctx->d_inl, (void*)ctx->d_mask})
+    if (p) (void)hipFree(p);
   delete ctx;
 }
 
@@ -657,6 +729,7 @@ extern "C" int acez_ransac_create(acez_ransac** out, int max_frames, int max_h, 
   ctx->max_frames = max_frames;
   ctx->max_h = max_h;
   ctx->max_w = max_w;
+  ctx->rgb.frames = ctx->rgbd.frames = max_frames;
   int rc = ACEZ_OK;
   auto A = [&](void** p, size_t bytes) {
     if (rc == ACEZ_OK && hipMalloc(p, bytes) != hipSuccess) {
@@ -664,7 +737,7 @@ extern "C" int acez_ransac_create(acez_ransac** out, int max_frames, int max_h, 
       rc = ACEZ_ERR_HIP;
     }
   };
-  for (ParamSlot& s : ctx->slot) {
+  for (acez_rs::ParamSlot& s : ctx->slot) {
     A((void**)&s.d, (size_t)max_frames * sizeof(FrameParam));
     if (rc == ACEZ_OK && (hipHostMalloc((void**)&s.h, (size_t)max_frames * sizeof(FrameParam)) != hipSuccess ||
                           hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess)) {
@@ -672,13 +745,11 @@ extern "C" int acez_ransac_create(acez_ransac** out, int max_frames, int max_h, 
       rc = ACEZ_ERR_HIP;
     }
   }
-  A((void**)&ctx->d_best, (size_t)max_frames * sizeof(int));
-  A((void**)&ctx->d_refined, (size_t)max_frames * 6 * sizeof(double));
   A((void**)&ctx->d_sc, (size_t)3 * max_h * max_w * sizeof(float));
   A((void**)&ctx->d_pose, 16 * sizeof(float));
   A((void**)&ctx->d_inl, sizeof(int));
   A((void**)&ctx->d_mask, (size_t)max_h * max_w);
-  if (rc == ACEZ_OK) rc = ensure_hyps(ctx, 64);
+  if (rc == ACEZ_OK) rc = acez_rs::ensure_hyps(ctx->rgb, 64, false);
   if (rc != ACEZ_OK) {
     acez_ransac_destroy(ctx);
     return rc;
@@ -699,52 +770,23 @@ extern "C" int acez_register_rgb_device(acez_ransac* ctx, const float* d_scene_c
   ACEZ_REQUIRE(params->subsampling > 0 && params->inlier_threshold > 0.f, "subsampling and inlier_threshold must be positive");
   ACEZ_HIP_CHECK(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
-  int rc = ensure_hyps(ctx, params->hypotheses);
+  acez_rs::Workspace& ws = ctx->rgb;
+  acez_rs::Geometry g;
+  acez_rs::ParamSlot* slot = nullptr;
+  int rc = acez_rs::ensure_hyps(ws, params->hypotheses, false);
+  if (rc == ACEZ_OK) rc = acez_rs::plan_launch(ws, h, w, params->hypotheses, 3, lds_bytes, &g);
+  if (rc == ACEZ_OK) rc = acez_rs::stage_params(ctx, s, n_frames, h_intrinsics, h_frame_ids, &slot);
   if (rc != ACEZ_OK) return rc;
-  const int N = h * w;
-  const int Npad = (N + 3) & ~3;
-  const size_t lds_full = lds_bytes(N, params->hypotheses, false);
-  const bool gc = lds_full > 160 * 1024;
-  const size_t lds = gc ? lds_bytes(N, params->hypotheses, true) : lds_full;
-  ACEZ_REQUIRE(lds <= 160 * 1024, "too many hypotheses for the 160 KB LDS of a CU");
-  if (gc && ctx->big_floats < (size_t)ctx->max_frames * 3 * Npad) {
-    ACEZ_HIP_CHECK(hipDeviceSynchronize());
-    if (ctx->d_big) (void)hipFree(ctx->d_big);
-    ctx->d_big = nullptr;
-    ctx->big_floats = 0;
-    ACEZ_HIP_CHECK(hipMalloc((void**)&ctx->d_big, (size_t)ctx->max_frames * 3 * Npad * sizeof(float)));
-    ctx->big_floats = (size_t)ctx->max_frames * 3 * Npad;
-  }
-  ParamSlot& slot = ctx->slot[ctx->next_slot];
-  ctx->next_slot = (ctx->next_slot + 1) % PARAM_SLOTS;
-  if (slot.in_flight) ACEZ_HIP_CHECK(hipEventSynchronize(slot.done));
-  for (int i = 0; i < n_frames; ++i) {
-    slot.h[i].focal = h_intrinsics[i].focal;
-    slot.h[i].ppx = h_intrinsics[i].ppx;
-    slot.h[i].ppy = h_intrinsics[i].ppy;
-    slot.h[i].pad = 0.f;
-    slot.h[i].frame_id = h_frame_ids ? h_frame_ids[i] : (uint64_t)i;
-  }
-  ACEZ_HIP_CHECK(hipMemcpyAsync(slot.d, slot.h, (size_t)n_frames * sizeof(FrameParam), hipMemcpyHostToDevice, s));
   RansacArgs a;
-  a.sc = d_scene_coords; a.fp = slot.d; a.big = ctx->d_big; a.H = h; a.W = w; a.N = N; a.hyps = params->hypotheses;
-  a.h_magic = h > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)h - 1) / (uint64_t)h) : 0u;
+  a.sc = d_scene_coords; a.fp = slot->d; a.big = ws.d_list; a.H = h; a.W = w; a.N = g.N; a.hyps = params->hypotheses;
+  a.h_magic = g.h_magic;
   a.max_tries = params->max_tries; a.sub = params->subsampling; a.max_ref_steps = params->max_ref_steps;
   a.thr = params->inlier_threshold; a.alpha = params->inlier_alpha; a.max_reproj = params->max_reproj; a.seed = seed;
-  a.hyp_poses = ctx->d_hyp_poses; a.scores = ctx->d_scores; a.best = ctx->d_best; a.refined = ctx->d_refined;
+  a.hyp_poses = ws.d_hyp_poses; a.scores = ws.d_scores; a.best = ws.d_best; a.refined = ws.d_refined;
   a.out_poses = d_out_poses; a.out_inliers = d_out_inliers; a.out_masks = d_out_masks;
-  if (gc) {
-    ACEZ_HIP_CHECK(hipFuncSetAttribute((const void*)ransac_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(ransac_kernel<true>, dim3(n_frames), dim3(256), lds, s, a);
-  } else {
-    ACEZ_HIP_CHECK(hipFuncSetAttribute((const void*)ransac_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(ransac_kernel<false>, dim3(n_frames), dim3(256), lds, s, a);
-  }
-  ACEZ_HIP_CHECK(hipGetLastError());
-  ACEZ_HIP_CHECK(hipEventRecord(slot.done, s));
-  slot.in_flight = true;
-  ctx->last_hyps = params->hypotheses;
-  return ACEZ_OK;
+  rc = acez_rs::launch(ransac_kernel<true>, ransac_kernel<false>, g, n_frames, 256, s, a, *slot);
+  if (rc == ACEZ_OK) ws.last_hyps = params->hypotheses;
+  return rc;
 }
 
 extern "C" int acez_register_rgb_host(acez_ransac* ctx, const float* h_scene_coords, int64_t stride_c, int64_t stride_h,
@@ -754,30 +796,15 @@ extern "C" int acez_register_rgb_host(acez_ransac* ctx, const float* h_scene_coo
   ACEZ_REQUIRE(ctx && h_scene_coords && params && intr && h_out_pose16 && out_inliers, "null pointer");
   ACEZ_REQUIRE(h > 0 && w > 0 && h <= ctx->max_h && w <= ctx->max_w, "frame larger than the context was created for");
   ACEZ_HIP_CHECK(hipSetDevice(ctx->device));
-  // honour the accessor strides of the caller's tensor (dsacstar.cpp:83-84) while packing to [3][h][w]
-  std::vector<float> packed((size_t)3 * h * w);
-  for (int c = 0; c < 3; ++c)
-    for (int y = 0; y < h; ++y)
-      for (int x = 0; x < w; ++x) packed[((size_t)c * h + y) * w + x] = h_scene_coords[c * stride_c + y * stride_h + x * stride_w];
-  ACEZ_HIP_CHECK(hipMemcpy(ctx->d_sc, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-  int rc = acez_register_rgb_device(ctx, ctx->d_sc, 1, h, w, params, intr, seed, &frame_id, ctx->d_pose, ctx->d_inl,
-                                    h_out_mask ? ctx->d_mask : nullptr, nullptr);
-  if (rc != ACEZ_OK) return rc;
-  ACEZ_HIP_CHECK(hipMemcpy(h_out_pose16, ctx->d_pose, 16 * sizeof(float), hipMemcpyDeviceToHost));
-  ACEZ_HIP_CHECK(hipMemcpy(out_inliers, ctx->d_inl, sizeof(int), hipMemcpyDeviceToHost));
-  if (h_out_mask) ACEZ_HIP_CHECK(hipMemcpy(h_out_mask, ctx->d_mask, (size_t)h * w, hipMemcpyDeviceToHost));
-  return ACEZ_OK;
+  int rc = acez_rs::upload_strided(ctx->d_sc, h_scene_coords, stride_c, stride_h, stride_w, h, w);
+  if (rc == ACEZ_OK)
+    rc = acez_register_rgb_device(ctx, ctx->d_sc, 1, h, w, params, intr, seed, &frame_id, ctx->d_pose, ctx->d_inl,
+                                  h_out_mask ? ctx->d_mask : nullptr, nullptr);
+  return rc == ACEZ_OK ? acez_rs::download_result(ctx, h, w, h_out_pose16, out_inliers, h_out_mask) : rc;
 }
 
 extern "C" int acez_ransac_debug_fetch(acez_ransac* ctx, int n_frames, int hypotheses, double* h_hyp_poses, double* h_scores,
                                        int32_t* h_best, double* h_refined) {
   ACEZ_REQUIRE(ctx, "null context");
-  ACEZ_REQUIRE(n_frames > 0 && n_frames <= ctx->max_frames && hypotheses == ctx->last_hyps, "shape does not match the last call");
-  ACEZ_HIP_CHECK(hipSetDevice(ctx->device));
-  ACEZ_HIP_CHECK(hipDeviceSynchronize());
-  if (h_hyp_poses) ACEZ_HIP_CHECK(hipMemcpy(h_hyp_poses, ctx->d_hyp_poses, (size_t)n_frames * hypotheses * 6 * sizeof(double), hipMemcpyDeviceToHost));
-  if (h_scores) ACEZ_HIP_CHECK(hipMemcpy(h_scores, ctx->d_scores, (size_t)n_frames * hypotheses * sizeof(double), hipMemcpyDeviceToHost));
-  if (h_best) ACEZ_HIP_CHECK(hipMemcpy(h_best, ctx->d_best, (size_t)n_frames * sizeof(int), hipMemcpyDeviceToHost));
-  if (h_refined) ACEZ_HIP_CHECK(hipMemcpy(h_refined, ctx->d_refined, (size_t)n_frames * 6 * sizeof(double), hipMemcpyDeviceToHost));
-  return ACEZ_OK;
+  return acez_rs::debug_fetch(ctx, ctx->rgb, n_frames, hypotheses, nullptr, h_hyp_poses, h_scores, h_best, h_refined);
 }

@@ -1,9 +1,11 @@
 // ransac_ctx.h -- the registration context (acez_ransac) shared by the RGB (ransac_api.hip) and RGB-D (ransac_rgbd.hip)
-// DSAC* kernels: one ring of per-call frame-parameter slots, the RGB workspaces, and the RGB-D workspaces hung off it.
+// DSAC* kernels, and the host helpers both units' entry points use. The helpers are defined in ransac_api.hip; each unit keeps its
+// kernel, its LDS layout (lds_bytes) and its extern "C" entry points.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "acez_common.h"
 
 namespace acez_rs {
 
@@ -22,27 +24,76 @@ struct ParamSlot {
   bool in_flight = false;
 };
 
-struct RgbdState;                 // ransac_rgbd.hip: created on the first RGB-D call
-void rgbd_release(RgbdState* s);  // frees its buffers (the caller has synchronised the device)
+// The device workspaces of one estimator. Each kind keeps its own, so a debug fetch sees the last call of its kind.
+struct Workspace {
+  double* d_hyp_poses = nullptr;  // [frames][hyps][6] (rvec, tvec)
+  double* d_scores = nullptr;     // [frames][hyps]
+  int* d_samples = nullptr;       // [frames][hyps][3] map indices of the kept triple (RGB-D only)
+  int* d_best = nullptr;          // [frames]
+  double* d_refined = nullptr;    // [frames][6]
+  float* d_list = nullptr;        // lists of frames that do not fit the LDS, allocated on first use
+  size_t list_floats = 0;
+  int frames = 0, hyps = 0;       // capacity
+  int last_hyps = 0;              // hypotheses of the last launch
+};
+
+// Allocate best / refined on first use and regrow the per-hypothesis buffers (samples too if asked) / the list buffer; both
+// synchronise the device before freeing buffers that earlier launches may still write. release: the caller has synchronised.
+int ensure_hyps(Workspace& ws, int hyps, bool samples);
+int ensure_list_floats(Workspace& ws, size_t floats);
+void release(Workspace& ws);
+
+struct Geometry {
+  int N, Npad;
+  uint32_t h_magic;  // ceil(2^32 / H): p / H == __umulhi(p, h_magic) for p < 2^16 (H >= 2)
+  size_t lds;        // dynamic LDS bytes
+  bool hbm;          // the lists go to ws.d_list (kernel<true>)
+};
+// The geometry of an h x w frame for a unit's LDS layout lds_bytes(Npad, hyps, lists_in_hbm): the lists go to HBM when the frame
+// does not fit the 160 KB LDS of a CU, and then ws's list buffer grows to list_floats_per_cell floats per cell and frame.
+int plan_launch(Workspace& ws, int h, int w, int hyps, int list_floats_per_cell, size_t (*lds_bytes)(int, int, bool), Geometry* g);
+
+// Fills the next slot of the ring for n frames (intrinsics null: zeros; frame ids null: 0, 1, ..) after waiting for the call that
+// used it last, and copies it to the device on s. launch() records the slot's event.
+int stage_params(acez_ransac* ctx, hipStream_t s, int n, const acez_intrinsics* h_intrinsics, const uint64_t* h_frame_ids,
+                 ParamSlot** out);
+
+// Sets the dynamic-LDS attribute, launches kernel<true> (lists in HBM) or kernel<false> (lists in LDS), one workgroup per frame,
+// and records the slot's event behind the launch.
+template <class Args>
+int launch(void (*hbm_kernel)(Args), void (*lds_kernel)(Args), const Geometry& g, int n_frames, int threads, hipStream_t s,
+           const Args& a, ParamSlot& slot) {
+  void (*kernel)(Args) = g.hbm ? hbm_kernel : lds_kernel;
+  ACEZ_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
+  hipLaunchKernelGGL(kernel, dim3(n_frames), dim3(threads), g.lds, s, a);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  ACEZ_HIP_CHECK(hipEventRecord(slot.done, s));
+  slot.in_flight = true;
+  return ACEZ_OK;
+}
+
+// The host-buffer entry points: pack a [3][h][w] host tensor with the caller's accessor strides (dsacstar.cpp:83-84) into the
+// staging buffer d_dst; after the device call, copy the pose, the inlier count and, if asked for, the mask back.
+int upload_strided(float* d_dst, const float* h_src, int64_t stride_c, int64_t stride_h, int64_t stride_w, int h, int w);
+int download_result(const acez_ransac* ctx, int h, int w, float* h_out_pose16, int32_t* out_inliers, uint8_t* h_out_mask);
+
+// The per-hypothesis results of ws's last launch; every output may be null.
+int debug_fetch(const acez_ransac* ctx, const Workspace& ws, int n_frames, int hypotheses, int32_t* h_samples, double* h_hyp_poses,
+                double* h_scores, int32_t* h_best, double* h_refined);
 
 }  // namespace acez_rs
 
 struct acez_ransac {
   int device = 0;
-  int max_frames = 0, max_h = 0, max_w = 0, max_hyps = 0;
+  int max_frames = 0, max_h = 0, max_w = 0;
   acez_rs::ParamSlot slot[acez_rs::PARAM_SLOTS];
   int next_slot = 0;
-  double* d_hyp_poses = nullptr;
-  double* d_scores = nullptr;
-  int* d_best = nullptr;
-  double* d_refined = nullptr;
-  float* d_big = nullptr;      // scan-order copies of frames that do not fit the LDS, allocated on first use
-  size_t big_floats = 0;
-  // staging for the host-buffer entry point
+  acez_rs::Workspace rgb;   // allocated at acez_ransac_create (64 hypotheses)
+  acez_rs::Workspace rgbd;  // allocated at the first RGB-D call
+  // staging for the host-buffer entry points
   float* d_sc = nullptr;
+  float* d_cc = nullptr;    // RGB-D camera coordinates, allocated at the first RGB-D host call
   float* d_pose = nullptr;
   int* d_inl = nullptr;
   uint8_t* d_mask = nullptr;
-  int last_hyps = 0;
-  acez_rs::RgbdState* rgbd = nullptr;
 };

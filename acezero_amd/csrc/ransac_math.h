@@ -693,4 +693,7 @@ ACEZ_HD inline void solve_normal6(const double A[36], const double b[6], double 
   if (!ok) solve_sym6(A, b, x);
 }
 
+// device only: x = p / H of a scan-order index p = x * H + y < 2^16, magic = ceil(2^32 / H) (the kernels' h_magic; unused for H == 1)
+__device__ __forceinline__ int div_h(int p, int H, uint32_t magic) { return H == 1 ? p : (int)__umulhi((uint32_t)p, magic); }
+
 }  // namespace rsm

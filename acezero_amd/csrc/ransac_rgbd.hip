@@ -19,17 +19,18 @@
 //   refine   refineHypRGBD: all threads classify the valid cells, count the inliers and stop unless the count exceeds the best
 //            so far (starting at 3); otherwise Kabsch on every inlier (two passes: means, then centred covariance), reduced in
 //            a fixed order, and the errors are recomputed. A rank-deficient inlier set stops the refinement.
+// The host side (workspaces, frame-parameter slots, launch geometry, staging, debug fetch) is ransac_api.hip's, declared in
+// ransac_ctx.h; this unit keeps the kernel, its LDS layout and its entry points.
 #include <hip/hip_runtime.h>
 #include "ransac_math.h"
 #include "acez_common.h"
 #include "ransac_ctx.h"
 #include "svd3.h"
-#include <new>
-#include <vector>
 
 namespace {
 
 using acez_rs::FrameParam;
+using rsm::div_h;
 
 constexpr int THREADS = 512;
 constexpr int WAVES = THREADS / 64;
@@ -54,8 +55,6 @@ struct RgbdArgs {
   int* out_inliers;     // [n]
   uint8_t* out_masks;   // [n][H][W] or null
 };
-
-__device__ __forceinline__ int div_h(int p, int H, uint32_t magic) { return H == 1 ? p : (int)__umulhi((uint32_t)p, magic); }
 
 // butterfly v_l + v_(l ^ off), off = 32, 16, .., 1: every lane ends with the same bits
 __device__ __forceinline__ double wave_sum(double v) {
@@ -396,61 +395,6 @@ __global__ __launch_bounds__(THREADS, 1) void rgbd_kernel(RgbdArgs a) {
 // ====================================================================================================
 // C ABI
 // ====================================================================================================
-namespace acez_rs {
-struct RgbdState {
-  int frames = 0, hyps = 0;
-  double* d_hyp = nullptr;
-  double* d_scores = nullptr;
-  int* d_samples = nullptr;
-  int* d_best = nullptr;
-  double* d_refined = nullptr;
-  float* d_big = nullptr;
-  size_t big_floats = 0;
-  float* d_cc = nullptr;   // staging of the host entry point's camera coordinates
-  int last_hyps = 0;
-};
-
-void rgbd_release(RgbdState* s) {
-  if (!s) return;
-  if (s->d_hyp) (void)hipFree(s->d_hyp);
-  if (s->d_scores) (void)hipFree(s->d_scores);
-  if (s->d_samples) (void)hipFree(s->d_samples);
-  if (s->d_best) (void)hipFree(s->d_best);
-  if (s->d_refined) (void)hipFree(s->d_refined);
-  if (s->d_big) (void)hipFree(s->d_big);
-  if (s->d_cc) (void)hipFree(s->d_cc);
-  delete s;
-}
-}  // namespace acez_rs
-
-// the RGB-D workspaces of a context: created on first use, the per-hypothesis buffers regrown for more hypotheses
-static int rgbd_state(acez_ransac* ctx, int hyps, acez_rs::RgbdState** out) {
-  acez_rs::RgbdState* s = ctx->rgbd;
-  if (!s) {
-    s = new (std::nothrow) acez_rs::RgbdState();
-    ACEZ_REQUIRE(s, "out of host memory");
-    ctx->rgbd = s;
-    s->frames = ctx->max_frames;
-    ACEZ_HIP_CHECK(hipMalloc((void**)&s->d_best, (size_t)s->frames * sizeof(int)));
-    ACEZ_HIP_CHECK(hipMalloc((void**)&s->d_refined, (size_t)s->frames * 6 * sizeof(double)));
-    ACEZ_HIP_CHECK(hipMalloc((void**)&s->d_cc, (size_t)3 * ctx->max_h * ctx->max_w * sizeof(float)));
-  }
-  if (hyps > s->hyps) {
-    ACEZ_HIP_CHECK(hipDeviceSynchronize());   // earlier launches may still write the old buffers
-    if (s->d_hyp) (void)hipFree(s->d_hyp);
-    if (s->d_scores) (void)hipFree(s->d_scores);
-    if (s->d_samples) (void)hipFree(s->d_samples);
-    s->d_hyp = nullptr; s->d_scores = nullptr; s->d_samples = nullptr;
-    s->hyps = 0;
-    ACEZ_HIP_CHECK(hipMalloc((void**)&s->d_hyp, (size_t)s->frames * hyps * 6 * sizeof(double)));
-    ACEZ_HIP_CHECK(hipMalloc((void**)&s->d_scores, (size_t)s->frames * hyps * sizeof(double)));
-    ACEZ_HIP_CHECK(hipMalloc((void**)&s->d_samples, (size_t)s->frames * hyps * 3 * sizeof(int)));
-    s->hyps = hyps;
-  }
-  *out = s;
-  return ACEZ_OK;
-}
-
 extern "C" int acez_register_rgbd_device(acez_ransac* ctx, const float* d_scene_coords, const float* d_camera_coords, int n_frames, int h,
                                          int w, const acez_ransac_params* params, uint64_t seed, const uint64_t* h_frame_ids,
                                          float* d_out_poses, int32_t* d_out_inliers, uint8_t* d_out_masks, void* stream) {
@@ -462,51 +406,24 @@ extern "C" int acez_register_rgbd_device(acez_ransac* ctx, const float* d_scene_
   ACEZ_REQUIRE(params->inlier_threshold > 0.f, "inlier_threshold must be positive");
   ACEZ_HIP_CHECK(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
-  acez_rs::RgbdState* st = nullptr;
-  int rc = rgbd_state(ctx, params->hypotheses, &st);
+  acez_rs::Workspace& ws = ctx->rgbd;
+  acez_rs::Geometry g;
+  acez_rs::ParamSlot* slot = nullptr;
+  int rc = acez_rs::ensure_hyps(ws, params->hypotheses, true);
+  if (rc == ACEZ_OK) rc = acez_rs::plan_launch(ws, h, w, params->hypotheses, 7, lds_bytes, &g);
+  if (rc == ACEZ_OK) rc = acez_rs::stage_params(ctx, s, n_frames, nullptr, h_frame_ids, &slot);
   if (rc != ACEZ_OK) return rc;
-  const int N = h * w;
-  const int Npad = (N + 3) & ~3;
-  const size_t lds_full = lds_bytes(Npad, params->hypotheses, false);
-  const bool gc = lds_full > 160 * 1024;
-  const size_t lds = gc ? lds_bytes(Npad, params->hypotheses, true) : lds_full;
-  ACEZ_REQUIRE(lds <= 160 * 1024, "too many hypotheses for the 160 KB LDS of a CU");
-  if (gc && st->big_floats < (size_t)ctx->max_frames * 7 * Npad) {
-    ACEZ_HIP_CHECK(hipDeviceSynchronize());
-    if (st->d_big) (void)hipFree(st->d_big);
-    st->d_big = nullptr;
-    st->big_floats = 0;
-    ACEZ_HIP_CHECK(hipMalloc((void**)&st->d_big, (size_t)ctx->max_frames * 7 * Npad * sizeof(float)));
-    st->big_floats = (size_t)ctx->max_frames * 7 * Npad;
-  }
-  acez_rs::ParamSlot& slot = ctx->slot[ctx->next_slot];
-  ctx->next_slot = (ctx->next_slot + 1) % acez_rs::PARAM_SLOTS;
-  if (slot.in_flight) ACEZ_HIP_CHECK(hipEventSynchronize(slot.done));
-  for (int i = 0; i < n_frames; ++i) {
-    slot.h[i].focal = slot.h[i].ppx = slot.h[i].ppy = slot.h[i].pad = 0.f;
-    slot.h[i].frame_id = h_frame_ids ? h_frame_ids[i] : (uint64_t)i;
-  }
-  ACEZ_HIP_CHECK(hipMemcpyAsync(slot.d, slot.h, (size_t)n_frames * sizeof(acez_rs::FrameParam), hipMemcpyHostToDevice, s));
   RgbdArgs a;
-  a.sc = d_scene_coords; a.cc = d_camera_coords; a.fp = slot.d; a.big = st->d_big;
-  a.H = h; a.W = w; a.N = N; a.Npad = Npad; a.hyps = params->hypotheses; a.max_tries = params->max_tries;
+  a.sc = d_scene_coords; a.cc = d_camera_coords; a.fp = slot->d; a.big = ws.d_list;
+  a.H = h; a.W = w; a.N = g.N; a.Npad = g.Npad; a.hyps = params->hypotheses; a.max_tries = params->max_tries;
   a.max_ref_steps = params->max_ref_steps;
-  a.h_magic = h > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)h - 1) / (uint64_t)h) : 0u;
+  a.h_magic = g.h_magic;
   a.thr = params->inlier_threshold; a.alpha = params->inlier_alpha; a.max_dist = params->max_reproj; a.seed = seed;
-  a.hyp_poses = st->d_hyp; a.scores = st->d_scores; a.samples = st->d_samples; a.best = st->d_best; a.refined = st->d_refined;
+  a.hyp_poses = ws.d_hyp_poses; a.scores = ws.d_scores; a.samples = ws.d_samples; a.best = ws.d_best; a.refined = ws.d_refined;
   a.out_poses = d_out_poses; a.out_inliers = d_out_inliers; a.out_masks = d_out_masks;
-  if (gc) {
-    ACEZ_HIP_CHECK(hipFuncSetAttribute((const void*)rgbd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(rgbd_kernel<true>, dim3(n_frames), dim3(THREADS), lds, s, a);
-  } else {
-    ACEZ_HIP_CHECK(hipFuncSetAttribute((const void*)rgbd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(rgbd_kernel<false>, dim3(n_frames), dim3(THREADS), lds, s, a);
-  }
-  ACEZ_HIP_CHECK(hipGetLastError());
-  ACEZ_HIP_CHECK(hipEventRecord(slot.done, s));
-  slot.in_flight = true;
-  st->last_hyps = params->hypotheses;
-  return ACEZ_OK;
+  rc = acez_rs::launch(rgbd_kernel<true>, rgbd_kernel<false>, g, n_frames, THREADS, s, a, *slot);
+  if (rc == ACEZ_OK) ws.last_hyps = params->hypotheses;
+  return rc;
 }
 
 extern "C" int acez_register_rgbd_host(acez_ransac* ctx, const float* h_scene_coords, int64_t sc_stride_c, int64_t sc_stride_h,
@@ -516,40 +433,17 @@ extern "C" int acez_register_rgbd_host(acez_ransac* ctx, const float* h_scene_co
   ACEZ_REQUIRE(ctx && h_scene_coords && h_camera_coords && params && h_out_pose16 && out_inliers, "null pointer");
   ACEZ_REQUIRE(h > 0 && w > 0 && h <= ctx->max_h && w <= ctx->max_w, "frame larger than the context was created for");
   ACEZ_HIP_CHECK(hipSetDevice(ctx->device));
-  acez_rs::RgbdState* st = nullptr;
-  int rc = rgbd_state(ctx, params->hypotheses > 0 ? params->hypotheses : 1, &st);
-  if (rc != ACEZ_OK) return rc;
-  // honour the accessor strides of the caller's tensors (dsacstar.cpp:517-521) while packing to [3][h][w]
-  std::vector<float> ps((size_t)3 * h * w), pc((size_t)3 * h * w);
-  for (int c = 0; c < 3; ++c)
-    for (int y = 0; y < h; ++y)
-      for (int x = 0; x < w; ++x) {
-        ps[((size_t)c * h + y) * w + x] = h_scene_coords[c * sc_stride_c + y * sc_stride_h + x * sc_stride_w];
-        pc[((size_t)c * h + y) * w + x] = h_camera_coords[c * cc_stride_c + y * cc_stride_h + x * cc_stride_w];
-      }
-  ACEZ_HIP_CHECK(hipMemcpy(ctx->d_sc, ps.data(), ps.size() * sizeof(float), hipMemcpyHostToDevice));
-  ACEZ_HIP_CHECK(hipMemcpy(st->d_cc, pc.data(), pc.size() * sizeof(float), hipMemcpyHostToDevice));
-  rc = acez_register_rgbd_device(ctx, ctx->d_sc, st->d_cc, 1, h, w, params, seed, &frame_id, ctx->d_pose, ctx->d_inl,
-                                 h_out_mask ? ctx->d_mask : nullptr, nullptr);
-  if (rc != ACEZ_OK) return rc;
-  ACEZ_HIP_CHECK(hipMemcpy(h_out_pose16, ctx->d_pose, 16 * sizeof(float), hipMemcpyDeviceToHost));
-  ACEZ_HIP_CHECK(hipMemcpy(out_inliers, ctx->d_inl, sizeof(int), hipMemcpyDeviceToHost));
-  if (h_out_mask) ACEZ_HIP_CHECK(hipMemcpy(h_out_mask, ctx->d_mask, (size_t)h * w, hipMemcpyDeviceToHost));
-  return ACEZ_OK;
+  if (!ctx->d_cc) ACEZ_HIP_CHECK(hipMalloc((void**)&ctx->d_cc, (size_t)3 * ctx->max_h * ctx->max_w * sizeof(float)));
+  int rc = acez_rs::upload_strided(ctx->d_sc, h_scene_coords, sc_stride_c, sc_stride_h, sc_stride_w, h, w);
+  if (rc == ACEZ_OK) rc = acez_rs::upload_strided(ctx->d_cc, h_camera_coords, cc_stride_c, cc_stride_h, cc_stride_w, h, w);
+  if (rc == ACEZ_OK)
+    rc = acez_register_rgbd_device(ctx, ctx->d_sc, ctx->d_cc, 1, h, w, params, seed, &frame_id, ctx->d_pose, ctx->d_inl,
+                                   h_out_mask ? ctx->d_mask : nullptr, nullptr);
+  return rc == ACEZ_OK ? acez_rs::download_result(ctx, h, w, h_out_pose16, out_inliers, h_out_mask) : rc;
 }
 
 extern "C" int acez_ransac_rgbd_debug_fetch(acez_ransac* ctx, int n_frames, int hypotheses, int32_t* h_samples, double* h_hyp_poses,
                                             double* h_scores, int32_t* h_best, double* h_refined) {
-  ACEZ_REQUIRE(ctx && ctx->rgbd, "no RGB-D call on this context");
-  const acez_rs::RgbdState* s = ctx->rgbd;
-  ACEZ_REQUIRE(n_frames > 0 && n_frames <= s->frames && hypotheses == s->last_hyps, "shape does not match the last call");
-  ACEZ_HIP_CHECK(hipSetDevice(ctx->device));
-  ACEZ_HIP_CHECK(hipDeviceSynchronize());
-  const size_t nh = (size_t)n_frames * hypotheses;
-  if (h_samples) ACEZ_HIP_CHECK(hipMemcpy(h_samples, s->d_samples, nh * 3 * sizeof(int), hipMemcpyDeviceToHost));
-  if (h_hyp_poses) ACEZ_HIP_CHECK(hipMemcpy(h_hyp_poses, s->d_hyp, nh * 6 * sizeof(double), hipMemcpyDeviceToHost));
-  if (h_scores) ACEZ_HIP_CHECK(hipMemcpy(h_scores, s->d_scores, nh * sizeof(double), hipMemcpyDeviceToHost));
-  if (h_best) ACEZ_HIP_CHECK(hipMemcpy(h_best, s->d_best, (size_t)n_frames * sizeof(int), hipMemcpyDeviceToHost));
-  if (h_refined) ACEZ_HIP_CHECK(hipMemcpy(h_refined, s->d_refined, (size_t)n_frames * 6 * sizeof(double), hipMemcpyDeviceToHost));
-  return ACEZ_OK;
+  ACEZ_REQUIRE(ctx && ctx->rgbd.d_best, "no RGB-D call on this context");
+  return acez_rs::debug_fetch(ctx, ctx->rgbd, n_frames, hypotheses, h_samples, h_hyp_poses, h_scores, h_best, h_refined);
 }
