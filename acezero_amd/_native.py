@@ -105,6 +105,23 @@ SYMBOLS = {
                                           C.POINTER(C.c_int32), C.c_void_p]),
     "acez_ransac_rgbd_debug_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p]),
+    "acez_register_rgb_backward_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RansacParams),
+                                                    C.POINTER(Intrinsics), C.c_float, C.c_float, C.c_float, C.c_uint64,
+                                                    C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "acez_register_rgb_backward_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int,
+                                                  C.POINTER(RansacParams), C.POINTER(Intrinsics), C.c_float, C.c_float, C.c_float,
+                                                  C.c_uint64, C.c_uint64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "acez_ransac_rgb_backward_debug_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "acez_register_rgbd_backward_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                     C.POINTER(RansacParams), C.c_float, C.c_float, C.c_float, C.c_uint64,
+                                                     C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "acez_register_rgbd_backward_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                                   C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.POINTER(RansacParams),
+                                                   C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int64,
+                                                   C.c_int64, C.c_int64, C.c_void_p]),
+    "acez_ransac_rgbd_backward_debug_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acez_head_num_params": (C.c_int64, [C.POINTER(HeadDesc)]),
     "acez_trainer_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(TrainConfig), C.POINTER(ParamBuffers), C.c_int]),
     "acez_trainer_destroy": (None, [C.c_void_p]),

@@ -26,6 +26,7 @@ UNITS = {
     "encoder_api.hip": [],
     "ransac_api.hip": ["-ffp-contract=off"],
     "ransac_rgbd.hip": ["-ffp-contract=off"],
+    "ransac_grad.hip": ["-ffp-contract=off"],
     "cloud_api.hip": ["-ffp-contract=off"],
     "align_api.hip": ["-ffp-contract=off"],
     "render_api.hip": ["-ffp-contract=off"],

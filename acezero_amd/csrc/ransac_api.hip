@@ -25,6 +25,7 @@
 #include "ransac_math.h"
 #include "acez_common.h"
 #include "ransac_ctx.h"
+#include "ransac_loss.h"
 #include <new>
 #include <vector>
 
@@ -51,6 +52,19 @@ struct RansacArgs {
   float* out_poses;   // [n][16]
   int* out_inliers;   // [n]
   uint8_t* out_masks; // [n][H][W] or null
+  // the backward pass only (GRAD instantiation)
+  int* samples;                // [n][hyps][4] scan indices x * H + y of the kept minimal set
+  const float* gt;             // [n][16] row-major cam->world ground truth
+  float w_rot, w_trans, cut;
+  double* probs;               // [n][hyps]
+  double* losses;              // [n][hyps]
+  double* ref_poses;           // [n][hyps][6]
+  unsigned long long* masks;   // [n][hyps][mwords]: bit p % 64 of word p / 64 = pixel p (scan order) is a final inlier
+  int mwords;
+  double* gacc;                // [n][3][N] fp64 accumulator
+  double* entropy;             // [n]
+  float* out_grad;             // [n][3][H][W], added to
+  double* out_loss;            // [n]
 };
 
 // ---- cross-lane sums of doubles without the LDS crossbar --------------------------------------------------------------------
@@ -194,10 +208,17 @@ __host__ __device__ inline int region_doubles(int hyps) { return 7 * hyps > REGI
 __host__ __device__ inline size_t lds_bytes(int Npad, int hyps, bool coords_in_hbm) {
   return (coords_in_hbm ? 0 : 12 * (size_t)Npad) + 2 * (size_t)Npad + 8 * (size_t)region_doubles(hyps) + 8 * sizeof(int);
 }
+// the backward pass adds probabilities [hyps], losses [hyps] and 64 doubles of hand-over (the 6x6 pseudo-inverse, v, E, a max)
+__host__ __device__ inline size_t grad_lds_bytes(int Npad, int hyps, bool coords_in_hbm) {
+  return lds_bytes(Npad, hyps, coords_in_hbm) + 8 * (size_t)(2 * hyps + 64);
+}
+__host__ __device__ inline int rgb_mask_words(int N) { return ((N + 255) >> 8) * 4; }
 
 // GC: the frame does not fit the LDS (more than ~11 400 scene coordinates): its scan-order copy lives in an HBM workspace (L2
 // resident, 12 N bytes) and every stage reads it from there; same arithmetic, same order, same bits.
-template <bool GC>
+// GRAD: the backward pass (dsacstar_rgb_backward) instead of the selection and the single refinement; the sampling, scoring and
+// refinement code is the same.
+template <bool GC, bool GRAD = false>
 __global__ __launch_bounds__(256, 2) void ransac_kernel(RansacArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int N = a.N, H = a.H, W = a.W;
@@ -250,6 +271,7 @@ __global__ __launch_bounds__(256, 2) void ransac_kernel(RansacArgs a) {
       Pose cur;
 #pragma unroll
       for (int i = 0; i < 3; ++i) cur.r[i] = cur.t[i] = 0;
+      int ps[4] = {0, 0, 0, 0};   // the draw's scan indices (kept by the backward pass)
       int status = 0;  // 0: PnP failed (zero pose), 1: solved but rejected by the 4-point check, 2: accepted
       if (!settled && t < a.max_tries) {
         const uint64_t key = rsm::try_key(a.seed, fp.frame_id, (uint32_t)h, (uint32_t)t);
@@ -261,6 +283,7 @@ __global__ __launch_bounds__(256, 2) void ransac_kernel(RansacArgs a) {
           img[j][0] = (float)(x * a.sub + half);
           img[j][1] = (float)(y * a.sub + half);
           const int p = x * H + y;
+          ps[j] = p;
           obj[j][0] = sX[p];
           obj[j][1] = sY[p];
           obj[j][2] = sZ[p];
@@ -296,6 +319,8 @@ __global__ __launch_bounds__(256, 2) void ransac_kernel(RansacArgs a) {
               sHyp[h * 6 + i] = cur.r[i];
               sHyp[h * 6 + 3 + i] = cur.t[i];
             }
+            if constexpr (GRAD)
+              for (int j = 0; j < 4; ++j) a.samples[((size_t)frame * a.hyps + h) * 4 + j] = ps[j];
           }
         }
       }
@@ -340,36 +365,6 @@ __global__ __launch_bounds__(256, 2) void ransac_kernel(RansacArgs a) {
   }
   __syncthreads();
 
-  // ---- select: softMax + draw(argmax)
-  if (tid == 0) {
-    double maxScore = 0;
-    for (int i = 0; i < a.hyps; i++)
-      if (i == 0 || sScores[i] > maxScore) maxScore = sScores[i];
-    double sum = 0.0;
-    for (int i = 0; i < a.hyps; i++) sum += detm::exp_(sScores[i] - maxScore);
-    double maxProb = -1;
-    int maxIdx = 0;
-    for (int idx = 0; idx < a.hyps; idx++) {
-      const double pr = detm::exp_(sScores[idx] - maxScore) / sum;
-      if (pr < 0.00000001) continue;
-      if (maxProb < 0 || pr > maxProb) {
-        maxProb = pr;
-        maxIdx = idx;
-      }
-    }
-    sInt[0] = maxIdx;
-    a.best[frame] = maxIdx;
-  }
-  __syncthreads();
-
-  // ---- refine
-  const int bestIdx = sInt[0];
-  double param[6];
-  {
-    const double* hp = a.hyp_poses + ((size_t)frame * a.hyps + bestIdx) * 6;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) param[i] = hp[i];
-  }
   const int rows = (N + 255) >> 8;  // thread tid looks at pixels p = tid + 256 i, i < rows (p < N)
 
   // bit i of the result: pixel tid + 256 i is an inlier of prm (getReproErrs + the threshold test of refineHyp, :536-560)
@@ -511,9 +506,12 @@ __global__ __launch_bounds__(256, 2) void ransac_kernel(RansacArgs a) {
     for (int i = 0; i < 6; ++i) prm[i] = prevParam[i] - sStep[i];
   };
 
-  uint64_t flags = classify(param), acc_flags = 0;
-  unsigned bestInliers = 4;
-  bool have_map = false;
+  // refineHyp of prm: the inlier flags of the last accepted step, whether one was accepted, and its inlier count
+  auto refine = [&](double* param, uint64_t& acc_flags, bool& have_map, unsigned& bestInliers) {
+  uint64_t flags = classify(param);
+  acc_flags = 0;
+  bestInliers = 4;
+  have_map = false;
   const int max_ref = a.max_ref_steps > 0 ? a.max_ref_steps : 100;
   for (int rStep = 0; rStep < max_ref; rStep++) {
     const int cnt = compact(flags);
@@ -564,6 +562,277 @@ __global__ __launch_bounds__(256, 2) void ransac_kernel(RansacArgs a) {
     have_map = true;
     flags = classify(param);
   }
+  };
+
+  if constexpr (GRAD) {
+    // ---- the backward pass (dsacstar_rgb_backward, dsacstar.cpp:208-490): probabilities, every hypothesis with p >= PROB_THRESH
+    // refined, losses, E, path I through the refinement's normal equations, path II through the scores and P3P
+    double* sProb = reinterpret_cast<double*>(sInt + 8);   // [hyps]
+    double* sLoss = sProb + a.hyps;                         // [hyps]
+    double* sM = sLoss + a.hyps;    // [0,36) (J^T J)^+, [36,42) v = (J^T J)^+ p dLoss, [42] E, [48,52) wavefront maxima
+    const float* G = a.gt + (size_t)frame * 16;
+    double* gacc = a.gacc + (size_t)frame * 3 * N;
+    unsigned long long* mw = a.masks + (size_t)frame * a.hyps * a.mwords;
+    for (int m = tid; m < 3 * N; m += 256) gacc[m] = 0.0;
+    for (int i = tid; i < a.hyps * a.mwords; i += 256) mw[i] = 0ull;
+    if (tid == 0) {   // dsacstar::softMax, dsacstar::entropy
+      double maxScore = 0;
+      for (int i = 0; i < a.hyps; i++)
+        if (i == 0 || sScores[i] > maxScore) maxScore = sScores[i];
+      double sum = 0.0;
+      for (int i = 0; i < a.hyps; i++) {
+        sProb[i] = detm::exp_(sScores[i] - maxScore);
+        sum += sProb[i];
+      }
+      double ent = 0.0;
+      for (int i = 0; i < a.hyps; i++) {
+        sProb[i] /= sum;
+        a.probs[(size_t)frame * a.hyps + i] = sProb[i];
+        if (sProb[i] > 0) ent -= sProb[i] * log2(sProb[i]);
+      }
+      a.entropy[frame] = ent;
+    }
+    __syncthreads();
+    const double NORM_EPS = 1e-8;   // the reference's max(|e|, EPS)
+    // d|e| / d(rvec, tvec) of pixel p at prm (one row of the refinement's Jacobian); false if its error exceeds max_reproj
+    auto norm_row = [&](int p, const double* R, const double* dRdr, const double* prm, double row[6]) -> bool {
+      const int x = div_h(p, H, magic), y = p - x * H;
+      double u, v, Ju[6], Jv[6];
+      rsm::project(R, prm + 3, k, sX[p], sY[p], sZ[p], &u, &v, dRdr, Ju, Jv);
+      const double du = u - (double)(float)(x * a.sub + half), dv = v - (double)(float)(y * a.sub + half);
+      double err = sqrt(du * du + dv * dv);
+      err = err > NORM_EPS ? err : NORM_EPS;
+      if (err > (double)a.max_reproj) return false;
+      for (int q = 0; q < 6; ++q) row[q] = (du * Ju[q] + dv * Jv[q]) / err;
+      return true;
+    };
+    // dProjectdObj: d|e| / dX of pixel p with the pose fixed; zero if the point is behind the camera or its error exceeds max_reproj
+    auto dproj_dobj = [&](int p, const double* R, const double* t, double g[3]) {
+      g[0] = g[1] = g[2] = 0.0;
+      const int x = div_h(p, H, magic), y = p - x * H;
+      const double X[3] = {sX[p], sY[p], sZ[p]};
+      double c[3];
+      for (int r = 0; r < 3; ++r) c[r] = ((R[r * 3 + 0] * X[0] + R[r * 3 + 1] * X[1]) + R[r * 3 + 2] * X[2]) + t[r];
+      if (fabs(c[2]) < NORM_EPS) return;
+      const double px = k.fx * c[0] / c[2] + k.cx, py = k.fy * c[1] / c[2] + k.cy;
+      const double ex = px - (double)(float)(x * a.sub + half), ey = py - (double)(float)(y * a.sub + half);
+      double err = sqrt(ex * ex + ey * ey);
+      if (err > (double)a.max_reproj) return;
+      err += NORM_EPS;
+      for (int q = 0; q < 3; ++q) {
+        const double pxd = k.fx * R[0 * 3 + q] / c[2] - k.fx * c[0] / (c[2] * c[2]) * R[2 * 3 + q];
+        const double pyd = k.fy * R[1 * 3 + q] / c[2] - k.fy * c[1] / (c[2] * c[2]) * R[2 * 3 + q];
+        g[q] = (ex * pxd + ey * pyd) / err;
+      }
+    };
+    // the largest value over the workgroup (wavefront butterflies, then the 4 wavefronts through LDS)
+    auto block_max = [&](double v) -> double {
+      for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+      if (lane == 0) sM[48 + wave] = v;
+      __syncthreads();
+      const double r = fmax(fmax(sM[48], sM[49]), fmax(sM[50], sM[51]));
+      __syncthreads();
+      return r;
+    };
+
+    // ---- refine, loss, path I
+    for (int h = 0; h < a.hyps; ++h) {
+      const double p = sProb[h];
+      const bool active = p >= acez_loss::PROB_THRESH;
+      double param[6];
+      for (int i = 0; i < 6; ++i) param[i] = a.hyp_poses[((size_t)frame * a.hyps + h) * 6 + i];
+      uint64_t accf = 0;
+      bool hm = false;
+      unsigned ninl = 0;
+      if (active) refine(param, accf, hm, ninl);
+      if (active && hm)
+        for (int i = 0; i < rows; ++i) {
+          const unsigned long long bits = __ballot((accf >> i) & 1ull);
+          if (lane == 0) mw[(size_t)h * a.mwords + i * 4 + wave] = bits;
+        }
+      double g6[6];
+      const double L = acez_loss::pose_loss(param, G, a.w_rot, a.w_trans, a.cut, active ? g6 : nullptr);
+      if (tid == 0) {
+        sLoss[h] = L;
+        const size_t o = (size_t)frame * a.hyps + h;
+        a.losses[o] = L;
+        for (int i = 0; i < 6; ++i) a.ref_poses[o * 6 + i] = param[i];
+      }
+      if (!(active && hm)) continue;
+      // dHyp/dObj = -(J^T J)^+ J^T dN/dObj over the final inliers, J the rows of d|e|/dHyp (dsacstar.cpp:362-420)
+      const int cnt = compact(accf);
+      double R[9], dRdr[27];
+      rsm::rodrigues(param, R, dRdr);
+      double acc[28];
+      for (int i = 0; i < 28; ++i) acc[i] = 0.0;
+      for (int j = tid; j < cnt; j += 256) {
+        double row[6];
+        if (!norm_row(sList[j], R, dRdr, param, row)) continue;
+        int q = 0;
+        for (int aa = 0; aa < 6; ++aa)
+          for (int bb = aa; bb < 6; ++bb) acc[q++] += row[aa] * row[bb];
+      }
+      LMAccum S;
+      reduce28(acc, &S);
+      if (tid == 0) {
+        for (int c = 0; c < 6; ++c) {
+          double e[6] = {0, 0, 0, 0, 0, 0}, col[6];
+          e[c] = 1.0;
+          rsm::solve_sym6(S.JtJ, e, col);   // inv(DECOMP_SVD)
+          for (int r = 0; r < 6; ++r) sM[r * 6 + c] = col[r];
+        }
+        for (int r = 0; r < 6; ++r) {
+          double v = 0;
+          for (int q = 0; q < 6; ++q) v += sM[r * 6 + q] * (p * g6[q]);
+          sM[36 + r] = v;
+        }
+      }
+      __syncthreads();
+      double mx = 0.0;   // maxJR: the largest entry of (J^T J)^+ J^T
+      for (int j = tid; j < cnt; j += 256) {
+        double row[6];
+        if (!norm_row(sList[j], R, dRdr, param, row)) continue;
+        for (int r = 0; r < 6; ++r) {
+          double w = 0;
+          for (int q = 0; q < 6; ++q) w += sM[r * 6 + q] * row[q];
+          mx = fmax(mx, fabs(w));
+        }
+      }
+      if (block_max(mx) > 10) continue;   // clamping for stability (dsacstar.cpp:403-404)
+      for (int j = tid; j < cnt; j += 256) {
+        const int pp = sList[j];
+        double row[6], g[3];
+        if (!norm_row(pp, R, dRdr, param, row)) continue;
+        double s = 0;
+        for (int q = 0; q < 6; ++q) s += sM[36 + q] * row[q];
+        dproj_dobj(pp, R, param + 3, g);
+        const int x = div_h(pp, H, magic), y = pp - x * H, m = y * W + x;
+        for (int c = 0; c < 3; ++c) gacc[c * N + m] += -s * g[c];
+      }
+      __syncthreads();
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double E = 0;
+      for (int h = 0; h < a.hyps; ++h) E += sProb[h] * sLoss[h];
+      sM[42] = E;
+      a.out_loss[frame] = E;
+    }
+    __syncthreads();
+    const double Eexp = sM[42];
+
+    // ---- path II (dSMScore / dScore): every pixel's own error with the hypothesis fixed, and the hypothesis through P3P (dPNP)
+    for (int h = 0; h < a.hyps; ++h) {
+      const double p = sProb[h];
+      if (!(p >= acez_loss::PROB_THRESH)) continue;
+      const double sg = p * (sLoss[h] - Eexp);
+      double prm[6], R[9], dRdr[27];
+      for (int i = 0; i < 6; ++i) prm[i] = a.hyp_poses[((size_t)frame * a.hyps + h) * 6 + i];
+      rsm::rodrigues(prm, R, dRdr);
+      double acc[28];
+      for (int i = 0; i < 28; ++i) acc[i] = 0.0;
+      for (int i = 0; i < rows; ++i) {
+        const int pp = tid + 256 * i;
+        if (pp >= N) break;
+        const int x = div_h(pp, H, magic), y = pp - x * H;
+        const float e = pixel_err(R, prm + 3, k, sX[pp], sY[pp], sZ[pp], x * a.sub + half, y * a.sub + half, a.max_reproj);
+        const float beta_e = inlierBeta * (e - a.thr);
+        if (beta_e > 40.f) continue;   // sigma' < 5e-18
+        const double st = 1 / (1 + exp_dev(-(double)beta_e));
+        const double dD = -st * (1 - st) * (double)inlierBeta * sg * (double)score_scale;
+        double row[6], g[3];
+        if (!norm_row(pp, R, dRdr, prm, row)) continue;
+        dproj_dobj(pp, R, prm + 3, g);
+        const int m = y * W + x;
+        for (int c = 0; c < 3; ++c) gacc[c * N + m] += dD * g[c];
+        for (int q = 0; q < 6; ++q) acc[21 + q] += dD * row[q];
+      }
+      LMAccum S;
+      reduce28(acc, &S);   // wavefront 0: S.JtErr = d score-path / d hypothesis
+      if (tid == 0) {
+        const int* smp = a.samples + ((size_t)frame * a.hyps + h) * 4;
+        float obj[4][3], img[4][2];
+        for (int j = 0; j < 4; ++j) {
+          const int x = div_h(smp[j], H, magic), y = smp[j] - x * H;
+          obj[j][0] = sX[smp[j]]; obj[j][1] = sY[smp[j]]; obj[j][2] = sZ[smp[j]];
+          img[j][0] = (float)(x * a.sub + half);
+          img[j][1] = (float)(y * a.sub + half);
+        }
+        // dPNP: central differences (eps 0.001, in float as the reference perturbs cv::Point3f) of P3P in the first three points
+        double cols[9][6];
+        bool ok = true;
+        double mxc = 0.0;
+        for (int i = 0; i < 3 && ok; ++i)
+          for (int c = 0; c < 3 && ok; ++c) {
+            float o[4][3];
+            for (int j = 0; j < 4; ++j)
+              for (int q = 0; q < 3; ++q) o[j][q] = obj[j][q];
+            Pose fw, bw;
+            o[i][c] = obj[i][c] + 0.001f;
+            ok = rsm::solve_pnp_p3p(o, img, k, &fw);
+            o[i][c] = o[i][c] - 2 * 0.001f;
+            ok = ok && rsm::solve_pnp_p3p(o, img, k, &bw);
+            for (int q = 0; q < 3 && ok; ++q) {
+              cols[i * 3 + c][q] = (fw.r[q] - bw.r[q]) / (double)(2 * 0.001f);
+              cols[i * 3 + c][3 + q] = (fw.t[q] - bw.t[q]) / (double)(2 * 0.001f);
+            }
+            for (int q = 0; q < 6 && ok; ++q) {
+              ok = isfinite(cols[i * 3 + c][q]);
+              mxc = fmax(mxc, fabs(cols[i * 3 + c][q]));
+            }
+          }
+        if (ok && !(mxc > 10)) {   // a failed solve or an entry above 10 zeroes the support term (dPNP, dScore)
+          for (int i = 0; i < 3; ++i) {
+            const int x = div_h(smp[i], H, magic), y = smp[i] - x * H, m = y * W + x;
+            for (int c = 0; c < 3; ++c) {
+              double v = 0;
+              for (int q = 0; q < 6; ++q) v += S.JtErr[q] * cols[i * 3 + c][q];
+              gacc[c * N + m] += v;
+            }
+          }
+        }
+      }
+      __syncthreads();
+    }
+    float* og = a.out_grad + (size_t)frame * 3 * N;
+    for (int i = tid; i < 3 * N; i += 256) og[i] += (float)gacc[i];
+    return;
+  }
+
+  // ---- select: softMax + draw(argmax)
+  if (tid == 0) {
+    double maxScore = 0;
+    for (int i = 0; i < a.hyps; i++)
+      if (i == 0 || sScores[i] > maxScore) maxScore = sScores[i];
+    double sum = 0.0;
+    for (int i = 0; i < a.hyps; i++) sum += detm::exp_(sScores[i] - maxScore);
+    double maxProb = -1;
+    int maxIdx = 0;
+    for (int idx = 0; idx < a.hyps; idx++) {
+      const double pr = detm::exp_(sScores[idx] - maxScore) / sum;
+      if (pr < 0.00000001) continue;
+      if (maxProb < 0 || pr > maxProb) {
+        maxProb = pr;
+        maxIdx = idx;
+      }
+    }
+    sInt[0] = maxIdx;
+    a.best[frame] = maxIdx;
+  }
+  __syncthreads();
+
+  // ---- refine
+  const int bestIdx = sInt[0];
+  double param[6];
+  {
+    const double* hp = a.hyp_poses + ((size_t)frame * a.hyps + bestIdx) * 6;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) param[i] = hp[i];
+  }
+  uint64_t acc_flags;
+  unsigned bestInliers;
+  bool have_map;
+  refine(param, acc_flags, have_map, bestInliers);
 
   // ---- outputs
   if (a.out_masks) {
@@ -610,7 +879,7 @@ int ensure_hyps(Workspace& ws, int hyps, bool samples) {
   ws.hyps = 0;
   ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_hyp_poses, (size_t)ws.frames * hyps * 6 * sizeof(double)));
   ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_scores, (size_t)ws.frames * hyps * sizeof(double)));
-  if (samples) ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_samples, (size_t)ws.frames * hyps * 3 * sizeof(int)));
+  if (samples) ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_samples, (size_t)ws.frames * hyps * 4 * sizeof(int)));
   ws.hyps = hyps;
   return ACEZ_OK;
 }
@@ -702,6 +971,8 @@ extern "C" void acez_ransac_destroy(acez_ransac* ctx) {
   }
   acez_rs::release(ctx->rgb);
   acez_rs::release(ctx->rgbd);
+  acez_rs::release_grad(ctx->rgbd_grad);
+  acez_rs::release_grad(ctx->rgb_grad);
   for (void* p : {(void*)ctx->d_sc, (void*)ctx->d_cc, (void*)ctx->d_pose, (void*)ctx->d_inl, (void*)ctx->d_mask})
     if (p) (void)hipFree(p);
   delete ctx;
@@ -729,7 +1000,7 @@ extern "C" int acez_ransac_create(acez_ransac** out, int max_frames, int max_h, 
   ctx->max_frames = max_frames;
   ctx->max_h = max_h;
   ctx->max_w = max_w;
-  ctx->rgb.frames = ctx->rgbd.frames = max_frames;
+  ctx->rgb.frames = ctx->rgbd.frames = ctx->rgbd_grad.ws.frames = ctx->rgb_grad.ws.frames = max_frames;
   int rc = ACEZ_OK;
   auto A = [&](void** p, size_t bytes) {
     if (rc == ACEZ_OK && hipMalloc(p, bytes) != hipSuccess) {
@@ -807,4 +1078,86 @@ extern "C" int acez_ransac_debug_fetch(acez_ransac* ctx, int n_frames, int hypot
                                        int32_t* h_best, double* h_refined) {
   ACEZ_REQUIRE(ctx, "null context");
   return acez_rs::debug_fetch(ctx, ctx->rgb, n_frames, hypotheses, nullptr, h_hyp_poses, h_scores, h_best, h_refined);
+}
+
+extern "C" int acez_register_rgb_backward_device(acez_ransac* ctx, const float* d_scene_coords, const float* d_gt_poses, int n_frames,
+                                                 int h, int w, const acez_ransac_params* params, const acez_intrinsics* h_intrinsics,
+                                                 float w_loss_rot, float w_loss_trans, float soft_clamp, uint64_t seed,
+                                                 const uint64_t* h_frame_ids, float* d_out_grad, double* d_out_loss, void* stream) {
+  ACEZ_REQUIRE(ctx && d_scene_coords && d_gt_poses && params && h_intrinsics && d_out_grad && d_out_loss, "null pointer");
+  ACEZ_REQUIRE(n_frames > 0 && n_frames <= ctx->max_frames, "n_frames exceeds the context's max_frames");
+  ACEZ_REQUIRE(h > 0 && w > 0 && h <= ctx->max_h && w <= ctx->max_w, "frame larger than the context was created for");
+  ACEZ_REQUIRE((int64_t)h * w <= 256 * MAX_ROWS, "at most 16384 scene coordinates per frame");
+  ACEZ_REQUIRE(params->hypotheses > 0 && params->max_tries > 0, "hypotheses and max_tries must be positive");
+  ACEZ_REQUIRE(params->subsampling > 0 && params->inlier_threshold > 0.f, "subsampling and inlier_threshold must be positive");
+  ACEZ_HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  acez_rs::GradWorkspace& gw = ctx->rgb_grad;
+  acez_rs::Geometry g;
+  acez_rs::ParamSlot* slot = nullptr;
+  int rc = acez_rs::ensure_grad(gw, params->hypotheses, h * w);
+  if (rc == ACEZ_OK) rc = acez_rs::plan_launch(gw.ws, h, w, params->hypotheses, 3, grad_lds_bytes, &g);
+  if (rc == ACEZ_OK) rc = acez_rs::stage_params(ctx, s, n_frames, h_intrinsics, h_frame_ids, &slot);
+  if (rc != ACEZ_OK) return rc;
+  RansacArgs a{};
+  a.sc = d_scene_coords; a.fp = slot->d; a.big = gw.ws.d_list; a.H = h; a.W = w; a.N = g.N; a.hyps = params->hypotheses;
+  a.h_magic = g.h_magic;
+  a.max_tries = params->max_tries; a.sub = params->subsampling; a.max_ref_steps = params->max_ref_steps;
+  a.thr = params->inlier_threshold; a.alpha = params->inlier_alpha; a.max_reproj = params->max_reproj; a.seed = seed;
+  a.hyp_poses = gw.ws.d_hyp_poses; a.scores = gw.ws.d_scores; a.best = gw.ws.d_best; a.refined = gw.ws.d_refined;
+  a.samples = gw.ws.d_samples; a.gt = d_gt_poses; a.w_rot = w_loss_rot; a.w_trans = w_loss_trans; a.cut = soft_clamp;
+  a.probs = gw.d_probs; a.losses = gw.d_losses; a.ref_poses = gw.d_ref_poses; a.masks = gw.d_masks; a.mwords = rgb_mask_words(h * w);
+  a.gacc = gw.d_gacc; a.entropy = gw.d_entropy; a.out_grad = d_out_grad; a.out_loss = d_out_loss;
+  rc = acez_rs::launch(ransac_kernel<true, true>, ransac_kernel<false, true>, g, n_frames, 256, s, a, *slot);
+  if (rc == ACEZ_OK) {
+    gw.last_hyps = gw.ws.last_hyps = params->hypotheses;
+    gw.last_cells = h * w;
+  }
+  return rc;
+}
+
+extern "C" int acez_register_rgb_backward_host(acez_ransac* ctx, const float* h_scene_coords, int64_t stride_c, int64_t stride_h,
+                                               int64_t stride_w, const float* h_gt_pose16, int h, int w, const acez_ransac_params* params,
+                                               const acez_intrinsics* intr, float w_loss_rot, float w_loss_trans, float soft_clamp,
+                                               uint64_t seed, uint64_t frame_id, float* h_grad, int64_t g_stride_c, int64_t g_stride_h,
+                                               int64_t g_stride_w, double* out_loss) {
+  ACEZ_REQUIRE(ctx && h_scene_coords && h_gt_pose16 && params && intr && h_grad && out_loss, "null pointer");
+  ACEZ_REQUIRE(h > 0 && w > 0 && h <= ctx->max_h && w <= ctx->max_w, "frame larger than the context was created for");
+  ACEZ_HIP_CHECK(hipSetDevice(ctx->device));
+  acez_rs::GradWorkspace& gw = ctx->rgb_grad;
+  int rc = acez_rs::ensure_grad(gw, params->hypotheses, h * w);
+  if (rc == ACEZ_OK) rc = acez_rs::upload_strided(ctx->d_sc, h_scene_coords, stride_c, stride_h, stride_w, h, w);
+  if (rc != ACEZ_OK) return rc;
+  const size_t cells = (size_t)h * w;
+  ACEZ_HIP_CHECK(hipMemcpy(gw.d_gt, h_gt_pose16, 16 * sizeof(float), hipMemcpyHostToDevice));
+  ACEZ_HIP_CHECK(hipMemset(gw.d_grad, 0, 3 * cells * sizeof(float)));
+  rc = acez_register_rgb_backward_device(ctx, ctx->d_sc, gw.d_gt, 1, h, w, params, intr, w_loss_rot, w_loss_trans, soft_clamp, seed,
+                                         &frame_id, gw.d_grad, gw.d_loss, nullptr);
+  if (rc != ACEZ_OK) return rc;
+  std::vector<float> grad(3 * cells);
+  ACEZ_HIP_CHECK(hipMemcpy(grad.data(), gw.d_grad, grad.size() * sizeof(float), hipMemcpyDeviceToHost));
+  ACEZ_HIP_CHECK(hipMemcpy(out_loss, gw.d_loss, sizeof(double), hipMemcpyDeviceToHost));
+  for (int c = 0; c < 3; ++c)
+    for (int y = 0; y < h; ++y)
+      for (int x = 0; x < w; ++x) h_grad[c * g_stride_c + y * g_stride_h + x * g_stride_w] += grad[((size_t)c * h + y) * w + x];
+  return ACEZ_OK;
+}
+
+extern "C" int acez_ransac_rgb_backward_debug_fetch(acez_ransac* ctx, int n_frames, int hypotheses, int h, int w, int32_t* h_samples,
+                                                    double* h_hyp_poses, double* h_scores, double* h_probs, double* h_losses,
+                                                    double* h_ref_poses, uint64_t* h_mask_words, double* h_entropy) {
+  ACEZ_REQUIRE(ctx && ctx->rgb_grad.ws.d_best, "no RGB backward call on this context");
+  acez_rs::GradWorkspace& gw = ctx->rgb_grad;
+  ACEZ_REQUIRE(h * w == gw.last_cells, "shape does not match the last call");
+  int rc = acez_rs::debug_fetch(ctx, gw.ws, n_frames, hypotheses, nullptr, h_hyp_poses, h_scores, nullptr, nullptr);
+  if (rc != ACEZ_OK) return rc;
+  const size_t nh = (size_t)n_frames * hypotheses;
+  if (h_samples) ACEZ_HIP_CHECK(hipMemcpy(h_samples, gw.ws.d_samples, nh * 4 * sizeof(int), hipMemcpyDeviceToHost));
+  if (h_probs) ACEZ_HIP_CHECK(hipMemcpy(h_probs, gw.d_probs, nh * sizeof(double), hipMemcpyDeviceToHost));
+  if (h_losses) ACEZ_HIP_CHECK(hipMemcpy(h_losses, gw.d_losses, nh * sizeof(double), hipMemcpyDeviceToHost));
+  if (h_ref_poses) ACEZ_HIP_CHECK(hipMemcpy(h_ref_poses, gw.d_ref_poses, nh * 6 * sizeof(double), hipMemcpyDeviceToHost));
+  if (h_mask_words)
+    ACEZ_HIP_CHECK(hipMemcpy(h_mask_words, gw.d_masks, nh * rgb_mask_words(h * w) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (h_entropy) ACEZ_HIP_CHECK(hipMemcpy(h_entropy, gw.d_entropy, (size_t)n_frames * sizeof(double), hipMemcpyDeviceToHost));
+  return ACEZ_OK;
 }

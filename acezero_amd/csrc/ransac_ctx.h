@@ -28,7 +28,7 @@ struct ParamSlot {
 struct Workspace {
   double* d_hyp_poses = nullptr;  // [frames][hyps][6] (rvec, tvec)
   double* d_scores = nullptr;     // [frames][hyps]
-  int* d_samples = nullptr;       // [frames][hyps][3] map indices of the kept triple (RGB-D only)
+  int* d_samples = nullptr;       // [frames][hyps][4] the kept sample (RGB-D: 3 map indices; RGB backward: 4 scan indices)
   int* d_best = nullptr;          // [frames]
   double* d_refined = nullptr;    // [frames][6]
   float* d_list = nullptr;        // lists of frames that do not fit the LDS, allocated on first use
@@ -81,6 +81,27 @@ int download_result(const acez_ransac* ctx, int h, int w, float* h_out_pose16, i
 int debug_fetch(const acez_ransac* ctx, const Workspace& ws, int n_frames, int hypotheses, int32_t* h_samples, double* h_hyp_poses,
                 double* h_scores, int32_t* h_best, double* h_refined);
 
+// The RGB-D backward pass's buffers beyond a Workspace (ransac_grad.hip): per-hypothesis probabilities, losses, refined poses and
+// inlier bitmasks, the per-frame fp64 gradient accumulator and entropy, and the host entry's staging.
+struct GradWorkspace {
+  Workspace ws;                           // sampled poses, scores, triples, HBM lists (best / refined unused)
+  double* d_probs = nullptr;              // [frames][hyps]
+  double* d_losses = nullptr;             // [frames][hyps]
+  double* d_ref_poses = nullptr;          // [frames][hyps][6]
+  unsigned long long* d_masks = nullptr;  // [frames][hyps][mwords]
+  double* d_gacc = nullptr;               // [frames][3][cells]
+  double* d_entropy = nullptr;            // [frames]
+  float* d_gt = nullptr;                  // [frames][16] host-entry staging
+  float* d_grad = nullptr;                // [3][cells] host-entry staging
+  double* d_loss = nullptr;               // [frames] host-entry staging
+  int hyps = 0, mwords = 0, cells = 0;    // capacity
+  int last_hyps = 0, last_cells = 0;      // shape of the last launch
+};
+// Both defined in ransac_grad.hip. ensure_grad: every buffer for hyps hypotheses and frames of up to `cells` cells (the mask words
+// are sized for the RGB-D layout, which is never smaller than the RGB one); release_grad: the caller has synchronised.
+int ensure_grad(GradWorkspace& g, int hyps, int cells);
+void release_grad(GradWorkspace& g);
+
 }  // namespace acez_rs
 
 struct acez_ransac {
@@ -90,6 +111,8 @@ struct acez_ransac {
   int next_slot = 0;
   acez_rs::Workspace rgb;   // allocated at acez_ransac_create (64 hypotheses)
   acez_rs::Workspace rgbd;  // allocated at the first RGB-D call
+  acez_rs::GradWorkspace rgbd_grad;  // allocated at the first RGB-D backward call
+  acez_rs::GradWorkspace rgb_grad;   // allocated at the first RGB backward call
   // staging for the host-buffer entry points
   float* d_sc = nullptr;
   float* d_cc = nullptr;    // RGB-D camera coordinates, allocated at the first RGB-D host call

@@ -58,15 +58,20 @@ def _check_1x3(name, t):
         raise RuntimeError(f"{name} must be a float32 tensor of shape 1x3xHxW")
 
 
-def _check_call(name, outPose):
-    """The checks both single-frame entries make after their input shapes; -> the frame id of this call (the shared counter)."""
+def _next_frame_id(name):
+    """-> the frame id of this call (the shared counter), after checking that a GPU is visible."""
     global _calls
-    if outPose.dim() != 2 or tuple(outPose.shape) != (4, 4) or outPose.dtype != torch.float32:
-        raise RuntimeError("outPose must be a float32 tensor of shape 4x4")
     if not torch.cuda.is_available():
         raise RuntimeError(f"dsacstar.{name}: no GPU visible; the MI355X implementation has no CPU path")
     _calls += 1
     return _calls - 1
+
+
+def _check_call(name, outPose):
+    """The checks both forward entries make after their input shapes; -> the frame id of this call (the shared counter)."""
+    if outPose.dim() != 2 or tuple(outPose.shape) != (4, 4) or outPose.dtype != torch.float32:
+        raise RuntimeError("outPose must be a float32 tensor of shape 4x4")
+    return _next_frame_id(name)
 
 
 def _host_call(entry, inputs, outPose, *args):
@@ -215,3 +220,217 @@ def register_batch_rgbd(scene_coords, camera_coords, params, seed, frame_ids=Non
 def debug_fetch_rgbd(n, hyps, device=None):
     """Per-hypothesis results of the last RGB-D call: sampled triples (map indices y*W+x), (rvec, tvec), scores, best, refined."""
     return _debug_fetch("acez_ransac_rgbd_debug_fetch", n, hyps, device, samples=True)
+
+
+# ---------------------------------------------------------------------------------------------------- RGB-D backward
+PROB_THRESH = 0.001  # dsacstar_derivative.h:36: hypotheses below it are neither refined nor differentiated
+
+
+def _gt_rows(gtPose, n, dev):
+    g = torch.as_tensor(gtPose, dtype=torch.float32).reshape(n, 4, 4)
+    return g.to(dev).contiguous()
+
+
+def register_batch_rgbd_backward(scene_coords, camera_coords, gt_poses, params, seed, frame_ids=None, w_loss_rot=1.0,
+                                 w_loss_trans=1.0, soft_clamp=100.0, out_grad=None):
+    """The DSAC* RGB-D backward pass of n frames: scene_coords, camera_coords CUDA float32 [n,3,H,W] (metres), gt_poses [n,4,4]
+    cam->world; params as register_batch_rgbd's. The hypotheses are those register_batch_rgbd draws for the same (seed, frame ids).
+    Returns (grad [n,3,H,W] f32, expected loss [n] f64), CUDA tensors; the gradient is added to out_grad if one is given (a
+    contiguous CUDA float32 [n,3,H,W]) and that tensor is returned. Asynchronous."""
+    for t in (scene_coords, camera_coords):
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] == 3
+    assert tuple(scene_coords.shape) == tuple(camera_coords.shape) and scene_coords.device == camera_coords.device
+    if not isinstance(params, N.RansacParams):
+        params = _params(**{**_RGBD_DEFAULTS, **params})
+    n, _, H, W = scene_coords.shape
+    dev = scene_coords.device
+    gt = _gt_rows(gt_poses, n, dev)
+    if out_grad is None:
+        out_grad = torch.zeros(n, 3, H, W, dtype=torch.float32, device=dev)
+    assert out_grad.is_cuda and out_grad.dtype == torch.float32 and out_grad.is_contiguous() and tuple(out_grad.shape) == (n, 3, H, W)
+    loss = torch.empty(n, dtype=torch.float64, device=dev)
+    sc, cc = scene_coords.contiguous(), camera_coords.contiguous()
+    ctx, L = _context(n, H, W, dev.index)
+    ids = (C.c_uint64 * n)(*[int(x) for x in frame_ids]) if frame_ids is not None else None
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        N.check(L.acez_register_rgbd_backward_device(ctx, C.c_void_p(sc.data_ptr()), C.c_void_p(cc.data_ptr()), C.c_void_p(gt.data_ptr()),
+                                                     n, H, W, C.byref(params), float(w_loss_rot), float(w_loss_trans), float(soft_clamp),
+                                                     C.c_uint64(int(seed)), ids, C.c_void_p(out_grad.data_ptr()),
+                                                     C.c_void_p(loss.data_ptr()), stream))
+    return out_grad, loss
+
+
+def backward_rgbd(sceneCoordinates, cameraCoordinates, outSceneCoordinatesGrad, gtPose, ransacHypotheses, inlierThreshold, wLossRot,
+                  wLossTrans, softClamp, inlierAlpha, maxDistError, randomSeed):
+    """The reference's commented-out binding (dsacstar.cpp:642-895): 1x3xHxW scene and camera coordinates (metres), 4x4 cam->world
+    gtPose; the gradient of the expected pose loss is ADDED to outSceneCoordinatesGrad (1x3xHxW float32) and the expected loss is
+    returned. inlierThreshold / maxDistError in centimetres. The frame id is the call counter forward_rgbd uses, the seed randomSeed."""
+    sc, cc, og = sceneCoordinates, cameraCoordinates, outSceneCoordinatesGrad
+    _check_1x3("sceneCoordinates", sc)
+    _check_1x3("cameraCoordinates", cc)
+    _check_1x3("outSceneCoordinatesGrad", og)
+    if tuple(sc.shape) != tuple(cc.shape) or tuple(sc.shape) != tuple(og.shape):
+        raise RuntimeError("sceneCoordinates, cameraCoordinates and outSceneCoordinatesGrad must have the same shape")
+    gt = torch.as_tensor(gtPose, dtype=torch.float32)
+    if tuple(gt.shape) != (4, 4):
+        raise RuntimeError("gtPose must be a 4x4 tensor")
+    frame_id = _next_frame_id("backward_rgbd")
+    prm = _params(ransacHypotheses, inlierThreshold, inlierAlpha, maxDistError, **_RGBD_DEFAULTS)
+    if sc.is_cuda or cc.is_cuda or og.is_cuda:
+        dev = next(t.device for t in (sc, cc, og) if t.is_cuda)
+        g, loss = register_batch_rgbd_backward(sc.to(dev), cc.to(dev), gt, prm, randomSeed, [frame_id], wLossRot, wLossTrans, softClamp)
+        og.add_(g.to(og.device))
+        return float(loss[0].item())
+    H, W = int(sc.shape[2]), int(sc.shape[3])
+    ctx, L = _context(1, H, W, torch.cuda.current_device())
+    gt16 = np.ascontiguousarray(gt.cpu().numpy(), np.float32)
+    out = C.c_double(0.0)
+    strided = [a for t in (sc, cc) for a in (C.c_void_p(t.data_ptr()), *t.stride()[1:])]
+    N.check(L.acez_register_rgbd_backward_host(ctx, *strided, gt16.ctypes.data_as(C.c_void_p), H, W, C.byref(prm), float(wLossRot),
+                                               float(wLossTrans), float(softClamp), C.c_uint64(int(randomSeed)), C.c_uint64(frame_id),
+                                               C.c_void_p(og.data_ptr()), *og.stride()[1:], C.byref(out)))
+    return float(out.value)
+
+
+def _debug_fetch_backward(entry, n, hyps, h, w, n_samples, words, device):
+    dev = torch.cuda.current_device() if device is None else device
+    L = N.lib()
+    out = dict(samples=np.zeros((n, hyps, n_samples), np.int32), hyp_poses=np.zeros((n, hyps, 6)), scores=np.zeros((n, hyps)),
+               probs=np.zeros((n, hyps)), losses=np.zeros((n, hyps)), ref_poses=np.zeros((n, hyps, 6)),
+               masks=np.zeros((n, hyps, words), np.uint64), entropy=np.zeros(n))
+    N.check(getattr(L, entry)(_ctx[(dev, L._name)]["h_"], n, hyps, h, w, *[a.ctypes.data_as(C.c_void_p) for a in out.values()]))
+    out["masks"] = np.unpackbits(out["masks"].view(np.uint8), axis=-1, bitorder="little").astype(bool)
+    return out
+
+
+def debug_fetch_rgbd_backward(n, hyps, h, w, device=None):
+    """Per-hypothesis results of the last RGB-D backward call: samples, hyp_poses, scores, probs, losses, ref_poses, masks (bool
+    [n,hyps,valid cells] over the valid cells in scan order), entropy."""
+    return _debug_fetch_backward("acez_ransac_rgbd_backward_debug_fetch", n, hyps, h, w, 3, ((h * w + 511) // 512) * 8, device)
+
+
+class _ExpectedPoseLossRGBD(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, coords, camera_coords, gt_poses, params, seed, frame_ids, w_rot, w_trans, clamp):
+        g, loss = register_batch_rgbd_backward(coords.detach(), camera_coords.detach(), gt_poses, params, seed, frame_ids, w_rot,
+                                               w_trans, clamp)
+        ctx.save_for_backward(g)
+        return loss.to(coords.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (g,) = ctx.saved_tensors
+        return (g * grad_out.to(g.dtype).view(-1, 1, 1, 1),) + (None,) * 8
+
+
+def expected_pose_loss_rgbd(coords, camera_coords, gt_poses, hypotheses=64, threshold=10.0, w_loss_rot=1.0, w_loss_trans=1.0,
+                            soft_clamp=100.0, inlier_alpha=100.0, max_dist=100.0, seed=0, frame_ids=None):
+    """Differentiable DSAC* RGB-D loss: the expected pose loss per frame, float32 [n] on the coordinates' device, whose .backward()
+    puts the backward pass's gradient into coords.grad. coords, camera_coords: CUDA [n,3,H,W] (metres); gt_poses [n,4,4] cam->world.
+    frame_ids default to the next values of the call counter forward_rgbd uses, so successive calls draw fresh hypotheses."""
+    global _calls
+    n = coords.shape[0]
+    if frame_ids is None:
+        frame_ids = list(range(_calls, _calls + n))
+        _calls += n
+    prm = _params(hypotheses, threshold, inlier_alpha, max_dist, **_RGBD_DEFAULTS)
+    return _ExpectedPoseLossRGBD.apply(coords, camera_coords, gt_poses, prm, seed, list(frame_ids), w_loss_rot, w_loss_trans, soft_clamp)
+
+
+# ---------------------------------------------------------------------------------------------------- RGB backward
+def register_batch_backward(scene_coords, intrinsics, gt_poses, params, seed, frame_ids=None, w_loss_rot=1.0, w_loss_trans=1.0,
+                            soft_clamp=100.0, out_grad=None):
+    """The DSAC* RGB backward pass of n frames: scene_coords CUDA float32 [n,3,H,W], intrinsics and params as register_batch's, gt_poses
+    [n,4,4] cam->world. The hypotheses are those register_batch draws for the same (seed, frame ids). Returns (grad [n,3,H,W] f32,
+    expected loss [n] f64), CUDA tensors; the gradient is added to out_grad if one is given. Asynchronous."""
+    assert scene_coords.is_cuda and scene_coords.dtype == torch.float32 and scene_coords.dim() == 4 and scene_coords.shape[1] == 3
+    if not isinstance(params, N.RansacParams):
+        params = _params(**params)
+    n, _, H, W = scene_coords.shape
+    dev = scene_coords.device
+    arr = (N.Intrinsics * n)()
+    for i, it in enumerate(intrinsics):
+        arr[i] = it if isinstance(it, N.Intrinsics) else N.Intrinsics(float(it[0]), float(it[1]), float(it[2]))
+    gt = _gt_rows(gt_poses, n, dev)
+    if out_grad is None:
+        out_grad = torch.zeros(n, 3, H, W, dtype=torch.float32, device=dev)
+    assert out_grad.is_cuda and out_grad.dtype == torch.float32 and out_grad.is_contiguous() and tuple(out_grad.shape) == (n, 3, H, W)
+    loss = torch.empty(n, dtype=torch.float64, device=dev)
+    sc = scene_coords.contiguous()
+    ctx, L = _context(n, H, W, dev.index)
+    ids = (C.c_uint64 * n)(*[int(x) for x in frame_ids]) if frame_ids is not None else None
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        N.check(L.acez_register_rgb_backward_device(ctx, C.c_void_p(sc.data_ptr()), C.c_void_p(gt.data_ptr()), n, H, W, C.byref(params),
+                                                    arr, float(w_loss_rot), float(w_loss_trans), float(soft_clamp), C.c_uint64(int(seed)),
+                                                    ids, C.c_void_p(out_grad.data_ptr()), C.c_void_p(loss.data_ptr()), stream))
+    return out_grad, loss
+
+
+def backward_rgb(sceneCoordinates, outSceneCoordinatesGrad, gtPose, ransacHypotheses, inlierThreshold, focalLength, ppointX, ppointY,
+                 wLossRot, wLossTrans, softClamp, inlierAlpha, maxReproj, subSampling, randomSeed):
+    """The reference's commented-out binding (dsacstar.cpp:208-490): 1x3xHxW scene coordinates, 4x4 cam->world gtPose; the gradient
+    of the expected pose loss is ADDED to outSceneCoordinatesGrad (1x3xHxW float32) and the expected loss is returned. The frame id
+    is the call counter forward_rgb uses, the seed randomSeed; the tries are forward_rgb's default (16)."""
+    sc, og = sceneCoordinates, outSceneCoordinatesGrad
+    _check_1x3("sceneCoordinates", sc)
+    _check_1x3("outSceneCoordinatesGrad", og)
+    if tuple(sc.shape) != tuple(og.shape):
+        raise RuntimeError("sceneCoordinates and outSceneCoordinatesGrad must have the same shape")
+    gt = torch.as_tensor(gtPose, dtype=torch.float32)
+    if tuple(gt.shape) != (4, 4):
+        raise RuntimeError("gtPose must be a 4x4 tensor")
+    frame_id = _next_frame_id("backward_rgb")
+    prm = _params(ransacHypotheses, inlierThreshold, inlierAlpha, maxReproj, subSampling, MAX_HYPOTHESES_TRIES)
+    intr = N.Intrinsics(float(focalLength), float(ppointX), float(ppointY))
+    if sc.is_cuda or og.is_cuda:
+        dev = sc.device if sc.is_cuda else og.device
+        g, loss = register_batch_backward(sc.to(dev), [intr], gt, prm, randomSeed, [frame_id], wLossRot, wLossTrans, softClamp)
+        og.add_(g.to(og.device))
+        return float(loss[0].item())
+    H, W = int(sc.shape[2]), int(sc.shape[3])
+    ctx, L = _context(1, H, W, torch.cuda.current_device())
+    gt16 = np.ascontiguousarray(gt.cpu().numpy(), np.float32)
+    out = C.c_double(0.0)
+    N.check(L.acez_register_rgb_backward_host(ctx, C.c_void_p(sc.data_ptr()), *sc.stride()[1:], gt16.ctypes.data_as(C.c_void_p), H, W,
+                                              C.byref(prm), C.byref(intr), float(wLossRot), float(wLossTrans), float(softClamp),
+                                              C.c_uint64(int(randomSeed)), C.c_uint64(frame_id), C.c_void_p(og.data_ptr()),
+                                              *og.stride()[1:], C.byref(out)))
+    return float(out.value)
+
+
+def debug_fetch_rgb_backward(n, hyps, h, w, device=None):
+    """Per-hypothesis results of the last RGB backward call: samples (4 scan indices x*h+y), hyp_poses, scores, probs, losses,
+    ref_poses, masks (bool [n,hyps,h*w] over all cells in scan order), entropy."""
+    out = _debug_fetch_backward("acez_ransac_rgb_backward_debug_fetch", n, hyps, h, w, 4, ((h * w + 255) // 256) * 4, device)
+    out["masks"] = out["masks"][:, :, :h * w]
+    return out
+
+
+class _ExpectedPoseLossRGB(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, coords, intrinsics, gt_poses, params, seed, frame_ids, w_rot, w_trans, clamp):
+        g, loss = register_batch_backward(coords.detach(), intrinsics, gt_poses, params, seed, frame_ids, w_rot, w_trans, clamp)
+        ctx.save_for_backward(g)
+        return loss.to(coords.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (g,) = ctx.saved_tensors
+        return (g * grad_out.to(g.dtype).view(-1, 1, 1, 1),) + (None,) * 8
+
+
+def expected_pose_loss_rgb(coords, intrinsics, gt_poses, hypotheses=64, threshold=10.0, w_loss_rot=1.0, w_loss_trans=1.0,
+                           soft_clamp=100.0, inlier_alpha=100.0, max_reproj=100.0, subsampling=8, seed=0, frame_ids=None,
+                           max_tries=MAX_HYPOTHESES_TRIES):
+    """Differentiable DSAC* RGB loss: the expected pose loss per frame, float32 [n], whose .backward() puts the backward pass's
+    gradient into coords.grad. coords: CUDA [n,3,H,W]; intrinsics: one (focal, ppx, ppy) per frame; gt_poses [n,4,4] cam->world.
+    frame_ids default to the next values of the call counter forward_rgb uses."""
+    global _calls
+    n = coords.shape[0]
+    if frame_ids is None:
+        frame_ids = list(range(_calls, _calls + n))
+        _calls += n
+    prm = _params(hypotheses, threshold, inlier_alpha, max_reproj, subsampling, max_tries)
+    return _ExpectedPoseLossRGB.apply(coords, list(intrinsics), gt_poses, prm, seed, list(frame_ids), w_loss_rot, w_loss_trans, soft_clamp)

@@ -7,6 +7,10 @@ dsacstar/dsacstar.cpp with OpenCV; here it is the MI355X implementation behind t
 
 Put the repository root on PYTHONPATH (or copy this directory next to register_mapping.py) and the reference's
 register_mapping.py runs unchanged on this call. forward_rgbd is the reference's commented-out RGB-D binding (dsacstar.cpp:901),
-same arguments. Extras (not in the reference): register_batch / register_batch_rgbd (device-resident, batched),
+same arguments. backward_rgb and backward_rgbd are the reference's commented-out gradients (dsacstar.cpp:208-490, 642-895), same
+arguments. Extras (not in the reference): register_batch / register_batch_rgbd / register_batch_backward / register_batch_rgbd_backward (device-resident,
+batched), expected_pose_loss_rgb / expected_pose_loss_rgbd (torch.autograd losses),
 set_verbose, reset_call_counter."""
-from acezero_amd.dsacstar import forward_rgb, forward_rgbd, register_batch, register_batch_rgbd, reset_call_counter, set_verbose  # noqa: F401
+from acezero_amd.dsacstar import (backward_rgb, backward_rgbd, expected_pose_loss_rgb, expected_pose_loss_rgbd, forward_rgb,  # noqa: F401
+                                  forward_rgbd, register_batch, register_batch_backward, register_batch_rgbd,
+                                  register_batch_rgbd_backward, reset_call_counter, set_verbose)

@@ -106,6 +106,34 @@ int acez_register_rgb_host(acez_ransac* ctx, const float* h_scene_coords, int64_
 int acez_ransac_debug_fetch(acez_ransac* ctx, int n_frames, int hypotheses, double* h_hyp_poses,
                             double* h_scores, int32_t* h_best, double* h_refined);
 
+/* RGB backward: the reference's commented-out dsacstar.backward_rgb (dsacstar.cpp:208-490). Samples and scores exactly as
+ * acez_register_rgb_device does for the same (seed, frame id), turns the scores into soft-max probabilities, refines every
+ * hypothesis with probability >= 0.001 and returns the expected pose loss per frame with its gradient with respect to the scene
+ * coordinates: the hypothesis path through the refinement's normal equations, -(J^T J)^+ J^T over the final inliers' reprojection
+ * errors (zero for a hypothesis if an entry exceeds 10), and the score path through every pixel's error and, by central
+ * differences of P3P (eps 0.001), the hypothesis' minimal set.
+ *   d_scene_coords, params, h_intrinsics, seed, h_frame_ids   as in acez_register_rgb_device
+ *   d_gt_poses, w_loss_rot, w_loss_trans, soft_clamp, d_out_grad, d_out_loss   as in acez_register_rgbd_backward_device
+ * Deterministic. Asynchronous on `stream`. Calls on one context share its workspaces: serialise them (one stream at a time). */
+int acez_register_rgb_backward_device(acez_ransac* ctx, const float* d_scene_coords, const float* d_gt_poses, int n_frames, int h,
+                                      int w, const acez_ransac_params* params, const acez_intrinsics* h_intrinsics,
+                                      float w_loss_rot, float w_loss_trans, float soft_clamp, uint64_t seed,
+                                      const uint64_t* h_frame_ids, float* d_out_grad, double* d_out_loss, void* stream);
+
+/* Host-buffer variant for ONE frame: strides in elements; the gradient is added to h_grad with its own strides. Synchronous. */
+int acez_register_rgb_backward_host(acez_ransac* ctx, const float* h_scene_coords, int64_t stride_c, int64_t stride_h,
+                                    int64_t stride_w, const float* h_gt_pose16, int h, int w, const acez_ransac_params* params,
+                                    const acez_intrinsics* intr, float w_loss_rot, float w_loss_trans, float soft_clamp,
+                                    uint64_t seed, uint64_t frame_id, float* h_grad, int64_t g_stride_c, int64_t g_stride_h,
+                                    int64_t g_stride_w, double* out_loss);
+
+/* Diagnostics of the LAST acez_register_rgb_backward_* call, as acez_ransac_rgbd_backward_debug_fetch except:
+ *   h_samples    int32  [n_frames][hypotheses][4]  scan indices x*h+y of the kept minimal set
+ *   h_mask_words uint64 [n_frames][hypotheses][ceil(h*w / 256) * 4]  final inliers over ALL cells in scan order (x-outer, y-inner) */
+int acez_ransac_rgb_backward_debug_fetch(acez_ransac* ctx, int n_frames, int hypotheses, int h, int w, int32_t* h_samples,
+                                         double* h_hyp_poses, double* h_scores, double* h_probs, double* h_losses,
+                                         double* h_ref_poses, uint64_t* h_mask_words, double* h_entropy);
+
 /* RGB-D registration: the reference's commented-out dsacstar.forward_rgbd (dsacstar.cpp:493-640). A pose from 3D-3D
  * correspondences (Kabsch on three cells per hypothesis, 3D distance scores, Kabsch refinement on the inliers), no PnP.
  * Same context as the RGB calls; acez_ransac_params keeps its fields with these meanings here:
@@ -143,6 +171,44 @@ int acez_register_rgbd_host(acez_ransac* ctx, const float* h_scene_coords, int64
  * Any pointer may be NULL. Synchronous. */
 int acez_ransac_rgbd_debug_fetch(acez_ransac* ctx, int n_frames, int hypotheses, int32_t* h_samples,
                                  double* h_hyp_poses, double* h_scores, int32_t* h_best, double* h_refined);
+
+/* RGB-D backward: the reference's commented-out dsacstar.backward_rgbd (dsacstar.cpp:642-895). Samples and scores exactly as
+ * acez_register_rgbd_device does for the same (seed, frame id), turns the scores into soft-max probabilities, refines every
+ * hypothesis with probability >= 0.001, and returns the expected pose loss E = sum_h p_h loss_h per frame with its gradient with
+ * respect to the scene coordinates (the hypothesis path through the refinement's Kabsch fit plus the score path).
+ *   d_scene_coords, d_camera_coords, params, seed, h_frame_ids   as in acez_register_rgbd_device
+ *   d_gt_poses       float32 [n_frames][4][4] row-major cam->world ground truth
+ *   w_loss_rot, w_loss_trans, soft_clamp   loss = w_rot * angle (degrees) + w_trans * |camera centre error|, softly clamped
+ *                    (sqrt(soft_clamp * loss)) above soft_clamp, at most 1e7
+ *   d_out_grad       float32 [n_frames][3][h][w]: the gradient is ADDED to it (the reference's +=)
+ *   d_out_loss       float64 [n_frames] expected loss
+ * Deterministic: the same inputs give the same bits. Asynchronous on `stream`. Calls on one context share its workspaces (the
+ * fp64 gradient accumulator among them): serialise them, one stream at a time. */
+int acez_register_rgbd_backward_device(acez_ransac* ctx, const float* d_scene_coords, const float* d_camera_coords,
+                                       const float* d_gt_poses, int n_frames, int h, int w, const acez_ransac_params* params,
+                                       float w_loss_rot, float w_loss_trans, float soft_clamp, uint64_t seed,
+                                       const uint64_t* h_frame_ids, float* d_out_grad, double* d_out_loss, void* stream);
+
+/* Host-buffer variant for ONE frame: strides in elements; the gradient is added to h_grad with its own strides. Synchronous. */
+int acez_register_rgbd_backward_host(acez_ransac* ctx, const float* h_scene_coords, int64_t sc_stride_c, int64_t sc_stride_h,
+                                     int64_t sc_stride_w, const float* h_camera_coords, int64_t cc_stride_c,
+                                     int64_t cc_stride_h, int64_t cc_stride_w, const float* h_gt_pose16, int h, int w,
+                                     const acez_ransac_params* params, float w_loss_rot, float w_loss_trans, float soft_clamp,
+                                     uint64_t seed, uint64_t frame_id, float* h_grad, int64_t g_stride_c, int64_t g_stride_h,
+                                     int64_t g_stride_w, double* out_loss);
+
+/* Diagnostics of the LAST acez_register_rgbd_backward_* call (h, w: its frame size):
+ *   h_samples, h_hyp_poses, h_scores   as acez_ransac_rgbd_debug_fetch
+ *   h_probs      float64 [n_frames][hypotheses]     soft-max probabilities
+ *   h_losses     float64 [n_frames][hypotheses]     loss of each (refined) hypothesis
+ *   h_ref_poses  float64 [n_frames][hypotheses][6]  (rvec, tvec) after refinement (the sampled pose if p < 0.001)
+ *   h_mask_words uint64  [n_frames][hypotheses][ceil(h*w / 512) * 8]  final inlier set over the valid cells in scan order
+ *                (x-outer, y-inner): bit j % 64 of word j / 64 is valid cell j; zero if not refined or no step was accepted
+ *   h_entropy    float64 [n_frames]                 entropy (bits) of the probabilities
+ * Any pointer may be NULL. Synchronous. */
+int acez_ransac_rgbd_backward_debug_fetch(acez_ransac* ctx, int n_frames, int hypotheses, int h, int w, int32_t* h_samples,
+                                          double* h_hyp_poses, double* h_scores, double* h_probs, double* h_losses,
+                                          double* h_ref_poses, uint64_t* h_mask_words, double* h_entropy);
 
 /* ------------------------------------------------------------------------------------------------
  * (T) head training / inference
