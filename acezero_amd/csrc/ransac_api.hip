@@ -19,8 +19,9 @@
 //               wavefronts in a fixed order through LDS; the 6x6 solve runs on wavefront 0.
 // Nothing is written to HBM between stages except the diagnostics (hypothesis poses / scores).
 // Roofline: per frame 57.6 KB in, ~5 KB out; the kernel is fp64-VALU/latency bound.
-// This unit also defines the registration host side that ransac_rgbd.hip shares (ransac_ctx.h): the context, the per-estimator
-// workspaces, the frame-parameter slot ring, the launch geometry, the host-buffer staging and the debug fetch.
+// This unit also defines the registration host side that ransac_rgbd.hip and ransac_grad.hip share (ransac_ctx.h): the context, the
+// per-estimator workspaces, the frame-parameter slot ring, the argument checks, the launch geometry, the host-buffer staging of the
+// forward and backward entries and the debug fetches.
 #include <hip/hip_runtime.h>
 #include "ransac_math.h"
 #include "acez_common.h"
@@ -54,17 +55,7 @@ struct RansacArgs {
   uint8_t* out_masks; // [n][H][W] or null
   // the backward pass only (GRAD instantiation)
   int* samples;                // [n][hyps][4] scan indices x * H + y of the kept minimal set
-  const float* gt;             // [n][16] row-major cam->world ground truth
-  float w_rot, w_trans, cut;
-  double* probs;               // [n][hyps]
-  double* losses;              // [n][hyps]
-  double* ref_poses;           // [n][hyps][6]
-  unsigned long long* masks;   // [n][hyps][mwords]: bit p % 64 of word p / 64 = pixel p (scan order) is a final inlier
-  int mwords;
-  double* gacc;                // [n][3][N] fp64 accumulator
-  double* entropy;             // [n]
-  float* out_grad;             // [n][3][H][W], added to
-  double* out_loss;            // [n]
+  acez_rs::GradOut grad;       // the masks are over all pixels
 };
 
 // ---- cross-lane sums of doubles without the LDS crossbar --------------------------------------------------------------------
@@ -202,6 +193,7 @@ __device__ bool inv4x4(const double Ain[16], double out[16]) {
 //   [8] int           best hypothesis
 // 60x80 (7-Scenes): 70.1 KB, 60x93 (Mip-NeRF 360 at 480 px): 81.7 KB with 64 hypotheses -> two workgroups per CU in both cases.
 constexpr int MAX_ROWS = 64;                        // pixels per thread (inlier flags are one 64-bit word): N <= 16384
+static_assert(acez_rs::RGB_THREADS * MAX_ROWS == acez_rs::MAX_CELLS, "check_frames' limit is this layout's");
 constexpr int RED_DOUBLES = 8 + 2 * 4 * 28;         // step hand-over + reduction scratch
 constexpr int REGION_MIN = RED_DOUBLES + MAX_ROWS * 4 / 2;
 __host__ __device__ inline int region_doubles(int hyps) { return 7 * hyps > REGION_MIN ? 7 * hyps : REGION_MIN; }
@@ -212,7 +204,6 @@ __host__ __device__ inline size_t lds_bytes(int Npad, int hyps, bool coords_in_h
 __host__ __device__ inline size_t grad_lds_bytes(int Npad, int hyps, bool coords_in_hbm) {
   return lds_bytes(Npad, hyps, coords_in_hbm) + 8 * (size_t)(2 * hyps + 64);
 }
-__host__ __device__ inline int rgb_mask_words(int N) { return ((N + 255) >> 8) * 4; }
 
 // GC: the frame does not fit the LDS (more than ~11 400 scene coordinates): its scan-order copy lives in an HBM workspace (L2
 // resident, 12 N bytes) and every stage reads it from there; same arithmetic, same order, same bits.
@@ -570,28 +561,12 @@ __global__ __launch_bounds__(256, 2) void ransac_kernel(RansacArgs a) {
     double* sProb = reinterpret_cast<double*>(sInt + 8);   // [hyps]
     double* sLoss = sProb + a.hyps;                         // [hyps]
     double* sM = sLoss + a.hyps;    // [0,36) (J^T J)^+, [36,42) v = (J^T J)^+ p dLoss, [42] E, [48,52) wavefront maxima
-    const float* G = a.gt + (size_t)frame * 16;
-    double* gacc = a.gacc + (size_t)frame * 3 * N;
-    unsigned long long* mw = a.masks + (size_t)frame * a.hyps * a.mwords;
-    for (int m = tid; m < 3 * N; m += 256) gacc[m] = 0.0;
-    for (int i = tid; i < a.hyps * a.mwords; i += 256) mw[i] = 0ull;
-    if (tid == 0) {   // dsacstar::softMax, dsacstar::entropy
-      double maxScore = 0;
-      for (int i = 0; i < a.hyps; i++)
-        if (i == 0 || sScores[i] > maxScore) maxScore = sScores[i];
-      double sum = 0.0;
-      for (int i = 0; i < a.hyps; i++) {
-        sProb[i] = detm::exp_(sScores[i] - maxScore);
-        sum += sProb[i];
-      }
-      double ent = 0.0;
-      for (int i = 0; i < a.hyps; i++) {
-        sProb[i] /= sum;
-        a.probs[(size_t)frame * a.hyps + i] = sProb[i];
-        if (sProb[i] > 0) ent -= sProb[i] * log2(sProb[i]);
-      }
-      a.entropy[frame] = ent;
-    }
+    const acez_rs::GradOut& go = a.grad;
+    const float* G = go.gt + (size_t)frame * 16;
+    double* gacc = go.gacc + (size_t)frame * 3 * N;
+    unsigned long long* mw = go.masks + (size_t)frame * a.hyps * go.mwords;
+    acez_loss::zero_frame(gacc, N, mw, a.hyps * go.mwords, tid, 256);
+    if (tid == 0) acez_loss::softmax_entropy(sScores, a.hyps, sProb, go.probs + (size_t)frame * a.hyps, go.entropy + frame);
     __syncthreads();
     const double NORM_EPS = 1e-8;   // the reference's max(|e|, EPS)
     // d|e| / d(rvec, tvec) of pixel p at prm (one row of the refinement's Jacobian); false if its error exceeds max_reproj
@@ -648,15 +623,15 @@ __global__ __launch_bounds__(256, 2) void ransac_kernel(RansacArgs a) {
       if (active && hm)
         for (int i = 0; i < rows; ++i) {
           const unsigned long long bits = __ballot((accf >> i) & 1ull);
-          if (lane == 0) mw[(size_t)h * a.mwords + i * 4 + wave] = bits;
+          if (lane == 0) mw[(size_t)h * go.mwords + i * 4 + wave] = bits;
         }
       double g6[6];
-      const double L = acez_loss::pose_loss(param, G, a.w_rot, a.w_trans, a.cut, active ? g6 : nullptr);
+      const double L = acez_loss::pose_loss(param, G, go.w_rot, go.w_trans, go.cut, active ? g6 : nullptr);
       if (tid == 0) {
         sLoss[h] = L;
         const size_t o = (size_t)frame * a.hyps + h;
-        a.losses[o] = L;
-        for (int i = 0; i < 6; ++i) a.ref_poses[o * 6 + i] = param[i];
+        go.losses[o] = L;
+        for (int i = 0; i < 6; ++i) go.ref_poses[o * 6 + i] = param[i];
       }
       if (!(active && hm)) continue;
       // dHyp/dObj = -(J^T J)^+ J^T dN/dObj over the final inliers, J the rows of d|e|/dHyp (dsacstar.cpp:362-420)
@@ -713,10 +688,9 @@ __global__ __launch_bounds__(256, 2) void ransac_kernel(RansacArgs a) {
     }
     __syncthreads();
     if (tid == 0) {
-      double E = 0;
-      for (int h = 0; h < a.hyps; ++h) E += sProb[h] * sLoss[h];
+      const double E = acez_loss::expected_loss(sProb, sLoss, a.hyps);
       sM[42] = E;
-      a.out_loss[frame] = E;
+      go.out_loss[frame] = E;
     }
     __syncthreads();
     const double Eexp = sM[42];
@@ -782,20 +756,17 @@ __global__ __launch_bounds__(256, 2) void ransac_kernel(RansacArgs a) {
             }
           }
         if (ok && !(mxc > 10)) {   // a failed solve or an entry above 10 zeroes the support term (dPNP, dScore)
+          int ms[3];
           for (int i = 0; i < 3; ++i) {
-            const int x = div_h(smp[i], H, magic), y = smp[i] - x * H, m = y * W + x;
-            for (int c = 0; c < 3; ++c) {
-              double v = 0;
-              for (int q = 0; q < 6; ++q) v += S.JtErr[q] * cols[i * 3 + c][q];
-              gacc[c * N + m] += v;
-            }
+            const int x = div_h(smp[i], H, magic), y = smp[i] - x * H;
+            ms[i] = y * W + x;
           }
+          acez_loss::scatter_support(gacc, N, ms, S.JtErr, cols);
         }
       }
       __syncthreads();
     }
-    float* og = a.out_grad + (size_t)frame * 3 * N;
-    for (int i = tid; i < 3 * N; i += 256) og[i] += (float)gacc[i];
+    acez_loss::flush_grad(go.out_grad + (size_t)frame * 3 * N, gacc, N, tid, 256);
     return;
   }
 
@@ -867,7 +838,7 @@ __global__ __launch_bounds__(256, 2) void ransac_kernel(RansacArgs a) {
 // ====================================================================================================
 namespace acez_rs {
 
-int ensure_hyps(Workspace& ws, int hyps, bool samples) {
+int ensure_hyps(Workspace& ws, int hyps) {
   if (!ws.d_best) ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_best, (size_t)ws.frames * sizeof(int)));
   if (!ws.d_refined) ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_refined, (size_t)ws.frames * 6 * sizeof(double)));
   if (hyps <= ws.hyps) return ACEZ_OK;
@@ -879,7 +850,8 @@ int ensure_hyps(Workspace& ws, int hyps, bool samples) {
   ws.hyps = 0;
   ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_hyp_poses, (size_t)ws.frames * hyps * 6 * sizeof(double)));
   ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_scores, (size_t)ws.frames * hyps * sizeof(double)));
-  if (samples) ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_samples, (size_t)ws.frames * hyps * 4 * sizeof(int)));
+  if (ws.sample_width)
+    ACEZ_HIP_CHECK(hipMalloc((void**)&ws.d_samples, (size_t)ws.frames * hyps * ws.sample_width * sizeof(int)));
   ws.hyps = hyps;
   return ACEZ_OK;
 }
@@ -899,6 +871,64 @@ void release(Workspace& ws) {
   for (void* p : {(void*)ws.d_hyp_poses, (void*)ws.d_scores, (void*)ws.d_samples, (void*)ws.d_best, (void*)ws.d_refined, (void*)ws.d_list})
     if (p) (void)hipFree(p);
   ws = Workspace();
+}
+
+int ensure_grad(GradWorkspace& g, int hyps, int cells) {
+  int rc = ensure_hyps(g.ws, hyps);
+  if (rc != ACEZ_OK) return rc;
+  const int frames = g.ws.frames, mw = mask_words(g, cells);
+  if (!g.d_entropy) {
+    ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_entropy, (size_t)frames * sizeof(double)));
+    ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_loss, (size_t)frames * sizeof(double)));
+    ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_gt, (size_t)frames * 16 * sizeof(float)));
+  }
+  if (hyps <= g.hyps && cells <= g.cells && mw <= g.mwords) return ACEZ_OK;
+  ACEZ_HIP_CHECK(hipDeviceSynchronize());   // earlier launches may still write the old buffers
+  for (void* p : {(void*)g.d_probs, (void*)g.d_losses, (void*)g.d_ref_poses, (void*)g.d_masks, (void*)g.d_gacc, (void*)g.d_grad})
+    if (p) (void)hipFree(p);
+  g.d_probs = g.d_losses = g.d_ref_poses = g.d_gacc = nullptr;
+  g.d_masks = nullptr;
+  g.d_grad = nullptr;
+  g.hyps = g.cells = g.mwords = 0;
+  const int H = hyps > g.ws.hyps ? hyps : g.ws.hyps;
+  ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_probs, (size_t)frames * H * sizeof(double)));
+  ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_losses, (size_t)frames * H * sizeof(double)));
+  ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_ref_poses, (size_t)frames * H * 6 * sizeof(double)));
+  ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_masks, (size_t)frames * H * mw * sizeof(unsigned long long)));
+  ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_gacc, (size_t)frames * 3 * cells * sizeof(double)));
+  ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_grad, (size_t)3 * cells * sizeof(float)));
+  g.hyps = H; g.cells = cells; g.mwords = mw;
+  return ACEZ_OK;
+}
+
+void release_grad(GradWorkspace& g) {
+  release(g.ws);
+  for (void* p : {(void*)g.d_probs, (void*)g.d_losses, (void*)g.d_ref_poses, (void*)g.d_masks, (void*)g.d_gacc, (void*)g.d_entropy,
+                  (void*)g.d_gt, (void*)g.d_grad, (void*)g.d_loss})
+    if (p) (void)hipFree(p);
+  g = GradWorkspace();
+}
+
+GradOut make_grad_out(const GradWorkspace& g, int cells, const float* gt, float w_rot, float w_trans, float cut, float* out_grad,
+                      double* out_loss) {
+  return GradOut{gt, w_rot, w_trans, cut, g.d_probs, g.d_losses, g.d_ref_poses, g.d_masks, mask_words(g, cells), g.d_gacc, g.d_entropy,
+                 out_grad, out_loss};
+}
+
+int check_frames(const acez_ransac* ctx, int n_frames, int h, int w, const acez_ransac_params* params, bool needs_subsampling,
+                 const char* noun) {
+  ACEZ_REQUIRE(n_frames > 0 && n_frames <= ctx->max_frames, "n_frames exceeds the context's max_frames");
+  ACEZ_REQUIRE(h > 0 && w > 0 && h <= ctx->max_h && w <= ctx->max_w, "frame larger than the context was created for");
+  if ((int64_t)h * w > MAX_CELLS) {
+    acez::set_error("invalid argument: at most 16384 %s per frame", noun);
+    return ACEZ_ERR_INVALID;
+  }
+  ACEZ_REQUIRE(params->hypotheses > 0 && params->max_tries > 0, "hypotheses and max_tries must be positive");
+  if (needs_subsampling)
+    ACEZ_REQUIRE(params->subsampling > 0 && params->inlier_threshold > 0.f, "subsampling and inlier_threshold must be positive");
+  else
+    ACEZ_REQUIRE(params->inlier_threshold > 0.f, "inlier_threshold must be positive");
+  return ACEZ_OK;
 }
 
 int plan_launch(Workspace& ws, int h, int w, int hyps, int list_floats_per_cell, size_t (*lds_bytes)(int, int, bool), Geometry* g) {
@@ -934,6 +964,13 @@ int upload_strided(float* d_dst, const float* h_src, int64_t stride_c, int64_t s
   return ACEZ_OK;
 }
 
+// upload_strided's counterpart: adds a packed [3][h][w] gradient to the caller's strided host tensor
+static void add_strided(float* h_dst, int64_t stride_c, int64_t stride_h, int64_t stride_w, const float* packed, int h, int w) {
+  for (int c = 0; c < 3; ++c)
+    for (int y = 0; y < h; ++y)
+      for (int x = 0; x < w; ++x) h_dst[c * stride_c + y * stride_h + x * stride_w] += packed[((size_t)c * h + y) * w + x];
+}
+
 int download_result(const acez_ransac* ctx, int h, int w, float* h_out_pose16, int32_t* out_inliers, uint8_t* h_out_mask) {
   ACEZ_HIP_CHECK(hipMemcpy(h_out_pose16, ctx->d_pose, 16 * sizeof(float), hipMemcpyDeviceToHost));
   ACEZ_HIP_CHECK(hipMemcpy(out_inliers, ctx->d_inl, sizeof(int), hipMemcpyDeviceToHost));
@@ -947,7 +984,7 @@ int debug_fetch(const acez_ransac* ctx, const Workspace& ws, int n_frames, int h
   ACEZ_HIP_CHECK(hipSetDevice(ctx->device));
   ACEZ_HIP_CHECK(hipDeviceSynchronize());
   const size_t nh = (size_t)n_frames * hypotheses;
-  if (h_samples) ACEZ_HIP_CHECK(hipMemcpy(h_samples, ws.d_samples, nh * 3 * sizeof(int), hipMemcpyDeviceToHost));
+  if (h_samples) ACEZ_HIP_CHECK(hipMemcpy(h_samples, ws.d_samples, nh * ws.sample_width * sizeof(int), hipMemcpyDeviceToHost));
   if (h_hyp_poses) ACEZ_HIP_CHECK(hipMemcpy(h_hyp_poses, ws.d_hyp_poses, nh * 6 * sizeof(double), hipMemcpyDeviceToHost));
   if (h_scores) ACEZ_HIP_CHECK(hipMemcpy(h_scores, ws.d_scores, nh * sizeof(double), hipMemcpyDeviceToHost));
   if (h_best) ACEZ_HIP_CHECK(hipMemcpy(h_best, ws.d_best, (size_t)n_frames * sizeof(int), hipMemcpyDeviceToHost));
@@ -955,7 +992,51 @@ int debug_fetch(const acez_ransac* ctx, const Workspace& ws, int n_frames, int h
   return ACEZ_OK;
 }
 
+int backward_host(GradWorkspace& g, int h, int w, const float* h_gt_pose16, float* h_grad, int64_t g_stride_c, int64_t g_stride_h,
+                  int64_t g_stride_w, double* out_loss, const std::function<int(const float*, float*, double*)>& launch) {
+  const size_t cells = (size_t)h * w;
+  ACEZ_HIP_CHECK(hipMemcpy(g.d_gt, h_gt_pose16, 16 * sizeof(float), hipMemcpyHostToDevice));
+  ACEZ_HIP_CHECK(hipMemset(g.d_grad, 0, 3 * cells * sizeof(float)));
+  const int rc = launch(g.d_gt, g.d_grad, g.d_loss);
+  if (rc != ACEZ_OK) return rc;
+  std::vector<float> grad(3 * cells);
+  ACEZ_HIP_CHECK(hipMemcpy(grad.data(), g.d_grad, grad.size() * sizeof(float), hipMemcpyDeviceToHost));
+  ACEZ_HIP_CHECK(hipMemcpy(out_loss, g.d_loss, sizeof(double), hipMemcpyDeviceToHost));
+  add_strided(h_grad, g_stride_c, g_stride_h, g_stride_w, grad.data(), h, w);
+  return ACEZ_OK;
+}
+
+int grad_debug_fetch(const acez_ransac* ctx, const GradWorkspace& g, int n_frames, int hypotheses, int h, int w, int32_t* h_samples,
+                     double* h_hyp_poses, double* h_scores, double* h_probs, double* h_losses, double* h_ref_poses,
+                     uint64_t* h_mask_words, double* h_entropy) {
+  ACEZ_REQUIRE(h * w == g.last_cells, "shape does not match the last call");
+  int rc = debug_fetch(ctx, g.ws, n_frames, hypotheses, h_samples, h_hyp_poses, h_scores, nullptr, nullptr);
+  if (rc != ACEZ_OK) return rc;
+  const size_t nh = (size_t)n_frames * hypotheses;
+  if (h_probs) ACEZ_HIP_CHECK(hipMemcpy(h_probs, g.d_probs, nh * sizeof(double), hipMemcpyDeviceToHost));
+  if (h_losses) ACEZ_HIP_CHECK(hipMemcpy(h_losses, g.d_losses, nh * sizeof(double), hipMemcpyDeviceToHost));
+  if (h_ref_poses) ACEZ_HIP_CHECK(hipMemcpy(h_ref_poses, g.d_ref_poses, nh * 6 * sizeof(double), hipMemcpyDeviceToHost));
+  if (h_mask_words)
+    ACEZ_HIP_CHECK(hipMemcpy(h_mask_words, g.d_masks, nh * mask_words(g, h * w) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (h_entropy) ACEZ_HIP_CHECK(hipMemcpy(h_entropy, g.d_entropy, (size_t)n_frames * sizeof(double), hipMemcpyDeviceToHost));
+  return ACEZ_OK;
+}
+
 }  // namespace acez_rs
+
+namespace {
+// The forward fields of the kernel's arguments (the backward fields stay zero).
+RansacArgs make_args(const float* d_scene_coords, const acez_rs::ParamSlot& slot, const acez_rs::Workspace& ws, const acez_rs::Geometry& g,
+                     int h, int w, const acez_ransac_params* params, uint64_t seed) {
+  RansacArgs a{};
+  a.sc = d_scene_coords; a.fp = slot.d; a.big = ws.d_list; a.H = h; a.W = w; a.N = g.N; a.hyps = params->hypotheses;
+  a.h_magic = g.h_magic;
+  a.max_tries = params->max_tries; a.sub = params->subsampling; a.max_ref_steps = params->max_ref_steps;
+  a.thr = params->inlier_threshold; a.alpha = params->inlier_alpha; a.max_reproj = params->max_reproj; a.seed = seed;
+  a.hyp_poses = ws.d_hyp_poses; a.scores = ws.d_scores; a.best = ws.d_best; a.refined = ws.d_refined;
+  return a;
+}
+}  // namespace
 
 // ====================================================================================================
 // C ABI
@@ -1001,6 +1082,10 @@ extern "C" int acez_ransac_create(acez_ransac** out, int max_frames, int max_h, 
   ctx->max_h = max_h;
   ctx->max_w = max_w;
   ctx->rgb.frames = ctx->rgbd.frames = ctx->rgbd_grad.ws.frames = ctx->rgb_grad.ws.frames = max_frames;
+  ctx->rgbd.sample_width = ctx->rgbd_grad.ws.sample_width = 3;   // the RGB-D triple
+  ctx->rgb_grad.ws.sample_width = 4;                             // the P3P minimal set
+  ctx->rgb_grad.row_words = acez_rs::RGB_THREADS / 64;
+  ctx->rgbd_grad.row_words = acez_rs::RGBD_THREADS / 64;
   int rc = ACEZ_OK;
   auto A = [&](void** p, size_t bytes) {
     if (rc == ACEZ_OK && hipMalloc(p, bytes) != hipSuccess) {
@@ -1020,7 +1105,7 @@ extern "C" int acez_ransac_create(acez_ransac** out, int max_frames, int max_h, 
   A((void**)&ctx->d_pose, 16 * sizeof(float));
   A((void**)&ctx->d_inl, sizeof(int));
   A((void**)&ctx->d_mask, (size_t)max_h * max_w);
-  if (rc == ACEZ_OK) rc = acez_rs::ensure_hyps(ctx->rgb, 64, false);
+  if (rc == ACEZ_OK) rc = acez_rs::ensure_hyps(ctx->rgb, 64);
   if (rc != ACEZ_OK) {
     acez_ransac_destroy(ctx);
     return rc;
@@ -1034,26 +1119,18 @@ extern "C" int acez_register_rgb_device(acez_ransac* ctx, const float* d_scene_c
                                         const uint64_t* h_frame_ids, float* d_out_poses, int32_t* d_out_inliers,
                                         uint8_t* d_out_masks, void* stream) {
   ACEZ_REQUIRE(ctx && d_scene_coords && params && h_intrinsics && d_out_poses && d_out_inliers, "null pointer");
-  ACEZ_REQUIRE(n_frames > 0 && n_frames <= ctx->max_frames, "n_frames exceeds the context's max_frames");
-  ACEZ_REQUIRE(h > 0 && w > 0 && h <= ctx->max_h && w <= ctx->max_w, "frame larger than the context was created for");
-  ACEZ_REQUIRE((int64_t)h * w <= 256 * MAX_ROWS, "at most 16384 scene coordinates per frame");
-  ACEZ_REQUIRE(params->hypotheses > 0 && params->max_tries > 0, "hypotheses and max_tries must be positive");
-  ACEZ_REQUIRE(params->subsampling > 0 && params->inlier_threshold > 0.f, "subsampling and inlier_threshold must be positive");
+  int rc = acez_rs::check_frames(ctx, n_frames, h, w, params, true, "scene coordinates");
+  if (rc != ACEZ_OK) return rc;
   ACEZ_HIP_CHECK(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
   acez_rs::Workspace& ws = ctx->rgb;
   acez_rs::Geometry g;
   acez_rs::ParamSlot* slot = nullptr;
-  int rc = acez_rs::ensure_hyps(ws, params->hypotheses, false);
+  rc = acez_rs::ensure_hyps(ws, params->hypotheses);
   if (rc == ACEZ_OK) rc = acez_rs::plan_launch(ws, h, w, params->hypotheses, 3, lds_bytes, &g);
   if (rc == ACEZ_OK) rc = acez_rs::stage_params(ctx, s, n_frames, h_intrinsics, h_frame_ids, &slot);
   if (rc != ACEZ_OK) return rc;
-  RansacArgs a;
-  a.sc = d_scene_coords; a.fp = slot->d; a.big = ws.d_list; a.H = h; a.W = w; a.N = g.N; a.hyps = params->hypotheses;
-  a.h_magic = g.h_magic;
-  a.max_tries = params->max_tries; a.sub = params->subsampling; a.max_ref_steps = params->max_ref_steps;
-  a.thr = params->inlier_threshold; a.alpha = params->inlier_alpha; a.max_reproj = params->max_reproj; a.seed = seed;
-  a.hyp_poses = ws.d_hyp_poses; a.scores = ws.d_scores; a.best = ws.d_best; a.refined = ws.d_refined;
+  RansacArgs a = make_args(d_scene_coords, *slot, ws, g, h, w, params, seed);
   a.out_poses = d_out_poses; a.out_inliers = d_out_inliers; a.out_masks = d_out_masks;
   rc = acez_rs::launch(ransac_kernel<true>, ransac_kernel<false>, g, n_frames, 256, s, a, *slot);
   if (rc == ACEZ_OK) ws.last_hyps = params->hypotheses;
@@ -1085,34 +1162,22 @@ extern "C" int acez_register_rgb_backward_device(acez_ransac* ctx, const float* 
                                                  float w_loss_rot, float w_loss_trans, float soft_clamp, uint64_t seed,
                                                  const uint64_t* h_frame_ids, float* d_out_grad, double* d_out_loss, void* stream) {
   ACEZ_REQUIRE(ctx && d_scene_coords && d_gt_poses && params && h_intrinsics && d_out_grad && d_out_loss, "null pointer");
-  ACEZ_REQUIRE(n_frames > 0 && n_frames <= ctx->max_frames, "n_frames exceeds the context's max_frames");
-  ACEZ_REQUIRE(h > 0 && w > 0 && h <= ctx->max_h && w <= ctx->max_w, "frame larger than the context was created for");
-  ACEZ_REQUIRE((int64_t)h * w <= 256 * MAX_ROWS, "at most 16384 scene coordinates per frame");
-  ACEZ_REQUIRE(params->hypotheses > 0 && params->max_tries > 0, "hypotheses and max_tries must be positive");
-  ACEZ_REQUIRE(params->subsampling > 0 && params->inlier_threshold > 0.f, "subsampling and inlier_threshold must be positive");
+  int rc = acez_rs::check_frames(ctx, n_frames, h, w, params, true, "scene coordinates");
+  if (rc != ACEZ_OK) return rc;
   ACEZ_HIP_CHECK(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
   acez_rs::GradWorkspace& gw = ctx->rgb_grad;
   acez_rs::Geometry g;
   acez_rs::ParamSlot* slot = nullptr;
-  int rc = acez_rs::ensure_grad(gw, params->hypotheses, h * w);
+  rc = acez_rs::ensure_grad(gw, params->hypotheses, h * w);
   if (rc == ACEZ_OK) rc = acez_rs::plan_launch(gw.ws, h, w, params->hypotheses, 3, grad_lds_bytes, &g);
   if (rc == ACEZ_OK) rc = acez_rs::stage_params(ctx, s, n_frames, h_intrinsics, h_frame_ids, &slot);
   if (rc != ACEZ_OK) return rc;
-  RansacArgs a{};
-  a.sc = d_scene_coords; a.fp = slot->d; a.big = gw.ws.d_list; a.H = h; a.W = w; a.N = g.N; a.hyps = params->hypotheses;
-  a.h_magic = g.h_magic;
-  a.max_tries = params->max_tries; a.sub = params->subsampling; a.max_ref_steps = params->max_ref_steps;
-  a.thr = params->inlier_threshold; a.alpha = params->inlier_alpha; a.max_reproj = params->max_reproj; a.seed = seed;
-  a.hyp_poses = gw.ws.d_hyp_poses; a.scores = gw.ws.d_scores; a.best = gw.ws.d_best; a.refined = gw.ws.d_refined;
-  a.samples = gw.ws.d_samples; a.gt = d_gt_poses; a.w_rot = w_loss_rot; a.w_trans = w_loss_trans; a.cut = soft_clamp;
-  a.probs = gw.d_probs; a.losses = gw.d_losses; a.ref_poses = gw.d_ref_poses; a.masks = gw.d_masks; a.mwords = rgb_mask_words(h * w);
-  a.gacc = gw.d_gacc; a.entropy = gw.d_entropy; a.out_grad = d_out_grad; a.out_loss = d_out_loss;
+  RansacArgs a = make_args(d_scene_coords, *slot, gw.ws, g, h, w, params, seed);
+  a.samples = gw.ws.d_samples;
+  a.grad = acez_rs::make_grad_out(gw, h * w, d_gt_poses, w_loss_rot, w_loss_trans, soft_clamp, d_out_grad, d_out_loss);
   rc = acez_rs::launch(ransac_kernel<true, true>, ransac_kernel<false, true>, g, n_frames, 256, s, a, *slot);
-  if (rc == ACEZ_OK) {
-    gw.last_hyps = gw.ws.last_hyps = params->hypotheses;
-    gw.last_cells = h * w;
-  }
+  if (rc == ACEZ_OK) acez_rs::note_launch(gw, params->hypotheses, h * w);
   return rc;
 }
 
@@ -1128,36 +1193,17 @@ extern "C" int acez_register_rgb_backward_host(acez_ransac* ctx, const float* h_
   int rc = acez_rs::ensure_grad(gw, params->hypotheses, h * w);
   if (rc == ACEZ_OK) rc = acez_rs::upload_strided(ctx->d_sc, h_scene_coords, stride_c, stride_h, stride_w, h, w);
   if (rc != ACEZ_OK) return rc;
-  const size_t cells = (size_t)h * w;
-  ACEZ_HIP_CHECK(hipMemcpy(gw.d_gt, h_gt_pose16, 16 * sizeof(float), hipMemcpyHostToDevice));
-  ACEZ_HIP_CHECK(hipMemset(gw.d_grad, 0, 3 * cells * sizeof(float)));
-  rc = acez_register_rgb_backward_device(ctx, ctx->d_sc, gw.d_gt, 1, h, w, params, intr, w_loss_rot, w_loss_trans, soft_clamp, seed,
-                                         &frame_id, gw.d_grad, gw.d_loss, nullptr);
-  if (rc != ACEZ_OK) return rc;
-  std::vector<float> grad(3 * cells);
-  ACEZ_HIP_CHECK(hipMemcpy(grad.data(), gw.d_grad, grad.size() * sizeof(float), hipMemcpyDeviceToHost));
-  ACEZ_HIP_CHECK(hipMemcpy(out_loss, gw.d_loss, sizeof(double), hipMemcpyDeviceToHost));
-  for (int c = 0; c < 3; ++c)
-    for (int y = 0; y < h; ++y)
-      for (int x = 0; x < w; ++x) h_grad[c * g_stride_c + y * g_stride_h + x * g_stride_w] += grad[((size_t)c * h + y) * w + x];
-  return ACEZ_OK;
+  auto launch = [&](const float* d_gt, float* d_grad, double* d_loss) {
+    return acez_register_rgb_backward_device(ctx, ctx->d_sc, d_gt, 1, h, w, params, intr, w_loss_rot, w_loss_trans, soft_clamp, seed,
+                                             &frame_id, d_grad, d_loss, nullptr);
+  };
+  return acez_rs::backward_host(gw, h, w, h_gt_pose16, h_grad, g_stride_c, g_stride_h, g_stride_w, out_loss, launch);
 }
 
 extern "C" int acez_ransac_rgb_backward_debug_fetch(acez_ransac* ctx, int n_frames, int hypotheses, int h, int w, int32_t* h_samples,
                                                     double* h_hyp_poses, double* h_scores, double* h_probs, double* h_losses,
                                                     double* h_ref_poses, uint64_t* h_mask_words, double* h_entropy) {
   ACEZ_REQUIRE(ctx && ctx->rgb_grad.ws.d_best, "no RGB backward call on this context");
-  acez_rs::GradWorkspace& gw = ctx->rgb_grad;
-  ACEZ_REQUIRE(h * w == gw.last_cells, "shape does not match the last call");
-  int rc = acez_rs::debug_fetch(ctx, gw.ws, n_frames, hypotheses, nullptr, h_hyp_poses, h_scores, nullptr, nullptr);
-  if (rc != ACEZ_OK) return rc;
-  const size_t nh = (size_t)n_frames * hypotheses;
-  if (h_samples) ACEZ_HIP_CHECK(hipMemcpy(h_samples, gw.ws.d_samples, nh * 4 * sizeof(int), hipMemcpyDeviceToHost));
-  if (h_probs) ACEZ_HIP_CHECK(hipMemcpy(h_probs, gw.d_probs, nh * sizeof(double), hipMemcpyDeviceToHost));
-  if (h_losses) ACEZ_HIP_CHECK(hipMemcpy(h_losses, gw.d_losses, nh * sizeof(double), hipMemcpyDeviceToHost));
-  if (h_ref_poses) ACEZ_HIP_CHECK(hipMemcpy(h_ref_poses, gw.d_ref_poses, nh * 6 * sizeof(double), hipMemcpyDeviceToHost));
-  if (h_mask_words)
-    ACEZ_HIP_CHECK(hipMemcpy(h_mask_words, gw.d_masks, nh * rgb_mask_words(h * w) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  if (h_entropy) ACEZ_HIP_CHECK(hipMemcpy(h_entropy, gw.d_entropy, (size_t)n_frames * sizeof(double), hipMemcpyDeviceToHost));
-  return ACEZ_OK;
+  return acez_rs::grad_debug_fetch(ctx, ctx->rgb_grad, n_frames, hypotheses, h, w, h_samples, h_hyp_poses, h_scores, h_probs, h_losses,
+                                   h_ref_poses, h_mask_words, h_entropy);
 }

@@ -33,7 +33,6 @@
 #include "ransac_ctx.h"
 #include "ransac_rgbd.h"
 #include "ransac_loss.h"
-#include <vector>
 
 namespace {
 
@@ -42,20 +41,9 @@ using namespace acez_loss;
 
 struct GradArgs {
   RgbdIn in;
-  const float* gt;             // [n][16] row-major cam->world ground truth
-  float w_rot, w_trans, cut;
-  double* probs;               // [n][hyps]
-  double* losses;              // [n][hyps]
-  double* ref_poses;           // [n][hyps][6]
-  unsigned long long* masks;   // [n][hyps][mwords]: bit j % 64 of word j / 64 = valid-list entry j
-  int mwords;
-  double* gacc;                // [n][3][N]
-  double* entropy;             // [n]
-  float* out_grad;             // [n][3][H][W], added to
-  double* out_loss;            // [n]
+  acez_rs::GradOut grad;   // the masks are over the valid list
 };
 
-__host__ __device__ inline int mask_words(int N) { return ((N + THREADS - 1) / THREADS) * WAVES; }
 __host__ __device__ inline size_t tail_bytes(int hyps) { return 8 * (size_t)(8 * hyps + 16); }
 __host__ __device__ inline size_t lds_bytes(int Npad, int hyps, bool lists_in_hbm) {
   return (lists_in_hbm ? 0 : 26 * (size_t)Npad) + ((region_bytes(hyps) + 7) & ~(size_t)7) + tail_bytes(hyps);
@@ -141,12 +129,12 @@ __global__ __launch_bounds__(THREADS, 1) void rgbd_grad_kernel(GradArgs a) {
   double* sHand = sRef + 6 * hyps;                      // [16] lane 0 -> workgroup
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint64_t frame_id = in.fp[frame].frame_id;
-  const float* G = a.gt + (size_t)frame * 16;
-  double* gacc = a.gacc + (size_t)frame * 3 * N;
-  unsigned long long* mw = a.masks + (size_t)frame * hyps * a.mwords;
+  const acez_rs::GradOut& go = a.grad;
+  const float* G = go.gt + (size_t)frame * 16;
+  double* gacc = go.gacc + (size_t)frame * 3 * N;
+  unsigned long long* mw = go.masks + (size_t)frame * hyps * go.mwords;
 
-  for (int m = tid; m < N; m += THREADS) gacc[m] = gacc[N + m] = gacc[2 * N + m] = 0.0;
-  for (int i = tid; i < hyps * a.mwords; i += THREADS) mw[i] = 0ull;
+  zero_frame(gacc, N, mw, hyps * go.mwords, tid, THREADS);
   compact_valid(in, f, frame, nullptr);
   const int nv = f.nv;
   const int vrows = (nv + THREADS - 1) / THREADS;
@@ -154,43 +142,27 @@ __global__ __launch_bounds__(THREADS, 1) void rgbd_grad_kernel(GradArgs a) {
   if (nv < 3) {   // as the forward kernel: zero poses, equal scores, no gradient
     for (int h = tid; h < hyps; h += THREADS) {
       const size_t o = (size_t)frame * hyps + h;
-      for (int i = 0; i < 6; ++i) in.hyp_poses[o * 6 + i] = a.ref_poses[o * 6 + i] = 0.0;
+      for (int i = 0; i < 6; ++i) in.hyp_poses[o * 6 + i] = go.ref_poses[o * 6 + i] = 0.0;
       for (int i = 0; i < 3; ++i) in.samples[o * 3 + i] = -1;
       in.scores[o] = 0.0;
     }
     if (tid == 0) {
       const double zero[6] = {0, 0, 0, 0, 0, 0};
-      const double L = pose_loss(zero, G, a.w_rot, a.w_trans, a.cut, nullptr);
+      const double L = pose_loss(zero, G, go.w_rot, go.w_trans, go.cut, nullptr);
       for (int h = 0; h < hyps; ++h) {
-        a.probs[(size_t)frame * hyps + h] = 1.0 / hyps;
-        a.losses[(size_t)frame * hyps + h] = L;
+        go.probs[(size_t)frame * hyps + h] = 1.0 / hyps;
+        go.losses[(size_t)frame * hyps + h] = L;
       }
-      a.entropy[frame] = log2((double)hyps);
-      a.out_loss[frame] = L;
+      go.entropy[frame] = log2((double)hyps);
+      go.out_loss[frame] = L;
     }
     return;
   }
   sample_hyps(in, f, frame_id);
   score_hyps(in, f, frame);
 
-  // ---- soft-max and entropy (dsacstar::softMax, dsacstar::entropy)
-  if (tid == 0) {
-    double maxScore = 0;
-    for (int i = 0; i < hyps; i++)
-      if (i == 0 || f.sScores[i] > maxScore) maxScore = f.sScores[i];
-    double sum = 0.0;
-    for (int i = 0; i < hyps; i++) {
-      sProb[i] = detm::exp_(f.sScores[i] - maxScore);
-      sum += sProb[i];
-    }
-    double ent = 0.0;
-    for (int i = 0; i < hyps; i++) {
-      sProb[i] /= sum;
-      a.probs[(size_t)frame * hyps + i] = sProb[i];
-      if (sProb[i] > 0) ent -= sProb[i] * log2(sProb[i]);
-    }
-    a.entropy[frame] = ent;
-  }
+  // ---- soft-max and entropy
+  if (tid == 0) softmax_entropy(f.sScores, hyps, sProb, go.probs + (size_t)frame * hyps, go.entropy + frame);
   __syncthreads();
 
   // ---- refine, loss, path I: hypothesis by hypothesis
@@ -204,16 +176,16 @@ __global__ __launch_bounds__(THREADS, 1) void rgbd_grad_kernel(GradArgs a) {
     if (active && rf.have_map) {
       for (int k = 0; k < vrows; ++k) {
         const unsigned long long bits = __ballot((rf.acc_flags >> k) & 1u);
-        if (lane == 0) mw[(size_t)h * a.mwords + k * WAVES + wave] = bits;
+        if (lane == 0) mw[(size_t)h * go.mwords + k * WAVES + wave] = bits;
       }
     }
     double g6[6];
-    const double L = pose_loss(param, G, a.w_rot, a.w_trans, a.cut, active ? g6 : nullptr);
+    const double L = pose_loss(param, G, go.w_rot, go.w_trans, go.cut, active ? g6 : nullptr);
     if (tid == 0) {
       sLoss[h] = L;
       const size_t o = (size_t)frame * hyps + h;
-      a.losses[o] = L;
-      for (int i = 0; i < 6; ++i) a.ref_poses[o * 6 + i] = sRef[h * 6 + i] = param[i];
+      go.losses[o] = L;
+      for (int i = 0; i < 6; ++i) go.ref_poses[o * 6 + i] = sRef[h * 6 + i] = param[i];
     }
     if (!(active && rf.have_map)) continue;
 
@@ -293,10 +265,9 @@ __global__ __launch_bounds__(THREADS, 1) void rgbd_grad_kernel(GradArgs a) {
 
   // ---- the expected loss
   if (tid == 0) {
-    double E = 0;
-    for (int h = 0; h < hyps; ++h) E += sProb[h] * sLoss[h];
+    const double E = expected_loss(sProb, sLoss, hyps);
     sHand[0] = E;
-    a.out_loss[frame] = E;
+    go.out_loss[frame] = E;
   }
   __syncthreads();
   const double E = sHand[0];
@@ -366,64 +337,17 @@ __global__ __launch_bounds__(THREADS, 1) void rgbd_grad_kernel(GradArgs a) {
             for (int q = 0; q < 6; ++q) mx = fmax(mx, fabs(cols[i * 3 + c][q]));
           }
         }
-        if (ok && !(mx > 10)) {   // dScoreRGBD: a Jacobian entry above 10 zeroes the support term
-          for (int i = 0; i < 3; ++i)
-            for (int c = 0; c < 3; ++c) {
-              double v = 0;
-              for (int q = 0; q < 6; ++q) v += s6[q] * cols[i * 3 + c][q];
-              gacc[c * N + ms[i]] += v;
-            }
-        }
+        if (ok && !(mx > 10)) scatter_support(gacc, N, ms, s6, cols);   // dScoreRGBD: an entry above 10 zeroes the support term
       }
     }
     __syncthreads();
   }
 
   // ---- the caller's gradient (+=)
-  float* og = a.out_grad + (size_t)frame * 3 * N;
-  for (int i = tid; i < 3 * N; i += THREADS) og[i] += (float)gacc[i];
+  flush_grad(go.out_grad + (size_t)frame * 3 * N, gacc, N, tid, THREADS);
 }
 
 }  // namespace
-
-namespace acez_rs {
-int ensure_grad(GradWorkspace& g, int hyps, int cells) {
-  int rc = ensure_hyps(g.ws, hyps, true);
-  if (rc != ACEZ_OK) return rc;
-  const int frames = g.ws.frames, mw = mask_words(cells);
-  if (!g.d_entropy) {
-    ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_entropy, (size_t)frames * sizeof(double)));
-    ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_loss, (size_t)frames * sizeof(double)));
-    ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_gt, (size_t)frames * 16 * sizeof(float)));
-  }
-  if (hyps <= g.hyps && cells <= g.cells && mw <= g.mwords) return ACEZ_OK;
-  ACEZ_HIP_CHECK(hipDeviceSynchronize());   // earlier launches may still write the old buffers
-  for (void* p : {(void*)g.d_probs, (void*)g.d_losses, (void*)g.d_ref_poses, (void*)g.d_masks, (void*)g.d_gacc, (void*)g.d_grad})
-    if (p) (void)hipFree(p);
-  g.d_probs = g.d_losses = g.d_ref_poses = g.d_gacc = nullptr;
-  g.d_masks = nullptr;
-  g.d_grad = nullptr;
-  g.hyps = g.cells = g.mwords = 0;
-  const int H = hyps > g.ws.hyps ? hyps : g.ws.hyps;
-  ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_probs, (size_t)frames * H * sizeof(double)));
-  ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_losses, (size_t)frames * H * sizeof(double)));
-  ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_ref_poses, (size_t)frames * H * 6 * sizeof(double)));
-  ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_masks, (size_t)frames * H * mw * sizeof(unsigned long long)));
-  ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_gacc, (size_t)frames * 3 * cells * sizeof(double)));
-  ACEZ_HIP_CHECK(hipMalloc((void**)&g.d_grad, (size_t)3 * cells * sizeof(float)));
-  g.hyps = H; g.cells = cells; g.mwords = mw;
-  return ACEZ_OK;
-}
-
-
-void release_grad(GradWorkspace& g) {
-  release(g.ws);
-  for (void* p : {(void*)g.d_probs, (void*)g.d_losses, (void*)g.d_ref_poses, (void*)g.d_masks, (void*)g.d_gacc, (void*)g.d_entropy,
-                  (void*)g.d_gt, (void*)g.d_grad, (void*)g.d_loss})
-    if (p) (void)hipFree(p);
-  g = GradWorkspace();
-}
-}  // namespace acez_rs
 
 // ====================================================================================================
 // C ABI
@@ -433,30 +357,21 @@ extern "C" int acez_register_rgbd_backward_device(acez_ransac* ctx, const float*
                                                   float w_loss_rot, float w_loss_trans, float soft_clamp, uint64_t seed,
                                                   const uint64_t* h_frame_ids, float* d_out_grad, double* d_out_loss, void* stream) {
   ACEZ_REQUIRE(ctx && d_scene_coords && d_camera_coords && d_gt_poses && params && d_out_grad && d_out_loss, "null pointer");
-  ACEZ_REQUIRE(n_frames > 0 && n_frames <= ctx->max_frames, "n_frames exceeds the context's max_frames");
-  ACEZ_REQUIRE(h > 0 && w > 0 && h <= ctx->max_h && w <= ctx->max_w, "frame larger than the context was created for");
-  ACEZ_REQUIRE((int64_t)h * w <= THREADS * MAX_ROWS, "at most 16384 cells per frame");
-  ACEZ_REQUIRE(params->hypotheses > 0 && params->max_tries > 0, "hypotheses and max_tries must be positive");
-  ACEZ_REQUIRE(params->inlier_threshold > 0.f, "inlier_threshold must be positive");
+  int rc = acez_rs::check_frames(ctx, n_frames, h, w, params, false, "cells");
+  if (rc != ACEZ_OK) return rc;
   ACEZ_HIP_CHECK(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
   acez_rs::GradWorkspace& gw = ctx->rgbd_grad;
   acez_rs::Geometry g;
   acez_rs::ParamSlot* slot = nullptr;
-  int rc = acez_rs::ensure_grad(gw, params->hypotheses, h * w);
+  rc = acez_rs::ensure_grad(gw, params->hypotheses, h * w);
   if (rc == ACEZ_OK) rc = acez_rs::plan_launch(gw.ws, h, w, params->hypotheses, 7, lds_bytes, &g);
   if (rc == ACEZ_OK) rc = acez_rs::stage_params(ctx, s, n_frames, nullptr, h_frame_ids, &slot);
   if (rc != ACEZ_OK) return rc;
-  GradArgs a;
-  a.in = acez_rgbd::make_in(d_scene_coords, d_camera_coords, slot->d, gw.ws, g, h, w, params, seed);
-  a.gt = d_gt_poses; a.w_rot = w_loss_rot; a.w_trans = w_loss_trans; a.cut = soft_clamp;
-  a.probs = gw.d_probs; a.losses = gw.d_losses; a.ref_poses = gw.d_ref_poses; a.masks = gw.d_masks; a.mwords = mask_words(h * w);
-  a.gacc = gw.d_gacc; a.entropy = gw.d_entropy; a.out_grad = d_out_grad; a.out_loss = d_out_loss;
+  const GradArgs a{acez_rgbd::make_in(d_scene_coords, d_camera_coords, slot->d, gw.ws, g, h, w, params, seed),
+                   acez_rs::make_grad_out(gw, h * w, d_gt_poses, w_loss_rot, w_loss_trans, soft_clamp, d_out_grad, d_out_loss)};
   rc = acez_rs::launch(rgbd_grad_kernel<true>, rgbd_grad_kernel<false>, g, n_frames, THREADS, s, a, *slot);
-  if (rc == ACEZ_OK) {
-    gw.last_hyps = gw.ws.last_hyps = params->hypotheses;
-    gw.last_cells = h * w;
-  }
+  if (rc == ACEZ_OK) acez_rs::note_launch(gw, params->hypotheses, h * w);
   return rc;
 }
 
@@ -475,35 +390,17 @@ extern "C" int acez_register_rgbd_backward_host(acez_ransac* ctx, const float* h
   if (rc == ACEZ_OK) rc = acez_rs::upload_strided(ctx->d_sc, h_scene_coords, sc_stride_c, sc_stride_h, sc_stride_w, h, w);
   if (rc == ACEZ_OK) rc = acez_rs::upload_strided(ctx->d_cc, h_camera_coords, cc_stride_c, cc_stride_h, cc_stride_w, h, w);
   if (rc != ACEZ_OK) return rc;
-  const size_t cells = (size_t)h * w;
-  ACEZ_HIP_CHECK(hipMemcpy(gw.d_gt, h_gt_pose16, 16 * sizeof(float), hipMemcpyHostToDevice));
-  ACEZ_HIP_CHECK(hipMemset(gw.d_grad, 0, 3 * cells * sizeof(float)));
-  rc = acez_register_rgbd_backward_device(ctx, ctx->d_sc, ctx->d_cc, gw.d_gt, 1, h, w, params, w_loss_rot, w_loss_trans, soft_clamp,
-                                          seed, &frame_id, gw.d_grad, gw.d_loss, nullptr);
-  if (rc != ACEZ_OK) return rc;
-  std::vector<float> grad(3 * cells);
-  ACEZ_HIP_CHECK(hipMemcpy(grad.data(), gw.d_grad, grad.size() * sizeof(float), hipMemcpyDeviceToHost));
-  ACEZ_HIP_CHECK(hipMemcpy(out_loss, gw.d_loss, sizeof(double), hipMemcpyDeviceToHost));
-  for (int c = 0; c < 3; ++c)
-    for (int y = 0; y < h; ++y)
-      for (int x = 0; x < w; ++x) h_grad[c * g_stride_c + y * g_stride_h + x * g_stride_w] += grad[((size_t)c * h + y) * w + x];
-  return ACEZ_OK;
+  auto launch = [&](const float* d_gt, float* d_grad, double* d_loss) {
+    return acez_register_rgbd_backward_device(ctx, ctx->d_sc, ctx->d_cc, d_gt, 1, h, w, params, w_loss_rot, w_loss_trans, soft_clamp,
+                                              seed, &frame_id, d_grad, d_loss, nullptr);
+  };
+  return acez_rs::backward_host(gw, h, w, h_gt_pose16, h_grad, g_stride_c, g_stride_h, g_stride_w, out_loss, launch);
 }
 
 extern "C" int acez_ransac_rgbd_backward_debug_fetch(acez_ransac* ctx, int n_frames, int hypotheses, int h, int w, int32_t* h_samples,
                                                      double* h_hyp_poses, double* h_scores, double* h_probs, double* h_losses,
                                                      double* h_ref_poses, uint64_t* h_mask_words, double* h_entropy) {
   ACEZ_REQUIRE(ctx && ctx->rgbd_grad.ws.d_best, "no RGB-D backward call on this context");
-  acez_rs::GradWorkspace& gw = ctx->rgbd_grad;
-  ACEZ_REQUIRE(h * w == gw.last_cells, "shape does not match the last call");
-  int rc = acez_rs::debug_fetch(ctx, gw.ws, n_frames, hypotheses, h_samples, h_hyp_poses, h_scores, nullptr, nullptr);
-  if (rc != ACEZ_OK) return rc;
-  const size_t nh = (size_t)n_frames * hypotheses;
-  if (h_probs) ACEZ_HIP_CHECK(hipMemcpy(h_probs, gw.d_probs, nh * sizeof(double), hipMemcpyDeviceToHost));
-  if (h_losses) ACEZ_HIP_CHECK(hipMemcpy(h_losses, gw.d_losses, nh * sizeof(double), hipMemcpyDeviceToHost));
-  if (h_ref_poses) ACEZ_HIP_CHECK(hipMemcpy(h_ref_poses, gw.d_ref_poses, nh * 6 * sizeof(double), hipMemcpyDeviceToHost));
-  if (h_mask_words)
-    ACEZ_HIP_CHECK(hipMemcpy(h_mask_words, gw.d_masks, nh * mask_words(h * w) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  if (h_entropy) ACEZ_HIP_CHECK(hipMemcpy(h_entropy, gw.d_entropy, (size_t)n_frames * sizeof(double), hipMemcpyDeviceToHost));
-  return ACEZ_OK;
+  return acez_rs::grad_debug_fetch(ctx, ctx->rgbd_grad, n_frames, hypotheses, h, w, h_samples, h_hyp_poses, h_scores, h_probs, h_losses,
+                                   h_ref_poses, h_mask_words, h_entropy);
 }

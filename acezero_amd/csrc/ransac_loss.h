@@ -1,5 +1,6 @@
-// ransac_loss.h -- the DSAC* pose loss (dsacstar_loss.h: loss, dLoss) and the small fp64 helpers both backward passes share
-// (ransac_api.hip for RGB, ransac_grad.hip for RGB-D). The including units are compiled with -ffp-contract=off.
+// ransac_loss.h -- the DSAC* pose loss (dsacstar_loss.h: loss, dLoss), the small fp64 helpers and the stages both backward kernels
+// share (ransac_api.hip for RGB, ransac_grad.hip for RGB-D): soft-max and entropy, the expected loss, the support-term scatter and
+// the zeroing / flushing of a frame's fp64 accumulator. The including units are compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ransac_math.h"
@@ -86,6 +87,56 @@ __device__ double pose_loss(const double prm[6], const float* G, float w_rot, fl
   if (!finite)
     for (int i = 0; i < 6; ++i) g[i] = 0.0;
   return L;
+}
+
+// ---- the stages of a backward kernel that do not depend on its kind
+
+// Zero the frame's fp64 accumulator gacc [3][N] and the mask words of all its hypotheses (every thread of the workgroup).
+__device__ __forceinline__ void zero_frame(double* gacc, int N, unsigned long long* mw, int words, int tid, int threads) {
+  for (int m = tid; m < N; m += threads) gacc[m] = gacc[N + m] = gacc[2 * N + m] = 0.0;
+  for (int i = tid; i < words; i += threads) mw[i] = 0ull;
+}
+
+// The caller's gradient og [3][N] += the accumulator, rounded once (every thread of the workgroup).
+__device__ __forceinline__ void flush_grad(float* og, const double* gacc, int N, int tid, int threads) {
+  for (int i = tid; i < 3 * N; i += threads) og[i] += (float)gacc[i];
+}
+
+// dsacstar::softMax and dsacstar::entropy of a frame's scores (one lane): p_h to sProb and probs_out, the entropy to *entropy_out.
+__device__ __forceinline__ void softmax_entropy(const double* scores, int hyps, double* sProb, double* probs_out, double* entropy_out) {
+  double maxScore = 0;
+  for (int i = 0; i < hyps; i++)
+    if (i == 0 || scores[i] > maxScore) maxScore = scores[i];
+  double sum = 0.0;
+  for (int i = 0; i < hyps; i++) {
+    sProb[i] = detm::exp_(scores[i] - maxScore);
+    sum += sProb[i];
+  }
+  double ent = 0.0;
+  for (int i = 0; i < hyps; i++) {
+    sProb[i] /= sum;
+    probs_out[i] = sProb[i];
+    if (sProb[i] > 0) ent -= sProb[i] * log2(sProb[i]);
+  }
+  *entropy_out = ent;
+}
+
+// E = sum_h p_h loss_h in index order (one lane)
+__device__ __forceinline__ double expected_loss(const double* sProb, const double* sLoss, int hyps) {
+  double E = 0;
+  for (int h = 0; h < hyps; ++h) E += sProb[h] * sLoss[h];
+  return E;
+}
+
+// The hypothesis' dependence on its minimal set (one lane): gacc[c][cells[i]] += sum_q S[q] cols[3 i + c][q] for the three
+// differentiated points i, S = d score-path / d hypothesis, cols = d hypothesis / d coordinate c of point i.
+__device__ __forceinline__ void scatter_support(double* gacc, int N, const int cells[3], const double S[6], const double (*cols)[6]) {
+  for (int i = 0; i < 3; ++i)
+    for (int c = 0; c < 3; ++c) {
+      double v = 0;
+      for (int q = 0; q < 6; ++q) v += S[q] * cols[i * 3 + c][q];
+      gacc[c * N + cells[i]] += v;
+    }
 }
 
 }  // namespace acez_loss

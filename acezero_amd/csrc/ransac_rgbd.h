@@ -10,9 +10,10 @@
 
 namespace acez_rgbd {
 
-constexpr int THREADS = 512;
+constexpr int THREADS = acez_rs::RGBD_THREADS;
 constexpr int WAVES = THREADS / 64;
 constexpr int MAX_ROWS = 32;          // valid-list entries per thread (flags in one 32-bit word): N <= 16384
+static_assert(THREADS * MAX_ROWS == acez_rs::MAX_CELLS, "check_frames' limit is this layout's");
 constexpr int RED_STRIDE = 16;        // doubles per wavefront in the reduction scratch
 
 // The inputs both kernels take.

@@ -124,17 +124,14 @@ extern "C" int acez_register_rgbd_device(acez_ransac* ctx, const float* d_scene_
                                          int w, const acez_ransac_params* params, uint64_t seed, const uint64_t* h_frame_ids,
                                          float* d_out_poses, int32_t* d_out_inliers, uint8_t* d_out_masks, void* stream) {
   ACEZ_REQUIRE(ctx && d_scene_coords && d_camera_coords && params && d_out_poses && d_out_inliers, "null pointer");
-  ACEZ_REQUIRE(n_frames > 0 && n_frames <= ctx->max_frames, "n_frames exceeds the context's max_frames");
-  ACEZ_REQUIRE(h > 0 && w > 0 && h <= ctx->max_h && w <= ctx->max_w, "frame larger than the context was created for");
-  ACEZ_REQUIRE((int64_t)h * w <= THREADS * MAX_ROWS, "at most 16384 cells per frame");
-  ACEZ_REQUIRE(params->hypotheses > 0 && params->max_tries > 0, "hypotheses and max_tries must be positive");
-  ACEZ_REQUIRE(params->inlier_threshold > 0.f, "inlier_threshold must be positive");
+  int rc = acez_rs::check_frames(ctx, n_frames, h, w, params, false, "cells");
+  if (rc != ACEZ_OK) return rc;
   ACEZ_HIP_CHECK(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
   acez_rs::Workspace& ws = ctx->rgbd;
   acez_rs::Geometry g;
   acez_rs::ParamSlot* slot = nullptr;
-  int rc = acez_rs::ensure_hyps(ws, params->hypotheses, true);
+  rc = acez_rs::ensure_hyps(ws, params->hypotheses);
   if (rc == ACEZ_OK) rc = acez_rs::plan_launch(ws, h, w, params->hypotheses, 7, lds_bytes, &g);
   if (rc == ACEZ_OK) rc = acez_rs::stage_params(ctx, s, n_frames, nullptr, h_frame_ids, &slot);
   if (rc != ACEZ_OK) return rc;

@@ -53,18 +53,48 @@ def _params(hyps, thr, alpha, max_reproj, sub, max_tries):
     return N.RansacParams(int(hyps), int(max_tries), float(thr), float(alpha), float(max_reproj), int(sub), MAX_REF_STEPS, 0)
 
 
-def _check_1x3(name, t):
-    if t.dim() != 4 or t.shape[0] != 1 or t.shape[1] != 3 or t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be a float32 tensor of shape 1x3xHxW")
+def _as_params(params, defaults=None):
+    """params as N.RansacParams: itself, or built from a dict of _params' arguments over `defaults`."""
+    return params if isinstance(params, N.RansacParams) else _params(**{**(defaults or {}), **params})
+
+
+def _intrinsics_array(intrinsics, n):
+    """n acez_intrinsics from a list of (focal, ppx, ppy) or N.Intrinsics."""
+    arr = (N.Intrinsics * n)()
+    for i, it in enumerate(intrinsics):
+        arr[i] = it if isinstance(it, N.Intrinsics) else N.Intrinsics(float(it[0]), float(it[1]), float(it[2]))
+    return arr
+
+
+def _check_1x3(**tensors):
+    """The tensor arguments of a single-frame entry, by name: each a float32 1x3xHxW, all of one shape."""
+    names = list(tensors)
+    for name, t in tensors.items():
+        if t.dim() != 4 or t.shape[0] != 1 or t.shape[1] != 3 or t.dtype != torch.float32:
+            raise RuntimeError(f"{name} must be a float32 tensor of shape 1x3xHxW")
+    if any(tuple(t.shape) != tuple(tensors[names[0]].shape) for t in tensors.values()):
+        raise RuntimeError(f"{', '.join(names[:-1])} and {names[-1]} must have the same shape")
+
+
+def _take_frame_ids(n):
+    """-> the next n values of the call counter all entries share."""
+    global _calls
+    _calls += n
+    return list(range(_calls - n, _calls))
 
 
 def _next_frame_id(name):
     """-> the frame id of this call (the shared counter), after checking that a GPU is visible."""
-    global _calls
     if not torch.cuda.is_available():
         raise RuntimeError(f"dsacstar.{name}: no GPU visible; the MI355X implementation has no CPU path")
-    _calls += 1
-    return _calls - 1
+    return _take_frame_ids(1)[0]
+
+
+def _check_batch(*tensors):
+    """The inputs of a batched entry: CUDA float32 [n,3,H,W] tensors of one shape on one device."""
+    for t in tensors:
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] == 3
+        assert tuple(t.shape) == tuple(tensors[0].shape) and t.device == tensors[0].device
 
 
 def _check_call(name, outPose):
@@ -122,7 +152,7 @@ def reset_call_counter(value=0):
 def forward_rgb(sceneCoordinates, outPose, ransacHypotheses, inlierThreshold, focalLength, ppointX, ppointY, inlierAlpha,
                 maxReproj, subSampling, randomSeed, max_hypotheses_tries):
     sc = sceneCoordinates
-    _check_1x3("sceneCoordinates", sc)
+    _check_1x3(sceneCoordinates=sc)
     frame_id = _check_call("forward_rgb", outPose)
     prm = _params(ransacHypotheses, inlierThreshold, inlierAlpha, maxReproj, subSampling, max_hypotheses_tries)
     intr = N.Intrinsics(float(focalLength), float(ppointX), float(ppointY))
@@ -146,14 +176,10 @@ def forward_rgb(sceneCoordinates, outPose, ransacHypotheses, inlierThreshold, fo
 def register_batch(scene_coords, intrinsics, params, seed, frame_ids=None, want_masks=True):
     """scene_coords: CUDA float32 [n,3,H,W]; intrinsics: list of (focal, ppx, ppy) or N.Intrinsics.
     Returns (poses [n,4,4] f32, inliers [n] i32, masks [n,H,W] u8 or None), all CUDA tensors; asynchronous."""
-    assert scene_coords.is_cuda and scene_coords.dtype == torch.float32 and scene_coords.dim() == 4 and scene_coords.shape[1] == 3
+    _check_batch(scene_coords)
     sc = scene_coords.contiguous()
-    if not isinstance(params, N.RansacParams):
-        params = _params(**params)
-    arr = (N.Intrinsics * sc.shape[0])()
-    for i, it in enumerate(intrinsics):
-        arr[i] = it if isinstance(it, N.Intrinsics) else N.Intrinsics(float(it[0]), float(it[1]), float(it[2]))
-    return _device_call("acez_register_rgb_device", [sc], (C.byref(params), arr, C.c_uint64(int(seed))), frame_ids, want_masks)
+    args = (C.byref(_as_params(params)), _intrinsics_array(intrinsics, sc.shape[0]), C.c_uint64(int(seed)))
+    return _device_call("acez_register_rgb_device", [sc], args, frame_ids, want_masks)
 
 
 def debug_fetch(n, hyps, device=None):
@@ -190,10 +216,7 @@ def forward_rgbd(sceneCoordinates, cameraCoordinates, outPose, ransacHypotheses,
     cam->world `outPose`, inlierThreshold / maxDistError in centimetres; returns the inlier count. As in forward_rgb, the per-process
     call counter keys the random stream (the reference's ThreadRand::init() continues one stream across calls)."""
     sc, cc = sceneCoordinates, cameraCoordinates
-    _check_1x3("sceneCoordinates", sc)
-    _check_1x3("cameraCoordinates", cc)
-    if tuple(sc.shape) != tuple(cc.shape):
-        raise RuntimeError("sceneCoordinates and cameraCoordinates must have the same shape")
+    _check_1x3(sceneCoordinates=sc, cameraCoordinates=cc)
     frame_id = _check_call("forward_rgbd", outPose)
     prm = _params(ransacHypotheses, inlierThreshold, inlierAlpha, maxDistError, **_RGBD_DEFAULTS)
     if sc.is_cuda or cc.is_cuda:
@@ -208,13 +231,9 @@ def register_batch_rgbd(scene_coords, camera_coords, params, seed, frame_ids=Non
     """scene_coords, camera_coords: CUDA float32 [n,3,H,W] (metres); params: N.RansacParams or dict(hyps, thr, alpha, max_reproj
     [, max_tries]) with thr / max_reproj in centimetres. Returns (poses [n,4,4] f32 cam->world, inliers [n] i32, masks [n,H,W] u8 or
     None), all CUDA tensors; asynchronous."""
-    for t in (scene_coords, camera_coords):
-        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] == 3
-    assert tuple(scene_coords.shape) == tuple(camera_coords.shape) and scene_coords.device == camera_coords.device
-    if not isinstance(params, N.RansacParams):
-        params = _params(**{**_RGBD_DEFAULTS, **params})
+    _check_batch(scene_coords, camera_coords)
     return _device_call("acez_register_rgbd_device", [scene_coords.contiguous(), camera_coords.contiguous()],
-                        (C.byref(params), C.c_uint64(int(seed))), frame_ids, want_masks)
+                        (C.byref(_as_params(params, _RGBD_DEFAULTS)), C.c_uint64(int(seed))), frame_ids, want_masks)
 
 
 def debug_fetch_rgbd(n, hyps, device=None):
@@ -222,13 +241,58 @@ def debug_fetch_rgbd(n, hyps, device=None):
     return _debug_fetch("acez_ransac_rgbd_debug_fetch", n, hyps, device, samples=True)
 
 
-# ---------------------------------------------------------------------------------------------------- RGB-D backward
+# ---------------------------------------------------------------------------------------------------- backward passes
 PROB_THRESH = 0.001  # dsacstar_derivative.h:36: hypotheses below it are neither refined nor differentiated
 
 
-def _gt_rows(gtPose, n, dev):
-    g = torch.as_tensor(gtPose, dtype=torch.float32).reshape(n, 4, 4)
-    return g.to(dev).contiguous()
+def _backward_device_call(entry, inputs, gt_poses, mid_args, seed, frame_ids, weights, out_grad):
+    """The device entry `entry`(ctx, inputs, gt, n, H, W, *mid_args, *weights, seed, frame ids, grad, loss, stream) on the current
+    stream of the inputs' device; mid_args: the params and, for RGB, the intrinsics. -> (gradient or out_grad with it added, loss)."""
+    n, _, H, W = inputs[0].shape
+    dev = inputs[0].device
+    gt = torch.as_tensor(gt_poses, dtype=torch.float32).reshape(n, 4, 4).to(dev).contiguous()
+    if out_grad is None:
+        out_grad = torch.zeros(n, 3, H, W, dtype=torch.float32, device=dev)
+    assert out_grad.is_cuda and out_grad.dtype == torch.float32 and out_grad.is_contiguous() and tuple(out_grad.shape) == (n, 3, H, W)
+    loss = torch.empty(n, dtype=torch.float64, device=dev)
+    inputs = [t.contiguous() for t in inputs]
+    ctx, L = _context(n, H, W, dev.index)
+    ids = (C.c_uint64 * n)(*[int(x) for x in frame_ids]) if frame_ids is not None else None
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        N.check(getattr(L, entry)(ctx, *[C.c_void_p(t.data_ptr()) for t in inputs], C.c_void_p(gt.data_ptr()), n, H, W, *mid_args,
+                                  *[float(x) for x in weights], C.c_uint64(int(seed)), ids, C.c_void_p(out_grad.data_ptr()),
+                                  C.c_void_p(loss.data_ptr()), stream))
+    return out_grad, loss
+
+
+def _backward_host_call(entry, inputs, og, gt, mid_args, seed, frame_id, weights):
+    """The host-buffer entry `entry`(ctx, (data, strides) of each [1,3,H,W] input, gt, H, W, *mid_args, *weights, seed, frame id,
+    (data, strides) of og, loss) of the current device's context: the gradient is added to og. -> the expected loss."""
+    H, W = int(og.shape[2]), int(og.shape[3])
+    ctx, L = _context(1, H, W, torch.cuda.current_device())
+    gt16 = np.ascontiguousarray(gt.cpu().numpy(), np.float32)
+    out = C.c_double(0.0)
+    strided = [a for t in inputs for a in (C.c_void_p(t.data_ptr()), *t.stride()[1:])]
+    N.check(getattr(L, entry)(ctx, *strided, gt16.ctypes.data_as(C.c_void_p), H, W, *mid_args, *[float(x) for x in weights],
+                              C.c_uint64(int(seed)), C.c_uint64(frame_id), C.c_void_p(og.data_ptr()), *og.stride()[1:], C.byref(out)))
+    return float(out.value)
+
+
+def _backward_single(kind, inputs, og, gtPose, mid_args, seed, weights):
+    """backward_rgb / backward_rgbd after their input checks: on the device of the first CUDA tensor among the inputs and og, or
+    through the host-buffer entry if all are host tensors. The gradient is added to og. -> the expected loss."""
+    gt = torch.as_tensor(gtPose, dtype=torch.float32)
+    if tuple(gt.shape) != (4, 4):
+        raise RuntimeError("gtPose must be a 4x4 tensor")
+    frame_id = _next_frame_id(f"backward_{kind}")
+    dev = next((t.device for t in (*inputs, og) if t.is_cuda), None)
+    if dev is None:
+        return _backward_host_call(f"acez_register_{kind}_backward_host", inputs, og, gt, mid_args, seed, frame_id, weights)
+    grad, loss = _backward_device_call(f"acez_register_{kind}_backward_device", [t.to(dev) for t in inputs], gt, mid_args, seed,
+                                       [frame_id], weights, None)
+    og.add_(grad.to(og.device))
+    return float(loss[0].item())
 
 
 def register_batch_rgbd_backward(scene_coords, camera_coords, gt_poses, params, seed, frame_ids=None, w_loss_rot=1.0,
@@ -237,28 +301,10 @@ def register_batch_rgbd_backward(scene_coords, camera_coords, gt_poses, params, 
     cam->world; params as register_batch_rgbd's. The hypotheses are those register_batch_rgbd draws for the same (seed, frame ids).
     Returns (grad [n,3,H,W] f32, expected loss [n] f64), CUDA tensors; the gradient is added to out_grad if one is given (a
     contiguous CUDA float32 [n,3,H,W]) and that tensor is returned. Asynchronous."""
-    for t in (scene_coords, camera_coords):
-        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] == 3
-    assert tuple(scene_coords.shape) == tuple(camera_coords.shape) and scene_coords.device == camera_coords.device
-    if not isinstance(params, N.RansacParams):
-        params = _params(**{**_RGBD_DEFAULTS, **params})
-    n, _, H, W = scene_coords.shape
-    dev = scene_coords.device
-    gt = _gt_rows(gt_poses, n, dev)
-    if out_grad is None:
-        out_grad = torch.zeros(n, 3, H, W, dtype=torch.float32, device=dev)
-    assert out_grad.is_cuda and out_grad.dtype == torch.float32 and out_grad.is_contiguous() and tuple(out_grad.shape) == (n, 3, H, W)
-    loss = torch.empty(n, dtype=torch.float64, device=dev)
-    sc, cc = scene_coords.contiguous(), camera_coords.contiguous()
-    ctx, L = _context(n, H, W, dev.index)
-    ids = (C.c_uint64 * n)(*[int(x) for x in frame_ids]) if frame_ids is not None else None
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        N.check(L.acez_register_rgbd_backward_device(ctx, C.c_void_p(sc.data_ptr()), C.c_void_p(cc.data_ptr()), C.c_void_p(gt.data_ptr()),
-                                                     n, H, W, C.byref(params), float(w_loss_rot), float(w_loss_trans), float(soft_clamp),
-                                                     C.c_uint64(int(seed)), ids, C.c_void_p(out_grad.data_ptr()),
-                                                     C.c_void_p(loss.data_ptr()), stream))
-    return out_grad, loss
+    _check_batch(scene_coords, camera_coords)
+    return _backward_device_call("acez_register_rgbd_backward_device", [scene_coords, camera_coords], gt_poses,
+                                 (C.byref(_as_params(params, _RGBD_DEFAULTS)),), seed, frame_ids, (w_loss_rot, w_loss_trans, soft_clamp),
+                                 out_grad)
 
 
 def backward_rgbd(sceneCoordinates, cameraCoordinates, outSceneCoordinatesGrad, gtPose, ransacHypotheses, inlierThreshold, wLossRot,
@@ -267,30 +313,40 @@ def backward_rgbd(sceneCoordinates, cameraCoordinates, outSceneCoordinatesGrad, 
     gtPose; the gradient of the expected pose loss is ADDED to outSceneCoordinatesGrad (1x3xHxW float32) and the expected loss is
     returned. inlierThreshold / maxDistError in centimetres. The frame id is the call counter forward_rgbd uses, the seed randomSeed."""
     sc, cc, og = sceneCoordinates, cameraCoordinates, outSceneCoordinatesGrad
-    _check_1x3("sceneCoordinates", sc)
-    _check_1x3("cameraCoordinates", cc)
-    _check_1x3("outSceneCoordinatesGrad", og)
-    if tuple(sc.shape) != tuple(cc.shape) or tuple(sc.shape) != tuple(og.shape):
-        raise RuntimeError("sceneCoordinates, cameraCoordinates and outSceneCoordinatesGrad must have the same shape")
-    gt = torch.as_tensor(gtPose, dtype=torch.float32)
-    if tuple(gt.shape) != (4, 4):
-        raise RuntimeError("gtPose must be a 4x4 tensor")
-    frame_id = _next_frame_id("backward_rgbd")
+    _check_1x3(sceneCoordinates=sc, cameraCoordinates=cc, outSceneCoordinatesGrad=og)
     prm = _params(ransacHypotheses, inlierThreshold, inlierAlpha, maxDistError, **_RGBD_DEFAULTS)
-    if sc.is_cuda or cc.is_cuda or og.is_cuda:
-        dev = next(t.device for t in (sc, cc, og) if t.is_cuda)
-        g, loss = register_batch_rgbd_backward(sc.to(dev), cc.to(dev), gt, prm, randomSeed, [frame_id], wLossRot, wLossTrans, softClamp)
-        og.add_(g.to(og.device))
-        return float(loss[0].item())
-    H, W = int(sc.shape[2]), int(sc.shape[3])
-    ctx, L = _context(1, H, W, torch.cuda.current_device())
-    gt16 = np.ascontiguousarray(gt.cpu().numpy(), np.float32)
-    out = C.c_double(0.0)
-    strided = [a for t in (sc, cc) for a in (C.c_void_p(t.data_ptr()), *t.stride()[1:])]
-    N.check(L.acez_register_rgbd_backward_host(ctx, *strided, gt16.ctypes.data_as(C.c_void_p), H, W, C.byref(prm), float(wLossRot),
-                                               float(wLossTrans), float(softClamp), C.c_uint64(int(randomSeed)), C.c_uint64(frame_id),
-                                               C.c_void_p(og.data_ptr()), *og.stride()[1:], C.byref(out)))
-    return float(out.value)
+    return _backward_single("rgbd", [sc, cc], og, gtPose, (C.byref(prm),), randomSeed, (wLossRot, wLossTrans, softClamp))
+
+
+def register_batch_backward(scene_coords, intrinsics, gt_poses, params, seed, frame_ids=None, w_loss_rot=1.0, w_loss_trans=1.0,
+                            soft_clamp=100.0, out_grad=None):
+    """The DSAC* RGB backward pass of n frames: scene_coords CUDA float32 [n,3,H,W], intrinsics and params as register_batch's, gt_poses
+    [n,4,4] cam->world. The hypotheses are those register_batch draws for the same (seed, frame ids). Returns (grad [n,3,H,W] f32,
+    expected loss [n] f64), CUDA tensors; the gradient is added to out_grad if one is given. Asynchronous."""
+    _check_batch(scene_coords)
+    mid_args = (C.byref(_as_params(params)), _intrinsics_array(intrinsics, scene_coords.shape[0]))
+    return _backward_device_call("acez_register_rgb_backward_device", [scene_coords], gt_poses, mid_args, seed, frame_ids,
+                                 (w_loss_rot, w_loss_trans, soft_clamp), out_grad)
+
+
+def backward_rgb(sceneCoordinates, outSceneCoordinatesGrad, gtPose, ransacHypotheses, inlierThreshold, focalLength, ppointX, ppointY,
+                 wLossRot, wLossTrans, softClamp, inlierAlpha, maxReproj, subSampling, randomSeed):
+    """The reference's commented-out binding (dsacstar.cpp:208-490): 1x3xHxW scene coordinates, 4x4 cam->world gtPose; the gradient
+    of the expected pose loss is ADDED to outSceneCoordinatesGrad (1x3xHxW float32) and the expected loss is returned. The frame id
+    is the call counter forward_rgb uses, the seed randomSeed; the tries are forward_rgb's default (16)."""
+    sc, og = sceneCoordinates, outSceneCoordinatesGrad
+    _check_1x3(sceneCoordinates=sc, outSceneCoordinatesGrad=og)
+    prm = _params(ransacHypotheses, inlierThreshold, inlierAlpha, maxReproj, subSampling, MAX_HYPOTHESES_TRIES)
+    intr = _intrinsics_array([(focalLength, ppointX, ppointY)], 1)   # one frame's: the device entry's array, the host entry's pointer
+    return _backward_single("rgb", [sc], og, gtPose, (C.byref(prm), intr), randomSeed, (wLossRot, wLossTrans, softClamp))
+
+
+def _mask_words_rgb(cells):
+    return ((cells + 255) // 256) * 4   # one word per wavefront and row of 256 threads (mask_words of the RGB backward workspace)
+
+
+def _mask_words_rgbd(cells):
+    return ((cells + 511) // 512) * 8   # one word per wavefront and row of 512 threads (mask_words of the RGB-D one)
 
 
 def _debug_fetch_backward(entry, n, hyps, h, w, n_samples, words, device):
@@ -307,21 +363,29 @@ def _debug_fetch_backward(entry, n, hyps, h, w, n_samples, words, device):
 def debug_fetch_rgbd_backward(n, hyps, h, w, device=None):
     """Per-hypothesis results of the last RGB-D backward call: samples, hyp_poses, scores, probs, losses, ref_poses, masks (bool
     [n,hyps,valid cells] over the valid cells in scan order), entropy."""
-    return _debug_fetch_backward("acez_ransac_rgbd_backward_debug_fetch", n, hyps, h, w, 3, ((h * w + 511) // 512) * 8, device)
+    return _debug_fetch_backward("acez_ransac_rgbd_backward_debug_fetch", n, hyps, h, w, 3, _mask_words_rgbd(h * w), device)
 
 
-class _ExpectedPoseLossRGBD(torch.autograd.Function):
+def debug_fetch_rgb_backward(n, hyps, h, w, device=None):
+    """Per-hypothesis results of the last RGB backward call: samples (4 scan indices x*h+y), hyp_poses, scores, probs, losses,
+    ref_poses, masks (bool [n,hyps,h*w] over all cells in scan order), entropy."""
+    out = _debug_fetch_backward("acez_ransac_rgb_backward_debug_fetch", n, hyps, h, w, 4, _mask_words_rgb(h * w), device)
+    out["masks"] = out["masks"][:, :, :h * w]
+    return out
+
+
+class _ExpectedPoseLoss(torch.autograd.Function):
+    """batch_fn: register_batch_backward or register_batch_rgbd_backward; second: what it takes after the coordinates."""
     @staticmethod
-    def forward(ctx, coords, camera_coords, gt_poses, params, seed, frame_ids, w_rot, w_trans, clamp):
-        g, loss = register_batch_rgbd_backward(coords.detach(), camera_coords.detach(), gt_poses, params, seed, frame_ids, w_rot,
-                                               w_trans, clamp)
+    def forward(ctx, batch_fn, coords, second, gt_poses, params, seed, frame_ids, w_rot, w_trans, clamp):
+        g, loss = batch_fn(coords.detach(), second, gt_poses, params, seed, frame_ids, w_rot, w_trans, clamp)
         ctx.save_for_backward(g)
         return loss.to(coords.dtype)
 
     @staticmethod
     def backward(ctx, grad_out):
         (g,) = ctx.saved_tensors
-        return (g * grad_out.to(g.dtype).view(-1, 1, 1, 1),) + (None,) * 8
+        return (None, g * grad_out.to(g.dtype).view(-1, 1, 1, 1)) + (None,) * 8
 
 
 def expected_pose_loss_rgbd(coords, camera_coords, gt_poses, hypotheses=64, threshold=10.0, w_loss_rot=1.0, w_loss_trans=1.0,
@@ -329,96 +393,10 @@ def expected_pose_loss_rgbd(coords, camera_coords, gt_poses, hypotheses=64, thre
     """Differentiable DSAC* RGB-D loss: the expected pose loss per frame, float32 [n] on the coordinates' device, whose .backward()
     puts the backward pass's gradient into coords.grad. coords, camera_coords: CUDA [n,3,H,W] (metres); gt_poses [n,4,4] cam->world.
     frame_ids default to the next values of the call counter forward_rgbd uses, so successive calls draw fresh hypotheses."""
-    global _calls
-    n = coords.shape[0]
-    if frame_ids is None:
-        frame_ids = list(range(_calls, _calls + n))
-        _calls += n
+    frame_ids = _take_frame_ids(coords.shape[0]) if frame_ids is None else list(frame_ids)
     prm = _params(hypotheses, threshold, inlier_alpha, max_dist, **_RGBD_DEFAULTS)
-    return _ExpectedPoseLossRGBD.apply(coords, camera_coords, gt_poses, prm, seed, list(frame_ids), w_loss_rot, w_loss_trans, soft_clamp)
-
-
-# ---------------------------------------------------------------------------------------------------- RGB backward
-def register_batch_backward(scene_coords, intrinsics, gt_poses, params, seed, frame_ids=None, w_loss_rot=1.0, w_loss_trans=1.0,
-                            soft_clamp=100.0, out_grad=None):
-    """The DSAC* RGB backward pass of n frames: scene_coords CUDA float32 [n,3,H,W], intrinsics and params as register_batch's, gt_poses
-    [n,4,4] cam->world. The hypotheses are those register_batch draws for the same (seed, frame ids). Returns (grad [n,3,H,W] f32,
-    expected loss [n] f64), CUDA tensors; the gradient is added to out_grad if one is given. Asynchronous."""
-    assert scene_coords.is_cuda and scene_coords.dtype == torch.float32 and scene_coords.dim() == 4 and scene_coords.shape[1] == 3
-    if not isinstance(params, N.RansacParams):
-        params = _params(**params)
-    n, _, H, W = scene_coords.shape
-    dev = scene_coords.device
-    arr = (N.Intrinsics * n)()
-    for i, it in enumerate(intrinsics):
-        arr[i] = it if isinstance(it, N.Intrinsics) else N.Intrinsics(float(it[0]), float(it[1]), float(it[2]))
-    gt = _gt_rows(gt_poses, n, dev)
-    if out_grad is None:
-        out_grad = torch.zeros(n, 3, H, W, dtype=torch.float32, device=dev)
-    assert out_grad.is_cuda and out_grad.dtype == torch.float32 and out_grad.is_contiguous() and tuple(out_grad.shape) == (n, 3, H, W)
-    loss = torch.empty(n, dtype=torch.float64, device=dev)
-    sc = scene_coords.contiguous()
-    ctx, L = _context(n, H, W, dev.index)
-    ids = (C.c_uint64 * n)(*[int(x) for x in frame_ids]) if frame_ids is not None else None
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        N.check(L.acez_register_rgb_backward_device(ctx, C.c_void_p(sc.data_ptr()), C.c_void_p(gt.data_ptr()), n, H, W, C.byref(params),
-                                                    arr, float(w_loss_rot), float(w_loss_trans), float(soft_clamp), C.c_uint64(int(seed)),
-                                                    ids, C.c_void_p(out_grad.data_ptr()), C.c_void_p(loss.data_ptr()), stream))
-    return out_grad, loss
-
-
-def backward_rgb(sceneCoordinates, outSceneCoordinatesGrad, gtPose, ransacHypotheses, inlierThreshold, focalLength, ppointX, ppointY,
-                 wLossRot, wLossTrans, softClamp, inlierAlpha, maxReproj, subSampling, randomSeed):
-    """The reference's commented-out binding (dsacstar.cpp:208-490): 1x3xHxW scene coordinates, 4x4 cam->world gtPose; the gradient
-    of the expected pose loss is ADDED to outSceneCoordinatesGrad (1x3xHxW float32) and the expected loss is returned. The frame id
-    is the call counter forward_rgb uses, the seed randomSeed; the tries are forward_rgb's default (16)."""
-    sc, og = sceneCoordinates, outSceneCoordinatesGrad
-    _check_1x3("sceneCoordinates", sc)
-    _check_1x3("outSceneCoordinatesGrad", og)
-    if tuple(sc.shape) != tuple(og.shape):
-        raise RuntimeError("sceneCoordinates and outSceneCoordinatesGrad must have the same shape")
-    gt = torch.as_tensor(gtPose, dtype=torch.float32)
-    if tuple(gt.shape) != (4, 4):
-        raise RuntimeError("gtPose must be a 4x4 tensor")
-    frame_id = _next_frame_id("backward_rgb")
-    prm = _params(ransacHypotheses, inlierThreshold, inlierAlpha, maxReproj, subSampling, MAX_HYPOTHESES_TRIES)
-    intr = N.Intrinsics(float(focalLength), float(ppointX), float(ppointY))
-    if sc.is_cuda or og.is_cuda:
-        dev = sc.device if sc.is_cuda else og.device
-        g, loss = register_batch_backward(sc.to(dev), [intr], gt, prm, randomSeed, [frame_id], wLossRot, wLossTrans, softClamp)
-        og.add_(g.to(og.device))
-        return float(loss[0].item())
-    H, W = int(sc.shape[2]), int(sc.shape[3])
-    ctx, L = _context(1, H, W, torch.cuda.current_device())
-    gt16 = np.ascontiguousarray(gt.cpu().numpy(), np.float32)
-    out = C.c_double(0.0)
-    N.check(L.acez_register_rgb_backward_host(ctx, C.c_void_p(sc.data_ptr()), *sc.stride()[1:], gt16.ctypes.data_as(C.c_void_p), H, W,
-                                              C.byref(prm), C.byref(intr), float(wLossRot), float(wLossTrans), float(softClamp),
-                                              C.c_uint64(int(randomSeed)), C.c_uint64(frame_id), C.c_void_p(og.data_ptr()),
-                                              *og.stride()[1:], C.byref(out)))
-    return float(out.value)
-
-
-def debug_fetch_rgb_backward(n, hyps, h, w, device=None):
-    """Per-hypothesis results of the last RGB backward call: samples (4 scan indices x*h+y), hyp_poses, scores, probs, losses,
-    ref_poses, masks (bool [n,hyps,h*w] over all cells in scan order), entropy."""
-    out = _debug_fetch_backward("acez_ransac_rgb_backward_debug_fetch", n, hyps, h, w, 4, ((h * w + 255) // 256) * 4, device)
-    out["masks"] = out["masks"][:, :, :h * w]
-    return out
-
-
-class _ExpectedPoseLossRGB(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, coords, intrinsics, gt_poses, params, seed, frame_ids, w_rot, w_trans, clamp):
-        g, loss = register_batch_backward(coords.detach(), intrinsics, gt_poses, params, seed, frame_ids, w_rot, w_trans, clamp)
-        ctx.save_for_backward(g)
-        return loss.to(coords.dtype)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        (g,) = ctx.saved_tensors
-        return (g * grad_out.to(g.dtype).view(-1, 1, 1, 1),) + (None,) * 8
+    return _ExpectedPoseLoss.apply(register_batch_rgbd_backward, coords, camera_coords, gt_poses, prm, seed, frame_ids, w_loss_rot,
+                                   w_loss_trans, soft_clamp)
 
 
 def expected_pose_loss_rgb(coords, intrinsics, gt_poses, hypotheses=64, threshold=10.0, w_loss_rot=1.0, w_loss_trans=1.0,
@@ -427,10 +405,7 @@ def expected_pose_loss_rgb(coords, intrinsics, gt_poses, hypotheses=64, threshol
     """Differentiable DSAC* RGB loss: the expected pose loss per frame, float32 [n], whose .backward() puts the backward pass's
     gradient into coords.grad. coords: CUDA [n,3,H,W]; intrinsics: one (focal, ppx, ppy) per frame; gt_poses [n,4,4] cam->world.
     frame_ids default to the next values of the call counter forward_rgb uses."""
-    global _calls
-    n = coords.shape[0]
-    if frame_ids is None:
-        frame_ids = list(range(_calls, _calls + n))
-        _calls += n
+    frame_ids = _take_frame_ids(coords.shape[0]) if frame_ids is None else list(frame_ids)
     prm = _params(hypotheses, threshold, inlier_alpha, max_reproj, subsampling, max_tries)
-    return _ExpectedPoseLossRGB.apply(coords, list(intrinsics), gt_poses, prm, seed, list(frame_ids), w_loss_rot, w_loss_trans, soft_clamp)
+    return _ExpectedPoseLoss.apply(register_batch_backward, coords, list(intrinsics), gt_poses, prm, seed, frame_ids, w_loss_rot,
+                                   w_loss_trans, soft_clamp)
