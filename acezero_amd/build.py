@@ -24,6 +24,8 @@ UNITS = {
     "acez_common.hip": [],
     "head_api.hip": [],
     "encoder_api.hip": [],
+    "conv_kernels.hip": [],
+    "buffer_api.hip": [],
     "ransac_api.hip": ["-ffp-contract=off"],
     "ransac_rgbd.hip": ["-ffp-contract=off"],
     "ransac_grad.hip": ["-ffp-contract=off"],

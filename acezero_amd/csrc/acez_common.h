@@ -7,6 +7,8 @@
 
 namespace acez {
 void set_error(const char* fmt, ...);
+// ACEZ_OK if a HIP device is visible; else ACEZ_ERR_NODEVICE with the error "no HIP device visible: <what> (there is no CPU fallback)"
+int require_device(const char* what);
 }
 
 #define ACEZ_HIP_CHECK(expr)                                                                   \

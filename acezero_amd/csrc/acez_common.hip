@@ -10,6 +10,15 @@ void set_error(const char* fmt, ...) {
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
 }
+int require_device(const char* what) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    (void)hipGetLastError();
+    set_error("no HIP device visible: %s (there is no CPU fallback)", what);
+    return ACEZ_ERR_NODEVICE;
+  }
+  return ACEZ_OK;
+}
 }  // namespace acez
 
 extern "C" const char* acez_last_error(void) { return acez::g_err; }

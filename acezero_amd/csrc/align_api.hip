@@ -427,12 +427,7 @@ extern "C" int acez_align_create(acez_align** out, int max_frames, int max_hyp, 
   *out = nullptr;
   ACEZ_REQUIRE(max_frames > 0 && max_hyp > 0, "sizes must be positive");
   ACEZ_REQUIRE(max_frames <= (1 << 24) && max_hyp <= (1 << 24), "at most 2^24 frames and hypotheses");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    (void)hipGetLastError();
-    acez::set_error("no HIP device visible: pose evaluation runs on a gfx950 GPU (there is no CPU fallback)");
-    return ACEZ_ERR_NODEVICE;
-  }
+  if (int rc = acez::require_device("pose evaluation runs on a gfx950 GPU")) return rc;
   if (device >= 0) ACEZ_HIP_CHECK(hipSetDevice(device));
   acez_align* c = new (std::nothrow) acez_align();
   ACEZ_REQUIRE(c, "out of host memory");

@@ -305,14 +305,7 @@ extern "C" int acez_point_cloud_filter(const float* d_scene_coords, const float*
   ACEZ_REQUIRE(map_h * map_w <= PC_MAX_HW, "scene-coordinate map larger than 24576 pixels");
   ACEZ_REQUIRE((int64_t)n_frames * map_h * map_w < (int64_t)1 << 31, "more than 2^31 map pixels in one call");
   ACEZ_REQUIRE(points_per_image_min >= 0 && points_per_image_max >= points_per_image_min, "bad per-image point budgets");
-  {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-      (void)hipGetLastError();
-      acez::set_error("no HIP device visible: point-cloud extraction runs on a gfx950 GPU (there is no CPU fallback)");
-      return ACEZ_ERR_NODEVICE;
-    }
-  }
+  if (int rc = acez::require_device("point-cloud extraction runs on a gfx950 GPU")) return rc;
   hipStream_t s = (hipStream_t)stream;
   CloudArgs a{d_scene_coords, d_poses_inv, d_intrinsics, map_h, map_w, filter_depth, dense_cloud, points_per_image_min, points_per_image_max,
               seed, first_frame_id, d_keep, d_counts};

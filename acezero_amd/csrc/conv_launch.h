@@ -1,5 +1,5 @@
-// conv_launch.h -- the implicit-GEMM convolution launcher (encoder_api.hip), shared with the head's large-batch inference path
-// (a 1x1 convolution over [rows][512] is the head's layer GEMM).
+// conv_launch.h -- the launchers of conv_kernels.hip: the encoder's layers (encoder_api.hip), and the implicit-GEMM launcher is shared
+// with the head's large-batch inference path (head_api.hip: a 1x1 convolution over [rows][512] is the head's layer GEMM).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,7 +28,21 @@ struct ConvGemmArgs {
   unsigned long long* trace;   // diagnostics build (tools/conv_trace.py): [tiles][8] s_memtime stamps of convgemm512's waves 0 and 8; else null
 };
 
-// tile_mode: 0 = choose by size, 80 / 256 / 512 = force that kernel where the layer shape allows it
+// tile_mode: 0 = choose by size, 3 / 512 / 256 / 80 = force that kernel where the layer shape allows it
 void launch_convgemm(const ConvGemmArgs& g, bool relu, hipStream_t s, int tile_mode);
+
+// conv1 + conv2 (conv12p_kernel)
+struct Conv12Args {
+  const float* img;        // [F][H][W] fp32
+  const uint16_t* w1;      // 16-bit [32][16]: k = tap (9 used)
+  const float* b1;         // [32]
+  const uint16_t* w2;      // 16-bit [64][Kp2], k = tap * 32 + ci
+  const float* b2;         // [64]
+  uint16_t* out;           // NHWC 16-bit [F][H2][W2][64]
+  int F, H, W, H2, W2, Kp2, tiles_y, tiles_x, n_tiles;   // tiles_x = ceil(W2 / 32) sizes the grid; tiles_y and n_tiles are read by nobody (they
+                           // stay: dropping them moves the kernel arguments behind them, and conv12p_kernel is to compile to the same code)
+  const float* zero;       // >= 4 bytes of zeros: source of the image-patch DMA outside the image
+};
+void launch_conv12p(const Conv12Args& c, bool f16, hipStream_t s);
 
 }  // namespace acez

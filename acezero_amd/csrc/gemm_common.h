@@ -1,4 +1,4 @@
-// gemm_common.h -- device helpers shared by the GEMM-shaped kernels (head_kernels.hip, encoder_api.hip, head_maps.hip):
+// gemm_common.h -- device helpers shared by the GEMM-shaped kernels (head_kernels.hip, conv_kernels.hip, head_maps.hip):
 // bf16 packing, LDS swizzles, LDS-DMA address-space typedefs, counted waits.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -47,6 +47,8 @@ __device__ __forceinline__ void unpack4(uint2 v, float* o) {
 // [row][64] bf16 K-stage tiles: 16-byte chunk index XOR (row >> 1) & 7 -> the ds_read_b128 fragment reads of 32
 // consecutive rows are conflict-free. Applied to the per-lane SOURCE chunk of the LDS-DMA and, identically, to the reads.
 __device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 7)) << 3); }
+// [row][32] K-stage tiles (convgemm512, conv3x3r): chunk index XOR (row >> 2) & 3
+__device__ __forceinline__ int swz32(int row, int chunk) { return row * 32 + ((chunk ^ ((row >> 2) & 3)) << 3); }
 // [rows][128] bf16 epilogue staging tiles: chunk index XOR row & 15 (conflict-free for the accumulator layout and for
 // the row-wise copy)
 __device__ __forceinline__ int st_off(int row, int col) { return row * 128 + ((((col >> 3) ^ (row & 15)) << 3) | (col & 7)); }
@@ -126,5 +128,42 @@ typedef __attribute__((address_space(1))) const void gvoid_t;
 typedef __attribute__((address_space(3))) void lvoid_t;
 #define ACEZ_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 #define ACEZ_VMCNT_C(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")   // n: integral constant expression
+// s_waitcnt vmcnt(n) for a wave-uniform n that is only known at run time (1 .. 31; anything else waits for everything)
+__device__ __forceinline__ void wait_vmcnt_dyn(int n) {
+  switch (n) {
+    case 1: ACEZ_VMCNT(1); break;
+    case 2: ACEZ_VMCNT(2); break;
+    case 3: ACEZ_VMCNT(3); break;
+    case 4: ACEZ_VMCNT(4); break;
+    case 5: ACEZ_VMCNT(5); break;
+    case 6: ACEZ_VMCNT(6); break;
+    case 7: ACEZ_VMCNT(7); break;
+    case 8: ACEZ_VMCNT(8); break;
+    case 9: ACEZ_VMCNT(9); break;
+    case 10: ACEZ_VMCNT(10); break;
+    case 11: ACEZ_VMCNT(11); break;
+    case 12: ACEZ_VMCNT(12); break;
+    case 13: ACEZ_VMCNT(13); break;
+    case 14: ACEZ_VMCNT(14); break;
+    case 15: ACEZ_VMCNT(15); break;
+    case 16: ACEZ_VMCNT(16); break;
+    case 17: ACEZ_VMCNT(17); break;
+    case 18: ACEZ_VMCNT(18); break;
+    case 19: ACEZ_VMCNT(19); break;
+    case 20: ACEZ_VMCNT(20); break;
+    case 21: ACEZ_VMCNT(21); break;
+    case 22: ACEZ_VMCNT(22); break;
+    case 23: ACEZ_VMCNT(23); break;
+    case 24: ACEZ_VMCNT(24); break;
+    case 25: ACEZ_VMCNT(25); break;
+    case 26: ACEZ_VMCNT(26); break;
+    case 27: ACEZ_VMCNT(27); break;
+    case 28: ACEZ_VMCNT(28); break;
+    case 29: ACEZ_VMCNT(29); break;
+    case 30: ACEZ_VMCNT(30); break;
+    case 31: ACEZ_VMCNT(31); break;
+    default: ACEZ_VMCNT(0); break;
+  }
+}
 
 }  // namespace acez

@@ -315,12 +315,7 @@ extern "C" int acez_trainer_create(acez_trainer** out, const acez_train_config* 
   ACEZ_REQUIRE(cfg->pose_refinement != 1 || (params->n_pose_params > 0 && params->n_pose_params % 12 == 0), "naive: n_pose_params must be 12 * n_images");
   ACEZ_REQUIRE(cfg->compute_dtype != ACEZ_DTYPE_FP32, "compute_dtype fp32 (train_ace.py --use_half False) is not implemented: choose ACEZ_DTYPE_BF16 or ACEZ_DTYPE_FP16");
   ACEZ_REQUIRE(cfg->compute_dtype == ACEZ_DTYPE_BF16 || cfg->compute_dtype == ACEZ_DTYPE_FP16, "unknown compute_dtype");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    (void)hipGetLastError();
-    set_error("no HIP device visible: the head kernels need a gfx950 GPU (there is no CPU fallback)");
-    return ACEZ_ERR_NODEVICE;
-  }
+  if (int rc = acez::require_device("the head kernels need a gfx950 GPU")) return rc;
   if (device >= 0) ACEZ_HIP_CHECK(hipSetDevice(device));
   acez_trainer* tr = new (std::nothrow) acez_trainer();
   ACEZ_REQUIRE(tr, "out of host memory");

@@ -687,44 +687,6 @@ __device__ __forceinline__ typename E::frag tr_frag(const uint16_t* p) {
 constexpr int WGRAD_RING = 4;                       // slots of the [dZ | In] stage ring, 32 KiB each (RING - 1 stages in flight per CU)
 constexpr int WGRAD_LOADERS = 8;                    // loader waves per workgroup (beside the 4 multiplier waves)
 constexpr int WGRAD_THREADS = 256 + 64 * WGRAD_LOADERS;
-// s_waitcnt vmcnt(n) for a wave-uniform n that is only known at run time (1 .. 31; anything else waits for everything)
-__device__ __forceinline__ void wait_vmcnt_dyn(int n) {
-  switch (n) {
-    case 1: ACEZ_VMCNT(1); break;
-    case 2: ACEZ_VMCNT(2); break;
-    case 3: ACEZ_VMCNT(3); break;
-    case 4: ACEZ_VMCNT(4); break;
-    case 5: ACEZ_VMCNT(5); break;
-    case 6: ACEZ_VMCNT(6); break;
-    case 7: ACEZ_VMCNT(7); break;
-    case 8: ACEZ_VMCNT(8); break;
-    case 9: ACEZ_VMCNT(9); break;
-    case 10: ACEZ_VMCNT(10); break;
-    case 11: ACEZ_VMCNT(11); break;
-    case 12: ACEZ_VMCNT(12); break;
-    case 13: ACEZ_VMCNT(13); break;
-    case 14: ACEZ_VMCNT(14); break;
-    case 15: ACEZ_VMCNT(15); break;
-    case 16: ACEZ_VMCNT(16); break;
-    case 17: ACEZ_VMCNT(17); break;
-    case 18: ACEZ_VMCNT(18); break;
-    case 19: ACEZ_VMCNT(19); break;
-    case 20: ACEZ_VMCNT(20); break;
-    case 21: ACEZ_VMCNT(21); break;
-    case 22: ACEZ_VMCNT(22); break;
-    case 23: ACEZ_VMCNT(23); break;
-    case 24: ACEZ_VMCNT(24); break;
-    case 25: ACEZ_VMCNT(25); break;
-    case 26: ACEZ_VMCNT(26); break;
-    case 27: ACEZ_VMCNT(27); break;
-    case 28: ACEZ_VMCNT(28); break;
-    case 29: ACEZ_VMCNT(29); break;
-    case 30: ACEZ_VMCNT(30); break;
-    case 31: ACEZ_VMCNT(31); break;
-    default: ACEZ_VMCNT(0); break;
-  }
-}
-
 // The K loop of one (layer, row slab, 128 x 128 tile) workgroup, shared by wgrad_kernel and wgrad_opt_kernel. Returns true in the
 // loader waves (their loop is over: every stage has landed and every barrier of the loop has been passed), false in the four multiplier
 // waves, whose accumulators then hold the slab's partial tile. KT = number of 64-row stages of this slab.
@@ -876,7 +838,8 @@ __global__ __launch_bounds__(WGRAD_THREADS) void wgrad_kernel(WgradArgs a) {
 constexpr int LOSS_ROWS = 8;
 __device__ __forceinline__ float sgn(float x) { return (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f); }
 
-// [32][512] bf16 activation tile of the row-persistent kernels (head_fused.hip, head_chain.hip): 16-byte chunk index XOR
+// [32][512] bf16 activation tile of the LDSACT form of the loss phases below (the row-persistent kernels it was written for,
+// headfwd_kernel and chain_kernel, live in the git history only; see the note on ACEZ_DIAG in acez_common.h): 16-byte chunk index XOR
 // (row & 15), so that the 16 rows a ds_read_b128 lane group touches land on 16 different slots of a 256-byte bank row
 __device__ __forceinline__ int act_off(int row, int ch) { return row * 512 + ((((ch >> 3) ^ (row & 15)) << 3) | (ch & 7)); }
 

@@ -1068,12 +1068,7 @@ extern "C" int acez_ransac_create(acez_ransac** out, int max_frames, int max_h, 
                     "CPU loop has no such limit", max_h, max_w, (long long)max_h * max_w, 256 * MAX_ROWS);
     return ACEZ_ERR_INVALID;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    (void)hipGetLastError();
-    acez::set_error("no HIP device visible: the DSAC* kernels need a gfx950 GPU (there is no CPU fallback)");
-    return ACEZ_ERR_NODEVICE;
-  }
+  if (int rc = acez::require_device("the DSAC* kernels need a gfx950 GPU")) return rc;
   if (device >= 0) ACEZ_HIP_CHECK(hipSetDevice(device));
   acez_ransac* ctx = new (std::nothrow) acez_ransac();
   ACEZ_REQUIRE(ctx, "out of host memory");

@@ -393,25 +393,13 @@ extern "C" int acez_render_texture_size(int width, int height, int* out_levels, 
   return ACEZ_OK;
 }
 
-namespace {
-int require_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    (void)hipGetLastError();
-    acez::set_error("no HIP device visible: rendering runs on a gfx950 GPU (there is no CPU fallback)");
-    return ACEZ_ERR_NODEVICE;
-  }
-  return ACEZ_OK;
-}
-}  // namespace
-
 extern "C" int acez_render_texture_build(const uint8_t* d_image, int width, int height, uint8_t* d_chain, int64_t chain_bytes, void* stream) {
   ACEZ_REQUIRE(d_image && d_chain, "null pointer");
   int levels = 0;
   int64_t bytes = 0;
   if (int rc = acez_render_texture_size(width, height, &levels, &bytes)) return rc;
   ACEZ_REQUIRE(chain_bytes >= bytes, "mip chain buffer too small (see acez_render_texture_size)");
-  if (int rc = require_device()) return rc;
+  if (int rc = acez::require_device("rendering runs on a gfx950 GPU")) return rc;
   hipStream_t s = (hipStream_t)stream;
   ACEZ_HIP_CHECK(hipMemcpyAsync(d_chain, d_image, (size_t)width * height * 3, hipMemcpyDeviceToDevice, s));
   uint8_t* src = d_chain;
@@ -469,7 +457,7 @@ extern "C" int acez_render_frame_tex(const float* d_xyz, const uint8_t* d_rgb, i
   c.zfar = zfar;
   c.W = width;
   c.H = height;
-  if (int rc = require_device()) return rc;
+  if (int rc = acez::require_device("rendering runs on a gfx950 GPU")) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int64_t px = (int64_t)width * height;
   unsigned long long* pkeys = d_work;

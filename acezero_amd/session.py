@@ -136,7 +136,7 @@ def warp_theta(H, W, scale, angles):
 
 
 def warp_views_device(images_n1hw, image_index, scale, angles, jitter=None, mask_hw=None):
-    """warp_views on the GPU through acez_buffer_warp_views (one launch per batch; no sampling grid, no gathered copy of the source frames):
+    """warp_views on the GPU through acez_buffer_warp_views (up to three launches per batch: warp, jitter mean, mask; no sampling grid, no gathered copy of the source frames):
     views of frames `image_index` of the resident table `images_n1hw`. Returns (views [B,1,hs,ws] float32, mask): mask is uint8
     [B,1,oh,ow] at the feature resolution `mask_hw` = (oh, ow) -- the cells the nearest-neighbour resize of ace_trainer.py:373-374 reads -- or
     None. Same arithmetic as warp_views (tests/test_buffer_gpu.py: values to 1e-5, masks identical)."""

@@ -539,8 +539,8 @@ int acez_buffer_sample_views_table(const void* d_features, int64_t n_feature_row
 
 /* Augmented training views of resident frames (dataset.py:283-343: resize by a common factor, rotate about the centre, ColorJitter
  * brightness / contrast on the grey values, a validity mask that goes through the same warp with zero padding), the step in front of the
- * encoder when ace_trainer.py:293-452 fills the buffer with --use_aug True. One launch per batch of views of one canvas size (+ a
- * per-view reduction when jitter is on) instead of a dozen framework kernels and a 157 MB sampling grid per 64 views.
+ * encoder when ace_trainer.py:293-452 fills the buffer with --use_aug True. Up to three launches per batch of views of one canvas size
+ * (the warp; + a per-view reduction when jitter is on; + the mask when one is asked for) instead of a dozen framework kernels and a 157 MB sampling grid per 64 views.
  *   d_images      float32 [n_images][H][W] normalised grey frames, resident on the device
  *   d_image_index int32 [n_views]: the frame each view is taken from
  *   d_theta       float32 [n_views][6]: the affine map of torch.nn.functional.affine_grid(align_corners=False) -- normalised output
