@@ -100,6 +100,8 @@ SYMBOLS = {
     "acez_ransac_debug_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acez_register_rgbd_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RansacParams),
                                             C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "acez_camera_coordinates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p]),
     "acez_register_rgbd_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                           C.c_int64, C.c_int, C.c_int, C.POINTER(RansacParams), C.c_uint64, C.c_uint64, C.c_void_p,
                                           C.POINTER(C.c_int32), C.c_void_p]),

@@ -122,7 +122,7 @@ REGISTER_FLAGS = [
 
 # ace_zero.py:41-177
 ACE_ZERO_FLAGS = [
-    (("--depth_files",), str, None, None, "depth maps (16 bit, millimetres) for the seed images; without them the reference downloads ZoeDepth"),
+    (("--depth_files",), str, None, None, "depth maps (16 bit, millimetres), one per image: read for the seed images, with --rgbd True for every image in every round; without them the reference downloads ZoeDepth"),
     (("--iterations_max",), int, 100, None, "maximum number of mapping / relocalisation rounds"),
     (("--registration_threshold",), float, 0.99, None, "stop when this ratio of images is registered"),
     (("--relative_registration_threshold",), float, 0.01, None, "stop when fewer new images than this were registered"),
@@ -231,6 +231,19 @@ def ace_zero_parser():
     p.add_argument("--encoder_path", type=Path, default=Path(__file__).resolve().parent.parent / "ace_encoder_pretrained.pt",
                    help="[additive] pre-trained encoder weights (train_ace.py / register_mapping.py take the same flag)")
     _add_dtype(p)
+    return p
+
+
+def ace_zero_cli_parser():
+    """What ace_zero.py parses: ace_zero_parser() -- the reference's flag surface, which tests/test_cli.py pins -- plus the flags of the
+    modes the reference does not have."""
+    p = ace_zero_parser()
+    p.add_argument("--rgbd", type=_strtobool, default=False,
+                   help="[additive] RGB-D reconstruction: --depth_files must match one depth map per image (not only the seeds'); every "
+                        "mapping round is depth-supervised and every registration DSAC*'s RGB-D estimator, so the result is in the "
+                        "sensor's metres. --ransac_threshold is then read in CENTIMETRES of 3D distance (10 = 10 cm), as "
+                        "register_mapping_rgbd.py reads --threshold, and the distance errors are clamped at 100 cm; "
+                        "--registration_confidence stays an inlier count over cells. One GPU.")
     return p
 
 
@@ -839,7 +852,7 @@ def frame_shapes(frames, n):
 def ace_zero_main(argv=None):
     import torch
     from .session import ReconstructionSession, default_options, write_pose_file
-    opt = ace_zero_parser().parse_args(argv)
+    opt = ace_zero_cli_parser().parse_args(argv)
     # `torchrun --nproc-per-node G ace_zero.py ...`: one process per GPU (RCCL). Frames, buffer and registration are sharded inside
     # the session; rank 0 writes the files. Without torchrun this is the single-GPU run.
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -853,6 +866,10 @@ def ace_zero_main(argv=None):
             raise SystemExit("--export_point_cloud True runs on one GPU: export from the written pose file with export_point_cloud.py")
         if opt.render_visualization:
             raise SystemExit("--render_visualization True runs on one GPU")
+        if opt.rgbd:
+            raise SystemExit("--rgbd True runs on one GPU: the depth-supervised buffer fill is not sharded over ranks (run without torchrun)")
+    if opt.rgbd and opt.depth_files is None:
+        raise SystemExit("--rgbd True needs --depth_files matching one depth map (16 bit, millimetres) per image")
     logging.basicConfig(level=logging.INFO if rank == 0 else logging.WARNING)
     opt.results_folder.mkdir(parents=True, exist_ok=True)
     files, frames, fscale, rgb = load_session_frames(opt.rgb_files, opt.image_resolution, return_rgb=True)

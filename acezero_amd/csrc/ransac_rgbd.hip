@@ -21,7 +21,8 @@
 //            a fixed order, and the errors are recomputed. A rank-deficient inlier set stops the refinement.
 // The host side (workspaces, frame-parameter slots, launch geometry, staging, debug fetch) is ransac_api.hip's, declared in
 // ransac_ctx.h. The stages (compaction, sampling, scoring, refinement) are ransac_rgbd.h's, shared with the backward kernel of
-// ransac_grad.hip; this unit keeps the forward kernel, its LDS size and its entry points.
+// ransac_grad.hip; this unit keeps the forward kernel, its LDS size and its entry points, and the launch that makes the camera
+// coordinates from depth (acez_camera_coordinates).
 #include <hip/hip_runtime.h>
 #include "ransac_math.h"
 #include "acez_common.h"
@@ -115,6 +116,25 @@ __global__ __launch_bounds__(THREADS, 1) void rgbd_kernel(RgbdArgs a) {
   }
 }
 
+// Camera coordinates of the feature-map cell centres (stride x + stride / 2) from measured depth: one thread per cell, one launch for
+// all frames. The operations and their order are dsacstar.camera_coordinates' (the mapping buffer's formula, dataset.py:347-388):
+// ((px - ppx) / f) * d, ((py - ppy) / f) * d, d in float32, IEEE division, nothing contracted; a cell without depth (d == 0) is +0.
+__global__ __launch_bounds__(256) void camera_coords_kernel(const float* __restrict__ depth, const float* __restrict__ focal, float ppx,
+                                                            float ppy, int h, int w, int stride, float* __restrict__ out) {
+  const int hw = h * w;
+  const int cell = blockIdx.x * 256 + threadIdx.x;
+  if (cell >= hw) return;
+  const size_t frame = blockIdx.y;
+  const float d = depth[frame * hw + cell];
+  const float f = focal[frame];
+  const float px = (float)((cell % w) * stride + stride / 2), py = (float)((cell / w) * stride + stride / 2);
+  const bool none = d == 0.f;
+  float* o = out + frame * 3 * hw + cell;
+  o[0] = none ? 0.f : (px - ppx) / f * d;
+  o[hw] = none ? 0.f : (py - ppy) / f * d;
+  o[2 * (size_t)hw] = none ? 0.f : d;
+}
+
 }  // namespace
 
 // ====================================================================================================
@@ -142,6 +162,17 @@ extern "C" int acez_register_rgbd_device(acez_ransac* ctx, const float* d_scene_
   rc = acez_rs::launch(rgbd_kernel<true>, rgbd_kernel<false>, g, n_frames, THREADS, s, a, *slot);
   if (rc == ACEZ_OK) ws.last_hyps = params->hypotheses;
   return rc;
+}
+
+extern "C" int acez_camera_coordinates(const float* d_depth, const float* d_focal, float ppx, float ppy, int n_frames, int h, int w,
+                                       int stride, float* d_out_coords, void* stream) {
+  ACEZ_REQUIRE(d_depth && d_focal && d_out_coords, "null pointer");
+  ACEZ_REQUIRE(n_frames > 0 && n_frames <= 65535 && h > 0 && w > 0 && stride > 0 && (int64_t)h * w <= (1 << 24), "bad shape");
+  if (int rc = acez::require_device("camera coordinates are computed on a gfx950 GPU")) return rc;
+  hipLaunchKernelGGL(camera_coords_kernel, dim3((h * w + 255) / 256, n_frames), dim3(256), 0, (hipStream_t)stream, d_depth, d_focal, ppx, ppy,
+                     h, w, stride, d_out_coords);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
 }
 
 extern "C" int acez_register_rgbd_host(acez_ransac* ctx, const float* h_scene_coords, int64_t sc_stride_c, int64_t sc_stride_h,

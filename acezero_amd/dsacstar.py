@@ -211,6 +211,24 @@ def camera_coordinates(depth, focal, ppx, ppy, stride=8):
     return torch.stack([(px - cx) / f * d, (py - cy) / f * d, d], dim=1).contiguous()
 
 
+def camera_coordinates_device(depth, focal, ppx, ppy, stride=8):
+    """camera_coordinates as ONE launch (acez_camera_coordinates): depth CUDA float32 [n,h,w], focal one value or one per frame, ppx /
+    ppy the frames' shared principal point. float32 [n,3,h,w] on depth's device, asynchronous on its current stream; bit for bit
+    camera_coordinates' values where there is depth, +0 in all three channels where there is none (depth == 0)."""
+    assert depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 3
+    d = depth.contiguous()
+    n, h, w = d.shape
+    dev = d.device
+    out = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    f = torch.from_numpy(np.broadcast_to(np.asarray(focal, np.float32), (n,)).copy()).to(dev)
+    with torch.cuda.device(dev):
+        N.check(N.lib().acez_camera_coordinates(C.c_void_p(d.data_ptr()), C.c_void_p(f.data_ptr()), float(ppx), float(ppy), n, h, w, int(stride),
+                                                C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
 def forward_rgbd(sceneCoordinates, cameraCoordinates, outPose, ransacHypotheses, inlierThreshold, inlierAlpha, maxDistError):
     """The reference's commented-out binding (dsacstar.cpp:493-640,901): 1x3xHxW scene and camera coordinates (metres), in-place
     cam->world `outPose`, inlierThreshold / maxDistError in centimetres; returns the inlier count. As in forward_rgb, the per-process

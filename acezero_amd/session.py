@@ -84,12 +84,48 @@ def default_options(**over):
              # register_mapping.py flags (:63-72)
              inlieralpha=100.0, maxpixelerror=100.0,
              # [additive] 16-bit operand format of encoder and head: "bf16" / "fp16" (the reference's autocast arithmetic); None: $ACEZ_DTYPE, else head.DEFAULT_DTYPE
-             compute_dtype=None)
+             compute_dtype=None,
+             # [additive] RGB-D reconstruction: a depth map for every frame; every mapping round is depth-supervised and
+             # every registration DSAC*'s RGB-D estimator, with ransac_threshold / maxpixelerror read in CENTIMETRES
+             rgbd=False)
     unknown = set(over) - set(o)
     if unknown:
         raise TypeError(f"unknown options: {sorted(unknown)}")
     o.update(over)
     return SimpleNamespace(**o)
+
+
+def ransac_params(opt, use_depth=False, max_tries=16):
+    """The DSAC* parameters a registration runs with (dsacstar._params' arguments). The numbers are the options' in both modes; what
+    changes is their unit: RGB reads ransac_threshold and maxpixelerror as pixels of reprojection error, RGB-D (use_depth) as
+    CENTIMETRES of 3D distance (register_mapping_rgbd.py's convention, dsacstar.cpp:498-500) -- 10 is 10 px or 10 cm, 100 is 100 px or
+    1 m. {"unit": ...} names it for logs and tests and is not passed on."""
+    return dict(hyps=int(opt.ransac_iterations), thr=float(opt.ransac_threshold), alpha=float(opt.inlieralpha), max_reproj=float(opt.maxpixelerror),
+                sub=8, max_tries=int(max_tries), unit="cm" if use_depth else "px")
+
+
+def check_rgbd_mode(images, depth, world=1):
+    """RGB-D mode (default_options(rgbd=True)) needs a depth map for EVERY frame, at the frame's own feature resolution, and runs in one
+    process. images / depth as ReconstructionSession takes them. Raises before any frame is encoded."""
+    if world > 1:
+        raise RuntimeError("--rgbd True runs on one GPU: the depth-supervised buffer fill is not sharded over ranks (run without torchrun)")
+    parts = [(range(images.shape[0]), images)] if torch.is_tensor(images) else list(images)
+    cells = {}
+    for pos, t in parts:
+        for i in pos:
+            cells[int(i)] = tuple(output_size(int(t.shape[2]), int(t.shape[3])))
+    n = len(cells)
+    why = "--rgbd True needs a depth map for every frame (ace_zero.py --depth_files, one file per image): "
+    if depth is None:
+        raise RuntimeError(why + "there is none")
+    if len(depth) != n:
+        raise RuntimeError(why + f"{len(depth)} depth maps for {n} frames")
+    for i in range(n):
+        d = depth[i]
+        if d is None:
+            raise RuntimeError(why + f"frame {i} has none")
+        if tuple(d.shape) != cells[i]:
+            raise RuntimeError(why + f"frame {i}'s has {tuple(d.shape)} cells for {cells[i][0]} x {cells[i][1]} scene coordinates")
 
 
 def warp_views(images_b1hw, scale, angles, jitter=None):
@@ -194,9 +230,11 @@ class ReconstructionSession:
         registration is sharded by frame with one gather of the poses, a mapping round shards the training buffer by image and
         sums the flat gradient bucket with one all-reduce per step (global batch unchanged), the seed trials run on different
         ranks side by side. Every rank takes the same decisions from the same gathered numbers; rank 0 writes the files."""
+        self.opt = opt or default_options()
+        if getattr(self.opt, "rgbd", False):                             # refused on the arguments alone: before the device, before any encoding
+            check_rgbd_mode(images, depth, rank_world(group)[1])
         if not torch.cuda.is_available():
             raise RuntimeError("ReconstructionSession needs a GPU: every stage is a HIP kernel (no CPU fallback)")
-        self.opt = opt or default_options()
         parts = [(np.arange(images.shape[0]), images)] if torch.is_tensor(images) else [(np.asarray(p, np.int64).reshape(-1), t) for p, t in images]
         n = sum(len(p) for p, _ in parts)
         if sorted(int(i) for p, _ in parts for i in p) != list(range(n)):
@@ -726,8 +764,8 @@ class ReconstructionSession:
         each with that frame's uint8 RGB image inside its frustum: images[i] for frame i (default: the visualiser's frame_rgb; none:
         outlines only).
         use_depth: RGB-D registration (dsacstar.forward_rgbd's estimator) from the session's depth maps: camera coordinates at the cell
-        centres (dsacstar.camera_coordinates, the mapping buffer's formula with each frame's focal and its class's principal point),
-        ransac_threshold and maxpixelerror read as centimetres."""
+        centres (dsacstar.camera_coordinates_device: one launch per size class; the mapping buffer's formula with each frame's focal
+        and its class's principal point), ransac_threshold and maxpixelerror read as centimetres (ransac_params)."""
         o = self.opt
         if use_depth and self.depth is None:
             raise RuntimeError("register(use_depth=True) needs the session's depth maps (depth=...)")
@@ -739,7 +777,8 @@ class ReconstructionSession:
         self.registered_ids = ids
         t0 = time.time()
         mine = ids[ids % self.world == self.rank]
-        prm = dict(hyps=o.ransac_iterations, thr=o.ransac_threshold, alpha=float(o.inlieralpha), max_reproj=float(o.maxpixelerror), sub=8, max_tries=max_tries)
+        prm = ransac_params(o, use_depth, max_tries)
+        prm.pop("unit")
         poses, inl = torch.zeros(len(mine), 4, 4), torch.zeros(len(mine), dtype=torch.int32)
         for ci, c in enumerate(self.classes):
             at = np.flatnonzero(self.frame_class[mine] == ci)
@@ -749,7 +788,8 @@ class ReconstructionSession:
             sc = self.scene_coordinates(head_sd, sub)
             keys = [int(i) for i in sub] if rng_ids is None else [int(rng_ids[i]) for i in sub]
             if use_depth:
-                cc = dsacstar.camera_coordinates(self.frame_depth(sub), [focal * self.frel[i] for i in sub], c.ppx, c.ppy)
+                # one launch per class: depth (resident), every frame's focal, the class's principal point -> [k,3,oh,ow] on the device
+                cc = dsacstar.camera_coordinates_device(self.frame_depth(sub), [focal * self.frel[i] for i in sub], c.ppx, c.ppy)
                 p_, i_, _ = dsacstar.register_batch_rgbd(sc, cc, prm, o.register_seed, keys, want_masks=False)
             else:
                 p_, i_, _ = dsacstar.register_batch(sc, [(focal * self.frel[i], c.ppx, c.ppy) for i in sub], prm, o.register_seed, keys,
@@ -820,12 +860,21 @@ class ReconstructionSession:
         return trials
 
     def score_seed(self, seed_idx, m):
-        _, inl = self.register(m["head"], self.focal0, max_estimates=self.opt.max_estimates_seed_scoring, tag=f"iteration0_seed{seed_idx}_fastcheck")
+        _, inl = self.register(m["head"], self.focal0, max_estimates=self.opt.max_estimates_seed_scoring, tag=f"iteration0_seed{seed_idx}_fastcheck",
+                               **self._rgbd_kw("use_depth"))
         return float((inl > self.opt.registration_confidence).mean())
+
+    def _rgbd_kw(self, name):
+        """{name: True} in RGB-D mode, nothing otherwise (the RGB loop's calls stay exactly as they were)."""
+        return {name: True} if getattr(self.opt, "rgbd", False) else {}
 
     def reconstruct(self, seed_parallel_workers=1, render=None):
         """ace_zero.py's loop. seed_parallel_workers: seed trials trained side by side per group (seed_groups; ace_zero.py
         --seed_parallel_workers); 1 maps and scores the seeds one after the other. The result is the same for every value.
+
+        With default_options(rgbd=True) every map() of the loop is depth-supervised (with_depth=True: targets from the round's incoming
+        poses and the frames' depth) and every register() is the RGB-D estimator (use_depth=True: ransac_threshold / maxpixelerror in
+        centimetres, confidence = its inlier count over cells); decisions, warm start, refinement and the outputs are the RGB loop's.
 
         render (ace_zero.py --render_visualization, one GPU): render(mapping_state_name, existing_state) -> a fresh
         acezero_amd.render.Visualizer. As the reference does, the best seed is mapped again with the video on, and every round's mapping
@@ -835,14 +884,17 @@ class ReconstructionSession:
         if render is not None and self.world > 1:
             raise RuntimeError("the reconstruction video is rendered by a single-GPU run")
         prev_state = None
+        reg_kw, map_kw = self._rgbd_kw("use_depth"), self._rgbd_kw("with_depth")
+        if reg_kw and self.world > 1:
+            raise RuntimeError("--rgbd True runs on one GPU: the depth-supervised buffer fill is not sharded over ranks (run without torchrun)")
 
         def register_rendered(head, focal, tag):
             nonlocal prev_state
             if render is None or (tag == "seed_network"):
-                return self.register(head, focal, tag=tag)
+                return self.register(head, focal, tag=tag, **reg_kw)
             vis = render(f"{tag}_mapping.pkl", None)
             vis.setup_reloc(self.n)
-            out = self.register(head, focal, tag=tag, visualizer=vis)
+            out = self.register(head, focal, tag=tag, visualizer=vis, **reg_kw)
             prev_state = f"{tag}_register.pkl"
             vis.save_reloc_state(os.path.join(vis.target_path, prev_state))
             return out
@@ -899,7 +951,7 @@ class ReconstructionSession:
             if render is not None:
                 kw["visualizer"] = render(f"iteration{iteration}_mapping.pkl", prev_state)
             current = self.map(sel, torch.from_numpy(poses[sel]), focal, refinement=o.refinement, refine_calibration=o.refine_calibration,
-                               load_weights=current["head"] if warm else None, tag=f"iteration{iteration}", **kw)
+                               load_weights=current["head"] if warm else None, tag=f"iteration{iteration}", **kw, **map_kw)
             focal = current["focal"]                                     # ace_zero.py:297-305: the refined focal goes to the registration
             poses, conf = register_rendered(current["head"], focal, f"iteration{iteration}")
             rate = float((conf > o.registration_confidence).mean())

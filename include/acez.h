@@ -155,6 +155,18 @@ int acez_register_rgbd_device(acez_ransac* ctx, const float* d_scene_coords, con
                               const uint64_t* h_frame_ids, float* d_out_poses, int32_t* d_out_inliers,
                               uint8_t* d_out_masks, void* stream);
 
+/* Camera coordinates for acez_register_rgbd_device from measured depth, in ONE launch for all frames: the back-projection of the
+ * feature-map cell centres (stride * x + stride / 2, stride * y + stride / 2).
+ *   d_depth        float32 [n_frames][h][w] camera z at the cell centres, metres; 0 = no depth
+ *   d_focal        float32 [n_frames] each frame's focal length, pixels (device memory)
+ *   ppx, ppy       principal point shared by the frames, pixels
+ *   d_out_coords   float32 [n_frames][3][h][w]: ((px - ppx) / f * d, (py - ppy) / f * d, d), evaluated in float32 in exactly this
+ *                  order (the mapping buffer's formula, so mapping targets and registration agree bit for bit); +0 in all three
+ *                  channels where d == 0
+ * Asynchronous on `stream`. */
+int acez_camera_coordinates(const float* d_depth, const float* d_focal, float ppx, float ppy, int n_frames, int h, int w,
+                            int stride, float* d_out_coords, void* stream);
+
 /* Host-buffer variant of dsacstar.forward_rgbd for ONE frame; strides in elements for each tensor. Synchronous. */
 int acez_register_rgbd_host(acez_ransac* ctx, const float* h_scene_coords, int64_t sc_stride_c, int64_t sc_stride_h,
                             int64_t sc_stride_w, const float* h_camera_coords, int64_t cc_stride_c,
