@@ -181,6 +181,9 @@ SYMBOLS = {
                                         C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acez_render_camera": (C.c_int, [C.POINTER(C.c_double), C.c_float, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_float),
                                      C.POINTER(C.c_float)]),
+    "acez_ingest_coeffs": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
+    "acez_ingest_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

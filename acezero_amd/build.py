@@ -18,8 +18,8 @@ STAMP = os.path.join(HERE, ".libacez.stamp")
 LIB_DIAG = os.path.join(HERE, "libacez_diag.so")
 STAMP_DIAG = os.path.join(HERE, ".libacez_diag.stamp")
 
-# translation unit -> extra flags.  The RANSAC (RGB and RGB-D), point-cloud, pose-evaluation and rendering units must not contract a*b+c into fma: their arithmetic
-# is compared bit-for-bit with the CPU oracle (DESIGN.md "Determinism").
+# translation unit -> extra flags.  The RANSAC (RGB and RGB-D), point-cloud, pose-evaluation, rendering and ingest units must not contract a*b+c into fma: their
+# arithmetic is compared bit-for-bit with the CPU oracle (DESIGN.md "Determinism"); the ingest unit's host-side tables with Pillow's.
 UNITS = {
     "acez_common.hip": [],
     "head_api.hip": [],
@@ -32,6 +32,7 @@ UNITS = {
     "cloud_api.hip": ["-ffp-contract=off"],
     "align_api.hip": ["-ffp-contract=off"],
     "render_api.hip": ["-ffp-contract=off"],
+    "ingest_api.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -157,7 +157,7 @@ ACE_ZERO_FLAGS = [
     (("--repro_loss_hard_clamp",), int, 1000, None, ""),
     (("--repro_loss_soft_clamp",), int, 50, None, ""),
     (("--aug_rotation",), int, 15, None, ""),
-    (("--num_data_workers",), int, 12, None, "accepted; frames are decoded once by the main process"),
+    (("--num_data_workers",), int, 12, None, "accepted; frames are decoded once by the main process (with --gpu_ingest True: decode threads)"),
     (("--training_buffer_cpu",), _strtobool, False, None, "accepted; the buffer lives in HBM"),
     (("--ransac_iterations",), int, 32, None, ""),
     (("--ransac_threshold",), float, 10, None, ""),
@@ -247,6 +247,27 @@ def ace_zero_cli_parser():
     return p
 
 
+def with_ingest_flag(p):
+    """What the image-reading scripts parse on top of their parser: the surfaces that tests/test_cli.py pins stay as they are."""
+    p.add_argument("--gpu_ingest", type=_strtobool, default=False,
+                   help="[additive] read the images through acezero_amd.ingest: --num_data_workers threads (at most 16) decode the files, "
+                        "resize, grey conversion and normalisation run as HIP kernels on the decoded frames. The frames, and so every "
+                        "result, are bit for bit those of the default host path.")
+    return p
+
+
+def _frame_loaders(opt):
+    """(load_frames, load_session_frames) of a run: the host functions below or, with --gpu_ingest True, their device counterparts
+    with --num_data_workers decode threads."""
+    if not getattr(opt, "gpu_ingest", False):
+        return load_frames, load_session_frames
+    import functools
+    from . import ingest
+    workers = getattr(opt, "num_data_workers", 12)
+    return (functools.partial(ingest.load_frames_device, workers=workers),
+            functools.partial(ingest.load_session_frames_device, workers=workers))
+
+
 def export_point_cloud_parser():
     """export_point_cloud.py:26-58."""
     p = argparse.ArgumentParser(description="Extract point cloud from network or visualization buffer file; .txt and .ply are supported.",
@@ -289,7 +310,7 @@ def save_feature_buffer(path, prob, image_files=None, with_depth_targets=False):
 
 # ------------------------------------------------------------------------------------------------------------ train
 def train_main(argv=None):
-    opt = train_parser().parse_args(argv)
+    opt = with_ingest_flag(train_parser()).parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     return train_with_options(opt)
 
@@ -482,6 +503,7 @@ def _train_from_images(opt):
     import torch
     from .session import ReconstructionSession
     rgb = None
+    _, load_session_frames = _frame_loaders(opt)
     if opt.use_ace_pose_file is not None:
         files, poses, focals = read_ace_pose_file(opt.use_ace_pose_file, opt.ace_pose_file_conf_threshold)
         files, frames, fscale, *rgb = load_session_frames(None, opt.image_resolution, files=files, return_rgb=opt.render_visualization)
@@ -567,6 +589,7 @@ def _register_mixed_sizes(opt, files, classes, depth_files=None):
     else:
         chosen = np.sort(torch.randperm(n, generator=torch.Generator().manual_seed(int(opt.base_seed)))[:opt.max_estimates].numpy())
     keep = set(int(i) for i in chosen)
+    load_frames, _ = _frame_loaders(opt)
     vis = None
     if opt.render_visualization:                                         # one video over all size classes, in size-class order
         vis = _register_visualizer(opt)
@@ -612,6 +635,7 @@ def _register_from_images(opt, depth_files=None):
     all_files, classes = frame_size_classes(opt.rgb_files)
     if len(classes) > 1:
         return _register_mixed_sizes(opt, all_files, classes, depth_files)
+    load_frames, _ = _frame_loaders(opt)
     files, frames, fscale, *rgb = load_frames(opt.rgb_files, opt.image_resolution, return_rgb=opt.render_visualization)
     depth = None
     if depth_files is not None:
@@ -640,7 +664,7 @@ def register_main(argv=None):
     import torch
     from . import dsacstar
     from .head import HeadTrainer
-    opt = register_parser().parse_args(argv)
+    opt = with_ingest_flag(register_parser()).parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     if opt.feature_file is None:
         return _register_from_images(opt)
@@ -697,7 +721,7 @@ def register_rgbd_main(argv=None):
     of every image gives camera coordinates at the feature-map cells, --threshold / --maxpixelerror are centimetres. Writes the same
     poses_<session>.txt."""
     import glob
-    opt = register_rgbd_parser().parse_args(argv)
+    opt = with_ingest_flag(register_rgbd_parser()).parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     if opt.feature_file is not None:
         raise SystemExit("register_mapping_rgbd.py reads the images and their depth maps; --feature_file holds neither the frames' pixels "
@@ -852,7 +876,7 @@ def frame_shapes(frames, n):
 def ace_zero_main(argv=None):
     import torch
     from .session import ReconstructionSession, default_options, write_pose_file
-    opt = ace_zero_cli_parser().parse_args(argv)
+    opt = with_ingest_flag(ace_zero_cli_parser()).parse_args(argv)
     # `torchrun --nproc-per-node G ace_zero.py ...`: one process per GPU (RCCL). Frames, buffer and registration are sharded inside
     # the session; rank 0 writes the files. Without torchrun this is the single-GPU run.
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -872,7 +896,7 @@ def ace_zero_main(argv=None):
         raise SystemExit("--rgbd True needs --depth_files matching one depth map (16 bit, millimetres) per image")
     logging.basicConfig(level=logging.INFO if rank == 0 else logging.WARNING)
     opt.results_folder.mkdir(parents=True, exist_ok=True)
-    files, frames, fscale, rgb = load_session_frames(opt.rgb_files, opt.image_resolution, return_rgb=True)
+    files, frames, fscale, rgb = _frame_loaders(opt)[1](opt.rgb_files, opt.image_resolution, return_rgb=True)
     mixed = not torch.is_tensor(frames)                                  # a folder of several frame sizes: its size classes
     frame_focals = None
     if mixed:
@@ -980,7 +1004,7 @@ def export_point_cloud_main(argv=None):
     import pickle
     import torch
     from .pointcloud import write_point_cloud
-    parser = export_point_cloud_parser()
+    parser = with_ingest_flag(export_point_cloud_parser())
     opt = parser.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     if opt.visualization_buffer is None and (opt.network is None or opt.pose_file is None):
@@ -998,7 +1022,7 @@ def export_point_cloud_main(argv=None):
         files, c2w, focals = read_ace_pose_file(opt.pose_file, opt.confidence_threshold)
         if not files:
             raise SystemExit("no pose above the confidence threshold")
-        files, frames, fscale, rgb = load_session_frames(None, opt.image_resolution, files=files, return_rgb=True)
+        files, frames, fscale, rgb = _frame_loaders(opt)[1](None, opt.image_resolution, files=files, return_rgb=True)
         frame_focals = None
         if torch.is_tensor(frames):
             assert np.allclose(focals, focals[0]), "a single focal length is supported"

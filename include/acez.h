@@ -703,6 +703,37 @@ int acez_render_frame_tex(const float* d_xyz, const uint8_t* d_rgb, int64_t n_po
  * cam_to_world, computed in double and rounded once; out_focal = (height / 2) * sqrt(3) in pixels. Same argument checks. */
 int acez_render_camera(const double* cam_to_world, float znear, float zfar, int width, int height, float* out_w2c12, float* out_focal);
 
+/* =====================================================================================================
+ * I. Image ingest (the reference's per-frame image path, dataset.py:189-195,227-237,146-160,293)
+ * =====================================================================================================
+ * Decoded uint8 RGB frames -> what Pillow's 8-bit resize(BILINEAR), convert("L") and the host's normalisation give, bit for bit:
+ *   resize      separable, horizontal pass first, its result kept as uint8. For output index xx of an axis of `in` -> `out` samples:
+ *               scale = in / out, fs = max(scale, 1), support = fs, center = (xx + 0.5) * scale, xmin = max(int(center - support
+ *               + 0.5), 0), xmax = min(int(center + support + 0.5), in); the tap at source index xmin + x is tri((x + xmin - center
+ *               + 0.5) / fs) with tri(v) = max(0, 1 - |v|); the taps are summed in order in double, each divided by the sum and fixed
+ *               to int(0.5 + k * 2^22); a pass computes (2^21 + sum pixel * k) >> 22 clipped to 0 .. 255;
+ *   grey        L = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16;
+ *   normalise   d_norm[L]: a float32 table of 256 entries the caller builds (the host path's own expression applied to 0 .. 255), so
+ *               the device does no float arithmetic.
+ * acez_ingest_coeffs: the table of one axis (host only, no device needed; the CPU tests check it against a restatement, and callers
+ * size d_tables with its ksize). out_ksize = ceil(support) * 2 + 1; out_bounds int32 [out][2] = (xmin, tap count); out_taps int32
+ * [out][ksize], zero past the tap count. out_bounds / out_taps may be NULL (ksize only). Tables are cached per (in, out) pair. */
+int acez_ingest_coeffs(int in_size, int out_size, int* out_ksize, int32_t* out_bounds, int32_t* out_taps);
+/* n frames of one source size in two launches on `stream` (horizontal: d_src -> d_tmp; vertical + grey + table: -> outputs), after
+ * the two axes' tables have been copied into d_tables on the same stream. Asynchronous; nothing is allocated; every pointer is owned
+ * by the caller:
+ *   d_src       uint8 [n][H][W][3]
+ *   d_tmp       uint8 [n][H][nw][3] scratch
+ *   d_tables    int32 scratch of table_bytes >= 4 * (nw * (2 + ksize_x) + nh * (2 + ksize_y)) bytes, ksize_x / ksize_y from
+ *               acez_ingest_coeffs(W, nw) / (H, nh). Calls that share it must share the stream.
+ *   d_norm      float32 [256]
+ *   d_out_rgb   uint8 [n][nh][nw][3], or NULL
+ *   d_out_grey  float32 [n][1][nh][nw]
+ * ACEZ_ERR_INVALID, before anything is launched, for: a null pointer (other than d_out_rgb), n outside 1 .. 65535, a side outside
+ * 1 .. 32768, a resized frame of more than 16384 scene coordinates (what the registration kernel takes), a table block too small. */
+int acez_ingest_frames(const uint8_t* d_src, int n, int H, int W, int nh, int nw, uint8_t* d_tmp, int32_t* d_tables, int64_t table_bytes,
+                       const float* d_norm, uint8_t* d_out_rgb, float* d_out_grey, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
