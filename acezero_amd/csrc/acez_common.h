@@ -33,9 +33,10 @@ int require_device(const char* what);
 // there (the measured-and-rejected kernels of rounds 1-5 -- chain_kernel, headfwd_kernel, headinfer_kernel, the 128-row rowgemm tiling,
 // wgrad256_kernel, conv12_kernel, conv3x3p_kernel -- and the timing-only ablation switches live in the git history and in
 // DESIGN_HISTORY.md, not in the tree). In the product library ACEZ_DIAG_ENV() is a null constant -- every
-// `if (const char* e = ACEZ_DIAG_ENV("..."))` folds away -- and no environment variable can change a result. The product reads exactly two
-// variables (head_api.hip): ACEZ_SEQ=0 (per-layer launches instead of the one-launch chains; bit-identical results) and ACEZ_SEQ_SPIN_US
-// (the hand-off poll budget).
+// `if (const char* e = ACEZ_DIAG_ENV("..."))` folds away -- and no environment variable can change a result. The product reads exactly three
+// variables (head_api.hip): ACEZ_SEQ=0 (per-layer launches instead of the one-launch chains; bit-identical results), ACEZ_LOSS_IN_CHAIN=0
+// (the fused step's loss as a launch of its own instead of stage -1 of the input-gradient launch; bit-identical results) and
+// ACEZ_SEQ_SPIN_US (the hand-off poll budget).
 #ifdef ACEZ_DIAG
 #include <stdlib.h>
 #define ACEZ_DIAG_ENV(name) getenv(name)

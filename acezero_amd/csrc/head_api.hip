@@ -114,6 +114,10 @@ struct acez_trainer {
   uint32_t seq_spin_limit = 40000;     // polls (>= ~0.5 us each: at least ~20 ms); ACEZ_SEQ_SPIN_US overrides (2 polls per us)
   int seq_faults = 0;                  // fall-backs taken so far
   int seq_probe = -1;                  // -1 not run, 0 failed (seq disabled), 1 passed
+  // The fused step's loss launch as stage -1 of the input-gradient chain's launch, the next batch's gather in its idle loader waves
+  // (rowseq_loss_kernel): three launches per step. ACEZ_LOSS_IN_CHAIN=0 = loss_kernel / loss_gather_kernel as a launch of their own
+  // (bit-identical results).
+  bool loss_in_chain = true;
   long seq_launches = 0, seq_fault_at = -1;   // tests: ACEZ_SEQ_FAULT_AT=<n> makes the n-th launch time out
   // wgrad_opt_kernel (head_kernels.hip): the optimiser step of the wide layers inside the weight-gradient launch of the single-GPU fused
   // step. Same placement contract and safety net as the one-launch chains (tr->seq, the probe, the bounded poll, seq_err): usable only
@@ -339,6 +343,7 @@ extern "C" int acez_trainer_create(acez_trainer** out, const acez_train_config* 
   tr->fc3_stride = ((int64_t)tr->no * 513 + 3) & ~3LL;
   tr->max_batch = cfg->max_batch;
   if (const char* e = getenv("ACEZ_SEQ")) tr->seq = atoi(e) != 0;
+  if (const char* e = getenv("ACEZ_LOSS_IN_CHAIN")) tr->loss_in_chain = atoi(e) != 0;
   {
     hipDeviceProp_t prop;
     ACEZ_HIP_CHECK(hipGetDeviceProperties(&prop, tr->device));
@@ -538,10 +543,14 @@ static bool wgrad_opt_usable(const acez_trainer* tr) {
          tr->cfg.pose_refinement == 0 && 256 * ((tr->L + 7) / 8) <= tr->n_cus;
 }
 
+// head != null (input gradients only): the chain's first launch is rowseq_loss_kernel -- the loss of the batch as its stage -1, one
+// hand-off more than its layers have between them
 template <bool BWD>
-static void launch_rowseq(acez_trainer* tr, const std::vector<SeqLayer>& layers, int n, const TrainState* st, hipStream_t s) {
+static void launch_rowseq(acez_trainer* tr, const std::vector<SeqLayer>& layers, int n, const TrainState* st, hipStream_t s,
+                          const SeqLossArgs* head = nullptr) {
   const int mtiles = (n + 79) / 80;
   for (size_t i0 = 0; i0 < layers.size(); i0 += SEQ_MAX_LAYERS) {
+    const bool with_loss = BWD && head && i0 == 0;
     RowSeqArgs a{};
     const int cnt = (int)std::min<size_t>(SEQ_MAX_LAYERS, layers.size() - i0);
     for (int i = 0; i < cnt; ++i) a.layer[i] = layers[i0 + i];
@@ -549,12 +558,16 @@ static void launch_rowseq(acez_trainer* tr, const std::vector<SeqLayer>& layers,
     for (int mt = 0; mt < 64; ++mt) a.base[mt] = tr->seq_base[mt];
     // tests (ACEZ_SEQ_FAULT_AT): this launch is told that a million seams have completed before it -- every hand-off then waits
     // for a count that never comes, which is what a sibling on a foreign XCD looks like
-    if (cnt > 1 && tr->seq_launches == tr->seq_fault_at)
+    if ((cnt > 1 || with_loss) && tr->seq_launches == tr->seq_fault_at)
       for (int mt = 0; mt < 64; ++mt) a.base[mt] += 1u << 20;
     ++tr->seq_launches;
-    if (tr->f16) hipLaunchKernelGGL((rowseq_kernel<BWD, EltF16>), dim3(32 * ((mtiles + 7) / 8)), dim3(512), 0, s, a);
+    if (with_loss) {
+      if (tr->f16) hipLaunchKernelGGL(rowseq_loss_kernel<EltF16>, dim3(32 * ((mtiles + 7) / 8)), dim3(512), 0, s, a, *head);
+      else hipLaunchKernelGGL(rowseq_loss_kernel<EltBf16>, dim3(32 * ((mtiles + 7) / 8)), dim3(512), 0, s, a, *head);
+    }
+    else if (tr->f16) hipLaunchKernelGGL((rowseq_kernel<BWD, EltF16>), dim3(32 * ((mtiles + 7) / 8)), dim3(512), 0, s, a);
     else hipLaunchKernelGGL(rowseq_kernel<BWD>, dim3(32 * ((mtiles + 7) / 8)), dim3(512), 0, s, a);
-    for (int mt = 0; mt < mtiles; ++mt) tr->seq_base[mt] += (uint32_t)(cnt - 1);
+    for (int mt = 0; mt < mtiles; ++mt) tr->seq_base[mt] += (uint32_t)(cnt - 1 + (with_loss ? 1 : 0));
     tr->prof_launches += cnt;   // accounted as layer GEMMs so that the per-layer average stays comparable
   }
 }
@@ -736,6 +749,7 @@ struct StepRun {
   const int64_t* idx; int n;
   const int64_t* next; int n_next;   // the announced next batch (none: null or no rows)
   int nblk;
+  bool loss_in_chain = false;   // the loss runs as stage -1 of the input-gradient chain's launch (train_step_impl decides)
   hipStream_t s, ps;     // ps: the stream of the pose launches the step does not carry (beside the head's chains; else = s)
   const TrainState* st;  // the slot the step reads (known after its begin launch)
 };
@@ -838,8 +852,26 @@ static void launch_train_loss(const StepRun& r) {
   tr->carry.hold(r.next, r.n_next, true);
 }
 
-// The input-gradient chain of a training step (collect != null: nothing is launched, the one-launch chain's layer table goes to *collect)
-static void launch_dgrad(acez_trainer* tr, int n, const TrainState* st, hipStream_t s, std::vector<SeqLayer>* collect = nullptr) {
+// The loss of a fused step as stage -1 of its input-gradient launch (rowseq_loss_kernel): launch_train_loss's arguments and record
+static SeqLossArgs train_loss_in_chain(const StepRun& r) {
+  acez_trainer* tr = r.tr;
+  SeqLossArgs x{};
+  fill_loss_train(tr, x.loss, tr->out[3 * (tr->nb + 1) + 1], r.idx, r.n, false);
+  x.nblk = r.nblk;
+  tr->last_nblk = r.nblk;
+  if (r.plan.next_at == NextAt::Loss) {
+    x.feat = (const uint16_t*)tr->buf.d_features; x.idx_next = r.next; x.out_next = tr->R0_alt; x.n_next = r.n_next;
+    x.meta = gather_meta(tr);
+    x.meta.dst = tr->batch_meta_alt;
+    tr->carry.hold(r.next, r.n_next, true);
+  }
+  return x;
+}
+
+// The input-gradient chain of a training step (collect != null: nothing is launched, the one-launch chain's layer table goes to *collect;
+// inchain != null: the step's loss and the next batch's gather ride in the chain's launch)
+static void launch_dgrad(acez_trainer* tr, int n, const TrainState* st, hipStream_t s, std::vector<SeqLayer>* collect = nullptr,
+                         const StepRun* inchain = nullptr) {
   const int f1 = 3 * (tr->nb + 1), f2 = f1 + 1;
   const bool seq = collect || seq_usable(tr, n);
   std::vector<SeqLayer> sq;
@@ -875,7 +907,12 @@ static void launch_dgrad(acez_trainer* tr, int n, const TrainState* st, hipStrea
     }
   }
   if (collect) *collect = sq;
+  else if (seq && inchain) {
+    const SeqLossArgs x = train_loss_in_chain(*inchain);
+    launch_rowseq<true>(tr, sq, n, st, s, &x);
+  }
   else if (seq) launch_rowseq<true>(tr, sq, n, st, s);
+  else if (inchain) abort();   // (train_step_impl only asks for it where the one-launch chain runs)
 }
 
 // The partial buffers of a step and its weight-gradient launch (wgrad_opt_kernel: Opt::WgradOpt); the split flow's gradient reduction
@@ -1031,12 +1068,12 @@ static void pose_bwd_launches(acez_trainer* tr, int n, hipStream_t q) {
 }
 
 static StepRun start_run(acez_trainer* tr, Flow flow, const int64_t* idx, int n, const int64_t* next, int n_next, hipStream_t s) {
-  return StepRun{tr, plan_step(tr, flow, idx, n, next, n_next), idx, n, next, n_next, loss_blocks(n), s, tr->pose_stream ? tr->pose_stream : s, nullptr};
+  return StepRun{tr, plan_step(tr, flow, idx, n, next, n_next), idx, n, next, n_next, loss_blocks(n), false, s, tr->pose_stream ? tr->pose_stream : s, nullptr};
 }
 
 // a run's GEMM chain on per-layer launches or rowseq_kernel: forward (bwd = false) or input gradients
 static void launch_chain(const StepRun& r, bool bwd) {
-  if (bwd) launch_dgrad(r.tr, r.n, r.st, r.s);
+  if (bwd) launch_dgrad(r.tr, r.n, r.st, r.s, nullptr, r.loss_in_chain ? &r : nullptr);
   else launch_forward(r.tr, r.tr->R[0], r.n, r.st, r.s);
 }
 
@@ -1064,7 +1101,7 @@ static int run_steps(StepRun* runs, int count, Chains chains) {
     StepRun& r = runs[i];
     acez_trainer* tr = r.tr;
     if (r.ps != r.s) ACEZ_HIP_CHECK(hipStreamWaitEvent(r.s, tr->ev_pose_fwd, 0));   // the loss kernel projects with the refined poses
-    launch_train_loss(r);
+    if (!r.loss_in_chain) launch_train_loss(r);   // (else: stage -1 of the input-gradient launch, launch_dgrad)
     if (r.ps != r.s) {   // the pose gradients start from the per-row pose gradients the loss kernel has just written
       ACEZ_HIP_CHECK(hipEventRecord(tr->ev_loss, r.s));
       ACEZ_HIP_CHECK(hipStreamWaitEvent(r.ps, tr->ev_loss, 0));
@@ -1095,6 +1132,8 @@ static int train_step_impl(acez_trainer* tr, Flow flow, const int64_t* d_indices
   ACEZ_REQUIRE(n > 0 && n <= tr->max_batch, "n must be in [1, max_batch]");
   ACEZ_HIP_CHECK(hipSetDevice(tr->device));
   StepRun r = start_run(tr, flow, d_indices, n, d_next, n_next, (hipStream_t)stream);
+  // three launches: only the single trainer's fused step on the one-launch chains (wgrad_opt_usable: no pose refinement, chains enabled)
+  r.loss_in_chain = tr->loss_in_chain && r.plan.opt == Opt::WgradOpt && seq_usable(tr, n);
   return run_steps(&r, 1, [&](bool bwd) { launch_chain(r, bwd); });
 }
 

@@ -572,6 +572,32 @@ struct RowSeqArgs {
                        // once), flags[64 * 32 + 1] = a copy of the poll budget (diagnostics)
 };
 
+// The layers of a chain for the workgroup of tile (mt, n0). SEAM0 = 1 (rowseq_loss_kernel): one hand-off of this launch lies in front of
+// layer 0 -- its In is produced inside the launch and its first four W stages have been requested by the caller.
+template <bool BWD, class E, int SEAM0>
+__device__ __forceinline__ void rowseq_layers(const RowSeqArgs& a, uint16_t* smem, const int mt, const int n0) {
+  for (int layer = 0; layer < a.n_layers; ++layer) {
+    const SeqLayer& y = a.layer[layer];
+    RowGemmArgs g;
+    g.In = y.In; g.W = y.W; g.bias = y.bias; g.add = y.add; g.mask_out = y.mask_out; g.mask_in = y.mask_in; g.res = y.res; g.out_main = y.out_main; g.out_aux = y.out_aux;
+    g.bias_partials = y.bias_partials; g.M = a.M; g.N = 512; g.K = 512; g.relu = BWD ? 0 : 1; g.aux_mode = y.aux_mode; g.st = a.st;
+    g.absmax = (BWD && a.st) ? const_cast<uint32_t*>(a.st->dz_absmax_slots) : nullptr;
+    SeqLink q;
+    q.flag = a.flags + mt * 32; q.target = (a.base[mt] + (uint32_t)(layer + SEAM0)) * 32u;   // 4 workgroups x 8 waves per seam
+    q.first = !SEAM0 && layer == 0; q.wait = SEAM0 || layer > 0; q.signal = layer + 1 < a.n_layers;
+    q.next_W = q.signal ? a.layer[layer + 1].W : nullptr;
+    q.flag_index = (uint32_t)(mt * 32); q.limit = a.spin_limit;
+    if (!BWD) {
+      if (y.aux_mode == AUX_RESIDUAL) rowgemm80_body<true, false, false, AUX_RESIDUAL, true, E>(g, smem, 1, mt, n0, q);
+      else rowgemm80_body<true, false, false, AUX_NONE, true, E>(g, smem, 1, mt, n0, q);
+    } else {
+      if (y.add) rowgemm80_body<false, true, true, AUX_UNMASKED, true, E>(g, smem, 1, mt, n0, q);
+      else if (y.aux_mode == AUX_UNMASKED) rowgemm80_body<false, false, true, AUX_UNMASKED, true, E>(g, smem, 1, mt, n0, q);
+      else rowgemm80_body<false, false, true, AUX_NONE, true, E>(g, smem, 1, mt, n0, q);
+    }
+  }
+}
+
 template <bool BWD, class E = EltBf16>
 __global__ __launch_bounds__(512) void rowseq_kernel(RowSeqArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t smem[RG80_SMEM_SEQ];
@@ -595,27 +621,7 @@ __global__ __launch_bounds__(512) void rowseq_kernel(RowSeqArgs a) {
     }
     return;
   }
-  const int n0 = (jx & 3) * 128;
-  for (int layer = 0; layer < a.n_layers; ++layer) {
-    const SeqLayer& y = a.layer[layer];
-    RowGemmArgs g;
-    g.In = y.In; g.W = y.W; g.bias = y.bias; g.add = y.add; g.mask_out = y.mask_out; g.mask_in = y.mask_in; g.res = y.res; g.out_main = y.out_main; g.out_aux = y.out_aux;
-    g.bias_partials = y.bias_partials; g.M = a.M; g.N = 512; g.K = 512; g.relu = BWD ? 0 : 1; g.aux_mode = y.aux_mode; g.st = a.st;
-    g.absmax = (BWD && a.st) ? const_cast<uint32_t*>(a.st->dz_absmax_slots) : nullptr;
-    SeqLink q;
-    q.flag = a.flags + mt * 32; q.target = (a.base[mt] + (uint32_t)layer) * 32u;   // 4 workgroups x 8 waves per seam
-    q.first = layer == 0; q.wait = layer > 0; q.signal = layer + 1 < a.n_layers;
-    q.next_W = q.signal ? a.layer[layer + 1].W : nullptr;
-    q.flag_index = (uint32_t)(mt * 32); q.limit = a.spin_limit;
-    if (!BWD) {
-      if (y.aux_mode == AUX_RESIDUAL) rowgemm80_body<true, false, false, AUX_RESIDUAL, true, E>(g, smem, 1, mt, n0, q);
-      else rowgemm80_body<true, false, false, AUX_NONE, true, E>(g, smem, 1, mt, n0, q);
-    } else {
-      if (y.add) rowgemm80_body<false, true, true, AUX_UNMASKED, true, E>(g, smem, 1, mt, n0, q);
-      else if (y.aux_mode == AUX_UNMASKED) rowgemm80_body<false, false, true, AUX_UNMASKED, true, E>(g, smem, 1, mt, n0, q);
-      else rowgemm80_body<false, false, true, AUX_NONE, true, E>(g, smem, 1, mt, n0, q);
-    }
-  }
+  rowseq_layers<BWD, E, 0>(a, smem, mt, (jx & 3) * 128);
 }
 
 // Placement probe (acez_trainer_create): a launch with rowseq_kernel's grid, block size and LDS footprint that only records
@@ -2157,6 +2163,96 @@ __device__ __forceinline__ void lds_bump(uint32_t* f) {   // after this wave's e
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(f, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// rowseq_loss: the input-gradient chain (rowseq_kernel<true>) with the loss launch as its stage -1 and the next batch's gather in the
+// waves that have nothing to do meanwhile -- the fused step's loss launch sat alone on the critical path between two launches that each
+// fill every CU: a 12 us latency chain on 320 small workgroups, plus a kernel boundary on either side.
+//   stage -1  An 80-row tile is five of loss_kernel's 16-row blocks: row tile mt owns blocks 5 mt .. 5 mt + 4, so every partial (fc3, fc2
+//             bias, statistics) lands in loss_kernel's slot and every sum downstream keeps its order -- bit-identical. A workgroup's two
+//             wave quartets are two loss workgroups: column tile 0 runs blocks 5 mt (multiplier waves) and 5 mt + 1 (loader waves), column
+//             tiles 1..3 run block 5 mt + 1 + nt on their multiplier waves. loss_body as loss_kernel instantiates it; the four waves of a
+//             quartet meet through an LDS counter of their own (a barrier would tie the two quartets together), the scratch lies in the
+//             staging tiles, which layer 0 does not touch before its K stage 4.
+//   hand-off  dZ of fc2 is the In of the first layer: every wave of a loss block bumps the row tile's counter behind the acknowledgement
+//             of its stores, 8 per workgroup, exactly as a layer epilogue does; layer 0 then waits for 32 like any later layer. A block
+//             past the batch's last row stores nothing (and owns no partial slot) and still bumps.
+//   W stages  the loader waves request the first layer's first four W stages before anything else, as the seam prefetch does.
+//   gather    the loader waves of column tiles 1..3 have only a hand-off to wait for: they copy the NEXT batch's rows (gather_rows, three
+//             dependent load levels -- shorter than a loss block's chain) into the trainer's other input buffer. Under the fault word
+//             nothing is stored (GatherMeta::hold); a launch that returns at entry still gathers, as loss_gather_kernel's workgroups did.
+// A poll that expires behind stage -1 is a fault like any other seam's: the partials and dZ written so far are per-step buffers.
+// ---------------------------------------------------------------------------------------------------
+struct SeqLossArgs {
+  LossArgs loss;
+  int nblk;                  // loss blocks of the batch (loss_kernel's grid)
+  const uint16_t* feat;      // the next batch: gather_rows' arguments (n_next = 0: none)
+  const int64_t* idx_next;
+  uint16_t* out_next;
+  int n_next;
+  GatherMeta meta;
+};
+
+template <class E = EltBf16>
+__global__ __launch_bounds__(512) void rowseq_loss_kernel(RowSeqArgs a, SeqLossArgs x) {
+  __shared__ __attribute__((aligned(16))) uint16_t smem[RG80_SMEM_SEQ];
+  const int mtiles = (a.M + 79) / 80;
+  const int per_xcd = (mtiles + 7) >> 3;
+  const int jx = blockIdx.x >> 3;
+  const int mt = (blockIdx.x & 7) * per_xcd + (jx >> 2);
+  if (mt >= mtiles) return;
+  const int t = threadIdx.x, l = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int nt = jx & 3, n0 = nt * 128;
+  if (a.xcc_dbg && t == 0) {
+    const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;   // HW_REG_XCC_ID[3:0]
+    atomicOr(a.xcc_dbg + (blockIdx.x & 7), 1u << xcc);
+    a.xcc_dbg[8 + mt * 4 + nt] = xcc;
+  }
+  // the quartets' meeting counters: in the bias-partial combine buffer (first used by layer 0's epilogue)
+  uint32_t* const qsync = reinterpret_cast<uint32_t*>(smem + RG80_SMEM);
+  if (t < 2) qsync[t] = 0u;
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  const bool dead = (a.st && !a.st->active) || a.flags[64 * 32];   // rowseq_kernel's entry test
+  if (w >= 4) {
+    const int lw = w - 4;
+    if (!dead) {   // rowgemm80_body's issueW(0 .. 3) for layer 0
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int row = (lw * 4 + j) * 8 + (l >> 3);
+        const uint16_t* g = a.layer[0].W + (size_t)(n0 + row) * 512 + ((l & 7) ^ ((row >> 1) & 7)) * 8;
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+          __builtin_amdgcn_global_load_lds((gvoid_t*)(g + kt * 64), (lvoid_t*)(smem + kt * RG80_STAGE + (lw * 4 + j) * 8 * 64), 16, 0, 0);
+      }
+    }
+    if (nt != 0 && x.n_next > 0) gather_rows<8>(x.feat, x.idx_next, x.out_next, x.n_next, (mt * 3 + nt - 1) * 4 + lw, mtiles * 12, l, x.meta);
+  }
+  if (dead) {   // no work, but the counters keep step with the host's bases (one seam more than rowseq_kernel's launch)
+    if (t == 0) {
+      const uint32_t inc = 8u * (uint32_t)a.n_layers;
+      asm volatile("global_atomic_add %0, %1, off" ::"v"(a.flags + mt * 32), "v"(inc) : "memory");
+    }
+    return;
+  }
+  if (w < 4 || nt == 0) {
+    const int quartet = w >> 2;
+    const int block = 5 * mt + (nt == 0 ? quartet : nt + 1);
+    if (block < x.nblk) {
+      float* scratch = reinterpret_cast<float*>(smem + 4 * RG80_STAGE) + quartet * (3 * 4 * 4 * 4);
+      uint32_t* const f = qsync + quartet;
+      loss_body<false, true, E, 4>(x.loss, block, w & 3, l, nullptr, scratch, LossPre{0, 0, 0, 0.f, 0.f}, [f] { lds_bump(f); lds_wait_ge(f, 4u); });
+    }
+    ACEZ_VMCNT(0);   // this wave's dZ stores are acknowledged by the L2 the four sibling workgroups share
+    if (l == 0) {
+      const uint32_t inc = nt == 0 ? 1u : 2u;   // 8 per workgroup: eight waves, or four
+      asm volatile("global_atomic_add %0, %1, off" ::"v"(a.flags + mt * 32), "v"(inc) : "memory");
+    }
+  }
+  rowseq_layers<true, E, 1>(a, smem, mt, n0);
+}
+
 #ifdef ACEZ_DIAG   // timeline of the epilogue (tools/wgo_trace.py): stamp i of this wave
 #define WGO_STAMP(i) do { if (o.trace && (threadIdx.x & 63) == 0) o.trace[((size_t)blockIdx.x * 12 + (threadIdx.x >> 6)) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
