@@ -33,6 +33,7 @@ UNITS = {
     "align_api.hip": ["-ffp-contract=off"],
     "render_api.hip": ["-ffp-contract=off"],
     "ingest_api.hip": ["-ffp-contract=off"],
+    "reproject_api.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -1096,3 +1096,63 @@ def eval_poses_main(argv=None):
     for line in log_lines(res):
         log.info(line)
     return 0
+
+
+# ------------------------------------------------------------------------------------------------------ benchmark_poses
+# benchmarks/benchmark_poses.py:12-27 ("required" in place of a default for the first three)
+BENCHMARK_FLAGS = [
+    (("--pose_file",), str, None, None, "Path to the poses file, in ACE0 format. Poses with confidence <1000 will be excluded from the "
+                                        "training set."),
+    (("--output_dir",), str, None, None, "Output directory where the benchmark results will be written"),
+    (("--images_glob_pattern",), str, None, None, "Pattern relative to working directory to glob for images"),
+    (("--split_json",), str, None, None, "Path to a JSON file containing splits; if not given, every 8 images will be test images"),
+    (("--method",), str, "reproject", ["reproject", "nerfacto", "splatfacto"],
+     "reproject [additive, the default here]: reprojection PSNR at 1/8 resolution on the GPU (acezero_amd.benchmark; NOT nerfacto PSNR); "
+     "nerfacto / splatfacto: the reference's choices, accepted with --no_run_nerfstudio only (nerfstudio is not part of this package)"),
+    (("--camera_optimizer",), str, "off", ["off", "SO3xR3", "SE3"], "Type of camera optimizer for nerfstudio; refused with --method reproject"),
+    (("--max_resolution",), int, 640, None, "Maximum resolution of the images of the written data set"),
+]
+
+
+def benchmark_poses_parser():
+    p = argparse.ArgumentParser(description="Benchmark some poses by view synthesis: writes the reference's nerfstudio data set and scores "
+                                            "the held-out views by reprojection on the GPU (--method reproject).",
+                                formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    for flags, typ, default, choices, hlp in BENCHMARK_FLAGS:
+        kw = {"type": typ, "help": hlp}
+        if choices is not None:
+            kw["choices"] = choices
+        if flags[0] in ("--pose_file", "--output_dir", "--images_glob_pattern"):
+            kw["required"] = True
+        elif flags[0] == "--split_json":
+            kw["required"] = False
+        else:
+            kw["default"] = default
+        p.add_argument(*flags, **kw)
+    p.add_argument("--no_run_nerfstudio", action="store_true",
+                   help="If given, the script will generate Nerfstudio input files and compute nothing")
+    p.add_argument("--network", type=Path, default=None, help="[additive, reproject] head weights (.pt) of the scene, e.g. the last round's")
+    p.add_argument("--encoder_path", type=Path, default="<path>", help="[additive, reproject] pre-trained encoder weights")
+    p.add_argument("--image_resolution", type=int, default=480, help="[additive, reproject] short side of the frames the network sees")
+    p.add_argument("--depth_band", type=float, default=0.05, help="[additive, reproject] points within this relative depth of a cell's "
+                                                                  "nearest point colour the cell")
+    p.add_argument("--use_half", type=_strtobool, default=True, help="[additive, reproject] 16-bit matrix arithmetic; False (fp32) is not "
+                                                                     "implemented and is refused")
+    _add_dtype(p)
+    return p
+
+
+def benchmark_poses_main(argv=None):
+    """benchmark_poses.py: the reference's data set for nerfstudio, and (--method reproject) the reprojection score of the held-out views."""
+    from . import benchmark
+    opt = benchmark_poses_parser().parse_args(argv)
+    logging.basicConfig(level=logging.INFO)
+    benchmark.check_method(opt.method, opt.no_run_nerfstudio, opt.camera_optimizer)
+    if not opt.use_half:
+        raise SystemExit("--use_half False (fp32 network arithmetic) is not implemented on this path; it is refused rather than silently "
+                         "run in 16 bits. Use --use_half True [--compute_dtype fp16 for the reference's autocast precision].")
+    benchmark.run(Path(opt.pose_file), opt.images_glob_pattern, Path(opt.output_dir), split_json=Path(opt.split_json) if opt.split_json else None,
+                  no_run_nerfstudio=opt.no_run_nerfstudio, method=opt.method, camera_optimizer=opt.camera_optimizer,
+                  max_resolution=opt.max_resolution, network=opt.network, encoder_path=opt.encoder_path,
+                  image_resolution=opt.image_resolution, depth_band=opt.depth_band, compute_dtype=opt.compute_dtype)
+    return 0

@@ -734,6 +734,34 @@ int acez_ingest_coeffs(int in_size, int out_size, int* out_ksize, int32_t* out_b
 int acez_ingest_frames(const uint8_t* d_src, int n, int H, int W, int nh, int nw, uint8_t* d_tmp, int32_t* d_tables, int64_t table_bytes,
                        const float* d_norm, uint8_t* d_out_rgb, float* d_out_grey, void* stream);
 
+/* =====================================================================================================
+ * J. Reprojection score of held-out views (benchmark_poses.py --method reproject)
+ * =====================================================================================================
+ * M coloured points seen from T views on a grid of oh x ow cells (a cell = an 8 x 8 px block of the network's input frame):
+ *   d_xyz      float32 [n_points][3] world coordinates (OpenCV convention), d_rgb uint8 [n_points][3]; n_points <= 2^24
+ *   d_views    float32 [n_views][15]: the 3 x 4 world -> camera rows (OpenCV camera: looks down +z), focal, cx, cy in CELL units
+ *              (pixels / 8)
+ *   d_targets  uint8 [n_views][oh][ow][3]: the held-out frames' cell means (the function below)
+ *   projection xc = m0 x + m1 y + m2 z + m3 (left to right; yc, zc alike), dropped unless zc >= 0.1; iz = 1 / zc;
+ *              u = cx + (f xc) iz, v = cy + (f yc) iz, dropped unless 0 <= u < ow and 0 <= v < oh; cell (floor v, floor u). All fp32,
+ *              round to nearest, no contraction
+ *   nearest    per cell the smallest (bits of zc << 32 | point index): the nearest point, at equal depth the lower index
+ *   accumulate a point adds its R, G, B and 1 to its cell's 32-bit sums if zc <= zmin * b, b = float(1.0 + double(depth_band))
+ *   score      per cell with count > 0: colour = (sum + count / 2) / count (integers); d_out_sse[view] += the three squared
+ *              differences to the target, d_out_covered[view] += 1; d_out_image uint8 [n_views][oh][ow][3] (0 where nothing landed)
+ *              and d_out_mask uint8 [n_views][oh][ow] (1 = covered) are optional (NULL)
+ * The outputs depend on no ordering of the atomics. Asynchronous on `stream`; nothing is allocated: d_scratch (8-byte aligned) holds
+ * at least acez_reproject_scratch_size's bytes (host only, no device needed). ACEZ_ERR_INVALID before anything is launched for: a null
+ * pointer (other than the two optional ones), n_views outside 1 .. 65535, oh or ow outside 1 .. 4096, n_points outside 0 .. 2^24,
+ * depth_band outside 0 .. 1, a scratch block too small. tests/reproject_restated.py restates every operation in numpy. */
+int acez_reproject_scratch_size(int n_views, int oh, int ow, int64_t* out_bytes);
+int acez_reproject_score(const float* d_xyz, const uint8_t* d_rgb, int64_t n_points, const float* d_views, int n_views, int oh, int ow,
+                         const uint8_t* d_targets, float depth_band, void* d_scratch, int64_t scratch_bytes, int64_t* d_out_sse,
+                         int32_t* d_out_covered, uint8_t* d_out_image, uint8_t* d_out_mask, void* stream);
+/* Cell means: d_frames uint8 [n_frames][H][W][3] -> d_out uint8 [n_frames][ceil(H/8)][ceil(W/8)][3], per channel the mean over the
+ * cell's pixels, (sum + count / 2) / count in integers (half up); a cell cut by the frame's edge averages the pixels it has. */
+int acez_reproject_cell_means(const uint8_t* d_frames, int n_frames, int H, int W, uint8_t* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
