@@ -175,7 +175,10 @@ def warp_views_device(images_n1hw, image_index, scale, angles, jitter=None, mask
     """warp_views on the GPU through acez_buffer_warp_views (up to three launches per batch: warp, jitter mean, mask; no sampling grid, no gathered copy of the source frames):
     views of frames `image_index` of the resident table `images_n1hw`. Returns (views [B,1,hs,ws] float32, mask): mask is uint8
     [B,1,oh,ow] at the feature resolution `mask_hw` = (oh, ow) -- the cells the nearest-neighbour resize of ace_trainer.py:373-374 reads -- or
-    None. Same arithmetic as warp_views (tests/test_buffer_gpu.py: values to 1e-5, masks identical)."""
+    None. Same arithmetic as warp_views in fp32. tests/test_buffer_warp_gpu.py asserts, per pixel against a float64 restatement,
+    |error| <= 8.04 * (L * eps32 * max(H, W) * g + eps32 * max|tap|) -- L the slope of the bilinear cell, g the largest entry of the map's
+    linear part, the constant measured in tests/warp_cases.py -- and that a mask cell differs only where its source coordinate is
+    within 8.04 * eps32 * max(H, W) * g pixels of the frame's limits -1, W, -1, H; tests/test_buffer_gpu.py compares with warp_views itself."""
     import ctypes as C
     from . import _native as N
     assert images_n1hw.is_cuda and images_n1hw.dtype == torch.float32 and images_n1hw.is_contiguous()
