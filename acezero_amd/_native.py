@@ -84,6 +84,14 @@ class Texture(C.Structure):
     _fields_ = [("offset", C.c_int64), ("width", C.c_int32), ("height", C.c_int32)]
 
 
+TSDF_MAX_FRAMES = 256           # ACEZ_TSDF_MAX_FRAMES
+
+
+class TsdfFrame(C.Structure):
+    _fields_ = [("m", C.c_float * 12), ("focal", C.c_float), ("ppx", C.c_float), ("ppy", C.c_float), ("h", C.c_int32), ("w", C.c_int32),
+                ("reserved", C.c_int32), ("offset", C.c_int64)]
+
+
 # every symbol include/acez.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "acez_last_error": (C.c_char_p, []),
@@ -188,6 +196,13 @@ SYMBOLS = {
     "acez_reproject_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float,
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acez_reproject_cell_means": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "acez_tsdf_integrate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                      C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(TsdfFrame), C.c_int, C.c_void_p, C.c_float,
+                                      C.c_float, C.c_float, C.c_int, C.c_void_p]),
+    "acez_tsdf_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                  C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "acez_tsdf_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 

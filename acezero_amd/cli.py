@@ -1156,3 +1156,100 @@ def benchmark_poses_main(argv=None):
                   max_resolution=opt.max_resolution, network=opt.network, encoder_path=opt.encoder_path,
                   image_resolution=opt.image_resolution, depth_band=opt.depth_band, compute_dtype=opt.compute_dtype)
     return 0
+
+
+# ----------------------------------------------------------------------------------------------------------- fuse_depth
+def fuse_depth_parser():
+    p = argparse.ArgumentParser(description="Fuse the depth maps of an RGB-D reconstruction along its estimated poses into a TSDF volume "
+                                            "on the GPU and write the surface as a coloured triangle mesh (.ply).",
+                                formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("pose_file", type=Path, help="ACE pose file of the reconstruction (file qw qx qy qz tx ty tz f conf)")
+    p.add_argument("rgb_files", type=str, help="glob of the RGB files, e.g. 'scene/*.jpg'")
+    p.add_argument("output_file", type=Path, help="mesh to write (.ply)")
+    p.add_argument("--depth_files", type=str, required=True, help="glob of the depth maps (16 bit), one per image, in the sorted order of the "
+                                                                  "images (the format ace_zero.py --depth_files reads)")
+    p.add_argument("--voxel_size", type=float, default=0.02, help="voxel edge in metres")
+    p.add_argument("--truncation", type=float, default=None, help="truncation distance in metres; default: 4 voxels")
+    p.add_argument("--max_depth", type=float, default=4.0, help="depth beyond this many metres is not fused")
+    p.add_argument("--min_weight", type=float, default=2, help="a voxel belongs to the surface once this many frames have observed it")
+    p.add_argument("--confidence_threshold", type=float, default=1000, help="ignore pose-file entries below this confidence")
+    p.add_argument("--depth_unit", type=float, default=0.001, help="metres per raw depth unit (0.001: millimetres)")
+    p.add_argument("--max_voxels", type=int, default=2 ** 28, help="refuse a volume of more voxels than this")
+    p.add_argument("--colour", type=_strtobool, default=True, help="colour the mesh from the RGB files")
+    return p
+
+
+def _read_depth_u16(path):
+    from PIL import Image
+    d = np.asarray(Image.open(path))
+    if d.ndim != 2:
+        raise SystemExit(f"{path}: a depth map must have one channel")
+    return np.ascontiguousarray(np.clip(d, 0, 65535).astype(np.uint16))
+
+
+def fuse_depth_main(argv=None):
+    """fuse_depth.py: depth maps at their own resolution + pose file -> TSDF volume (HIP) -> surface-net mesh (HIP) -> .ply."""
+    import glob
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    from . import fusion
+    opt = fuse_depth_parser().parse_args(argv)
+    logging.basicConfig(level=logging.INFO)
+    log = logging.getLogger("fuse_depth")
+    if not str(opt.output_file).endswith(".ply"):
+        raise SystemExit("output file format not supported: use .ply")
+    if opt.voxel_size <= 0:
+        raise SystemExit("--voxel_size must be positive")
+    truncation = 4.0 * opt.voxel_size if opt.truncation is None else opt.truncation
+    rgb_files, depth_files = sorted(glob.glob(opt.rgb_files)), sorted(glob.glob(opt.depth_files))
+    if len(depth_files) != len(rgb_files):
+        raise SystemExit(f"{len(depth_files)} depth files for {len(rgb_files)} images")
+    names, c2w_all, focals_all = read_ace_pose_file(opt.pose_file, opt.confidence_threshold)
+    if not names:
+        raise SystemExit("no pose above the confidence threshold")
+    by_name = {n: k for k, n in enumerate(names)}
+    by_base = {os.path.basename(n): k for k, n in enumerate(names)}
+    pairs = []                                                  # (rgb file, depth file, row of the pose file), in the folder's order
+    for rgb_file, depth_file in zip(rgb_files, depth_files):
+        k = by_name.get(rgb_file, by_base.get(os.path.basename(rgb_file)))
+        if k is not None:
+            pairs.append((rgb_file, depth_file, k))
+    if not pairs:
+        raise SystemExit("no image of the glob has a pose above the confidence threshold in the pose file")
+    t0 = time.perf_counter()
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+        depth = list(pool.map(_read_depth_u16, [p[1] for p in pairs]))
+        image_h = [Image.open(p[0]).size[1] for p in pairs]
+        c2w = np.stack([c2w_all[p[2]] for p in pairs])
+        # a pose file's focal is in pixels of the original image; the depth map is that image at another scale
+        focals = np.array([focals_all[p[2]] * d.shape[0] / ih for p, d, ih in zip(pairs, depth, image_h)])
+        origin, dims = fusion.bounds_from_frames(depth, c2w, focals, opt.voxel_size, truncation, depth_unit=opt.depth_unit,
+                                                 max_depth=opt.max_depth, max_voxels=opt.max_voxels)
+        rgb = None
+        if opt.colour:
+            def read_rgb(job):
+                path, (h, w) = job
+                return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB").resize((w, h), Image.NEAREST), np.uint8))
+            rgb = list(pool.map(read_rgb, [(p[0], d.shape) for p, d in zip(pairs, depth)]))
+    t_decode = time.perf_counter() - t0
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("fuse_depth.py needs a GPU: TSDF fusion is a HIP kernel, there is no CPU path")
+    t0 = time.perf_counter()
+    vol = fusion.TSDFVolume(origin, dims, opt.voxel_size, truncation, "cuda")
+    vol.integrate(depth, cam_to_world=c2w, focals=focals, rgb=rgb, depth_unit=opt.depth_unit, max_depth=opt.max_depth)
+    vertices, colours, faces = vol.extract_mesh(opt.min_weight)
+    known = vol.known_voxels(opt.min_weight)
+    vertices, colours, faces = vertices.cpu(), colours.cpu(), faces.cpu()
+    t_device = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    if rgb is None:
+        colours[:] = 200
+    fusion.write_mesh_ply(opt.output_file, vertices, colours, faces)
+    t_write = time.perf_counter() - t0
+    log.info(f"Fused {len(pairs)} of {len(rgb_files)} frames into a volume of {dims[0]} x {dims[1]} x {dims[2]} voxels "
+             f"({opt.voxel_size} m, truncation {truncation} m).")
+    log.info(f"Known voxels: {known}. Mesh: {len(vertices)} vertices, {len(faces)} faces.")
+    log.info(f"Decode {t_decode:.2f} s, upload + kernels + download {t_device:.2f} s, write {t_write:.2f} s.")
+    log.info(f"Done. Wrote mesh to: {opt.output_file}")
+    return 0

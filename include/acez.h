@@ -762,6 +762,87 @@ int acez_reproject_score(const float* d_xyz, const uint8_t* d_rgb, int64_t n_poi
  * cell's pixels, (sum + count / 2) / count in integers (half up); a cell cut by the frame's edge averages the pixels it has. */
 int acez_reproject_cell_means(const uint8_t* d_frames, int n_frames, int H, int W, uint8_t* d_out, void* stream);
 
+/* =====================================================================================================
+ * K. TSDF fusion of depth maps along the estimated poses, and the surface as a mesh (fuse_depth.py)
+ * =====================================================================================================
+ * The volume has nx x ny x nz voxels, x fastest: voxel (i, j, k) is element (k * ny + j) * nx + i of
+ *   d_tsdf    float32 [nz][ny][nx]     truncated signed distance in units of the truncation, <= 1, positive in free space
+ *   d_weight  float32 [nz][ny][nx]     number of observations, capped; 0 = never observed (the tsdf value is then not read by the
+ *                                      extraction; the integration reads it, so it must be finite: the caller clears it)
+ *   d_colour  float32 [3][nz][ny][nx]  R, G, B planes, 0 .. 255; optional (NULL)
+ * `origin` (ox, oy, oz) is the world position of voxel (0, 0, 0)'s centre (OpenCV convention, metres), v = voxel_size, tau = truncation.
+ * Every entry point is stateless and allocates nothing; every buffer is the caller's. All float arithmetic below is fp32, round to
+ * nearest, one rounding per operation in the order written (the unit is built without contraction), division is IEEE division.
+ * tests/tsdf_restated.py restates all of it in numpy.
+ *
+ * INTEGRATE. One thread per voxel walks the call's frames in table order and keeps the voxel in registers, so the result does not
+ * depend on how the caller cuts a sequence into calls. Frame row (acez_tsdf_frame): m[12] = the 3 x 4 world -> camera rows, focal,
+ * ppx, ppy in pixels of THIS frame, its size h x w, and `offset`: the element index of its pixel (0, 0) in d_depth (uint16, raw
+ * sensor units, row-major h x w) and, times 3, in d_rgb (uint8 RGB, optional). Frames of different sizes may share a call. Per frame:
+ *   1. px = ox + float(i) * v                                                (py, pz alike)
+ *   2. xc = ((m0 * px + m1 * py) + m2 * pz) + m3                             (yc from m4..m7, zc from m8..m11)
+ *   3. skip unless zc > 0
+ *   4. u = (focal * xc) / zc + ppx,  w_ = (focal * yc) / zc + ppy            (pixel index and image coordinate are the same number)
+ *   5. skip unless u >= -0.5 && u < float(w) - 0.5 && w_ >= -0.5 && w_ < float(h) - 0.5     (tested on the floats: rejects NaN / inf)
+ *      ix = min(int(floor(u + 0.5)), w - 1), iy = min(int(floor(w_ + 0.5)), h - 1)          (the min only guards the sum's rounding)
+ *   6. raw = d_depth[offset + iy * w + ix]; skip if raw == 0; d = float(raw) * depth_unit; skip if d > max_depth
+ *   7. sdf = d - zc; skip if sdf < -tau
+ *   8. t = min(1, sdf / tau)
+ *   9. w1 = weight + 1; tsdf = (tsdf * weight + t) / w1; with colour, per channel c = (c * weight + float(rgb)) / w1;
+ *      weight = min(w1, max_weight)
+ * A workgroup is a brick of 32 x 4 x 2 voxels. With frustum_skip != 0, thread f of the brick first tests frame f against the brick's
+ * box in double (the eight corners against the five planes zc > 0, u >= -0.5, u < w - 0.5 and the two of w_, each with a slack of
+ * 1e-5 of the magnitudes that enter, some twenty times the rounding error of steps 1-4), and the brick's waves pass over a frame whose
+ * test says that every voxel fails step 3 or 5. The results are those of frustum_skip == 0, bit for bit.
+ * h_frames is a HOST array of n_frames rows, checked here (that is what bounds every index the kernel forms) and copied into d_frames,
+ * device scratch of n_frames rows, on `stream`; the copy has completed when the call returns (h_frames may be reused), the kernel is
+ * asynchronous. Calls that share d_frames must share the stream. n_frames = 0 does nothing.
+ * ACEZ_ERR_INVALID, before anything is launched, for: a null pointer (other than d_colour, d_rgb; d_colour without d_rgb leaves the
+ * colour as it is, d_rgb without d_colour is refused), a dimension < 1 or nx * ny * nz >= 2^31, v or tau not > 0 (or not finite),
+ * depth_unit, max_depth or max_weight not > 0, n_frames outside 0 .. 256, a row with h or w outside 1 .. 32768, focal not > 0,
+ * a non-finite number, offset < 0 or offset + h * w > n_pixels (the length of d_depth in elements). */
+#define ACEZ_TSDF_MAX_FRAMES 256
+typedef struct {
+  float m[12];
+  float focal, ppx, ppy;
+  int32_t h, w;
+  int32_t reserved;
+  int64_t offset;
+} acez_tsdf_frame;
+int acez_tsdf_integrate(float* d_tsdf, float* d_weight, float* d_colour, int nx, int ny, int nz, float ox, float oy, float oz,
+                        float voxel_size, float truncation, const uint16_t* d_depth, const uint8_t* d_rgb, int64_t n_pixels,
+                        const acez_tsdf_frame* h_frames, int n_frames, acez_tsdf_frame* d_frames, float depth_unit, float max_depth,
+                        float max_weight, int frustum_skip, void* stream);
+/* EXTRACT (naive surface nets: one vertex per active cell, one quad per sign-changing voxel edge; no case table).
+ * A voxel is KNOWN if weight >= min_weight and INSIDE if tsdf < 0 (-0.0 is outside). Cell (i, j, k), i < nx - 1, j < ny - 1,
+ * k < nz - 1, has the corners (i + dx, j + dy, k + dz), corner number dx + 2 dy + 4 dz; it is ACTIVE if all eight are known and not
+ * all on one side. A cell's linear index is its corner 0's voxel index. Its vertex: over the 12 edges in the order
+ *   x: (0,1) (2,3) (4,5) (6,7)   y: (0,2) (1,3) (4,6) (5,7)   z: (0,4) (1,5) (2,6) (3,7)      (a, b) = corner numbers, a the lower end
+ * every edge whose ends differ in side adds its crossing, s = da / (da - db), point = pa + s * (pb - pa) per component with pa, pb the
+ * corners' (dx, dy, dz) as floats, to a running sum (three components, in edge order); mean = sum / float(count); the vertex is
+ * ox + (float(i) + mean_x) * v, and alike in y and z. Colour: the same running sum and mean of ca + s * (cb - ca) per channel, then
+ * min(max(floor(mean + 0.5), 0), 255) as uint8.
+ *   acez_tsdf_cells, d_vertex_rank == NULL: d_active uint8 [nz][ny][nx] := 1 for the active cells, 0 elsewhere.
+ *   acez_tsdf_cells, d_vertex_rank = the INCLUSIVE prefix sum (int32) of d_active: every active cell writes its vertex, and its colour
+ *     if d_colour and d_out_colours are given, to row rank - 1 of d_out_vertices float32 [n_vertices][3] / d_out_colours uint8
+ *     [n_vertices][3] (a rank outside 1 .. n_vertices writes nothing). Vertex ids ascend with the cell's linear index.
+ * Faces: axis a = x, y, z with (a, b, c) = (x, y, z), (y, z, x), (z, x, y). The edge from voxel p to p + e_a makes a quad if both ends
+ * are known, their sides differ and the four cells p - e_b - e_c, p - e_c, p, p - e_b (in this order c0, c1, c2, c3: counter-clockwise
+ * seen from +a) are in range and active; it gives the triangles (c0, c1, c2), (c0, c2, c3) if the lower end p is inside, and
+ * (c0, c2, c1), (c0, c3, c2) if it is outside: the normals point to positive tsdf (free space).
+ *   acez_tsdf_faces, d_edge_rank == NULL: d_edge_flags uint8 [3][nz][ny][nx] (axis-major, the edge at its lower end's voxel index) := 1 / 0.
+ *   acez_tsdf_faces, d_edge_rank = the inclusive prefix sum (int32) of d_edge_flags: the edge of rank r writes its triangles to rows
+ *     2 (r - 1), 2 (r - 1) + 1 of d_out_faces int32 [n_faces][3] (nothing past n_faces), vertex id = d_vertex_rank[cell] - 1.
+ * Faces are therefore axis-major, then ascending in the edge's linear index: the mesh is a deterministic function of the volume.
+ * Asynchronous. ACEZ_ERR_INVALID for a null pointer (other than the optional ones named), a dimension < 1, nx * ny * nz >= 2^31 / 3,
+ * v not > 0, a negative output count. */
+int acez_tsdf_cells(const float* d_tsdf, const float* d_weight, const float* d_colour, int nx, int ny, int nz, float ox, float oy,
+                    float oz, float voxel_size, float min_weight, uint8_t* d_active, const int32_t* d_vertex_rank,
+                    float* d_out_vertices, uint8_t* d_out_colours, int64_t n_vertices, void* stream);
+int acez_tsdf_faces(const float* d_tsdf, const float* d_weight, int nx, int ny, int nz, float min_weight, const uint8_t* d_active,
+                    uint8_t* d_edge_flags, const int32_t* d_vertex_rank, const int32_t* d_edge_rank, int32_t* d_out_faces,
+                    int64_t n_faces, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
