@@ -92,6 +92,9 @@ class TsdfFrame(C.Structure):
                 ("reserved", C.c_int32), ("offset", C.c_int64)]
 
 
+MVS_MAX_SOURCES = 8             # ACEZ_MVS_MAX_SOURCES; a row of the stereo entry points' table (acez_mvs_frame) is a TsdfFrame
+
+
 # every symbol include/acez.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "acez_last_error": (C.c_char_p, []),
@@ -203,6 +206,12 @@ SYMBOLS = {
                                   C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "acez_tsdf_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int64, C.c_void_p]),
+    "acez_mvs_prefilter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(TsdfFrame), C.c_int, C.c_void_p, C.c_void_p]),
+    "acez_mvs_relative": (C.c_int, [C.POINTER(TsdfFrame), C.POINTER(TsdfFrame), C.POINTER(C.c_float)]),
+    "acez_mvs_sweep": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(TsdfFrame), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_float,
+                                 C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "acez_mvs_check": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(TsdfFrame), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_float,
+                                 C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -1253,3 +1253,125 @@ def fuse_depth_main(argv=None):
     log.info(f"Decode {t_decode:.2f} s, upload + kernels + download {t_device:.2f} s, write {t_write:.2f} s.")
     log.info(f"Done. Wrote mesh to: {opt.output_file}")
     return 0
+
+
+# ------------------------------------------------------------------------------------------------------- estimate_depth
+def estimate_depth_parser():
+    p = argparse.ArgumentParser(description="Estimate a depth map per image of an RGB reconstruction by plane-sweep stereo over "
+                                            "neighbouring frames on the GPU and write them as 16-bit PNGs, the input of fuse_depth.py.",
+                                formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("pose_file", type=Path, help="ACE pose file of the reconstruction (file qw qx qy qz tx ty tz f conf)")
+    p.add_argument("rgb_files", type=str, help="glob of the RGB files, e.g. 'scene/*.jpg'")
+    p.add_argument("output_dir", type=Path, help="folder for the depth maps: one 16-bit PNG per image of the glob, named after it")
+    p.add_argument("--image_resolution", type=int, default=240, help="short side of the working images and of the depth maps")
+    p.add_argument("--point_cloud", type=Path, default=None, help="the reconstruction's point cloud (.ply of ace_zero.py "
+                                                                  "--export_point_cloud True or of export_point_cloud.py): gives every "
+                                                                  "frame its depth range")
+    p.add_argument("--cloud_convention", type=str, default="opencv", choices=["opengl", "opencv"],
+                   help="coordinate convention of --point_cloud: ace_zero.py --export_point_cloud True writes OpenCV (pc_final.ply), "
+                        "export_point_cloud.py OpenGL unless it is given --convention opencv")
+    p.add_argument("--depth_range", type=float, nargs=2, default=None, metavar=("NEAR", "FAR"), help="one depth range in metres for all frames, "
+                                                                                                   "instead of --point_cloud")
+    p.add_argument("--planes", type=int, default=128, help="depth planes, uniform in inverse depth")
+    p.add_argument("--sources", type=int, default=4, help="neighbouring frames to match each frame against (1 .. 8)")
+    p.add_argument("--keep", type=int, default=None, help="the plane cost sums the KEEP best sources; default: half of them, rounded up")
+    p.add_argument("--window", type=int, default=2, help="matching window radius in pixels (0 .. 4)")
+    p.add_argument("--uniqueness", type=int, default=5, help="the best plane must beat every plane outside its neighbourhood by this many percent")
+    p.add_argument("--tolerance", type=float, default=0.01, help="relative depth difference up to which a source's depth map agrees")
+    p.add_argument("--min_consistent", type=int, default=2, help="a depth is kept if this many sources agree with it")
+    p.add_argument("--confidence_threshold", type=float, default=1000, help="ignore pose-file entries below this confidence")
+    p.add_argument("--depth_unit", type=float, default=0.001, help="metres per unit of the written depth maps (0.001: millimetres)")
+    return p
+
+
+def estimate_depth_main(argv=None):
+    """estimate_depth.py: images + pose file (+ point cloud) -> prefilter, plane sweep, consistency check (HIP) -> 16-bit depth PNGs."""
+    import glob
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    from . import mvs
+    opt = estimate_depth_parser().parse_args(argv)
+    logging.basicConfig(level=logging.INFO)
+    log = logging.getLogger("estimate_depth")
+    if (opt.point_cloud is None) == (opt.depth_range is None):
+        raise SystemExit("give exactly one of --point_cloud and --depth_range")
+    if opt.depth_range is not None and not 0 < opt.depth_range[0] < opt.depth_range[1] < math.inf:
+        raise SystemExit("--depth_range needs 0 < NEAR < FAR")
+    if opt.image_resolution < 16:
+        raise SystemExit("--image_resolution must be at least 16")
+    if not 2 <= opt.planes <= 1024:
+        raise SystemExit("--planes must be in 2 .. 1024")
+    if not 1 <= opt.sources <= 8:
+        raise SystemExit("--sources must be in 1 .. 8")
+    if opt.keep is not None and not 1 <= opt.keep <= opt.sources:
+        raise SystemExit("--keep must be in 1 .. --sources")
+    if not 0 <= opt.window <= 4:
+        raise SystemExit("--window must be in 0 .. 4")
+    if not 0 <= opt.uniqueness <= 100:
+        raise SystemExit("--uniqueness is a percentage (0 .. 100)")
+    if not 0 <= opt.tolerance < math.inf:
+        raise SystemExit("--tolerance must not be negative")
+    if opt.min_consistent < 0:
+        raise SystemExit("--min_consistent must not be negative")
+    if not 0 < opt.depth_unit < math.inf:
+        raise SystemExit("--depth_unit must be positive")
+    rgb_files = sorted(glob.glob(opt.rgb_files))
+    if not rgb_files:
+        raise SystemExit(f"no files match {opt.rgb_files!r}")
+    stems = [os.path.splitext(os.path.basename(f))[0] for f in rgb_files]
+    if len(set(stems)) != len(stems):
+        raise SystemExit("two images of the glob share a name: their depth maps would overwrite each other")
+    names, c2w_all, focals_all = read_ace_pose_file(opt.pose_file, opt.confidence_threshold)
+    if not names:
+        raise SystemExit("no pose above the confidence threshold")
+    by_name = {n: k for k, n in enumerate(names)}
+    by_base = {os.path.basename(n): k for k, n in enumerate(names)}
+    pose_row = [by_name.get(f, by_base.get(os.path.basename(f))) for f in rgb_files]
+    if all(k is None for k in pose_row):
+        raise SystemExit("no image of the glob has a pose above the confidence threshold in the pose file")
+    cloud = None
+    if opt.point_cloud is not None:
+        cloud = mvs.read_point_cloud_ply(opt.point_cloud).astype(np.float64)
+        if opt.cloud_convention == "opengl":
+            cloud[:, 1], cloud[:, 2] = -cloud[:, 1], -cloud[:, 2]
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("estimate_depth.py needs a GPU: plane-sweep stereo is a HIP kernel, there is no CPU path")
+    t0 = time.perf_counter()
+    grey, image_h = mvs.load_grey_frames(rgb_files, opt.image_resolution)
+    t_decode = time.perf_counter() - t0
+    n = len(rgb_files)
+    c2w = np.full((n, 4, 4), np.nan)
+    focals = np.ones(n)
+    ranges = [None] * n
+    for f, k in enumerate(pose_row):
+        if k is None:
+            continue
+        h, w = grey[f].shape
+        c2w[f] = c2w_all[k]
+        focals[f] = focals_all[k] * h / image_h[f]               # the pose file's focal is in pixels of the original image
+        if cloud is None:
+            ranges[f] = tuple(opt.depth_range)
+        else:
+            ranges[f] = mvs.depth_range_from_cloud(cloud, np.linalg.inv(c2w[f]), focals[f], w / 2.0, h / 2.0, h, w)
+    scene_depth = np.array([math.sqrt(r[0] * r[1]) if r is not None else np.nan for r in ranges])
+    sources = mvs.select_sources(c2w, focals, [g.shape for g in grey], scene_depth, opt.sources)
+    sources = [s if r is not None else [] for s, r in zip(sources, ranges)]
+    t0 = time.perf_counter()
+    maps = mvs.estimate_depth_maps(grey, cam_to_world=np.where(np.isfinite(c2w), c2w, np.eye(4)), focals=focals, sources=sources, ranges=ranges,
+                                   planes=opt.planes, window=opt.window, keep=opt.keep, uniqueness=opt.uniqueness, tolerance=opt.tolerance,
+                                   min_consistent=opt.min_consistent, depth_unit=opt.depth_unit)
+    t_device = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    os.makedirs(opt.output_dir, exist_ok=True)
+    with ThreadPoolExecutor(max_workers=min(16, len(os.sched_getaffinity(0)))) as pool:
+        list(pool.map(lambda job: Image.fromarray(job[1]).save(os.path.join(opt.output_dir, job[0] + ".png")), zip(stems, maps)))
+    t_write = time.perf_counter() - t0
+    estimated = sum(1 for s in sources if s)
+    filled = float(np.mean([float((m > 0).mean()) for m, s in zip(maps, sources) if s])) if estimated else 0.0
+    log.info(f"Estimated {estimated} of {n} depth maps ({opt.planes} planes, up to {opt.sources} sources, window radius {opt.window}); "
+             f"{n - estimated} frames without a usable pose, range or neighbour got an empty map.")
+    log.info(f"Pixels with a depth in the estimated maps: {100.0 * filled:.1f} %.")
+    log.info(f"Decode {t_decode:.2f} s, upload + kernels + download {t_device:.2f} s, write {t_write:.2f} s.")
+    log.info(f"Done. Wrote depth maps to: {opt.output_dir}")
+    return 0

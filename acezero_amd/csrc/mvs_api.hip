@@ -1,0 +1,355 @@
+// mvs_api.hip -- plane-sweep multi-view stereo: dense depth per frame of an RGB reconstruction (include/acez.h section L:
+// acez_mvs_prefilter, acez_mvs_relative, acez_mvs_sweep, acez_mvs_check). estimate_depth.py.
+//
+// The header's section L is the definition: every float operation below is written in its order, the unit is built with
+// -ffp-contract=off, and tests/mvs_restated.py restates it in numpy float32 and integers for the bit-for-bit comparison.
+//
+// prefilter  one thread per pixel, blockIdx.y = the frame (its row is read through scalar loads); integers only.
+// sweep      one 256-thread workgroup per 16 x 16 reference pixels. A thread owns up to three pixels of the (16 + 2w)^2 halo tile
+//            (their g_r and rays stay in registers over the planes) and, per plane and source, writes their raw costs to LDS; after
+//            one barrier every thread sums its own window from LDS. Two LDS tiles alternate, so a step needs one barrier. The
+//            relative poses and intrinsics are launch arguments. Eight views of 20 scalars do not fit the scalar register file
+//            (unrolled over the slots the kernel spilled 166 of them to vector lanes), so thread 0 copies them once, from constant
+//            offsets, into LDS, and a step reads its view from there at one address per wave. A_s is an ascending list of eight
+//            registers that every source is inserted into. No cost volume exists in memory, and there is no scratch.
+// check      one thread per reference pixel; the sources unrolled over the 8 slots, read at constant offsets (scalar registers).
+// No atomics, no communication between workgroups, plain loads and stores.
+#include <math.h>
+#include <stdint.h>
+
+#include "acez_common.h"
+
+namespace {
+
+constexpr int MV_THREADS = 256;
+constexpr int MV_TILE = 16;
+constexpr int MV_MAX_RADIUS = 4;
+constexpr int MV_MAX_HALO = (MV_TILE + 2 * MV_MAX_RADIUS) * (MV_TILE + 2 * MV_MAX_RADIUS);   // 576
+constexpr int MV_PER_THREAD = (MV_MAX_HALO + MV_THREADS - 1) / MV_THREADS;                    // 3
+constexpr int MV_MAX_SIDE = 32768;
+constexpr int MV_IN_VIEW = 0x8000;      // bit 15 of an LDS entry; the raw cost (<= 255) is below it
+constexpr int MV_NO_COST = 1 << 28;     // an unused source slot: above any A_s (<= 81 * 255)
+
+struct View {        // a source as the kernels see it: the relative pose reference -> source and the source's own row
+  float m[12];
+  float focal, ppx, ppy;
+  int h, w;
+  int64_t offset;
+};
+
+struct SweepArgs {
+  View src[ACEZ_MVS_MAX_SOURCES];
+  float focal, ppx, ppy;   // the reference
+  int h, w;
+  int64_t offset;
+  float inv_far, step;
+  int planes, radius, truncation, keep, uniqueness, n_sources;
+};
+
+struct CheckArgs {
+  View src[ACEZ_MVS_MAX_SOURCES];
+  float focal, ppx, ppy;
+  int h, w;
+  int64_t offset;
+  float tolerance, depth_unit;
+  int need, n_sources;
+};
+
+__global__ void __launch_bounds__(MV_THREADS) prefilter_kernel(const uint8_t* __restrict__ grey, uint8_t* __restrict__ out,
+                                                               const acez_mvs_frame* __restrict__ frames) {
+  const acez_mvs_frame& fr = frames[blockIdx.y];            // uniform address: scalar loads
+  const int h = fr.h, w = fr.w;
+  const int i = blockIdx.x * MV_THREADS + threadIdx.x;
+  if (i >= h * w) return;
+  const int y = i / w, x = i - y * w;
+  const int x0 = max(x - 4, 0), x1 = min(x + 4, w - 1), y0 = max(y - 4, 0), y1 = min(y + 4, h - 1);
+  const uint8_t* img = grey + fr.offset;                     // [offset, offset + h * w): the host checked that range
+  int sum = 0;
+  for (int yy = y0; yy <= y1; ++yy)
+    for (int xx = x0; xx <= x1; ++xx) sum += img[yy * w + xx];
+  const int n = (x1 - x0 + 1) * (y1 - y0 + 1);
+  const int m = (sum + n / 2) / n;
+  out[fr.offset + i] = (uint8_t)min(max((int)img[i] - m + 128, 0), 255);
+}
+
+// steps 2-4 of the header's raw cost: the point (X, Y, Z) of the reference camera in source v. false: not in front of it.
+__device__ __forceinline__ bool project(const View& v, float X, float Y, float Z, float& u, float& w_, float& zc) {
+  const float xc = ((v.m[0] * X + v.m[1] * Y) + v.m[2] * Z) + v.m[3];
+  const float yc = ((v.m[4] * X + v.m[5] * Y) + v.m[6] * Z) + v.m[7];
+  zc = ((v.m[8] * X + v.m[9] * Y) + v.m[10] * Z) + v.m[11];
+  u = (v.focal * xc) / zc + v.ppx;
+  w_ = (v.focal * yc) / zc + v.ppy;
+  return zc > 0.0f;
+}
+
+// steps 1-7: the LDS entry (raw cost, bit 15 = in view) of a halo pixel with reference value gr (< 0: outside the reference frame)
+__device__ __forceinline__ int raw_cost(const uint8_t* __restrict__ g, const View& v, int gr, float rx, float ry, float z, int T) {
+  if (gr < 0) return T;
+  float u, w_, zc;
+  const bool front = project(v, rx * z, ry * z, z, u, w_, zc);
+  if (!(front && u >= 0.0f && u <= (float)(v.w - 1) && w_ >= 0.0f && w_ <= (float)(v.h - 1))) return T;
+  const int x0 = min(max((int)floorf(u), 0), v.w - 1), y0 = min(max((int)floorf(w_), 0), v.h - 1);   // the clamps only restate the test
+  const int x1 = min(x0 + 1, v.w - 1), y1 = min(y0 + 1, v.h - 1);
+  const float fx = u - (float)x0, fy = w_ - (float)y0;
+  const uint8_t* img = g + v.offset;
+  const float a = (float)img[y0 * v.w + x0], b = (float)img[y0 * v.w + x1];
+  const float c = (float)img[y1 * v.w + x0], d = (float)img[y1 * v.w + x1];
+  const float top = a + fx * (b - a);
+  const float bot = c + fx * (d - c);
+  const float val = top + fy * (bot - top);
+  const int sample = (int)(val + 0.5f);
+  return min(abs(gr - sample), T) | MV_IN_VIEW;
+}
+
+__global__ void __launch_bounds__(MV_THREADS) sweep_kernel(const uint8_t* __restrict__ g, const SweepArgs a, float* __restrict__ out_depth,
+                                                           int32_t* __restrict__ out_cost, int32_t* __restrict__ out_plane) {
+  __shared__ uint16_t s_raw[2][MV_MAX_HALO];
+  __shared__ View s_view[ACEZ_MVS_MAX_SOURCES];
+  const int t = threadIdx.x;
+  if (t == 0) {
+#pragma unroll
+    for (int s = 0; s < ACEZ_MVS_MAX_SOURCES; ++s) s_view[s] = a.src[s];   // constant offsets into the launch arguments
+  }
+  const int R = a.radius, side = MV_TILE + 2 * R, n_halo = side * side, T = a.truncation;
+  const int x_base = blockIdx.x * MV_TILE - R, y_base = blockIdx.y * MV_TILE - R;
+  int gr[MV_PER_THREAD];
+  float rx[MV_PER_THREAD], ry[MV_PER_THREAD];
+#pragma unroll
+  for (int j = 0; j < MV_PER_THREAD; ++j) {
+    const int e = t + j * MV_THREADS;
+    const int hy = y_base + e / side, hx = x_base + e % side;
+    const bool inside = e < n_halo && hx >= 0 && hx < a.w && hy >= 0 && hy < a.h;
+    gr[j] = inside ? (int)g[a.offset + (int64_t)hy * a.w + hx] : -1;
+    rx[j] = ((float)hx - a.ppx) / a.focal;
+    ry[j] = ((float)hy - a.ppy) / a.focal;
+  }
+  __syncthreads();
+  const int centre = ((t >> 4) + R) * side + (t & 15) + R;   // this thread's pixel in the halo tile; its window stays inside the tile
+  int v0 = INT32_MAX, v1 = INT32_MAX, v2 = INT32_MAX, v3 = INT32_MAX;   // the four smallest (C, k), ascending, ties by k
+  int k0 = -1, k1 = -1, k2 = -1, k3 = -1;
+  int c_before = 0, c_after = 0, c_prev = 0, n_star = 0;
+  int buf = 0;
+  for (int k = 0; k < a.planes; ++k) {
+    const float inv_k = a.inv_far + (float)k * a.step;
+    const float z = 1.0f / inv_k;
+    int A[ACEZ_MVS_MAX_SOURCES];                               // A_s in ascending order; only constant indices
+#pragma unroll
+    for (int i = 0; i < ACEZ_MVS_MAX_SOURCES; ++i) A[i] = MV_NO_COST;
+    int n_in = 0;
+    for (int s = 0; s < a.n_sources; ++s) {                   // uniform over the grid
+      const View v = s_view[s];                               // one address for the whole wave: broadcast reads
+#pragma unroll
+      for (int j = 0; j < MV_PER_THREAD; ++j) {
+        const int e = t + j * MV_THREADS;
+        if (e < n_halo) s_raw[buf][e] = (uint16_t)raw_cost(g, v, gr[j], rx[j], ry[j], z, T);
+      }
+      __syncthreads();
+      int sum = 0;
+      for (int dy = -R; dy <= R; ++dy)
+        for (int dx = -R; dx <= R; ++dx) sum += s_raw[buf][centre + dy * side + dx] & (MV_IN_VIEW - 1);
+      n_in += s_raw[buf][centre] >> 15;
+      buf ^= 1;                                               // the next step writes the other tile: one barrier per step
+#pragma unroll
+      for (int i = 0; i < ACEZ_MVS_MAX_SOURCES; ++i) {        // insert into the ascending list
+        const int lo = min(A[i], sum);
+        sum = max(A[i], sum);
+        A[i] = lo;
+      }
+    }
+    int C = 0;
+#pragma unroll
+    for (int i = 0; i < ACEZ_MVS_MAX_SOURCES; ++i)
+      if (i < a.keep) C += A[i];
+    if (k0 == k - 1) c_after = C;                             // (k0 = -1 at k = 0: c_after is only read for an interior k*)
+    if (C < v0) {
+      c_before = c_prev;
+      n_star = n_in;
+    }
+    c_prev = C;
+    if (C < v3) {
+      v3 = C, k3 = k;
+      if (v3 < v2) {
+        int tv = v2, tk = k2;
+        v2 = v3, k2 = k3, v3 = tv, k3 = tk;
+        if (v2 < v1) {
+          tv = v1, tk = k1;
+          v1 = v2, k1 = k2, v2 = tv, k2 = tk;
+          if (v1 < v0) {
+            tv = v0, tk = k0;
+            v0 = v1, k0 = k1, v1 = tv, k1 = tk;
+          }
+        }
+      }
+    }
+  }
+  const int x = blockIdx.x * MV_TILE + (t & 15), y = blockIdx.y * MV_TILE + (t >> 4);
+  if (x >= a.w || y >= a.h) return;                           // (after the last barrier)
+  const int best = v0, ks = k0, D = a.planes;
+  bool unique = true;                                         // no plane outside the neighbourhood (D <= 3)
+  if (k1 >= 0 && abs(k1 - ks) > 1) unique = v1 > 0 && 100 * best <= (100 - a.uniqueness) * v1;
+  else if (k2 >= 0 && abs(k2 - ks) > 1) unique = v2 > 0 && 100 * best <= (100 - a.uniqueness) * v2;
+  else if (k3 >= 0 && abs(k3 - ks) > 1) unique = v3 > 0 && 100 * best <= (100 - a.uniqueness) * v3;
+  float delta = 0.0f;
+  if (ks > 0 && ks < D - 1) {
+    const int den = c_before - 2 * best + c_after;
+    if (den > 0) delta = (float)(c_before - c_after) / (float)(2 * den);
+  }
+  float depth = 1.0f / (a.inv_far + ((float)ks + delta) * a.step);
+  if (n_star < a.keep || !unique || (D > 2 && (ks == 0 || ks == D - 1))) depth = 0.0f;
+  const int64_t at = a.offset + (int64_t)y * a.w + x;
+  out_depth[at] = depth;
+  if (out_cost) out_cost[at] = best;
+  if (out_plane) out_plane[at] = ks;
+}
+
+__global__ void __launch_bounds__(MV_THREADS) check_kernel(const float* __restrict__ depth, const CheckArgs a, uint16_t* __restrict__ out) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= a.w || y >= a.h) return;
+  const int64_t at = a.offset + (int64_t)y * a.w + x;
+  const float d = depth[at];
+  uint16_t result = 0;
+  if (d > 0.0f) {
+    const float rx = ((float)x - a.ppx) / a.focal, ry = ((float)y - a.ppy) / a.focal;
+    const float X = rx * d, Y = ry * d;
+    int agree = 0;
+#pragma unroll
+    for (int s = 0; s < ACEZ_MVS_MAX_SOURCES; ++s) {
+      if (s < a.n_sources) {
+        const View& v = a.src[s];
+        float u, w_, zc;
+        const bool front = project(v, X, Y, d, u, w_, zc);
+        if (front && u >= -0.5f && u < (float)v.w - 0.5f && w_ >= -0.5f && w_ < (float)v.h - 0.5f) {
+          const int ix = min(max((int)floorf(u + 0.5f), 0), v.w - 1), iy = min(max((int)floorf(w_ + 0.5f), 0), v.h - 1);
+          const float ds = depth[v.offset + (int64_t)iy * v.w + ix];
+          if (ds > 0.0f && fabsf(ds - zc) <= a.tolerance * zc) ++agree;
+        }
+      }
+    }
+    const float qd = floorf(d / a.depth_unit + 0.5f);
+    if (agree >= a.need && qd <= 65535.0f) result = (uint16_t)qd;
+  }
+  out[at] = result;
+}
+
+bool finite_all(const float* p, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!isfinite(p[i])) return false;
+  return true;
+}
+
+void relative(const acez_mvs_frame& r, const acez_mvs_frame& s, float* out12) {
+  for (int i = 0; i < 3; ++i) {
+    double R[3];
+    for (int j = 0; j < 3; ++j)
+      R[j] = ((double)s.m[4 * i] * (double)r.m[4 * j] + (double)s.m[4 * i + 1] * (double)r.m[4 * j + 1]) + (double)s.m[4 * i + 2] * (double)r.m[4 * j + 2];
+    const double t = (double)s.m[4 * i + 3] - ((R[0] * (double)r.m[3] + R[1] * (double)r.m[7]) + R[2] * (double)r.m[11]);
+    out12[4 * i] = (float)R[0];
+    out12[4 * i + 1] = (float)R[1];
+    out12[4 * i + 2] = (float)R[2];
+    out12[4 * i + 3] = (float)t;
+  }
+}
+
+View view_of(const acez_mvs_frame& r, const acez_mvs_frame& s) {
+  View v;
+  relative(r, s, v.m);
+  v.focal = s.focal, v.ppx = s.ppx, v.ppy = s.ppy, v.h = s.h, v.w = s.w, v.offset = s.offset;
+  return v;
+}
+
+}  // namespace
+
+#define MV_REQUIRE_ROW(fr, n_pixels)                                                                                                     \
+  ACEZ_REQUIRE((fr).h >= 1 && (fr).w >= 1 && (fr).h <= MV_MAX_SIDE && (fr).w <= MV_MAX_SIDE, "frame size out of range (1 .. 32768 px per side)"); \
+  ACEZ_REQUIRE(finite_all((fr).m, 12) && isfinite((fr).focal) && isfinite((fr).ppx) && isfinite((fr).ppy),                                \
+               "non-finite pose or intrinsics in the frame table");                                                                     \
+  ACEZ_REQUIRE((fr).focal > 0.0f, "focal length must be positive");                                                                     \
+  ACEZ_REQUIRE((fr).offset >= 0 && (fr).offset <= (n_pixels) && (int64_t)(fr).h * (fr).w <= (n_pixels) - (fr).offset,                   \
+               "frame past the end of the buffer")
+
+// the rows a sweep or a check touches: the reference and its sources
+#define MV_REQUIRE_VIEWS()                                                                                               \
+  ACEZ_REQUIRE(n_pixels >= 0, "negative buffer length");                                                                 \
+  ACEZ_REQUIRE(n_frames >= 1, "frame count must be at least 1");                                                         \
+  ACEZ_REQUIRE(ref >= 0 && ref < n_frames, "reference index outside the frame table");                                   \
+  ACEZ_REQUIRE(n_sources >= 1 && n_sources <= ACEZ_MVS_MAX_SOURCES, "source count out of range (1 .. 8)");                \
+  MV_REQUIRE_ROW(h_frames[ref], n_pixels);                                                                               \
+  for (int s = 0; s < n_sources; ++s) {                                                                                  \
+    ACEZ_REQUIRE(h_sources[s] >= 0 && h_sources[s] < n_frames, "source index outside the frame table");                  \
+    MV_REQUIRE_ROW(h_frames[h_sources[s]], n_pixels);                                                                    \
+  }
+
+extern "C" int acez_mvs_prefilter(const uint8_t* d_grey, uint8_t* d_out, int64_t n_pixels, const acez_mvs_frame* h_frames, int n_frames,
+                                  acez_mvs_frame* d_frames, void* stream) {
+  ACEZ_REQUIRE(d_grey && d_out && h_frames && d_frames, "null pointer");
+  ACEZ_REQUIRE(n_pixels >= 0, "negative buffer length");
+  ACEZ_REQUIRE(n_frames >= 1 && n_frames <= 65535, "frame count out of range (1 .. 65535)");
+  int64_t largest = 0;
+  for (int f = 0; f < n_frames; ++f) {
+    MV_REQUIRE_ROW(h_frames[f], n_pixels);
+    largest = largest > (int64_t)h_frames[f].h * h_frames[f].w ? largest : (int64_t)h_frames[f].h * h_frames[f].w;
+  }
+  if (int rc = acez::require_device("the stereo prefilter runs on a gfx950 GPU")) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  ACEZ_HIP_CHECK(hipMemcpyAsync(d_frames, h_frames, sizeof(acez_mvs_frame) * (size_t)n_frames, hipMemcpyHostToDevice, s));
+  ACEZ_HIP_CHECK(hipStreamSynchronize(s));   // h_frames is the caller's again
+  const dim3 grid((unsigned)((largest + MV_THREADS - 1) / MV_THREADS), (unsigned)n_frames);
+  hipLaunchKernelGGL(prefilter_kernel, grid, dim3(MV_THREADS), 0, s, d_grey, d_out, (const acez_mvs_frame*)d_frames);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}
+
+extern "C" int acez_mvs_relative(const acez_mvs_frame* ref, const acez_mvs_frame* src, float* out12) {
+  ACEZ_REQUIRE(ref && src && out12, "null pointer");
+  ACEZ_REQUIRE(finite_all(ref->m, 12) && finite_all(src->m, 12), "non-finite pose or intrinsics in the frame table");
+  relative(*ref, *src, out12);
+  return ACEZ_OK;
+}
+
+extern "C" int acez_mvs_sweep(const uint8_t* d_filtered, int64_t n_pixels, const acez_mvs_frame* h_frames, int n_frames, int ref,
+                              const int32_t* h_sources, int n_sources, float z_near, float z_far, int planes, int radius, int truncation,
+                              int keep, int uniqueness, float* d_out_depth, int32_t* d_out_cost, int32_t* d_out_plane, void* stream) {
+  ACEZ_REQUIRE(d_filtered && h_frames && h_sources && d_out_depth, "null pointer");
+  MV_REQUIRE_VIEWS();
+  ACEZ_REQUIRE(isfinite(z_near) && isfinite(z_far) && z_near > 0.0f && z_near < z_far, "the depth range needs 0 < near < far");
+  ACEZ_REQUIRE(planes >= 2 && planes <= 1024, "plane count out of range (2 .. 1024)");
+  ACEZ_REQUIRE(radius >= 0 && radius <= MV_MAX_RADIUS, "window radius out of range (0 .. 4)");
+  ACEZ_REQUIRE(truncation >= 1 && truncation <= 255, "cost truncation out of range (1 .. 255)");
+  ACEZ_REQUIRE(keep >= 1 && keep <= n_sources, "keep out of range (1 .. sources)");
+  ACEZ_REQUIRE(uniqueness >= 0 && uniqueness <= 100, "uniqueness percentage out of range (0 .. 100)");
+  SweepArgs a;
+  const acez_mvs_frame& r = h_frames[ref];
+  for (int s = 0; s < ACEZ_MVS_MAX_SOURCES; ++s) a.src[s] = view_of(r, h_frames[h_sources[s < n_sources ? s : 0]]);
+  a.focal = r.focal, a.ppx = r.ppx, a.ppy = r.ppy, a.h = r.h, a.w = r.w, a.offset = r.offset;
+  const float inv_near = 1.0f / z_near;
+  a.inv_far = 1.0f / z_far;
+  a.step = (inv_near - a.inv_far) / (float)(planes - 1);
+  a.planes = planes, a.radius = radius, a.truncation = truncation, a.keep = keep, a.uniqueness = uniqueness, a.n_sources = n_sources;
+  if (int rc = acez::require_device("the plane sweep runs on a gfx950 GPU")) return rc;
+  const dim3 grid((r.w + MV_TILE - 1) / MV_TILE, (r.h + MV_TILE - 1) / MV_TILE);
+  hipLaunchKernelGGL(sweep_kernel, grid, dim3(MV_THREADS), 0, (hipStream_t)stream, d_filtered, a, d_out_depth, d_out_cost, d_out_plane);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}
+
+extern "C" int acez_mvs_check(const float* d_depth, int64_t n_pixels, const acez_mvs_frame* h_frames, int n_frames, int ref,
+                              const int32_t* h_sources, int n_sources, float tolerance, int min_consistent, float depth_unit,
+                              uint16_t* d_out, void* stream) {
+  ACEZ_REQUIRE(d_depth && h_frames && h_sources && d_out, "null pointer");
+  MV_REQUIRE_VIEWS();
+  ACEZ_REQUIRE(isfinite(tolerance) && tolerance >= 0.0f, "tolerance must be finite and not negative");
+  ACEZ_REQUIRE(min_consistent >= 0, "min_consistent must not be negative");
+  ACEZ_REQUIRE(isfinite(depth_unit) && depth_unit > 0.0f, "depth unit must be positive");
+  CheckArgs a;
+  const acez_mvs_frame& r = h_frames[ref];
+  for (int s = 0; s < ACEZ_MVS_MAX_SOURCES; ++s) a.src[s] = view_of(r, h_frames[h_sources[s < n_sources ? s : 0]]);
+  a.focal = r.focal, a.ppx = r.ppx, a.ppy = r.ppy, a.h = r.h, a.w = r.w, a.offset = r.offset;
+  a.tolerance = tolerance, a.depth_unit = depth_unit;
+  a.need = min_consistent < n_sources ? min_consistent : n_sources;
+  a.n_sources = n_sources;
+  if (int rc = acez::require_device("the consistency check runs on a gfx950 GPU")) return rc;
+  const dim3 grid((r.w + 63) / 64, (r.h + 3) / 4);
+  hipLaunchKernelGGL(check_kernel, grid, dim3(MV_THREADS), 0, (hipStream_t)stream, d_depth, a, d_out);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}

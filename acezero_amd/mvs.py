@@ -1,0 +1,209 @@
+"""Dense depth for RGB reconstructions by plane-sweep stereo over neighbouring frames (include/acez.h section L, DESIGN.md section 4k;
+estimate_depth.py is the command line).
+
+    sources = select_sources(cam_to_world, focals, sizes, scene_depth, 4)
+    maps = estimate_depth_maps(grey_images, cam_to_world=cam_to_world, focals=focals, sources=sources, ranges=ranges)
+
+The result is one uint16 depth map per frame in the units acezero_amd.fusion takes. Prefilter, sweep and consistency check are HIP
+kernels (acezero_amd/csrc/mvs_api.hip). There is no CPU fallback. This is classical multi-view stereo, not a learned one."""
+import concurrent.futures
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _native as N
+from .fusion import _per_frame, _w2c34
+from .head import _ptr, _stream
+
+MAX_AXIS_ANGLE_DEG = 30.0           # select_sources: a source looks within this angle of the frame's own optical axis
+BASELINE_RATIO = (0.02, 0.5)        # ... and stands this far away, in units of the scene depth
+BEST_BASELINE_RATIO = 0.1           # ... preferably this far
+MIN_CLOUD_POINTS = 16               # depth_range_from_cloud: fewer points inside the frame give no range
+RANGE_MARGIN = 1.25
+SWEEP_STREAMS = 4                   # StereoFrames.sweep_frames: reference frames swept side by side
+
+
+def select_sources(c2w, focals, sizes, scene_depth, n_sources):
+    """For every frame the up to n_sources other frames to match it against, best first (host numpy). c2w [n,4,4] camera -> world; a
+    frame without a usable pose has a non-finite one and neither gets nor serves as a source. A candidate's optical axis is within
+    30 degrees of the frame's own and its baseline / scene_depth (one number, or one per frame) within [0.02, 0.5]; candidates are
+    ordered by |ratio - 0.1|, ties by frame index. focals and sizes ([(h, w)]) are part of the signature for rankings that weigh
+    the overlap; this one does not read them. Returns a list of n lists of frame indices; an empty one means no depth map."""
+    c2w = np.asarray(c2w, np.float64).reshape(-1, 4, 4)
+    n = len(c2w)
+    depth = np.broadcast_to(np.asarray(scene_depth, np.float64), (n,))
+    posed = np.isfinite(c2w).all((1, 2))
+    axis, centre = c2w[:, :3, 2], c2w[:, :3, 3]
+    out = []
+    for i in range(n):
+        ranked = []
+        if posed[i] and np.isfinite(depth[i]) and depth[i] > 0:
+            for j in range(n):
+                if j == i or not posed[j]:
+                    continue
+                cos = float(axis[i] @ axis[j]) / float(np.linalg.norm(axis[i]) * np.linalg.norm(axis[j]))
+                ratio = float(np.linalg.norm(centre[j] - centre[i])) / float(depth[i])
+                if cos >= np.cos(np.radians(MAX_AXIS_ANGLE_DEG)) and BASELINE_RATIO[0] <= ratio <= BASELINE_RATIO[1]:
+                    ranked.append((abs(ratio - BEST_BASELINE_RATIO), j))
+        out.append([j for _, j in sorted(ranked)[:int(n_sources)]])
+    return out
+
+
+def depth_range_from_cloud(points, w2c, focal, ppx, ppy, h, w):
+    """(near, far) of a frame from a point cloud [m,3] in world coordinates: the 1st and 99th percentile of camera z over the points
+    that project inside the frame (section K's pixel convention), widened by 1 / 1.25 and 1.25. None if fewer than 16 points do."""
+    m = np.asarray(w2c, np.float64)[:3]
+    cam = np.asarray(points, np.float64).reshape(-1, 3) @ m[:, :3].T + m[:, 3]
+    z = cam[:, 2]
+    with np.errstate(all="ignore"):
+        u, v = focal * cam[:, 0] / z + ppx, focal * cam[:, 1] / z + ppy
+        inside = (z > 0) & (u >= -0.5) & (u < w - 0.5) & (v >= -0.5) & (v < h - 0.5)
+    if int(inside.sum()) < MIN_CLOUD_POINTS:
+        return None
+    near, far = np.percentile(z[inside], [1.0, 99.0])
+    return float(near / RANGE_MARGIN), float(far * RANGE_MARGIN)
+
+
+def read_point_cloud_ply(path):
+    """float32 [m,3] of a binary little-endian .ply whose vertex element is what pointcloud.write_point_cloud writes (float x y z,
+    uchar red green blue alpha); further elements (a mesh's faces) are ignored."""
+    blob = open(str(path), "rb").read()
+    head, sep, body = blob.partition(b"end_header\n")
+    lines = head.decode("ascii", "replace").splitlines()
+    if not sep or lines[:2] != ["ply", "format binary_little_endian 1.0"]:
+        raise SystemExit(f"{path}: not a binary little-endian .ply")
+    count, props, element = 0, [], None
+    for line in lines:
+        tok = line.split()
+        if tok[:1] == ["element"]:
+            element = tok[1]
+            if element == "vertex":
+                count = int(tok[2])
+        elif tok[:1] == ["property"] and element == "vertex":
+            props.append(tuple(tok[1:]))
+    if props != [("float", "x"), ("float", "y"), ("float", "z"), ("uchar", "red"), ("uchar", "green"), ("uchar", "blue"), ("uchar", "alpha")]:
+        raise SystemExit(f"{path}: expected the vertex layout export_point_cloud.py writes (float x y z, uchar red green blue alpha)")
+    if len(body) < 16 * count:
+        raise SystemExit(f"{path}: truncated")
+    rec = np.frombuffer(body[:16 * count], dtype=[("xyz", "<f4", (3,)), ("rgba", "u1", (4,))])
+    return rec["xyz"].copy()
+
+
+def load_grey_frames(files, image_resolution, workers=12):
+    """Decode in a pool of threads (ingest.decode_frames), resize so that the short side is image_resolution and convert to grey,
+    both as cli.load_frames does (Pillow bilinear, convert('L')): (list of uint8 [h,w], list of the files' original heights)."""
+    from PIL import Image
+    from .ingest import decode_frames, pool_size, resized_size
+    decoded = decode_frames(files, workers)
+
+    def small(a):
+        _, nh, nw = resized_size(a.shape[1], a.shape[0], image_resolution)
+        return np.ascontiguousarray(np.asarray(Image.fromarray(a).resize((nw, nh), Image.BILINEAR).convert("L"), np.uint8))
+    with concurrent.futures.ThreadPoolExecutor(max_workers=pool_size(workers)) as pool:
+        return list(pool.map(small, decoded)), [a.shape[0] for a in decoded]
+
+
+class StereoFrames:
+    """The frames of one estimate on the device: `grey`, `filtered` uint8, `depth` float32, `cost`, `plane` int32 and `out` int16
+    (the uint16 bits), each one packed buffer of n_pixels elements, and the host table of rows (offset, size, pose, intrinsics)."""
+
+    def __init__(self, images, world_to_cam=None, cam_to_world=None, focals=None, ppx=None, ppy=None, device="cuda"):
+        device = torch.device(device)
+        if device.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("plane-sweep stereo needs a GPU: prefilter, sweep and check are HIP kernels, there is no CPU path")
+        if focals is None:
+            raise ValueError("focals is required")
+        self.device, n = device, len(images)
+        if torch.is_tensor(images):
+            if images.dtype != torch.uint8 or images.dim() != 3:
+                raise TypeError(f"expected a uint8 tensor [n,h,w], got {images.dtype} {tuple(images.shape)}")
+            self.sizes = [tuple(images.shape[1:])] * n
+            self.grey = images.to(device).contiguous().reshape(-1)
+        else:
+            arrays = [np.ascontiguousarray(a.cpu().numpy() if torch.is_tensor(a) else a) for a in images]
+            for a in arrays:
+                if a.dtype != np.uint8 or a.ndim != 2:
+                    raise TypeError(f"expected uint8 [h,w] grey images, got {a.dtype} {a.shape}")
+            self.sizes = [a.shape for a in arrays]
+            self.grey = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrays]) if arrays else np.zeros(0, np.uint8)).to(device)
+        self.offsets = [int(o) for o in np.concatenate([[0], np.cumsum([h * w for h, w in self.sizes])])[:n]]
+        self.n, self.n_pixels = n, int(self.grey.numel())
+        w2c, focals = _w2c34(world_to_cam, cam_to_world, n), _per_frame(focals, n)
+        self.rows = (N.TsdfFrame * max(n, 1))()
+        for f in range(n):
+            h, w = self.sizes[f]
+            row = self.rows[f]
+            row.m[:] = w2c[f].reshape(12).tolist()
+            row.focal = float(focals[f])
+            row.ppx = float(_per_frame(ppx, n)[f]) if ppx is not None else w / 2.0
+            row.ppy = float(_per_frame(ppy, n)[f]) if ppy is not None else h / 2.0
+            row.h, row.w, row.offset = int(h), int(w), self.offsets[f]
+        new = lambda dtype: torch.zeros(self.n_pixels, dtype=dtype, device=device)
+        self.filtered, self.depth, self.cost, self.plane, self.out = new(torch.uint8), new(torch.float32), new(torch.int32), new(torch.int32), new(torch.int16)
+        self._d_rows = torch.empty(max(n, 1) * C.sizeof(N.TsdfFrame), dtype=torch.uint8, device=device)
+
+    def prefilter(self):
+        with torch.cuda.device(self.device):
+            N.check(N.lib().acez_mvs_prefilter(_ptr(self.grey), _ptr(self.filtered), self.n_pixels, self.rows, self.n, _ptr(self._d_rows), _stream()))
+        return self
+
+    def sweep(self, ref, sources, z_near, z_far, planes=128, window=2, truncation=40, keep=None, uniqueness=5):
+        """The depth map of frame `ref` into `depth` (and C(k*), k* into `cost`, `plane`); keep defaults to ceil(sources / 2)."""
+        src = (C.c_int32 * max(len(sources), 1))(*[int(s) for s in sources])
+        keep = -(-len(sources) // 2) if keep is None else int(keep)
+        with torch.cuda.device(self.device):
+            N.check(N.lib().acez_mvs_sweep(_ptr(self.filtered), self.n_pixels, self.rows, self.n, int(ref), src, len(sources), float(z_near),
+                                           float(z_far), int(planes), int(window), int(truncation), keep, int(uniqueness), _ptr(self.depth),
+                                           _ptr(self.cost), _ptr(self.plane), _stream()))
+        return self
+
+    def sweep_frames(self, jobs, planes=128, window=2, truncation=40, uniqueness=5, streams=SWEEP_STREAMS):
+        """sweep() for every (ref, sources, z_near, z_far, keep) of jobs. A frame's sweep is 20 x 15 workgroups at 240 x 320 px, about
+        one wave per SIMD, so the launches go round-robin to `streams` streams that start after the current stream's work (the
+        prefilter) and that the current stream then waits for. The frames write disjoint parts of the buffers: the same bits."""
+        if not jobs:
+            return self
+        main = torch.cuda.current_stream(self.device)
+        side = [torch.cuda.Stream(self.device) for _ in range(max(1, min(int(streams), len(jobs))))]
+        for s in side:
+            s.wait_stream(main)
+        for i, (ref, sources, z_near, z_far, keep) in enumerate(jobs):
+            with torch.cuda.stream(side[i % len(side)]):
+                self.sweep(ref, sources, z_near, z_far, planes, window, truncation, keep, uniqueness)
+        for s in side:
+            main.wait_stream(s)
+        return self
+
+    def check(self, ref, sources, tolerance=0.01, min_consistent=2, depth_unit=0.001):
+        src = (C.c_int32 * max(len(sources), 1))(*[int(s) for s in sources])
+        with torch.cuda.device(self.device):
+            N.check(N.lib().acez_mvs_check(_ptr(self.depth), self.n_pixels, self.rows, self.n, int(ref), src, len(sources), float(tolerance),
+                                           int(min_consistent), float(depth_unit), _ptr(self.out), _stream()))
+        return self
+
+    def frame(self, buffer, f):
+        """Frame f of one of the packed buffers as a host array [h,w] (`out` as uint16)."""
+        h, w = self.sizes[f]
+        a = buffer[self.offsets[f]:self.offsets[f] + h * w].reshape(h, w).cpu().numpy()
+        return a.view(np.uint16) if a.dtype == np.int16 else a
+
+
+def estimate_depth_maps(images, world_to_cam=None, cam_to_world=None, focals=None, ppx=None, ppy=None, sources=None, ranges=None, planes=128,
+                        window=2, truncation=40, keep=None, uniqueness=5, tolerance=0.01, min_consistent=2, depth_unit=0.001, device="cuda"):
+    """One uint16 depth map [h,w] per frame (0 = no depth), in units of depth_unit metres. images: a uint8 device tensor [n,h,w] or a
+    list of uint8 [h,w] host arrays whose sizes may differ (grey). sources: select_sources' lists; ranges: per frame (near, far) or
+    None. A frame without sources or range gets an all-zero map. keep: None = ceil(sources / 2) of each frame, else capped at the
+    frame's number of sources. Upload, prefilter once, sweep every frame, check every frame, download."""
+    if sources is None or ranges is None:
+        raise ValueError("sources and ranges are required")
+    fs = StereoFrames(images, world_to_cam, cam_to_world, focals, ppx, ppy, device)
+    live = [f for f in range(fs.n) if len(sources[f]) and ranges[f] is not None]
+    if live:
+        fs.prefilter()
+    fs.sweep_frames([(f, sources[f], ranges[f][0], ranges[f][1], None if keep is None else min(int(keep), len(sources[f]))) for f in live],
+                    planes, window, truncation, uniqueness)
+    for f in live:
+        fs.check(f, sources[f], tolerance, min_consistent, depth_unit)
+    torch.cuda.synchronize(fs.device)
+    return [fs.frame(fs.out, f) for f in range(fs.n)]

@@ -843,6 +843,81 @@ int acez_tsdf_faces(const float* d_tsdf, const float* d_weight, int nx, int ny, 
                     uint8_t* d_edge_flags, const int32_t* d_vertex_rank, const int32_t* d_edge_rank, int32_t* d_out_faces,
                     int64_t n_faces, void* stream);
 
+/* =====================================================================================================
+ * L. Dense depth for RGB reconstructions: plane-sweep multi-view stereo (estimate_depth.py)
+ * =====================================================================================================
+ * Frames arrive as in section K: packed buffers of n_pixels elements and a HOST table of acez_mvs_frame rows (= acez_tsdf_frame:
+ * m[12] the 3 x 4 world -> camera rows, focal, ppx, ppy in pixels of THIS frame, h, w, and `offset`, the element index of the frame's
+ * pixel (0, 0) in every packed buffer of the call). Frames of different sizes may share a call. Camera model and pixel convention are
+ * section K's: u = (focal * xc) / zc + ppx, pixel index = image coordinate, nearest pixel floor(u + 0.5), so the fuser reads a depth
+ * map at the coordinates it was estimated at. Every entry point is stateless, allocates nothing and reads no environment variable;
+ * kernels run on `stream`. All float arithmetic is fp32, round to nearest, one rounding per operation in the order written (the unit
+ * is built without contraction), division is IEEE division, int(x) truncates. tests/mvs_restated.py restates all of it in numpy.
+ *
+ * PREFILTER (acez_mvs_prefilter, one launch over all frames). Per pixel (x, y) of a frame, integers only: sum and n = the sum and the
+ * number of the frame's pixels in [x - 4, x + 4] x [y - 4, y + 4]; m = (sum + n / 2) / n; g = min(max(I - m + 128, 0), 255).
+ * d_grey and d_out are uint8 [n_pixels] and must not overlap. The table is copied into d_frames (device scratch of n_frames rows) on
+ * `stream`; the copy has completed when the call returns. n_frames in 1 .. 65535.
+ *
+ * RELATIVE POSE (acez_mvs_relative; host only, no device needed; the sweep and the check call it). From the rows r (reference) and s
+ * (source), in DOUBLE, one rounding per operation, then each of the 12 numbers rounded once to float:
+ *   R[i][j] = (s.m[4i] * r.m[4j] + s.m[4i+1] * r.m[4j+1]) + s.m[4i+2] * r.m[4j+2]
+ *   t[i]    = s.m[4i+3] - ((R[i][0] * r.m[3] + R[i][1] * r.m[7]) + R[i][2] * r.m[11])
+ *   out12   = float of R[0][0], R[0][1], R[0][2], t[0], R[1][0], ...           (a point of r's camera -> s's camera)
+ *
+ * SWEEP (acez_mvs_sweep, one launch per reference frame r, on the PREFILTERED buffer g). S sources h_sources[0 .. S-1] (rows of the
+ * table), D planes fronto-parallel to r and uniform in inverse depth, window radius w, truncation T, `keep`, uniqueness percentage q.
+ *   planes    inv_near = 1 / z_near; inv_far = 1 / z_far; step = (inv_near - inv_far) / float(D - 1)      (host, fp32)
+ *             inv_k = inv_far + float(k) * step; z_k = 1 / inv_k, k = 0 (far) .. D - 1 (near)
+ *   ray       rx = (float(x) - r.ppx) / r.focal, ry = (float(y) - r.ppy) / r.focal of reference pixel p' = (x, y)
+ *   raw(p', k, s), with M = the relative pose r -> s, f, cx, cy, hs, ws = s's focal, ppx, ppy, h, w:
+ *     1. X = rx * z_k, Y = ry * z_k
+ *     2. xc = ((M0 * X + M1 * Y) + M2 * z_k) + M3                              (yc from M4..M7, zc from M8..M11)
+ *     3. u = (f * xc) / zc + cx, v = (f * yc) / zc + cy
+ *     4. IN VIEW iff zc > 0 && u >= 0 && u <= float(ws - 1) && v >= 0 && v <= float(hs - 1)      (on the floats: NaN fails)
+ *     5. x0 = int(floor(u)), x1 = min(x0 + 1, ws - 1), fx = u - float(x0); y0, y1, fy alike     (all four texels inside the frame)
+ *     6. a = g_s[y0][x0], b = g_s[y0][x1], c = g_s[y1][x0], d = g_s[y1][x1] as floats;
+ *        top = a + fx * (b - a); bot = c + fx * (d - c); val = top + fy * (bot - top); sample = int(val + 0.5)
+ *     7. raw = min(|g_r(p') - sample|, T) in view, T out of view; T for a p' outside the reference frame (never in view)
+ *   A_s(p, k) = the sum of raw over the (2w + 1)^2 pixels p' around p. C(p, k) = the sum of the `keep` smallest of A_0 .. A_{S-1}.
+ *   k* = the first minimum of C over k. N* = the number of sources with p itself in view at k*.
+ *   C2 = the smallest C(p, k) over the planes with |k - k*| > 1. UNIQUE iff there is no such plane, or
+ *        C2 > 0 && 100 * C(k*) <= (100 - q) * C2                               (integers; 0 against 0 is a tie, not a winner)
+ *   delta = 0; if 0 < k* < D - 1: den = C(k*-1) - 2 C(k*) + C(k*+1); if den > 0: delta = float(C(k*-1) - C(k*+1)) / float(2 * den)
+ *   depth = 1 / (inv_far + (float(k*) + delta) * step), and 0 if N* < keep, or not UNIQUE, or (D > 2 and k* is 0 or D - 1).
+ * Outputs at r's offset, row-major h x w: d_out_depth float32 [n_pixels]; optional (NULL) d_out_cost int32 = C(k*), d_out_plane
+ * int32 = k* (both written for every pixel, kept or not). Only r's h x w elements are written.
+ * Kernel shape (acezero_amd/csrc/mvs_api.hip): a 256-thread workgroup owns 16 x 16 reference pixels, reads their halo of g_r once
+ * (up to three halo pixels per thread, kept in registers), then per plane and source writes the raw costs of the (16 + 2w)^2 halo
+ * tile to LDS and sums the windows from there; A_s, the four smallest (C, k) and the costs beside the best stay in registers. No cost volume exists in memory. The relative poses and
+ * intrinsics are launch arguments. No atomics, no communication between workgroups, plain loads and stores.
+ *
+ * CHECK (acez_mvs_check, one launch per reference frame, after every source has a depth map in d_depth float32 [n_pixels]).
+ * Per pixel (x, y) of r with d = d_depth[r.offset + y * w + x] > 0, per source s:
+ *     1. X = rx * d, Y = ry * d (rx, ry as above); xc, yc, zc as step 2 with z_k = d; skip unless zc > 0; u, v as step 3
+ *     2. skip unless u >= -0.5 && u < float(ws) - 0.5 && v >= -0.5 && v < float(hs) - 0.5
+ *        ix = min(int(floor(u + 0.5)), ws - 1), iy = min(int(floor(v + 0.5)), hs - 1); ds = d_depth[s.offset + iy * ws + ix]
+ *     3. s AGREES iff ds > 0 && |ds - zc| <= tolerance * zc
+ * The pixel is kept iff at least min(min_consistent, S) sources agree. d_out uint16 [n_pixels] at r's offset:
+ * qd = floor(d / depth_unit + 0.5); qd as uint16 if kept and qd <= 65535, else 0. d_depth is not written.
+ *
+ * ACEZ_ERR_INVALID, before anything is launched, for: a null pointer (other than the two optional outputs), n_pixels < 0, n_frames
+ * < 1, a row with h or w outside 1 .. 32768, focal not > 0, a non-finite number, offset < 0 or offset + h * w > n_pixels, `ref` or a
+ * source index outside 0 .. n_frames - 1, n_sources outside 1 .. 8, not 0 < z_near < z_far (or not finite), planes
+ * outside 2 .. 1024, radius outside 0 .. 4, truncation outside 1 .. 255, keep outside 1 .. n_sources, uniqueness outside 0 .. 100,
+ * tolerance not finite or < 0, min_consistent < 0, depth_unit not > 0. */
+#define ACEZ_MVS_MAX_SOURCES 8
+typedef acez_tsdf_frame acez_mvs_frame;
+int acez_mvs_prefilter(const uint8_t* d_grey, uint8_t* d_out, int64_t n_pixels, const acez_mvs_frame* h_frames, int n_frames,
+                       acez_mvs_frame* d_frames, void* stream);
+int acez_mvs_relative(const acez_mvs_frame* ref, const acez_mvs_frame* src, float* out12);
+int acez_mvs_sweep(const uint8_t* d_filtered, int64_t n_pixels, const acez_mvs_frame* h_frames, int n_frames, int ref,
+                   const int32_t* h_sources, int n_sources, float z_near, float z_far, int planes, int radius, int truncation, int keep,
+                   int uniqueness, float* d_out_depth, int32_t* d_out_cost, int32_t* d_out_plane, void* stream);
+int acez_mvs_check(const float* d_depth, int64_t n_pixels, const acez_mvs_frame* h_frames, int n_frames, int ref,
+                   const int32_t* h_sources, int n_sources, float tolerance, int min_consistent, float depth_unit, uint16_t* d_out,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
