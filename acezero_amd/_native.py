@@ -212,6 +212,12 @@ SYMBOLS = {
                                  C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acez_mvs_check": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(TsdfFrame), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_float,
                                  C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "acez_mvs_volume": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(TsdfFrame), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_float,
+                                  C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "acez_mvs_aggregate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p]),
+    "acez_mvs_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(TsdfFrame), C.c_int, C.c_int, C.c_float, C.c_float,
+                                  C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

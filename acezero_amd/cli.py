@@ -1281,6 +1281,13 @@ def estimate_depth_parser():
     p.add_argument("--min_consistent", type=int, default=2, help="a depth is kept if this many sources agree with it")
     p.add_argument("--confidence_threshold", type=float, default=1000, help="ignore pose-file entries below this confidence")
     p.add_argument("--depth_unit", type=float, default=0.001, help="metres per unit of the written depth maps (0.001: millimetres)")
+    p.add_argument("--aggregation", type=str, default="none", choices=["none", "sgm"],
+                   help="sgm: smooth the plane costs along scanlines before a plane is chosen (semi-global matching), so that textureless "
+                        "walls inherit the depth of the texture around them instead of coming out empty")
+    p.add_argument("--sgm_paths", type=int, default=None, choices=[4, 8], help="scanline directions of --aggregation sgm; default: 4")
+    p.add_argument("--sgm_p1", type=int, default=None, help="penalty for moving one plane; default: 1.6 per sample of a cost "
+                                                            "(KEEP * (2 WINDOW + 1)^2 samples)")
+    p.add_argument("--sgm_p2", type=int, default=None, help="penalty for a jump of more than one plane; default: 12.8 per sample")
     return p
 
 
@@ -1315,6 +1322,14 @@ def estimate_depth_main(argv=None):
         raise SystemExit("--min_consistent must not be negative")
     if not 0 < opt.depth_unit < math.inf:
         raise SystemExit("--depth_unit must be positive")
+    sgm = opt.aggregation == "sgm"
+    if not sgm and (opt.sgm_paths is not None or opt.sgm_p1 is not None or opt.sgm_p2 is not None):
+        raise SystemExit("--sgm_paths, --sgm_p1 and --sgm_p2 need --aggregation sgm")
+    if sgm:
+        keep_most = opt.keep if opt.keep is not None else -(-opt.sources // 2)
+        p1, p2 = mvs.sgm_penalties(keep_most, opt.window, opt.sgm_p1, opt.sgm_p2)
+        if not 1 <= p1 <= p2 <= 32767:
+            raise SystemExit("--sgm_p1 and --sgm_p2 need 1 <= P1 <= P2 <= 32767")
     rgb_files = sorted(glob.glob(opt.rgb_files))
     if not rgb_files:
         raise SystemExit(f"no files match {opt.rgb_files!r}")
@@ -1358,9 +1373,11 @@ def estimate_depth_main(argv=None):
     sources = mvs.select_sources(c2w, focals, [g.shape for g in grey], scene_depth, opt.sources)
     sources = [s if r is not None else [] for s, r in zip(sources, ranges)]
     t0 = time.perf_counter()
+    info = {}
     maps = mvs.estimate_depth_maps(grey, cam_to_world=np.where(np.isfinite(c2w), c2w, np.eye(4)), focals=focals, sources=sources, ranges=ranges,
                                    planes=opt.planes, window=opt.window, keep=opt.keep, uniqueness=opt.uniqueness, tolerance=opt.tolerance,
-                                   min_consistent=opt.min_consistent, depth_unit=opt.depth_unit)
+                                   min_consistent=opt.min_consistent, depth_unit=opt.depth_unit, aggregation=opt.aggregation if sgm else None,
+                                   sgm_paths=opt.sgm_paths, sgm_p1=opt.sgm_p1, sgm_p2=opt.sgm_p2, info=info)
     t_device = time.perf_counter() - t0
     t0 = time.perf_counter()
     os.makedirs(opt.output_dir, exist_ok=True)
@@ -1371,6 +1388,11 @@ def estimate_depth_main(argv=None):
     filled = float(np.mean([float((m > 0).mean()) for m, s in zip(maps, sources) if s])) if estimated else 0.0
     log.info(f"Estimated {estimated} of {n} depth maps ({opt.planes} planes, up to {opt.sources} sources, window radius {opt.window}); "
              f"{n - estimated} frames without a usable pose, range or neighbour got an empty map.")
+    if sgm:
+        log.info(f"Aggregation: sgm, {opt.sgm_paths or mvs.SGM_PATHS} paths, P1 / P2 = {p1} / {p2} at KEEP = {keep_most}; scratch (cost volume and "
+                 f"aggregated costs, one pair per stream) {info.get('sgm_scratch_bytes', 0) / 2 ** 20:.1f} MiB.")
+    else:
+        log.info("Aggregation: none (each pixel's best plane on its own).")
     log.info(f"Pixels with a depth in the estimated maps: {100.0 * filled:.1f} %.")
     log.info(f"Decode {t_decode:.2f} s, upload + kernels + download {t_device:.2f} s, write {t_write:.2f} s.")
     log.info(f"Done. Wrote depth maps to: {opt.output_dir}")

@@ -13,7 +13,19 @@
 //            offsets, into LDS, and a step reads its view from there at one address per wave. A_s is an ascending list of eight
 //            registers that every source is inserted into. No cost volume exists in memory, and there is no scratch.
 // check      one thread per reference pixel; the sources unrolled over the 8 slots, read at constant offsets (scalar registers).
-// No atomics, no communication between workgroups, plain loads and stores.
+// The three above: no atomics, no communication between workgroups, plain loads and stores.
+//
+// Section M (semi-global aggregation of the plane costs: acez_mvs_volume, acez_mvs_aggregate, acez_mvs_select):
+// volume     the sweep kernel's second instantiation (template parameter VOLUME): the same plane loop, but C(p, k) and V(p, k) go to
+//            memory per plane (uint16, V in bit 15, [y][x][k]) instead of into the best-four registers.
+// aggregate  one wavefront walks one scanline of one direction; a 256-thread workgroup holds four of them, the grid all scanlines of
+//            all directions of the call. Lane l holds the planes l, l + 64, ...: L_r(q, .) stays in registers from step to step, the
+//            k - 1 / k + 1 neighbours come from one wave rotate each (DPP; lane 0 / 63 take the neighbouring register's rotated
+//            value), min_j L_r(q, j) from a DPP reduction inside each row of 16 lanes and four lane reads. A step reads the
+//            pixel's D costs as one contiguous run, requested AG_AHEAD steps before it is needed, and adds L_r into S with 32-bit
+//            integer atomics that return nothing: the directions run side by side, and integer addition makes the sum
+//            independent of their order. No LDS.
+// select     16 lanes per pixel: a first pass over the D values finds the first minimum (the key X * 1024 + k), a second C2.
 #include <math.h>
 #include <stdint.h>
 
@@ -101,8 +113,11 @@ __device__ __forceinline__ int raw_cost(const uint8_t* __restrict__ g, const Vie
   return min(abs(gr - sample), T) | MV_IN_VIEW;
 }
 
+// VOLUME: write C(p, k) | V(p, k) << 15 of every plane to `volume` ([y][x][k] of the reference frame) and nothing else.
+template <bool VOLUME>
 __global__ void __launch_bounds__(MV_THREADS) sweep_kernel(const uint8_t* __restrict__ g, const SweepArgs a, float* __restrict__ out_depth,
-                                                           int32_t* __restrict__ out_cost, int32_t* __restrict__ out_plane) {
+                                                           int32_t* __restrict__ out_cost, int32_t* __restrict__ out_plane,
+                                                           uint16_t* __restrict__ volume) {
   __shared__ uint16_t s_raw[2][MV_MAX_HALO];
   __shared__ View s_view[ACEZ_MVS_MAX_SOURCES];
   const int t = threadIdx.x;
@@ -129,6 +144,9 @@ __global__ void __launch_bounds__(MV_THREADS) sweep_kernel(const uint8_t* __rest
   int k0 = -1, k1 = -1, k2 = -1, k3 = -1;
   int c_before = 0, c_after = 0, c_prev = 0, n_star = 0;
   int buf = 0;
+  const int px = blockIdx.x * MV_TILE + (t & 15), py = blockIdx.y * MV_TILE + (t >> 4);
+  const bool in_frame = px < a.w && py < a.h;
+  const int64_t cell = ((int64_t)py * a.w + px) * a.planes;   // this pixel's run of the volume
   for (int k = 0; k < a.planes; ++k) {
     const float inv_k = a.inv_far + (float)k * a.step;
     const float z = 1.0f / inv_k;
@@ -160,6 +178,10 @@ __global__ void __launch_bounds__(MV_THREADS) sweep_kernel(const uint8_t* __rest
 #pragma unroll
     for (int i = 0; i < ACEZ_MVS_MAX_SOURCES; ++i)
       if (i < a.keep) C += A[i];
+    if constexpr (VOLUME) {
+      if (in_frame) volume[cell + k] = (uint16_t)(C | (n_in >= a.keep ? MV_IN_VIEW : 0));   // the host checked C <= 32767
+      continue;
+    }
     if (k0 == k - 1) c_after = C;                             // (k0 = -1 at k = 0: c_after is only read for an interior k*)
     if (C < v0) {
       c_before = c_prev;
@@ -182,8 +204,8 @@ __global__ void __launch_bounds__(MV_THREADS) sweep_kernel(const uint8_t* __rest
       }
     }
   }
-  const int x = blockIdx.x * MV_TILE + (t & 15), y = blockIdx.y * MV_TILE + (t >> 4);
-  if (x >= a.w || y >= a.h) return;                           // (after the last barrier)
+  if (VOLUME || !in_frame) return;                            // (after the last barrier)
+  const int x = px, y = py;
   const int best = v0, ks = k0, D = a.planes;
   bool unique = true;                                         // no plane outside the neighbourhood (D <= 3)
   if (k1 >= 0 && abs(k1 - ks) > 1) unique = v1 > 0 && 100 * best <= (100 - a.uniqueness) * v1;
@@ -229,6 +251,154 @@ __global__ void __launch_bounds__(MV_THREADS) check_kernel(const float* __restri
     if (agree >= a.need && qd <= 65535.0f) result = (uint16_t)qd;
   }
   out[at] = result;
+}
+
+// ------------------------------------------------------------------------------------------------- section M: aggregate, select
+constexpr int AG_INF = 1 << 29;          // an absent plane: above any L_r (<= 65534), and AG_INF + P1 does not overflow
+constexpr int AG_LINES = MV_THREADS / 64;   // scanlines (wavefronts) per workgroup
+constexpr int AG_AHEAD = 4;              // pixels of a scanline whose costs are requested before they are needed
+constexpr int SEL_LANES = 16;            // lanes per pixel of the select kernel
+
+struct AggArgs {
+  int h, w, planes, p1, p2, n_dirs;
+  int dy[8], dx[8];
+  int first[9];                          // first[i] .. first[i + 1] - 1: the scanlines of the call's i-th direction
+};
+
+// lane l's value of lane (l - 1) mod 64 / (l + 1) mod 64: one DPP move over the whole wave (wave_ror:1 = 0x13C, wave_rol:1 = 0x134)
+__device__ __forceinline__ int from_lane_below(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x13C, 0xF, 0xF, false); }
+__device__ __forceinline__ int from_lane_above(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x134, 0xF, 0xF, false); }
+
+// the minimum over the wave's 64 lanes as a scalar: xor 1, xor 2 inside a quad, mirror inside 8, mirror inside 16, then the four rows
+__device__ __forceinline__ int wave_min(int v) {
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));    // quad_perm [1, 0, 3, 2]
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));    // quad_perm [2, 3, 0, 1]
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));   // row_half_mirror
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));   // row_mirror
+  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+             min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+
+// NPL: planes per lane; the host picks the smallest with 64 * NPL >= D
+template <int NPL>
+__global__ void __launch_bounds__(MV_THREADS) aggregate_kernel(const uint16_t* __restrict__ volume, uint32_t* __restrict__ S, const AggArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int line = __builtin_amdgcn_readfirstlane((int)blockIdx.x * AG_LINES + (int)(threadIdx.x >> 6));
+  if (line >= a.first[8]) return;   // (first[8] = the call's scanlines) whole waves leave: every DPP move below sees 64 active lanes
+  int dy = a.dy[0], dx = a.dx[0], base = 0;
+#pragma unroll
+  for (int i = 1; i < 8; ++i)
+    if (i < a.n_dirs && line >= a.first[i]) dy = a.dy[i], dx = a.dx[i], base = a.first[i];
+  // the scanline's first pixel: the pixels whose predecessor is outside the frame, the edge dy enters through first, then dx's edge
+  const int i = line - base, h = a.h, w = a.w, D = a.planes, P1 = a.p1, P2 = a.p2;
+  int x, y;
+  if (dy != 0 && i < w) {
+    x = i, y = dy > 0 ? 0 : h - 1;
+  } else {
+    const int j = i - (dy != 0 ? w : 0);
+    y = dy == 0 ? j : (dy > 0 ? j + 1 : h - 2 - j);
+    x = dx > 0 ? 0 : w - 1;
+  }
+  auto inside = [&](int px, int py) { return px >= 0 && px < w && py >= 0 && py < h; };   // uniform over the wave
+  auto load = [&](int (&dst)[NPL], int px, int py) {
+    const int64_t at = ((int64_t)min(max(py, 0), h - 1) * w + min(max(px, 0), w - 1)) * D;   // past the scanline's end: a pixel nobody uses
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+      const int k = j * 64 + lane;
+      dst[j] = volume[at + min(k, D - 1)];   // raw, and read by every lane: whatever uses the value next to the read waits for it there
+    }
+  };
+  // The raw costs of the next AG_AHEAD pixels of the scanline are in flight or in registers. For a read to stay in flight it must
+  // not sit under a branch (so every lane reads, at clamped plane and pixel) and its value must first be touched in the step that
+  // consumes it: otherwise the wait for it is placed right behind the read. The waits then sit once per unrolled round of AG_AHEAD steps.
+  int ahead[AG_AHEAD][NPL], L[NPL];
+#pragma unroll
+  for (int s = 0; s < AG_AHEAD; ++s)
+    load(ahead[s], x + s * dx, y + s * dy);
+  int m = 0;
+  bool first = true;
+  while (true) {
+#pragma unroll
+    for (int s = 0; s < AG_AHEAD; ++s) {                      // constant indices into `ahead`
+      const int64_t at = ((int64_t)y * w + x) * D;
+      int c[NPL];
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) c[j] = j * 64 + lane < D ? (ahead[s][j] & (MV_IN_VIEW - 1)) : AG_INF;
+      load(ahead[s], x + AG_AHEAD * dx, y + AG_AHEAD * dy);
+      if (first) {
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) L[j] = c[j];
+        first = false;
+      } else {
+        int below[NPL], above[NPL];
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) below[j] = from_lane_below(L[j]), above[j] = from_lane_above(L[j]);
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) {
+          // plane k - 1 is the lane below, for lane 0 lane 63 of the register before; k + 1 alike. AG_INF: absent
+          const int prev = lane == 0 ? (j > 0 ? below[j > 0 ? j - 1 : 0] : AG_INF) : below[j];
+          const int next = lane == 63 ? (j < NPL - 1 ? above[j < NPL - 1 ? j + 1 : 0] : AG_INF) : above[j];
+          const int best = min(min(L[j], min(prev, next) + P1), m + P2);
+          c[j] = c[j] < AG_INF ? c[j] + (best - m) : AG_INF;
+        }
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) L[j] = c[j];
+      }
+      int lowest = L[0];
+#pragma unroll
+      for (int j = 1; j < NPL; ++j) lowest = min(lowest, L[j]);
+      m = wave_min(lowest);
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) {
+        const int k = j * 64 + lane;
+        if (k < D) atomicAdd(&S[at + k], (uint32_t)L[j]);      // the result is not read: an atomic without return
+      }
+      x += dx, y += dy;
+      if (!inside(x, y)) return;
+    }
+  }
+}
+
+struct SelectArgs {
+  int h, w, planes, uniqueness;
+  int64_t offset;
+  float inv_far, step;
+};
+
+// X = S, or C of the volume where S is null. 16 lanes share a pixel; a workgroup has 16 pixels.
+__global__ void __launch_bounds__(MV_THREADS) select_kernel(const uint16_t* __restrict__ volume, const uint32_t* __restrict__ S, const SelectArgs a,
+                                                            float* __restrict__ out_depth, int32_t* __restrict__ out_cost,
+                                                            int32_t* __restrict__ out_plane) {
+  const int sub = threadIdx.x & (SEL_LANES - 1), D = a.planes;
+  const int64_t pixel = (int64_t)blockIdx.x * (MV_THREADS / SEL_LANES) + (threadIdx.x / SEL_LANES);
+  if (pixel >= (int64_t)a.h * a.w) return;                    // all 16 lanes of a pixel leave together
+  const int64_t at = pixel * D;
+  auto X = [&](int k) { return S ? (int)S[at + k] : (int)(volume[at + k] & (MV_IN_VIEW - 1)); };
+  int key = INT32_MAX;                                        // X * 1024 + k: X <= 8 * 65534 < 2^19, k < 2^10; its minimum is the first minimum
+  for (int k = sub; k < D; k += SEL_LANES) key = min(key, X(k) * 1024 + k);
+#pragma unroll
+  for (int d = SEL_LANES / 2; d >= 1; d >>= 1) key = min(key, __shfl_xor(key, d, SEL_LANES));
+  const int ks = key & 1023, best = key >> 10;
+  int c2 = INT32_MAX;                                         // INT32_MAX: no plane outside the neighbourhood
+  for (int k = sub; k < D; k += SEL_LANES)
+    if (abs(k - ks) > 1) c2 = min(c2, X(k));
+#pragma unroll
+  for (int d = SEL_LANES / 2; d >= 1; d >>= 1) c2 = min(c2, __shfl_xor(c2, d, SEL_LANES));
+  if (sub != 0) return;
+  const bool unique = c2 == INT32_MAX || (c2 > 0 && 100 * best <= (100 - a.uniqueness) * c2);
+  float delta = 0.0f;
+  if (ks > 0 && ks < D - 1) {
+    const int before = X(ks - 1), after = X(ks + 1);
+    const int den = before - 2 * best + after;
+    if (den > 0) delta = (float)(before - after) / (float)(2 * den);
+  }
+  float depth = 1.0f / (a.inv_far + ((float)ks + delta) * a.step);
+  const bool in_view = (volume[at + ks] & MV_IN_VIEW) != 0;
+  if (!in_view || !unique || (D > 2 && (ks == 0 || ks == D - 1))) depth = 0.0f;
+  const int64_t out = a.offset + pixel;
+  out_depth[out] = depth;
+  if (out_cost) out_cost[out] = best;
+  if (out_plane) out_plane[out] = ks;
 }
 
 bool finite_all(const float* p, int n) {
@@ -306,10 +476,11 @@ extern "C" int acez_mvs_relative(const acez_mvs_frame* ref, const acez_mvs_frame
   return ACEZ_OK;
 }
 
-extern "C" int acez_mvs_sweep(const uint8_t* d_filtered, int64_t n_pixels, const acez_mvs_frame* h_frames, int n_frames, int ref,
-                              const int32_t* h_sources, int n_sources, float z_near, float z_far, int planes, int radius, int truncation,
-                              int keep, int uniqueness, float* d_out_depth, int32_t* d_out_cost, int32_t* d_out_plane, void* stream) {
-  ACEZ_REQUIRE(d_filtered && h_frames && h_sources && d_out_depth, "null pointer");
+// the argument checks and the launch arguments the sweep and the volume share
+static int sweep_args(const uint8_t* d_filtered, int64_t n_pixels, const acez_mvs_frame* h_frames, int n_frames, int ref,
+                      const int32_t* h_sources, int n_sources, float z_near, float z_far, int planes, int radius, int truncation, int keep,
+                      int uniqueness, const void* d_out, SweepArgs& a) {
+  ACEZ_REQUIRE(d_filtered && h_frames && h_sources && d_out, "null pointer");
   MV_REQUIRE_VIEWS();
   ACEZ_REQUIRE(isfinite(z_near) && isfinite(z_far) && z_near > 0.0f && z_near < z_far, "the depth range needs 0 < near < far");
   ACEZ_REQUIRE(planes >= 2 && planes <= 1024, "plane count out of range (2 .. 1024)");
@@ -317,7 +488,6 @@ extern "C" int acez_mvs_sweep(const uint8_t* d_filtered, int64_t n_pixels, const
   ACEZ_REQUIRE(truncation >= 1 && truncation <= 255, "cost truncation out of range (1 .. 255)");
   ACEZ_REQUIRE(keep >= 1 && keep <= n_sources, "keep out of range (1 .. sources)");
   ACEZ_REQUIRE(uniqueness >= 0 && uniqueness <= 100, "uniqueness percentage out of range (0 .. 100)");
-  SweepArgs a;
   const acez_mvs_frame& r = h_frames[ref];
   for (int s = 0; s < ACEZ_MVS_MAX_SOURCES; ++s) a.src[s] = view_of(r, h_frames[h_sources[s < n_sources ? s : 0]]);
   a.focal = r.focal, a.ppx = r.ppx, a.ppy = r.ppy, a.h = r.h, a.w = r.w, a.offset = r.offset;
@@ -325,9 +495,20 @@ extern "C" int acez_mvs_sweep(const uint8_t* d_filtered, int64_t n_pixels, const
   a.inv_far = 1.0f / z_far;
   a.step = (inv_near - a.inv_far) / (float)(planes - 1);
   a.planes = planes, a.radius = radius, a.truncation = truncation, a.keep = keep, a.uniqueness = uniqueness, a.n_sources = n_sources;
+  return ACEZ_OK;
+}
+
+extern "C" int acez_mvs_sweep(const uint8_t* d_filtered, int64_t n_pixels, const acez_mvs_frame* h_frames, int n_frames, int ref,
+                              const int32_t* h_sources, int n_sources, float z_near, float z_far, int planes, int radius, int truncation,
+                              int keep, int uniqueness, float* d_out_depth, int32_t* d_out_cost, int32_t* d_out_plane, void* stream) {
+  SweepArgs a;
+  if (int rc = sweep_args(d_filtered, n_pixels, h_frames, n_frames, ref, h_sources, n_sources, z_near, z_far, planes, radius, truncation, keep,
+                          uniqueness, d_out_depth, a))
+    return rc;
   if (int rc = acez::require_device("the plane sweep runs on a gfx950 GPU")) return rc;
-  const dim3 grid((r.w + MV_TILE - 1) / MV_TILE, (r.h + MV_TILE - 1) / MV_TILE);
-  hipLaunchKernelGGL(sweep_kernel, grid, dim3(MV_THREADS), 0, (hipStream_t)stream, d_filtered, a, d_out_depth, d_out_cost, d_out_plane);
+  const dim3 grid((a.w + MV_TILE - 1) / MV_TILE, (a.h + MV_TILE - 1) / MV_TILE);
+  hipLaunchKernelGGL(sweep_kernel<false>, grid, dim3(MV_THREADS), 0, (hipStream_t)stream, d_filtered, a, d_out_depth, d_out_cost, d_out_plane,
+                     (uint16_t*)nullptr);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
 }
@@ -350,6 +531,82 @@ extern "C" int acez_mvs_check(const float* d_depth, int64_t n_pixels, const acez
   if (int rc = acez::require_device("the consistency check runs on a gfx950 GPU")) return rc;
   const dim3 grid((r.w + 63) / 64, (r.h + 3) / 4);
   hipLaunchKernelGGL(check_kernel, grid, dim3(MV_THREADS), 0, (hipStream_t)stream, d_depth, a, d_out);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ section M
+extern "C" int acez_mvs_volume(const uint8_t* d_filtered, int64_t n_pixels, const acez_mvs_frame* h_frames, int n_frames, int ref,
+                               const int32_t* h_sources, int n_sources, float z_near, float z_far, int planes, int radius, int truncation,
+                               int keep, uint16_t* d_volume, int64_t n_volume, void* stream) {
+  SweepArgs a;
+  if (int rc = sweep_args(d_filtered, n_pixels, h_frames, n_frames, ref, h_sources, n_sources, z_near, z_far, planes, radius, truncation, keep,
+                          0, d_volume, a))
+    return rc;
+  ACEZ_REQUIRE(keep * (2 * radius + 1) * (2 * radius + 1) * truncation <= 32767, "keep * (2 * radius + 1)^2 * truncation exceeds 32767: the costs do not fit the volume's 15 bits");
+  ACEZ_REQUIRE(n_volume >= 0 && (int64_t)a.h * a.w * planes <= n_volume, "volume smaller than h * w * planes elements");
+  if (int rc = acez::require_device("the cost volume runs on a gfx950 GPU")) return rc;
+  const dim3 grid((a.w + MV_TILE - 1) / MV_TILE, (a.h + MV_TILE - 1) / MV_TILE);
+  hipLaunchKernelGGL(sweep_kernel<true>, grid, dim3(MV_THREADS), 0, (hipStream_t)stream, d_filtered, a, (float*)nullptr, (int32_t*)nullptr,
+                     (int32_t*)nullptr, d_volume);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}
+
+extern "C" int acez_mvs_aggregate(const uint16_t* d_volume, uint32_t* d_s, int64_t n_volume, int h, int w, int planes, int paths, int direction,
+                                  int p1, int p2, void* stream) {
+  static const int DY[8] = {0, 0, 1, -1, 1, 1, -1, -1}, DX[8] = {1, -1, 0, 0, 1, -1, 1, -1};
+  ACEZ_REQUIRE(d_volume && d_s, "null pointer");
+  ACEZ_REQUIRE(h >= 1 && w >= 1 && h <= MV_MAX_SIDE && w <= MV_MAX_SIDE, "frame size out of range (1 .. 32768 px per side)");
+  ACEZ_REQUIRE(planes >= 2 && planes <= 1024, "plane count out of range (2 .. 1024)");
+  ACEZ_REQUIRE(paths == 4 || paths == 8, "paths must be 4 or 8");
+  ACEZ_REQUIRE(direction >= 0 && direction <= paths, "direction out of range (0 = all, 1 .. paths)");
+  ACEZ_REQUIRE(p1 >= 1 && p1 <= p2 && p2 <= 32767, "penalties need 1 <= P1 <= P2 <= 32767");
+  ACEZ_REQUIRE(n_volume >= 0 && (int64_t)h * w * planes <= n_volume, "volume smaller than h * w * planes elements");
+  AggArgs a;
+  a.h = h, a.w = w, a.planes = planes, a.p1 = p1, a.p2 = p2;
+  a.n_dirs = direction ? 1 : paths;
+  a.first[0] = 0;
+  for (int i = 0; i < 8; ++i) {
+    const int d = direction ? direction - 1 : (i < paths ? i : 0);
+    a.dy[i] = DY[d], a.dx[i] = DX[d];
+    const int lines = (DY[d] ? w : 0) + (DX[d] ? h : 0) - (DY[d] && DX[d] ? 1 : 0);   // <= 65535
+    a.first[i + 1] = a.first[i] + (i < a.n_dirs ? lines : 0);
+  }
+  if (int rc = acez::require_device("the cost aggregation runs on a gfx950 GPU")) return rc;
+  const dim3 grid((a.first[8] + AG_LINES - 1) / AG_LINES), block(MV_THREADS);
+  hipStream_t s = (hipStream_t)stream;
+  if (planes <= 64) hipLaunchKernelGGL(aggregate_kernel<1>, grid, block, 0, s, d_volume, d_s, a);
+  else if (planes <= 128) hipLaunchKernelGGL(aggregate_kernel<2>, grid, block, 0, s, d_volume, d_s, a);
+  else if (planes <= 256) hipLaunchKernelGGL(aggregate_kernel<4>, grid, block, 0, s, d_volume, d_s, a);
+  else if (planes <= 512) hipLaunchKernelGGL(aggregate_kernel<8>, grid, block, 0, s, d_volume, d_s, a);
+  else hipLaunchKernelGGL(aggregate_kernel<16>, grid, block, 0, s, d_volume, d_s, a);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}
+
+extern "C" int acez_mvs_select(const uint16_t* d_volume, const uint32_t* d_s, int64_t n_volume, int64_t n_pixels, const acez_mvs_frame* h_frames,
+                               int n_frames, int ref, float z_near, float z_far, int planes, int uniqueness, float* d_out_depth,
+                               int32_t* d_out_cost, int32_t* d_out_plane, void* stream) {
+  ACEZ_REQUIRE(d_volume && h_frames && d_out_depth, "null pointer");
+  ACEZ_REQUIRE(n_pixels >= 0, "negative buffer length");
+  ACEZ_REQUIRE(n_frames >= 1, "frame count must be at least 1");
+  ACEZ_REQUIRE(ref >= 0 && ref < n_frames, "reference index outside the frame table");
+  MV_REQUIRE_ROW(h_frames[ref], n_pixels);
+  ACEZ_REQUIRE(isfinite(z_near) && isfinite(z_far) && z_near > 0.0f && z_near < z_far, "the depth range needs 0 < near < far");
+  ACEZ_REQUIRE(planes >= 2 && planes <= 1024, "plane count out of range (2 .. 1024)");
+  ACEZ_REQUIRE(uniqueness >= 0 && uniqueness <= 100, "uniqueness percentage out of range (0 .. 100)");
+  const acez_mvs_frame& r = h_frames[ref];
+  ACEZ_REQUIRE(n_volume >= 0 && (int64_t)r.h * r.w * planes <= n_volume, "volume smaller than h * w * planes elements");
+  SelectArgs a;
+  a.h = r.h, a.w = r.w, a.planes = planes, a.uniqueness = uniqueness, a.offset = r.offset;
+  const float inv_near = 1.0f / z_near;
+  a.inv_far = 1.0f / z_far;
+  a.step = (inv_near - a.inv_far) / (float)(planes - 1);
+  if (int rc = acez::require_device("the plane selection runs on a gfx950 GPU")) return rc;
+  const int per_block = MV_THREADS / SEL_LANES;
+  const dim3 grid((unsigned)(((int64_t)r.h * r.w + per_block - 1) / per_block));
+  hipLaunchKernelGGL(select_kernel, grid, dim3(MV_THREADS), 0, (hipStream_t)stream, d_volume, d_s, a, d_out_depth, d_out_cost, d_out_plane);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
 }

@@ -918,6 +918,64 @@ int acez_mvs_check(const float* d_depth, int64_t n_pixels, const acez_mvs_frame*
                    const int32_t* h_sources, int n_sources, float tolerance, int min_consistent, float depth_unit, uint16_t* d_out,
                    void* stream);
 
+/* =====================================================================================================
+ * M. Semi-global aggregation of the plane costs (estimate_depth.py --aggregation sgm)
+ * =====================================================================================================
+ * Section L's sweep takes each pixel's best plane on its own, so a textureless surface, whose costs do not tell the planes apart,
+ * comes out empty. Here the costs C(p, k) of a reference frame are written to memory, smoothed along scanlines with a small penalty
+ * P1 for moving one plane and a larger one P2 for jumping (semi-global matching, Hirschmueller), and the plane is chosen from the
+ * smoothed costs by section L's own rule. Three stateless entry points on one reference frame r of section L's frame table; frames,
+ * conventions, arithmetic, stream and validation are section L's. Everything from C on is integer arithmetic.
+ * tests/sgm_restated.py restates AGGREGATE and SELECT in numpy; VOLUME's reference is tests/mvs_restated.cost_volume.
+ *
+ * Storage. The VOLUME of r is uint16 [h][w][D], element ((y * w + x) * D + k): C(p, k) in bits 0 .. 14, V(p, k) in bit 15. S is
+ * uint32 [h][w][D], the same indexing. Neither carries r.offset: they are scratch of one frame, reused from frame to frame.
+ * n_volume is the number of ELEMENTS the caller has allocated for each of the two; all indices into them are 64-bit.
+ *
+ * VOLUME (acez_mvs_volume). SWEEP's steps 1 - 7, A_s and C(p, k) exactly as written in section L, for every pixel p of r and every
+ * plane k, without the reduction over k. V(p, k) = (the number of sources with p itself IN VIEW at k) >= keep. Writes h * w * D
+ * elements of d_volume and nothing else. C <= keep * (2w + 1)^2 * T must fit 15 bits.
+ *
+ * AGGREGATE (acez_mvs_aggregate). `paths` in {4, 8}, penalties 1 <= P1 <= P2 <= 32767. The directions (dy, dx), in this order:
+ *   1 (0,+1)  2 (0,-1)  3 (+1,0)  4 (-1,0)  5 (+1,+1)  6 (+1,-1)  7 (-1,+1)  8 (-1,-1);          four paths are directions 1 - 4.
+ * For direction r and pixel p = (y, x) with predecessor q = p - r = (y - dy, x - dx):
+ *   q outside the frame:  L_r(p, k) = C(p, k)
+ *   otherwise:            m = min_j L_r(q, j)
+ *                         L_r(p, k) = C(p, k) + min(L_r(q, k), L_r(q, k-1) + P1, L_r(q, k+1) + P1, m + P2) - m
+ *                         (the term with k - 1 < 0 or k + 1 > D - 1 is absent)
+ * so C <= L_r <= C + P2. C is bits 0 .. 14 of the volume; bit 15 is ignored. With direction = 0 every element of d_s gains
+ * S(p, k) = the sum of L_r(p, k) over the `paths` directions; with direction = r in 1 .. paths it gains L_r(p, k) alone (the tests
+ * check each direction by itself). d_s is ADDED to, with integer additions whose order is free: the caller zeroes it before the
+ * first call of a frame. S <= paths * (32767 + P2) < 2^19.
+ * Frames with h = 1 or w = 1 are allowed: every diagonal predecessor is then outside.
+ *
+ * SELECT (acez_mvs_select). SWEEP's rule from k* to `depth` verbatim on a cost volume X in place of C, X = S (d_s) or, with d_s
+ * NULL, C itself (no aggregation ran): k* = the first minimum of X(p, .); C2 = the smallest X(p, k) with |k - k*| > 1; UNIQUE iff
+ * there is no such plane or C2 > 0 && 100 * X(k*) <= (100 - q) * C2; delta from X(k* - 1), X(k*), X(k* + 1) as in SWEEP;
+ * depth = 1 / (inv_far + (float(k*) + delta) * step), and 0 if !V(p, k*) (SWEEP's N* < keep), or not UNIQUE, or (D > 2 and k* is 0
+ * or D - 1). Outputs as SWEEP's, at r.offset: d_out_depth float32 [n_pixels], optional d_out_cost int32 = X(k*), d_out_plane = k*.
+ * Every element of d_s that SELECT reads must be <= 8 * 65534 = 524272, which AGGREGATE into a zeroed buffer guarantees; a buffer that
+ * was not zeroed, or that several calls with direction = 0 accumulated into, is outside the definition (the kernel packs X and k into
+ * one 32-bit key). VOLUME followed by SELECT with d_s NULL gives acez_mvs_sweep's three outputs bit for bit.
+ *
+ * Kernel shape (acezero_amd/csrc/mvs_api.hip). VOLUME is the sweep kernel's second instantiation: one plane loop, C and V stored
+ * per plane. AGGREGATE: one wavefront per scanline of a direction, its lanes hold the planes (lane l: l, l + 64, ...), L_r(q, .) in
+ * registers, k - 1 / k + 1 by wave rotates, m by a wave-wide minimum, S by 32-bit integer atomics without return; all scanlines of
+ * all directions of a call are one launch. SELECT: 16 lanes per pixel, two passes over the D values. No communication between
+ * workgroups.
+ *
+ * ACEZ_ERR_INVALID, before anything is launched, for everything section L refuses for the same argument, and: keep * (2w + 1)^2 * T
+ * > 32767 (VOLUME), `paths` not 4 or 8, `direction` outside 0 .. paths, penalties outside 1 <= P1 <= P2 <= 32767, h or w outside
+ * 1 .. 32768, a null d_volume or (AGGREGATE) d_s, n_volume < h * w * D. */
+int acez_mvs_volume(const uint8_t* d_filtered, int64_t n_pixels, const acez_mvs_frame* h_frames, int n_frames, int ref,
+                    const int32_t* h_sources, int n_sources, float z_near, float z_far, int planes, int radius, int truncation, int keep,
+                    uint16_t* d_volume, int64_t n_volume, void* stream);
+int acez_mvs_aggregate(const uint16_t* d_volume, uint32_t* d_s, int64_t n_volume, int h, int w, int planes, int paths, int direction, int p1,
+                       int p2, void* stream);
+int acez_mvs_select(const uint16_t* d_volume, const uint32_t* d_s, int64_t n_volume, int64_t n_pixels, const acez_mvs_frame* h_frames,
+                    int n_frames, int ref, float z_near, float z_far, int planes, int uniqueness, float* d_out_depth, int32_t* d_out_cost,
+                    int32_t* d_out_plane, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,6 +2,8 @@
 section 4k). HIP events around each call, median of the repetitions; the frames are on the device before the timed calls.
 
     python tools/mvs_timing.py [--frames 48] [--planes 128] [--sources 4] [--window 2] [--reps 10] [--no_cli] [--out profiles/mvs_timing.json]
+    python tools/mvs_timing.py --sgm           (adds the legs of --aggregation sgm: volume, aggregate with 4 and 8 paths, select, on one
+                                                frame and over all frames on four streams; writes profiles/mvs_timing_sgm.json)
 
 The scene is the wall and box of tests/mvs_cases.py at 240 x 320 px, the cameras on a line. Prints one JSON line and writes it to --out."""
 import argparse
@@ -30,8 +32,11 @@ def main():
     ap.add_argument("--window", type=int, default=2)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--no_cli", action="store_true")
-    ap.add_argument("--out", type=str, default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "mvs_timing.json"))
+    ap.add_argument("--sgm", action="store_true")
+    ap.add_argument("--out", type=str, default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "mvs_timing_sgm.json" if a.sgm else "mvs_timing.json")
     n, h, w, focal = a.frames, 240, 320, MC.FOCAL * 2.5
     c2w = MC.cameras(n, spacing=0.05)
     images = np.stack([MC.render(T, h, w, focal)[0] for T in c2w])
@@ -58,6 +63,27 @@ def main():
     out["sweep_samples_per_s"] = n * h * w * a.planes * a.sources / (out["sweep_ms"] * 1e-3)     # pixel x plane x source
     out["check_ms"] = _time(check_all, a.reps)
     out["pixels_with_depth_nearest_sources"] = float((fs.out != 0).float().mean().item())     # (the command line picks wider baselines)
+    if a.sgm:
+        mid = n // 2
+        keep = -(-len(sources[mid]) // 2)
+        p1, p2 = mvs.sgm_penalties(keep, a.window)
+        sc = mvs.SgmScratch(h * w * a.planes, fs.device)
+        out["sgm_p1_p2"] = [p1, p2]
+        out["sgm_scratch_bytes_per_stream"] = mvs.SgmScratch.nbytes(sc.elements)
+        out["volume_one_frame_ms"] = _time(lambda: fs.volume(mid, sources[mid], MC.Z_NEAR, MC.Z_FAR, sc, a.planes, a.window), a.reps)
+        out["zero_s_one_frame_ms"] = _time(lambda: sc.s.zero_(), a.reps)
+        for paths in (4, 8):                                      # (includes zeroing S)
+            out[f"aggregate_{paths}_paths_one_frame_ms"] = _time(lambda: fs.aggregate(mid, sc, a.planes, paths, p1, p2), a.reps)
+        out["select_on_s_one_frame_ms"] = _time(lambda: fs.select(mid, MC.Z_NEAR, MC.Z_FAR, sc, a.planes), a.reps)
+        out["select_on_c_one_frame_ms"] = _time(lambda: fs.select(mid, MC.Z_NEAR, MC.Z_FAR, sc, a.planes, aggregated=False), a.reps)
+        for paths in (4, 8):
+            run = lambda: fs.sweep_frames(jobs, a.planes, a.window, aggregation="sgm", sgm_paths=paths)
+            out[f"sgm_{paths}_paths_ms"] = _time(run, a.reps)
+            out[f"sgm_{paths}_paths_ms_per_frame"] = out[f"sgm_{paths}_paths_ms"] / n
+            check_all()
+            torch.cuda.synchronize()
+            out[f"pixels_with_depth_sgm_{paths}_paths"] = float((fs.out != 0).float().mean().item())
+        out["sgm_scratch_bytes"] = fs.sgm_scratch_bytes
     if not a.no_cli:
         with tempfile.TemporaryDirectory() as tmp:
             from PIL import Image
@@ -73,11 +99,11 @@ def main():
             t0 = time.perf_counter()
             cli.estimate_depth_main([os.path.join(tmp, "poses.txt"), os.path.join(tmp, "frame_*.png"), os.path.join(tmp, "depth"), "--image_resolution",
                                      str(h), "--depth_range", str(MC.Z_NEAR), str(MC.Z_FAR), "--planes", str(a.planes), "--sources", str(a.sources),
-                                     "--window", str(a.window)])
+                                     "--window", str(a.window)] + (["--aggregation", "sgm"] if a.sgm else []))
             out["cli_total_s"] = time.perf_counter() - t0
             m = re.search(r"Decode ([\d.]+) s, upload \+ kernels \+ download ([\d.]+) s, write ([\d.]+) s", "\n".join(lines))
             out["cli_decode_s"], out["cli_device_s"], out["cli_write_s"] = (float(g) for g in m.groups())
-            out["cli_log"] = [ln for ln in lines if ln.startswith("Estimated") or ln.startswith("Pixels")]
+            out["cli_log"] = [ln for ln in lines if ln.startswith(("Estimated", "Pixels", "Aggregation"))]
     line = json.dumps({k: (float(f"{x:.4g}") if isinstance(x, float) else x) for k, x in out.items()})
     print(line)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
