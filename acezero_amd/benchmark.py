@@ -22,6 +22,8 @@ from pathlib import Path
 
 import numpy as np
 
+from .formats import pose_matrix, read_pose_file
+
 _logger = logging.getLogger("acezero_amd.benchmark")
 
 TRAIN_CONFIDENCE = 1000        # train frames below it are left out of the fit
@@ -34,24 +36,15 @@ GL_FROM_CV = np.diag([1.0, -1.0, -1.0, 1.0])
 
 # ------------------------------------------------------------------------------------------------------ pose conversion
 def parse_pose_file(path):
-    """An ACE0 pose file: [(file, [qw, qx, qy, qz], [tx, ty, tz], focal, confidence)], one per line of ten fields."""
-    out = []
-    with open(path) as f:
-        for line in f.readlines():
-            tok = line.strip().split()
-            assert len(tok) == 10, f"Unexpected line length {len(tok)}; expected 10"
-            out.append((tok[0], [float(v) for v in tok[1:5]], [float(v) for v in tok[5:8]], float(tok[8]), int(tok[9])))
-    return out
+    """An ACE0 pose file: [(file, world -> camera 4 x 4 (OpenCV), focal, confidence)], one per line of ten fields. The confidence is
+    an integer literal, as transforms.json keeps it: anything else (inf included) is a ValueError."""
+    return [(e.file, e.w2c, e.focal, int(e.confidence_text)) for e in read_pose_file(path)]
 
 
 def transform_matrix_from_pose(q_wxyz, t):
     """World -> camera (OpenCV: x right, y down, z forward) quaternion + translation -> camera -> world 4 x 4 in the OpenGL / Blender
     convention (x right, y up, z back) nerfstudio reads."""
-    from .cli import quat_wxyz_to_matrix
-    w2c = np.eye(4)
-    w2c[:3, :3] = quat_wxyz_to_matrix(q_wxyz)
-    w2c[:3, 3] = t
-    return np.linalg.inv(GL_FROM_CV @ w2c)
+    return np.linalg.inv(GL_FROM_CV @ pose_matrix(q_wxyz, t))
 
 
 def pose_from_transform_matrix(transform_matrix):
@@ -72,8 +65,8 @@ def build_frames(pose_file, images_glob_pattern):
     images = [Path(p) for p in glob.glob(images_glob_pattern)]
     assert len(images) > 0, "Expected at least one frame"
     by_file = {}
-    for file, q, t, focal, conf in parse_pose_file(pose_file):
-        by_file[file] = {"file_path": file, "transform_matrix": transform_matrix_from_pose(q, t).tolist(), "confidence_score": conf,
+    for file, w2c, focal, conf in parse_pose_file(pose_file):
+        by_file[file] = {"file_path": file, "transform_matrix": np.linalg.inv(GL_FROM_CV @ w2c).tolist(), "confidence_score": conf,
                          "fl_x": focal, "fl_y": focal}
     sizes = [_image_size(p) for p in images]
     assert len(set(sizes)) == 1, f"Expected all resolutions equal, but got {sorted(set(sizes))} (height, width)"

@@ -21,6 +21,7 @@ from pathlib import Path
 import numpy as np
 
 from . import DEFAULT_DTYPE
+from .formats import match_poses, read_ace_pose_file, read_depth_png, read_ply_vertices, write_depth_png, write_ply, write_pose_line
 
 _logger = logging.getLogger("acezero_amd")
 
@@ -289,15 +290,7 @@ def _default_encoder_path(path):
     return Path(__file__).resolve().parent.parent / "ace_encoder_pretrained.pt" if str(path) == "<path>" else Path(path)
 
 
-# ------------------------------------------------------------------------------------------------------- file formats
-def write_pose_line(f, rgb_file, pose_w2c, confidence, focal_length):
-    """dataset_io.py:159-186: `file qw qx qy qz tx ty tz focal confidence`, world->cam."""
-    from scipy.spatial.transform import Rotation
-    q = Rotation.from_matrix(np.asarray(pose_w2c, np.float64)[:3, :3]).as_quat()
-    t = np.asarray(pose_w2c)[:3, 3]
-    f.write(f"{rgb_file} {q[3]} {q[0]} {q[1]} {q[2]} {t[0]} {t[1]} {t[2]} {focal_length} {confidence}\n")
-
-
+# ------------------------------------------------------------------------------------------------------- feature buffer
 def save_feature_buffer(path, prob, image_files=None, with_depth_targets=False):
     """Write a training buffer (dict in the layout of acezero_amd.synth.make_training_problem) as .npz."""
     n_img = prob["image_pose_inv"].shape[0]
@@ -464,29 +457,6 @@ def _finalize_mapping_visualization(opt, vis, tr, buf, n, max_points=1_000_000):
     xyz = xyz[keep].copy()
     xyz[:, 1:] *= -1
     vis.finalize_mapping(xyz, clr, poses, vis.poses_w2c_orig)
-
-
-def quat_wxyz_to_matrix(q_wxyz):
-    """Rotation matrix of a pose file's (qw, qx, qy, qz) (dataset_io.py:130-134, eval_poses.py:77)."""
-    from scipy.spatial.transform import Rotation
-    q = list(q_wxyz)
-    return Rotation.from_quat(q[1:] + [q[0]]).as_matrix()
-
-
-def read_ace_pose_file(path, confidence_threshold):
-    """dataset_io.load_dataset_ace (:96-156): (files, cam->world 4x4 float64 [k,4,4], focal lengths) of the entries whose confidence
-    is not below the threshold."""
-    files, poses, focals = [], [], []
-    for line in open(path).read().splitlines():
-        tok = line.split()
-        assert len(tok) == 10, f"Expected 10 tokens per line in pose file, got {len(tok)}"
-        if float(tok[-1]) < confidence_threshold:
-            continue
-        T = np.eye(4)
-        T[:3, :3] = quat_wxyz_to_matrix([float(t) for t in tok[1:5]])
-        T[:3, 3] = [float(t) for t in tok[5:8]]
-        files.append(tok[0]); poses.append(np.linalg.inv(T)); focals.append(float(tok[-2]))
-    return files, np.stack(poses) if poses else np.zeros((0, 4, 4)), focals
 
 
 def _session_options(opt, **extra):
@@ -938,7 +908,7 @@ def ace_zero_main(argv=None):
         _logger.info(f"{h['id']}: registered {h['registration_rate'] * 100:.1f}% of the images")
     write_pose_file(opt.results_folder / "poses_final.txt", files, res["poses"], res["confidence"], orig(res["focal"]))
     if opt.export_point_cloud:
-        from .pointcloud import write_point_cloud
+        from .pointcloud import point_colours, write_point_cloud
         xyz, src, sel = res["point_cloud"]
         write_point_cloud(opt.results_folder / "pc_final.ply", xyz, point_colours(ses, rgb, src, sel))
     if opt.render_visualization:
@@ -973,37 +943,12 @@ def _render_video(opt, render_dir):
 
 
 # ------------------------------------------------------------------------------------------------ export_point_cloud
-def source_colours(rgb_nhw3, frame_of_point, pixel_of_point, map_w):
-    """Colour of every kept map pixel: the image value at its centre (nearest-neighbour sub-sampling with offset 4, stride 8,
-    ace_vis_util.py:566-570), as 0..255 floats. rgb_nhw3: [n,H,W,3], or a list of n [H_i,W_i,3] frames with map_w per point."""
-    y, x = np.divmod(pixel_of_point.astype(np.int64), map_w)
-    if not isinstance(rgb_nhw3, list):
-        yy = np.minimum(y * 8 + 4, rgb_nhw3.shape[1] - 1)
-        xx = np.minimum(x * 8 + 4, rgb_nhw3.shape[2] - 1)
-        return rgb_nhw3[frame_of_point, yy, xx].astype(np.float64)
-    out = np.zeros((len(frame_of_point), 3), np.float64)
-    for fr in np.unique(frame_of_point):
-        at = np.flatnonzero(frame_of_point == fr)
-        img = rgb_nhw3[int(fr)]
-        out[at] = img[np.minimum(y[at] * 8 + 4, img.shape[0] - 1), np.minimum(x[at] * 8 + 4, img.shape[1] - 1)]
-    return out
-
-
-def point_colours(ses, rgb, src, sel):
-    """source_colours of ReconstructionSession.point_cloud's points."""
-    if len(ses.classes) == 1:
-        f, p = np.divmod(src.astype(np.int64), ses.hw)
-        return source_colours(rgb, sel[f], p, ses.ow)
-    frame, p, ow = ses.source_pixels(src, sel)
-    return source_colours(rgb, frame, p, ow)
-
-
 def export_point_cloud_main(argv=None):
     """export_point_cloud.py: from a visualisation buffer (host only) or from network + pose file (encoder -> head -> filter on
     the device)."""
     import pickle
     import torch
-    from .pointcloud import write_point_cloud
+    from .pointcloud import point_colours, write_point_cloud
     parser = with_ingest_flag(export_point_cloud_parser())
     opt = parser.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
@@ -1179,14 +1124,6 @@ def fuse_depth_parser():
     return p
 
 
-def _read_depth_u16(path):
-    from PIL import Image
-    d = np.asarray(Image.open(path))
-    if d.ndim != 2:
-        raise SystemExit(f"{path}: a depth map must have one channel")
-    return np.ascontiguousarray(np.clip(d, 0, 65535).astype(np.uint16))
-
-
 def fuse_depth_main(argv=None):
     """fuse_depth.py: depth maps at their own resolution + pose file -> TSDF volume (HIP) -> surface-net mesh (HIP) -> .ply."""
     import glob
@@ -1207,18 +1144,13 @@ def fuse_depth_main(argv=None):
     names, c2w_all, focals_all = read_ace_pose_file(opt.pose_file, opt.confidence_threshold)
     if not names:
         raise SystemExit("no pose above the confidence threshold")
-    by_name = {n: k for k, n in enumerate(names)}
-    by_base = {os.path.basename(n): k for k, n in enumerate(names)}
-    pairs = []                                                  # (rgb file, depth file, row of the pose file), in the folder's order
-    for rgb_file, depth_file in zip(rgb_files, depth_files):
-        k = by_name.get(rgb_file, by_base.get(os.path.basename(rgb_file)))
-        if k is not None:
-            pairs.append((rgb_file, depth_file, k))
+    # (rgb file, depth file, row of the pose file), in the folder's order
+    pairs = [(r, d, k) for r, d, k in zip(rgb_files, depth_files, match_poses(names, rgb_files)) if k is not None]
     if not pairs:
         raise SystemExit("no image of the glob has a pose above the confidence threshold in the pose file")
     t0 = time.perf_counter()
     with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
-        depth = list(pool.map(_read_depth_u16, [p[1] for p in pairs]))
+        depth = list(pool.map(read_depth_png, [p[1] for p in pairs]))
         image_h = [Image.open(p[0]).size[1] for p in pairs]
         c2w = np.stack([c2w_all[p[2]] for p in pairs])
         # a pose file's focal is in pixels of the original image; the depth map is that image at another scale
@@ -1245,7 +1177,7 @@ def fuse_depth_main(argv=None):
     t0 = time.perf_counter()
     if rgb is None:
         colours[:] = 200
-    fusion.write_mesh_ply(opt.output_file, vertices, colours, faces)
+    write_ply(opt.output_file, vertices, colours, faces)
     t_write = time.perf_counter() - t0
     log.info(f"Fused {len(pairs)} of {len(rgb_files)} frames into a volume of {dims[0]} x {dims[1]} x {dims[2]} voxels "
              f"({opt.voxel_size} m, truncation {truncation} m).")
@@ -1295,7 +1227,6 @@ def estimate_depth_main(argv=None):
     """estimate_depth.py: images + pose file (+ point cloud) -> prefilter, plane sweep, consistency check (HIP) -> 16-bit depth PNGs."""
     import glob
     from concurrent.futures import ThreadPoolExecutor
-    from PIL import Image
     from . import mvs
     opt = estimate_depth_parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO)
@@ -1339,14 +1270,12 @@ def estimate_depth_main(argv=None):
     names, c2w_all, focals_all = read_ace_pose_file(opt.pose_file, opt.confidence_threshold)
     if not names:
         raise SystemExit("no pose above the confidence threshold")
-    by_name = {n: k for k, n in enumerate(names)}
-    by_base = {os.path.basename(n): k for k, n in enumerate(names)}
-    pose_row = [by_name.get(f, by_base.get(os.path.basename(f))) for f in rgb_files]
+    pose_row = match_poses(names, rgb_files)
     if all(k is None for k in pose_row):
         raise SystemExit("no image of the glob has a pose above the confidence threshold in the pose file")
     cloud = None
     if opt.point_cloud is not None:
-        cloud = mvs.read_point_cloud_ply(opt.point_cloud).astype(np.float64)
+        cloud = read_ply_vertices(opt.point_cloud).astype(np.float64)
         if opt.cloud_convention == "opengl":
             cloud[:, 1], cloud[:, 2] = -cloud[:, 1], -cloud[:, 2]
     import torch
@@ -1382,7 +1311,7 @@ def estimate_depth_main(argv=None):
     t0 = time.perf_counter()
     os.makedirs(opt.output_dir, exist_ok=True)
     with ThreadPoolExecutor(max_workers=min(16, len(os.sched_getaffinity(0)))) as pool:
-        list(pool.map(lambda job: Image.fromarray(job[1]).save(os.path.join(opt.output_dir, job[0] + ".png")), zip(stems, maps)))
+        list(pool.map(write_depth_png, [os.path.join(opt.output_dir, s + ".png") for s in stems], maps))
     t_write = time.perf_counter() - t0
     estimated = sum(1 for s in sources if s)
     filled = float(np.mean([float((m > 0).mean()) for m, s in zip(maps, sources) if s])) if estimated else 0.0

@@ -14,6 +14,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _native as N
+from .formats import read_pose_file
 
 # eval_poses_util.py:11-17
 TestEstimate = namedtuple("TestEstimate", ["pose_est", "pose_gt", "focal_length", "confidence", "image_file"])
@@ -120,18 +121,9 @@ def evaluate_poses(poses_est, poses_gt, confidences, *, estimate_alignment=True,
 
 
 def read_pose_file_with_confidence(path):
-    """eval_poses.py:60-88: every line of an ACE pose file -> {file name: (cam->world 4x4 float64, confidence)}; the confidence is
-    the last token (acezero_amd.cli.read_ace_pose_file instead drops low-confidence lines)."""
-    from .cli import quat_wxyz_to_matrix
-    out = {}
-    with open(path) as f:
-        for line in f.readlines():
-            tok = line.split()
-            T = np.eye(4)
-            T[:3, :3] = quat_wxyz_to_matrix([float(t) for t in tok[1:5]])
-            T[:3, 3] = [float(t) for t in tok[5:8]]
-            out[tok[0]] = (np.linalg.inv(T), float(tok[-1]))
-    return out
+    """eval_poses.py:60-88: every line of an ACE pose file -> {file name: (cam->world 4x4 float64, confidence)}; a later line of the
+    same name replaces an earlier one (formats.read_ace_pose_file instead drops low-confidence lines)."""
+    return {e.file: (np.linalg.inv(e.w2c), e.confidence) for e in read_pose_file(path)}
 
 
 def load_gt_pose_files(pattern):

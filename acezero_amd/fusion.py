@@ -4,7 +4,7 @@ section 4j; fuse_depth.py is the command line).
     vol = TSDFVolume(origin, (nx, ny, nz), voxel_size=0.02, truncation=0.08, device="cuda")
     vol.integrate(depth_u16, cam_to_world=poses, focals=f, ppx=cx, ppy=cy, rgb=rgb)
     vertices, colours, faces = vol.extract_mesh(min_weight=2)
-    write_mesh_ply("scene.ply", vertices, colours, faces)
+    formats.write_ply("scene.ply", vertices.cpu(), colours.cpu(), faces.cpu())
 
 The volume lives in HBM; integration and extraction are HIP kernels (acezero_amd/csrc/fusion_api.hip). There is no CPU fallback.
 """
@@ -188,21 +188,3 @@ def bounds_from_frames(depth, cam_to_world, focals, voxel_size, truncation, dept
                          f"--max_voxels {max_voxels}: raise --voxel_size, lower --max_depth or raise --max_voxels")
     return (lo_i * voxel_size).astype(np.float32), dims
 
-
-def write_mesh_ply(path, vertices, colours, faces):
-    """Binary little-endian PLY: the vertex element of pointcloud.write_point_cloud (float x y z, uchar red green blue alpha) and a
-    face element (uchar count, int vertex indices)."""
-    def host(a):
-        return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-    xyz, clr, tri = host(vertices).astype(np.float32).reshape(-1, 3), host(colours).astype(np.uint8).reshape(-1, 3), host(faces).reshape(-1, 3)
-    vrec = np.zeros(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("r", "u1"), ("g", "u1"), ("b", "u1"), ("a", "u1")])
-    vrec["x"], vrec["y"], vrec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
-    vrec["r"], vrec["g"], vrec["b"], vrec["a"] = clr[:, 0], clr[:, 1], clr[:, 2], 255
-    frec = np.zeros(len(tri), dtype=[("n", "u1"), ("v", "<i4", (3,))])
-    frec["n"], frec["v"] = 3, tri
-    with open(str(path), "wb") as fh:
-        fh.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-                  "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n"
-                  "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(xyz), len(tri))).encode())
-        fh.write(vrec.tobytes())
-        fh.write(frec.tobytes())

@@ -99,31 +99,6 @@ def depth_range_from_cloud(points, w2c, focal, ppx, ppy, h, w):
     return float(near / RANGE_MARGIN), float(far * RANGE_MARGIN)
 
 
-def read_point_cloud_ply(path):
-    """float32 [m,3] of a binary little-endian .ply whose vertex element is what pointcloud.write_point_cloud writes (float x y z,
-    uchar red green blue alpha); further elements (a mesh's faces) are ignored."""
-    blob = open(str(path), "rb").read()
-    head, sep, body = blob.partition(b"end_header\n")
-    lines = head.decode("ascii", "replace").splitlines()
-    if not sep or lines[:2] != ["ply", "format binary_little_endian 1.0"]:
-        raise SystemExit(f"{path}: not a binary little-endian .ply")
-    count, props, element = 0, [], None
-    for line in lines:
-        tok = line.split()
-        if tok[:1] == ["element"]:
-            element = tok[1]
-            if element == "vertex":
-                count = int(tok[2])
-        elif tok[:1] == ["property"] and element == "vertex":
-            props.append(tuple(tok[1:]))
-    if props != [("float", "x"), ("float", "y"), ("float", "z"), ("uchar", "red"), ("uchar", "green"), ("uchar", "blue"), ("uchar", "alpha")]:
-        raise SystemExit(f"{path}: expected the vertex layout export_point_cloud.py writes (float x y z, uchar red green blue alpha)")
-    if len(body) < 16 * count:
-        raise SystemExit(f"{path}: truncated")
-    rec = np.frombuffer(body[:16 * count], dtype=[("xyz", "<f4", (3,)), ("rgba", "u1", (4,))])
-    return rec["xyz"].copy()
-
-
 def load_grey_frames(files, image_resolution, workers=12):
     """Decode in a pool of threads (ingest.decode_frames), resize so that the short side is image_resolution and convert to grey,
     both as cli.load_frames does (Pillow bilinear, convert('L')): (list of uint8 [h,w], list of the files' original heights)."""

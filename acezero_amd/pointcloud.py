@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .formats import write_ply
 from .head import _ptr, _stream
 
 PC_POINTS_MIN, PC_POINTS_MAX = 100000, 1000000   # ace_vis_util.py:447-448
@@ -89,13 +90,31 @@ def write_point_cloud(path, pc_xyz, pc_clr):
             for pt in range(xyz.shape[0]):
                 fh.write(f"{xyz[pt, 0]} {xyz[pt, 1]} {xyz[pt, 2]} {clr[pt, 0]:.0f} {clr[pt, 1]:.0f} {clr[pt, 2]:.0f}\n")
     elif path.endswith(".ply"):
-        rec = np.zeros(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("r", "u1"), ("g", "u1"), ("b", "u1"), ("a", "u1")])
-        rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
-        c8 = np.clip(np.rint(clr), 0, 255).astype(np.uint8)
-        rec["r"], rec["g"], rec["b"], rec["a"] = c8[:, 0], c8[:, 1], c8[:, 2], 255
-        with open(path, "wb") as fh:
-            fh.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-                      "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\nend_header\n" % len(xyz)).encode())
-            fh.write(rec.tobytes())
+        write_ply(path, xyz, np.clip(np.rint(clr), 0, 255))
     else:
         raise ValueError("output file format not supported: use .txt or .ply (export_point_cloud.py:124-125)")
+
+
+def source_colours(rgb_nhw3, frame_of_point, pixel_of_point, map_w):
+    """Colour of every kept map pixel: the image value at its centre (nearest-neighbour sub-sampling with offset 4, stride 8,
+    ace_vis_util.py:566-570), as 0..255 floats. rgb_nhw3: [n,H,W,3], or a list of n [H_i,W_i,3] frames with map_w per point."""
+    y, x = np.divmod(pixel_of_point.astype(np.int64), map_w)
+    if not isinstance(rgb_nhw3, list):
+        yy = np.minimum(y * 8 + 4, rgb_nhw3.shape[1] - 1)
+        xx = np.minimum(x * 8 + 4, rgb_nhw3.shape[2] - 1)
+        return rgb_nhw3[frame_of_point, yy, xx].astype(np.float64)
+    out = np.zeros((len(frame_of_point), 3), np.float64)
+    for fr in np.unique(frame_of_point):
+        at = np.flatnonzero(frame_of_point == fr)
+        img = rgb_nhw3[int(fr)]
+        out[at] = img[np.minimum(y[at] * 8 + 4, img.shape[0] - 1), np.minimum(x[at] * 8 + 4, img.shape[1] - 1)]
+    return out
+
+
+def point_colours(ses, rgb, src, sel):
+    """source_colours of ReconstructionSession.point_cloud's points."""
+    if len(ses.classes) == 1:
+        f, p = np.divmod(src.astype(np.int64), ses.hw)
+        return source_colours(rgb, sel[f], p, ses.ow)
+    frame, p, ow = ses.source_pixels(src, sel)
+    return source_colours(rgb, frame, p, ow)

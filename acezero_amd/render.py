@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .formats import read_ace_pose_file, read_pose_file, write_ply
 
 _logger = logging.getLogger("acezero_amd")
 
@@ -718,7 +719,7 @@ def pose_iteration_table(last_pose_file, max_iteration, confidence_threshold=CON
     (iteration 0: the seed's poses_iteration0_seed<k>.txt). Images never registered keep max_iteration."""
     from pathlib import Path
     last = Path(last_pose_file)
-    table = {line.split()[0]: max_iteration for line in open(last).read().splitlines() if line.strip()}
+    table = {e.file: max_iteration for e in read_pose_file(last, strict=False)}
     for it in reversed(range(max_iteration)):
         stem = last.stem.split("_")
         stem[-1] = f"iteration{it}"
@@ -732,10 +733,9 @@ def pose_iteration_table(last_pose_file, max_iteration, confidence_threshold=CON
             path = last.parent / f"{name}.txt"
             if not path.exists():
                 continue
-        for line in open(path).read().splitlines():
-            tok = line.split()
-            if tok and float(tok[-1]) > confidence_threshold:
-                table[tok[0]] = it
+        for e in read_pose_file(path, strict=False):
+            if e.confidence > confidence_threshold:
+                table[e.file] = it
     return table
 
 
@@ -743,7 +743,6 @@ def render_final_sweep_main(argv=None):
     """render_final_sweep.py: render_folder [--render_camera_z_offset] [--render_marker_size]."""
     import argparse
     from pathlib import Path
-    from .cli import read_ace_pose_file
     p = argparse.ArgumentParser(description="Renders additional frames at the end of a reconstruction visualisation.",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("render_folder", type=Path)
@@ -792,31 +791,11 @@ def camera_mesh(poses_c2w_cv, confidences, frustum_scale=0.1, frustum_markers=Fa
     return traj.mesh()
 
 
-def write_ply_mesh(path, mesh):
-    """Binary little-endian PLY: float vertices, uint8 vertex colours (a vertex takes its face's colour), int32 triangle lists."""
-    verts = mesh.verts[mesh.faces].reshape(-1, 3)
-    clr = np.repeat(mesh.rgba[:, :3], 3, axis=0)
-    faces = np.arange(len(verts), dtype=np.int32).reshape(-1, 3)
-    vrec = np.empty(len(verts), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
-    vrec["x"], vrec["y"], vrec["z"] = verts[:, 0], verts[:, 1], verts[:, 2]
-    vrec["red"], vrec["green"], vrec["blue"] = clr[:, 0], clr[:, 1], clr[:, 2]
-    frec = np.empty(len(faces), dtype=[("n", "u1"), ("v", "<i4", (3,))])
-    frec["n"], frec["v"] = 3, faces
-    head = ("ply\nformat binary_little_endian 1.0\n"
-            f"element vertex {len(verts)}\nproperty float x\nproperty float y\nproperty float z\n"
-            "property uchar red\nproperty uchar green\nproperty uchar blue\n"
-            f"element face {len(faces)}\nproperty list uchar int vertex_indices\nend_header\n")
-    with open(path, "wb") as f:
-        f.write(head.encode("ascii"))
-        f.write(vrec.tobytes())
-        f.write(frec.tobytes())
-
-
 def export_cameras_main(argv=None):
     """export_cameras.py: pose_file output_file [--frustum_scale] [--frustum_markers] [--draw_non_confident] [--confidence_threshold]."""
     import argparse
     from pathlib import Path
-    from .cli import _strtobool, quat_wxyz_to_matrix
+    from .cli import _strtobool
     p = argparse.ArgumentParser(description="Export the cameras of an ACE pose file as a mesh (PLY).",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("pose_file", type=Path, help="ACE pose file (file qw qx qy qz tx ty tz focal confidence)")
@@ -827,17 +806,11 @@ def export_cameras_main(argv=None):
     p.add_argument("--confidence_threshold", type=int, default=CONFIDENCE_THRESHOLD, help="confidence threshold of the colour coding")
     opt = p.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
-    poses, conf = [], []
-    for line in open(opt.pose_file).read().splitlines():
-        tok = line.split()
-        if len(tok) != 10:
-            continue
-        T = np.eye(4)
-        T[:3, :3] = quat_wxyz_to_matrix([float(t) for t in tok[1:5]])
-        T[:3, 3] = [float(t) for t in tok[5:8]]
-        poses.append(np.linalg.inv(T))
-        conf.append(float(tok[9]))
+    entries = read_pose_file(opt.pose_file, strict=False)        # a line that does not have ten fields is skipped
+    poses, conf = [np.linalg.inv(e.w2c) for e in entries], [e.confidence for e in entries]
     mesh = camera_mesh(poses, conf, opt.frustum_scale, opt.frustum_markers, opt.draw_non_confident, opt.confidence_threshold)
-    write_ply_mesh(opt.output_file, mesh)
+    # a vertex takes its face's colour: every face gets three vertices of its own
+    write_ply(opt.output_file, mesh.verts[mesh.faces], np.repeat(mesh.rgba[:, :3], 3, axis=0),
+              np.arange(3 * len(mesh.faces), dtype=np.int32), alpha=False)
     _logger.info(f"Done. {len(mesh.faces)} triangles of {len(poses)} cameras stored as: {opt.output_file}")
     return 0

@@ -33,8 +33,10 @@ from . import dsacstar
 from .encoder import Encoder, output_size
 import torch.distributed as dist
 
+from .formats import write_pose_line
 from .head import HeadGroup, HeadTrainer, _ptr, _stream, epoch_batches, epoch_permutations
 from .parallel import epoch_local_batches, gather_registrations, make_data_parallel, rank_world
+from .pointcloud import filter_scene_coordinates, point_colours
 
 _logger = logging.getLogger("acezero_amd.session")
 
@@ -709,7 +711,6 @@ class ReconstructionSession:
     def _finalize_map_visualization(self, vis, out, image_ids):
         """The end of a rendered mapping run: the N4 point cloud of the trained head over the mapped frames (refined poses, the
         visualiser's depth filter, OpenGL convention, the frames' RGB colours), grown over the transition frames; the `_mapping.pkl`."""
-        from .cli import point_colours
         c2w = np.tile(np.eye(4), (self.n, 1, 1))
         conf = np.full(self.n, -np.inf)
         ids = np.asarray(image_ids, np.int64)
@@ -982,7 +983,6 @@ class ReconstructionSession:
         (xyz [N,3] float32, source [N] = row of the point's map pixel in the maps of the registered frames one after the other --
         position * hw + map pixel when all have one size; source_pixels decodes it -- , the registered frame ids). One filter launch
         per size class. OpenCV convention by default, as ace_zero.py requests it (--convention opencv, :398)."""
-        from .pointcloud import filter_scene_coordinates
         sel = np.flatnonzero(np.asarray(confidence) >= self.opt.registration_confidence)   # load_dataset_ace keeps confidence >= threshold
         if self.world > 1:
             raise NotImplementedError("point-cloud export runs on one GPU (python export_point_cloud.py on the written pose file)")
@@ -1012,7 +1012,6 @@ class ReconstructionSession:
 
 def write_pose_file(path, image_names, poses_c2w, confidences, focal):
     """poses_<session>.txt (register_mapping.py:261-276): world->camera quaternion + translation, focal (one, or one per image), confidence."""
-    from .cli import write_pose_line
     focals = np.broadcast_to(np.asarray(focal, np.float64), (len(image_names),))
     with open(path, "w") as f:
         for name, p, c, fl in zip(image_names, poses_c2w, confidences, focals):

@@ -112,7 +112,7 @@ def write_room_scene(folder, n, h, w, focal, rgb_scale=2, confidence=5000):
 
 
 def read_mesh_ply(path):
-    """(vertices float32 [V,3], colours uint8 [V,3], faces int32 [F,3]) of a file fusion.write_mesh_ply wrote."""
+    """(vertices float32 [V,3], colours uint8 [V,3], faces int32 [F,3]) of a file formats.write_ply wrote."""
     import re
     blob = open(path, "rb").read()
     head, body = blob.split(b"end_header\n", 1)

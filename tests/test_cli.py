@@ -10,7 +10,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from acezero_amd import cli, synth
+from acezero_amd import cli, pointcloud, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -143,7 +143,7 @@ def test_export_point_cloud_from_visualization_buffer(tmp_path):
         cli.export_point_cloud_main([str(tmp_path / "pc.txt")])                                    # neither buffer nor network + pose file
     with pytest.raises(SystemExit):
         cli.export_point_cloud_main([str(tmp_path / "pc.txt"), "--visualization_buffer", str(tmp_path / "buf.pkl"), "--dense_point_cloud", "True"])
-    c = cli.source_colours(np.arange(2 * 16 * 24 * 3, dtype=np.uint8).reshape(2, 16, 24, 3), np.array([1, 0]), np.array([4, 0]), 3)
+    c = pointcloud.source_colours(np.arange(2 * 16 * 24 * 3, dtype=np.uint8).reshape(2, 16, 24, 3), np.array([1, 0]), np.array([4, 0]), 3)
     assert c.shape == (2, 3) and np.array_equal(c[1], np.arange(2 * 16 * 24 * 3, dtype=np.uint8).reshape(2, 16, 24, 3)[0, 4, 4])
 
 

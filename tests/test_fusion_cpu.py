@@ -118,11 +118,11 @@ def test_extraction_edge_cases():
 
 
 def test_ply_round_trip(tmp_path):
-    from acezero_amd.fusion import write_mesh_ply
+    from acezero_amd.formats import write_ply
     v, c, f = sphere_mesh()
     c = (np.arange(len(v) * 3) % 251).astype(np.uint8).reshape(-1, 3)
     path = tmp_path / "mesh.ply"
-    write_mesh_ply(path, v, c, f)
+    write_ply(path, v, c, f)
     blob = path.read_bytes()
     head, body = blob.split(b"end_header\n", 1)
     lines = head.decode().splitlines()

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from acezero_amd import cli, session
+from acezero_amd import cli, pointcloud, session
 
 # (w, h) of the frames in sorted order: landscape, portrait, and one wider frame (a class of its own)
 SIZES = [(64, 48), (48, 64), (64, 48), (48, 64), (80, 48), (64, 48)]
@@ -101,7 +101,7 @@ def test_point_sources_of_mixed_frames():
     assert frame.tolist() == [1, 1, 2, 2, 3, 3] and pix.tolist() == [0, 11, 0, 11, 0, 19] and ow.tolist() == [3, 3, 4, 4, 5, 5]
     rgb = [np.full((24, 32, 3), 0, np.uint8), np.arange(32 * 24 * 3, dtype=np.uint8).reshape(32, 24, 3) % 200,
            np.full((24, 32, 3), 7, np.uint8), np.full((32, 40, 3), 9, np.uint8)]
-    clr = cli.source_colours(rgb, frame, pix, ow)
+    clr = pointcloud.source_colours(rgb, frame, pix, ow)
     assert np.array_equal(clr[0], rgb[1][4, 4]) and np.array_equal(clr[1], rgb[1][28, 20]) and (clr[2:4] == 7).all() and (clr[4:] == 9).all()
 
 

@@ -173,17 +173,16 @@ def test_depth_range_from_cloud():
 
 
 def test_point_cloud_reader(tmp_path):
-    from acezero_amd.fusion import write_mesh_ply
-    from acezero_amd.mvs import read_point_cloud_ply
+    from acezero_amd.formats import read_ply_vertices, write_ply
     from acezero_amd.pointcloud import write_point_cloud
     xyz = np.random.default_rng(2).normal(size=(37, 3)).astype(np.float32)
     write_point_cloud(tmp_path / "pc.ply", xyz, np.full((37, 3), 200.0))
-    assert np.array_equal(read_point_cloud_ply(tmp_path / "pc.ply"), xyz)
-    write_mesh_ply(tmp_path / "mesh.ply", xyz, np.zeros((37, 3), np.uint8), np.array([[0, 1, 2]], np.int32))
-    assert np.array_equal(read_point_cloud_ply(tmp_path / "mesh.ply"), xyz)
+    assert np.array_equal(read_ply_vertices(tmp_path / "pc.ply"), xyz)
+    write_ply(tmp_path / "mesh.ply", xyz, np.zeros((37, 3), np.uint8), np.array([[0, 1, 2]], np.int32))
+    assert np.array_equal(read_ply_vertices(tmp_path / "mesh.ply"), xyz)
     (tmp_path / "bad.ply").write_bytes(b"ply\nformat ascii 1.0\nend_header\n")
     with pytest.raises(SystemExit, match="not a binary"):
-        read_point_cloud_ply(tmp_path / "bad.ply")
+        read_ply_vertices(tmp_path / "bad.ply")
 
 
 def native_rows(rows):
