@@ -168,7 +168,8 @@ def test_training_steps_match_oracle_and_golden(name):
         assert abs(st["lr"] - orc.sched.lr) <= 1e-15 * max(1.0, abs(orc.sched.lr)) + 1e-18
         if it + 1 < len(g["lr"]):
             assert abs(st["lr"] - g["lr"][it + 1]) < 1e-12
-        # AdamW: the GPU applied its own gradient; compare with the oracle's update from the same start
+        # AdamW, end to end only: the GPU applied its own gradient, the oracle its own (they differ by bf16 rounding), hence the wide
+        # bound. The optimiser arithmetic itself is pinned bit for bit in tests/test_adamw_exact_gpu.py.
         assert _rel(tr.params.cpu().numpy() - flat0.numpy(), orc.head.p.flat.numpy() - flat0.numpy()) < 6e-2
         if cfg["refine_calibration"]:
             # (the scalar's AdamW state is not re-synchronised between steps: 1e-3 per step, a few percent of that as drift)
@@ -177,6 +178,7 @@ def test_training_steps_match_oracle_and_golden(name):
             moved = np.abs(tr.pose_params.cpu().numpy() - pose_before).max()
             assert (moved > 0) == (it > cfg["pose_refinement_wait"])          # ace_trainer.py:634: strict >
             if it > cfg["pose_refinement_wait"]:
+                # (the end-to-end figure, each side with its own pose gradient; the arithmetic: tests/test_adamw_exact_gpu.py)
                 assert _rel(tr.pose_params.cpu().numpy() - pose_before, orc.pose.flat.detach().numpy() - pose_before) < 5e-2
             if it < g["poses"].shape[0]:
                 # vs the reference PoseRefiner: identical until the first pose update; afterwards each AdamW step moves every
