@@ -118,6 +118,11 @@ struct acez_trainer {
   // (rowseq_loss_kernel): three launches per step. ACEZ_LOSS_IN_CHAIN=0 = loss_kernel / loss_gather_kernel as a launch of their own
   // (bit-identical results).
   bool loss_in_chain = true;
+  // ... and the forward chain in front of it in the same launch (rowstep_kernel): two launches per step. acez_trainer_set_step_chain(0)
+  // (HeadTrainer: ACEZ_STEP_CHAIN=0 at creation) = the three-launch flow (bit-identical results), which also runs while profiling is on:
+  // its event pairs around the chain launches keep their meaning.
+  bool step_chain = true;
+  long step_chain_steps = 0;   // steps run through the merged launch (acez_trainer_step_chain_status)
   long seq_launches = 0, seq_fault_at = -1;   // tests: ACEZ_SEQ_FAULT_AT=<n> makes the n-th launch time out
   // wgrad_opt_kernel (head_kernels.hip): the optimiser step of the wide layers inside the weight-gradient launch of the single-GPU fused
   // step. Same placement contract and safety net as the one-launch chains (tr->seq, the probe, the bounded poll, seq_err): usable only
@@ -750,6 +755,7 @@ struct StepRun {
   const int64_t* next; int n_next;   // the announced next batch (none: null or no rows)
   int nblk;
   bool loss_in_chain = false;   // the loss runs as stage -1 of the input-gradient chain's launch (train_step_impl decides)
+  bool step_chain = false;      // ... and the forward chain in front of it, in the same launch (rowstep_kernel; implies loss_in_chain)
   hipStream_t s, ps;     // ps: the stream of the pose launches the step does not carry (beside the head's chains; else = s)
   const TrainState* st;  // the slot the step reads (known after its begin launch)
 };
@@ -915,6 +921,33 @@ static void launch_dgrad(acez_trainer* tr, int n, const TrainState* st, hipStrea
   else if (inchain) abort();   // (train_step_impl only asks for it where the one-launch chain runs)
 }
 
+// Both chains of a fused step and its loss as ONE launch (rowstep_kernel): the layer tables of launch_forward and launch_dgrad, the loss
+// arguments of the three-launch flow, launch_rowseq's host bookkeeping for n_fwd + n_bwd hand-offs per row tile
+static void launch_rowstep(const StepRun& r) {
+  acez_trainer* tr = r.tr;
+  std::vector<SeqLayer> fwd, bwd;
+  launch_forward(tr, tr->R[0], r.n, r.st, r.s, &fwd);
+  launch_dgrad(tr, r.n, r.st, r.s, &bwd);
+  if (fwd.size() > SEQ_MAX_LAYERS || bwd.size() > SEQ_MAX_LAYERS || bwd.empty()) abort();   // (train_step_impl only asks for it where both tables fit)
+  const int mtiles = (r.n + 79) / 80;
+  RowStepArgs a{};
+  for (size_t i = 0; i < fwd.size(); ++i) a.fwd[i] = fwd[i];
+  for (size_t i = 0; i < bwd.size(); ++i) a.bwd[i] = bwd[i];
+  a.n_fwd = (int)fwd.size(); a.n_bwd = (int)bwd.size(); a.M = r.n;
+  a.st = r.st ? r.st : tr->st_infer; a.flags = tr->seq_flags; a.xcc_dbg = tr->seq_xcc; a.spin_limit = tr->seq_spin_limit;
+  for (int mt = 0; mt < 64; ++mt) a.base[mt] = tr->seq_base[mt];
+  // tests (ACEZ_SEQ_FAULT_AT): the launch stands for two of the three-launch flow's, the forward chain's and the input-gradient chain's
+  if (tr->seq_fault_at >= tr->seq_launches && tr->seq_fault_at < tr->seq_launches + 2)
+    for (int mt = 0; mt < 64; ++mt) a.base[mt] += 1u << 20;
+  tr->seq_launches += 2;
+  a.x = train_loss_in_chain(r);
+  if (tr->f16) hipLaunchKernelGGL(rowstep_kernel<EltF16>, dim3(32 * ((mtiles + 7) / 8)), dim3(512), 0, r.s, a);
+  else hipLaunchKernelGGL(rowstep_kernel<EltBf16>, dim3(32 * ((mtiles + 7) / 8)), dim3(512), 0, r.s, a);
+  for (int mt = 0; mt < mtiles; ++mt) tr->seq_base[mt] += (uint32_t)(a.n_fwd + a.n_bwd);
+  tr->prof_launches += a.n_fwd + a.n_bwd;
+  ++tr->step_chain_steps;
+}
+
 // The partial buffers of a step and its weight-gradient launch (wgrad_opt_kernel: Opt::WgradOpt); the split flow's gradient reduction
 static void launch_weight_grads(acez_trainer* tr, const StepPlan& p, int n, int nblk, const TrainState* st, hipStream_t s) {
   const bool fused = p.flow == Flow::Fused;
@@ -1068,12 +1101,15 @@ static void pose_bwd_launches(acez_trainer* tr, int n, hipStream_t q) {
 }
 
 static StepRun start_run(acez_trainer* tr, Flow flow, const int64_t* idx, int n, const int64_t* next, int n_next, hipStream_t s) {
-  return StepRun{tr, plan_step(tr, flow, idx, n, next, n_next), idx, n, next, n_next, loss_blocks(n), false, s, tr->pose_stream ? tr->pose_stream : s, nullptr};
+  return StepRun{tr, plan_step(tr, flow, idx, n, next, n_next), idx, n, next, n_next, loss_blocks(n), false, false, s, tr->pose_stream ? tr->pose_stream : s, nullptr};
 }
 
 // a run's GEMM chain on per-layer launches or rowseq_kernel: forward (bwd = false) or input gradients
 static void launch_chain(const StepRun& r, bool bwd) {
-  if (bwd) launch_dgrad(r.tr, r.n, r.st, r.s, nullptr, r.loss_in_chain ? &r : nullptr);
+  if (r.step_chain) {   // one launch for both chains, made where the input-gradient chain's would be
+    if (bwd) launch_rowstep(r);
+  }
+  else if (bwd) launch_dgrad(r.tr, r.n, r.st, r.s, nullptr, r.loss_in_chain ? &r : nullptr);
   else launch_forward(r.tr, r.tr->R[0], r.n, r.st, r.s);
 }
 
@@ -1134,7 +1170,24 @@ static int train_step_impl(acez_trainer* tr, Flow flow, const int64_t* d_indices
   StepRun r = start_run(tr, flow, d_indices, n, d_next, n_next, (hipStream_t)stream);
   // three launches: only the single trainer's fused step on the one-launch chains (wgrad_opt_usable: no pose refinement, chains enabled)
   r.loss_in_chain = tr->loss_in_chain && r.plan.opt == Opt::WgradOpt && seq_usable(tr, n);
+  // two launches: the forward chain in that launch too, unless the chains' event pairs are being timed (bitwise the same step either way)
+  r.step_chain = r.loss_in_chain && tr->step_chain && !tr->profiling && tr->L <= SEQ_MAX_LAYERS;
   return run_steps(&r, 1, [&](bool bwd) { launch_chain(r, bwd); });
+}
+
+// The steps of the two flows are bitwise equal and share the counter bases: the switch is safe between any two steps
+extern "C" int acez_trainer_set_step_chain(acez_trainer* tr, int enable) {
+  ACEZ_REQUIRE(tr, "null trainer");
+  tr->step_chain = enable != 0;
+  return ACEZ_OK;
+}
+
+// which flow the plain fused step takes (train_step_impl's conditions that do not depend on the batch) and how often it took the merged launch
+extern "C" int acez_trainer_step_chain_status(acez_trainer* tr, int* enabled, long long* steps) {
+  ACEZ_REQUIRE(tr, "null trainer");
+  if (enabled) *enabled = (tr->step_chain && tr->loss_in_chain && wgrad_opt_usable(tr) && tr->L <= SEQ_MAX_LAYERS) ? 1 : 0;
+  if (steps) *steps = tr->step_chain_steps;
+  return ACEZ_OK;
 }
 
 extern "C" int acez_train_backward(acez_trainer* tr, const int64_t* d_indices, int n, void* stream) {

@@ -572,21 +572,32 @@ struct RowSeqArgs {
                        // once), flags[64 * 32 + 1] = a copy of the poll budget (diagnostics)
 };
 
-// The layers of a chain for the workgroup of tile (mt, n0). SEAM0 = 1 (rowseq_loss_kernel): one hand-off of this launch lies in front of
-// layer 0 -- its In is produced inside the launch and its first four W stages have been requested by the caller.
-template <bool BWD, class E, int SEAM0>
-__device__ __forceinline__ void rowseq_layers(const RowSeqArgs& a, uint16_t* smem, const int mt, const int n0) {
-  for (int layer = 0; layer < a.n_layers; ++layer) {
-    const SeqLayer& y = a.layer[layer];
+// What the layers of a chain share: the batch, the trainer's state and counters, and where the chain stands among the launch's hand-offs
+struct SeqCtx {
+  int M;
+  const TrainState* st;
+  uint32_t* flags;       // RowSeqArgs::flags
+  uint32_t base;         // seams of this row tile completed by earlier launches (RowSeqArgs::base[mt])
+  uint32_t seam0;        // hand-offs of THIS launch in front of the chain's layer 0
+  uint32_t limit;        // RowSeqArgs::spin_limit
+};
+
+// The layers of a chain for the workgroup of tile (mt, n0). HEAD (rowseq_loss_kernel, rowstep_kernel's second chain): c.seam0 hand-offs of
+// this launch lie in front of layer 0 -- its In is produced inside the launch and its first four W stages have been requested by the
+// caller. TAIL (rowstep_kernel's first chain): a consumer follows the last layer inside the launch, so that layer signals too.
+template <bool BWD, class E, bool HEAD, bool TAIL = false>
+__device__ __forceinline__ void rowseq_layers(const SeqLayer* layers, const int n_layers, const SeqCtx& c, uint16_t* smem, const int mt, const int n0) {
+  for (int layer = 0; layer < n_layers; ++layer) {
+    const SeqLayer& y = layers[layer];
     RowGemmArgs g;
     g.In = y.In; g.W = y.W; g.bias = y.bias; g.add = y.add; g.mask_out = y.mask_out; g.mask_in = y.mask_in; g.res = y.res; g.out_main = y.out_main; g.out_aux = y.out_aux;
-    g.bias_partials = y.bias_partials; g.M = a.M; g.N = 512; g.K = 512; g.relu = BWD ? 0 : 1; g.aux_mode = y.aux_mode; g.st = a.st;
-    g.absmax = (BWD && a.st) ? const_cast<uint32_t*>(a.st->dz_absmax_slots) : nullptr;
+    g.bias_partials = y.bias_partials; g.M = c.M; g.N = 512; g.K = 512; g.relu = BWD ? 0 : 1; g.aux_mode = y.aux_mode; g.st = c.st;
+    g.absmax = (BWD && c.st) ? const_cast<uint32_t*>(c.st->dz_absmax_slots) : nullptr;
     SeqLink q;
-    q.flag = a.flags + mt * 32; q.target = (a.base[mt] + (uint32_t)(layer + SEAM0)) * 32u;   // 4 workgroups x 8 waves per seam
-    q.first = !SEAM0 && layer == 0; q.wait = SEAM0 || layer > 0; q.signal = layer + 1 < a.n_layers;
-    q.next_W = q.signal ? a.layer[layer + 1].W : nullptr;
-    q.flag_index = (uint32_t)(mt * 32); q.limit = a.spin_limit;
+    q.flag = c.flags + mt * 32; q.target = (c.base + c.seam0 + (uint32_t)layer) * 32u;   // 4 workgroups x 8 waves per seam
+    q.first = !HEAD && layer == 0; q.wait = HEAD || layer > 0; q.signal = TAIL || layer + 1 < n_layers;
+    q.next_W = layer + 1 < n_layers ? layers[layer + 1].W : nullptr;
+    q.flag_index = (uint32_t)(mt * 32); q.limit = c.limit;
     if (!BWD) {
       if (y.aux_mode == AUX_RESIDUAL) rowgemm80_body<true, false, false, AUX_RESIDUAL, true, E>(g, smem, 1, mt, n0, q);
       else rowgemm80_body<true, false, false, AUX_NONE, true, E>(g, smem, 1, mt, n0, q);
@@ -621,7 +632,7 @@ __global__ __launch_bounds__(512) void rowseq_kernel(RowSeqArgs a) {
     }
     return;
   }
-  rowseq_layers<BWD, E, 0>(a, smem, mt, (jx & 3) * 128);
+  rowseq_layers<BWD, E, false>(a.layer, a.n_layers, SeqCtx{a.M, a.st, a.flags, a.base[mt], 0u, a.spin_limit}, smem, mt, (jx & 3) * 128);
 }
 
 // Placement probe (acez_trainer_create): a launch with rowseq_kernel's grid, block size and LDS footprint that only records
@@ -2193,35 +2204,57 @@ struct SeqLossArgs {
   GatherMeta meta;
 };
 
-template <class E = EltBf16>
-__global__ __launch_bounds__(512) void rowseq_loss_kernel(RowSeqArgs a, SeqLossArgs x) {
-  __shared__ __attribute__((aligned(16))) uint16_t smem[RG80_SMEM_SEQ];
-  const int mtiles = (a.M + 79) / 80;
-  const int per_xcd = (mtiles + 7) >> 3;
-  const int jx = blockIdx.x >> 3;
-  const int mt = (blockIdx.x & 7) * per_xcd + (jx >> 2);
-  if (mt >= mtiles) return;
+// rowgemm80_body's hand-off poll for a consumer that is not a layer (the loss blocks of rowstep_kernel): the same bounded single asm
+// statement, sc1 past this CU's L1 (see there). True: the budget expired.
+__device__ __forceinline__ bool seq_poll_expired(const uint32_t* flag, uint32_t target, uint32_t limit) {
+  uint32_t vseen, sseen, spins, timed;
+  asm volatile(
+      "s_mov_b32 %[spins], 0\n\t"
+      "s_mov_b32 %[timed], 0\n"
+      "1:\n\t"
+      "global_load_dword %[vseen], %[flag], off sc1\n\t"
+      "s_waitcnt vmcnt(0)\n\t"
+      "v_readfirstlane_b32 %[sseen], %[vseen]\n\t"
+      "s_sub_i32 %[sseen], %[sseen], %[target]\n\t"
+      "s_cmp_ge_i32 %[sseen], 0\n\t"
+      "s_cbranch_scc1 2f\n\t"
+      "s_sleep 1\n\t"
+      "s_add_u32 %[spins], %[spins], 1\n\t"
+      "s_cmp_lt_u32 %[spins], %[limit]\n\t"
+      "s_cbranch_scc1 1b\n\t"
+      "s_mov_b32 %[timed], 1\n"
+      "2:"
+      : [vseen] "=&v"(vseen), [sseen] "=&s"(sseen), [spins] "=&s"(spins), [timed] "=&s"(timed)
+      : [flag] "v"(flag), [target] "s"(target), [limit] "s"(limit)
+      : "memory", "scc");
+  return timed != 0;
+}
+
+// Stage -1 for the workgroup of tile (mt, nt), all eight waves: the first layer's W stages, the next batch's gather, the tile's loss
+// blocks and their hand-off to layer 0 (`W0`: that layer's weights). `dead`: the launch's entry test -- only the gather runs.
+// FWD_SEAM (rowstep_kernel): the blocks' `act` rows are produced inside this launch, by the four workgroups of the row tile: every wave
+// that runs a block first waits for the tile's counter to reach `c.base + c.seam0 - 1` seams, as a layer's loader waves would. Nothing
+// is requested in front of that poll: the four workgroups of a tile run in step, so the poll is usually passed at its first look, and
+// whatever sits in front of its vmcnt(0) is a round trip added to the chain, not hidden by it (W3, b3 and the rows' indices and metadata
+// touched there, to warm this CU's L1 for loss_body: +0.8 us per step, DESIGN_HISTORY).
+template <class E, bool FWD_SEAM>
+__device__ __forceinline__ void rowseq_loss_stage(const uint16_t* W0, const SeqLossArgs& x, const SeqCtx& c, const bool dead, uint16_t* smem,
+                                                  const int mt, const int nt, const int mtiles) {
   const int t = threadIdx.x, l = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int nt = jx & 3, n0 = nt * 128;
-  if (a.xcc_dbg && t == 0) {
-    const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;   // HW_REG_XCC_ID[3:0]
-    atomicOr(a.xcc_dbg + (blockIdx.x & 7), 1u << xcc);
-    a.xcc_dbg[8 + mt * 4 + nt] = xcc;
-  }
+  const int n0 = nt * 128;
   // the quartets' meeting counters: in the bias-partial combine buffer (first used by layer 0's epilogue)
   uint32_t* const qsync = reinterpret_cast<uint32_t*>(smem + RG80_SMEM);
   if (t < 2) qsync[t] = 0u;
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  const bool dead = (a.st && !a.st->active) || a.flags[64 * 32];   // rowseq_kernel's entry test
+  __builtin_amdgcn_s_barrier();   // (FWD_SEAM: also every wave's last read of the staging tiles the scratch lies in)
   if (w >= 4) {
     const int lw = w - 4;
     if (!dead) {   // rowgemm80_body's issueW(0 .. 3) for layer 0
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int row = (lw * 4 + j) * 8 + (l >> 3);
-        const uint16_t* g = a.layer[0].W + (size_t)(n0 + row) * 512 + ((l & 7) ^ ((row >> 1) & 7)) * 8;
+        const uint16_t* g = W0 + (size_t)(n0 + row) * 512 + ((l & 7) ^ ((row >> 1) & 7)) * 8;
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt)
           __builtin_amdgcn_global_load_lds((gvoid_t*)(g + kt * 64), (lvoid_t*)(smem + kt * RG80_STAGE + (lw * 4 + j) * 8 * 64), 16, 0, 0);
@@ -2229,16 +2262,15 @@ __global__ __launch_bounds__(512) void rowseq_loss_kernel(RowSeqArgs a, SeqLossA
     }
     if (nt != 0 && x.n_next > 0) gather_rows<8>(x.feat, x.idx_next, x.out_next, x.n_next, (mt * 3 + nt - 1) * 4 + lw, mtiles * 12, l, x.meta);
   }
-  if (dead) {   // no work, but the counters keep step with the host's bases (one seam more than rowseq_kernel's launch)
-    if (t == 0) {
-      const uint32_t inc = 8u * (uint32_t)a.n_layers;
-      asm volatile("global_atomic_add %0, %1, off" ::"v"(a.flags + mt * 32), "v"(inc) : "memory");
-    }
-    return;
-  }
+  if (dead) return;
   if (w < 4 || nt == 0) {
+    uint32_t* const flag = c.flags + mt * 32;
     const int quartet = w >> 2;
     const int block = 5 * mt + (nt == 0 ? quartet : nt + 1);
+    if (FWD_SEAM && seq_poll_expired(flag, (c.base + c.seam0 - 1u) * 32u, c.limit) && l == 0) {   // rowgemm80_body's fault path
+      __hip_atomic_store(c.flags + 64 * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (c.st) __hip_atomic_store(const_cast<int*>(&c.st->active), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     if (block < x.nblk) {
       float* scratch = reinterpret_cast<float*>(smem + 4 * RG80_STAGE) + quartet * (3 * 4 * 4 * 4);
       uint32_t* const f = qsync + quartet;
@@ -2247,10 +2279,90 @@ __global__ __launch_bounds__(512) void rowseq_loss_kernel(RowSeqArgs a, SeqLossA
     ACEZ_VMCNT(0);   // this wave's dZ stores are acknowledged by the L2 the four sibling workgroups share
     if (l == 0) {
       const uint32_t inc = nt == 0 ? 1u : 2u;   // 8 per workgroup: eight waves, or four
-      asm volatile("global_atomic_add %0, %1, off" ::"v"(a.flags + mt * 32), "v"(inc) : "memory");
+      asm volatile("global_atomic_add %0, %1, off" ::"v"(flag), "v"(inc) : "memory");
     }
   }
-  rowseq_layers<true, E, 1>(a, smem, mt, n0);
+}
+
+template <class E = EltBf16>
+__global__ __launch_bounds__(512) void rowseq_loss_kernel(RowSeqArgs a, SeqLossArgs x) {
+  __shared__ __attribute__((aligned(16))) uint16_t smem[RG80_SMEM_SEQ];
+  const int mtiles = (a.M + 79) / 80;
+  const int per_xcd = (mtiles + 7) >> 3;
+  const int jx = blockIdx.x >> 3;
+  const int mt = (blockIdx.x & 7) * per_xcd + (jx >> 2);
+  if (mt >= mtiles) return;
+  const int nt = jx & 3;
+  if (a.xcc_dbg && threadIdx.x == 0) {
+    const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;   // HW_REG_XCC_ID[3:0]
+    atomicOr(a.xcc_dbg + (blockIdx.x & 7), 1u << xcc);
+    a.xcc_dbg[8 + mt * 4 + nt] = xcc;
+  }
+  const bool dead = (a.st && !a.st->active) || a.flags[64 * 32];   // rowseq_kernel's entry test
+  const SeqCtx c{a.M, a.st, a.flags, a.base[mt], 1u, a.spin_limit};
+  rowseq_loss_stage<E, false>(a.layer[0].W, x, c, dead, smem, mt, nt, mtiles);
+  if (dead) {   // no work, but the counters keep step with the host's bases (one seam more than rowseq_kernel's launch)
+    if (threadIdx.x == 0) {
+      const uint32_t inc = 8u * (uint32_t)a.n_layers;
+      asm volatile("global_atomic_add %0, %1, off" ::"v"(a.flags + mt * 32), "v"(inc) : "memory");
+    }
+    return;
+  }
+  rowseq_layers<true, E, true>(a.layer, a.n_layers, c, smem, mt, nt * 128);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// rowstep: the forward chain, the loss stage and the input-gradient chain of a fused step in ONE launch -- rowseq_kernel<false> followed
+// by rowseq_loss_kernel on the same grid, decode and LDS. The dependency from the last forward layer to the loss blocks to the first
+// input-gradient layer is local to a row tile, whose four workgroups share an XCD in both chains: the kernel boundary between the two
+// launches ordered nothing that the row tile's counter does not order, and cost a launch ramp plus the drain of the forward chain's
+// dirty lines (which now leave the L2 by eviction, under the input-gradient layers).
+//   seams     per launch and row tile: n_fwd - 1 between the forward layers, one from the last forward layer (which signals: TAIL) to the
+//             loss blocks, one from the loss blocks to the first input-gradient layer, n_bwd - 1 between those: n_fwd + n_bwd (15 for the
+//             default head). One counter array, one base per row tile; a dead launch adds the same amount.
+//   L1        nothing is read through a CU's L1 before it is produced: `act` (fc2's output) has no reader inside the forward chain, the
+//             buffers the input-gradient chain and the loss write are none of the forward chain's inputs, the mask bits are written and
+//             read by the same lane. No fence, no cache write-back or invalidate anywhere in the launch.
+// ---------------------------------------------------------------------------------------------------
+struct RowStepArgs {
+  SeqLayer fwd[SEQ_MAX_LAYERS], bwd[SEQ_MAX_LAYERS];
+  int n_fwd, n_bwd, M;
+  const TrainState* st;
+  uint32_t* flags;       // as RowSeqArgs: flags, base, spin_limit, xcc_dbg -- once for both chains
+  uint32_t base[64];
+  uint32_t spin_limit;
+  uint32_t* xcc_dbg;
+  SeqLossArgs x;
+};
+static_assert(sizeof(RowStepArgs) <= 4096, "kernel-argument segment");
+
+template <class E = EltBf16>
+__global__ __launch_bounds__(512) void rowstep_kernel(RowStepArgs a) {
+  __shared__ __attribute__((aligned(16))) uint16_t smem[RG80_SMEM_SEQ];
+  const int mtiles = (a.M + 79) / 80;
+  const int per_xcd = (mtiles + 7) >> 3;
+  const int jx = blockIdx.x >> 3;
+  const int mt = (blockIdx.x & 7) * per_xcd + (jx >> 2);
+  if (mt >= mtiles) return;   // (a workgroup without a row tile touches no counter)
+  const int nt = jx & 3;
+  if (a.xcc_dbg && threadIdx.x == 0) {
+    const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;   // HW_REG_XCC_ID[3:0]
+    atomicOr(a.xcc_dbg + (blockIdx.x & 7), 1u << xcc);
+    a.xcc_dbg[8 + mt * 4 + nt] = xcc;
+  }
+  const bool dead = (a.st && !a.st->active) || a.flags[64 * 32];   // rowseq_kernel's entry test
+  const uint32_t base = a.base[mt];
+  if (!dead) rowseq_layers<false, E, false, true>(a.fwd, a.n_fwd, SeqCtx{a.M, a.st, a.flags, base, 0u, a.spin_limit}, smem, mt, nt * 128);
+  const SeqCtx c{a.M, a.st, a.flags, base, (uint32_t)a.n_fwd + 1u, a.spin_limit};
+  rowseq_loss_stage<E, true>(a.bwd[0].W, a.x, c, dead, smem, mt, nt, mtiles);
+  if (dead) {   // no work, but the counters keep step with the host's bases
+    if (threadIdx.x == 0) {
+      const uint32_t inc = 8u * (uint32_t)(a.n_fwd + a.n_bwd);
+      asm volatile("global_atomic_add %0, %1, off" ::"v"(a.flags + mt * 32), "v"(inc) : "memory");
+    }
+    return;
+  }
+  rowseq_layers<true, E, true>(a.bwd, a.n_bwd, c, smem, mt, nt * 128);
 }
 
 #ifdef ACEZ_DIAG   // timeline of the epilogue (tools/wgo_trace.py): stamp i of this wave

@@ -7,6 +7,7 @@ Mirrors the reference's seams:
 """
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import torch
@@ -191,6 +192,10 @@ class HeadTrainer:
         h = C.c_void_p()
         N.check(self.lib.acez_trainer_create(C.byref(h), C.byref(cfg), C.byref(pb), self.device.index))
         self._h = h
+        # ACEZ_STEP_CHAIN=0: the plain fused step keeps its two chains in a launch each (three launches, bitwise the same step); read
+        # here, at creation -- the shipped library has a call for it, not a variable
+        if os.environ.get("ACEZ_STEP_CHAIN") is not None and hasattr(self.lib, "acez_trainer_set_step_chain"):
+            N.check(self.lib.acez_trainer_set_step_chain(h, int(os.environ["ACEZ_STEP_CHAIN"] != "0")))
         self._buf = None
         self.iterations = int(iterations)
 
@@ -349,12 +354,19 @@ class HeadTrainer:
                 "nan": bool(st.nan_flag), "lr": st.lr, "loss": st.last_loss, "batch_inliers": st.last_batch_inliers,
                 "focal_scale": st.focal_scale, "grad_scale": st.grad_scale, "opt_steps": st.opt_steps}
 
-    def seq_status(self):
+    def seq_status(self, step_chain=False):
         """One-launch GEMM chains (rowseq_kernel): {'enabled', 'probe' (placement probe at creation: 1 passed, 0 failed, -1 not run),
-        'faults' (fall-backs to per-layer launches taken after an expired hand-off poll; state() performs them)}."""
+        'faults' (fall-backs to per-layer launches taken after an expired hand-off poll; state() performs them)}.
+        step_chain=True adds the merged chain launch of the plain fused step (rowstep_kernel): 'step_chain' (such a step would take it)
+        and 'step_chain_steps' (steps that have run through it)."""
         en, pr, fl = C.c_int(0), C.c_int(0), C.c_int(0)
         N.check(self.lib.acez_trainer_seq_status(self._h, C.byref(en), C.byref(pr), C.byref(fl)))
-        return {"enabled": bool(en.value), "probe": pr.value, "faults": fl.value}
+        out = {"enabled": bool(en.value), "probe": pr.value, "faults": fl.value}
+        if step_chain:
+            on, steps = C.c_int(0), C.c_longlong(0)
+            N.check(self.lib.acez_trainer_step_chain_status(self._h, C.byref(on), C.byref(steps)))
+            out.update(step_chain=bool(on.value), step_chain_steps=steps.value)
+        return out
 
     def log(self, first, count):
         loss = np.zeros(count, np.float32)

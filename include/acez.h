@@ -395,8 +395,11 @@ int acez_trainer_import_weights16_all(acez_trainer* tr, int own_lo, int own_hi, 
  * parameters as the two calls above; afterwards d_grad holds the bias / fc3 gradients and the statistics only (its wide-layer weight
  * part is not written). Without pose refinement, and while the one-launch chains are enabled (acez_trainer_seq_status), the weight-gradient
  * launch applies the whole optimiser step itself (wgrad_opt_kernel: the split-K halves of a tile are exchanged inside one XCD's L2 and
- * never reach memory) and closes the step's schedule; otherwise the slabs go through memory to a separate optimiser launch. Use
- * backward / all-reduce / update when ranks exchange d_grad. */
+ * never reach memory) and closes the step's schedule; otherwise the slabs go through memory to a separate optimiser launch. That step is
+ * two launches: the forward chain, the loss and the input-gradient chain as one (rowstep_kernel), then wgrad_opt_kernel.
+ * acez_trainer_set_step_chain(tr, 0) (the Python HeadTrainer calls it at creation when ACEZ_STEP_CHAIN=0 is set), profiling
+ * (acez_trainer_set_profiling) and a head whose chains are longer than eight layers keep the two chains in a launch each, the loss inside the second (three launches; ACEZ_LOSS_IN_CHAIN=0: four) -- bitwise the same step, so the flows
+ * may alternate. Use backward / all-reduce / update when ranks exchange d_grad. */
 int acez_train_step(acez_trainer* tr, const int64_t* d_indices, int n, void* stream);
 /* acez_train_step with the NEXT step's indices announced (run_epoch walks consecutive slices of one permutation, ace_trainer.py:466-494,
  * so the caller knows them): the next batch is gathered inside this step's launches (beside the loss kernel, into the second of the
@@ -447,6 +450,10 @@ int acez_trainer_get_profile(acez_trainer* tr, float* h_ms8, int32_t* h_counts8)
  * rows that were not updated are updated with that step's optimiser scalars -- so that the state is exactly the step after, bit for bit
  * what acez_train_backward + acez_train_update would have produced. */
 int acez_trainer_seq_status(acez_trainer* tr, int* enabled, int* probe, int* faults);
+/* The merged chain launch of the plain fused step (acez_train_step): *enabled = 1 while such a step would take it (profiling off),
+ * *steps = steps that have run through it. Any pointer may be NULL. */
+int acez_trainer_step_chain_status(acez_trainer* tr, int* enabled, long long* steps);
+int acez_trainer_set_step_chain(acez_trainer* tr, int enable);   /* default 1; may be changed between any two steps */
 
 /* Diagnostics for the tests: copy one intermediate device buffer of the last backward call to the host (synchronous).
  * kind 0: post-ReLU output of wide layer `index`, bf16 [n][512];  1: dZ of layer `index`, bf16 [n][512];
