@@ -21,7 +21,8 @@ from pathlib import Path
 import numpy as np
 
 from . import DEFAULT_DTYPE
-from .formats import match_poses, read_ace_pose_file, read_depth_png, read_ply_vertices, write_depth_png, write_ply, write_pose_line
+from .formats import (match_poses, read_ace_pose_file, read_depth_png, read_ply_points, read_ply_vertices, write_depth_png, write_ply,
+                      write_pose_line)
 
 _logger = logging.getLogger("acezero_amd")
 
@@ -1184,6 +1185,94 @@ def fuse_depth_main(argv=None):
     log.info(f"Known voxels: {known}. Mesh: {len(vertices)} vertices, {len(faces)} faces.")
     log.info(f"Decode {t_decode:.2f} s, upload + kernels + download {t_device:.2f} s, write {t_write:.2f} s.")
     log.info(f"Done. Wrote mesh to: {opt.output_file}")
+    return 0
+
+
+# -------------------------------------------------------------------------------------------------------- eval_geometry
+def eval_geometry_parser():
+    from .evaluate import DEFAULT_SEED
+    p = argparse.ArgumentParser(description="Score a reconstructed point cloud or mesh (by its vertices) against a ground-truth cloud on "
+                                            "the GPU: precision, recall and F-score per distance threshold (the Tanks and Temples metric).",
+                                formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("reconstruction", type=Path, help="reconstructed cloud or mesh (.ply, binary little-endian or ASCII)")
+    p.add_argument("ground_truth", type=Path, help="ground-truth cloud (.ply)")
+    p.add_argument("--thresholds", type=float, nargs="+", default=[0.01, 0.02, 0.05], help="distance thresholds in metres")
+    p.add_argument("--voxel_size", type=float, default=None, help="downsample both clouds to one point (the mean) per voxel of this edge first")
+    p.add_argument("--max_distance", type=float, default=None, help="search radius, and the value distances are clipped to in the means; "
+                                                                    "default: the largest threshold")
+    p.add_argument("--crop", type=_strtobool, default=True, help="drop reconstruction points outside the ground truth's bounding box "
+                                                                 "enlarged by the search radius")
+    p.add_argument("--transform", type=Path, default=None, help="text file with a 4x4 similarity, reconstruction -> ground-truth frame")
+    p.add_argument("--ace_pose_file", type=Path, default=None, help="ACE pose file of the reconstruction; with --gt_pose_files the "
+                                                                    "similarity is estimated from the two sets of poses as eval_poses.py does")
+    p.add_argument("--gt_pose_files", type=str, default=None, help="glob of ground-truth pose files (4x4 cam2world, one per image, matched "
+                                                                   "to the pose file's images by alphabetical order)")
+    p.add_argument("--estimate_alignment_conf_threshold", type=float, default=500, help="only poses above this confidence enter the alignment")
+    p.add_argument("--seed", type=int, default=DEFAULT_SEED, help="key of the alignment's stream of RANSAC samples")
+    p.add_argument("--output_json", type=Path, default=None, help="write the numbers to this file")
+    return p
+
+
+def eval_geometry_main(argv=None):
+    """eval_geometry.py: two .ply files (+ an alignment) -> nearest-neighbour distances both ways (HIP) -> precision / recall / F-score."""
+    import json
+    from . import geometry
+    opt = eval_geometry_parser().parse_args(argv)
+    logging.basicConfig(level=logging.INFO)
+    log = logging.getLogger("eval_geometry")
+    if opt.transform is not None and (opt.ace_pose_file is not None or opt.gt_pose_files is not None):
+        raise SystemExit("give either --transform or the pair --ace_pose_file / --gt_pose_files, not both")
+    if (opt.ace_pose_file is None) != (opt.gt_pose_files is None):
+        raise SystemExit("--ace_pose_file and --gt_pose_files go together")
+    for path in (opt.reconstruction, opt.ground_truth, opt.transform, opt.ace_pose_file):
+        if path is not None and not os.path.isfile(path):
+            raise SystemExit(f"{path}: no such file")
+    if any(not (math.isfinite(t) and t > 0) for t in opt.thresholds):
+        raise SystemExit("--thresholds must be positive")
+    for name in ("voxel_size", "max_distance"):
+        value = getattr(opt, name)
+        if value is not None and not (math.isfinite(value) and value > 0):
+            raise SystemExit(f"--{name} must be positive")
+    rec, gt = read_ply_points(opt.reconstruction), read_ply_points(opt.ground_truth)
+    log.info(f"Read {len(rec)} points from {opt.reconstruction} and {len(gt)} from {opt.ground_truth}.")
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("eval_geometry.py needs a GPU: the cloud distances are HIP kernels, there is no CPU path")
+    transform = None
+    if opt.transform is not None:
+        try:
+            transform = np.loadtxt(opt.transform, dtype=np.float64).reshape(4, 4)
+        except ValueError:
+            raise SystemExit(f"{opt.transform}: expected 16 numbers, a 4x4 matrix")
+    elif opt.ace_pose_file is not None:
+        from .evaluate import evaluate_poses, load_gt_pose_files, read_pose_file_with_confidence
+        estimates = read_pose_file_with_confidence(opt.ace_pose_file)
+        pairs = list(zip([estimates[key] for key in sorted(estimates.keys())], load_gt_pose_files(opt.gt_pose_files)))
+        if not pairs:
+            raise SystemExit("no (estimate, ground truth) pose pairs to align with")
+        res = evaluate_poses(np.stack([p[0][0] for p in pairs]), np.stack([p[1] for p in pairs]), np.array([p[0][1] for p in pairs]),
+                             estimate_alignment_conf_threshold=opt.estimate_alignment_conf_threshold, seed=opt.seed)
+        if res["T"] is None:
+            raise SystemExit("the alignment of the estimated poses to the ground-truth poses failed: too few confident poses, or no "
+                             "consistent similarity")
+        transform = np.linalg.inv(res["T"])                       # T maps ground truth -> estimates (its rotation part carries the scale)
+        log.info(f"Aligned on {len(pairs)} pose pairs: scale {res['scale']:.6f} (ground truth -> reconstruction), median pose error "
+                 f"{res['median_r_deg']:.2f}deg, {res['median_t_cm']:.1f}cm.")
+    t0 = time.perf_counter()
+    try:
+        res = geometry.evaluate_geometry(torch.from_numpy(rec).cuda(), torch.from_numpy(gt).cuda(), opt.thresholds, transform=transform,
+                                         voxel=opt.voxel_size, crop=opt.crop, max_distance=opt.max_distance)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    t_device = time.perf_counter() - t0
+    for line in geometry.log_lines(res):
+        log.info(line)
+    log.info(f"Upload + kernels + download {t_device:.2f} s.")
+    if opt.output_json is not None:
+        res["transform"] = None if transform is None else [[float(x) for x in row] for row in transform]
+        with open(opt.output_json, "w") as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write("\n")
     return 0
 
 

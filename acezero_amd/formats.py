@@ -118,6 +118,55 @@ def read_ply_vertices(path):
     return np.stack([rec["x"], rec["y"], rec["z"]], axis=1)
 
 
+# PLY scalar type -> numpy type without byte order (both spellings of the format's type names)
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply_points(path):
+    """float32 [m,3]: the x, y, z of the vertex element of a binary little-endian or ASCII .ply, whatever else the element carries
+    (normals, colours with or without alpha, doubles): ground-truth scans and other tools' clouds. The vertex element must come
+    first (it does in every file met so far) and have scalar properties only; further elements (faces) are ignored."""
+    blob = open(str(path), "rb").read()
+    head, sep, body = blob.partition(_PLY_END)
+    lines = [line.strip() for line in head.decode("ascii", "replace").splitlines()]
+    if not sep or lines[:1] != ["ply"]:
+        raise SystemExit(f"{path}: not a .ply file")
+    fmt = [line.split()[1] for line in lines if line.split()[:1] == ["format"]]
+    if fmt not in (["binary_little_endian"], ["ascii"]):
+        raise SystemExit(f"{path}: only binary little-endian and ASCII .ply files are read")
+    count, props, elements = 0, [], []
+    for line in lines:
+        tok = line.split()
+        if tok[:1] == ["element"] and len(tok) == 3:
+            elements.append(tok[1])
+            if tok[1] == "vertex":
+                count = int(tok[2])
+        elif tok[:1] == ["property"] and elements[-1:] == ["vertex"]:
+            if len(tok) != 3 or tok[1] not in _PLY_TYPES:
+                raise SystemExit(f"{path}: vertex property '{line}' is not a scalar of a known type")
+            props.append((tok[2], _PLY_TYPES[tok[1]]))
+    if elements[:1] != ["vertex"]:
+        raise SystemExit(f"{path}: the first element is not 'vertex'")
+    names = [name for name, _ in props]
+    if not all(axis in names for axis in "xyz") or len(set(names)) != len(names):
+        raise SystemExit(f"{path}: the vertex element has no x, y, z (properties: {' '.join(names)})")
+    if fmt == ["ascii"]:
+        tok = body.split()
+        if len(tok) < count * len(props):
+            raise SystemExit(f"{path}: truncated")
+        try:
+            table = np.array(tok[:count * len(props)], dtype=np.float64).reshape(count, len(props))
+        except ValueError:
+            raise SystemExit(f"{path}: a vertex line holds something that is not a number")
+        return np.ascontiguousarray(np.stack([table[:, names.index(axis)] for axis in "xyz"], axis=1).astype(np.float32))
+    vertex = np.dtype([(name, "<" + dt) for name, dt in props])
+    if len(body) < vertex.itemsize * count:
+        raise SystemExit(f"{path}: truncated")
+    rec = np.frombuffer(body[:vertex.itemsize * count], dtype=vertex)
+    return np.ascontiguousarray(np.stack([rec["x"], rec["y"], rec["z"]], axis=1).astype(np.float32))
+
+
 # ------------------------------------------------------------------------------------------------------------ depth PNG
 def write_depth_png(path, depth_u16):
     """A uint16 [h,w] depth map as a 16-bit single-channel PNG."""

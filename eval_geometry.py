@@ -1,0 +1,10 @@
+#!/usr/bin/env python3
+"""eval_geometry.py -- score a reconstructed cloud or mesh against a ground-truth cloud: precision, recall and F-score per distance
+threshold, the nearest-neighbour distances on the GPU (acezero_amd/cli.py, acezero_amd/geometry.py):
+eval_geometry.py RECONSTRUCTION.ply GROUND_TRUTH.ply --thresholds 0.01 0.02 0.05 [--transform T.txt] [--output_json scores.json]"""
+import sys
+
+from acezero_amd.cli import eval_geometry_main
+
+if __name__ == "__main__":
+    sys.exit(eval_geometry_main())

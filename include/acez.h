@@ -983,6 +983,48 @@ int acez_mvs_select(const uint16_t* d_volume, const uint32_t* d_s, int64_t n_vol
                     int n_frames, int ref, float z_near, float z_far, int planes, int uniqueness, float* d_out_depth, int32_t* d_out_cost,
                     int32_t* d_out_plane, void* stream);
 
+/* =====================================================================================================
+ * N. Distances between two point clouds: uniform grid, nearest neighbour within a radius, voxel means (eval_geometry.py)
+ * =====================================================================================================
+ * Three stateless entry points that allocate nothing; every buffer is the caller's. Points are float32 [count][3]. All float
+ * arithmetic below is fp32, round to nearest, one rounding per operation in the order written (the unit is built without
+ * contraction), division is IEEE division. tests/geometry_restated.py restates all of it in numpy.
+ *
+ * GRID. origin (ox, oy, oz), cell edge c, dimensions nx, ny, nz, each 1 .. 1024, nx * ny * nz <= 2^24. A point's cell on an axis is
+ * floor((x - ox) / c); its linear cell is (k * ny + j) * nx + i (x fastest).
+ *
+ * CELLS (acez_geom_cells). d_out_cells int32 [n]: the linear cell of every point, or -1 if a coordinate is not finite or a cell
+ * index is outside 0 .. n_axis - 1. The caller sorts by it (stably) and builds `cell_start` int32 [cells + 1], element v = the number
+ * of sorted points in cells < v: plumbing, not part of this library.
+ *
+ * NEAREST (acez_geom_nearest). d_ref: the m reference points SORTED BY CELL (none with cell -1), d_ref_index int32 [m] their original
+ * indices, d_cell_start as above; d_query: n points in any order. Per query (qx, qy, qz), over ALL reference points (px, py, pz):
+ *   dx = qx - px (dy, dz alike),  d2 = (dx * dx + dy * dy) + dz * dz
+ *   d_out_d2 = the smallest d2 with d2 <= radius * radius (the product in fp32), d_out_index = the smallest ORIGINAL index among the
+ *   points that attain it; +inf and -1 if there is none. A query with a non-finite coordinate has none.
+ * That is the whole contract: the result does not depend on the grid or on the order inside a cell, it is the brute-force scan's.
+ * The search visits the 3 x 3 x 3 cells around the query's cell, the query's cell indices clamped to -1 .. n_axis (queries outside
+ * the box are legal). It is complete because the call refuses c < radius * (1 + 2^-10) (product in fp32): with that margin and at
+ * most 1024 cells per axis, the two roundings of (x - ox) / c cannot put a reference that passes d2 <= radius^2 two cells away
+ * (DESIGN.md section 4l has the argument). d_cell_start is device data that cannot be checked here: the kernel clamps every range
+ * it forms to [0, m], so a malformed table gives wrong numbers, never a read out of bounds. Queries ordered by their own cell run
+ * fastest (a workgroup whose queries lie in one or two cells stages the neighbouring ranges in LDS); any order gives the same bits.
+ *
+ * VOXEL MEANS (acez_geom_voxel_means). d_points: n points sorted stably by voxel; d_segment_start int32 [segments + 1], ascending:
+ * segment v is the points start[v] .. start[v + 1] - 1 (clamped to [0, n]). d_out_means float32 [segments][3]: per component the
+ * sequential sum in array order, from 0.0f, divided by float(count).
+ *
+ * Asynchronous on `stream`. ACEZ_ERR_INVALID, before anything is launched, for: a null pointer (an array whose count is 0 may be
+ * null), a negative count or one >= 2^31, a dimension outside 1 .. 1024 or more than 2^24 cells, a non-finite origin, c or radius
+ * not finite or not > 0, c < radius * (1 + 2^-10). */
+int acez_geom_cells(const float* d_points, int64_t n, float ox, float oy, float oz, float cell, int nx, int ny, int nz,
+                    int32_t* d_out_cells, void* stream);
+int acez_geom_nearest(const float* d_ref, const int32_t* d_ref_index, const int32_t* d_cell_start, int64_t m, float ox, float oy, float oz,
+                      float cell, int nx, int ny, int nz, const float* d_query, int64_t n, float radius, float* d_out_d2,
+                      int32_t* d_out_index, void* stream);
+int acez_geom_voxel_means(const float* d_points, int64_t n, const int32_t* d_segment_start, int64_t segments, float* d_out_means,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
