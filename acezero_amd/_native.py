@@ -225,6 +225,11 @@ SYMBOLS = {
     "acez_geom_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
                                     C.c_int, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acez_geom_voxel_means": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "acez_geom_icp_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                           C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "acez_geom_icp_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

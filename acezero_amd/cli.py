@@ -1209,6 +1209,14 @@ def eval_geometry_parser():
                                                                    "to the pose file's images by alphabetical order)")
     p.add_argument("--estimate_alignment_conf_threshold", type=float, default=500, help="only poses above this confidence enter the alignment")
     p.add_argument("--seed", type=int, default=DEFAULT_SEED, help="key of the alignment's stream of RANSAC samples")
+    p.add_argument("--icp", type=_strtobool, default=False, help="refine the alignment (--transform, the pose pair, or the identity) by "
+                                                                 "ICP on the GPU before scoring, coarse to fine")
+    p.add_argument("--icp_distances", type=float, nargs="+", default=None, help="correspondence radius of every ICP stage in metres; "
+                                                                                "default: 4, 2 and 1 times the search radius")
+    p.add_argument("--icp_voxel_sizes", type=float, nargs="+", default=None, help="downsample both clouds to this voxel edge in every ICP "
+                                                                                  "stage: one value per stage")
+    p.add_argument("--icp_max_iterations", type=int, default=30, help="iterations per ICP stage")
+    p.add_argument("--icp_scale", type=_strtobool, default=False, help="let ICP estimate a scale factor as well")
     p.add_argument("--output_json", type=Path, default=None, help="write the numbers to this file")
     return p
 
@@ -1233,6 +1241,18 @@ def eval_geometry_main(argv=None):
         value = getattr(opt, name)
         if value is not None and not (math.isfinite(value) and value > 0):
             raise SystemExit(f"--{name} must be positive")
+    icp_distances = None
+    if opt.icp:
+        radius = max(opt.thresholds) if opt.max_distance is None else opt.max_distance
+        icp_distances = [4 * radius, 2 * radius, radius] if opt.icp_distances is None else opt.icp_distances
+        if any(not (math.isfinite(d) and d > 0) for d in icp_distances):
+            raise SystemExit("--icp_distances must be positive")
+        if opt.icp_voxel_sizes is not None and len(opt.icp_voxel_sizes) != len(icp_distances):
+            raise SystemExit(f"--icp_voxel_sizes has {len(opt.icp_voxel_sizes)} values for {len(icp_distances)} ICP stages: give one per stage")
+        if opt.icp_voxel_sizes is not None and any(not (math.isfinite(v) and v > 0) for v in opt.icp_voxel_sizes):
+            raise SystemExit("--icp_voxel_sizes must be positive")
+        if opt.icp_max_iterations < 1:
+            raise SystemExit("--icp_max_iterations must be at least 1")
     rec, gt = read_ply_points(opt.reconstruction), read_ply_points(opt.ground_truth)
     log.info(f"Read {len(rec)} points from {opt.reconstruction} and {len(gt)} from {opt.ground_truth}.")
     import torch
@@ -1260,8 +1280,17 @@ def eval_geometry_main(argv=None):
                  f"{res['median_r_deg']:.2f}deg, {res['median_t_cm']:.1f}cm.")
     t0 = time.perf_counter()
     try:
-        res = geometry.evaluate_geometry(torch.from_numpy(rec).cuda(), torch.from_numpy(gt).cuda(), opt.thresholds, transform=transform,
-                                         voxel=opt.voxel_size, crop=opt.crop, max_distance=opt.max_distance)
+        rec_d, gt_d = torch.from_numpy(rec).cuda(), torch.from_numpy(gt).cuda()
+        if opt.icp:
+            transform_initial = transform
+            transform, stages = geometry.refine_alignment(rec_d, gt_d, transform, distances=icp_distances, voxels=opt.icp_voxel_sizes,
+                                                          max_iterations=opt.icp_max_iterations, with_scale=opt.icp_scale)
+            for stage in stages:
+                log.info(f"ICP stage at {stage['distance']} m: {stage['iterations']} iterations, {stage['status']}"
+                         + (", the alignment before it kept" if stage["kept_previous"] else "")
+                         + (f", fitness {stage['fitness'][-1] * 100:.2f}%, rmse {stage['rmse'][-1] * 1000:.3f} mm" if stage["iterations"] else ""))
+        res = geometry.evaluate_geometry(rec_d, gt_d, opt.thresholds, transform=transform, voxel=opt.voxel_size, crop=opt.crop,
+                                         max_distance=opt.max_distance)
     except ValueError as e:
         raise SystemExit(str(e))
     t_device = time.perf_counter() - t0
@@ -1270,6 +1299,11 @@ def eval_geometry_main(argv=None):
     log.info(f"Upload + kernels + download {t_device:.2f} s.")
     if opt.output_json is not None:
         res["transform"] = None if transform is None else [[float(x) for x in row] for row in transform]
+        if opt.icp:
+            res["transform_initial"] = None if transform_initial is None else [[float(x) for x in row] for row in transform_initial]
+            # a stage without correspondences has rmse = sqrt(0 / 0): null in the file, which stays strict JSON
+            res["icp"] = [{k: [x if math.isfinite(x) else None for x in v] if isinstance(v, list) else v
+                           for k, v in stage.items() if k != "transforms"} for stage in stages]
         with open(opt.output_json, "w") as f:
             json.dump(res, f, indent=1, sort_keys=True)
             f.write("\n")

@@ -1,5 +1,6 @@
 // geometry_api.hip -- nearest-neighbour distances between two point clouds on a uniform grid, and the voxel downsample
-// (include/acez.h section N: acez_geom_cells, acez_geom_nearest, acez_geom_voxel_means). eval_geometry.py.
+// (include/acez.h section N: acez_geom_cells, acez_geom_nearest, acez_geom_voxel_means), and the ICP loop built on the search
+// (acez_geom_icp_accumulate, acez_geom_icp_update). eval_geometry.py.
 //
 // The header's section N is the definition: every float operation below is written in its order, the unit is built with
 // -ffp-contract=off, and tests/geometry_restated.py restates it in numpy float32 for the bit-for-bit comparison.
@@ -14,6 +15,10 @@
 //              references within R). Otherwise (queries scattered over many sparse cells) every lane walks the nine ranges of its
 //              own 3 x 3 x 3 cells through L2. Both forms give the same bits.
 // voxel_means  one lane per segment, a sequential sum in array order.
+// icp          ACCUMULATE is the nearest kernel with the query computed from the source point and the device-resident transform, and
+//              with the 18 fp64 moments of the lane's correspondence reduced per workgroup in a fixed order (one search_nearest for
+//              both kernels); UPDATE is one workgroup that sums the workgroups' rows and runs the solve of icp_solve.h. Both return at
+//              once when the state says the loop has stopped, so a whole stage is enqueued without a host round trip.
 // No atomics, no communication between workgroups, plain loads and stores. Every range read from the cell table is clamped to
 // [0, m], so every loop is bounded by m and a malformed table cannot cause a read out of bounds.
 #include <limits.h>
@@ -21,8 +26,11 @@
 #include <stdint.h>
 
 #include "acez_common.h"
+#include "icp_solve.h"
 
 namespace {
+
+using namespace acez;
 
 constexpr int GE_THREADS = 256;     // cells, voxel means
 constexpr int GN_THREADS = 256;     // nearest: queries per workgroup
@@ -56,17 +64,22 @@ __global__ void __launch_bounds__(GE_THREADS) geom_cells_kernel(const float* __r
   out[p] = ok ? (k * g.ny + j) * g.nx + i : -1;
 }
 
+// The search of NEAREST for one lane's query (qx, qy, qz); `live` says whether the lane has one. Called by all GN_THREADS lanes of a
+// workgroup (it holds barriers). The winner's position in the sorted reference array comes along for the caller that wants its
+// coordinates (ICP); the nearest kernel leaves it unused.
 struct Best {
   float d2;
   int idx;
+  int pos;
 };
 
-__device__ inline void consider(float qx, float qy, float qz, float px, float py, float pz, int idx, float r2, Best& b) {
+__device__ __forceinline__ void consider(float qx, float qy, float qz, float px, float py, float pz, int idx, int pos, float r2, Best& b) {
   const float dx = qx - px, dy = qy - py, dz = qz - pz;
   const float d2 = (dx * dx + dy * dy) + dz * dz;
   if (d2 <= r2 && (d2 < b.d2 || (d2 == b.d2 && idx < b.idx))) {
     b.d2 = d2;
     b.idx = idx;
+    b.pos = pos;
   }
 }
 
@@ -75,23 +88,15 @@ __device__ inline int wave_min(int v) {
   return v;
 }
 
-__global__ void __launch_bounds__(GN_THREADS) geom_nearest_kernel(const float* __restrict__ ref, const int32_t* __restrict__ ref_index,
-                                                                   const int32_t* __restrict__ cell_start, int m, Grid g,
-                                                                   const float* __restrict__ query, int64_t n, float r2,
-                                                                   float* __restrict__ out_d2, int32_t* __restrict__ out_index, int plain) {
+__device__ __forceinline__ Best search_nearest(const float* __restrict__ ref, const int32_t* __restrict__ ref_index,
+                                               const int32_t* __restrict__ cell_start, int m, const Grid& g, float qx, float qy, float qz,
+                                               bool live, float r2, int plain) {
   __shared__ float4 s_pts[GE_CHUNK];
   __shared__ int s_red[GN_WAVES][6];
   __shared__ int s_lo[GE_MAX_ROWS], s_hi[GE_MAX_ROWS];
   const int t = threadIdx.x;
-  const int64_t q = (int64_t)blockIdx.x * GN_THREADS + t;
-  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-  bool live = false;
-  if (q < n) {
-    qx = query[3 * q], qy = query[3 * q + 1], qz = query[3 * q + 2];
-    live = isfinite(qx) && isfinite(qy) && isfinite(qz);
-  }
   const int ci = axis_cell(qx, g.ox, g.c, g.nx), cj = axis_cell(qy, g.oy, g.c, g.ny), ck = axis_cell(qz, g.oz, g.c, g.nz);
-  Best best{INFINITY, INT_MAX};
+  Best best{INFINITY, INT_MAX, 0};
 
   // the box of the workgroup's live query cells: min and max per axis (max as the min of the negation)
   {
@@ -143,7 +148,7 @@ __global__ void __launch_bounds__(GN_THREADS) geom_nearest_kernel(const float* _
 #pragma unroll 4
           for (int e = 0; e < cnt; ++e) {
             const float4 pt = s_pts[e];
-            consider(qx, qy, qz, pt.x, pt.y, pt.z, __float_as_int(pt.w), r2, best);
+            consider(qx, qy, qz, pt.x, pt.y, pt.z, __float_as_int(pt.w), at + e, r2, best);
           }
       }
     }
@@ -156,12 +161,112 @@ __global__ void __launch_bounds__(GN_THREADS) geom_nearest_kernel(const float* _
         const int base = (k * g.ny + j) * g.nx;
         const int lo = clamp_m(cell_start[base + i0], m), hi = clamp_m(cell_start[base + i1 + 1], m);
 #pragma unroll 4
-        for (int64_t p = lo; p < hi; ++p) consider(qx, qy, qz, ref[3 * p], ref[3 * p + 1], ref[3 * p + 2], ref_index[p], r2, best);
+        for (int64_t p = lo; p < hi; ++p) consider(qx, qy, qz, ref[3 * p], ref[3 * p + 1], ref[3 * p + 2], ref_index[p], (int)p, r2, best);
       }
   }
+  return best;
+}
+
+__global__ void __launch_bounds__(GN_THREADS) geom_nearest_kernel(const float* __restrict__ ref, const int32_t* __restrict__ ref_index,
+                                                                   const int32_t* __restrict__ cell_start, int m, Grid g,
+                                                                   const float* __restrict__ query, int64_t n, float r2,
+                                                                   float* __restrict__ out_d2, int32_t* __restrict__ out_index, int plain) {
+  const int64_t q = (int64_t)blockIdx.x * GN_THREADS + threadIdx.x;
+  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+  bool live = false;
+  if (q < n) {
+    qx = query[3 * q], qy = query[3 * q + 1], qz = query[3 * q + 2];
+    live = isfinite(qx) && isfinite(qy) && isfinite(qz);
+  }
+  const Best best = search_nearest(ref, ref_index, cell_start, m, g, qx, qy, qz, live, r2, plain);
   if (q < n) {
     out_d2[q] = best.d2;
     out_index[q] = best.idx == INT_MAX ? -1 : best.idx;
+  }
+}
+
+// xor butterfly 32, 16, .. 1: every lane ends with the wavefront's sum, the same bits in all of them (a + b == b + a)
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_xor(v, s, 64);
+  return v;
+}
+
+// the ICP_TERMS values of every lane of the workgroup -> their sums: the butterfly per wavefront, then the wavefronts in ascending
+// order. Threads 0 .. ICP_TERMS - 1 return the sum of their own term, the others 0.
+__device__ __forceinline__ double block_sum_terms(const double (&v)[ICP_TERMS], double (*s_sum)[ICP_TERMS]) {
+  const int t = threadIdx.x;
+  for (int i = 0; i < ICP_TERMS; ++i) {
+    const double w = wave_sum(v[i]);
+    if ((t & 63) == 0) s_sum[t >> 6][i] = w;
+  }
+  __syncthreads();
+  double r = 0.0;
+  if (t < ICP_TERMS) {
+    r = s_sum[0][t];
+    for (int w = 1; w < GN_WAVES; ++w) r = r + s_sum[w][t];
+  }
+  return r;
+}
+
+// ACCUMULATE: one lane per source point. x' = T x in fp64 rounded once, the search of NEAREST on x', the 18 terms of the lane's
+// correspondence (zeros without one), one row of sums per workgroup.
+__global__ void __launch_bounds__(GN_THREADS) geom_icp_accumulate_kernel(const float* __restrict__ ref, const int32_t* __restrict__ ref_index,
+                                                                          const int32_t* __restrict__ cell_start, int m, Grid g,
+                                                                          const float* __restrict__ src, int64_t n, float r2, float px, float py,
+                                                                          float pz, const double* state, double* __restrict__ partials, int plain) {
+  __shared__ double s_sum[GN_WAVES][ICP_TERMS];
+  if (state[ICP_STATUS] != ICP_RUNNING) return;                   // the loop has stopped (uniform over the grid)
+  const int t = threadIdx.x;
+  const int64_t q = (int64_t)blockIdx.x * GN_THREADS + t;
+  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+  bool live = false;
+  if (q < n) {
+    const double x = src[3 * q], y = src[3 * q + 1], z = src[3 * q + 2];
+    qx = (float)(((state[0] * x + state[1] * y) + state[2] * z) + state[3]);
+    qy = (float)(((state[4] * x + state[5] * y) + state[6] * z) + state[7]);
+    qz = (float)(((state[8] * x + state[9] * y) + state[10] * z) + state[11]);
+    live = isfinite(qx) && isfinite(qy) && isfinite(qz);
+  }
+  const Best best = search_nearest(ref, ref_index, cell_start, m, g, qx, qy, qz, live, r2, plain);
+  double v[ICP_TERMS];
+  for (int i = 0; i < ICP_TERMS; ++i) v[i] = 0.0;
+  if (live && best.idx != INT_MAX) {                              // then 0 <= best.pos < m
+    const int64_t p = best.pos;
+    const double a[3] = {(double)qx - (double)px, (double)qy - (double)py, (double)qz - (double)pz};
+    const double b[3] = {(double)ref[3 * p] - (double)px, (double)ref[3 * p + 1] - (double)py, (double)ref[3 * p + 2] - (double)pz};
+    v[0] = 1.0;
+    for (int c = 0; c < 3; ++c) {
+      v[1 + c] = a[c];
+      v[4 + c] = b[c];
+      for (int r = 0; r < 3; ++r) v[7 + 3 * r + c] = b[r] * a[c];
+    }
+    v[16] = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2];
+    v[17] = (double)best.d2;
+  }
+  const double total = block_sum_terms(v, s_sum);
+  if (t < ICP_TERMS) partials[(int64_t)blockIdx.x * ICP_TERMS + t] = total;
+}
+
+// UPDATE: one workgroup. Thread t sums the partial rows t, t + 256, .. in ascending order, the workgroup's sums as in ACCUMULATE,
+// thread 0 runs icp_update (icp_solve.h) on the totals.
+__global__ void __launch_bounds__(GN_THREADS) geom_icp_update_kernel(const double* __restrict__ partials, int64_t rows, int64_t n, float px,
+                                                                      float py, float pz, int with_scale, double rel_fitness, double rel_rmse,
+                                                                      int max_iterations, double* state, double* history) {
+  __shared__ double s_sum[GN_WAVES][ICP_TERMS];
+  __shared__ double s_total[ICP_TERMS];
+  const double iteration = state[ICP_ITERATIONS];
+  if (state[ICP_STATUS] != ICP_RUNNING || !(iteration >= 0.0 && iteration < (double)max_iterations)) return;   // uniform
+  const int t = threadIdx.x;
+  double v[ICP_TERMS];
+  for (int i = 0; i < ICP_TERMS; ++i) v[i] = 0.0;
+  for (int64_t r = t; r < rows; r += GN_THREADS)
+    for (int i = 0; i < ICP_TERMS; ++i) v[i] = v[i] + partials[r * ICP_TERMS + i];
+  const double total = block_sum_terms(v, s_sum);
+  if (t < ICP_TERMS) s_total[t] = total;
+  __syncthreads();
+  if (t == 0) {
+    const double pivot[3] = {(double)px, (double)py, (double)pz};
+    icp_update(state, s_total, n, pivot, with_scale, rel_fitness, rel_rmse, history);
   }
 }
 
@@ -235,6 +340,39 @@ extern "C" int acez_geom_voxel_means(const float* d_points, int64_t n, const int
   if (segments == 0) return ACEZ_OK;
   hipLaunchKernelGGL(geom_voxel_means_kernel, dim3(blocks_for(segments)), dim3(GE_THREADS), 0, (hipStream_t)stream, d_points, n,
                      d_segment_start, segments, d_out_means);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}
+
+extern "C" int acez_geom_icp_accumulate(const float* d_ref, const int32_t* d_ref_index, const int32_t* d_cell_start, int64_t m, float ox,
+                                        float oy, float oz, float cell, int nx, int ny, int nz, const float* d_src, int64_t n, float radius,
+                                        float px, float py, float pz, const double* d_state, double* d_partials, void* stream) {
+  ACEZ_REQUIRE(m >= 0 && m <= GE_MAX_COUNT && n >= 1 && n <= GE_MAX_COUNT, "point count out of range (references 0 .. 2^31 - 1, sources 1 .. 2^31 - 1)");
+  ACEZ_REQUIRE(d_cell_start && (m == 0 || (d_ref && d_ref_index)) && d_src && d_state && d_partials, "null pointer");
+  GE_REQUIRE_GRID();
+  ACEZ_REQUIRE(isfinite(radius) && radius > 0.0f, "the radius must be positive and finite");
+  ACEZ_REQUIRE(!(cell < radius * 1.0009765625f), "the cell edge must be at least radius * (1 + 2^-10)");
+  ACEZ_REQUIRE(isfinite(px) && isfinite(py) && isfinite(pz), "non-finite pivot");
+  if (int rc = acez::require_device("the ICP correspondence search runs on a gfx950 GPU")) return rc;
+  const Grid g{ox, oy, oz, cell, nx, ny, nz};
+  const int plain = ACEZ_DIAG_ENV("ACEZ_GEOM_PLAIN") != nullptr;    // diagnostics build: every workgroup takes the per-lane form
+  hipLaunchKernelGGL(geom_icp_accumulate_kernel, dim3((unsigned)((n + GN_THREADS - 1) / GN_THREADS)), dim3(GN_THREADS), 0, (hipStream_t)stream,
+                     d_ref, d_ref_index, d_cell_start, (int)m, g, d_src, n, radius * radius, px, py, pz, d_state, d_partials, plain);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}
+
+extern "C" int acez_geom_icp_update(const double* d_partials, int64_t n, float px, float py, float pz, int with_scale, double rel_fitness,
+                                    double rel_rmse, int max_iterations, double* d_state, double* d_history, void* stream) {
+  ACEZ_REQUIRE(n >= 1 && n <= GE_MAX_COUNT, "point count out of range (sources 1 .. 2^31 - 1)");
+  ACEZ_REQUIRE(d_partials && d_state && d_history, "null pointer");
+  ACEZ_REQUIRE(isfinite(px) && isfinite(py) && isfinite(pz), "non-finite pivot");
+  ACEZ_REQUIRE(max_iterations >= 1, "max_iterations must be at least 1");
+  ACEZ_REQUIRE(isfinite(rel_fitness) && rel_fitness >= 0.0 && isfinite(rel_rmse) && rel_rmse >= 0.0,
+               "the tolerances must be finite and not negative");
+  if (int rc = acez::require_device("the ICP update runs on a gfx950 GPU")) return rc;
+  hipLaunchKernelGGL(geom_icp_update_kernel, dim3(1), dim3(GN_THREADS), 0, (hipStream_t)stream, d_partials, (n + GN_THREADS - 1) / GN_THREADS, n,
+                     px, py, pz, with_scale != 0, rel_fitness, rel_rmse, max_iterations, d_state, d_history);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
 }

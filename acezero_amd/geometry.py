@@ -5,9 +5,14 @@ command line).
     d2, index = nearest_distances(query, ref, radius=0.05)            # squared distance and index of the nearest ref within 5 cm
     small = voxel_downsample(points, voxel=0.01)
     res = evaluate_geometry(rec, gt, [0.01, 0.02, 0.05], transform=T)  # dict: precision, recall, fscore per threshold, ...
+    T, info = icp_stage(src, tgt, radius=0.05)                         # one ICP stage from the identity, the loop on the device
+    T, stages = refine_alignment(rec, gt, T0, distances=[0.2, 0.1, 0.05])  # coarse to fine, from the alignment T0
 
-The clouds live in HBM; the grid cells, the nearest-neighbour search and the voxel means are HIP kernels
-(acezero_amd/csrc/geometry_api.hip), sorting and prefix sums are torch's. There is no CPU fallback."""
+The clouds live in HBM; the grid cells, the nearest-neighbour search, the voxel means and the ICP loop (the search with the
+correspondence moments, the Umeyama solve) are HIP kernels (acezero_amd/csrc/geometry_api.hip), sorting and prefix sums are torch's.
+There is no CPU fallback."""
+import collections
+
 import numpy as np
 import torch
 
@@ -58,19 +63,17 @@ def point_cells(points, origin, c, dims):
     return out
 
 
-def nearest_distances(query, ref, radius, cell=None):
-    """For every query point [n,3] the nearest reference point [m,3] within `radius`: (d2 float32 [n], index int32 [n]), the squared
-    distance (dx * dx + dy * dy) + dz * dz in fp32 and the reference's row; +inf and -1 where no reference is within the radius (or
-    the query is not finite). Among references at the same d2 the lowest row wins: the result is that of a brute-force scan, bit for
-    bit, whatever the grid. The grid covers the reference's bounding box with cells of radius * (1 + 2^-10), enlarged until it has
-    at most 1024 cells per axis and 2^24 in all; `cell` sets the edge instead (tests)."""
-    query, ref = _points(query, "nearest_distances"), _points(ref, "nearest_distances")
-    if ref.device != query.device:
-        raise ValueError("query and ref must be on the same device")
-    r = np.float32(radius)
-    if not (np.isfinite(r) and r > 0):
-        raise ValueError(f"radius must be positive and finite, got {radius}")
-    dev, n = query.device, query.shape[0]
+Grid = collections.namedtuple("Grid", "ref_sorted ref_index cell_start origin cell dims hi")
+
+
+def build_grid(ref, radius, cell=None):
+    """The grid of section N over the reference cloud (a float32 [m,3] device tensor): Grid(ref_sorted, ref_index, cell_start, origin,
+    cell, dims, hi) -- the references sorted by cell (stable; those that are not finite dropped), their original rows (int32), the
+    first sorted position of every cell (int32 [cells + 1]), the box's minimum (float32 [3] host array), the cell edge (float32), the
+    cells per axis, and the box's maximum. The cell edge is radius * (1 + 2^-10), enlarged until the grid has at most 1024 cells per
+    axis and 2^24 in all; `cell` sets the edge instead."""
+    ref, r = _points(ref, "build_grid"), _radius(radius)
+    dev = ref.device
     box = _bounds(ref)
     lo, hi = box if box is not None else (np.zeros(3, np.float32), np.zeros(3, np.float32))
     with np.errstate(over="ignore"):
@@ -95,21 +98,132 @@ def nearest_distances(query, ref, radius, cell=None):
     cell_start = torch.zeros(n_cells + 1, dtype=torch.int32, device=dev)
     if rows.shape[0]:
         cell_start[1:] = torch.cumsum(torch.bincount(order.values.long(), minlength=n_cells), 0).to(torch.int32)
+    return Grid(ref_sorted, ref_index, cell_start, lo, c, dims, hi)
+
+
+def order_by_cell(points, grid):
+    """int64 [n]: the stable order of the points by the cell of their nearest point of the grid's box, so that a wavefront's lanes
+    share a neighbourhood."""
+    points = _points(points, "order_by_cell")
+    dev = points.device
+    t_lo, t_hi = torch.from_numpy(grid.origin).to(dev), torch.from_numpy(grid.hi).to(dev)
+    key = point_cells(torch.minimum(torch.maximum(points, t_lo), t_hi), grid.origin, grid.cell, grid.dims)
+    return torch.sort(key, stable=True).indices
+
+
+def _radius(radius):
+    r = np.float32(radius)
+    if not (np.isfinite(r) and r > 0):
+        raise ValueError(f"radius must be positive and finite, got {radius}")
+    return r
+
+
+def nearest_distances(query, ref, radius, cell=None):
+    """For every query point [n,3] the nearest reference point [m,3] within `radius`: (d2 float32 [n], index int32 [n]), the squared
+    distance (dx * dx + dy * dy) + dz * dz in fp32 and the reference's row; +inf and -1 where no reference is within the radius (or
+    the query is not finite). Among references at the same d2 the lowest row wins: the result is that of a brute-force scan, bit for
+    bit, whatever the grid. The grid covers the reference's bounding box with cells of radius * (1 + 2^-10), enlarged until it has
+    at most 1024 cells per axis and 2^24 in all; `cell` sets the edge instead (tests)."""
+    query, ref = _points(query, "nearest_distances"), _points(ref, "nearest_distances")
+    if ref.device != query.device:
+        raise ValueError("query and ref must be on the same device")
+    r = _radius(radius)
+    dev, n = query.device, query.shape[0]
+    g = build_grid(ref, r, cell)
+    lo, c, dims = g.origin, g.cell, g.dims
     # queries ordered by the cell of their nearest point of the box, so that a wavefront's lanes share a neighbourhood
-    t_lo, t_hi = torch.from_numpy(lo).to(dev), torch.from_numpy(hi).to(dev)
-    key = point_cells(torch.minimum(torch.maximum(query, t_lo), t_hi), lo, c, dims)
-    q_order = torch.sort(key, stable=True).indices
+    q_order = order_by_cell(query, g)
     q_sorted = query[q_order].contiguous()
     d2_sorted = torch.empty(n, dtype=torch.float32, device=dev)
     index_sorted = torch.empty(n, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        N.check(N.lib().acez_geom_nearest(_ptr(ref_sorted), _ptr(ref_index), _ptr(cell_start), ref_sorted.shape[0], float(lo[0]), float(lo[1]),
-                                          float(lo[2]), float(c), dims[0], dims[1], dims[2], _ptr(q_sorted), n, float(r), _ptr(d2_sorted),
-                                          _ptr(index_sorted), _stream()))
+        N.check(N.lib().acez_geom_nearest(_ptr(g.ref_sorted), _ptr(g.ref_index), _ptr(g.cell_start), g.ref_sorted.shape[0], float(lo[0]),
+                                          float(lo[1]), float(lo[2]), float(c), dims[0], dims[1], dims[2], _ptr(q_sorted), n, float(r),
+                                          _ptr(d2_sorted), _ptr(index_sorted), _stream()))
     d2, index = torch.empty_like(d2_sorted), torch.empty_like(index_sorted)
     d2[q_order] = d2_sorted
     index[q_order] = index_sorted
     return d2, index
+
+
+ICP_STATUS = {0: "max_iterations", 1: "converged", 2: "degenerate"}     # state[12]; a loop still running after the last pair ran out
+
+
+def icp_stage(src, tgt, radius, *, max_iterations=30, with_scale=False, rel_fitness=1e-6, rel_rmse=1e-6, cell=None):
+    """One ICP stage from the identity (include/acez.h section N, ICP): the similarity T (4 x 4 float64) that brings the source cloud
+    [n,3] onto the target cloud [m,3] by iterated closest points within `radius`, rigid or with_scale, and an info dict: status
+    ("converged": fitness and rmse both moved less than rel_fitness / rel_rmse; "max_iterations"; "degenerate": fewer than three
+    or collinear correspondences, T is then the last well-determined one), iterations, and per iteration fitness (the share of
+    sources with a target within the radius), rmse (over those), count, sum_d2 and transforms (the T the iteration searched under).
+    The target grid is built once, the sources are ordered by cell once, and the max_iterations ACCUMULATE + UPDATE launches are
+    enqueued back to back on the current stream: the loop's state lives on the device, launches after it has stopped return at
+    once, and the host reads state and history back once."""
+    src, tgt = _points(src, "icp_stage"), _points(tgt, "icp_stage")
+    if src.device != tgt.device:
+        raise ValueError("src and tgt must be on the same device")
+    r = _radius(radius)
+    max_iterations = int(max_iterations)
+    if max_iterations < 1:
+        raise ValueError("max_iterations must be at least 1")
+    if not all(np.isfinite(v) and v >= 0 for v in (rel_fitness, rel_rmse)):
+        raise ValueError("rel_fitness and rel_rmse must be finite and not negative")
+    dev, n = src.device, src.shape[0]
+    if n == 0:
+        raise ValueError("the source cloud is empty")
+    g = build_grid(tgt, r, cell)
+    lo, c, dims = g.origin, g.cell, g.dims
+    pivot = (g.origin + g.hi) * np.float32(0.5)
+    pivot = [float(v) if np.isfinite(v) else 0.0 for v in pivot]
+    src_sorted = src[order_by_cell(src, g)].contiguous()
+    state = torch.zeros(34, dtype=torch.float64, device=dev)
+    state[[0, 5, 10]] = 1.0
+    partials = torch.empty(((n + 255) // 256, 18), dtype=torch.float64, device=dev)
+    history = torch.zeros((max_iterations, 16), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        lib, stream = N.lib(), _stream()
+        for _ in range(max_iterations):                            # no synchronisation in between
+            N.check(lib.acez_geom_icp_accumulate(_ptr(g.ref_sorted), _ptr(g.ref_index), _ptr(g.cell_start), g.ref_sorted.shape[0], float(lo[0]),
+                                                 float(lo[1]), float(lo[2]), float(c), dims[0], dims[1], dims[2], _ptr(src_sorted), n, float(r),
+                                                 pivot[0], pivot[1], pivot[2], _ptr(state), _ptr(partials), stream))
+            N.check(lib.acez_geom_icp_update(_ptr(partials), n, pivot[0], pivot[1], pivot[2], int(bool(with_scale)), float(rel_fitness),
+                                             float(rel_rmse), max_iterations, _ptr(state), _ptr(history), stream))
+    both = torch.cat([state, history.reshape(-1)]).cpu().numpy()  # the one read-back
+    state_h, history_h = both[:34], both[34:].reshape(max_iterations, 16)
+    done = int(state_h[13])
+    T = np.eye(4)
+    T[:3] = state_h[:12].reshape(3, 4)
+    info = {"status": ICP_STATUS[int(state_h[12])], "iterations": done, "fitness": [float(v) for v in history_h[:done, 14]],
+            "rmse": [float(v) for v in history_h[:done, 15]], "count": [int(v) for v in history_h[:done, 12]],
+            "sum_d2": [float(v) for v in history_h[:done, 13]],
+            "transforms": [np.vstack([history_h[k, :12].reshape(3, 4), [0.0, 0.0, 0.0, 1.0]]) for k in range(done)]}
+    return T, info
+
+
+def refine_alignment(rec, gt, transform=None, *, distances, voxels=None, max_iterations=30, with_scale=False):
+    """Refine the similarity `transform` (4 x 4, reconstruction -> ground truth; None: the identity) by ICP, coarse to fine as Tanks
+    and Temples does after its trajectory alignment: one icp_stage per search radius of `distances`, on the clouds downsampled to
+    voxels[k] where that is given. Stage k takes apply_similarity(rec, T) under the alignment found so far, runs from the identity
+    and composes T <- T_stage T. A degenerate stage keeps the alignment it started with (its info says "kept_previous": True).
+    Returns (T 4 x 4 float64, the list of stage infos: icp_stage's, plus distance, voxel, kept_previous)."""
+    rec, gt = _points(rec, "refine_alignment"), _points(gt, "refine_alignment")
+    distances = [float(d) for d in distances]
+    if not distances or not all(np.isfinite(d) and d > 0 for d in distances):
+        raise ValueError("distances must be positive numbers, at least one")
+    voxels = [None] * len(distances) if voxels is None else [None if v is None else float(v) for v in voxels]
+    if len(voxels) != len(distances):
+        raise ValueError(f"{len(voxels)} voxel sizes for {len(distances)} distances: one per stage")
+    T = np.eye(4) if transform is None else np.array(transform, np.float64).reshape(4, 4)
+    infos = []
+    for d, v in zip(distances, voxels):
+        moved, target = apply_similarity(rec, T), gt
+        if v is not None:
+            moved, target = voxel_downsample(moved, v), voxel_downsample(target, v)
+        T_stage, info = icp_stage(moved, target, d, max_iterations=max_iterations, with_scale=with_scale)
+        info.update(distance=d, voxel=v, kept_previous=info["status"] == "degenerate")
+        if not info["kept_previous"]:
+            T = T_stage @ T
+        infos.append(info)
+    return T, infos
 
 
 def voxel_downsample(points, voxel):
@@ -234,4 +348,4 @@ def log_lines(res):
 
 
 __all__ = ["nearest_distances", "voxel_downsample", "evaluate_geometry", "apply_similarity", "crop_to_box", "scores", "fscore",
-           "log_lines", "grid_dims", "point_cells"]
+           "log_lines", "grid_dims", "point_cells", "build_grid", "order_by_cell", "icp_stage", "refine_alignment"]

@@ -986,7 +986,8 @@ int acez_mvs_select(const uint16_t* d_volume, const uint32_t* d_s, int64_t n_vol
 /* =====================================================================================================
  * N. Distances between two point clouds: uniform grid, nearest neighbour within a radius, voxel means (eval_geometry.py)
  * =====================================================================================================
- * Three stateless entry points that allocate nothing; every buffer is the caller's. Points are float32 [count][3]. All float
+ * Three stateless entry points, and the two of the ICP loop at the end of the section whose only state is a caller-owned device
+ * block; none allocates anything, every buffer is the caller's. Points are float32 [count][3]. All float
  * arithmetic below is fp32, round to nearest, one rounding per operation in the order written (the unit is built without
  * contraction), division is IEEE division. tests/geometry_restated.py restates all of it in numpy.
  *
@@ -1024,6 +1025,48 @@ int acez_geom_nearest(const float* d_ref, const int32_t* d_ref_index, const int3
                       int32_t* d_out_index, void* stream);
 int acez_geom_voxel_means(const float* d_points, int64_t n, const int32_t* d_segment_start, int64_t segments, float* d_out_means,
                           void* stream);
+
+/* ICP: refine a similarity between two clouds by iterated closest points, the loop resident on the device (DESIGN.md section 4m;
+ * acezero_amd.geometry.icp_stage enqueues max_iterations ACCUMULATE + UPDATE pairs and reads the result back once;
+ * tests/icp_restated.py restates both in numpy).
+ *
+ * STATE. d_state: 34 doubles owned by the caller. [0..11] the current transform T, rows 0..2 of the 4 x 4, row-major; [12] status:
+ * 0 running, 1 converged, 2 degenerate; [13] the number of records written; [14], [15] fitness and rmse of the previous record;
+ * [16..33] the 18 totals of the last UPDATE that ran. A stage starts from T (the identity, or any similarity), status 0, the rest 0.
+ *
+ * ACCUMULATE (acez_geom_icp_accumulate). The target grid exactly as NEAREST takes it; d_src: the n source points in their own frame;
+ * pivot (px, py, pz): any finite point, the host passes the centre of the target's box (it keeps the moments small). If status != 0
+ * the kernel returns at once. Otherwise, per source point (x, y, z), with T from the state:
+ *   x' = float(((T00 x + T01 y) + T02 z) + T03) in fp64, rounded to fp32 once (y', z' alike): geometry.apply_similarity's arithmetic
+ *   q  = the nearest target of x' within the radius under the NEAREST contract above (same d2, same tie rule), so the
+ *        correspondences are those of NEAREST on the transformed cloud, bit for bit; none if x' is not finite
+ *   a = (double)x' - (double)pivot, b = (double)q - (double)pivot, and the 18 terms, all fp64:
+ *     [0] 1   [1..3] a   [4..6] b   [7 + 3 r + c] b_r * a_c   [16] (ax * ax + ay * ay) + az * az   [17] (double)d2
+ *   A source without a correspondence contributes eighteen zeros.
+ * Reduction: source i is lane i % 64 of wavefront (i / 64) % 4 of workgroup i / 256 (lanes past n hold zeros). Per term: within a
+ * wavefront the xor butterfly v = v + v[lane ^ s] for s = 32, 16, 8, 4, 2, 1 (every lane ends with the same bits), then the
+ * workgroup's four wavefronts added in ascending order, (((w0 + w1) + w2) + w3). d_partials double [ceil(n / 256)][18]: one row per
+ * workgroup. No atomics: nothing depends on scheduling.
+ *
+ * UPDATE (acez_geom_icp_update). One workgroup of 256 threads. If status != 0, or [13] is not in 0 .. max_iterations - 1, it returns
+ * at once. Totals: thread t adds rows t, t + 256, t + 512, .. in ascending order from 0.0, per term; the 256 threads' sums are reduced
+ * as above (butterfly, then wavefronts ascending). Then, in this order (acezero_amd/csrc/icp_solve.h is the text):
+ *   count = total[0], fitness = count / n, rmse = sqrt(total[17] / count)
+ *   record [13] of d_history (16 doubles each: T (12), count, total[17], fitness, rmse) is written, [13] += 1, the totals are kept
+ *   (a) from the second record on: |fitness - previous| < rel_fitness and |rmse - previous| < rel_rmse -> status 1, T unchanged
+ *   (b) count < 3, a total that is not finite, or sigma1 <= 1e-12 * sigma0 of the covariance -> status 2, T unchanged
+ *   else Umeyama: C = S_ba - S_b S_a^T / count = U diag(sigma) V^T (csrc/svd3.h), R = U diag(1, 1, sign) V^T,
+ *     s = (sigma0 + sigma1 + sign * sigma2) / (S_aa - |S_a|^2 / count) with with_scale (a scale that is not positive and finite is
+ *     status 2), else 1; Delta(x') = s R (x' - pivot - S_a / count) + S_b / count + pivot; T <- Delta * T in fp64.
+ * d_history holds max_iterations records.
+ *
+ * Asynchronous on `stream`. ACEZ_ERR_INVALID, before anything is launched, for: what NEAREST refuses; n < 1; a null d_src, d_state,
+ * d_partials or d_history; a pivot that is not finite; max_iterations < 1; a tolerance that is negative or not finite. */
+int acez_geom_icp_accumulate(const float* d_ref, const int32_t* d_ref_index, const int32_t* d_cell_start, int64_t m, float ox, float oy,
+                             float oz, float cell, int nx, int ny, int nz, const float* d_src, int64_t n, float radius, float px, float py,
+                             float pz, const double* d_state, double* d_partials, void* stream);
+int acez_geom_icp_update(const double* d_partials, int64_t n, float px, float py, float pz, int with_scale, double rel_fitness,
+                         double rel_rmse, int max_iterations, double* d_state, double* d_history, void* stream);
 
 #ifdef __cplusplus
 }
