@@ -230,6 +230,12 @@ SYMBOLS = {
                                            C.c_void_p, C.c_void_p]),
     "acez_geom_icp_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "acez_geom_face_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_uint64, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "acez_geom_sample_faces": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "acez_geom_crop_polygon": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                         C.c_void_p]),
 }
 
 

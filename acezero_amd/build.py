@@ -18,7 +18,7 @@ STAMP = os.path.join(HERE, ".libacez.stamp")
 LIB_DIAG = os.path.join(HERE, "libacez_diag.so")
 STAMP_DIAG = os.path.join(HERE, ".libacez_diag.stamp")
 
-# translation unit -> extra flags.  The RANSAC (RGB and RGB-D), point-cloud, pose-evaluation, rendering, ingest, reprojection, fusion, stereo and cloud-distance units must not contract a*b+c into fma: their
+# translation unit -> extra flags.  The RANSAC (RGB and RGB-D), point-cloud, pose-evaluation, rendering, ingest, reprojection, fusion, stereo, cloud-distance and surface units must not contract a*b+c into fma: their
 # arithmetic is compared bit-for-bit with the CPU oracle (DESIGN.md "Determinism"); the ingest unit's host-side tables with Pillow's.
 UNITS = {
     "acez_common.hip": [],
@@ -37,6 +37,7 @@ UNITS = {
     "fusion_api.hip": ["-ffp-contract=off"],
     "mvs_api.hip": ["-ffp-contract=off"],
     "geometry_api.hip": ["-ffp-contract=off"],
+    "surface_api.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

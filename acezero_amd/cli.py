@@ -21,8 +21,8 @@ from pathlib import Path
 import numpy as np
 
 from . import DEFAULT_DTYPE
-from .formats import (match_poses, read_ace_pose_file, read_depth_png, read_ply_points, read_ply_vertices, write_depth_png, write_ply,
-                      write_pose_line)
+from .formats import (match_poses, read_ace_pose_file, read_crop_file, read_depth_png, read_ply_mesh, read_ply_points, read_ply_vertices,
+                      write_depth_png, write_ply, write_pose_line)
 
 _logger = logging.getLogger("acezero_amd")
 
@@ -1191,8 +1191,9 @@ def fuse_depth_main(argv=None):
 # -------------------------------------------------------------------------------------------------------- eval_geometry
 def eval_geometry_parser():
     from .evaluate import DEFAULT_SEED
-    p = argparse.ArgumentParser(description="Score a reconstructed point cloud or mesh (by its vertices) against a ground-truth cloud on "
-                                            "the GPU: precision, recall and F-score per distance threshold (the Tanks and Temples metric).",
+    p = argparse.ArgumentParser(description="Score a reconstructed point cloud or mesh (by its vertices, or with --sample_spacing by "
+                                            "samples of its surface) against a ground-truth cloud on the GPU: precision, recall and "
+                                            "F-score per distance threshold (the Tanks and Temples metric).",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("reconstruction", type=Path, help="reconstructed cloud or mesh (.ply, binary little-endian or ASCII)")
     p.add_argument("ground_truth", type=Path, help="ground-truth cloud (.ply)")
@@ -1217,6 +1218,16 @@ def eval_geometry_parser():
                                                                                   "stage: one value per stage")
     p.add_argument("--icp_max_iterations", type=int, default=30, help="iterations per ICP stage")
     p.add_argument("--icp_scale", type=_strtobool, default=False, help="let ICP estimate a scale factor as well")
+    p.add_argument("--sample_spacing", type=float, default=None, help="score the reconstruction, a mesh, by its surface instead of its "
+                                                                      "vertices: samples of its faces on the GPU, about this many metres "
+                                                                      "(of the ground truth's frame) apart")
+    p.add_argument("--gt_sample_spacing", type=float, default=None, help="the same for a ground truth that is a mesh")
+    p.add_argument("--sample_seed", type=int, default=0, help="key of the samples' random stream")
+    p.add_argument("--write_samples", type=Path, default=None, help="write the reconstruction's samples as they are scored to this .ply")
+    p.add_argument("--crop_file", type=Path, default=None, help="Tanks and Temples crop file (.json: a polygon swept along an axis, in the "
+                                                                "ground truth's frame): reconstruction points outside it are dropped "
+                                                                "before ICP and before scoring")
+    p.add_argument("--crop_file_ground_truth", type=_strtobool, default=False, help="apply --crop_file to the ground truth as well")
     p.add_argument("--output_json", type=Path, default=None, help="write the numbers to this file")
     return p
 
@@ -1253,7 +1264,34 @@ def eval_geometry_main(argv=None):
             raise SystemExit("--icp_voxel_sizes must be positive")
         if opt.icp_max_iterations < 1:
             raise SystemExit("--icp_max_iterations must be at least 1")
-    rec, gt = read_ply_points(opt.reconstruction), read_ply_points(opt.ground_truth)
+    for name in ("sample_spacing", "gt_sample_spacing"):
+        value = getattr(opt, name)
+        try:
+            if value is not None:
+                geometry.sample_density(value)
+        except ValueError:
+            raise SystemExit(f"--{name} must be positive (and its square within float64's range)")
+    if opt.write_samples is not None and opt.sample_spacing is None:
+        raise SystemExit("--write_samples needs --sample_spacing: without it the reconstruction is scored by its vertices")
+    if opt.crop_file_ground_truth and opt.crop_file is None:
+        raise SystemExit("--crop_file_ground_truth needs --crop_file")
+    if opt.crop_file is not None and not os.path.isfile(opt.crop_file):
+        raise SystemExit(f"{opt.crop_file}: no such file")
+    crop_volume = None if opt.crop_file is None else read_crop_file(opt.crop_file)
+    surface = opt.sample_spacing is not None or opt.gt_sample_spacing is not None or crop_volume is not None
+    rec_colours = rec_faces = gt_faces = None
+    if opt.sample_spacing is not None:
+        rec, rec_colours, rec_faces = read_ply_mesh(opt.reconstruction)
+        if len(rec_faces) == 0:
+            raise SystemExit(f"{opt.reconstruction}: --sample_spacing needs a mesh, and this file has no faces")
+    else:
+        rec = read_ply_points(opt.reconstruction)
+    if opt.gt_sample_spacing is not None:
+        gt, _, gt_faces = read_ply_mesh(opt.ground_truth)
+        if len(gt_faces) == 0:
+            raise SystemExit(f"{opt.ground_truth}: --gt_sample_spacing needs a mesh, and this file has no faces")
+    else:
+        gt = read_ply_points(opt.ground_truth)
     log.info(f"Read {len(rec)} points from {opt.reconstruction} and {len(gt)} from {opt.ground_truth}.")
     import torch
     if not torch.cuda.is_available():
@@ -1279,10 +1317,48 @@ def eval_geometry_main(argv=None):
         log.info(f"Aligned on {len(pairs)} pose pairs: scale {res['scale']:.6f} (ground truth -> reconstruction), median pose error "
                  f"{res['median_r_deg']:.2f}deg, {res['median_t_cm']:.1f}cm.")
     t0 = time.perf_counter()
+    sampling = crop_info = colours_d = None
     try:
         rec_d, gt_d = torch.from_numpy(rec).cuda(), torch.from_numpy(gt).cuda()
-        if opt.icp:
+        if surface:
+            # the order of DESIGN 4n: read, move the vertices, sample, polygon crop, ICP (from the identity), voxel, box crop, search
             transform_initial = transform
+            if transform is not None:
+                rec_d = geometry.apply_similarity(rec_d, transform)
+            transform = None
+            if opt.sample_spacing is not None or opt.gt_sample_spacing is not None:
+                sampling = {"seed": opt.sample_seed}
+            if opt.sample_spacing is not None:
+                colours_d = None if rec_colours is None else torch.from_numpy(rec_colours).cuda()
+                rec_d, _, colours_d, info = geometry.sample_mesh(rec_d, torch.from_numpy(rec_faces).cuda(), spacing=opt.sample_spacing,
+                                                                 seed=opt.sample_seed, colours=colours_d)
+                sampling.update(spacing=opt.sample_spacing, **info)
+                log.info(f"Sampled {info['samples']} points, {opt.sample_spacing} m apart, from the {info['faces']} faces of the "
+                         f"reconstruction ({info['area']:.4f} m^2; {info['faces_invalid']} faces invalid).")
+            if opt.gt_sample_spacing is not None:
+                gt_d, _, _, info = geometry.sample_mesh(gt_d, torch.from_numpy(gt_faces).cuda(), spacing=opt.gt_sample_spacing, seed=opt.sample_seed)
+                sampling.update(gt_spacing=opt.gt_sample_spacing, **{"gt_" + k: v for k, v in info.items()})
+                log.info(f"Sampled {info['samples']} points, {opt.gt_sample_spacing} m apart, from the {info['faces']} faces of the "
+                         f"ground truth ({info['area']:.4f} m^2; {info['faces_invalid']} faces invalid).")
+            if crop_volume is not None:
+                keep = geometry.polygon_mask(rec_d, crop_volume)
+                crop_info = {"file": str(opt.crop_file), "orthogonal_axis": "XYZ"[crop_volume.axis], "corners": int(len(crop_volume.polygon)),
+                             "axis_min": float(crop_volume.axis_min), "axis_max": float(crop_volume.axis_max),
+                             "dropped": int(rec_d.shape[0] - int(keep.sum().item()))}
+                rec_d = rec_d[keep].contiguous()
+                if opt.sample_spacing is not None and colours_d is not None:
+                    colours_d = colours_d[keep].contiguous()
+                if opt.crop_file_ground_truth:
+                    gt_d, crop_info["gt_dropped"] = geometry.crop_to_polygon(gt_d, crop_volume)
+                log.info(f"Crop file {opt.crop_file}: {crop_info['corners']} corners along {crop_info['orthogonal_axis']}, "
+                         f"{crop_info['dropped']} reconstruction points dropped, {rec_d.shape[0]} kept"
+                         + (f"; {crop_info['gt_dropped']} ground-truth points dropped" if opt.crop_file_ground_truth else "") + ".")
+                if rec_d.shape[0] == 0:
+                    raise ValueError(f"the reconstruction is empty after the crop file's polygon ({crop_info['dropped']} points dropped): "
+                                     "are the clouds in the same frame?")
+        if opt.icp:
+            if not surface:
+                transform_initial = transform
             transform, stages = geometry.refine_alignment(rec_d, gt_d, transform, distances=icp_distances, voxels=opt.icp_voxel_sizes,
                                                           max_iterations=opt.icp_max_iterations, with_scale=opt.icp_scale)
             for stage in stages:
@@ -1291,14 +1367,26 @@ def eval_geometry_main(argv=None):
                          + (f", fitness {stage['fitness'][-1] * 100:.2f}%, rmse {stage['rmse'][-1] * 1000:.3f} mm" if stage["iterations"] else ""))
         res = geometry.evaluate_geometry(rec_d, gt_d, opt.thresholds, transform=transform, voxel=opt.voxel_size, crop=opt.crop,
                                          max_distance=opt.max_distance)
+        if opt.write_samples is not None:                         # as they are scored: cropped by the polygon, under the final alignment
+            scored = rec_d if transform is None else geometry.apply_similarity(rec_d, transform)
+            write_ply(opt.write_samples, scored.cpu().numpy(), np.full((scored.shape[0], 3), 200, np.uint8) if colours_d is None
+                      else colours_d.cpu().numpy())
+            log.info(f"Wrote {scored.shape[0]} samples to {opt.write_samples}.")
     except ValueError as e:
-        raise SystemExit(str(e))
+        raise SystemExit(str(e) + (f" (the crop file's polygon dropped {crop_info['dropped']} points before)"
+                                   if crop_info is not None and "crop file" not in str(e) and "is empty" in str(e) else ""))
+    if surface and transform_initial is not None:                  # what is reported maps the file's frame: T_icp T_initial
+        transform = transform_initial if transform is None else transform @ transform_initial
     t_device = time.perf_counter() - t0
     for line in geometry.log_lines(res):
         log.info(line)
     log.info(f"Upload + kernels + download {t_device:.2f} s.")
     if opt.output_json is not None:
         res["transform"] = None if transform is None else [[float(x) for x in row] for row in transform]
+        if sampling is not None:
+            res["sampling"] = sampling
+        if crop_info is not None:
+            res["crop_file"] = crop_info
         if opt.icp:
             res["transform_initial"] = None if transform_initial is None else [[float(x) for x in row] for row in transform_initial]
             # a stage without correspondences has rmse = sqrt(0 / 0): null in the file, which stays strict JSON

@@ -1,6 +1,7 @@
 """The files that carry results from one command line to the next, each read and written in one place: the ACE pose file
 (`file qw qx qy qz tx ty tz focal confidence`, world->camera), binary little-endian PLY (point clouds, fused meshes, camera
-meshes) and the 16-bit depth PNG that estimate_depth.py writes and fuse_depth.py reads. Host code only."""
+meshes; read_ply_mesh also reads other tools' meshes), the Tanks and Temples crop file (JSON) and the 16-bit depth PNG that
+estimate_depth.py writes and fuse_depth.py reads. Host code only."""
 import os
 from collections import namedtuple
 
@@ -165,6 +166,206 @@ def read_ply_points(path):
         raise SystemExit(f"{path}: truncated")
     rec = np.frombuffer(body[:vertex.itemsize * count], dtype=vertex)
     return np.ascontiguousarray(np.stack([rec["x"], rec["y"], rec["z"]], axis=1).astype(np.float32))
+
+
+def _ply_header(path, blob):
+    """(format, [(element, count, [property tokens after 'property'])], body) of a binary little-endian or ASCII .ply."""
+    head, sep, body = blob.partition(_PLY_END)
+    lines = [line.strip() for line in head.decode("ascii", "replace").splitlines()]
+    if not sep or lines[:1] != ["ply"]:
+        raise SystemExit(f"{path}: not a .ply file")
+    fmt = [line.split()[1] for line in lines if line.split()[:1] == ["format"] and len(line.split()) > 1]
+    if fmt not in (["binary_little_endian"], ["ascii"]):
+        raise SystemExit(f"{path}: only binary little-endian and ASCII .ply files are read")
+    elements = []
+    for line in lines:
+        tok = line.split()
+        if tok[:1] == ["element"] and len(tok) == 3:
+            try:
+                elements.append((tok[1], int(tok[2]), []))
+            except ValueError:
+                raise SystemExit(f"{path}: '{line}' does not give a count")
+        elif tok[:1] == ["property"] and elements:
+            elements[-1][2].append(tok[1:])
+    return fmt[0], elements, body
+
+
+def _fan(rows, width):
+    """int64 [len(rows) * (width - 2), 3]: every polygon (row of `width` indices) split as the fan (0, i, i + 1)."""
+    tri = np.stack([np.stack([rows[:, 0], rows[:, i], rows[:, i + 1]], 1) for i in range(1, width - 1)], 1)
+    return tri.reshape(-1, 3)
+
+
+def read_ply_mesh(path):
+    """(vertices float32 [m,3], colours uint8 [m,3] or None, triangles int32 [k,3]) of a binary little-endian or ASCII .ply: the x, y,
+    z of the vertex element as read_ply_points reads them, its uchar red, green, blue where it has them, and the face element's
+    `vertex_indices` (or `vertex_index`) list, of any integer count and index type. A polygon of more than three vertices is split
+    as the fan (0, i, i + 1) in file order. The vertex element comes first; elements between it and the faces, and further scalar
+    properties of a face, are skipped; elements after the faces are ignored. A file without a face element, or with `element face
+    0`, gives triangles [0,3]. An index that does not fit int32 becomes -1 (the sampler counts such a face as invalid)."""
+    blob = open(str(path), "rb").read()
+    fmt, elements, body = _ply_header(path, blob)
+    if [e[0] for e in elements[:1]] != ["vertex"]:
+        raise SystemExit(f"{path}: the first element is not 'vertex'")
+    vertices = read_ply_points(path)
+    _, count, vprops = elements[0]
+    names = [p[1] for p in vprops]
+    has_rgb = all(c in names and _PLY_TYPES.get(vprops[names.index(c)][0]) == "u1" for c in ("red", "green", "blue"))
+    ascii_ = fmt == "ascii"
+    tokens = body.split() if ascii_ else None
+    at = 0                                                           # position in tokens (ASCII) or in body (binary)
+
+    def scalars(props, what):
+        for p in props:
+            if len(p) != 2 or p[0] not in _PLY_TYPES:
+                raise SystemExit(f"{path}: property '{' '.join(p)}' of element '{what}' is not a scalar of a known type")
+        return np.dtype([(f"f{i}", "<" + _PLY_TYPES[p[0]]) for i, p in enumerate(props)])
+
+    colours = None
+    vertex = scalars(vprops, "vertex")
+    if has_rgb:
+        if ascii_:
+            table = np.array(tokens[:count * len(names)], dtype=np.float64).reshape(count, len(names))
+            colours = np.stack([table[:, names.index(c)] for c in ("red", "green", "blue")], 1).astype(np.uint8)
+        else:
+            rec = np.frombuffer(body[:vertex.itemsize * count], dtype=vertex)
+            colours = np.ascontiguousarray(np.stack([rec[f"f{names.index(c)}"] for c in ("red", "green", "blue")], 1))
+    at = count * len(names) if ascii_ else vertex.itemsize * count
+    empty = np.zeros((0, 3), np.int32)
+    for name, n, props in elements[1:]:
+        if name != "face":
+            dt = scalars(props, name)                                # an element with a list before the faces cannot be skipped
+            at += n * len(props) if ascii_ else n * dt.itemsize
+            continue
+        lists = [i for i, p in enumerate(props) if p[:1] == ["list"]]
+        if len(lists) != 1 or len(props[lists[0]]) != 4 or props[lists[0]][3] not in ("vertex_indices", "vertex_index"):
+            raise SystemExit(f"{path}: the face element needs one list property, vertex_indices or vertex_index")
+        li = lists[0]
+        _, ct, it, _ = props[li]
+        if _PLY_TYPES.get(ct, "f")[0] not in "iu" or _PLY_TYPES.get(it, "f")[0] not in "iu":
+            raise SystemExit(f"{path}: the face list 'property {' '.join(props[li])}' needs integer count and index types")
+        before, after = scalars(props[:li], "face"), scalars(props[li + 1:], "face")
+        if n == 0:
+            return vertices, colours, empty
+        if ascii_:
+            rest = tokens[at:]
+            nb, na = len(props[:li]), len(props[li + 1:])
+            try:
+                width = int(rest[nb]) if len(rest) > nb else -1
+                row = nb + 1 + width + na
+                rows = None
+                if width >= 3 and len(rest) >= n * row:              # every face the same size: one table
+                    table = np.array(rest[:n * row], dtype=np.float64).reshape(n, row)
+                    if (table[:, nb] == width).all():
+                        rows = table[:, nb + 1:nb + 1 + width].astype(np.int64)
+                if rows is not None:
+                    tri = _fan(rows, width)
+                else:
+                    out, pos = [], 0
+                    for _ in range(n):
+                        if pos + nb >= len(rest):
+                            raise SystemExit(f"{path}: truncated")
+                        w = int(rest[pos + nb])
+                        if w < 3:
+                            raise SystemExit(f"{path}: a face with {w} vertices")
+                        if pos + nb + 1 + w + na > len(rest):
+                            raise SystemExit(f"{path}: truncated")
+                        out.append(_fan(np.array([rest[pos + nb + 1:pos + nb + 1 + w]], dtype=np.float64).astype(np.int64), w))
+                        pos += nb + 1 + w + na
+                    tri = np.concatenate(out)
+            except ValueError:
+                raise SystemExit(f"{path}: a face line holds something that is not a number")
+        else:
+            rest = body[at:]
+            cdt, idt = np.dtype("<" + _PLY_TYPES[ct]), np.dtype("<" + _PLY_TYPES[it])
+            if len(rest) < before.itemsize + cdt.itemsize:
+                raise SystemExit(f"{path}: truncated")
+            width = int(np.frombuffer(rest, cdt, 1, before.itemsize)[0])
+            rows = None
+            if width >= 3:                                           # every face the same size: one record type
+                face = np.dtype([("b", before), ("n", cdt), ("v", idt, (width,)), ("a", after)])
+                if len(rest) >= n * face.itemsize:
+                    rec = np.frombuffer(rest[:n * face.itemsize], dtype=face)
+                    if (rec["n"] == width).all():
+                        rows = rec["v"].astype(np.int64)
+            if rows is not None:
+                tri = _fan(rows, width)
+            else:
+                out, pos = [], 0
+                for _ in range(n):
+                    if pos + before.itemsize + cdt.itemsize > len(rest):
+                        raise SystemExit(f"{path}: truncated")
+                    w = int(np.frombuffer(rest, cdt, 1, pos + before.itemsize)[0])
+                    if w < 3:
+                        raise SystemExit(f"{path}: a face with {w} vertices")
+                    start = pos + before.itemsize + cdt.itemsize
+                    if start + w * idt.itemsize + after.itemsize > len(rest):
+                        raise SystemExit(f"{path}: truncated")
+                    out.append(_fan(np.frombuffer(rest, idt, w, start).astype(np.int64)[None, :], w))
+                    pos = start + w * idt.itemsize + after.itemsize
+                tri = np.concatenate(out)
+        tri = np.where((tri >= -2 ** 31) & (tri < 2 ** 31), tri, -1)
+        return vertices, colours, np.ascontiguousarray(tri.astype(np.int32))
+    return vertices, colours, empty
+
+
+# ----------------------------------------------------------------------------------------------------------- crop files
+# read_crop_file's result: the polygon's corners (U, V) in the plane orthogonal to `axis` (0, 1, 2 = X, Y, Z) as float32 [p,2], the
+# bounds along the axis as float32; the fields acezero_amd.geometry.crop_to_polygon takes
+CropVolume = namedtuple("CropVolume", ["polygon", "axis", "axis_min", "axis_max"])
+CROP_PLANE = {0: (1, 2), 1: (0, 2), 2: (0, 1)}                        # the in-plane axes (u, v): (y, z) for X, (x, z) for Y, (x, y) for Z
+CROP_MAX_CORNERS = 1024
+
+
+def read_crop_file(path):
+    """The crop volume of a Tanks and Temples crop file (a JSON object, the layout of Open3D's SelectionPolygonVolume): a polygon,
+    `bounding_polygon` (3 .. 1024 rows of three numbers, of which the two in the plane orthogonal to `orthogonal_axis` count), swept
+    along `orthogonal_axis` ("X", "Y" or "Z") from `axis_min` to `axis_max`. Returns a CropVolume, polygon and bounds rounded to
+    float32 once. Other keys are ignored; `class_name`, if present, must be "SelectionPolygonVolume". Anything else is a SystemExit
+    that names the file and the key."""
+    import json
+    import math
+
+    def refuse(key, what):
+        raise SystemExit(f"{path}: {key}: {what}")
+
+    try:
+        with open(str(path)) as f:
+            doc = json.load(f)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"{path}: not a JSON crop file ({e})")
+    if not isinstance(doc, dict):
+        raise SystemExit(f"{path}: not a JSON object")
+    for key in ("bounding_polygon", "orthogonal_axis", "axis_min", "axis_max"):
+        if key not in doc:
+            refuse(key, "missing")
+    if "class_name" in doc and doc["class_name"] != "SelectionPolygonVolume":
+        refuse("class_name", f"expected 'SelectionPolygonVolume', got {doc['class_name']!r}")
+    axis = doc["orthogonal_axis"]
+    if not isinstance(axis, str) or axis.upper() not in ("X", "Y", "Z"):
+        refuse("orthogonal_axis", f"expected 'X', 'Y' or 'Z', got {axis!r}")
+    axis = "XYZ".index(axis.upper())
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+    for key in ("axis_min", "axis_max"):
+        if not number(doc[key]):
+            refuse(key, f"expected a finite number, got {doc[key]!r}")
+    with np.errstate(over="ignore"):
+        lo, hi = np.float32(doc["axis_min"]), np.float32(doc["axis_max"])
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        refuse("axis_min" if not np.isfinite(lo) else "axis_max", "overflows float32")
+    if doc["axis_min"] > doc["axis_max"]:
+        refuse("axis_min", f"{doc['axis_min']} is above axis_max {doc['axis_max']}")
+    rows = doc["bounding_polygon"]
+    if not isinstance(rows, list) or not 3 <= len(rows) <= CROP_MAX_CORNERS:
+        refuse("bounding_polygon", f"expected 3 .. {CROP_MAX_CORNERS} rows" + (f", got {len(rows)}" if isinstance(rows, list) else ""))
+    for k, row in enumerate(rows):
+        if not isinstance(row, list) or len(row) != 3 or not all(number(v) for v in row):
+            refuse("bounding_polygon", f"row {k} is not three finite numbers")
+    with np.errstate(over="ignore"):
+        polygon = np.array(rows, dtype=np.float64).astype(np.float32)[:, list(CROP_PLANE[axis])]
+    if not np.isfinite(polygon).all():
+        refuse("bounding_polygon", "overflows float32")
+    return CropVolume(np.ascontiguousarray(polygon), axis, lo, hi)
 
 
 # ------------------------------------------------------------------------------------------------------------ depth PNG

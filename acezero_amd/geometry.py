@@ -7,9 +7,12 @@ command line).
     res = evaluate_geometry(rec, gt, [0.01, 0.02, 0.05], transform=T)  # dict: precision, recall, fscore per threshold, ...
     T, info = icp_stage(src, tgt, radius=0.05)                         # one ICP stage from the identity, the loop on the device
     T, stages = refine_alignment(rec, gt, T0, distances=[0.2, 0.1, 0.05])  # coarse to fine, from the alignment T0
+    points, face, colours, info = sample_mesh(vertices, faces, spacing=0.005)   # a mesh as its surface: section O, DESIGN 4n
+    kept, dropped = crop_to_polygon(points, formats.read_crop_file(path))       # the volume of a Tanks and Temples crop file
 
 The clouds live in HBM; the grid cells, the nearest-neighbour search, the voxel means and the ICP loop (the search with the
-correspondence moments, the Umeyama solve) are HIP kernels (acezero_amd/csrc/geometry_api.hip), sorting and prefix sums are torch's.
+correspondence moments, the Umeyama solve) are HIP kernels (acezero_amd/csrc/geometry_api.hip), and so are the face counts, the
+face samples and the polygon crop (acezero_amd/csrc/surface_api.hip); sorting and prefix sums are torch's.
 There is no CPU fallback."""
 import collections
 
@@ -334,6 +337,88 @@ def evaluate_geometry(rec, gt, thresholds, *, transform=None, voxel=None, crop=T
     return res
 
 
+# ------------------------------------------------------------------------------------- surfaces (include/acez.h section O)
+MAX_SAMPLES = 2 ** 31 - 1
+
+
+def sample_density(spacing):
+    """Samples per square metre at `spacing` metres between samples: 1 / spacing^2 in float64, the product first."""
+    s = float(spacing)
+    if not (np.isfinite(s) and s > 0):
+        raise ValueError(f"spacing must be positive and finite, got {spacing}")
+    if s * s == 0.0 or 1.0 / (s * s) == 0.0:
+        raise ValueError(f"spacing {spacing}: its square or the density 1 / spacing^2 is outside float64's range")
+    return 1.0 / (s * s)
+
+
+def sample_mesh(vertices, faces, *, spacing, seed=0, colours=None):
+    """Sample the surface of a triangle mesh at about one point per spacing x spacing (include/acez.h section O): vertices float32
+    [m,3] and faces int32 [k,3] device tensors, colours uint8 [m,3] or None. Every face draws its own number of samples, floor(area /
+    spacing^2) plus one more with the probability of the remainder, and its own uniform samples, from a counter-based stream keyed by
+    (seed, face): the result is a function of the mesh, the spacing and the seed alone. Returns (points float32 [n,3], face_index
+    int32 [n], colours uint8 [n,3] or None, info): the samples in face order, and info = dict(faces, faces_invalid (an index outside
+    the vertices, or an area that is not finite: no samples), area (the valid faces' areas, summed in face order by math.fsum),
+    samples). ValueError if the mesh asks for more than 2^31 - 1 samples."""
+    import math
+    vertices = _points(vertices, "sample_mesh")
+    dev = vertices.device
+    if not torch.is_tensor(faces) or faces.device != dev:
+        raise _no_cpu("sample_mesh")
+    if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"sample_mesh: expected integer faces [k,3], got {faces.dtype} {tuple(faces.shape)}")
+    faces = faces.to(torch.int32).contiguous()
+    if colours is not None:
+        if not torch.is_tensor(colours) or colours.device != dev:
+            raise _no_cpu("sample_mesh")
+        if colours.dtype != torch.uint8 or tuple(colours.shape) != tuple(vertices.shape):
+            raise ValueError(f"sample_mesh: expected uint8 colours {tuple(vertices.shape)}, got {colours.dtype} {tuple(colours.shape)}")
+        colours = colours.contiguous()
+    density, seed = sample_density(spacing), int(seed) & (2 ** 64 - 1)
+    m, k = vertices.shape[0], faces.shape[0]
+    counts = torch.empty(k, dtype=torch.int32, device=dev)
+    areas = torch.empty(k, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        N.check(N.lib().acez_geom_face_counts(_ptr(vertices), m, _ptr(faces), k, density, seed, _ptr(counts), _ptr(areas), _stream()))
+    offsets = torch.zeros(k + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(counts, 0, dtype=torch.int64)       # the one scan: over integers
+    areas_h = areas.cpu().numpy()
+    n = int(offsets[-1].item())
+    info = {"faces": k, "faces_invalid": int((areas_h < 0).sum()), "area": math.fsum(areas_h[areas_h >= 0].tolist()), "samples": n}
+    if n > MAX_SAMPLES:
+        raise ValueError(f"spacing {spacing} asks for {n} samples of {info['area']:.6g} m^2, more than 2^31 - 1: use a larger spacing")
+    points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    face_index = torch.empty(n, dtype=torch.int32, device=dev)
+    out_colours = None if colours is None else torch.empty((n, 3), dtype=torch.uint8, device=dev)
+    if n:
+        with torch.cuda.device(dev):
+            N.check(N.lib().acez_geom_sample_faces(_ptr(vertices), m, _ptr(faces), k, _ptr(offsets), n, seed,
+                                                   None if colours is None else _ptr(colours), _ptr(points), _ptr(face_index),
+                                                   None if colours is None else _ptr(out_colours), _stream()))
+    return points, face_index, out_colours, info
+
+
+def polygon_mask(points, crop):
+    """bool [n]: the points inside the volume `crop` (a formats.CropVolume, read_crop_file's result): finite, axis_min <= w <= axis_max, and inside the
+    polygon by the crossing rule of include/acez.h section O (acez_geom_crop_polygon)."""
+    points = _points(points, "crop_to_polygon")
+    polygon = np.ascontiguousarray(np.asarray(crop.polygon, np.float32).reshape(-1, 2))
+    if not np.isfinite(polygon).all():
+        raise ValueError("the crop polygon has a corner that is not finite")
+    keep = torch.empty(points.shape[0], dtype=torch.uint8, device=points.device)
+    poly_d = torch.from_numpy(polygon).to(points.device)
+    with torch.cuda.device(points.device):
+        N.check(N.lib().acez_geom_crop_polygon(_ptr(points), points.shape[0], _ptr(poly_d), polygon.shape[0], int(crop.axis),
+                                               float(np.float32(crop.axis_min)), float(np.float32(crop.axis_max)), _ptr(keep), _stream()))
+    return keep.bool()
+
+
+def crop_to_polygon(points, crop):
+    """(the points inside the crop volume, the number dropped): polygon_mask's points, compacted by torch as in crop_to_box."""
+    points = _points(points, "crop_to_polygon")
+    keep = polygon_mask(points, crop)
+    return points[keep].contiguous(), int(points.shape[0] - int(keep.sum().item()))
+
+
 def log_lines(res):
     """The summary eval_geometry.py logs: the counts, then one line per threshold."""
     lines = [f"Reconstruction: {res['rec_points']} points ({res['rec_points_read']} read, {res['dropped']} dropped outside the ground "
@@ -348,4 +433,5 @@ def log_lines(res):
 
 
 __all__ = ["nearest_distances", "voxel_downsample", "evaluate_geometry", "apply_similarity", "crop_to_box", "scores", "fscore",
-           "log_lines", "grid_dims", "point_cells", "build_grid", "order_by_cell", "icp_stage", "refine_alignment"]
+           "log_lines", "grid_dims", "point_cells", "build_grid", "order_by_cell", "icp_stage", "refine_alignment", "sample_mesh",
+           "sample_density", "crop_to_polygon", "polygon_mask"]

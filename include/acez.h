@@ -1068,6 +1068,57 @@ int acez_geom_icp_accumulate(const float* d_ref, const int32_t* d_ref_index, con
 int acez_geom_icp_update(const double* d_partials, int64_t n, float px, float py, float pz, int with_scale, double rel_fitness,
                          double rel_rmse, int max_iterations, double* d_state, double* d_history, void* stream);
 
+/* =====================================================================================================
+ * O. A mesh scored by its surface: samples of the faces, and the polygon crop (eval_geometry.py --sample_spacing, --crop_file)
+ * =====================================================================================================
+ * Three stateless entry points; none allocates anything, every buffer is the caller's. d_vertices float32 [m][3], d_faces int32
+ * [k][3] (triangles, rows of d_vertices). Everything below is fp64 unless it says otherwise, round to nearest, one rounding per
+ * operation in the order written (the unit is built without contraction); the random stream is 64-bit integer arithmetic modulo
+ * 2^64 with mix64 of acezero_amd/csrc/ransac_math.h. Nothing depends on scheduling: no atomics and no floating-point sum over
+ * faces; every face decides its own number of samples, and the only scan, the exclusive sum of those integers, is the caller's.
+ * tests/surface_restated.py restates all of it in numpy.
+ *
+ * COUNTS (acez_geom_face_counts). Per face t with vertices a, b, c (each component widened to fp64):
+ *   e1 = b - a, e2 = c - a
+ *   n  = (e1y * e2z - e1z * e2y,  e1z * e2x - e1x * e2z,  e1x * e2y - e1y * e2x)
+ *   S  = (nx * nx + ny * ny) + nz * nz,  area = 0.5 * sqrt(S)
+ *   The face is INVALID if an index is outside 0 .. m - 1 or area is not finite: d_out_areas[t] = -1.0, d_out_counts[t] = 0.
+ *   Otherwise d_out_areas[t] = area and, with `density` in samples per square metre:
+ *     x = area * density, f = floor(x)
+ *     key_t = mix64(mix64(seed) ^ t),  u0 = (key_t >> 11) * 2^-53
+ *     d_out_counts[t] = min(f, 2^30) + (u0 < x - f ? 1 : 0)
+ *   so the expected count is x: a face smaller than 1 / density is not lost, it gets a sample with probability x.
+ *
+ * SAMPLE (acez_geom_sample_faces). d_offsets int64 [k + 1]: the exclusive sums of the counts, d_offsets[0] = 0, d_offsets[k] = n.
+ * Per sample j of n:
+ *   t = the last face in 0 .. k - 1 with d_offsets[t] <= j (faces without samples are skipped by this rule), i = j - d_offsets[t]
+ *   r = mix64(key_t + (i + 1) * 0xD1B54A32D192ED03),  u = (r >> 40) * 2^-24,  v = ((r >> 16) & 0xFFFFFF) * 2^-24
+ *   if u + v > 1: u = 1 - u, v = 1 - v        (the fold: uniform over the triangle without a square root)
+ *   per axis p = float((a + u * e1) + v * e2), rounded to fp32 once;  d_out_points float32 [n][3], d_out_face int32 [n] = t
+ *   with d_colours uint8 [m][3]: d_out_colours uint8 [n][3] = floor((((1 - u) - v) * ca + u * cb) + v * cc + 0.5) per channel,
+ *   the sums from left to right. d_colours and d_out_colours are both null or both given.
+ * t is clamped to 0 .. k - 1 and every vertex index to 0 .. m - 1 before anything is loaded: d_offsets and d_faces are device data
+ * that cannot be checked here, and a wrong table gives wrong numbers, never an access out of bounds.
+ *
+ * CROP (acez_geom_crop_polygon). The volume of a Tanks and Temples crop file: a polygon swept along a coordinate axis. d_polygon
+ * float32 [corners][2]: the corners (U, V) in the plane orthogonal to `axis`; (u, v, w) of a point (x, y, z) is (y, z, x) for axis 0,
+ * (x, z, y) for axis 1, (x, y, z) for axis 2. d_out_keep uint8 [n] = 1 iff x, y, z are finite, axis_min <= w <= axis_max (fp32
+ * comparisons) and the number of crossings is odd. Edge i -> j = (i + 1) mod corners counts only if (V_i > v) != (V_j > v); then, with
+ * everything widened to fp64, lhs = (u - U_i) * (V_j - V_i), rhs = (v - V_i) * (U_j - U_i), and the edge is a crossing if
+ * V_j > V_i ? lhs < rhs : lhs > rhs. The half-open rule counts a corner once; an edge along u never counts.
+ *
+ * Asynchronous on `stream`. ACEZ_ERR_INVALID, before anything is launched, for: a null pointer (an array whose count is 0 may be
+ * null), a negative count or one >= 2^31, a density that is not positive and finite, samples (n > 0) of a mesh with m = 0 or k = 0,
+ * only one of d_colours / d_out_colours, corners outside 3 .. 1024, an axis outside 0 .. 2, axis bounds that are not finite or
+ * axis_min > axis_max. */
+int acez_geom_face_counts(const float* d_vertices, int64_t m, const int32_t* d_faces, int64_t k, double density, uint64_t seed,
+                          int32_t* d_out_counts, double* d_out_areas, void* stream);
+int acez_geom_sample_faces(const float* d_vertices, int64_t m, const int32_t* d_faces, int64_t k, const int64_t* d_offsets, int64_t n,
+                           uint64_t seed, const uint8_t* d_colours, float* d_out_points, int32_t* d_out_face, uint8_t* d_out_colours,
+                           void* stream);
+int acez_geom_crop_polygon(const float* d_points, int64_t n, const float* d_polygon, int corners, int axis, float axis_min,
+                           float axis_max, uint8_t* d_out_keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
