@@ -1105,6 +1105,10 @@ def benchmark_poses_main(argv=None):
 
 
 # ----------------------------------------------------------------------------------------------------------- fuse_depth
+MAX_GRID_VOXELS = 2 ** 62                # --sparse True: the virtual grid is limited by its block grid, not by --max_voxels
+MAX_SPARSE_GRID_BLOCKS = 2 ** 28         # one flag byte and one int32 table entry per block: 1.3 GB
+
+
 def fuse_depth_parser():
     p = argparse.ArgumentParser(description="Fuse the depth maps of an RGB-D reconstruction along its estimated poses into a TSDF volume "
                                             "on the GPU and write the surface as a coloured triangle mesh (.ply).",
@@ -1122,6 +1126,9 @@ def fuse_depth_parser():
     p.add_argument("--depth_unit", type=float, default=0.001, help="metres per raw depth unit (0.001: millimetres)")
     p.add_argument("--max_voxels", type=int, default=2 ** 28, help="refuse a volume of more voxels than this")
     p.add_argument("--colour", type=_strtobool, default=True, help="colour the mesh from the RGB files")
+    p.add_argument("--sparse", type=_strtobool, default=False, help="store only the 8^3-voxel blocks near a surface: the same mesh (rows in "
+                                                                    "another order) for scenes whose dense volume does not fit; "
+                                                                    "--max_voxels then limits the allocated voxels")
     return p
 
 
@@ -1157,7 +1164,12 @@ def fuse_depth_main(argv=None):
         # a pose file's focal is in pixels of the original image; the depth map is that image at another scale
         focals = np.array([focals_all[p[2]] * d.shape[0] / ih for p, d, ih in zip(pairs, depth, image_h)])
         origin, dims = fusion.bounds_from_frames(depth, c2w, focals, opt.voxel_size, truncation, depth_unit=opt.depth_unit,
-                                                 max_depth=opt.max_depth, max_voxels=opt.max_voxels)
+                                                 max_depth=opt.max_depth, max_voxels=MAX_GRID_VOXELS if opt.sparse else opt.max_voxels)
+        if opt.sparse:
+            grid = fusion.block_grid(dims)
+            if grid[0] * grid[1] * grid[2] > MAX_SPARSE_GRID_BLOCKS:
+                raise SystemExit(f"the volume would have {grid[0]} x {grid[1]} x {grid[2]} = {grid[0] * grid[1] * grid[2]} blocks of 8^3 voxels, "
+                                 f"more than 2^28: raise --voxel_size or lower --max_depth")
         rgb = None
         if opt.colour:
             def read_rgb(job):
@@ -1169,8 +1181,17 @@ def fuse_depth_main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("fuse_depth.py needs a GPU: TSDF fusion is a HIP kernel, there is no CPU path")
     t0 = time.perf_counter()
-    vol = fusion.TSDFVolume(origin, dims, opt.voxel_size, truncation, "cuda")
-    vol.integrate(depth, cam_to_world=c2w, focals=focals, rgb=rgb, depth_unit=opt.depth_unit, max_depth=opt.max_depth)
+    if opt.sparse:
+        vol = fusion.SparseTSDFVolume(origin, dims, opt.voxel_size, truncation, "cuda", max_blocks=opt.max_voxels // fusion.BLOCK_VOXELS)
+        vol.mark(depth, cam_to_world=c2w, focals=focals, depth_unit=opt.depth_unit, max_depth=opt.max_depth)
+        try:
+            n_blocks = vol.allocate()
+        except ValueError as e:
+            raise SystemExit(f"{e}: the volume would allocate more than --max_voxels {opt.max_voxels} voxels: raise --voxel_size, lower "
+                             f"--max_depth or raise --max_voxels")
+    else:
+        vol = fusion.TSDFVolume(origin, dims, opt.voxel_size, truncation, "cuda")
+    vol.integrate(depth, cam_to_world=c2w, focals=focals, rgb=rgb, depth_unit=opt.depth_unit, max_depth=opt.max_depth)   # 64 frames a call
     vertices, colours, faces = vol.extract_mesh(opt.min_weight)
     known = vol.known_voxels(opt.min_weight)
     vertices, colours, faces = vertices.cpu(), colours.cpu(), faces.cpu()
@@ -1182,6 +1203,11 @@ def fuse_depth_main(argv=None):
     t_write = time.perf_counter() - t0
     log.info(f"Fused {len(pairs)} of {len(rgb_files)} frames into a volume of {dims[0]} x {dims[1]} x {dims[2]} voxels "
              f"({opt.voxel_size} m, truncation {truncation} m).")
+    if opt.sparse:
+        grid = fusion.block_grid(dims)
+        n_grid, n_vox = grid[0] * grid[1] * grid[2], dims[0] * dims[1] * dims[2]
+        log.info(f"Allocated blocks: {n_blocks} of {n_grid} ({100.0 * n_blocks / n_grid:.2f} % of the block grid), "
+                 f"{n_blocks * fusion.BLOCK_VOXELS * 20 + n_grid * 5} bytes of volume storage where the dense volume would take {n_vox * 20}.")
     log.info(f"Known voxels: {known}. Mesh: {len(vertices)} vertices, {len(faces)} faces.")
     log.info(f"Decode {t_decode:.2f} s, upload + kernels + download {t_device:.2f} s, write {t_write:.2f} s.")
     log.info(f"Done. Wrote mesh to: {opt.output_file}")

@@ -12,6 +12,15 @@
 // cells      one thread per voxel index; flags the active cells, or (second mode) writes their vertices at their ranks.
 // faces      one thread per (axis, voxel index); flags the quads, or (second mode) writes their triangles at their ranks.
 // No atomics, no communication between workgroups, plain loads and stores.
+//
+// Section K2 (acez_tsdf_mark, acez_tsdf_integrate_blocks, acez_tsdf_cells_blocks, acez_tsdf_faces_blocks) is the same function on a
+// block-sparse volume: 8 x 8 x 8 blocks, stored only where depth puts a surface, found through a table.
+// mark             one thread per depth pixel; thread 0 of a workgroup (one frame) inverts the pose in double into LDS; plain byte
+//                  stores of 1, every thread that hits a block stores the same value.
+// integrate_blocks one 512-thread workgroup per allocated block, thread t = voxel t (x fastest): a wave is one z slice of the block,
+//                  256 contiguous bytes per volume load or store. The per-voxel walk is fuse_frames(), the dense kernel's.
+// cells_blocks,    one 512-thread workgroup per allocated block; the block and its one-voxel halo (a 10^3 tile of storage offsets,
+// faces_blocks     tsdf, weight and, for the faces, the active flags) go to LDS through the table, 13 KB.
 #include <math.h>
 #include <stdint.h>
 
@@ -58,6 +67,46 @@ __device__ bool brick_outside(const acez_tsdf_frame& fr, const double lo[3], con
   return behind || left || right || above || below;
 }
 
+// Section K's steps 2-9 for one voxel at (px, py, pz) over the call's frames in table order: the one per-voxel update, used by the dense
+// kernel and by the block kernel. `skip` (LDS, one verdict per frame, read if use_skip) is uniform over the workgroup. true: a frame touched it.
+__device__ __forceinline__ bool fuse_frames(float px, float py, float pz, float& d_t, float& d_w, float& c0, float& c1, float& c2,
+                                            bool with_colour, float tau, const uint16_t* __restrict__ depth, const uint8_t* __restrict__ rgb,
+                                            const acez_tsdf_frame* __restrict__ frames, int n_frames, float depth_unit, float max_depth,
+                                            float max_weight, bool use_skip, const uint8_t* skip) {
+  bool touched = false;
+  for (int f = 0; f < n_frames; ++f) {
+    if (use_skip && skip[f]) continue;                       // uniform over the workgroup
+    const acez_tsdf_frame& fr = frames[f];                   // uniform address: scalar loads
+    const float xc = ((fr.m[0] * px + fr.m[1] * py) + fr.m[2] * pz) + fr.m[3];
+    const float yc = ((fr.m[4] * px + fr.m[5] * py) + fr.m[6] * pz) + fr.m[7];
+    const float zc = ((fr.m[8] * px + fr.m[9] * py) + fr.m[10] * pz) + fr.m[11];
+    if (!(zc > 0.0f)) continue;
+    const float u = (fr.focal * xc) / zc + fr.ppx;
+    const float w_ = (fr.focal * yc) / zc + fr.ppy;
+    if (!(u >= -0.5f && u < (float)fr.w - 0.5f && w_ >= -0.5f && w_ < (float)fr.h - 0.5f)) continue;
+    const int ix = min((int)floorf(u + 0.5f), fr.w - 1);
+    const int iy = min((int)floorf(w_ + 0.5f), fr.h - 1);
+    const int64_t pix = fr.offset + (int64_t)iy * fr.w + ix;   // in [offset, offset + h * w): the host checked that range
+    const uint16_t raw = depth[pix];
+    if (raw == 0) continue;
+    const float d = (float)raw * depth_unit;
+    if (d > max_depth) continue;
+    const float sdf = d - zc;
+    if (sdf < -tau) continue;
+    const float tt = fminf(1.0f, sdf / tau);
+    const float w1 = d_w + 1.0f;
+    d_t = (d_t * d_w + tt) / w1;
+    if (with_colour) {
+      c0 = (c0 * d_w + (float)rgb[3 * pix]) / w1;
+      c1 = (c1 * d_w + (float)rgb[3 * pix + 1]) / w1;
+      c2 = (c2 * d_w + (float)rgb[3 * pix + 2]) / w1;
+    }
+    d_w = fminf(w1, max_weight);
+    touched = true;
+  }
+  return touched;
+}
+
 __global__ void __launch_bounds__(FU_THREADS) integrate_kernel(float* __restrict__ tsdf, float* __restrict__ weight, float* __restrict__ colour,
                                                                Volume vol, float tau, const uint16_t* __restrict__ depth,
                                                                const uint8_t* __restrict__ rgb, const acez_tsdf_frame* __restrict__ frames,
@@ -91,37 +140,8 @@ __global__ void __launch_bounds__(FU_THREADS) integrate_kernel(float* __restrict
     c1 = colour[n_vox + at];
     c2 = colour[2 * n_vox + at];
   }
-  bool touched = false;
-  for (int f = 0; f < n_frames; ++f) {
-    if (frustum_skip && s_skip[f]) continue;                // uniform over the workgroup
-    const acez_tsdf_frame& fr = frames[f];                   // uniform address: scalar loads
-    const float xc = ((fr.m[0] * px + fr.m[1] * py) + fr.m[2] * pz) + fr.m[3];
-    const float yc = ((fr.m[4] * px + fr.m[5] * py) + fr.m[6] * pz) + fr.m[7];
-    const float zc = ((fr.m[8] * px + fr.m[9] * py) + fr.m[10] * pz) + fr.m[11];
-    if (!(zc > 0.0f)) continue;
-    const float u = (fr.focal * xc) / zc + fr.ppx;
-    const float w_ = (fr.focal * yc) / zc + fr.ppy;
-    if (!(u >= -0.5f && u < (float)fr.w - 0.5f && w_ >= -0.5f && w_ < (float)fr.h - 0.5f)) continue;
-    const int ix = min((int)floorf(u + 0.5f), fr.w - 1);
-    const int iy = min((int)floorf(w_ + 0.5f), fr.h - 1);
-    const int64_t pix = fr.offset + (int64_t)iy * fr.w + ix;   // in [offset, offset + h * w): the host checked that range
-    const uint16_t raw = depth[pix];
-    if (raw == 0) continue;
-    const float d = (float)raw * depth_unit;
-    if (d > max_depth) continue;
-    const float sdf = d - zc;
-    if (sdf < -tau) continue;
-    const float tt = fminf(1.0f, sdf / tau);
-    const float w1 = d_w + 1.0f;
-    d_t = (d_t * d_w + tt) / w1;
-    if (with_colour) {
-      c0 = (c0 * d_w + (float)rgb[3 * pix]) / w1;
-      c1 = (c1 * d_w + (float)rgb[3 * pix + 1]) / w1;
-      c2 = (c2 * d_w + (float)rgb[3 * pix + 2]) / w1;
-    }
-    d_w = fminf(w1, max_weight);
-    touched = true;
-  }
+  const bool touched = fuse_frames(px, py, pz, d_t, d_w, c0, c1, c2, with_colour, tau, depth, rgb, frames, n_frames, depth_unit, max_depth,
+                                   max_weight, frustum_skip != 0, s_skip);
   if (!touched) return;
   tsdf[at] = d_t;
   weight[at] = d_w;
@@ -135,6 +155,44 @@ __global__ void __launch_bounds__(FU_THREADS) integrate_kernel(float* __restrict
 // corner numbers (dx + 2 dy + 4 dz) of the 12 edges, lower end first; the axis of edge e is e / 4
 __device__ const int8_t kEdgeA[12] = {0, 2, 4, 6, 0, 1, 4, 5, 0, 1, 2, 3};
 __device__ const int8_t kEdgeB[12] = {1, 3, 5, 7, 2, 3, 6, 7, 4, 5, 6, 7};
+
+// Section K's vertex of the active cell (i, j, k) with corner values d[8], written to row `id`: the one definition, used by the dense
+// and by the block kernel. idx[c] is corner c's element in a colour plane, `plane` the length of one plane.
+__device__ __forceinline__ void write_vertex(const float d[8], const int64_t idx[8], const float* __restrict__ colour, int64_t plane,
+                                             const Volume& vol, int i, int j, int k, int64_t id, float* __restrict__ out_v,
+                                             uint8_t* __restrict__ out_c) {
+  const bool with_colour = colour != nullptr && out_c != nullptr;
+  float sum[3] = {0.0f, 0.0f, 0.0f}, csum[3] = {0.0f, 0.0f, 0.0f};
+  int count = 0;
+#pragma unroll
+  for (int e = 0; e < 12; ++e) {
+    const int a = kEdgeA[e], b = kEdgeB[e];
+    const float da = d[a], db = d[b];
+    if ((da < 0.0f) == (db < 0.0f)) continue;
+    const float s = da / (da - db);
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+      const float pa = (float)((a >> ax) & 1), pb = (float)((b >> ax) & 1);
+      sum[ax] = sum[ax] + (pa + s * (pb - pa));
+    }
+    if (with_colour) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const float ca = colour[ch * plane + idx[a]], cb = colour[ch * plane + idx[b]];
+        csum[ch] = csum[ch] + (ca + s * (cb - ca));
+      }
+    }
+    ++count;
+  }
+  const float n = (float)count;                             // >= 1: an active cell has a crossing
+  out_v[3 * id] = vol.ox + ((float)i + sum[0] / n) * vol.v;
+  out_v[3 * id + 1] = vol.oy + ((float)j + sum[1] / n) * vol.v;
+  out_v[3 * id + 2] = vol.oz + ((float)k + sum[2] / n) * vol.v;
+  if (with_colour) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) out_c[3 * id + ch] = (uint8_t)fminf(fmaxf(floorf(csum[ch] / n + 0.5f), 0.0f), 255.0f);
+  }
+}
 
 __global__ void __launch_bounds__(FU_THREADS) cells_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight,
                                                            const float* __restrict__ colour, Volume vol, float min_weight,
@@ -168,37 +226,7 @@ __global__ void __launch_bounds__(FU_THREADS) cells_kernel(const float* __restri
   }
   const int64_t id = (int64_t)rank[at] - 1;
   if (!is_active || id < 0 || id >= n_vertices) return;
-  const bool with_colour = colour != nullptr && out_c != nullptr;
-  float sum[3] = {0.0f, 0.0f, 0.0f}, csum[3] = {0.0f, 0.0f, 0.0f};
-  int count = 0;
-#pragma unroll
-  for (int e = 0; e < 12; ++e) {
-    const int a = kEdgeA[e], b = kEdgeB[e];
-    const float da = d[a], db = d[b];
-    if ((da < 0.0f) == (db < 0.0f)) continue;
-    const float s = da / (da - db);
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-      const float pa = (float)((a >> ax) & 1), pb = (float)((b >> ax) & 1);
-      sum[ax] = sum[ax] + (pa + s * (pb - pa));
-    }
-    if (with_colour) {
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        const float ca = colour[ch * n_vox + idx[a]], cb = colour[ch * n_vox + idx[b]];
-        csum[ch] = csum[ch] + (ca + s * (cb - ca));
-      }
-    }
-    ++count;
-  }
-  const float n = (float)count;                             // >= 1: an active cell has a crossing
-  out_v[3 * id] = vol.ox + ((float)i + sum[0] / n) * vol.v;
-  out_v[3 * id + 1] = vol.oy + ((float)j + sum[1] / n) * vol.v;
-  out_v[3 * id + 2] = vol.oz + ((float)k + sum[2] / n) * vol.v;
-  if (with_colour) {
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) out_c[3 * id + ch] = (uint8_t)fminf(fmaxf(floorf(csum[ch] / n + 0.5f), 0.0f), 255.0f);
-  }
+  write_vertex(d, idx, colour, n_vox, vol, i, j, k, id, out_v, out_c);
 }
 
 __global__ void __launch_bounds__(FU_THREADS) faces_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight, Volume vol,
@@ -246,6 +274,264 @@ __global__ void __launch_bounds__(FU_THREADS) faces_kernel(const float* __restri
   o[5] = lower_inside ? v3 : v2;
 }
 
+// ---------------------------------------------------------------------------------------------- section K2: the block-sparse volume
+constexpr int SB = 8, SB_VOX = SB * SB * SB;      // a block; SB_VOX threads per workgroup, thread t = voxel t of the block, x fastest
+constexpr int SB_TILE = SB + 2, SB_TILE_N = SB_TILE * SB_TILE * SB_TILE;   // the block and its one-voxel halo, local coordinates -1 .. 8
+constexpr int MK_THREADS = 256;
+
+struct Blocks {
+  int bx, by, bz;        // the block grid, ceil(n / 8) per axis
+  int n_blocks;          // allocated blocks = slots
+};
+
+// Per frame, in double, in this order (tests/tsdf_sparse_restated.py restates it): the inverse of the pose's 3 x 3 part by cofactors,
+// and the world slack per axis. Thread 0 of a workgroup writes them to LDS.
+struct MarkFrame {
+  double inv[9];         // world = inv * (camera - t)
+  double t[3];
+  double slack[3];       // world, per axis: sum_r |inv[a][r]| * FU_SLACK * M_r
+  double su, sv;         // pixels
+};
+
+__device__ void mark_frame(const acez_tsdf_frame& fr, const Volume& vol, MarkFrame& o) {
+  const double r00 = fr.m[0], r01 = fr.m[1], r02 = fr.m[2], r10 = fr.m[4], r11 = fr.m[5], r12 = fr.m[6], r20 = fr.m[8], r21 = fr.m[9], r22 = fr.m[10];
+  const double c00 = r11 * r22 - r12 * r21, c01 = r02 * r21 - r01 * r22, c02 = r01 * r12 - r02 * r11;
+  const double c10 = r12 * r20 - r10 * r22, c11 = r00 * r22 - r02 * r20, c12 = r02 * r10 - r00 * r12;
+  const double c20 = r10 * r21 - r11 * r20, c21 = r01 * r20 - r00 * r21, c22 = r00 * r11 - r01 * r10;
+  const double det = (r00 * c00 + r01 * c10) + r02 * c20;
+  const double c[9] = {c00, c01, c02, c10, c11, c12, c20, c21, c22};
+  for (int e = 0; e < 9; ++e) o.inv[e] = c[e] / det;
+  o.t[0] = fr.m[3];
+  o.t[1] = fr.m[7];
+  o.t[2] = fr.m[11];
+  const double v = vol.v;
+  const double o3[3] = {vol.ox, vol.oy, vol.oz};
+  const int n3[3] = {vol.nx, vol.ny, vol.nz};
+  double A[3], e3[3];
+  for (int a = 0; a < 3; ++a) A[a] = fmax(fabs(o3[a]), fabs(o3[a] + (double)(n3[a] - 1) * v));
+  for (int r = 0; r < 3; ++r) {
+    const double M = ((fabs((double)fr.m[4 * r]) * A[0] + fabs((double)fr.m[4 * r + 1]) * A[1]) + fabs((double)fr.m[4 * r + 2]) * A[2]) + fabs((double)fr.m[4 * r + 3]);
+    e3[r] = FU_SLACK * M;
+  }
+  for (int a = 0; a < 3; ++a) o.slack[a] = (fabs(o.inv[3 * a]) * e3[0] + fabs(o.inv[3 * a + 1]) * e3[1]) + fabs(o.inv[3 * a + 2]) * e3[2];
+  o.su = FU_SLACK * ((fabs((double)fr.ppx) + (double)fr.w) + 1.0);
+  o.sv = FU_SLACK * ((fabs((double)fr.ppy) + (double)fr.h) + 1.0);
+}
+
+// grid (ceil(largest h * w / 256), n_frames): workgroup (x, f) takes 256 pixels of frame f
+__global__ void __launch_bounds__(MK_THREADS) mark_kernel(uint8_t* __restrict__ flags, Volume vol, Blocks bl, float tau,
+                                                          const uint16_t* __restrict__ depth, const acez_tsdf_frame* __restrict__ frames,
+                                                          float depth_unit, float max_depth) {
+  __shared__ MarkFrame s_mf;
+  const acez_tsdf_frame& fr = frames[blockIdx.y];             // uniform address: scalar loads
+  if (threadIdx.x == 0) mark_frame(fr, vol, s_mf);
+  __syncthreads();
+  const int64_t p = (int64_t)blockIdx.x * MK_THREADS + threadIdx.x;
+  if (p >= (int64_t)fr.h * fr.w) return;                      // (after the only barrier)
+  const uint16_t raw = depth[fr.offset + p];                  // in [offset, offset + h * w): the host checked that range
+  if (raw == 0) return;
+  const float d = (float)raw * depth_unit;
+  if (d > max_depth) return;
+  const int ix = (int)(p % fr.w), iy = (int)(p / fr.w);
+  const double dd = d, f = fr.focal;
+  const double sd = FU_SLACK * (dd + (double)tau);
+  const double zs[2] = {fmax(dd - sd, 0.0), (dd + (double)tau) + sd};
+  const double us[2] = {((double)ix - 0.5) - s_mf.su, ((double)ix + 0.5) + s_mf.su};
+  const double ws[2] = {((double)iy - 0.5) - s_mf.sv, ((double)iy + 0.5) + s_mf.sv};
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int c = 0; c < 8; ++c) {
+    const double z = zs[c >> 2];
+    const double x = ((us[c & 1] - (double)fr.ppx) / f) * z, y = ((ws[(c >> 1) & 1] - (double)fr.ppy) / f) * z;
+    const double qx = x - s_mf.t[0], qy = y - s_mf.t[1], qz = z - s_mf.t[2];
+    for (int a = 0; a < 3; ++a) {
+      const double wa = (s_mf.inv[3 * a] * qx + s_mf.inv[3 * a + 1] * qy) + s_mf.inv[3 * a + 2] * qz;
+      lo[a] = fmin(lo[a], wa);
+      hi[a] = fmax(hi[a], wa);
+    }
+  }
+  const double v = vol.v;
+  const double o3[3] = {vol.ox, vol.oy, vol.oz};
+  const int n3[3] = {vol.nx, vol.ny, vol.nz};
+  int b0[3], b1[3];
+  for (int a = 0; a < 3; ++a) {
+    const double first = fmax(floor(((lo[a] - s_mf.slack[a]) - o3[a]) / v) - 1.0, 0.0);
+    const double last = fmin(ceil(((hi[a] + s_mf.slack[a]) - o3[a]) / v) + 1.0, (double)(n3[a] - 1));
+    if (!(first <= last)) return;                             // the box misses the grid (or is not a number)
+    b0[a] = (int)first >> 3;
+    b1[a] = (int)last >> 3;
+  }
+  for (int bk = b0[2]; bk <= b1[2]; ++bk)
+    for (int bj = b0[1]; bj <= b1[1]; ++bj)
+      for (int bi = b0[0]; bi <= b1[0]; ++bi) flags[((int64_t)bk * bl.by + bj) * bl.bx + bi] = 1;
+}
+
+__global__ void __launch_bounds__(SB_VOX) integrate_blocks_kernel(float* __restrict__ tsdf, float* __restrict__ weight, float* __restrict__ colour,
+                                                                  const int32_t* __restrict__ slot_blocks, Volume vol, Blocks bl, float tau,
+                                                                  const uint16_t* __restrict__ depth, const uint8_t* __restrict__ rgb,
+                                                                  const acez_tsdf_frame* __restrict__ frames, int n_frames, float depth_unit,
+                                                                  float max_depth, float max_weight, int frustum_skip) {
+  __shared__ uint8_t s_skip[ACEZ_TSDF_MAX_FRAMES];
+  const int t = threadIdx.x;
+  const int64_t b = slot_blocks[blockIdx.x];                  // uniform
+  if (b < 0 || b >= (int64_t)bl.bx * bl.by * bl.bz) return;   // not a block of this grid: nothing is read or written (uniform)
+  const int i0 = (int)(b % bl.bx) * SB, j0 = (int)((b / bl.bx) % bl.by) * SB, k0 = (int)(b / ((int64_t)bl.bx * bl.by)) * SB;
+  if (frustum_skip) {
+    if (t < n_frames) {
+      const int i1 = min(i0 + SB, vol.nx) - 1, j1 = min(j0 + SB, vol.ny) - 1, k1 = min(k0 + SB, vol.nz) - 1;
+      const double v = vol.v;
+      const double lo[3] = {vol.ox + i0 * v, vol.oy + j0 * v, vol.oz + k0 * v};
+      const double hi[3] = {vol.ox + i1 * v, vol.oy + j1 * v, vol.oz + k1 * v};
+      s_skip[t] = brick_outside(frames[t], lo, hi) ? 1 : 0;
+    }
+    __syncthreads();
+  }
+  const int i = i0 + (t & 7), j = j0 + ((t >> 3) & 7), k = k0 + (t >> 6);
+  if (i >= vol.nx || j >= vol.ny || k >= vol.nz) return;   // (after the only barrier) a partial block's voxels beyond the grid
+  const int64_t plane = (int64_t)bl.n_blocks * SB_VOX;
+  const int64_t at = (int64_t)blockIdx.x * SB_VOX + t;
+  const float px = vol.ox + (float)i * vol.v;
+  const float py = vol.oy + (float)j * vol.v;
+  const float pz = vol.oz + (float)k * vol.v;
+  float d_t = tsdf[at], d_w = weight[at];
+  float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
+  const bool with_colour = colour != nullptr && rgb != nullptr;
+  if (with_colour) {
+    c0 = colour[at];
+    c1 = colour[plane + at];
+    c2 = colour[2 * plane + at];
+  }
+  const bool touched = fuse_frames(px, py, pz, d_t, d_w, c0, c1, c2, with_colour, tau, depth, rgb, frames, n_frames, depth_unit, max_depth,
+                                   max_weight, frustum_skip != 0, s_skip);
+  if (!touched) return;
+  tsdf[at] = d_t;
+  weight[at] = d_w;
+  if (with_colour) {
+    colour[at] = c0;
+    colour[plane + at] = c1;
+    colour[2 * plane + at] = c2;
+  }
+}
+
+__device__ __forceinline__ int tile_at(int li, int lj, int lk) { return ((lk + 1) * SB_TILE + (lj + 1)) * SB_TILE + (li + 1); }
+
+// The storage element (slot * 512 + voxel) of every voxel of the 10^3 tile around the block at (i0, j0, k0), -1 for a voxel outside
+// the grid, in a block without a slot or with a table entry that is no slot (>= n_blocks). Ends with a barrier.
+__device__ void load_tile_offsets(const int32_t* __restrict__ table, const Volume& vol, const Blocks& bl, int i0, int j0, int k0,
+                                  int32_t* s_off) {
+  for (int e = threadIdx.x; e < SB_TILE_N; e += SB_VOX) {
+    const int gi = i0 + e % SB_TILE - 1, gj = j0 + (e / SB_TILE) % SB_TILE - 1, gk = k0 + e / (SB_TILE * SB_TILE) - 1;
+    int32_t off = -1;
+    if (gi >= 0 && gj >= 0 && gk >= 0 && gi < vol.nx && gj < vol.ny && gk < vol.nz) {
+      const int32_t slot = table[((int64_t)(gk >> 3) * bl.by + (gj >> 3)) * bl.bx + (gi >> 3)];
+      if (slot >= 0 && slot < bl.n_blocks) off = slot * SB_VOX + ((gk & 7) * SB + (gj & 7)) * SB + (gi & 7);
+    }
+    s_off[e] = off;
+  }
+  __syncthreads();
+}
+
+__global__ void __launch_bounds__(SB_VOX) cells_blocks_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight,
+                                                              const float* __restrict__ colour, const int32_t* __restrict__ table,
+                                                              const int32_t* __restrict__ slot_blocks, Volume vol, Blocks bl, float min_weight,
+                                                              uint8_t* __restrict__ active, const int32_t* __restrict__ rank,
+                                                              float* __restrict__ out_v, uint8_t* __restrict__ out_c, int64_t n_vertices) {
+  __shared__ int32_t s_off[SB_TILE_N];
+  __shared__ float s_t[SB_TILE_N], s_w[SB_TILE_N];
+  const int t = threadIdx.x;
+  const int64_t at = (int64_t)blockIdx.x * SB_VOX + t;
+  const int64_t b = slot_blocks[blockIdx.x];                  // uniform
+  if (b < 0 || b >= (int64_t)bl.bx * bl.by * bl.bz) {          // not a block of this grid (uniform)
+    if (!rank) active[at] = 0;
+    return;
+  }
+  const int i0 = (int)(b % bl.bx) * SB, j0 = (int)((b / bl.bx) % bl.by) * SB, k0 = (int)(b / ((int64_t)bl.bx * bl.by)) * SB;
+  load_tile_offsets(table, vol, bl, i0, j0, k0, s_off);
+  for (int e = t; e < SB_TILE_N; e += SB_VOX) {
+    const int32_t off = s_off[e];
+    s_t[e] = off >= 0 ? tsdf[off] : 1.0f;
+    s_w[e] = off >= 0 ? weight[off] : 0.0f;                    // unknown: min_weight > 0
+  }
+  __syncthreads();
+  const int li = t & 7, lj = (t >> 3) & 7, lk = t >> 6;
+  if (rank && !active[at]) return;
+  float d[8];
+  int64_t idx[8];
+  bool known = true;
+  int inside = 0;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const int e = tile_at(li + (c & 1), lj + ((c >> 1) & 1), lk + (c >> 2));
+    idx[c] = s_off[e];
+    d[c] = s_t[e];
+    known = known && (s_w[e] >= min_weight);
+    inside += d[c] < 0.0f ? 1 : 0;
+  }
+  const bool is_active = known && inside != 0 && inside != 8;
+  if (!rank) {
+    active[at] = is_active ? 1 : 0;
+    return;
+  }
+  const int64_t id = (int64_t)rank[at] - 1;
+  if (!is_active || id < 0 || id >= n_vertices) return;
+  write_vertex(d, idx, colour, (int64_t)bl.n_blocks * SB_VOX, vol, i0 + li, j0 + lj, k0 + lk, id, out_v, out_c);
+}
+
+__global__ void __launch_bounds__(SB_VOX) faces_blocks_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight,
+                                                              const int32_t* __restrict__ table, const int32_t* __restrict__ slot_blocks,
+                                                              Volume vol, Blocks bl, float min_weight, const uint8_t* __restrict__ active,
+                                                              uint8_t* __restrict__ flags, const int32_t* __restrict__ vrank,
+                                                              const int32_t* __restrict__ erank, int32_t* __restrict__ out_f, int64_t n_faces) {
+  __shared__ int32_t s_off[SB_TILE_N];
+  __shared__ float s_t[SB_TILE_N], s_w[SB_TILE_N];
+  __shared__ uint8_t s_a[SB_TILE_N];
+  const int t = threadIdx.x;
+  const int64_t plane = (int64_t)bl.n_blocks * SB_VOX;
+  const int64_t at = (int64_t)blockIdx.x * SB_VOX + t;
+  const int64_t b = slot_blocks[blockIdx.x];                  // uniform
+  if (b < 0 || b >= (int64_t)bl.bx * bl.by * bl.bz) {          // not a block of this grid (uniform)
+    if (!erank)
+      for (int axis = 0; axis < 3; ++axis) flags[axis * plane + at] = 0;
+    return;
+  }
+  const int i0 = (int)(b % bl.bx) * SB, j0 = (int)((b / bl.bx) % bl.by) * SB, k0 = (int)(b / ((int64_t)bl.bx * bl.by)) * SB;
+  load_tile_offsets(table, vol, bl, i0, j0, k0, s_off);
+  for (int e = t; e < SB_TILE_N; e += SB_VOX) {
+    const int32_t off = s_off[e];
+    s_t[e] = off >= 0 ? tsdf[off] : 1.0f;
+    s_w[e] = off >= 0 ? weight[off] : 0.0f;
+    s_a[e] = off >= 0 ? active[off] : 0;                       // a cell outside the grid or in a block without a slot is not active
+  }
+  __syncthreads();
+  const int l[3] = {t & 7, (t >> 3) & 7, t >> 6};
+  const int step[3] = {1, SB_TILE, SB_TILE * SB_TILE};
+  const int here = tile_at(l[0], l[1], l[2]);
+#pragma unroll
+  for (int axis = 0; axis < 3; ++axis) {
+    const int64_t e = axis * plane + at;
+    if (erank && !flags[e]) continue;
+    const int bb = (axis + 1) % 3, cc = (axis + 2) % 3;
+    const int hi = here + step[axis];
+    const int cell[4] = {here - step[bb] - step[cc], here - step[cc], here, here - step[bb]};
+    const bool lower_inside = s_t[here] < 0.0f;
+    const bool quad = s_w[here] >= min_weight && s_w[hi] >= min_weight && lower_inside != (s_t[hi] < 0.0f) && s_a[cell[0]] && s_a[cell[1]] &&
+                      s_a[cell[2]] && s_a[cell[3]];
+    if (!erank) {
+      flags[e] = quad ? 1 : 0;
+      continue;
+    }
+    const int64_t row = 2 * ((int64_t)erank[e] - 1);
+    if (!quad || row < 0 || row + 2 > n_faces) continue;
+    const int32_t v0 = vrank[s_off[cell[0]]] - 1, v1 = vrank[s_off[cell[1]]] - 1, v2 = vrank[s_off[cell[2]]] - 1, v3 = vrank[s_off[cell[3]]] - 1;
+    int32_t* o = out_f + 3 * row;
+    o[0] = v0;
+    o[1] = lower_inside ? v1 : v2;
+    o[2] = lower_inside ? v2 : v1;
+    o[3] = v0;
+    o[4] = lower_inside ? v2 : v3;
+    o[5] = lower_inside ? v3 : v2;
+  }
+}
+
 bool finite_all(const float* p, int n) {
   for (int i = 0; i < n; ++i)
     if (!isfinite(p[i])) return false;
@@ -257,6 +543,18 @@ bool finite_all(const float* p, int n) {
 #define FU_REQUIRE_DIMS(limit)                                                                                        \
   ACEZ_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1, "volume dimensions must be at least 1");                                \
   ACEZ_REQUIRE((int64_t)nx * ny <= (limit) && (int64_t)nx * ny * nz <= (limit), "volume too large for 32-bit voxel indices")
+
+// the frame table's rows: what bounds every index a kernel forms from them
+static int check_frames(const acez_tsdf_frame* h_frames, int n_frames, int64_t n_pixels) {
+  for (int f = 0; f < n_frames; ++f) {
+    const acez_tsdf_frame& fr = h_frames[f];
+    ACEZ_REQUIRE(fr.h >= 1 && fr.w >= 1 && fr.h <= FU_MAX_SIDE && fr.w <= FU_MAX_SIDE, "frame size out of range (1 .. 32768 px per side)");
+    ACEZ_REQUIRE(finite_all(fr.m, 12) && isfinite(fr.focal) && isfinite(fr.ppx) && isfinite(fr.ppy), "non-finite pose or intrinsics in the frame table");
+    ACEZ_REQUIRE(fr.focal > 0.0f, "focal length must be positive");
+    ACEZ_REQUIRE(fr.offset >= 0 && fr.offset <= n_pixels && (int64_t)fr.h * fr.w <= n_pixels - fr.offset, "frame past the end of the depth buffer");
+  }
+  return ACEZ_OK;
+}
 
 extern "C" int acez_tsdf_integrate(float* d_tsdf, float* d_weight, float* d_colour, int nx, int ny, int nz, float ox, float oy, float oz,
                                    float voxel_size, float truncation, const uint16_t* d_depth, const uint8_t* d_rgb, int64_t n_pixels,
@@ -271,13 +569,7 @@ extern "C" int acez_tsdf_integrate(float* d_tsdf, float* d_weight, float* d_colo
   ACEZ_REQUIRE(depth_unit > 0.0f && max_depth > 0.0f && max_weight > 0.0f, "depth unit, depth limit and weight cap must be positive");
   ACEZ_REQUIRE(n_frames >= 0 && n_frames <= ACEZ_TSDF_MAX_FRAMES, "frame count out of range (0 .. 256 per call)");
   ACEZ_REQUIRE(n_pixels >= 0, "negative depth buffer length");
-  for (int f = 0; f < n_frames; ++f) {
-    const acez_tsdf_frame& fr = h_frames[f];
-    ACEZ_REQUIRE(fr.h >= 1 && fr.w >= 1 && fr.h <= FU_MAX_SIDE && fr.w <= FU_MAX_SIDE, "frame size out of range (1 .. 32768 px per side)");
-    ACEZ_REQUIRE(finite_all(fr.m, 12) && isfinite(fr.focal) && isfinite(fr.ppx) && isfinite(fr.ppy), "non-finite pose or intrinsics in the frame table");
-    ACEZ_REQUIRE(fr.focal > 0.0f, "focal length must be positive");
-    ACEZ_REQUIRE(fr.offset >= 0 && fr.offset <= n_pixels && (int64_t)fr.h * fr.w <= n_pixels - fr.offset, "frame past the end of the depth buffer");
-  }
+  if (int rc = check_frames(h_frames, n_frames, n_pixels)) return rc;
   ACEZ_REQUIRE((ny + FU_BY - 1) / FU_BY <= 65535 && (nz + FU_BZ - 1) / FU_BZ <= 65535, "volume too large (more than 65535 bricks along y or z)");
   if (int rc = acez::require_device("TSDF integration runs on a gfx950 GPU")) return rc;
   if (n_frames == 0) return ACEZ_OK;
@@ -323,6 +615,124 @@ extern "C" int acez_tsdf_faces(const float* d_tsdf, const float* d_weight, int n
   const Volume vol{nx, ny, nz, 0.0f, 0.0f, 0.0f, 1.0f};
   hipLaunchKernelGGL(faces_kernel, dim3((unsigned)((n_edges + FU_THREADS - 1) / FU_THREADS)), dim3(FU_THREADS), 0, (hipStream_t)stream, d_tsdf,
                      d_weight, vol, min_weight, d_active, d_edge_flags, d_vertex_rank, d_edge_rank, d_out_faces, n_faces);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- section K2: the block-sparse volume
+// the virtual grid and its block grid; fills `bl`
+static int check_block_grid(int nx, int ny, int nz, float ox, float oy, float oz, float voxel_size, int n_blocks, Blocks* bl) {
+  ACEZ_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1, "volume dimensions must be at least 1");
+  ACEZ_REQUIRE(isfinite(ox) && isfinite(oy) && isfinite(oz) && isfinite(voxel_size) && voxel_size > 0.0f, "voxel size must be positive, the origin finite");
+  const int64_t bx = ((int64_t)nx + SB - 1) / SB, by = ((int64_t)ny + SB - 1) / SB, bz = ((int64_t)nz + SB - 1) / SB;
+  ACEZ_REQUIRE(bx * by < ((int64_t)1 << 31) && bx * by * bz < ((int64_t)1 << 31), "block grid too large (2^31 blocks or more)");
+  ACEZ_REQUIRE(n_blocks >= 0, "negative block count");
+  ACEZ_REQUIRE(n_blocks <= bx * by * bz, "more blocks than the block grid has");
+  *bl = Blocks{(int)bx, (int)by, (int)bz, n_blocks};
+  return ACEZ_OK;
+}
+
+extern "C" int acez_tsdf_mark(uint8_t* d_block_flags, int nx, int ny, int nz, float ox, float oy, float oz, float voxel_size, float truncation,
+                              const uint16_t* d_depth, int64_t n_pixels, const acez_tsdf_frame* h_frames, int n_frames,
+                              acez_tsdf_frame* d_frames, float depth_unit, float max_depth, void* stream) {
+  ACEZ_REQUIRE(d_block_flags && d_depth && h_frames && d_frames, "null pointer");
+  Blocks bl;
+  if (int rc = check_block_grid(nx, ny, nz, ox, oy, oz, voxel_size, 0, &bl)) return rc;
+  const float scal[3] = {truncation, depth_unit, max_depth};
+  ACEZ_REQUIRE(finite_all(scal, 3), "non-finite truncation, depth unit or depth limit");
+  ACEZ_REQUIRE(truncation > 0.0f, "voxel size and truncation must be positive");
+  ACEZ_REQUIRE(depth_unit > 0.0f && max_depth > 0.0f, "depth unit and depth limit must be positive");
+  ACEZ_REQUIRE(n_frames >= 0 && n_frames <= ACEZ_TSDF_MAX_FRAMES, "frame count out of range (0 .. 256 per call)");
+  ACEZ_REQUIRE(n_pixels >= 0, "negative depth buffer length");
+  if (int rc = check_frames(h_frames, n_frames, n_pixels)) return rc;
+  int64_t most = 0;
+  for (int f = 0; f < n_frames; ++f) {
+    const float* m = h_frames[f].m;
+    const double det = ((double)m[0] * ((double)m[5] * m[10] - (double)m[6] * m[9]) + (double)m[1] * ((double)m[6] * m[8] - (double)m[4] * m[10])) +
+                       (double)m[2] * ((double)m[4] * m[9] - (double)m[5] * m[8]);
+    ACEZ_REQUIRE(isfinite(det) && fabs(det) >= 1e-6, "singular pose in the frame table");
+    most = most > (int64_t)h_frames[f].h * h_frames[f].w ? most : (int64_t)h_frames[f].h * h_frames[f].w;
+  }
+  if (int rc = acez::require_device("marking TSDF blocks runs on a gfx950 GPU")) return rc;
+  if (n_frames == 0) return ACEZ_OK;
+  hipStream_t s = (hipStream_t)stream;
+  ACEZ_HIP_CHECK(hipMemcpyAsync(d_frames, h_frames, sizeof(acez_tsdf_frame) * (size_t)n_frames, hipMemcpyHostToDevice, s));
+  ACEZ_HIP_CHECK(hipStreamSynchronize(s));   // h_frames is the caller's again
+  const Volume vol{nx, ny, nz, ox, oy, oz, voxel_size};
+  hipLaunchKernelGGL(mark_kernel, dim3((unsigned)((most + MK_THREADS - 1) / MK_THREADS), (unsigned)n_frames), dim3(MK_THREADS), 0, s, d_block_flags,
+                     vol, bl, truncation, d_depth, (const acez_tsdf_frame*)d_frames, depth_unit, max_depth);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}
+
+extern "C" int acez_tsdf_integrate_blocks(float* d_tsdf, float* d_weight, float* d_colour, const int32_t* d_slot_blocks, int n_blocks, int nx,
+                                          int ny, int nz, float ox, float oy, float oz, float voxel_size, float truncation,
+                                          const uint16_t* d_depth, const uint8_t* d_rgb, int64_t n_pixels, const acez_tsdf_frame* h_frames,
+                                          int n_frames, acez_tsdf_frame* d_frames, float depth_unit, float max_depth, float max_weight,
+                                          int frustum_skip, void* stream) {
+  ACEZ_REQUIRE(d_tsdf && d_weight && d_slot_blocks && d_depth && h_frames && d_frames, "null pointer");
+  ACEZ_REQUIRE(!d_rgb || d_colour, "colour images without a colour volume");
+  Blocks bl;
+  if (int rc = check_block_grid(nx, ny, nz, ox, oy, oz, voxel_size, n_blocks, &bl)) return rc;
+  const float scal[4] = {truncation, depth_unit, max_depth, max_weight};
+  ACEZ_REQUIRE(finite_all(scal, 4), "non-finite truncation, depth unit, depth limit or weight cap");
+  ACEZ_REQUIRE(truncation > 0.0f, "voxel size and truncation must be positive");
+  ACEZ_REQUIRE(depth_unit > 0.0f && max_depth > 0.0f && max_weight > 0.0f, "depth unit, depth limit and weight cap must be positive");
+  ACEZ_REQUIRE(n_frames >= 0 && n_frames <= ACEZ_TSDF_MAX_FRAMES, "frame count out of range (0 .. 256 per call)");
+  ACEZ_REQUIRE(n_pixels >= 0, "negative depth buffer length");
+  if (int rc = check_frames(h_frames, n_frames, n_pixels)) return rc;
+  if (int rc = acez::require_device("TSDF integration runs on a gfx950 GPU")) return rc;
+  if (n_frames == 0 || n_blocks == 0) return ACEZ_OK;
+  hipStream_t s = (hipStream_t)stream;
+  ACEZ_HIP_CHECK(hipMemcpyAsync(d_frames, h_frames, sizeof(acez_tsdf_frame) * (size_t)n_frames, hipMemcpyHostToDevice, s));
+  ACEZ_HIP_CHECK(hipStreamSynchronize(s));   // h_frames is the caller's again
+  const Volume vol{nx, ny, nz, ox, oy, oz, voxel_size};
+  hipLaunchKernelGGL(integrate_blocks_kernel, dim3((unsigned)n_blocks), dim3(SB_VOX), 0, s, d_tsdf, d_weight, d_colour, d_slot_blocks, vol, bl,
+                     truncation, d_depth, d_rgb, (const acez_tsdf_frame*)d_frames, n_frames, depth_unit, max_depth, max_weight, frustum_skip);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}
+
+// the extraction's outputs are indexed in 32 bits: [3][n_blocks][512] edge flags and their int32 prefix sum
+#define FU_REQUIRE_BLOCK_COUNT() \
+  ACEZ_REQUIRE((int64_t)n_blocks * SB_VOX <= (((int64_t)1 << 31) - 1) / 3, "too many blocks for 32-bit voxel indices")
+
+extern "C" int acez_tsdf_cells_blocks(const float* d_tsdf, const float* d_weight, const float* d_colour, const int32_t* d_block_table,
+                                      const int32_t* d_slot_blocks, int n_blocks, int nx, int ny, int nz, float ox, float oy, float oz,
+                                      float voxel_size, float min_weight, uint8_t* d_active, const int32_t* d_vertex_rank,
+                                      float* d_out_vertices, uint8_t* d_out_colours, int64_t n_vertices, void* stream) {
+  ACEZ_REQUIRE(d_tsdf && d_weight && d_block_table && d_slot_blocks && d_active, "null pointer");
+  Blocks bl;
+  if (int rc = check_block_grid(nx, ny, nz, ox, oy, oz, voxel_size, n_blocks, &bl)) return rc;
+  FU_REQUIRE_BLOCK_COUNT();
+  ACEZ_REQUIRE(min_weight > 0.0f, "min_weight must be positive (a voxel without a block has weight 0)");
+  ACEZ_REQUIRE(n_vertices >= 0, "negative vertex count");
+  ACEZ_REQUIRE(!d_vertex_rank || n_vertices == 0 || d_out_vertices, "vertex ranks without a vertex buffer");
+  if (int rc = acez::require_device("mesh extraction runs on a gfx950 GPU")) return rc;
+  if (n_blocks == 0 || (d_vertex_rank && n_vertices == 0)) return ACEZ_OK;
+  const Volume vol{nx, ny, nz, ox, oy, oz, voxel_size};
+  hipLaunchKernelGGL(cells_blocks_kernel, dim3((unsigned)n_blocks), dim3(SB_VOX), 0, (hipStream_t)stream, d_tsdf, d_weight, d_colour,
+                     d_block_table, d_slot_blocks, vol, bl, min_weight, d_active, d_vertex_rank, d_out_vertices, d_out_colours, n_vertices);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}
+
+extern "C" int acez_tsdf_faces_blocks(const float* d_tsdf, const float* d_weight, const int32_t* d_block_table, const int32_t* d_slot_blocks,
+                                      int n_blocks, int nx, int ny, int nz, float min_weight, const uint8_t* d_active, uint8_t* d_edge_flags,
+                                      const int32_t* d_vertex_rank, const int32_t* d_edge_rank, int32_t* d_out_faces, int64_t n_faces,
+                                      void* stream) {
+  ACEZ_REQUIRE(d_tsdf && d_weight && d_block_table && d_slot_blocks && d_active && d_edge_flags, "null pointer");
+  Blocks bl;
+  if (int rc = check_block_grid(nx, ny, nz, 0.0f, 0.0f, 0.0f, 1.0f, n_blocks, &bl)) return rc;
+  FU_REQUIRE_BLOCK_COUNT();
+  ACEZ_REQUIRE(min_weight > 0.0f, "min_weight must be positive (a voxel without a block has weight 0)");
+  ACEZ_REQUIRE(n_faces >= 0, "negative face count");
+  ACEZ_REQUIRE(!d_edge_rank || n_faces == 0 || (d_vertex_rank && d_out_faces), "edge ranks without vertex ranks or a face buffer");
+  if (int rc = acez::require_device("mesh extraction runs on a gfx950 GPU")) return rc;
+  if (n_blocks == 0 || (d_edge_rank && n_faces == 0)) return ACEZ_OK;
+  const Volume vol{nx, ny, nz, 0.0f, 0.0f, 0.0f, 1.0f};
+  hipLaunchKernelGGL(faces_blocks_kernel, dim3((unsigned)n_blocks), dim3(SB_VOX), 0, (hipStream_t)stream, d_tsdf, d_weight, d_block_table,
+                     d_slot_blocks, vol, bl, min_weight, d_active, d_edge_flags, d_vertex_rank, d_edge_rank, d_out_faces, n_faces);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
 }

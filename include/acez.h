@@ -851,6 +851,86 @@ int acez_tsdf_faces(const float* d_tsdf, const float* d_weight, int nx, int ny, 
                     int64_t n_faces, void* stream);
 
 /* =====================================================================================================
+ * K2. The same fusion on a block-sparse volume: scenes whose dense volume does not fit (fuse_depth.py --sparse True)
+ * =====================================================================================================
+ * The VIRTUAL grid is section K's: origin, nx x ny x nz, v, tau; nothing of its size is ever stored but one byte (mark) and one int32
+ * (table) per BLOCK. A block is 8 x 8 x 8 voxels; the block grid has bx = ceil(nx / 8), by, bz blocks, block (bi, bj, bk) has the
+ * linear index (bk * by + bj) * bx + bi (x fastest) and holds the voxels 8 bi .. 8 bi + 7 (and alike). A block grid of 2^31 entries
+ * or more is refused. Blocks that get storage are numbered by SLOTS 0 .. n_blocks - 1 in ascending block index:
+ *   d_block_table  int32 [bz][by][bx]                the block's slot, or -1 (any value outside 0 .. n_blocks - 1 reads as -1)
+ *   d_slot_blocks  int32 [n_blocks]                  the slot's block index (a value that is no block index: the slot is passed over,
+ *                                                    nothing of it is read or written)
+ *   d_tsdf, d_weight  float32 [n_blocks][8][8][8]    voxel (i, j, k) is element (k & 7) * 64 + (j & 7) * 8 + (i & 7) of its block's slot
+ *   d_colour       float32 [3][n_blocks][8][8][8]    optional
+ * The caller clears the storage as in section K (finite tsdf, weight 0 = never observed). The table lives in device memory, so a bad
+ * entry cannot be refused on the host without a synchronisation per call; the kernels bound every index they form from it instead.
+ * Voxels of a block beyond nx, ny, nz are never written and read as unknown. A voxel of a block without a slot is UNKNOWN.
+ *
+ * MARK (acez_tsdf_mark) decides where blocks are needed. One thread per depth pixel (ix, iy) of the call's frames (table and packed
+ * buffer as in acez_tsdf_integrate). raw == 0 or d = float(raw) * depth_unit > max_depth (fp32, step 6) marks nothing. Otherwise,
+ * everything in DOUBLE, one rounding per operation in the order written (R = the row's 3 x 3 part, t = m3, m7, m11; S = 1e-5):
+ *   per frame   C = the transposed cofactors of R, each a difference of two products: C00 = R11 R22 - R12 R21, C01 = R02 R21 - R01 R22,
+ *               C02 = R01 R12 - R02 R11, C10 = R12 R20 - R10 R22, C11 = R00 R22 - R02 R20, C12 = R02 R10 - R00 R12,
+ *               C20 = R10 R21 - R11 R20, C21 = R01 R20 - R00 R21, C22 = R00 R11 - R01 R10; det = (R00 C00 + R01 C10) + R02 C20;
+ *               I = C / det (nine divisions; |det| < 1e-6 is refused on the host)
+ *               A_c = max(|o_c|, |o_c + double(n_c - 1) * v|)                 (how far a voxel centre is from 0, per world axis c)
+ *               M_r = ((|R_r0| A_0 + |R_r1| A_1) + |R_r2| A_2) + |t_r|,  e_r = S * M_r      (camera axis r)
+ *               s_a = (|I_a0| e_0 + |I_a1| e_1) + |I_a2| e_2                               (world axis a)
+ *               su = S * ((|ppx| + double(w)) + 1),  sv = S * ((|ppy| + double(h)) + 1)
+ *   per pixel   sd = S * (d + tau);  z in { max(d - sd, 0), (d + tau) + sd };  u in { (ix - 0.5) - su, (ix + 0.5) + su };
+ *               w_ in { (iy - 0.5) - sv, (iy + 0.5) + sv }
+ *               the eight corners: x = ((u - ppx) / focal) * z, y = ((w_ - ppy) / focal) * z,
+ *               world_a = (I_a0 (x - t_0) + I_a1 (y - t_1)) + I_a2 (z - t_2);  lo_a, hi_a = their min and max
+ *               first_a = max(floor(((lo_a - s_a) - o_a) / v) - 1, 0),  last_a = min(ceil(((hi_a + s_a) - o_a) / v) + 1, n_a - 1)
+ *               nothing unless first_a <= last_a on every axis; else d_block_flags[block] := 1 for every block of
+ *               first_a >> 3 .. last_a >> 3. Flags are only ever set: the caller clears d_block_flags uint8 [bz][by][bx] once, and
+ *               any number of calls in any split of the frames leaves the same bytes. Plain stores of the same value, no atomics.
+ * Why this is a SUPERSET of what the dense extraction reads (min_weight > 0). (1) tsdf < 0 with weight > 0 needs a frame whose step 8
+ * gave t < 0, that is sdf in [-tau, 0): the mean of values >= 0 is not negative. (2) For that frame the voxel's fp32 triple
+ * T = (xc, yc, zc) has floor(u + 0.5) = ix, so (focal xc) / zc + ppx is in [ix - 0.5, ix + 0.5] up to the three roundings of step 4
+ * and the one of u + 0.5, each below 2^-23 of |u - ppx| + |u| + 1 <= 2 (|ppx| + w + 1): within su, some forty times that; d - zc is in
+ * [-tau, 0) up to one rounding of d + tau: within sd. So T lies in the widened cell, the convex hull of the eight corners (z >= 0).
+ * (3) The voxel's exact centre P = o + index * v has the exact camera point Q = R P + t, and |Q_r - T_r| <= e_r: step 1 rounds twice
+ * (2^-23 of A), step 2 four times (2^-22 of M_r), against S = 1e-5, the margin section K's frustum skip takes. P = I (Q - t) =
+ * I (T - t) + I (Q - T) then lies in the corners' box widened by s_a. (4) first / last widen by one more voxel, so the box holds the
+ * voxel and its 26 neighbours. (5) An active cell has an inside corner, and its eight corners are among that corner's neighbours; a
+ * quad's edge has an inside end, and the four cells around the edge hold both ends, so all their corners are that end's neighbours.
+ * Every voxel the dense extraction reads to make a vertex or a face therefore lies in a marked block, and a cell with a corner in an
+ * unmarked block is inactive in the dense volume too (it would need an inside corner, whose neighbours are all marked).
+ * ACEZ_ERR_INVALID as in acez_tsdf_integrate (null pointer, dimension < 1, v, tau, depth_unit, max_depth not > 0, the frame table's
+ * rows, an offset past the buffer), for the block-grid limit and for a singular pose.
+ *
+ * INTEGRATE (acez_tsdf_integrate_blocks). One workgroup of 512 threads per slot, thread = voxel of the block, x fastest. Every voxel
+ * whose global index (i, j, k) lies inside nx, ny, nz runs section K's steps 1-9 over the call's frames, with the GLOBAL index in
+ * step 1; it is the same device function as the dense kernel's. The frustum skip is section K's, on the block's box. The voxels of
+ * the allocated blocks therefore hold the dense volume's bits, whatever the split into calls. Arguments and refusals as in
+ * acez_tsdf_integrate, plus n_blocks < 0 or > bx by bz and the block-grid limit; n_blocks = 0 does nothing.
+ *
+ * EXTRACT (acez_tsdf_cells_blocks, acez_tsdf_faces_blocks): section K's cells, vertices, colours, quads and orientation, with
+ * "unknown" extended to voxels outside the grid and voxels of blocks without a slot; min_weight must be > 0. One workgroup per slot
+ * loads the block and its one-voxel halo through the table. The two modes and the prefix sums between them are section K's, over
+ *   d_active, d_vertex_rank   [n_blocks][8][8][8]       d_edge_flags, d_edge_rank   [3][n_blocks][8][8][8]
+ * so vertex ids ascend by block index, then by voxel index inside the block, and faces are axis-major, then in that order. A cell's
+ * vertex is o + (float(global index) + mean) * v. The mesh is the dense mesh with its rows in another order, if every block the
+ * dense extraction reads has a slot (MARK). ACEZ_ERR_INVALID as in acez_tsdf_cells / acez_tsdf_faces, plus min_weight not > 0,
+ * n_blocks < 0 or > bx by bz, n_blocks * 512 >= 2^31 / 3 and the block-grid limit. */
+int acez_tsdf_mark(uint8_t* d_block_flags, int nx, int ny, int nz, float ox, float oy, float oz, float voxel_size, float truncation,
+                   const uint16_t* d_depth, int64_t n_pixels, const acez_tsdf_frame* h_frames, int n_frames, acez_tsdf_frame* d_frames,
+                   float depth_unit, float max_depth, void* stream);
+int acez_tsdf_integrate_blocks(float* d_tsdf, float* d_weight, float* d_colour, const int32_t* d_slot_blocks, int n_blocks, int nx, int ny,
+                               int nz, float ox, float oy, float oz, float voxel_size, float truncation, const uint16_t* d_depth,
+                               const uint8_t* d_rgb, int64_t n_pixels, const acez_tsdf_frame* h_frames, int n_frames,
+                               acez_tsdf_frame* d_frames, float depth_unit, float max_depth, float max_weight, int frustum_skip,
+                               void* stream);
+int acez_tsdf_cells_blocks(const float* d_tsdf, const float* d_weight, const float* d_colour, const int32_t* d_block_table,
+                           const int32_t* d_slot_blocks, int n_blocks, int nx, int ny, int nz, float ox, float oy, float oz,
+                           float voxel_size, float min_weight, uint8_t* d_active, const int32_t* d_vertex_rank, float* d_out_vertices,
+                           uint8_t* d_out_colours, int64_t n_vertices, void* stream);
+int acez_tsdf_faces_blocks(const float* d_tsdf, const float* d_weight, const int32_t* d_block_table, const int32_t* d_slot_blocks,
+                           int n_blocks, int nx, int ny, int nz, float min_weight, const uint8_t* d_active, uint8_t* d_edge_flags,
+                           const int32_t* d_vertex_rank, const int32_t* d_edge_rank, int32_t* d_out_faces, int64_t n_faces, void* stream);
+
+/* =====================================================================================================
  * L. Dense depth for RGB reconstructions: plane-sweep multi-view stereo (estimate_depth.py)
  * =====================================================================================================
  * Frames arrive as in section K: packed buffers of n_pixels elements and a HOST table of acez_mvs_frame rows (= acez_tsdf_frame:
