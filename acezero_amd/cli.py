@@ -1129,7 +1129,33 @@ def fuse_depth_parser():
     p.add_argument("--sparse", type=_strtobool, default=False, help="store only the 8^3-voxel blocks near a surface: the same mesh (rows in "
                                                                     "another order) for scenes whose dense volume does not fit; "
                                                                     "--max_voxels then limits the allocated voxels")
+    _add_component_flags(p)
     return p
+
+
+def _add_component_flags(p):
+    """The three criteria of mesh.filter_components; a component must meet all that are given."""
+    p.add_argument("--min_component_faces", type=int, default=0, help="drop the connected components of the mesh with fewer faces than this")
+    p.add_argument("--min_component_ratio", type=float, default=0.0, help="drop the components with fewer faces than this fraction of the "
+                                                                          "largest component's")
+    p.add_argument("--keep_largest", type=int, default=None, help="keep only this many components, the ones with the most faces")
+
+
+def _component_criteria(opt):
+    """filter_components' keyword arguments from the flags, or None if every flag has its default (the filter is then not called)."""
+    if opt.min_component_faces < 0 or not 0.0 <= opt.min_component_ratio <= 1.0 or (opt.keep_largest is not None and opt.keep_largest < 1):
+        raise SystemExit("--min_component_faces must not be negative, --min_component_ratio must be in 0 .. 1, --keep_largest at least 1")
+    if opt.min_component_faces == 0 and opt.min_component_ratio == 0.0 and opt.keep_largest is None:
+        return None
+    return dict(min_faces=opt.min_component_faces, min_ratio=opt.min_component_ratio, keep_largest=opt.keep_largest)
+
+
+def _component_summary(info):
+    h = info["size_histogram"]
+    return (f"{info['components']} connected components, the largest of {info['largest_component_faces']} faces ({h[0]} of 1-9 faces, "
+            f"{h[1]} of 10-99, {h[2]} of 100-999, {h[3]} of 1000-9999, {h[4]} of 10000 or more); kept "
+            f"{info['components_kept']}, dropped {info['faces_dropped']} faces ({info['invalid_faces']} with an index out of range, "
+            f"{info['degenerate_faces']} degenerate) and {info['vertices_dropped']} vertices")
 
 
 def fuse_depth_main(argv=None):
@@ -1145,6 +1171,7 @@ def fuse_depth_main(argv=None):
         raise SystemExit("output file format not supported: use .ply")
     if opt.voxel_size <= 0:
         raise SystemExit("--voxel_size must be positive")
+    criteria = _component_criteria(opt)
     truncation = 4.0 * opt.voxel_size if opt.truncation is None else opt.truncation
     rgb_files, depth_files = sorted(glob.glob(opt.rgb_files)), sorted(glob.glob(opt.depth_files))
     if len(depth_files) != len(rgb_files):
@@ -1194,6 +1221,10 @@ def fuse_depth_main(argv=None):
     vol.integrate(depth, cam_to_world=c2w, focals=focals, rgb=rgb, depth_unit=opt.depth_unit, max_depth=opt.max_depth)   # 64 frames a call
     vertices, colours, faces = vol.extract_mesh(opt.min_weight)
     known = vol.known_voxels(opt.min_weight)
+    dropped = None
+    if criteria is not None:
+        from . import mesh
+        vertices, colours, faces, dropped = mesh.filter_components(vertices, colours, faces, **criteria)
     vertices, colours, faces = vertices.cpu(), colours.cpu(), faces.cpu()
     t_device = time.perf_counter() - t0
     t0 = time.perf_counter()
@@ -1209,8 +1240,51 @@ def fuse_depth_main(argv=None):
         log.info(f"Allocated blocks: {n_blocks} of {n_grid} ({100.0 * n_blocks / n_grid:.2f} % of the block grid), "
                  f"{n_blocks * fusion.BLOCK_VOXELS * 20 + n_grid * 5} bytes of volume storage where the dense volume would take {n_vox * 20}.")
     log.info(f"Known voxels: {known}. Mesh: {len(vertices)} vertices, {len(faces)} faces.")
+    if dropped is not None:
+        log.info(f"Extracted mesh: {_component_summary(dropped)}.")
     log.info(f"Decode {t_decode:.2f} s, upload + kernels + download {t_device:.2f} s, write {t_write:.2f} s.")
     log.info(f"Done. Wrote mesh to: {opt.output_file}")
+    return 0
+
+
+# ----------------------------------------------------------------------------------------------------------- clean_mesh
+def clean_mesh_parser():
+    p = argparse.ArgumentParser(description="Drop the floating fragments of a triangle mesh on the GPU: label its connected components "
+                                            "and keep those that meet every given criterion. Faces with an index out of range or with "
+                                            "two equal indices, and vertices that no kept face uses, are dropped in any case.",
+                                formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("input_file", type=Path, help="mesh to clean (.ply, binary little-endian or ASCII)")
+    p.add_argument("output_file", type=Path, help="mesh to write (.ply)")
+    _add_component_flags(p)
+    return p
+
+
+def clean_mesh_main(argv=None):
+    """clean_mesh.py: .ply -> connected components (HIP) -> the kept components' faces and vertices in their order (HIP) -> .ply."""
+    opt = clean_mesh_parser().parse_args(argv)
+    logging.basicConfig(level=logging.INFO)
+    log = logging.getLogger("clean_mesh")
+    if not str(opt.output_file).endswith(".ply"):
+        raise SystemExit("output file format not supported: use .ply")
+    criteria = _component_criteria(opt)
+    if not opt.input_file.is_file():
+        raise SystemExit(f"{opt.input_file}: no such file")
+    vertices, colours, faces = read_ply_mesh(opt.input_file)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("clean_mesh.py needs a GPU: the component labelling is a HIP kernel, there is no CPU path")
+    from . import mesh
+    if criteria is None:
+        log.info("No criterion given: only faces with an index out of range, degenerate faces and unreferenced vertices are dropped.")
+    d_colours = None if colours is None else torch.from_numpy(colours).cuda()
+    out_v, out_c, out_f, info = mesh.filter_components(torch.from_numpy(vertices).cuda(), d_colours,
+                                                       torch.from_numpy(np.ascontiguousarray(faces, np.int32)).cuda(), **(criteria or {}))
+    log.info(f"Read {len(vertices)} vertices, {len(faces)} faces: {_component_summary(info)}.")
+    if len(out_f) == 0:
+        log.warning("Nothing is left of the mesh: writing an empty file.")
+    out_c = np.full((len(out_v), 3), 200, np.uint8) if out_c is None else out_c.cpu().numpy()
+    write_ply(opt.output_file, out_v.cpu().numpy(), out_c, out_f.cpu().numpy())
+    log.info(f"Done. Wrote {len(out_v)} vertices, {len(out_f)} faces to: {opt.output_file}")
     return 0
 
 

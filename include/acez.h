@@ -1199,6 +1199,70 @@ int acez_geom_sample_faces(const float* d_vertices, int64_t m, const int32_t* d_
 int acez_geom_crop_polygon(const float* d_points, int64_t n, const float* d_polygon, int corners, int axis, float axis_min,
                            float axis_max, uint8_t* d_out_keep, void* stream);
 
+/* =====================================================================================================
+ * P. A mesh without its floating fragments: connected components (clean_mesh.py, fuse_depth.py --min_component_faces ..)
+ * =====================================================================================================
+ * Four stateless entry points; none allocates anything, every buffer is the caller's. d_faces int32 [k][3] (triangles), m the number
+ * of vertices. Everything is integer arithmetic, and the result is a function of the mesh alone: no floating-point sum, nothing that
+ * depends on scheduling. Connectivity is by index: two vertices with the same coordinates are two vertices (no welding). Surface area
+ * per component is not computed: a sum over a component's faces has no fixed order without a sort. tests/mesh_restated.py restates
+ * all of it in numpy.
+ *
+ * Terms. A face is INVALID if an index lies outside 0 .. m - 1, and DEGENERATE if it is not invalid and two of its indices are
+ * equal. Invalid and degenerate faces connect nothing and are never kept; every other face is VALID. Two vertices are connected if a
+ * valid face holds both; the components are the transitive closure. label[v] is the SMALLEST vertex id of v's component; a vertex in
+ * no valid face is its own label. A face's component is the label of its first vertex. A component EXISTS if it has at least one
+ * valid face.
+ *
+ * COMPONENTS (acez_mesh_components). d_labels int32 [m] = label[]; d_status int32 [1] is cleared, and set to a value other than 0
+ * only if one of the bounded loops below ran out, which no input can cause (the caller reads it with the counts and refuses the
+ * result). A lock-free union-find in three launches, d_labels serving as parent[]:
+ *   init     parent[v] = v
+ *   hook     one thread per valid face (a, b, c) unites (a, b) and (b, c): find both roots, compare-and-swap the LARGER root under
+ *            the SMALLER (expecting the larger to be a root still), and on failure start again from the new roots. parent[v] <= v
+ *            always and only ever decreases (a find also replaces parent[v] by the minimum of itself and v's grandparent), so the
+ *            smallest vertex of a component never gets a parent and the one root left is that vertex. Every access to parent[] in
+ *            this launch is a relaxed agent-scope atomic: a plain load can be served from another XCD's stale line.
+ *   flatten  label[v] = the root of v, in place, plain loads (after the kernel boundary).
+ * A walk descends strictly: fewer than m steps. A compare-and-swap fails only because another thread linked that root, which
+ * happens once per vertex: at most m failures. Both loops stop after m + 1 trips and set *d_status; no thread waits for another.
+ *
+ * COUNTS (acez_mesh_component_counts). d_faces_of, d_vertices_of int32 [m], cleared here: faces_of[c] = the number of valid faces
+ * whose component is c; vertices_of[c] = the number of vertices with label c if component c exists; 0 everywhere else (so a vertex
+ * in no valid face counts nowhere). Integer atomic adds; where a wavefront's active lanes share a label, one lane adds their number.
+ *
+ * Selection (the caller's, acezero_amd/mesh.py with torch operations on the device; all criteria conjunctive, each off by default):
+ * rank the existing components by faces_of descending, ties by the smaller label (a stable descending sort over ascending labels).
+ * Component c is kept iff faces_of[c] >= min_faces, and (double)faces_of[c] >= min_ratio * (double)(largest faces_of), one fp64
+ * product, and rank[c] < keep_largest.
+ *
+ * SELECT (acez_mesh_select), flag mode. d_keep_component uint8 [m] (indexed by label). d_face_keep uint8 [k] = 1 iff the face is
+ * valid and its component is kept, else 0; d_vertex_used uint8 [m] is cleared here and set to 1 (plain byte stores) for the three
+ * vertices of every kept face.
+ *
+ * COMPACT (acez_mesh_compact), scatter mode. d_face_rank int32 [k] and d_vertex_rank int32 [m] are the inclusive sums of the two flag
+ * arrays (the caller's), n_faces and n_vertices their last entries. Kept face t goes to row d_face_rank[t] - 1 of d_out_faces int32
+ * [n_faces][3] with every index v renamed to d_vertex_rank[v] - 1; used vertex v goes to row d_vertex_rank[v] - 1 of d_out_vertices
+ * float32 [n_vertices][3] (the bits are copied) and, with d_colours uint8 [m][3], of d_out_colours uint8 [n_vertices][3]. So the
+ * kept faces and the vertices they use keep their original order, and unreferenced vertices disappear. d_colours and d_out_colours
+ * are both null or both given.
+ *
+ * Every index formed from device data (a face's vertices, a label, a rank) is range-checked before it is used as an address: a row
+ * outside the output is not written, an index that cannot be renamed becomes -1; wrong tables give wrong numbers, never an access
+ * out of bounds.
+ *
+ * Asynchronous on `stream`. ACEZ_ERR_INVALID, before anything is launched, for: a null pointer (an array whose count is 0 may be
+ * null; d_status never), a negative count or one >= 2^31, n_vertices > m or n_faces > k, only one of d_colours / d_out_colours. */
+int acez_mesh_components(const int32_t* d_faces, int64_t k, int64_t m, int32_t* d_labels, int32_t* d_status, void* stream);
+int acez_mesh_component_counts(const int32_t* d_faces, int64_t k, const int32_t* d_labels, int64_t m, int32_t* d_faces_of,
+                               int32_t* d_vertices_of, void* stream);
+int acez_mesh_select(const int32_t* d_faces, int64_t k, const int32_t* d_labels, int64_t m, const uint8_t* d_keep_component,
+                     uint8_t* d_face_keep, uint8_t* d_vertex_used, void* stream);
+int acez_mesh_compact(const float* d_vertices, const uint8_t* d_colours, int64_t m, const int32_t* d_faces, int64_t k,
+                      const uint8_t* d_face_keep, const int32_t* d_face_rank, const uint8_t* d_vertex_used, const int32_t* d_vertex_rank,
+                      float* d_out_vertices, uint8_t* d_out_colours, int64_t n_vertices, int32_t* d_out_faces, int64_t n_faces,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
