@@ -21,16 +21,21 @@
 //                  256 contiguous bytes per volume load or store. The per-voxel walk is fuse_frames(), the dense kernel's.
 // cells_blocks,    one 512-thread workgroup per allocated block; the block and its one-voxel halo (a 10^3 tile of storage offsets,
 // faces_blocks     tsdf, weight and, for the faces, the active flags) go to LDS through the table, 13 KB.
+//
+// The dense and the block kernels differ in where a voxel lies, not in what happens to it. The steps they share are device functions:
+// frustum_verdicts (the per-frame skip of a workgroup's box, with the barrier), update_voxel (load, fuse_frames over the call's frames,
+// store if touched), write_vertex and write_quad. The host's checks of the frame arguments are check_frame_call, the rows' own checks
+// and the table's upload are frame_table.h's, which mvs_api.hip shares.
 #include <math.h>
 #include <stdint.h>
 
 #include "acez_common.h"
+#include "frame_table.h"
 
 namespace {
 
 constexpr int FU_THREADS = 256;
 constexpr int FU_BX = 32, FU_BY = 4, FU_BZ = 2;   // the brick; FU_BX * FU_BY * FU_BZ == FU_THREADS
-constexpr int FU_MAX_SIDE = 32768;
 constexpr double FU_SLACK = 1e-5;                  // of the magnitudes entering a plane's value; rounding of steps 1-4 is below 5e-7 of them
 
 struct Volume {
@@ -107,28 +112,29 @@ __device__ __forceinline__ bool fuse_frames(float px, float py, float pz, float&
   return touched;
 }
 
-__global__ void __launch_bounds__(FU_THREADS) integrate_kernel(float* __restrict__ tsdf, float* __restrict__ weight, float* __restrict__ colour,
-                                                               Volume vol, float tau, const uint16_t* __restrict__ depth,
-                                                               const uint8_t* __restrict__ rgb, const acez_tsdf_frame* __restrict__ frames,
-                                                               int n_frames, float depth_unit, float max_depth, float max_weight,
-                                                               int frustum_skip) {
-  __shared__ uint8_t s_skip[ACEZ_TSDF_MAX_FRAMES];
+// The frustum test of a workgroup's box of voxels, (i0, j0, k0) of extent (ex, ey, ez) clipped to the grid: thread f tests frame f,
+// the verdicts go to s_skip. Ends with the workgroup's only barrier; without the skip there is none.
+__device__ __forceinline__ void frustum_verdicts(const Volume& vol, int i0, int j0, int k0, int ex, int ey, int ez,
+                                                 const acez_tsdf_frame* __restrict__ frames, int n_frames, int frustum_skip, uint8_t* s_skip) {
+  if (!frustum_skip) return;
   const int t = threadIdx.x;
-  const int i0 = blockIdx.x * FU_BX, j0 = blockIdx.y * FU_BY, k0 = blockIdx.z * FU_BZ;
-  if (frustum_skip) {
-    if (t < n_frames) {
-      const int i1 = min(i0 + FU_BX, vol.nx) - 1, j1 = min(j0 + FU_BY, vol.ny) - 1, k1 = min(k0 + FU_BZ, vol.nz) - 1;
-      const double v = vol.v;
-      const double lo[3] = {vol.ox + i0 * v, vol.oy + j0 * v, vol.oz + k0 * v};
-      const double hi[3] = {vol.ox + i1 * v, vol.oy + j1 * v, vol.oz + k1 * v};
-      s_skip[t] = brick_outside(frames[t], lo, hi) ? 1 : 0;
-    }
-    __syncthreads();
+  if (t < n_frames) {
+    const int i1 = min(i0 + ex, vol.nx) - 1, j1 = min(j0 + ey, vol.ny) - 1, k1 = min(k0 + ez, vol.nz) - 1;
+    const double v = vol.v;
+    const double lo[3] = {vol.ox + i0 * v, vol.oy + j0 * v, vol.oz + k0 * v};
+    const double hi[3] = {vol.ox + i1 * v, vol.oy + j1 * v, vol.oz + k1 * v};
+    s_skip[t] = brick_outside(frames[t], lo, hi) ? 1 : 0;
   }
-  const int i = i0 + (t & (FU_BX - 1)), j = j0 + ((t >> 5) & (FU_BY - 1)), k = k0 + (t >> 7);
-  if (i >= vol.nx || j >= vol.ny || k >= vol.nz) return;   // (after the only barrier)
-  const int64_t n_vox = (int64_t)vol.nx * vol.ny * vol.nz;
-  const int64_t at = ((int64_t)k * vol.ny + j) * vol.nx + i;
+  __syncthreads();
+}
+
+// The voxel (i, j, k), stored at element `at` of planes of `plane` elements: read once, fuse_frames() over the call's frames in
+// registers, written once and only if a frame touched it.
+__device__ __forceinline__ void update_voxel(float* __restrict__ tsdf, float* __restrict__ weight, float* __restrict__ colour, int64_t at,
+                                             int64_t plane, const Volume& vol, int i, int j, int k, float tau,
+                                             const uint16_t* __restrict__ depth, const uint8_t* __restrict__ rgb,
+                                             const acez_tsdf_frame* __restrict__ frames, int n_frames, float depth_unit, float max_depth,
+                                             float max_weight, int frustum_skip, const uint8_t* s_skip) {
   const float px = vol.ox + (float)i * vol.v;
   const float py = vol.oy + (float)j * vol.v;
   const float pz = vol.oz + (float)k * vol.v;
@@ -137,8 +143,8 @@ __global__ void __launch_bounds__(FU_THREADS) integrate_kernel(float* __restrict
   const bool with_colour = colour != nullptr && rgb != nullptr;
   if (with_colour) {
     c0 = colour[at];
-    c1 = colour[n_vox + at];
-    c2 = colour[2 * n_vox + at];
+    c1 = colour[plane + at];
+    c2 = colour[2 * plane + at];
   }
   const bool touched = fuse_frames(px, py, pz, d_t, d_w, c0, c1, c2, with_colour, tau, depth, rgb, frames, n_frames, depth_unit, max_depth,
                                    max_weight, frustum_skip != 0, s_skip);
@@ -147,9 +153,24 @@ __global__ void __launch_bounds__(FU_THREADS) integrate_kernel(float* __restrict
   weight[at] = d_w;
   if (with_colour) {
     colour[at] = c0;
-    colour[n_vox + at] = c1;
-    colour[2 * n_vox + at] = c2;
+    colour[plane + at] = c1;
+    colour[2 * plane + at] = c2;
   }
+}
+
+__global__ void __launch_bounds__(FU_THREADS) integrate_kernel(float* __restrict__ tsdf, float* __restrict__ weight, float* __restrict__ colour,
+                                                               Volume vol, float tau, const uint16_t* __restrict__ depth,
+                                                               const uint8_t* __restrict__ rgb, const acez_tsdf_frame* __restrict__ frames,
+                                                               int n_frames, float depth_unit, float max_depth, float max_weight,
+                                                               int frustum_skip) {
+  __shared__ uint8_t s_skip[ACEZ_TSDF_MAX_FRAMES];
+  const int t = threadIdx.x;
+  const int i0 = blockIdx.x * FU_BX, j0 = blockIdx.y * FU_BY, k0 = blockIdx.z * FU_BZ;
+  frustum_verdicts(vol, i0, j0, k0, FU_BX, FU_BY, FU_BZ, frames, n_frames, frustum_skip, s_skip);
+  const int i = i0 + (t & (FU_BX - 1)), j = j0 + ((t >> 5) & (FU_BY - 1)), k = k0 + (t >> 7);
+  if (i >= vol.nx || j >= vol.ny || k >= vol.nz) return;   // (after the only barrier)
+  update_voxel(tsdf, weight, colour, ((int64_t)k * vol.ny + j) * vol.nx + i, (int64_t)vol.nx * vol.ny * vol.nz, vol, i, j, k, tau, depth, rgb,
+               frames, n_frames, depth_unit, max_depth, max_weight, frustum_skip, s_skip);
 }
 
 // corner numbers (dx + 2 dy + 4 dz) of the 12 edges, lower end first; the axis of edge e is e / 4
@@ -229,6 +250,19 @@ __global__ void __launch_bounds__(FU_THREADS) cells_kernel(const float* __restri
   write_vertex(d, idx, colour, n_vox, vol, i, j, k, id, out_v, out_c);
 }
 
+// The two triangles of a quad, rows `row` and `row + 1` of the faces, from its four cells' vertex ids in the order section K walks them;
+// the winding turns with the side the surface is seen from.
+__device__ __forceinline__ void write_quad(int32_t* __restrict__ out_f, int64_t row, int32_t v0, int32_t v1, int32_t v2, int32_t v3,
+                                           bool lower_inside) {
+  int32_t* o = out_f + 3 * row;
+  o[0] = v0;
+  o[1] = lower_inside ? v1 : v2;
+  o[2] = lower_inside ? v2 : v1;
+  o[3] = v0;
+  o[4] = lower_inside ? v2 : v3;
+  o[5] = lower_inside ? v3 : v2;
+}
+
 __global__ void __launch_bounds__(FU_THREADS) faces_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight, Volume vol,
                                                            float min_weight, const uint8_t* __restrict__ active, uint8_t* __restrict__ flags,
                                                            const int32_t* __restrict__ vrank, const int32_t* __restrict__ erank,
@@ -264,14 +298,7 @@ __global__ void __launch_bounds__(FU_THREADS) faces_kernel(const float* __restri
   }
   const int64_t row = 2 * ((int64_t)erank[e] - 1);
   if (!quad || row < 0 || row + 2 > n_faces) return;
-  const int32_t v0 = vrank[cell[0]] - 1, v1 = vrank[cell[1]] - 1, v2 = vrank[cell[2]] - 1, v3 = vrank[cell[3]] - 1;
-  int32_t* o = out_f + 3 * row;
-  o[0] = v0;
-  o[1] = lower_inside ? v1 : v2;
-  o[2] = lower_inside ? v2 : v1;
-  o[3] = v0;
-  o[4] = lower_inside ? v2 : v3;
-  o[5] = lower_inside ? v3 : v2;
+  write_quad(out_f, row, vrank[cell[0]] - 1, vrank[cell[1]] - 1, vrank[cell[2]] - 1, vrank[cell[3]] - 1, lower_inside);
 }
 
 // ---------------------------------------------------------------------------------------------- section K2: the block-sparse volume
@@ -375,41 +402,11 @@ __global__ void __launch_bounds__(SB_VOX) integrate_blocks_kernel(float* __restr
   const int64_t b = slot_blocks[blockIdx.x];                  // uniform
   if (b < 0 || b >= (int64_t)bl.bx * bl.by * bl.bz) return;   // not a block of this grid: nothing is read or written (uniform)
   const int i0 = (int)(b % bl.bx) * SB, j0 = (int)((b / bl.bx) % bl.by) * SB, k0 = (int)(b / ((int64_t)bl.bx * bl.by)) * SB;
-  if (frustum_skip) {
-    if (t < n_frames) {
-      const int i1 = min(i0 + SB, vol.nx) - 1, j1 = min(j0 + SB, vol.ny) - 1, k1 = min(k0 + SB, vol.nz) - 1;
-      const double v = vol.v;
-      const double lo[3] = {vol.ox + i0 * v, vol.oy + j0 * v, vol.oz + k0 * v};
-      const double hi[3] = {vol.ox + i1 * v, vol.oy + j1 * v, vol.oz + k1 * v};
-      s_skip[t] = brick_outside(frames[t], lo, hi) ? 1 : 0;
-    }
-    __syncthreads();
-  }
+  frustum_verdicts(vol, i0, j0, k0, SB, SB, SB, frames, n_frames, frustum_skip, s_skip);
   const int i = i0 + (t & 7), j = j0 + ((t >> 3) & 7), k = k0 + (t >> 6);
   if (i >= vol.nx || j >= vol.ny || k >= vol.nz) return;   // (after the only barrier) a partial block's voxels beyond the grid
-  const int64_t plane = (int64_t)bl.n_blocks * SB_VOX;
-  const int64_t at = (int64_t)blockIdx.x * SB_VOX + t;
-  const float px = vol.ox + (float)i * vol.v;
-  const float py = vol.oy + (float)j * vol.v;
-  const float pz = vol.oz + (float)k * vol.v;
-  float d_t = tsdf[at], d_w = weight[at];
-  float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
-  const bool with_colour = colour != nullptr && rgb != nullptr;
-  if (with_colour) {
-    c0 = colour[at];
-    c1 = colour[plane + at];
-    c2 = colour[2 * plane + at];
-  }
-  const bool touched = fuse_frames(px, py, pz, d_t, d_w, c0, c1, c2, with_colour, tau, depth, rgb, frames, n_frames, depth_unit, max_depth,
-                                   max_weight, frustum_skip != 0, s_skip);
-  if (!touched) return;
-  tsdf[at] = d_t;
-  weight[at] = d_w;
-  if (with_colour) {
-    colour[at] = c0;
-    colour[plane + at] = c1;
-    colour[2 * plane + at] = c2;
-  }
+  update_voxel(tsdf, weight, colour, (int64_t)blockIdx.x * SB_VOX + t, (int64_t)bl.n_blocks * SB_VOX, vol, i, j, k, tau, depth, rgb, frames,
+               n_frames, depth_unit, max_depth, max_weight, frustum_skip, s_skip);
 }
 
 __device__ __forceinline__ int tile_at(int li, int lj, int lk) { return ((lk + 1) * SB_TILE + (lj + 1)) * SB_TILE + (li + 1); }
@@ -521,21 +518,8 @@ __global__ void __launch_bounds__(SB_VOX) faces_blocks_kernel(const float* __res
     }
     const int64_t row = 2 * ((int64_t)erank[e] - 1);
     if (!quad || row < 0 || row + 2 > n_faces) continue;
-    const int32_t v0 = vrank[s_off[cell[0]]] - 1, v1 = vrank[s_off[cell[1]]] - 1, v2 = vrank[s_off[cell[2]]] - 1, v3 = vrank[s_off[cell[3]]] - 1;
-    int32_t* o = out_f + 3 * row;
-    o[0] = v0;
-    o[1] = lower_inside ? v1 : v2;
-    o[2] = lower_inside ? v2 : v1;
-    o[3] = v0;
-    o[4] = lower_inside ? v2 : v3;
-    o[5] = lower_inside ? v3 : v2;
+    write_quad(out_f, row, vrank[s_off[cell[0]]] - 1, vrank[s_off[cell[1]]] - 1, vrank[s_off[cell[2]]] - 1, vrank[s_off[cell[3]]] - 1, lower_inside);
   }
-}
-
-bool finite_all(const float* p, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!isfinite(p[i])) return false;
-  return true;
 }
 
 }  // namespace
@@ -544,15 +528,19 @@ bool finite_all(const float* p, int n) {
   ACEZ_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1, "volume dimensions must be at least 1");                                \
   ACEZ_REQUIRE((int64_t)nx * ny <= (limit) && (int64_t)nx * ny * nz <= (limit), "volume too large for 32-bit voxel indices")
 
-// the frame table's rows: what bounds every index a kernel forms from them
-static int check_frames(const acez_tsdf_frame* h_frames, int n_frames, int64_t n_pixels) {
-  for (int f = 0; f < n_frames; ++f) {
-    const acez_tsdf_frame& fr = h_frames[f];
-    ACEZ_REQUIRE(fr.h >= 1 && fr.w >= 1 && fr.h <= FU_MAX_SIDE && fr.w <= FU_MAX_SIDE, "frame size out of range (1 .. 32768 px per side)");
-    ACEZ_REQUIRE(finite_all(fr.m, 12) && isfinite(fr.focal) && isfinite(fr.ppx) && isfinite(fr.ppy), "non-finite pose or intrinsics in the frame table");
-    ACEZ_REQUIRE(fr.focal > 0.0f, "focal length must be positive");
-    ACEZ_REQUIRE(fr.offset >= 0 && fr.offset <= n_pixels && (int64_t)fr.h * fr.w <= n_pixels - fr.offset, "frame past the end of the depth buffer");
-  }
+// what the three frame-taking entry points share: the fusion scalars (max_weight: null where the entry point has no weight cap), the
+// frame count and the table's rows, which bound every index a kernel forms from them
+static int check_frame_call(float truncation, float depth_unit, float max_depth, const float* max_weight, int64_t n_pixels,
+                            const acez_tsdf_frame* h_frames, int n_frames) {
+  const float scal[3] = {truncation, depth_unit, max_depth};
+  ACEZ_REQUIRE(acez::finite_all(scal, 3), "non-finite truncation, depth unit or depth limit");
+  ACEZ_REQUIRE(truncation > 0.0f, "truncation must be positive");
+  ACEZ_REQUIRE(depth_unit > 0.0f && max_depth > 0.0f, "depth unit and depth limit must be positive");
+  ACEZ_REQUIRE(!max_weight || (isfinite(*max_weight) && *max_weight > 0.0f), "weight cap must be positive and finite");
+  ACEZ_REQUIRE(n_frames >= 0 && n_frames <= ACEZ_TSDF_MAX_FRAMES, "frame count out of range (0 .. 256 per call)");
+  ACEZ_REQUIRE(n_pixels >= 0, "negative depth buffer length");
+  for (int f = 0; f < n_frames; ++f)
+    if (int rc = acez::check_frame(h_frames[f], n_pixels)) return rc;
   return ACEZ_OK;
 }
 
@@ -563,19 +551,13 @@ extern "C" int acez_tsdf_integrate(float* d_tsdf, float* d_weight, float* d_colo
   ACEZ_REQUIRE(d_tsdf && d_weight && d_depth && h_frames && d_frames, "null pointer");
   ACEZ_REQUIRE(!d_rgb || d_colour, "colour images without a colour volume");
   FU_REQUIRE_DIMS(((int64_t)1 << 31) - 1);
-  const float scal[8] = {ox, oy, oz, voxel_size, truncation, depth_unit, max_depth, max_weight};
-  ACEZ_REQUIRE(finite_all(scal, 8), "non-finite origin, voxel size, truncation, depth unit, depth limit or weight cap");
-  ACEZ_REQUIRE(voxel_size > 0.0f && truncation > 0.0f, "voxel size and truncation must be positive");
-  ACEZ_REQUIRE(depth_unit > 0.0f && max_depth > 0.0f && max_weight > 0.0f, "depth unit, depth limit and weight cap must be positive");
-  ACEZ_REQUIRE(n_frames >= 0 && n_frames <= ACEZ_TSDF_MAX_FRAMES, "frame count out of range (0 .. 256 per call)");
-  ACEZ_REQUIRE(n_pixels >= 0, "negative depth buffer length");
-  if (int rc = check_frames(h_frames, n_frames, n_pixels)) return rc;
+  ACEZ_REQUIRE(isfinite(ox) && isfinite(oy) && isfinite(oz) && isfinite(voxel_size) && voxel_size > 0.0f, "voxel size must be positive, the origin finite");
+  if (int rc = check_frame_call(truncation, depth_unit, max_depth, &max_weight, n_pixels, h_frames, n_frames)) return rc;
   ACEZ_REQUIRE((ny + FU_BY - 1) / FU_BY <= 65535 && (nz + FU_BZ - 1) / FU_BZ <= 65535, "volume too large (more than 65535 bricks along y or z)");
   if (int rc = acez::require_device("TSDF integration runs on a gfx950 GPU")) return rc;
   if (n_frames == 0) return ACEZ_OK;
   hipStream_t s = (hipStream_t)stream;
-  ACEZ_HIP_CHECK(hipMemcpyAsync(d_frames, h_frames, sizeof(acez_tsdf_frame) * (size_t)n_frames, hipMemcpyHostToDevice, s));
-  ACEZ_HIP_CHECK(hipStreamSynchronize(s));   // h_frames is the caller's again
+  if (int rc = acez::upload_frames(d_frames, h_frames, n_frames, s)) return rc;
   const dim3 grid((nx + FU_BX - 1) / FU_BX, (ny + FU_BY - 1) / FU_BY, (nz + FU_BZ - 1) / FU_BZ);
   const Volume vol{nx, ny, nz, ox, oy, oz, voxel_size};
   hipLaunchKernelGGL(integrate_kernel, grid, dim3(FU_THREADS), 0, s, d_tsdf, d_weight, d_colour, vol, truncation, d_depth, d_rgb,
@@ -638,13 +620,7 @@ extern "C" int acez_tsdf_mark(uint8_t* d_block_flags, int nx, int ny, int nz, fl
   ACEZ_REQUIRE(d_block_flags && d_depth && h_frames && d_frames, "null pointer");
   Blocks bl;
   if (int rc = check_block_grid(nx, ny, nz, ox, oy, oz, voxel_size, 0, &bl)) return rc;
-  const float scal[3] = {truncation, depth_unit, max_depth};
-  ACEZ_REQUIRE(finite_all(scal, 3), "non-finite truncation, depth unit or depth limit");
-  ACEZ_REQUIRE(truncation > 0.0f, "voxel size and truncation must be positive");
-  ACEZ_REQUIRE(depth_unit > 0.0f && max_depth > 0.0f, "depth unit and depth limit must be positive");
-  ACEZ_REQUIRE(n_frames >= 0 && n_frames <= ACEZ_TSDF_MAX_FRAMES, "frame count out of range (0 .. 256 per call)");
-  ACEZ_REQUIRE(n_pixels >= 0, "negative depth buffer length");
-  if (int rc = check_frames(h_frames, n_frames, n_pixels)) return rc;
+  if (int rc = check_frame_call(truncation, depth_unit, max_depth, nullptr, n_pixels, h_frames, n_frames)) return rc;
   int64_t most = 0;
   for (int f = 0; f < n_frames; ++f) {
     const float* m = h_frames[f].m;
@@ -656,8 +632,7 @@ extern "C" int acez_tsdf_mark(uint8_t* d_block_flags, int nx, int ny, int nz, fl
   if (int rc = acez::require_device("marking TSDF blocks runs on a gfx950 GPU")) return rc;
   if (n_frames == 0) return ACEZ_OK;
   hipStream_t s = (hipStream_t)stream;
-  ACEZ_HIP_CHECK(hipMemcpyAsync(d_frames, h_frames, sizeof(acez_tsdf_frame) * (size_t)n_frames, hipMemcpyHostToDevice, s));
-  ACEZ_HIP_CHECK(hipStreamSynchronize(s));   // h_frames is the caller's again
+  if (int rc = acez::upload_frames(d_frames, h_frames, n_frames, s)) return rc;
   const Volume vol{nx, ny, nz, ox, oy, oz, voxel_size};
   hipLaunchKernelGGL(mark_kernel, dim3((unsigned)((most + MK_THREADS - 1) / MK_THREADS), (unsigned)n_frames), dim3(MK_THREADS), 0, s, d_block_flags,
                      vol, bl, truncation, d_depth, (const acez_tsdf_frame*)d_frames, depth_unit, max_depth);
@@ -674,18 +649,11 @@ extern "C" int acez_tsdf_integrate_blocks(float* d_tsdf, float* d_weight, float*
   ACEZ_REQUIRE(!d_rgb || d_colour, "colour images without a colour volume");
   Blocks bl;
   if (int rc = check_block_grid(nx, ny, nz, ox, oy, oz, voxel_size, n_blocks, &bl)) return rc;
-  const float scal[4] = {truncation, depth_unit, max_depth, max_weight};
-  ACEZ_REQUIRE(finite_all(scal, 4), "non-finite truncation, depth unit, depth limit or weight cap");
-  ACEZ_REQUIRE(truncation > 0.0f, "voxel size and truncation must be positive");
-  ACEZ_REQUIRE(depth_unit > 0.0f && max_depth > 0.0f && max_weight > 0.0f, "depth unit, depth limit and weight cap must be positive");
-  ACEZ_REQUIRE(n_frames >= 0 && n_frames <= ACEZ_TSDF_MAX_FRAMES, "frame count out of range (0 .. 256 per call)");
-  ACEZ_REQUIRE(n_pixels >= 0, "negative depth buffer length");
-  if (int rc = check_frames(h_frames, n_frames, n_pixels)) return rc;
+  if (int rc = check_frame_call(truncation, depth_unit, max_depth, &max_weight, n_pixels, h_frames, n_frames)) return rc;
   if (int rc = acez::require_device("TSDF integration runs on a gfx950 GPU")) return rc;
   if (n_frames == 0 || n_blocks == 0) return ACEZ_OK;
   hipStream_t s = (hipStream_t)stream;
-  ACEZ_HIP_CHECK(hipMemcpyAsync(d_frames, h_frames, sizeof(acez_tsdf_frame) * (size_t)n_frames, hipMemcpyHostToDevice, s));
-  ACEZ_HIP_CHECK(hipStreamSynchronize(s));   // h_frames is the caller's again
+  if (int rc = acez::upload_frames(d_frames, h_frames, n_frames, s)) return rc;
   const Volume vol{nx, ny, nz, ox, oy, oz, voxel_size};
   hipLaunchKernelGGL(integrate_blocks_kernel, dim3((unsigned)n_blocks), dim3(SB_VOX), 0, s, d_tsdf, d_weight, d_colour, d_slot_blocks, vol, bl,
                      truncation, d_depth, d_rgb, (const acez_tsdf_frame*)d_frames, n_frames, depth_unit, max_depth, max_weight, frustum_skip);

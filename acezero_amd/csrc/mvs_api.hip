@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "acez_common.h"
+#include "frame_table.h"
 
 namespace {
 
@@ -38,7 +39,6 @@ constexpr int MV_TILE = 16;
 constexpr int MV_MAX_RADIUS = 4;
 constexpr int MV_MAX_HALO = (MV_TILE + 2 * MV_MAX_RADIUS) * (MV_TILE + 2 * MV_MAX_RADIUS);   // 576
 constexpr int MV_PER_THREAD = (MV_MAX_HALO + MV_THREADS - 1) / MV_THREADS;                    // 3
-constexpr int MV_MAX_SIDE = 32768;
 constexpr int MV_IN_VIEW = 0x8000;      // bit 15 of an LDS entry; the raw cost (<= 255) is below it
 constexpr int MV_NO_COST = 1 << 28;     // an unused source slot: above any A_s (<= 81 * 255)
 
@@ -401,12 +401,6 @@ __global__ void __launch_bounds__(MV_THREADS) select_kernel(const uint16_t* __re
   if (out_plane) out_plane[out] = ks;
 }
 
-bool finite_all(const float* p, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!isfinite(p[i])) return false;
-  return true;
-}
-
 void relative(const acez_mvs_frame& r, const acez_mvs_frame& s, float* out12) {
   for (int i = 0; i < 3; ++i) {
     double R[3];
@@ -429,24 +423,16 @@ View view_of(const acez_mvs_frame& r, const acez_mvs_frame& s) {
 
 }  // namespace
 
-#define MV_REQUIRE_ROW(fr, n_pixels)                                                                                                     \
-  ACEZ_REQUIRE((fr).h >= 1 && (fr).w >= 1 && (fr).h <= MV_MAX_SIDE && (fr).w <= MV_MAX_SIDE, "frame size out of range (1 .. 32768 px per side)"); \
-  ACEZ_REQUIRE(finite_all((fr).m, 12) && isfinite((fr).focal) && isfinite((fr).ppx) && isfinite((fr).ppy),                                \
-               "non-finite pose or intrinsics in the frame table");                                                                     \
-  ACEZ_REQUIRE((fr).focal > 0.0f, "focal length must be positive");                                                                     \
-  ACEZ_REQUIRE((fr).offset >= 0 && (fr).offset <= (n_pixels) && (int64_t)(fr).h * (fr).w <= (n_pixels) - (fr).offset,                   \
-               "frame past the end of the buffer")
-
 // the rows a sweep or a check touches: the reference and its sources
 #define MV_REQUIRE_VIEWS()                                                                                               \
   ACEZ_REQUIRE(n_pixels >= 0, "negative buffer length");                                                                 \
   ACEZ_REQUIRE(n_frames >= 1, "frame count must be at least 1");                                                         \
   ACEZ_REQUIRE(ref >= 0 && ref < n_frames, "reference index outside the frame table");                                   \
   ACEZ_REQUIRE(n_sources >= 1 && n_sources <= ACEZ_MVS_MAX_SOURCES, "source count out of range (1 .. 8)");                \
-  MV_REQUIRE_ROW(h_frames[ref], n_pixels);                                                                               \
+  if (int rc = acez::check_frame(h_frames[ref], n_pixels)) return rc;                                                    \
   for (int s = 0; s < n_sources; ++s) {                                                                                  \
     ACEZ_REQUIRE(h_sources[s] >= 0 && h_sources[s] < n_frames, "source index outside the frame table");                  \
-    MV_REQUIRE_ROW(h_frames[h_sources[s]], n_pixels);                                                                    \
+    if (int rc = acez::check_frame(h_frames[h_sources[s]], n_pixels)) return rc;                                         \
   }
 
 extern "C" int acez_mvs_prefilter(const uint8_t* d_grey, uint8_t* d_out, int64_t n_pixels, const acez_mvs_frame* h_frames, int n_frames,
@@ -456,13 +442,12 @@ extern "C" int acez_mvs_prefilter(const uint8_t* d_grey, uint8_t* d_out, int64_t
   ACEZ_REQUIRE(n_frames >= 1 && n_frames <= 65535, "frame count out of range (1 .. 65535)");
   int64_t largest = 0;
   for (int f = 0; f < n_frames; ++f) {
-    MV_REQUIRE_ROW(h_frames[f], n_pixels);
+    if (int rc = acez::check_frame(h_frames[f], n_pixels)) return rc;
     largest = largest > (int64_t)h_frames[f].h * h_frames[f].w ? largest : (int64_t)h_frames[f].h * h_frames[f].w;
   }
   if (int rc = acez::require_device("the stereo prefilter runs on a gfx950 GPU")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  ACEZ_HIP_CHECK(hipMemcpyAsync(d_frames, h_frames, sizeof(acez_mvs_frame) * (size_t)n_frames, hipMemcpyHostToDevice, s));
-  ACEZ_HIP_CHECK(hipStreamSynchronize(s));   // h_frames is the caller's again
+  if (int rc = acez::upload_frames(d_frames, h_frames, n_frames, s)) return rc;
   const dim3 grid((unsigned)((largest + MV_THREADS - 1) / MV_THREADS), (unsigned)n_frames);
   hipLaunchKernelGGL(prefilter_kernel, grid, dim3(MV_THREADS), 0, s, d_grey, d_out, (const acez_mvs_frame*)d_frames);
   ACEZ_HIP_CHECK(hipGetLastError());
@@ -471,7 +456,7 @@ extern "C" int acez_mvs_prefilter(const uint8_t* d_grey, uint8_t* d_out, int64_t
 
 extern "C" int acez_mvs_relative(const acez_mvs_frame* ref, const acez_mvs_frame* src, float* out12) {
   ACEZ_REQUIRE(ref && src && out12, "null pointer");
-  ACEZ_REQUIRE(finite_all(ref->m, 12) && finite_all(src->m, 12), "non-finite pose or intrinsics in the frame table");
+  ACEZ_REQUIRE(acez::finite_all(ref->m, 12) && acez::finite_all(src->m, 12), "non-finite pose or intrinsics in the frame table");
   relative(*ref, *src, out12);
   return ACEZ_OK;
 }
@@ -557,7 +542,7 @@ extern "C" int acez_mvs_aggregate(const uint16_t* d_volume, uint32_t* d_s, int64
                                   int p1, int p2, void* stream) {
   static const int DY[8] = {0, 0, 1, -1, 1, 1, -1, -1}, DX[8] = {1, -1, 0, 0, 1, -1, 1, -1};
   ACEZ_REQUIRE(d_volume && d_s, "null pointer");
-  ACEZ_REQUIRE(h >= 1 && w >= 1 && h <= MV_MAX_SIDE && w <= MV_MAX_SIDE, "frame size out of range (1 .. 32768 px per side)");
+  ACEZ_REQUIRE(h >= 1 && w >= 1 && h <= acez::FRAME_MAX_SIDE && w <= acez::FRAME_MAX_SIDE, "frame size out of range (1 .. 32768 px per side)");
   ACEZ_REQUIRE(planes >= 2 && planes <= 1024, "plane count out of range (2 .. 1024)");
   ACEZ_REQUIRE(paths == 4 || paths == 8, "paths must be 4 or 8");
   ACEZ_REQUIRE(direction >= 0 && direction <= paths, "direction out of range (0 = all, 1 .. paths)");
@@ -592,7 +577,7 @@ extern "C" int acez_mvs_select(const uint16_t* d_volume, const uint32_t* d_s, in
   ACEZ_REQUIRE(n_pixels >= 0, "negative buffer length");
   ACEZ_REQUIRE(n_frames >= 1, "frame count must be at least 1");
   ACEZ_REQUIRE(ref >= 0 && ref < n_frames, "reference index outside the frame table");
-  MV_REQUIRE_ROW(h_frames[ref], n_pixels);
+  if (int rc = acez::check_frame(h_frames[ref], n_pixels)) return rc;
   ACEZ_REQUIRE(isfinite(z_near) && isfinite(z_far) && z_near > 0.0f && z_near < z_far, "the depth range needs 0 < near < far");
   ACEZ_REQUIRE(planes >= 2 && planes <= 1024, "plane count out of range (2 .. 1024)");
   ACEZ_REQUIRE(uniqueness >= 0 && uniqueness <= 100, "uniqueness percentage out of range (0 .. 100)");

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .fusion import _per_frame, _w2c34
+from .frames import device_rows, frame_rows, pack
 from .head import _ptr, _stream
 
 MAX_AXIS_ANGLE_DEG = 30.0           # select_sources: a source looks within this angle of the frame's own optical axis
@@ -123,34 +123,13 @@ class StereoFrames:
             raise RuntimeError("plane-sweep stereo needs a GPU: prefilter, sweep and check are HIP kernels, there is no CPU path")
         if focals is None:
             raise ValueError("focals is required")
-        self.device, n = device, len(images)
-        if torch.is_tensor(images):
-            if images.dtype != torch.uint8 or images.dim() != 3:
-                raise TypeError(f"expected a uint8 tensor [n,h,w], got {images.dtype} {tuple(images.shape)}")
-            self.sizes = [tuple(images.shape[1:])] * n
-            self.grey = images.to(device).contiguous().reshape(-1)
-        else:
-            arrays = [np.ascontiguousarray(a.cpu().numpy() if torch.is_tensor(a) else a) for a in images]
-            for a in arrays:
-                if a.dtype != np.uint8 or a.ndim != 2:
-                    raise TypeError(f"expected uint8 [h,w] grey images, got {a.dtype} {a.shape}")
-            self.sizes = [a.shape for a in arrays]
-            self.grey = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrays]) if arrays else np.zeros(0, np.uint8)).to(device)
-        self.offsets = [int(o) for o in np.concatenate([[0], np.cumsum([h * w for h, w in self.sizes])])[:n]]
-        self.n, self.n_pixels = n, int(self.grey.numel())
-        w2c, focals = _w2c34(world_to_cam, cam_to_world, n), _per_frame(focals, n)
-        self.rows = (N.TsdfFrame * max(n, 1))()
-        for f in range(n):
-            h, w = self.sizes[f]
-            row = self.rows[f]
-            row.m[:] = w2c[f].reshape(12).tolist()
-            row.focal = float(focals[f])
-            row.ppx = float(_per_frame(ppx, n)[f]) if ppx is not None else w / 2.0
-            row.ppy = float(_per_frame(ppy, n)[f]) if ppy is not None else h / 2.0
-            row.h, row.w, row.offset = int(h), int(w), self.offsets[f]
+        self.device = device
+        self.grey, self.sizes, self.offsets = pack(images, np.uint8, (), device)
+        self.n, self.n_pixels = len(self.sizes), int(self.grey.numel())
+        self.rows = frame_rows(self.sizes, self.offsets, world_to_cam, cam_to_world, focals, ppx, ppy, length=max(self.n, 1))
         new = lambda dtype: torch.zeros(self.n_pixels, dtype=dtype, device=device)
         self.filtered, self.depth, self.cost, self.plane, self.out = new(torch.uint8), new(torch.float32), new(torch.int32), new(torch.int32), new(torch.int16)
-        self._d_rows = torch.empty(max(n, 1) * C.sizeof(N.TsdfFrame), dtype=torch.uint8, device=device)
+        self._d_rows = device_rows(max(self.n, 1), device)
 
     def prefilter(self):
         with torch.cuda.device(self.device):
