@@ -1130,7 +1130,25 @@ def fuse_depth_parser():
                                                                     "another order) for scenes whose dense volume does not fit; "
                                                                     "--max_voxels then limits the allocated voxels")
     _add_component_flags(p)
+    p.add_argument("--simplify_cell", type=float, default=None, help="simplify the mesh before it is written: one vertex per grid cell of "
+                                                                     "this edge in metres (after the component filter)")
+    p.add_argument("--simplify_placement", type=str, default="quadric", choices=["quadric", "mean"],
+                   help="with --simplify_cell: a cell's vertex minimises the plane quadrics of the faces around it, or is the mean of its vertices")
     return p
+
+
+def _simplify_cell(value, flag):
+    """The cell edge of simplify.simplify_mesh from a flag's value."""
+    if not (math.isfinite(value) and value > 0.0):
+        raise SystemExit(f"{flag} must be positive and finite")
+    return value
+
+
+def _simplify_summary(info):
+    return (f"{info['vertices_in']} vertices, {info['faces_in']} faces ({info['invalid_faces']} invalid, {info['degenerate_faces']} degenerate, "
+            f"{info['nonfinite_vertices']} vertices not finite) in {info['clusters']} cells; {info['collapsed_faces']} faces collapsed, "
+            f"{info['duplicate_faces']} duplicates and {info['unused_clusters']} cells without a face dropped; {info['vertices_out']} vertices "
+            f"({info['fallbacks']} placed at the mean for want of a usable quadric), {info['faces_out']} faces left")
 
 
 def _add_component_flags(p):
@@ -1172,6 +1190,7 @@ def fuse_depth_main(argv=None):
     if opt.voxel_size <= 0:
         raise SystemExit("--voxel_size must be positive")
     criteria = _component_criteria(opt)
+    simplify_cell = None if opt.simplify_cell is None else _simplify_cell(opt.simplify_cell, "--simplify_cell")
     truncation = 4.0 * opt.voxel_size if opt.truncation is None else opt.truncation
     rgb_files, depth_files = sorted(glob.glob(opt.rgb_files)), sorted(glob.glob(opt.depth_files))
     if len(depth_files) != len(rgb_files):
@@ -1225,6 +1244,10 @@ def fuse_depth_main(argv=None):
     if criteria is not None:
         from . import mesh
         vertices, colours, faces, dropped = mesh.filter_components(vertices, colours, faces, **criteria)
+    simplified = None
+    if simplify_cell is not None:
+        from . import simplify
+        vertices, colours, faces, simplified = simplify.simplify_mesh(vertices, colours, faces, simplify_cell, opt.simplify_placement)
     vertices, colours, faces = vertices.cpu(), colours.cpu(), faces.cpu()
     t_device = time.perf_counter() - t0
     t0 = time.perf_counter()
@@ -1242,6 +1265,8 @@ def fuse_depth_main(argv=None):
     log.info(f"Known voxels: {known}. Mesh: {len(vertices)} vertices, {len(faces)} faces.")
     if dropped is not None:
         log.info(f"Extracted mesh: {_component_summary(dropped)}.")
+    if simplified is not None:
+        log.info(f"Simplified at a cell of {simplify_cell} m ({opt.simplify_placement}): {_simplify_summary(simplified)}.")
     log.info(f"Decode {t_decode:.2f} s, upload + kernels + download {t_device:.2f} s, write {t_write:.2f} s.")
     log.info(f"Done. Wrote mesh to: {opt.output_file}")
     return 0
@@ -1280,6 +1305,48 @@ def clean_mesh_main(argv=None):
     out_v, out_c, out_f, info = mesh.filter_components(torch.from_numpy(vertices).cuda(), d_colours,
                                                        torch.from_numpy(np.ascontiguousarray(faces, np.int32)).cuda(), **(criteria or {}))
     log.info(f"Read {len(vertices)} vertices, {len(faces)} faces: {_component_summary(info)}.")
+    if len(out_f) == 0:
+        log.warning("Nothing is left of the mesh: writing an empty file.")
+    out_c = np.full((len(out_v), 3), 200, np.uint8) if out_c is None else out_c.cpu().numpy()
+    write_ply(opt.output_file, out_v.cpu().numpy(), out_c, out_f.cpu().numpy())
+    log.info(f"Done. Wrote {len(out_v)} vertices, {len(out_f)} faces to: {opt.output_file}")
+    return 0
+
+
+# -------------------------------------------------------------------------------------------------------- simplify_mesh
+def simplify_mesh_parser():
+    p = argparse.ArgumentParser(description="Simplify a triangle mesh on the GPU by vertex clustering: the vertices of one grid cell become "
+                                            "one vertex, the faces that collapse and the duplicates are dropped. Faces with an index out "
+                                            "of range, with two equal indices or with a vertex that is not finite are dropped in any case.",
+                                formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("input_file", type=Path, help="mesh to simplify (.ply, binary little-endian or ASCII)")
+    p.add_argument("output_file", type=Path, help="mesh to write (.ply)")
+    p.add_argument("--cell", type=float, required=True, help="edge of the grid cells in metres")
+    p.add_argument("--placement", type=str, default="quadric", choices=["quadric", "mean"],
+                   help="a cell's vertex minimises the plane quadrics of the faces around it (walls stay flat, corners sharp), or is the "
+                        "mean of its vertices")
+    return p
+
+
+def simplify_mesh_main(argv=None):
+    """simplify_mesh.py: .ply -> clusters, per-cluster quadrics and their minimisers, surviving faces (HIP) -> .ply."""
+    opt = simplify_mesh_parser().parse_args(argv)
+    logging.basicConfig(level=logging.INFO)
+    log = logging.getLogger("simplify_mesh")
+    if not str(opt.output_file).endswith(".ply"):
+        raise SystemExit("output file format not supported: use .ply")
+    cell = _simplify_cell(opt.cell, "--cell")
+    if not opt.input_file.is_file():
+        raise SystemExit(f"{opt.input_file}: no such file")
+    vertices, colours, faces = read_ply_mesh(opt.input_file)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("simplify_mesh.py needs a GPU: the simplification is HIP kernels, there is no CPU path")
+    from . import simplify
+    d_colours = None if colours is None else torch.from_numpy(colours).cuda()
+    out_v, out_c, out_f, info = simplify.simplify_mesh(torch.from_numpy(vertices).cuda(), d_colours,
+                                                       torch.from_numpy(np.ascontiguousarray(faces, np.int32)).cuda(), cell, opt.placement)
+    log.info(f"Simplified at a cell of {cell} m ({opt.placement}): {_simplify_summary(info)}.")
     if len(out_f) == 0:
         log.warning("Nothing is left of the mesh: writing an empty file.")
     out_c = np.full((len(out_v), 3), 200, np.uint8) if out_c is None else out_c.cpu().numpy()

@@ -1263,6 +1263,91 @@ int acez_mesh_compact(const float* d_vertices, const uint8_t* d_colours, int64_t
                       float* d_out_vertices, uint8_t* d_out_colours, int64_t n_vertices, int32_t* d_out_faces, int64_t n_faces,
                       void* stream);
 
+/* =====================================================================================================
+ * Q. A mesh with fewer faces: quadric vertex clustering (simplify_mesh.py, fuse_depth.py --simplify_cell)
+ * =====================================================================================================
+ * Six stateless entry points; none allocates anything, every buffer is the caller's. The stable sorts, the prefix sums and the
+ * segment searches between them are the caller's (acezero_amd/simplify.py, torch on the device), the compaction at the end is section
+ * P's acez_mesh_compact. The output is a function of the input alone: every floating-point sum has the fixed order given below.
+ * Steps 4 - 6 compute in fp64, one rounding per operation (the unit is compiled with -ffp-contract=off), and every result is rounded
+ * to fp32 once, at the end. tests/simplify_restated.py restates all of it in numpy, bit for bit.
+ *
+ * Input: vertices float32 [m][3], colours uint8 [m][3] or none, faces int32 [k][3], cell > 0 (float32), placement quadric or mean.
+ *
+ * 1 CELLS. A vertex is FINITE if its three coordinates are. origin = the component-wise minimum of the finite vertices, max their
+ *   component-wise maximum (fp32; the caller's). The cell of a finite vertex p is floor((p - origin) / cell) per axis, in fp32, one
+ *   rounding per operation; a vertex that is not finite has no cell. An axis may have at most 2^21 - 1 cells (the limits of section N
+ *   are too small for a room at 1 cm). The key of a cell is x | y << 21 | z << 42 in an int64; a vertex without a cell has the key
+ *   2^63 - 1.
+ * 2 CLUSTERS. The occupied cells in ascending key order are the clusters 0 .. K - 1. A cluster's vertices are taken in ascending
+ *   vertex id (a stable sort of the keys).
+ * 3 FACES THAT COUNT. A face is INVALID if an index lies outside 0 .. m - 1 or, with all indices in range and pairwise different, a
+ *   vertex of it has no cell; DEGENERATE if its indices are in range and two are equal; VALID otherwise. Only valid faces enter the
+ *   steps below.
+ * 4 MEAN. mean = (the fp64 sum of the cluster's vertices, each converted to fp64, added one by one to 0.0 in the order of step 2)
+ *   / (double)count. The colour is, per channel, (2 sum + count) / (2 count) in integers.
+ * 5 QUADRIC. Every corner of every valid face contributes its face's plane quadric to the cluster of that corner's vertex (a face
+ *   with two corners in one cluster contributes to it twice). centre = (double)origin + ((double)index + 0.5) * (double)cell per axis
+ *   is the cluster's cell centre. For the face (a, b, c), its vertices converted to fp64 and the centre subtracted:
+ *   n = (b - a) x (c - a), each component p * q - r * s, unnormalised (the weight is |n|^2 = 4 area^2); d = -((n0 a0 + n1 a1) + n2 a2);
+ *   the nine terms n0 n0, n0 n1, n0 n2, n1 n1, n1 n2, n2 n2 (A, symmetric) and d n0, d n1, d n2 (b) are each added to their running
+ *   sum, which starts at 0.0. THE ORDER: let the cluster's corners stand in ascending 3 face + corner (a stable sort of the corners
+ *   by cluster) at positions 0, 1, .. of its segment. One wavefront takes the cluster: lane l (0 .. 63) adds the corners at positions
+ *   l, l + 64, l + 128, .. one by one to its own nine sums (all 0.0 for a lane without a corner); then, for s = 32, 16, 8, 4, 2, 1,
+ *   every lane l replaces each of its sums by itself + the sum of lane l xor s (an addition commutes, so all lanes hold the same
+ *   bits); the result is lane 0's. Chosen by measurement over one thread per cluster walking the whole segment serially, which is
+ *   two to three times slower on fused rooms (tools/simplify_timing.py).
+ * 6 PLACEMENT (acezero_amd/csrc/simplify_solve.h). mean: the vertex is the mean. quadric: with r = mean - centre, decompose A with
+ *   svd3 (acezero_amd/csrc/svd3.h: A = U diag(s) V^T, fixed sweep order and cap); g_j = -b_j - ((A_j0 r0 + A_j1 r1) + A_j2 r2);
+ *   y = r; for i = 0, 1, 2 with s_i > 1e-3 * s_0: y_j = y_j + v_i[j] * (((v_i[0] g0 + v_i[1] g1) + v_i[2] g2) / s_i) (rank 1 on a
+ *   wall, 2 on an edge, 3 at a corner). The vertex is centre + y, unless s_0 > 0 does not hold (A is zero), or a y_j is not finite,
+ *   or |y_j| > cell: then it is the mean (a FALLBACK). Either way one rounding to fp32.
+ * 7 OUTPUT FACES. A valid face is mapped to the clusters of its vertices. It is COLLAPSED if two of the three are equal, else a
+ *   candidate: rotated so that its smallest cluster comes first (the orientation stays; (a, b, c) and (a, c, b) are different
+ *   faces). Of the candidates with the same rotated triple only the one with the lowest input index survives, the others are
+ *   DUPLICATES. The output faces are the surviving rotated triples in input order.
+ * 8 OUTPUT VERTICES. The clusters that no output face uses are dropped, the others keep their order, and the faces are renumbered.
+ *
+ * KEYS (acez_simplify_keys). d_keys int64 [m] = the keys of step 1. Refused before anything is launched if an axis would have 2^21
+ *   or more cells: floor((max - origin) / cell) + 1 >= 2^21, or not finite.
+ * CLUSTERS (acez_simplify_clusters). d_order int64 [m]: the stable ascending sort of the keys; d_cluster_sorted int32 [m]: for every
+ *   sorted position its cluster (the number of different keys before it), m where the key is 2^63 - 1. d_vertex_cluster int32 [m]
+ *   = the cluster of every vertex, -1 without a cell.
+ * FACES (acez_simplify_faces). d_face_class uint8 [k]: 0 invalid, 1 degenerate, 2 collapsed, 3 candidate. d_triples int32 [k][3]: a
+ *   candidate's rotated triple, (m, m, m) for every other face. d_corner_keys int32 [3 k]: the cluster of corner 3 t + c of a valid
+ *   face t, m for the corners of the others, so that a stable sort puts every cluster's corners in the order of step 5.
+ * QUADRICS (acez_simplify_quadrics). d_sorted_keys int64 [m] the sorted keys, d_segments int64 [m + 1]: cluster c's vertices stand
+ *   at the sorted positions d_segments[c] .. d_segments[c + 1] - 1 (an empty range past the last cluster); d_corner_order int64 [3 k]
+ *   the stable ascending sort of the corner keys and d_corner_segments int64 [m + 1] likewise. Row c of d_out_quadrics double [m][9]
+ *   = the nine sums of step 5 (A: xx, xy, xz, yy, yz, zz; b: x, y, z) for every cluster c, and no other row is written.
+ * PLACE (acez_simplify_place). d_sorted_keys, d_order, d_segments as above; d_quadrics the sums of QUADRICS, or null for the mean
+ *   placement. Row c of d_out_vertices float32 [m][3], d_out_colours uint8 [m][3] (null iff d_colours is) and d_out_fallback uint8
+ *   [m] (1: a fallback) is written for every cluster c and for no other row.
+ * UNIQUE (acez_simplify_unique). d_perm int64 [k]: the faces sorted by their triples (first, second, third), equal triples in input
+ *   order (two stable sorts: by the third, then by first * (m + 1) + second). d_face_keep uint8 [k] = 1 for the surviving candidates,
+ *   else 0; d_cluster_used uint8 [m] is cleared and set to 1 (plain byte stores) for the clusters of the surviving faces.
+ * Then acez_mesh_compact on (d_out_vertices, d_out_colours, m, d_triples, k, d_face_keep, d_cluster_used and their inclusive sums).
+ *
+ * No kernel waits on anything: no atomics, no loop that is not bounded by a segment length, by m or by svd3's sweep cap. Every index formed
+ * from device data is range-checked before it is used as an address: wrong tables give wrong numbers, never an access out of bounds.
+ *
+ * Asynchronous on `stream`. ACEZ_ERR_INVALID, before anything is launched, for: a null pointer (an array whose count is 0 may be
+ * null), a negative count or one >= 2^31, a cell that is not positive and finite, bounds that are not finite or not ordered, the
+ * limit of 2^21 cells per axis, only one of d_colours / d_out_colours. */
+int acez_simplify_keys(const float* d_vertices, int64_t m, float origin_x, float origin_y, float origin_z, float max_x, float max_y,
+                       float max_z, float cell, int64_t* d_keys, void* stream);
+int acez_simplify_clusters(const int64_t* d_order, const int32_t* d_cluster_sorted, int64_t m, int32_t* d_vertex_cluster, void* stream);
+int acez_simplify_faces(const int32_t* d_faces, int64_t k, const int32_t* d_vertex_cluster, int64_t m, uint8_t* d_face_class,
+                        int32_t* d_triples, int32_t* d_corner_keys, void* stream);
+int acez_simplify_quadrics(const float* d_vertices, int64_t m, const int32_t* d_faces, int64_t k, const int64_t* d_sorted_keys,
+                           const int64_t* d_segments, const int64_t* d_corner_order, const int64_t* d_corner_segments, float origin_x,
+                           float origin_y, float origin_z, float cell, double* d_out_quadrics, void* stream);
+int acez_simplify_place(const float* d_vertices, const uint8_t* d_colours, int64_t m, const int64_t* d_sorted_keys, const int64_t* d_order,
+                        const int64_t* d_segments, const double* d_quadrics, float origin_x, float origin_y, float origin_z, float cell,
+                        float* d_out_vertices, uint8_t* d_out_colours, uint8_t* d_out_fallback, void* stream);
+int acez_simplify_unique(const int32_t* d_triples, const uint8_t* d_face_class, const int64_t* d_perm, int64_t k, int64_t m,
+                         uint8_t* d_face_keep, uint8_t* d_cluster_used, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
