@@ -189,7 +189,7 @@ def cell_means(frames):
     """uint8 device tensor [n,H,W,3] -> uint8 [n,ceil(H/8),ceil(W/8),3] cell means (acez_reproject_cell_means)."""
     import torch
     from . import _native as N
-    from .head import _ptr, _stream
+    from ._device import ptr as _ptr, stream as _stream
     if not (torch.is_tensor(frames) and frames.is_cuda):
         raise RuntimeError("cell_means needs a device tensor: it is a HIP kernel, there is no CPU path")
     assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3
@@ -207,9 +207,9 @@ def score_views(points, colours, views, targets, depth_band=0.05, want_image=Tru
     import ctypes as C
     import torch
     from . import _native as N
-    from .head import _ptr, _stream
+    from ._device import no_cpu, ptr as _ptr, stream as _stream
     if not (torch.is_tensor(targets) and targets.is_cuda):
-        raise RuntimeError("score_views needs device tensors: the scorer is a HIP kernel, there is no CPU path")
+        raise no_cpu("score_views", "the scorer is a HIP kernel")
     dev = targets.device
     tg = targets.to(torch.uint8).contiguous()
     T, oh, ow, _ = tg.shape

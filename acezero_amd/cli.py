@@ -1144,11 +1144,11 @@ def _simplify_cell(value, flag):
     return value
 
 
-def _simplify_summary(info):
-    return (f"{info['vertices_in']} vertices, {info['faces_in']} faces ({info['invalid_faces']} invalid, {info['degenerate_faces']} degenerate, "
+def _simplify_line(cell, placement, info):
+    return (f"Simplified at a cell of {cell} m ({placement}): {info['vertices_in']} vertices, {info['faces_in']} faces ({info['invalid_faces']} invalid, {info['degenerate_faces']} degenerate, "
             f"{info['nonfinite_vertices']} vertices not finite) in {info['clusters']} cells; {info['collapsed_faces']} faces collapsed, "
             f"{info['duplicate_faces']} duplicates and {info['unused_clusters']} cells without a face dropped; {info['vertices_out']} vertices "
-            f"({info['fallbacks']} placed at the mean for want of a usable quadric), {info['faces_out']} faces left")
+            f"({info['fallbacks']} placed at the mean for want of a usable quadric), {info['faces_out']} faces left.")
 
 
 def _add_component_flags(p):
@@ -1266,7 +1266,7 @@ def fuse_depth_main(argv=None):
     if dropped is not None:
         log.info(f"Extracted mesh: {_component_summary(dropped)}.")
     if simplified is not None:
-        log.info(f"Simplified at a cell of {simplify_cell} m ({opt.simplify_placement}): {_simplify_summary(simplified)}.")
+        log.info(_simplify_line(simplify_cell, opt.simplify_placement, simplified))
     log.info(f"Decode {t_decode:.2f} s, upload + kernels + download {t_device:.2f} s, write {t_write:.2f} s.")
     log.info(f"Done. Wrote mesh to: {opt.output_file}")
     return 0
@@ -1284,33 +1284,41 @@ def clean_mesh_parser():
     return p
 
 
-def clean_mesh_main(argv=None):
-    """clean_mesh.py: .ply -> connected components (HIP) -> the kept components' faces and vertices in their order (HIP) -> .ply."""
-    opt = clean_mesh_parser().parse_args(argv)
+def _mesh_command(name, opt, check, why, run):
+    """clean_mesh.py and simplify_mesh.py: .ply -> the device -> one call -> .ply. check(opt) gives what the call takes from the options
+    or refuses them; run(log, that, vertices, colours, faces) gives the new mesh on the device and the line that sums it up."""
     logging.basicConfig(level=logging.INFO)
-    log = logging.getLogger("clean_mesh")
+    log = logging.getLogger(name)
     if not str(opt.output_file).endswith(".ply"):
         raise SystemExit("output file format not supported: use .ply")
-    criteria = _component_criteria(opt)
+    options = check(opt)
     if not opt.input_file.is_file():
         raise SystemExit(f"{opt.input_file}: no such file")
     vertices, colours, faces = read_ply_mesh(opt.input_file)
     import torch
     if not torch.cuda.is_available():
-        raise SystemExit("clean_mesh.py needs a GPU: the component labelling is a HIP kernel, there is no CPU path")
-    from . import mesh
-    if criteria is None:
-        log.info("No criterion given: only faces with an index out of range, degenerate faces and unreferenced vertices are dropped.")
-    d_colours = None if colours is None else torch.from_numpy(colours).cuda()
-    out_v, out_c, out_f, info = mesh.filter_components(torch.from_numpy(vertices).cuda(), d_colours,
-                                                       torch.from_numpy(np.ascontiguousarray(faces, np.int32)).cuda(), **(criteria or {}))
-    log.info(f"Read {len(vertices)} vertices, {len(faces)} faces: {_component_summary(info)}.")
+        raise SystemExit(f"{name}.py needs a GPU: {why}, there is no CPU path")
+    device = lambda a: None if a is None else torch.from_numpy(a).cuda()
+    out_v, out_c, out_f, summary = run(log, options, device(vertices), device(colours), device(np.ascontiguousarray(faces, np.int32)))
+    log.info(summary)
     if len(out_f) == 0:
         log.warning("Nothing is left of the mesh: writing an empty file.")
     out_c = np.full((len(out_v), 3), 200, np.uint8) if out_c is None else out_c.cpu().numpy()
     write_ply(opt.output_file, out_v.cpu().numpy(), out_c, out_f.cpu().numpy())
     log.info(f"Done. Wrote {len(out_v)} vertices, {len(out_f)} faces to: {opt.output_file}")
     return 0
+
+
+def clean_mesh_main(argv=None):
+    """clean_mesh.py: .ply -> connected components (HIP) -> the kept components' faces and vertices in their order (HIP) -> .ply."""
+    def run(log, criteria, vertices, colours, faces):
+        from . import mesh
+        if criteria is None:
+            log.info("No criterion given: only faces with an index out of range, degenerate faces and unreferenced vertices are dropped.")
+        *out, info = mesh.filter_components(vertices, colours, faces, **(criteria or {}))
+        return (*out, f"Read {len(vertices)} vertices, {len(faces)} faces: {_component_summary(info)}.")
+
+    return _mesh_command("clean_mesh", clean_mesh_parser().parse_args(argv), _component_criteria, "the component labelling is a HIP kernel", run)
 
 
 # -------------------------------------------------------------------------------------------------------- simplify_mesh
@@ -1331,28 +1339,13 @@ def simplify_mesh_parser():
 def simplify_mesh_main(argv=None):
     """simplify_mesh.py: .ply -> clusters, per-cluster quadrics and their minimisers, surviving faces (HIP) -> .ply."""
     opt = simplify_mesh_parser().parse_args(argv)
-    logging.basicConfig(level=logging.INFO)
-    log = logging.getLogger("simplify_mesh")
-    if not str(opt.output_file).endswith(".ply"):
-        raise SystemExit("output file format not supported: use .ply")
-    cell = _simplify_cell(opt.cell, "--cell")
-    if not opt.input_file.is_file():
-        raise SystemExit(f"{opt.input_file}: no such file")
-    vertices, colours, faces = read_ply_mesh(opt.input_file)
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("simplify_mesh.py needs a GPU: the simplification is HIP kernels, there is no CPU path")
-    from . import simplify
-    d_colours = None if colours is None else torch.from_numpy(colours).cuda()
-    out_v, out_c, out_f, info = simplify.simplify_mesh(torch.from_numpy(vertices).cuda(), d_colours,
-                                                       torch.from_numpy(np.ascontiguousarray(faces, np.int32)).cuda(), cell, opt.placement)
-    log.info(f"Simplified at a cell of {cell} m ({opt.placement}): {_simplify_summary(info)}.")
-    if len(out_f) == 0:
-        log.warning("Nothing is left of the mesh: writing an empty file.")
-    out_c = np.full((len(out_v), 3), 200, np.uint8) if out_c is None else out_c.cpu().numpy()
-    write_ply(opt.output_file, out_v.cpu().numpy(), out_c, out_f.cpu().numpy())
-    log.info(f"Done. Wrote {len(out_v)} vertices, {len(out_f)} faces to: {opt.output_file}")
-    return 0
+
+    def run(log, cell, vertices, colours, faces):
+        from . import simplify
+        *out, info = simplify.simplify_mesh(vertices, colours, faces, cell, opt.placement)
+        return (*out, _simplify_line(cell, opt.placement, info))
+
+    return _mesh_command("simplify_mesh", opt, lambda o: _simplify_cell(o.cell, "--cell"), "the simplification is HIP kernels", run)
 
 
 # -------------------------------------------------------------------------------------------------------- eval_geometry

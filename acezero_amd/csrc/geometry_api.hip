@@ -27,6 +27,7 @@
 
 #include "acez_common.h"
 #include "icp_solve.h"
+#include "launch1d.h"
 
 namespace {
 
@@ -40,7 +41,6 @@ constexpr int GE_MAX_ROWS = 12;     // (jspan + 2) * (kspan + 2) with the querie
 constexpr int GE_MAX_ISPAN = 4;     // the staged x-range is at most 6 cells where a lane's own is 3
 constexpr int GE_MAX_DIM = 1024;
 constexpr int64_t GE_MAX_CELLS = (int64_t)1 << 24;
-constexpr int64_t GE_MAX_COUNT = ((int64_t)1 << 31) - 1;
 
 struct Grid {
   float ox, oy, oz, c;
@@ -289,8 +289,6 @@ __global__ void __launch_bounds__(GE_THREADS) geom_voxel_means_kernel(const floa
   out[3 * v + 2] = sz / cnt;
 }
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + GE_THREADS - 1) / GE_THREADS); }
-
 }  // namespace
 
 #define GE_REQUIRE_GRID()                                                                                                          \
@@ -302,13 +300,13 @@ inline unsigned blocks_for(int64_t n) { return (unsigned)((n + GE_THREADS - 1) /
 
 extern "C" int acez_geom_cells(const float* d_points, int64_t n, float ox, float oy, float oz, float cell, int nx, int ny, int nz,
                                int32_t* d_out_cells, void* stream) {
-  ACEZ_REQUIRE(n >= 0 && n <= GE_MAX_COUNT, "point count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_POINT_COUNTS(n);
   ACEZ_REQUIRE(n == 0 || (d_points && d_out_cells), "null pointer");
   GE_REQUIRE_GRID();
   if (int rc = acez::require_device("the point grid runs on a gfx950 GPU")) return rc;
   if (n == 0) return ACEZ_OK;
   const Grid g{ox, oy, oz, cell, nx, ny, nz};
-  hipLaunchKernelGGL(geom_cells_kernel, dim3(blocks_for(n)), dim3(GE_THREADS), 0, (hipStream_t)stream, d_points, n, g, d_out_cells);
+  hipLaunchKernelGGL(geom_cells_kernel, dim3(blocks_for(n, GE_THREADS)), dim3(GE_THREADS), 0, (hipStream_t)stream, d_points, n, g, d_out_cells);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
 }
@@ -316,7 +314,7 @@ extern "C" int acez_geom_cells(const float* d_points, int64_t n, float ox, float
 extern "C" int acez_geom_nearest(const float* d_ref, const int32_t* d_ref_index, const int32_t* d_cell_start, int64_t m, float ox, float oy,
                                  float oz, float cell, int nx, int ny, int nz, const float* d_query, int64_t n, float radius,
                                  float* d_out_d2, int32_t* d_out_index, void* stream) {
-  ACEZ_REQUIRE(m >= 0 && m <= GE_MAX_COUNT && n >= 0 && n <= GE_MAX_COUNT, "point count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_POINT_COUNTS(m, n);
   ACEZ_REQUIRE(d_cell_start && (m == 0 || (d_ref && d_ref_index)) && (n == 0 || (d_query && d_out_d2 && d_out_index)), "null pointer");
   GE_REQUIRE_GRID();
   ACEZ_REQUIRE(isfinite(radius) && radius > 0.0f, "the radius must be positive and finite");
@@ -326,7 +324,7 @@ extern "C" int acez_geom_nearest(const float* d_ref, const int32_t* d_ref_index,
   if (n == 0) return ACEZ_OK;
   const Grid g{ox, oy, oz, cell, nx, ny, nz};
   const int plain = ACEZ_DIAG_ENV("ACEZ_GEOM_PLAIN") != nullptr;    // diagnostics build: every workgroup takes the per-lane form
-  hipLaunchKernelGGL(geom_nearest_kernel, dim3((unsigned)((n + GN_THREADS - 1) / GN_THREADS)), dim3(GN_THREADS), 0, (hipStream_t)stream, d_ref, d_ref_index, d_cell_start,
+  hipLaunchKernelGGL(geom_nearest_kernel, dim3(blocks_for(n, GN_THREADS)), dim3(GN_THREADS), 0, (hipStream_t)stream, d_ref, d_ref_index, d_cell_start,
                      (int)m, g, d_query, n, radius * radius, d_out_d2, d_out_index, plain);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
@@ -334,11 +332,11 @@ extern "C" int acez_geom_nearest(const float* d_ref, const int32_t* d_ref_index,
 
 extern "C" int acez_geom_voxel_means(const float* d_points, int64_t n, const int32_t* d_segment_start, int64_t segments, float* d_out_means,
                                      void* stream) {
-  ACEZ_REQUIRE(n >= 0 && n <= GE_MAX_COUNT && segments >= 0 && segments <= GE_MAX_COUNT, "count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_COUNTS(n, segments);
   ACEZ_REQUIRE(d_segment_start && (n == 0 || d_points) && (segments == 0 || d_out_means), "null pointer");
   if (int rc = acez::require_device("the voxel downsample runs on a gfx950 GPU")) return rc;
   if (segments == 0) return ACEZ_OK;
-  hipLaunchKernelGGL(geom_voxel_means_kernel, dim3(blocks_for(segments)), dim3(GE_THREADS), 0, (hipStream_t)stream, d_points, n,
+  hipLaunchKernelGGL(geom_voxel_means_kernel, dim3(blocks_for(segments, GE_THREADS)), dim3(GE_THREADS), 0, (hipStream_t)stream, d_points, n,
                      d_segment_start, segments, d_out_means);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
@@ -347,7 +345,7 @@ extern "C" int acez_geom_voxel_means(const float* d_points, int64_t n, const int
 extern "C" int acez_geom_icp_accumulate(const float* d_ref, const int32_t* d_ref_index, const int32_t* d_cell_start, int64_t m, float ox,
                                         float oy, float oz, float cell, int nx, int ny, int nz, const float* d_src, int64_t n, float radius,
                                         float px, float py, float pz, const double* d_state, double* d_partials, void* stream) {
-  ACEZ_REQUIRE(m >= 0 && m <= GE_MAX_COUNT && n >= 1 && n <= GE_MAX_COUNT, "point count out of range (references 0 .. 2^31 - 1, sources 1 .. 2^31 - 1)");
+  ACEZ_REQUIRE(m >= 0 && m <= ACEZ_MAX_COUNT && n >= 1 && n <= ACEZ_MAX_COUNT, "point count out of range (references 0 .. 2^31 - 1, sources 1 .. 2^31 - 1)");
   ACEZ_REQUIRE(d_cell_start && (m == 0 || (d_ref && d_ref_index)) && d_src && d_state && d_partials, "null pointer");
   GE_REQUIRE_GRID();
   ACEZ_REQUIRE(isfinite(radius) && radius > 0.0f, "the radius must be positive and finite");
@@ -356,7 +354,7 @@ extern "C" int acez_geom_icp_accumulate(const float* d_ref, const int32_t* d_ref
   if (int rc = acez::require_device("the ICP correspondence search runs on a gfx950 GPU")) return rc;
   const Grid g{ox, oy, oz, cell, nx, ny, nz};
   const int plain = ACEZ_DIAG_ENV("ACEZ_GEOM_PLAIN") != nullptr;    // diagnostics build: every workgroup takes the per-lane form
-  hipLaunchKernelGGL(geom_icp_accumulate_kernel, dim3((unsigned)((n + GN_THREADS - 1) / GN_THREADS)), dim3(GN_THREADS), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(geom_icp_accumulate_kernel, dim3(blocks_for(n, GN_THREADS)), dim3(GN_THREADS), 0, (hipStream_t)stream,
                      d_ref, d_ref_index, d_cell_start, (int)m, g, d_src, n, radius * radius, px, py, pz, d_state, d_partials, plain);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
@@ -364,7 +362,7 @@ extern "C" int acez_geom_icp_accumulate(const float* d_ref, const int32_t* d_ref
 
 extern "C" int acez_geom_icp_update(const double* d_partials, int64_t n, float px, float py, float pz, int with_scale, double rel_fitness,
                                     double rel_rmse, int max_iterations, double* d_state, double* d_history, void* stream) {
-  ACEZ_REQUIRE(n >= 1 && n <= GE_MAX_COUNT, "point count out of range (sources 1 .. 2^31 - 1)");
+  ACEZ_REQUIRE(n >= 1 && n <= ACEZ_MAX_COUNT, "point count out of range (sources 1 .. 2^31 - 1)");
   ACEZ_REQUIRE(d_partials && d_state && d_history, "null pointer");
   ACEZ_REQUIRE(isfinite(px) && isfinite(py) && isfinite(pz), "non-finite pivot");
   ACEZ_REQUIRE(max_iterations >= 1, "max_iterations must be at least 1");

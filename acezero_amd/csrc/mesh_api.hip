@@ -28,13 +28,13 @@
 #include <stdint.h>
 
 #include "acez_common.h"
+#include "launch1d.h"
 
 namespace {
 
 using namespace acez;
 
 constexpr int MS_THREADS = 256;
-constexpr int64_t MS_MAX_COUNT = ((int64_t)1 << 31) - 1;
 
 #define MS_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 
@@ -195,27 +195,25 @@ __global__ void __launch_bounds__(MS_THREADS) compact_kernel(const float* __rest
   }
 }
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + MS_THREADS - 1) / MS_THREADS); }
-
 }  // namespace
 
 extern "C" int acez_mesh_components(const int32_t* d_faces, int64_t k, int64_t m, int32_t* d_labels, int32_t* d_status, void* stream) {
-  ACEZ_REQUIRE(m >= 0 && m <= MS_MAX_COUNT && k >= 0 && k <= MS_MAX_COUNT, "count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_COUNTS(m, k);
   ACEZ_REQUIRE(d_status && (m == 0 || d_labels) && (k == 0 || d_faces), "null pointer");
   if (int rc = acez::require_device("mesh components are labelled on a gfx950 GPU")) return rc;
   hipStream_t s = (hipStream_t)stream;
   ACEZ_HIP_CHECK(hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
   if (m == 0) return ACEZ_OK;
-  hipLaunchKernelGGL(init_kernel, dim3(blocks_for(m)), dim3(MS_THREADS), 0, s, d_labels, (int)m);
-  if (k > 0) hipLaunchKernelGGL(hook_kernel, dim3(blocks_for(k)), dim3(MS_THREADS), 0, s, d_faces, k, (int)m, d_labels, d_status);
-  hipLaunchKernelGGL(flatten_kernel, dim3(blocks_for(m)), dim3(MS_THREADS), 0, s, d_labels, (int)m, d_status);
+  hipLaunchKernelGGL(init_kernel, dim3(blocks_for(m, MS_THREADS)), dim3(MS_THREADS), 0, s, d_labels, (int)m);
+  if (k > 0) hipLaunchKernelGGL(hook_kernel, dim3(blocks_for(k, MS_THREADS)), dim3(MS_THREADS), 0, s, d_faces, k, (int)m, d_labels, d_status);
+  hipLaunchKernelGGL(flatten_kernel, dim3(blocks_for(m, MS_THREADS)), dim3(MS_THREADS), 0, s, d_labels, (int)m, d_status);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
 }
 
 extern "C" int acez_mesh_component_counts(const int32_t* d_faces, int64_t k, const int32_t* d_labels, int64_t m, int32_t* d_faces_of,
                                           int32_t* d_vertices_of, void* stream) {
-  ACEZ_REQUIRE(m >= 0 && m <= MS_MAX_COUNT && k >= 0 && k <= MS_MAX_COUNT, "count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_COUNTS(m, k);
   ACEZ_REQUIRE((m == 0 || (d_labels && d_faces_of && d_vertices_of)) && (k == 0 || d_faces), "null pointer");
   if (int rc = acez::require_device("mesh components are counted on a gfx950 GPU")) return rc;
   if (m == 0) return ACEZ_OK;
@@ -223,8 +221,8 @@ extern "C" int acez_mesh_component_counts(const int32_t* d_faces, int64_t k, con
   ACEZ_HIP_CHECK(hipMemsetAsync(d_faces_of, 0, sizeof(int32_t) * (size_t)m, s));
   ACEZ_HIP_CHECK(hipMemsetAsync(d_vertices_of, 0, sizeof(int32_t) * (size_t)m, s));
   if (k == 0) return ACEZ_OK;
-  hipLaunchKernelGGL(count_faces_kernel, dim3(blocks_for(k)), dim3(MS_THREADS), 0, s, d_faces, k, d_labels, (int)m, d_faces_of);
-  hipLaunchKernelGGL(count_vertices_kernel, dim3(blocks_for(m)), dim3(MS_THREADS), 0, s, d_labels, (int)m, (const int32_t*)d_faces_of,
+  hipLaunchKernelGGL(count_faces_kernel, dim3(blocks_for(k, MS_THREADS)), dim3(MS_THREADS), 0, s, d_faces, k, d_labels, (int)m, d_faces_of);
+  hipLaunchKernelGGL(count_vertices_kernel, dim3(blocks_for(m, MS_THREADS)), dim3(MS_THREADS), 0, s, d_labels, (int)m, (const int32_t*)d_faces_of,
                      d_vertices_of);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
@@ -232,13 +230,13 @@ extern "C" int acez_mesh_component_counts(const int32_t* d_faces, int64_t k, con
 
 extern "C" int acez_mesh_select(const int32_t* d_faces, int64_t k, const int32_t* d_labels, int64_t m, const uint8_t* d_keep_component,
                                 uint8_t* d_face_keep, uint8_t* d_vertex_used, void* stream) {
-  ACEZ_REQUIRE(m >= 0 && m <= MS_MAX_COUNT && k >= 0 && k <= MS_MAX_COUNT, "count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_COUNTS(m, k);
   ACEZ_REQUIRE((m == 0 || (d_labels && d_keep_component && d_vertex_used)) && (k == 0 || (d_faces && d_face_keep)), "null pointer");
   if (int rc = acez::require_device("mesh components are selected on a gfx950 GPU")) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (m > 0) ACEZ_HIP_CHECK(hipMemsetAsync(d_vertex_used, 0, (size_t)m, s));
   if (k == 0) return ACEZ_OK;
-  hipLaunchKernelGGL(select_kernel, dim3(blocks_for(k)), dim3(MS_THREADS), 0, s, d_faces, k, d_labels, (int)m, d_keep_component, d_face_keep,
+  hipLaunchKernelGGL(select_kernel, dim3(blocks_for(k, MS_THREADS)), dim3(MS_THREADS), 0, s, d_faces, k, d_labels, (int)m, d_keep_component, d_face_keep,
                      d_vertex_used);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
@@ -248,7 +246,7 @@ extern "C" int acez_mesh_compact(const float* d_vertices, const uint8_t* d_colou
                                  const uint8_t* d_face_keep, const int32_t* d_face_rank, const uint8_t* d_vertex_used,
                                  const int32_t* d_vertex_rank, float* d_out_vertices, uint8_t* d_out_colours, int64_t n_vertices,
                                  int32_t* d_out_faces, int64_t n_faces, void* stream) {
-  ACEZ_REQUIRE(m >= 0 && m <= MS_MAX_COUNT && k >= 0 && k <= MS_MAX_COUNT, "count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_COUNTS(m, k);
   ACEZ_REQUIRE(n_vertices >= 0 && n_vertices <= m && n_faces >= 0 && n_faces <= k, "more output rows than input rows, or a negative number");
   ACEZ_REQUIRE((d_colours == nullptr) == (d_out_colours == nullptr), "vertex colours and output colours go together");
   ACEZ_REQUIRE((m == 0 || (d_vertices && d_vertex_used && d_vertex_rank)) && (k == 0 || (d_faces && d_face_keep && d_face_rank)), "null pointer");
@@ -256,7 +254,7 @@ extern "C" int acez_mesh_compact(const float* d_vertices, const uint8_t* d_colou
   if (int rc = acez::require_device("meshes are compacted on a gfx950 GPU")) return rc;
   const int64_t lanes = m > k ? m : k;
   if (lanes == 0) return ACEZ_OK;
-  hipLaunchKernelGGL(compact_kernel, dim3(blocks_for(lanes)), dim3(MS_THREADS), 0, (hipStream_t)stream, d_vertices, d_colours, (int)m, d_faces, k,
+  hipLaunchKernelGGL(compact_kernel, dim3(blocks_for(lanes, MS_THREADS)), dim3(MS_THREADS), 0, (hipStream_t)stream, d_vertices, d_colours, (int)m, d_faces, k,
                      d_face_keep, d_face_rank, d_vertex_used, d_vertex_rank, d_out_vertices, d_out_colours, (int)n_vertices, d_out_faces, (int)n_faces);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "acez_common.h"
+#include "launch1d.h"
 #include "simplify_solve.h"
 
 namespace {
@@ -34,7 +35,6 @@ using namespace acez;
 
 constexpr int SQ_THREADS = 256, SQ_WAVE = 64;
 constexpr int64_t SQ_QUADRIC_BLOCKS = 4096;      // of four wavefronts: enough to fill 256 CUs several times over, whatever m is
-constexpr int64_t SQ_MAX_COUNT = ((int64_t)1 << 31) - 1;
 constexpr int SQ_AXIS_BITS = 21;
 constexpr int64_t SQ_AXIS_CELLS = (int64_t)1 << SQ_AXIS_BITS;
 constexpr int64_t SQ_NO_CELL = INT64_MAX;
@@ -209,10 +209,6 @@ __global__ void __launch_bounds__(SQ_THREADS) unique_kernel(const int32_t* __res
   cluster_used[r2] = 1;
 }
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + SQ_THREADS - 1) / SQ_THREADS); }
-
-inline bool counts_ok(int64_t m, int64_t k) { return m >= 0 && m <= SQ_MAX_COUNT && k >= 0 && k <= SQ_MAX_COUNT; }
-
 // the grid of step 1: finite bounds, a positive finite cell, and fewer than 2^21 cells on every axis
 inline bool grid_ok(const float* o, const float* h, float cell) {
   if (!(isfinite(cell) && cell > 0.0f)) return false;
@@ -227,37 +223,37 @@ inline bool grid_ok(const float* o, const float* h, float cell) {
 
 extern "C" int acez_simplify_keys(const float* d_vertices, int64_t m, float origin_x, float origin_y, float origin_z, float max_x, float max_y,
                                   float max_z, float cell, int64_t* d_keys, void* stream) {
-  ACEZ_REQUIRE(counts_ok(m, 0), "count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_COUNTS(m);
   const float o[3] = {origin_x, origin_y, origin_z}, h[3] = {max_x, max_y, max_z};
   ACEZ_REQUIRE(grid_ok(o, h, cell), "the cell must be positive and finite, the bounds finite and ordered, and an axis have fewer than 2^21 cells");
   ACEZ_REQUIRE(m == 0 || (d_vertices && d_keys), "null pointer");
   if (int rc = acez::require_device("meshes are simplified on a gfx950 GPU")) return rc;
   if (m == 0) return ACEZ_OK;
-  hipLaunchKernelGGL(keys_kernel, dim3(blocks_for(m)), dim3(SQ_THREADS), 0, (hipStream_t)stream, d_vertices, (int)m, origin_x, origin_y, origin_z,
+  hipLaunchKernelGGL(keys_kernel, dim3(blocks_for(m, SQ_THREADS)), dim3(SQ_THREADS), 0, (hipStream_t)stream, d_vertices, (int)m, origin_x, origin_y, origin_z,
                      cell, d_keys);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
 }
 
 extern "C" int acez_simplify_clusters(const int64_t* d_order, const int32_t* d_cluster_sorted, int64_t m, int32_t* d_vertex_cluster, void* stream) {
-  ACEZ_REQUIRE(counts_ok(m, 0), "count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_COUNTS(m);
   ACEZ_REQUIRE(m == 0 || (d_order && d_cluster_sorted && d_vertex_cluster), "null pointer");
   if (int rc = acez::require_device("meshes are simplified on a gfx950 GPU")) return rc;
   if (m == 0) return ACEZ_OK;
   hipStream_t s = (hipStream_t)stream;
   ACEZ_HIP_CHECK(hipMemsetAsync(d_vertex_cluster, 0xff, sizeof(int32_t) * (size_t)m, s));      // -1: no cluster
-  hipLaunchKernelGGL(clusters_kernel, dim3(blocks_for(m)), dim3(SQ_THREADS), 0, s, d_order, d_cluster_sorted, (int)m, d_vertex_cluster);
+  hipLaunchKernelGGL(clusters_kernel, dim3(blocks_for(m, SQ_THREADS)), dim3(SQ_THREADS), 0, s, d_order, d_cluster_sorted, (int)m, d_vertex_cluster);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
 }
 
 extern "C" int acez_simplify_faces(const int32_t* d_faces, int64_t k, const int32_t* d_vertex_cluster, int64_t m, uint8_t* d_face_class,
                                    int32_t* d_triples, int32_t* d_corner_keys, void* stream) {
-  ACEZ_REQUIRE(counts_ok(m, k), "count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_COUNTS(m, k);
   ACEZ_REQUIRE((m == 0 || d_vertex_cluster) && (k == 0 || (d_faces && d_face_class && d_triples && d_corner_keys)), "null pointer");
   if (int rc = acez::require_device("meshes are simplified on a gfx950 GPU")) return rc;
   if (k == 0) return ACEZ_OK;
-  hipLaunchKernelGGL(faces_kernel, dim3(blocks_for(k)), dim3(SQ_THREADS), 0, (hipStream_t)stream, d_faces, k, d_vertex_cluster, (int)m, d_face_class,
+  hipLaunchKernelGGL(faces_kernel, dim3(blocks_for(k, SQ_THREADS)), dim3(SQ_THREADS), 0, (hipStream_t)stream, d_faces, k, d_vertex_cluster, (int)m, d_face_class,
                      d_triples, d_corner_keys);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
@@ -266,7 +262,7 @@ extern "C" int acez_simplify_faces(const int32_t* d_faces, int64_t k, const int3
 extern "C" int acez_simplify_quadrics(const float* d_vertices, int64_t m, const int32_t* d_faces, int64_t k, const int64_t* d_sorted_keys,
                                       const int64_t* d_segments, const int64_t* d_corner_order, const int64_t* d_corner_segments, float origin_x,
                                       float origin_y, float origin_z, float cell, double* d_out_quadrics, void* stream) {
-  ACEZ_REQUIRE(counts_ok(m, k), "count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_COUNTS(m, k);
   ACEZ_REQUIRE(isfinite(cell) && cell > 0.0f && isfinite(origin_x) && isfinite(origin_y) && isfinite(origin_z),
                "the cell must be positive and finite, the origin finite");
   ACEZ_REQUIRE(m == 0 || (d_vertices && d_sorted_keys && d_segments && d_corner_segments && d_out_quadrics), "null pointer");
@@ -285,14 +281,14 @@ extern "C" int acez_simplify_place(const float* d_vertices, const uint8_t* d_col
                                    const int64_t* d_order, const int64_t* d_segments, const double* d_quadrics, float origin_x, float origin_y,
                                    float origin_z, float cell, float* d_out_vertices, uint8_t* d_out_colours, uint8_t* d_out_fallback,
                                    void* stream) {
-  ACEZ_REQUIRE(counts_ok(m, 0), "count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_COUNTS(m);
   ACEZ_REQUIRE(isfinite(cell) && cell > 0.0f && isfinite(origin_x) && isfinite(origin_y) && isfinite(origin_z),
                "the cell must be positive and finite, the origin finite");
   ACEZ_REQUIRE((d_colours == nullptr) == (d_out_colours == nullptr), "vertex colours and output colours go together");
   ACEZ_REQUIRE(m == 0 || (d_vertices && d_sorted_keys && d_order && d_segments && d_out_vertices && d_out_fallback), "null pointer");
   if (int rc = acez::require_device("meshes are simplified on a gfx950 GPU")) return rc;
   if (m == 0) return ACEZ_OK;
-  hipLaunchKernelGGL(place_kernel, dim3(blocks_for(m)), dim3(SQ_THREADS), 0, (hipStream_t)stream, d_vertices, d_colours, (int)m, d_sorted_keys, d_order,
+  hipLaunchKernelGGL(place_kernel, dim3(blocks_for(m, SQ_THREADS)), dim3(SQ_THREADS), 0, (hipStream_t)stream, d_vertices, d_colours, (int)m, d_sorted_keys, d_order,
                      d_segments, d_quadrics, origin_x, origin_y, origin_z, cell, d_out_vertices, d_out_colours, d_out_fallback);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
@@ -300,7 +296,7 @@ extern "C" int acez_simplify_place(const float* d_vertices, const uint8_t* d_col
 
 extern "C" int acez_simplify_unique(const int32_t* d_triples, const uint8_t* d_face_class, const int64_t* d_perm, int64_t k, int64_t m,
                                     uint8_t* d_face_keep, uint8_t* d_cluster_used, void* stream) {
-  ACEZ_REQUIRE(counts_ok(m, k), "count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_COUNTS(m, k);
   ACEZ_REQUIRE((m == 0 || d_cluster_used) && (k == 0 || (d_triples && d_face_class && d_perm && d_face_keep)), "null pointer");
   if (int rc = acez::require_device("meshes are simplified on a gfx950 GPU")) return rc;
   hipStream_t s = (hipStream_t)stream;
@@ -308,7 +304,7 @@ extern "C" int acez_simplify_unique(const int32_t* d_triples, const uint8_t* d_f
   if (k == 0) return ACEZ_OK;
   ACEZ_HIP_CHECK(hipMemsetAsync(d_face_keep, 0, (size_t)k, s));
   if (m == 0) return ACEZ_OK;
-  hipLaunchKernelGGL(unique_kernel, dim3(blocks_for(k)), dim3(SQ_THREADS), 0, s, d_triples, d_face_class, d_perm, k, (int)m, d_face_keep, d_cluster_used);
+  hipLaunchKernelGGL(unique_kernel, dim3(blocks_for(k, SQ_THREADS)), dim3(SQ_THREADS), 0, s, d_triples, d_face_class, d_perm, k, (int)m, d_face_keep, d_cluster_used);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
 }

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "acez_common.h"
+#include "launch1d.h"
 #include "ransac_math.h"
 
 namespace {
@@ -28,7 +29,6 @@ using rsm::mix64;
 
 constexpr int SF_THREADS = 256;
 constexpr int SF_MAX_POLYGON = 1024;
-constexpr int64_t SF_MAX_COUNT = ((int64_t)1 << 31) - 1;
 constexpr uint64_t SF_STRIDE = 0xD1B54A32D192ED03ULL;
 constexpr double SF_2_53 = 1.0 / 9007199254740992.0;   // 2^-53
 constexpr double SF_2_24 = 1.0 / 16777216.0;            // 2^-24
@@ -134,18 +134,16 @@ __global__ void __launch_bounds__(SF_THREADS) crop_polygon_kernel(const float* _
   keep[p] = ok ? 1 : 0;
 }
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + SF_THREADS - 1) / SF_THREADS); }
-
 }  // namespace
 
 extern "C" int acez_geom_face_counts(const float* d_vertices, int64_t m, const int32_t* d_faces, int64_t k, double density, uint64_t seed,
                                      int32_t* d_out_counts, double* d_out_areas, void* stream) {
-  ACEZ_REQUIRE(m >= 0 && m <= SF_MAX_COUNT && k >= 0 && k <= SF_MAX_COUNT, "count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_COUNTS(m, k);
   ACEZ_REQUIRE((m == 0 || d_vertices) && (k == 0 || (d_faces && d_out_counts && d_out_areas)), "null pointer");
   ACEZ_REQUIRE(isfinite(density) && density > 0.0, "the density must be positive and finite");
   if (int rc = acez::require_device("the mesh sampler runs on a gfx950 GPU")) return rc;
   if (k == 0) return ACEZ_OK;
-  hipLaunchKernelGGL(face_counts_kernel, dim3(blocks_for(k)), dim3(SF_THREADS), 0, (hipStream_t)stream, d_vertices, (int)m, d_faces, k, density,
+  hipLaunchKernelGGL(face_counts_kernel, dim3(blocks_for(k, SF_THREADS)), dim3(SF_THREADS), 0, (hipStream_t)stream, d_vertices, (int)m, d_faces, k, density,
                      mix64(seed), d_out_counts, d_out_areas);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
@@ -154,13 +152,13 @@ extern "C" int acez_geom_face_counts(const float* d_vertices, int64_t m, const i
 extern "C" int acez_geom_sample_faces(const float* d_vertices, int64_t m, const int32_t* d_faces, int64_t k, const int64_t* d_offsets, int64_t n,
                                       uint64_t seed, const uint8_t* d_colours, float* d_out_points, int32_t* d_out_face,
                                       uint8_t* d_out_colours, void* stream) {
-  ACEZ_REQUIRE(m >= 0 && m <= SF_MAX_COUNT && k >= 0 && k <= SF_MAX_COUNT && n >= 0 && n <= SF_MAX_COUNT, "count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_COUNTS(m, k, n);
   ACEZ_REQUIRE(n == 0 || (m >= 1 && k >= 1), "samples of a mesh without vertices or without faces");
   ACEZ_REQUIRE(n == 0 || (d_vertices && d_faces && d_offsets && d_out_points && d_out_face), "null pointer");
   ACEZ_REQUIRE((d_colours == nullptr) == (d_out_colours == nullptr), "vertex colours and sample colours go together");
   if (int rc = acez::require_device("the mesh sampler runs on a gfx950 GPU")) return rc;
   if (n == 0) return ACEZ_OK;
-  hipLaunchKernelGGL(sample_faces_kernel, dim3(blocks_for(n)), dim3(SF_THREADS), 0, (hipStream_t)stream, d_vertices, (int)m, d_faces, (int)k,
+  hipLaunchKernelGGL(sample_faces_kernel, dim3(blocks_for(n, SF_THREADS)), dim3(SF_THREADS), 0, (hipStream_t)stream, d_vertices, (int)m, d_faces, (int)k,
                      d_offsets, n, mix64(seed), d_colours, d_out_points, d_out_face, d_out_colours);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
@@ -168,14 +166,14 @@ extern "C" int acez_geom_sample_faces(const float* d_vertices, int64_t m, const 
 
 extern "C" int acez_geom_crop_polygon(const float* d_points, int64_t n, const float* d_polygon, int corners, int axis, float axis_min,
                                       float axis_max, uint8_t* d_out_keep, void* stream) {
-  ACEZ_REQUIRE(n >= 0 && n <= SF_MAX_COUNT, "point count out of range (0 .. 2^31 - 1)");
+  ACEZ_REQUIRE_POINT_COUNTS(n);
   ACEZ_REQUIRE(corners >= 3 && corners <= SF_MAX_POLYGON, "the polygon must have 3 .. 1024 corners");
   ACEZ_REQUIRE(d_polygon && (n == 0 || (d_points && d_out_keep)), "null pointer");
   ACEZ_REQUIRE(axis >= 0 && axis <= 2, "the orthogonal axis must be 0, 1 or 2");
   ACEZ_REQUIRE(isfinite(axis_min) && isfinite(axis_max) && axis_min <= axis_max, "the axis bounds must be finite, the lower not above the upper");
   if (int rc = acez::require_device("the polygon crop runs on a gfx950 GPU")) return rc;
   if (n == 0) return ACEZ_OK;
-  hipLaunchKernelGGL(crop_polygon_kernel, dim3(blocks_for(n)), dim3(SF_THREADS), 0, (hipStream_t)stream, d_points, n, d_polygon, corners, axis,
+  hipLaunchKernelGGL(crop_polygon_kernel, dim3(blocks_for(n, SF_THREADS)), dim3(SF_THREADS), 0, (hipStream_t)stream, d_points, n, d_polygon, corners, axis,
                      axis_min, axis_max, d_out_keep);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;

@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from ._device import no_cpu
 
 
 def _w2c34(world_to_cam, cam_to_world, n):
@@ -92,7 +93,7 @@ def calls(depth_u16, world_to_cam, cam_to_world, focals, ppx, ppy, rgb, frames_p
     ppy = None if ppy is None else _per_frame(ppy, n)
     for images in (depth_u16, rgb):
         if torch.is_tensor(images) and images.device.type != device.type:
-            raise RuntimeError("TSDFVolume.integrate needs device tensors: TSDF fusion is a HIP kernel, there is no CPU path")
+            raise no_cpu("TSDFVolume.integrate", "TSDF fusion is a HIP kernel")
     for lo in range(0, n, int(frames_per_call)):
         part = slice(lo, min(n, lo + int(frames_per_call)))
         d_depth, sizes, offsets = pack(depth_u16[part], np.uint16, (), device)

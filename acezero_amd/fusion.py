@@ -14,11 +14,7 @@ import torch
 
 from . import _native as N
 from .frames import _per_frame, _w2c34, calls  # noqa: F401  (_w2c34: the tests restate poses through fusion._w2c34)
-from .head import _ptr, _stream
-
-
-def _no_cpu(what):
-    return RuntimeError(f"{what} needs device tensors: TSDF fusion is a HIP kernel, there is no CPU path")
+from ._device import no_cpu, ptr as _ptr, stream as _stream
 
 
 class _Volume:
@@ -29,7 +25,7 @@ class _Volume:
     def __init__(self, origin, dims, voxel_size, truncation, device, max_weight):
         device = torch.device(device)
         if device.type != "cuda":
-            raise _no_cpu(type(self).__name__)
+            raise no_cpu(type(self).__name__, "TSDF fusion is a HIP kernel")
         self.origin = tuple(float(np.float32(o)) for o in origin)
         self.dims = tuple(int(d) for d in dims)
         self.voxel_size, self.truncation, self.max_weight = float(voxel_size), float(truncation), float(max_weight)

@@ -20,20 +20,17 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .head import _ptr, _stream
+from ._device import no_cpu, ptr as _ptr, stream as _stream
 
 MAX_DIM = 1024                      # cells per axis (section N)
 MAX_CELLS = 2 ** 24
 MARGIN = np.float32(1.0 + 2.0 ** -10)
-
-
-def _no_cpu(what):
-    return RuntimeError(f"{what} needs device tensors: the cloud distances are HIP kernels, there is no CPU path")
+WHY = "the cloud distances are HIP kernels"
 
 
 def _points(t, what):
     if not torch.is_tensor(t) or not t.is_cuda:
-        raise _no_cpu(what)
+        raise no_cpu(what, WHY)
     if t.ndim != 2 or t.shape[1] != 3:
         raise ValueError(f"{what}: expected points [n,3], got {tuple(t.shape)}")
     return t.to(torch.float32).contiguous()
@@ -363,13 +360,13 @@ def sample_mesh(vertices, faces, *, spacing, seed=0, colours=None):
     vertices = _points(vertices, "sample_mesh")
     dev = vertices.device
     if not torch.is_tensor(faces) or faces.device != dev:
-        raise _no_cpu("sample_mesh")
+        raise no_cpu("sample_mesh", WHY)
     if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64):
         raise ValueError(f"sample_mesh: expected integer faces [k,3], got {faces.dtype} {tuple(faces.shape)}")
     faces = faces.to(torch.int32).contiguous()
     if colours is not None:
         if not torch.is_tensor(colours) or colours.device != dev:
-            raise _no_cpu("sample_mesh")
+            raise no_cpu("sample_mesh", WHY)
         if colours.dtype != torch.uint8 or tuple(colours.shape) != tuple(vertices.shape):
             raise ValueError(f"sample_mesh: expected uint8 colours {tuple(vertices.shape)}, got {colours.dtype} {tuple(colours.shape)}")
         colours = colours.contiguous()

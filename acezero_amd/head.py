@@ -14,6 +14,7 @@ import torch
 
 from . import DEFAULT_DTYPE  # when neither an argument nor $ACEZ_DTYPE names a format
 from . import _native as N
+from ._device import ptr as _ptr, stream as _stream  # the tests take them from here too
 
 LOSS_TYPES = {"tanh": 0, "dyntanh": 1, "l1": 2, "l1+sqrt": 3, "l1+logl1": 4, "l1+log": 4}
 SCHEDULES = {"constant": 0, "1cyclepoly": 1, "circle": 2}
@@ -59,14 +60,6 @@ def init_pose_network(seed):
         parts.append((torch.rand(o * k, generator=g) * 2 - 1) * bound)
         parts.append((torch.rand(o, generator=g) * 2 - 1) * bound)
     return torch.cat(parts).float()
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def epoch_permutations(n, seed, device):

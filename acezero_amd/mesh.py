@@ -14,23 +14,60 @@ import math
 import torch
 
 from . import _native as N
-from .head import _ptr, _stream
+from ._device import no_cpu, ptr as _ptr, stream as _stream
 
 __all__ = ["connected_components", "component_sizes", "filter_components"]
 
 HISTOGRAM_EDGES = (10, 100, 1000, 10000)     # info["size_histogram"]: the components of 1-9, 10-99, .. and 10000 or more faces
+WHY = "mesh components are HIP kernels"      # there is no CPU path
 
 
-def _no_cpu(what):
-    return RuntimeError(f"{what} needs device tensors: mesh components are HIP kernels, there is no CPU path")
-
-
-def _faces(faces, what):
+def _faces(faces, what, why=WHY):
     if not torch.is_tensor(faces) or not faces.is_cuda:
-        raise _no_cpu(what)
+        raise no_cpu(what, why)
     if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
         raise ValueError(f"{what}: expected int32 faces [k,3], got {faces.dtype} {tuple(faces.shape)}")
     return faces.contiguous()
+
+
+def check_mesh(vertices, colours, faces, what, why):
+    """(vertices float32 [m,3], colours uint8 [m,3] or None, faces int32 [k,3]), contiguous, or the error of the first rule broken:
+    all of them device tensors, then the faces' type and shape, the vertices', the colours'."""
+    if not all(torch.is_tensor(t) and t.is_cuda for t in (vertices, faces) + (() if colours is None else (colours,))):
+        raise no_cpu(what, why)
+    faces = _faces(faces, what, why)
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+        raise ValueError(f"{what}: expected float32 vertices [m,3], got {vertices.dtype} {tuple(vertices.shape)}")
+    if colours is not None and (colours.shape != vertices.shape or colours.dtype != torch.uint8):
+        raise ValueError(f"{what}: expected uint8 colours {tuple(vertices.shape)}, got {colours.dtype} {tuple(colours.shape)}")
+    return vertices.contiguous(), None if colours is None else colours.contiguous(), faces
+
+
+def empty_mesh(device, with_colours):                # (vertices, colours or None, faces) of the mesh without a vertex
+    return (torch.empty((0, 3), dtype=torch.float32, device=device), torch.empty((0, 3), dtype=torch.uint8, device=device) if with_colours else None,
+            torch.empty((0, 3), dtype=torch.int32, device=device))
+
+
+def compact_ranks(face_keep, vertex_used):
+    """The compaction's first half, without a synchronisation: (face_rank, vertex_rank, n_faces, n_vertices) from the byte flags of the
+    faces and of the vertices (at least one): their inclusive int32 prefix sums, and the rows that stay as int64 device scalars."""
+    face_rank, vertex_rank = (torch.cumsum(flags, 0, dtype=torch.int32) for flags in (face_keep, vertex_used))
+    n_faces = face_rank[-1].long() if face_keep.shape[0] else torch.zeros((), dtype=torch.int64, device=face_keep.device)
+    return face_rank, vertex_rank, n_faces, vertex_rank[-1].long()
+
+
+def compact(vertices, colours, faces, face_keep, face_rank, vertex_used, vertex_rank, n_faces, n_vertices):
+    """The compaction's second half, the two counts on the host: the flagged rows in their order, the faces renamed (acez_mesh_compact)."""
+    dev, m, k = vertices.device, vertices.shape[0], faces.shape[0]
+    out_vertices = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
+    out_colours = None if colours is None else torch.empty((n_vertices, 3), dtype=torch.uint8, device=dev)
+    out_faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+    if n_vertices:                                                                   # else no face is kept: nothing to move
+        with torch.cuda.device(dev):
+            N.check(N.lib().acez_mesh_compact(_ptr(vertices), _ptr(colours), m, _ptr(faces), k, _ptr(face_keep), _ptr(face_rank), _ptr(vertex_used),
+                                              _ptr(vertex_rank), _ptr(out_vertices), _ptr(out_colours), n_vertices, _ptr(out_faces), n_faces,
+                                              _stream()))
+    return out_vertices, out_colours, out_faces
 
 
 def _label(faces, m):
@@ -66,7 +103,7 @@ def component_sizes(faces, labels):
     face; 0 everywhere else."""
     faces = _faces(faces, "component_sizes")
     if not torch.is_tensor(labels) or not labels.is_cuda:
-        raise _no_cpu("component_sizes")
+        raise no_cpu("component_sizes", WHY)
     if labels.ndim != 1 or labels.dtype != torch.int32:
         raise ValueError(f"component_sizes: expected int32 labels [m], got {labels.dtype} {tuple(labels.shape)}")
     labels = labels.contiguous()
@@ -87,25 +124,16 @@ def filter_components(vertices, colours, faces, min_faces=0, min_ratio=0.0, keep
     and the vertices no kept face uses are dropped in any case; what stays keeps its order. colours may be None. One host
     synchronisation. info: components, components_kept, faces_dropped, vertices_dropped, largest_component_faces, invalid_faces,
     degenerate_faces, size_histogram (the components found with 1-9, 10-99, 100-999, 1000-9999 and 10000 or more faces)."""
-    faces = _faces(faces, "filter_components")
-    if not torch.is_tensor(vertices) or not vertices.is_cuda or (colours is not None and (not torch.is_tensor(colours) or not colours.is_cuda)):
-        raise _no_cpu("filter_components")
-    if vertices.ndim != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
-        raise ValueError(f"filter_components: expected float32 vertices [m,3], got {vertices.dtype} {tuple(vertices.shape)}")
-    if colours is not None and (colours.shape != vertices.shape or colours.dtype != torch.uint8):
-        raise ValueError(f"filter_components: expected uint8 colours {tuple(vertices.shape)}, got {colours.dtype} {tuple(colours.shape)}")
+    _faces(faces, "filter_components")                                # the faces' shape is refused before anyone asks where the vertices live
+    vertices, colours, faces = check_mesh(vertices, colours, faces, "filter_components", WHY)
     min_faces, min_ratio = int(min_faces), float(min_ratio)
     if min_faces < 0 or not math.isfinite(min_ratio) or min_ratio < 0.0 or (keep_largest is not None and int(keep_largest) < 0):
         raise ValueError("min_faces, min_ratio and keep_largest must not be negative, min_ratio finite")
     dev, m, k = faces.device, vertices.shape[0], faces.shape[0]
-    vertices = vertices.contiguous()
-    colours = None if colours is None else colours.contiguous()
     if k == 0 or m == 0:
         info = dict(components=0, components_kept=0, faces_dropped=k, vertices_dropped=m, largest_component_faces=0,
                     invalid_faces=k if m == 0 else 0, degenerate_faces=0, size_histogram=[0] * (len(HISTOGRAM_EDGES) + 1))
-        return (torch.empty((0, 3), dtype=torch.float32, device=dev), None if colours is None else torch.empty((0, 3), dtype=torch.uint8, device=dev),
-                torch.empty((0, 3), dtype=torch.int32, device=dev), info)
-    lib = N.lib()
+        return (*empty_mesh(dev, colours is not None), info)
     labels, status = _label(faces, m)
     faces_of, vertices_of = component_sizes(faces, labels)
     exists = faces_of > 0
@@ -120,23 +148,16 @@ def filter_components(vertices, colours, faces, min_faces=0, min_ratio=0.0, keep
     face_keep = torch.empty(k, dtype=torch.uint8, device=dev)
     vertex_used = torch.empty(m, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        N.check(lib.acez_mesh_select(_ptr(faces), k, _ptr(labels), m, _ptr(keep), _ptr(face_keep), _ptr(vertex_used), _stream()))
-    face_rank = torch.cumsum(face_keep, 0, dtype=torch.int32)
-    vertex_rank = torch.cumsum(vertex_used, 0, dtype=torch.int32)
+        N.check(N.lib().acez_mesh_select(_ptr(faces), k, _ptr(labels), m, _ptr(keep), _ptr(face_keep), _ptr(vertex_used), _stream()))
+    face_rank, vertex_rank, d_n_f, d_n_v = compact_ranks(face_keep, vertex_used)
     invalid = ((faces < 0) | (faces >= m)).any(1)
     degenerate = ~invalid & ((faces[:, 0] == faces[:, 1]) | (faces[:, 1] == faces[:, 2]) | (faces[:, 0] == faces[:, 2]))
     n_f, n_v, bad, found, kept, most, n_invalid, n_degenerate, *at_least = torch.stack(
-        [face_rank[-1].long(), vertex_rank[-1].long(), status[0].long(), exists.sum(), keep.sum(), largest.long(), invalid.sum(),
+        [d_n_f, d_n_v, status[0].long(), exists.sum(), keep.sum(), largest.long(), invalid.sum(),
          degenerate.sum()] + [(faces_of >= t).sum() for t in HISTOGRAM_EDGES]).cpu().tolist()       # the one synchronisation
     _check_status(bad)
-    out_vertices = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
-    out_colours = None if colours is None else torch.empty((n_v, 3), dtype=torch.uint8, device=dev)
-    out_faces = torch.empty((n_f, 3), dtype=torch.int32, device=dev)
-    if n_v:                                                                          # else no face is kept: nothing to move
-        with torch.cuda.device(dev):
-            N.check(lib.acez_mesh_compact(_ptr(vertices), _ptr(colours), m, _ptr(faces), k, _ptr(face_keep), _ptr(face_rank), _ptr(vertex_used),
-                                          _ptr(vertex_rank), _ptr(out_vertices), _ptr(out_colours), n_v, _ptr(out_faces), n_f, _stream()))
+    out = compact(vertices, colours, faces, face_keep, face_rank, vertex_used, vertex_rank, n_f, n_v)
     info = dict(components=found, components_kept=kept, faces_dropped=k - n_f, vertices_dropped=m - n_v, largest_component_faces=most,
                 invalid_faces=n_invalid, degenerate_faces=n_degenerate,
                 size_histogram=[found - at_least[0]] + [a - b for a, b in zip(at_least, at_least[1:] + [0])])
-    return out_vertices, out_colours, out_faces, info
+    return (*out, info)

@@ -17,7 +17,7 @@ import torch
 
 from . import _native as N
 from .frames import device_rows, frame_rows, pack
-from .head import _ptr, _stream
+from ._device import ptr as _ptr, stream as _stream
 
 MAX_AXIS_ANGLE_DEG = 30.0           # select_sources: a source looks within this angle of the frame's own optical axis
 BASELINE_RATIO = (0.02, 0.5)        # ... and stands this far away, in units of the scene depth

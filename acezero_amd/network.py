@@ -16,7 +16,8 @@ import torch
 from . import _native as N
 from . import dsacstar
 from .encoder import Encoder, output_size
-from .head import HeadTrainer, _ptr, _stream, layer_names
+from ._device import ptr as _ptr, stream as _stream
+from .head import HeadTrainer, layer_names
 
 
 class Regressor:

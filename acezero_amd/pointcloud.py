@@ -15,7 +15,7 @@ import torch
 
 from . import _native as N
 from .formats import write_ply
-from .head import _ptr, _stream
+from ._device import no_cpu, ptr as _ptr, stream as _stream
 
 PC_POINTS_MIN, PC_POINTS_MAX = 100000, 1000000   # ace_vis_util.py:447-448
 
@@ -31,7 +31,7 @@ def filter_scene_coordinates(scene_coords, poses_inv, intrinsics, filter_depth, 
 
     scene_coords [B,3,h,w] f32, poses_inv [B,4,4] or [B,3,4] world->camera, intrinsics [B,3,3]."""
     if not scene_coords.is_cuda:
-        raise RuntimeError("filter_scene_coordinates needs device tensors: the point-cloud filter is a HIP kernel, there is no CPU path")
+        raise no_cpu("filter_scene_coordinates", "the point-cloud filter is a HIP kernel")
     dev = scene_coords.device
     b, _, h, w = scene_coords.shape
     sc = scene_coords.to(torch.float32).contiguous()

@@ -34,7 +34,8 @@ from .encoder import Encoder, output_size
 import torch.distributed as dist
 
 from .formats import write_pose_line
-from .head import HeadGroup, HeadTrainer, _ptr, _stream, epoch_batches, epoch_permutations
+from ._device import ptr as _ptr, stream as _stream
+from .head import HeadGroup, HeadTrainer, epoch_batches, epoch_permutations
 from .parallel import epoch_local_batches, gather_registrations, make_data_parallel, rank_world
 from .pointcloud import filter_scene_coordinates, point_colours
 

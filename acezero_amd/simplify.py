@@ -15,7 +15,8 @@ import math
 import torch
 
 from . import _native as N
-from .head import _ptr, _stream
+from ._device import ptr as _ptr, stream as _stream
+from .mesh import check_mesh, compact, compact_ranks, empty_mesh
 
 __all__ = ["simplify_mesh"]
 
@@ -41,31 +42,20 @@ def simplify_mesh(vertices, colours, faces, cell, placement="quadric"):
     vertices_in, faces_in, vertices_out, faces_out, invalid_faces, degenerate_faces, nonfinite_vertices, collapsed_faces,
     duplicate_faces, unused_clusters, fallbacks (output vertices placed at the mean for want of a usable quadric)."""
     what = "simplify_mesh"
-    tensors = [vertices, faces] + ([] if colours is None else [colours])
-    if not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
-        raise RuntimeError(f"{what} needs device tensors: the simplification is HIP kernels, there is no CPU path")
-    if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
-        raise ValueError(f"{what}: expected int32 faces [k,3], got {faces.dtype} {tuple(faces.shape)}")
-    if vertices.ndim != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
-        raise ValueError(f"{what}: expected float32 vertices [m,3], got {vertices.dtype} {tuple(vertices.shape)}")
-    if colours is not None and (colours.shape != vertices.shape or colours.dtype != torch.uint8):
-        raise ValueError(f"{what}: expected uint8 colours {tuple(vertices.shape)}, got {colours.dtype} {tuple(colours.shape)}")
+    vertices, colours, faces = check_mesh(vertices, colours, faces, what, "the simplification is HIP kernels")
     cell = float(cell)
     if not (math.isfinite(cell) and cell > 0.0):
         raise ValueError(f"{what}: cell must be positive and finite")
     if placement not in PLACEMENTS:
         raise ValueError(f"{what}: placement must be one of {PLACEMENTS}")
     dev, m, k = vertices.device, vertices.shape[0], faces.shape[0]
-    vertices, faces = vertices.contiguous(), faces.contiguous()
-    colours = None if colours is None else colours.contiguous()
     quadric = placement == "quadric"
 
     def empty(n_clusters, counts):
         info = dict(clusters=n_clusters, vertices_in=m, faces_in=k, vertices_out=0, faces_out=0, invalid_faces=0, degenerate_faces=0,
                     nonfinite_vertices=0, collapsed_faces=0, duplicate_faces=0, unused_clusters=n_clusters, fallbacks=0)
         info.update(counts)
-        return (torch.empty((0, 3), dtype=torch.float32, device=dev), None if colours is None else torch.empty((0, 3), dtype=torch.uint8, device=dev),
-                torch.empty((0, 3), dtype=torch.int32, device=dev), info)
+        return (*empty_mesh(dev, colours is not None), info)
 
     if m == 0:
         return empty(0, dict(invalid_faces=k))
@@ -110,23 +100,15 @@ def simplify_mesh(vertices, colours, faces, cell, placement="quadric"):
         face_keep = torch.empty(k, dtype=torch.uint8, device=dev)
         cluster_used = torch.empty(m, dtype=torch.uint8, device=dev)
         N.check(lib.acez_simplify_unique(_ptr(triples), _ptr(face_class), _ptr(perm), k, m, _ptr(face_keep), _ptr(cluster_used), _stream()))
-    face_rank = torch.cumsum(face_keep, 0, dtype=torch.int32)
-    cluster_rank = torch.cumsum(cluster_used, 0, dtype=torch.int32)
-    zero = torch.zeros((), dtype=torch.int64, device=dev)
+    face_rank, cluster_rank, d_n_f, d_n_v = compact_ranks(face_keep, cluster_used)
     n_f, n_v, n_clusters, n_cells, n_invalid, n_degenerate, n_collapsed, n_candidates, n_fallbacks = torch.stack(
-        [face_rank[-1].long() if k else zero, cluster_rank[-1].long(), first.sum(), has_cell.sum()]
+        [d_n_f, d_n_v, first.sum(), has_cell.sum()]
         + [(face_class == c).sum() for c in (INVALID, DEGENERATE, COLLAPSED, CANDIDATE)] + [(fallback & cluster_used).sum()]).cpu().tolist()   # synchronises
     counts = dict(invalid_faces=n_invalid, degenerate_faces=n_degenerate, nonfinite_vertices=m - n_cells, collapsed_faces=n_collapsed,
                   duplicate_faces=n_candidates - n_f)
     if n_f == 0:
         return empty(n_clusters, counts)
-    out_vertices = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
-    out_colours = None if colours is None else torch.empty((n_v, 3), dtype=torch.uint8, device=dev)
-    out_faces = torch.empty((n_f, 3), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        N.check(lib.acez_mesh_compact(_ptr(positions), _ptr(cluster_colours), m, _ptr(triples), k, _ptr(face_keep), _ptr(face_rank),
-                                      _ptr(cluster_used), _ptr(cluster_rank), _ptr(out_vertices), _ptr(out_colours), n_v, _ptr(out_faces), n_f,
-                                      _stream()))
+    out = compact(positions, cluster_colours, triples, face_keep, face_rank, cluster_used, cluster_rank, n_f, n_v)
     info = dict(clusters=n_clusters, vertices_in=m, faces_in=k, vertices_out=n_v, faces_out=n_f, unused_clusters=n_clusters - n_v,
                 fallbacks=n_fallbacks, **counts)
-    return out_vertices, out_colours, out_faces, info
+    return (*out, info)

@@ -299,3 +299,38 @@ def big_problem(n_images=24, patches_per_view=512):
     prob = synth.make_training_problem(seed=SEED + 7, n_images=n_images, views_per_image=2, patches_per_view=patches_per_view)
     prob["features"] = torch.from_numpy(prob["features"]).to(torch.bfloat16).to(torch.float32).numpy()
     return prob
+
+
+# ---- the mesh tools' GPU tests (tests/test_mesh_gpu.py, tests/test_simplify_gpu.py, tests/test_mesh_args_gpu.py) ----
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def device(a):
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def host(t):
+    return None if t is None else t.cpu().numpy()
+
+
+def run(script, args):
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, script)] + [str(a) for a in args], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return r.stderr
+
+
+def call(main, args, caplog):
+    """A command's main() in this process (the import and the device start-up are paid once): its log."""
+    import logging
+    caplog.clear()
+    with caplog.at_level(logging.INFO):
+        assert main([str(a) for a in args]) == 0
+    return caplog.text
+
+
+def assert_file_is(path, want):
+    from tests import fusion_cases as FC
+    v, c, f = FC.read_mesh_ply(path)
+    assert np.array_equal(v.view(np.uint32), want[0].view(np.uint32)) and np.array_equal(c, want[1]) and np.array_equal(f, want[2])

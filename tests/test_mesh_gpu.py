@@ -1,10 +1,6 @@
 """GPU: the mesh clean-up kernels (acezero_amd/csrc/mesh_api.hip) against the host restatement of include/acez.h section P
 (tests/mesh_restated.py), integer for integer: the labels, the counts, the filtered mesh; then clean_mesh.py and fuse_depth.py's
 three flags end to end. The restated labels are computed once (tests/test_mesh_cpu.py: restated) and shared."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
@@ -15,15 +11,10 @@ from acezero_amd.head import _ptr
 from tests import fusion_cases as FC
 from tests import mesh_cases as MC
 from tests import mesh_restated as MR
+from tests.helpers import assert_file_is, device, run
 from tests.test_mesh_cpu import check_refusals, entry_point_calls, restated
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def device(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @pytest.mark.parametrize("name", sorted(MC.label_cases()))
@@ -92,17 +83,6 @@ def test_argument_validation_with_device_buffers():
     assert lib.acez_mesh_compact(None, None, 0, None, 0, None, None, None, None, None, None, 0, None, 0, None) == 0
     torch.cuda.synchronize()
     assert int(status.item()) == 0
-
-
-def run(script, args):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, script)] + [str(a) for a in args], cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stderr
-
-
-def assert_file_is(path, want):
-    v, c, f = FC.read_mesh_ply(path)
-    assert np.array_equal(v.view(np.uint32), want[0].view(np.uint32)) and np.array_equal(c, want[1]) and np.array_equal(f, want[2])
 
 
 def test_clean_mesh_end_to_end(tmp_path):

@@ -1,11 +1,6 @@
 """GPU: the mesh simplification kernels (acezero_amd/csrc/simplify_api.hip) against the host restatement of include/acez.h section Q
 (tests/simplify_restated.py), bit for bit in vertices and colours, integer for integer in faces and info; then simplify_mesh.py and
 fuse_depth.py --simplify_cell end to end. The restated results are computed once (tests/test_simplify_cpu.py: restated) and shared."""
-import logging
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
@@ -17,19 +12,10 @@ from tests import mesh_cases as MC
 from tests import mesh_restated as MR
 from tests import simplify_cases as SC
 from tests import simplify_restated as SR
+from tests.helpers import assert_file_is, call, device, host, run
 from tests.test_simplify_cpu import check_refusals, entry_point_calls, restated
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def device(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return None if t is None else t.cpu().numpy()
 
 
 def assert_same(got, want):
@@ -88,25 +74,6 @@ def test_argument_validation_with_device_buffers():
         simplify.simplify_mesh(torch.zeros((3, 3), device="cuda"), None, torch.zeros((1, 3), dtype=torch.int32, device="cuda"), 0.1, "median")
     with pytest.raises(N.AcezError, match="ACEZ_ERR_INVALID.*2\\^21"):                             # 1 m at a cell of 0.1 um
         simplify.simplify_mesh(torch.eye(3, device="cuda"), None, torch.zeros((1, 3), dtype=torch.int32, device="cuda"), 1e-7)
-
-
-def run(script, args):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, script)] + [str(a) for a in args], cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stderr
-
-
-def call(main, args, caplog):
-    """A command's main() in this process (the import and the device start-up are paid once): its log."""
-    caplog.clear()
-    with caplog.at_level(logging.INFO):
-        assert main([str(a) for a in args]) == 0
-    return caplog.text
-
-
-def assert_file_is(path, want):
-    v, c, f = FC.read_mesh_ply(path)
-    assert np.array_equal(v.view(np.uint32), want[0].view(np.uint32)) and np.array_equal(c, want[1]) and np.array_equal(f, want[2])
 
 
 def test_simplify_mesh_end_to_end(tmp_path, caplog):

@@ -5,7 +5,8 @@ the device before the timed calls.
     python tools/simplify_timing.py [--frames 48] [--dim 256] [--sparse_voxel 0.0075] [--reps 10] [--no_sparse]
 
 Meshes: the room of tools/fusion_timing.py fused into the dense dim^3 volume at 0.02 m, and the same room fused into the block-sparse
-volume at --sparse_voxel. Stages: the kernels of acezero_amd/csrc/simplify_api.hip one by one and torch's sorts and searches between
+volume at --sparse_voxel. `filter_*_ms`: mesh.filter_components on the same mesh, without a criterion and with keep_largest=1, whole
+calls like `whole_*_ms`. Stages: the kernels of acezero_amd/csrc/simplify_api.hip one by one and torch's sorts and searches between
 them. `layouts`: the per-cluster quadric sums alone in the two layouts of include/acez.h section Q step 5 (tools/simplify_layouts.hip,
 built here into tools/libacez_simplify_layouts.so): one lane per cluster, and one wavefront per cluster, which is what the product
 does, alternating, with the largest relative difference between their sums. open3d's simplify_vertex_clustering on the host is timed on the same
@@ -24,7 +25,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from acezero_amd import _native as N  # noqa: E402
-from acezero_amd import fusion, simplify  # noqa: E402
+from acezero_amd import fusion, mesh, simplify  # noqa: E402
 from acezero_amd.head import _ptr, _stream  # noqa: E402
 from tests import fusion_cases as FC  # noqa: E402
 from tools.rgbd_timing import _time  # noqa: E402
@@ -50,6 +51,8 @@ def stages(vertices, colours, faces, cell, reps):
     out = {"vertices": m, "faces": k, "cell": cell}
     for placement in simplify.PLACEMENTS:
         out[f"whole_{placement}_ms"] = _time(lambda: simplify.simplify_mesh(vertices, colours, faces, cell, placement), reps)
+    for name, criteria in (("plain", {}), ("keep_largest", dict(keep_largest=1))):      # the clean-up that shares the compaction (mesh.py)
+        out[f"filter_{name}_ms"] = _time(lambda: mesh.filter_components(vertices, colours, faces, **criteria), reps)
     got = simplify.simplify_mesh(vertices, colours, faces, cell)
     out["info"] = got[3]
     finite = torch.isfinite(vertices).all(1, keepdim=True)
@@ -131,12 +134,12 @@ def stages(vertices, colours, faces, cell, reps):
     except ImportError:
         out["open3d"] = "not importable on this machine: no same-machine comparison"
     else:
-        mesh = o3d.geometry.TriangleMesh(o3d.utility.Vector3dVector(vertices.cpu().numpy().astype(np.float64)),
-                                         o3d.utility.Vector3iVector(faces.cpu().numpy()))
+        o3d_mesh = o3d.geometry.TriangleMesh(o3d.utility.Vector3dVector(vertices.cpu().numpy().astype(np.float64)),
+                                             o3d.utility.Vector3iVector(faces.cpu().numpy()))
         best = []
         for _ in range(3):
             t0 = time.perf_counter()
-            small = mesh.simplify_vertex_clustering(cell, o3d.geometry.SimplificationContraction.Quadric)
+            small = o3d_mesh.simplify_vertex_clustering(cell, o3d.geometry.SimplificationContraction.Quadric)
             best.append((time.perf_counter() - t0) * 1e3)
         out["open3d"] = {"host_ms": min(best), "vertices": len(small.vertices), "faces": len(small.triangles)}
     return out
