@@ -8,7 +8,6 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
-#include "acez_common.h"
 #include <vector>
 #include <new>
 
@@ -110,7 +109,7 @@ struct acez_trainer {
   // the one-launch chains are used at all; every poll is bounded and raises `seq_err` (device), which turns the optimiser /
   // schedule kernels of that step into no-ops; the next state read (seq_fault_check) resets the counters and switches this
   // trainer to per-layer launches for good. The abandoned iterations are not counted, so the training loop simply runs them again.
-  int* seq_err = nullptr;              // = (int*)(seq_flags + 64 * 32): one allocation, so that the kernel needs no second pointer
+  int* seq_err = nullptr;              // = (int*)(seq_flags + SEQ_FAULT_WORD): one allocation, so that the kernel needs no second pointer
   uint32_t seq_spin_limit = 40000;     // polls (>= ~0.5 us each: at least ~20 ms); ACEZ_SEQ_SPIN_US overrides (2 polls per us)
   int seq_faults = 0;                  // fall-backs taken so far
   int seq_probe = -1;                  // -1 not run, 0 failed (seq disabled), 1 passed
@@ -239,7 +238,7 @@ static int seq_placement_probe(acez_trainer* tr) {
   for (int rep = 0; rep < 2 && ok; ++rep) {   // the full grid, and a ragged one (41 row tiles: 6 per XCD, the last XCDs short)
     const int mtiles = rep == 0 ? 64 : 41;
     (void)hipMemset(d_rec, 0xff, 256 * sizeof(uint32_t));
-    hipLaunchKernelGGL(seq_probe_kernel, dim3(32 * ((mtiles + 7) / 8)), dim3(512), 0, 0, d_rec, mtiles);
+    hipLaunchKernelGGL(seq_probe_kernel, chain_grid(mtiles), dim3(512), 0, 0, d_rec, mtiles);
     if (hipGetLastError() != hipSuccess || hipMemcpy(h, d_rec, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) { ok = false; break; }
     for (int mt = 0; mt < mtiles && ok; ++mt)
       for (int nt = 0; nt < 4; ++nt) {
@@ -270,13 +269,13 @@ static void wgo_recover(acez_trainer* tr, hipStream_t s) {
   fill_wgrad_args(tr, a, rec.M, nullptr);   // (st = null: the fault handler has cleared `active`)
   a.In[0] = rec.in0;
   const int groups = tr->L * tr->nslabs;
-  if (tr->f16) hipLaunchKernelGGL(wgrad_kernel<EltF16>, dim3(128 * ((groups + 7) / 8)), dim3(WGRAD_THREADS), 0, s, a);
-  else hipLaunchKernelGGL(wgrad_kernel<EltBf16>, dim3(128 * ((groups + 7) / 8)), dim3(WGRAD_THREADS), 0, s, a);
+  with_elt(tr->f16, [&](auto e) { hipLaunchKernelGGL(wgrad_kernel<decltype(e)>, dim3(128 * ((groups + 7) / 8)), dim3(WGRAD_THREADS), 0, s, a); });
   AdamArgs ad;
   fill_adam_args(tr, ad);
   const dim3 grid(256 * ((tr->L + 7) / 8));
-  if (tr->f16) hipLaunchKernelGGL(wgo_recover_kernel<EltF16>, grid, dim3(512), 0, s, ad, (const float*)tr->slabs, tr->n_wide, (const uint32_t*)tr->wg_status, (const WgoFaultRec*)tr->wg_rec, tr->L);
-  else hipLaunchKernelGGL(wgo_recover_kernel<EltBf16>, grid, dim3(512), 0, s, ad, (const float*)tr->slabs, tr->n_wide, (const uint32_t*)tr->wg_status, (const WgoFaultRec*)tr->wg_rec, tr->L);
+  with_elt(tr->f16, [&](auto e) {
+    hipLaunchKernelGGL(wgo_recover_kernel<decltype(e)>, grid, dim3(512), 0, s, ad, (const float*)tr->slabs, tr->n_wide, (const uint32_t*)tr->wg_status, (const WgoFaultRec*)tr->wg_rec, tr->L);
+  });
   (void)hipMemsetAsync(tr->wg_rec, 0, sizeof(WgoFaultRec), s);
   ++tr->wgo_recovered;
 }
@@ -289,7 +288,7 @@ static int seq_fault_check(acez_trainer* tr, hipStream_t s) {
   if (!err) return 0;
   wgo_recover(tr, s);   // (before the fault word comes down: nothing else may run on this trainer's buffers in between)
   tr->carry.drop_batch();   // batches "gathered ahead" since the fault were held back
-  (void)hipMemsetAsync(tr->seq_flags, 0, (64 * 32 + 1) * sizeof(uint32_t), s);   // counters + fault word (the poll budget behind them stays)
+  (void)hipMemsetAsync(tr->seq_flags, 0, (SEQ_FAULT_WORD + 1) * sizeof(uint32_t), s);   // counters + fault word (the poll budget behind them stays)
   hipLaunchKernelGGL(sched_reactivate_kernel, dim3(1), dim3(64), 0, s, tr->st);
   const int one = 1;
   (void)hipMemcpyAsync(&tr->st_infer->active, &one, sizeof(int), hipMemcpyHostToDevice, s);
@@ -382,7 +381,7 @@ extern "C" int acez_trainer_create(acez_trainer** out, const acez_train_config* 
   if (trains) {
     A((void**)&tr->dR[0], act_bytes);
     A((void**)&tr->dR[1], act_bytes);
-    tr->mask_stride = (size_t)((tr->max_batch + 79) / 80) * 4 * 4 * 64;
+    tr->mask_stride = (size_t)row_tiles(tr->max_batch) * 4 * 4 * 64;
     A((void**)&tr->maskbits, (size_t)tr->L * tr->mask_stride * sizeof(uint2));
     A((void**)&tr->slabs, (size_t)tr->nslabs * tr->n_wide * sizeof(float));
     A((void**)&tr->fc3_partials, (size_t)max_loss_blocks * tr->fc3_stride * sizeof(float));
@@ -391,7 +390,7 @@ extern "C" int acez_trainer_create(acez_trainer** out, const acez_train_config* 
     A((void**)&tr->xyz, (size_t)tr->max_batch * 3 * sizeof(float));
     A((void**)&tr->batch_meta, (size_t)tr->max_batch * sizeof(int4));
   }
-  A((void**)&tr->seq_flags, (64 * 32 + 32) * sizeof(uint32_t));
+  A((void**)&tr->seq_flags, (SEQ_FAULT_WORD + 32) * sizeof(uint32_t));
   if (ACEZ_DIAG_ENV("ACEZ_SEQ_XCC")) A((void**)&tr->seq_xcc, (8 + 256) * sizeof(uint32_t));
   if (ACEZ_DIAG_ENV("ACEZ_POSE_TRACE")) A((void**)&tr->pose_trace, 3 * 1024 * 16 * sizeof(unsigned long long));
   if (ACEZ_DIAG_ENV("ACEZ_WGO_TRACE")) A((void**)&tr->wgo_trace, 256 * 12 * 8 * sizeof(unsigned long long));
@@ -413,10 +412,10 @@ extern "C" int acez_trainer_create(acez_trainer** out, const acez_train_config* 
   A((void**)&tr->st_infer, sizeof(TrainState));
   }   // (allocation passes)
   if (rc != ACEZ_OK) { acez_trainer_destroy(tr); return rc; }
-  ACEZ_HIP_CHECK(hipMemset(tr->seq_flags, 0, (64 * 32 + 32) * sizeof(uint32_t)));
-  tr->seq_err = reinterpret_cast<int*>(tr->seq_flags + 64 * 32);
+  ACEZ_HIP_CHECK(hipMemset(tr->seq_flags, 0, (SEQ_FAULT_WORD + 32) * sizeof(uint32_t)));
+  tr->seq_err = reinterpret_cast<int*>(tr->seq_flags + SEQ_FAULT_WORD);
   if (const char* e = getenv("ACEZ_SEQ_SPIN_US")) tr->seq_spin_limit = (uint32_t)std::max(1L, atol(e)) * 2u;
-  ACEZ_HIP_CHECK(hipMemcpy(tr->seq_flags + 64 * 32 + 1, &tr->seq_spin_limit, sizeof(uint32_t), hipMemcpyHostToDevice));
+  ACEZ_HIP_CHECK(hipMemcpy(tr->seq_flags + SEQ_FAULT_WORD + 1, &tr->seq_spin_limit, sizeof(uint32_t), hipMemcpyHostToDevice));
   if (const char* e = ACEZ_DIAG_ENV("ACEZ_SEQ_FAULT_AT")) tr->seq_fault_at = atol(e);
   if (tr->seq_xcc) ACEZ_HIP_CHECK(hipMemset(tr->seq_xcc, 0, (8 + 256) * sizeof(uint32_t)));
   if (const char* e = ACEZ_DIAG_ENV("ACEZ_WGRAD_OPT")) tr->wgrad_opt = atoi(e) != 0;
@@ -534,8 +533,8 @@ extern "C" int acez_trainer_sync_weights(acez_trainer* tr, void* stream) {
 // forward chain on n rows whose input features are in `in0`; returns the fc2 output buffer
 // rowseq_kernel is usable when its workgroups wait for each other safely: all of them resident at once
 static bool seq_usable(const acez_trainer* tr, int n) {
-  const int mtiles = (n + 79) / 80;
-  return tr->seq && mtiles <= 64 && 32 * ((mtiles + 7) / 8) <= tr->n_cus;
+  const int mtiles = row_tiles(n);
+  return tr->seq && mtiles <= 64 && (int)chain_grid(mtiles).x <= tr->n_cus;
 }
 
 // wgrad_opt_kernel's workgroups wait for each other too: same conditions, its own grid (both slabs of a layer on one XCD: 32 workgroups
@@ -548,32 +547,38 @@ static bool wgrad_opt_usable(const acez_trainer* tr) {
          tr->cfg.pose_refinement == 0 && 256 * ((tr->L + 7) / 8) <= tr->n_cus;
 }
 
+// The host's side of the hand-off protocol (head_kernels.hip) for one launch on a trainer's counters, in front of the launch: `base`
+// (the launch's argument) = the seams completed so far per row tile; the trainer's own bases move on by the `seams` the launch adds to
+// the row tiles of ITS n-row batch (seq_seams: the device adds as much when the launch returns at entry). `stands_for`: the launches of
+// the per-chain flow this one counts as in seq_launches; `layers`: the layer GEMMs it is accounted as in a profiling scope, so that the
+// per-layer average stays comparable.
+// tests (ACEZ_SEQ_FAULT_AT): the launch that the n-th launch falls in is told that a million seams have completed before it -- every
+// hand-off then waits for a count that never comes, which is what a sibling on a foreign XCD looks like (a launch without a seam: not)
+static void seq_account(acez_trainer* tr, uint32_t (&base)[64], int n, uint32_t seams, int layers, int stands_for = 1) {
+  const bool fault = seams > 0 && tr->seq_fault_at >= tr->seq_launches && tr->seq_fault_at < tr->seq_launches + stands_for;
+  for (int mt = 0; mt < 64; ++mt) base[mt] = tr->seq_base[mt] + (fault ? 1u << 20 : 0u);
+  tr->seq_launches += stands_for;
+  for (int mt = 0; mt < row_tiles(n); ++mt) tr->seq_base[mt] += seams;
+  tr->prof_launches += layers;
+}
+
 // head != null (input gradients only): the chain's first launch is rowseq_loss_kernel -- the loss of the batch as its stage -1, one
 // hand-off more than its layers have between them
 template <bool BWD>
 static void launch_rowseq(acez_trainer* tr, const std::vector<SeqLayer>& layers, int n, const TrainState* st, hipStream_t s,
                           const SeqLossArgs* head = nullptr) {
-  const int mtiles = (n + 79) / 80;
+  const dim3 grid = chain_grid(row_tiles(n));
   for (size_t i0 = 0; i0 < layers.size(); i0 += SEQ_MAX_LAYERS) {
     const bool with_loss = BWD && head && i0 == 0;
     RowSeqArgs a{};
     const int cnt = (int)std::min<size_t>(SEQ_MAX_LAYERS, layers.size() - i0);
     for (int i = 0; i < cnt; ++i) a.layer[i] = layers[i0 + i];
     a.n_layers = cnt; a.M = n; a.st = st ? st : tr->st_infer; a.flags = tr->seq_flags; a.xcc_dbg = tr->seq_xcc; a.spin_limit = tr->seq_spin_limit;
-    for (int mt = 0; mt < 64; ++mt) a.base[mt] = tr->seq_base[mt];
-    // tests (ACEZ_SEQ_FAULT_AT): this launch is told that a million seams have completed before it -- every hand-off then waits
-    // for a count that never comes, which is what a sibling on a foreign XCD looks like
-    if ((cnt > 1 || with_loss) && tr->seq_launches == tr->seq_fault_at)
-      for (int mt = 0; mt < 64; ++mt) a.base[mt] += 1u << 20;
-    ++tr->seq_launches;
-    if (with_loss) {
-      if (tr->f16) hipLaunchKernelGGL(rowseq_loss_kernel<EltF16>, dim3(32 * ((mtiles + 7) / 8)), dim3(512), 0, s, a, *head);
-      else hipLaunchKernelGGL(rowseq_loss_kernel<EltBf16>, dim3(32 * ((mtiles + 7) / 8)), dim3(512), 0, s, a, *head);
-    }
-    else if (tr->f16) hipLaunchKernelGGL((rowseq_kernel<BWD, EltF16>), dim3(32 * ((mtiles + 7) / 8)), dim3(512), 0, s, a);
-    else hipLaunchKernelGGL(rowseq_kernel<BWD>, dim3(32 * ((mtiles + 7) / 8)), dim3(512), 0, s, a);
-    for (int mt = 0; mt < mtiles; ++mt) tr->seq_base[mt] += (uint32_t)(cnt - 1 + (with_loss ? 1 : 0));
-    tr->prof_launches += cnt;   // accounted as layer GEMMs so that the per-layer average stays comparable
+    seq_account(tr, a.base, n, seq_seams(cnt, with_loss ? 1 : 0), cnt);
+    with_elt(tr->f16, [&](auto e) {
+      if (with_loss) hipLaunchKernelGGL(rowseq_loss_kernel<decltype(e)>, grid, dim3(512), 0, s, a, *head);
+      else hipLaunchKernelGGL((rowseq_kernel<BWD, decltype(e)>), grid, dim3(512), 0, s, a);
+    });
   }
 }
 
@@ -628,8 +633,7 @@ static void fill_loss_head(acez_trainer* tr, LossArgs& a) {
 
 
 static void launch_loss(acez_trainer* tr, int nblk, hipStream_t s, const LossArgs& a) {
-  if (tr->f16) hipLaunchKernelGGL((loss_kernel<EltF16, 4>), dim3(nblk), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((loss_kernel<EltBf16, 4>), dim3(nblk), dim3(256), 0, s, a);
+  with_elt(tr->f16, [&](auto e) { hipLaunchKernelGGL((loss_kernel<decltype(e), 4>), dim3(nblk), dim3(256), 0, s, a); });
 }
 
 // training-mode arguments of the loss kernel
@@ -853,8 +857,9 @@ static void launch_train_loss(const StepRun& r) {
   const int gblocks = std::min((r.n_next + 31) / 32, std::max(32, 2 * tr->n_cus - r.nblk));
   GatherMeta gm = gather_meta(tr);
   gm.dst = tr->batch_meta_alt;
-  if (tr->f16) hipLaunchKernelGGL((loss_gather_kernel<EltF16, 4>), dim3(r.nblk + gblocks), dim3(256), 0, r.s, a, r.nblk, (const uint16_t*)tr->buf.d_features, r.next, tr->R0_alt, r.n_next, gm);
-  else hipLaunchKernelGGL((loss_gather_kernel<EltBf16, 4>), dim3(r.nblk + gblocks), dim3(256), 0, r.s, a, r.nblk, (const uint16_t*)tr->buf.d_features, r.next, tr->R0_alt, r.n_next, gm);
+  with_elt(tr->f16, [&](auto e) {
+    hipLaunchKernelGGL((loss_gather_kernel<decltype(e), 4>), dim3(r.nblk + gblocks), dim3(256), 0, r.s, a, r.nblk, (const uint16_t*)tr->buf.d_features, r.next, tr->R0_alt, r.n_next, gm);
+  });
   tr->carry.hold(r.next, r.n_next, true);
 }
 
@@ -922,29 +927,22 @@ static void launch_dgrad(acez_trainer* tr, int n, const TrainState* st, hipStrea
 }
 
 // Both chains of a fused step and its loss as ONE launch (rowstep_kernel): the layer tables of launch_forward and launch_dgrad, the loss
-// arguments of the three-launch flow, launch_rowseq's host bookkeeping for n_fwd + n_bwd hand-offs per row tile
+// arguments of the three-launch flow, seq_account for n_fwd + n_bwd hand-offs per row tile
 static void launch_rowstep(const StepRun& r) {
   acez_trainer* tr = r.tr;
   std::vector<SeqLayer> fwd, bwd;
   launch_forward(tr, tr->R[0], r.n, r.st, r.s, &fwd);
   launch_dgrad(tr, r.n, r.st, r.s, &bwd);
   if (fwd.size() > SEQ_MAX_LAYERS || bwd.size() > SEQ_MAX_LAYERS || bwd.empty()) abort();   // (train_step_impl only asks for it where both tables fit)
-  const int mtiles = (r.n + 79) / 80;
   RowStepArgs a{};
   for (size_t i = 0; i < fwd.size(); ++i) a.fwd[i] = fwd[i];
   for (size_t i = 0; i < bwd.size(); ++i) a.bwd[i] = bwd[i];
   a.n_fwd = (int)fwd.size(); a.n_bwd = (int)bwd.size(); a.M = r.n;
   a.st = r.st ? r.st : tr->st_infer; a.flags = tr->seq_flags; a.xcc_dbg = tr->seq_xcc; a.spin_limit = tr->seq_spin_limit;
-  for (int mt = 0; mt < 64; ++mt) a.base[mt] = tr->seq_base[mt];
-  // tests (ACEZ_SEQ_FAULT_AT): the launch stands for two of the three-launch flow's, the forward chain's and the input-gradient chain's
-  if (tr->seq_fault_at >= tr->seq_launches && tr->seq_fault_at < tr->seq_launches + 2)
-    for (int mt = 0; mt < 64; ++mt) a.base[mt] += 1u << 20;
-  tr->seq_launches += 2;
+  // (the launch stands for two of the three-launch flow's, the forward chain's and the input-gradient chain's)
+  seq_account(tr, a.base, r.n, seq_seams(a.n_fwd + a.n_bwd, 1), a.n_fwd + a.n_bwd, 2);
   a.x = train_loss_in_chain(r);
-  if (tr->f16) hipLaunchKernelGGL(rowstep_kernel<EltF16>, dim3(32 * ((mtiles + 7) / 8)), dim3(512), 0, r.s, a);
-  else hipLaunchKernelGGL(rowstep_kernel<EltBf16>, dim3(32 * ((mtiles + 7) / 8)), dim3(512), 0, r.s, a);
-  for (int mt = 0; mt < mtiles; ++mt) tr->seq_base[mt] += (uint32_t)(a.n_fwd + a.n_bwd);
-  tr->prof_launches += a.n_fwd + a.n_bwd;
+  with_elt(tr->f16, [&](auto e) { hipLaunchKernelGGL(rowstep_kernel<decltype(e)>, chain_grid(row_tiles(r.n)), dim3(512), 0, r.s, a); });
   ++tr->step_chain_steps;
 }
 
@@ -962,7 +960,7 @@ static void launch_weight_grads(acez_trainer* tr, const StepPlan& p, int n, int 
     a.skip_wide = fused ? 1 : 0;
     a.fault = tr->seq_err;
     // partial rows per layer: one per loss workgroup for fc2, one per 80-row tile from the input-gradient GEMMs
-    for (int l = 0; l < tr->L; ++l) a.bias_count[l] = (l == f2) ? nblk : (n + 79) / 80;
+    for (int l = 0; l < tr->L; ++l) a.bias_count[l] = (l == f2) ? nblk : row_tiles(n);
     tr->last_reduce = a;   // the fused update reduces the partials itself
   }
   // weight gradients of all wide layers in one launch
@@ -991,12 +989,10 @@ static void launch_weight_grads(acez_trainer* tr, const StepPlan& p, int n, int 
       const dim3 grid(256 * ((tr->L + 7) / 8));
       if ((int)grid.x < o.nsmall) abort();
       const PostArgs post = post_args(tr);
-      if (tr->f16) hipLaunchKernelGGL(wgrad_opt_kernel<EltF16>, grid, dim3(WGRAD_THREADS), 0, s, a, o, post);
-      else hipLaunchKernelGGL(wgrad_opt_kernel<EltBf16>, grid, dim3(WGRAD_THREADS), 0, s, a, o, post);
+      with_elt(tr->f16, [&](auto e) { hipLaunchKernelGGL(wgrad_opt_kernel<decltype(e)>, grid, dim3(WGRAD_THREADS), 0, s, a, o, post); });
       wave_ran(tr);
     }
-    else if (tr->f16) hipLaunchKernelGGL(wgrad_kernel<EltF16>, dim3(128 * ((groups + 7) / 8)), dim3(WGRAD_THREADS), 0, s, a);
-    else hipLaunchKernelGGL(wgrad_kernel<EltBf16>, dim3(128 * ((groups + 7) / 8)), dim3(WGRAD_THREADS), 0, s, a);
+    else with_elt(tr->f16, [&](auto e) { hipLaunchKernelGGL(wgrad_kernel<decltype(e)>, dim3(128 * ((groups + 7) / 8)), dim3(WGRAD_THREADS), 0, s, a); });
   }
   if (!fused) {
     const int64_t wide_blocks = (tr->n_wide / 4 + 255) / 256;
@@ -1357,8 +1353,7 @@ static uint16_t* launch_forward_maps(acez_trainer* tr, const uint16_t* in0, int 
   }
   const int ntiles = (n + 127) / 128, cus = tr->n_cus > 0 ? tr->n_cus : 256;
   const dim3 grid(ntiles < cus ? ntiles : cus), blk(512);
-  if (tr->f16) hipLaunchKernelGGL((head_maps_kernel<EltF16>), grid, blk, 0, s, a);
-  else hipLaunchKernelGGL((head_maps_kernel<EltBf16>), grid, blk, 0, s, a);
+  with_elt(tr->f16, [&](auto e) { hipLaunchKernelGGL((head_maps_kernel<decltype(e)>), grid, blk, 0, s, a); });
   return tr->out[f2];
 }
 

@@ -36,22 +36,19 @@ __global__ __launch_bounds__(512) void rowseq_group_kernel(RowSeqGroupArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t smem[RG80_SMEM_SEQ];
   __shared__ uint32_t run_mask;
   // rowseq_kernel's decode over the largest member's row tiles: the four column tiles of row tile mt of EVERY member share one XCD
-  const int per_xcd = (a.mtiles + 7) >> 3;
-  const int jx = blockIdx.x >> 3;
-  const int mt = (blockIdx.x & 7) * per_xcd + (jx >> 2);
-  if (mt >= a.mtiles) return;
-  const int n0 = (jx & 3) * 128;
+  RowTile t;
+  if (!row_tile_decode(a.mtiles, t)) return;
+  const int mt = t.mt, n0 = t.n0();
   if (threadIdx.x == 0) {
     // which members this workgroup runs, decided once for the whole workgroup: row tile mt inside the member's batch, its schedule
     // active and its fault word down (rowseq_kernel's entry test, per member). A member that does not run keeps its counters in step with
-    // the host's bases exactly as rowseq_kernel's early return does; row tiles past a member's batch are not counted (launch_rowseq).
+    // the host's bases exactly as rowseq_kernel's early return does; row tiles past a member's batch are not counted (seq_account).
     uint32_t run = 0;
     for (int h = 0; h < a.H; ++h) {
-      if (mt >= (a.M[h] + 79) / 80) continue;
+      if (mt >= row_tiles(a.M[h])) continue;
       uint32_t* flags = a.heads[h].flags;
-      if ((a.st[h] && !a.st[h]->active) || flags[64 * 32]) {
-        const uint32_t inc = 8u * (uint32_t)(a.n_layers - 1);
-        asm volatile("global_atomic_add %0, %1, off" ::"v"(flags + mt * 32), "v"(inc) : "memory");
+      if (SEQ_DEAD(a.st[h], flags)) {
+        seq_catch_up(seq_seams(a.n_layers), flags, mt);
         continue;
       }
       run |= 1u << h;
@@ -76,7 +73,7 @@ __global__ __launch_bounds__(512) void rowseq_group_kernel(RowSeqGroupArgs a) {
       if (later) next_W = table(__builtin_ctz(later), layer).W;
       else if (layer + 1 < a.n_layers) next_W = table(__builtin_ctz(run), layer + 1).W;
       const TrainState* st = a.st[h];
-      RowGemmArgs g;
+      RowGemmArgs g;   // (rowseq_layers' row -> RowGemmArgs, SeqLink and epilogue shape, written out: see there)
       g.In = y.In; g.W = y.W; g.bias = y.bias; g.add = y.add; g.mask_out = y.mask_out; g.mask_in = y.mask_in; g.res = y.res; g.out_main = y.out_main; g.out_aux = y.out_aux;
       g.bias_partials = y.bias_partials; g.M = a.M[h]; g.N = 512; g.K = 512; g.relu = BWD ? 0 : 1; g.aux_mode = y.aux_mode; g.st = st;
       g.absmax = (BWD && st) ? const_cast<uint32_t*>(st->dz_absmax_slots) : nullptr;
@@ -99,6 +96,7 @@ __global__ __launch_bounds__(512) void rowseq_group_kernel(RowSeqGroupArgs a) {
     }
   }
 }
+#undef SEQ_DEAD
 
 struct acez_train_group {
   std::vector<acez_trainer*> m;
@@ -161,7 +159,7 @@ extern "C" int acez_train_group_create(acez_train_group** out, acez_trainer* con
 }
 
 // one of the two GEMM chains of the members listed in `idx` (all of them seq_usable for their batch) as one launch per SEQ_MAX_LAYERS
-// layers, with launch_rowseq's host bookkeeping per member
+// layers, with seq_account per member
 template <bool BWD>
 static void launch_rowseq_group(acez_train_group* g, const std::vector<int>& idx, const StepRun* runs, hipStream_t s) {
   const int total = BWD ? g->n_bwd : g->n_fwd;
@@ -176,19 +174,10 @@ static void launch_rowseq_group(acez_train_group* g, const std::vector<int>& idx
     for (int i : idx) {
       acez_trainer* tr = g->m[i];
       a.st[i] = runs[i].st; a.M[i] = runs[i].n; a.variant[i] = tr->R[0] == g->in0[i] ? 0 : 1;
-      a.mtiles = std::max(a.mtiles, (runs[i].n + 79) / 80);
-      for (int mt = 0; mt < 64; ++mt) a.base[i][mt] = tr->seq_base[mt];
-      if (cnt > 1 && tr->seq_launches == tr->seq_fault_at)   // tests (ACEZ_SEQ_FAULT_AT): as launch_rowseq
-        for (int mt = 0; mt < 64; ++mt) a.base[i][mt] += 1u << 20;
-      ++tr->seq_launches;
+      a.mtiles = std::max(a.mtiles, row_tiles(runs[i].n));
+      seq_account(tr, a.base[i], runs[i].n, seq_seams(cnt), 0);   // (layers = 0: the group's chain launches open no profiling scope)
     }
-    const dim3 grid(32 * ((a.mtiles + 7) / 8));
-    if (f16) hipLaunchKernelGGL((rowseq_group_kernel<BWD, EltF16>), grid, dim3(512), 0, s, a);
-    else hipLaunchKernelGGL((rowseq_group_kernel<BWD, EltBf16>), grid, dim3(512), 0, s, a);
-    for (int i : idx) {
-      acez_trainer* tr = g->m[i];
-      for (int mt = 0; mt < (runs[i].n + 79) / 80; ++mt) tr->seq_base[mt] += (uint32_t)(cnt - 1);
-    }
+    with_elt(f16, [&](auto e) { hipLaunchKernelGGL((rowseq_group_kernel<BWD, decltype(e)>), chain_grid(a.mtiles), dim3(512), 0, s, a); });
   }
 }
 

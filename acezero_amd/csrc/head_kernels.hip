@@ -121,6 +121,110 @@ __device__ __forceinline__ uint32_t absmax_all(const TrainState* st, int lane) {
   return m;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The same-XCD hand-off protocol, each piece once. Its users: the chain kernels (rowseq_kernel,
+// rowseq_loss_kernel, rowstep_kernel, head_group.hip's rowseq_group_kernel) through rowgemm80_body<..., SEQ> and rowseq_loss_stage, and
+// wgrad_opt_kernel's exchange. The host's side is seq_account (head_api.hip).
+// ---------------------------------------------------------------------------------------------------
+constexpr int SEQ_FAULT_WORD = 64 * 32;   // flags[SEQ_FAULT_WORD]: the trainer's sticky fault word, behind its 64 row-tile counters (one 128-byte line each)
+
+// Row tiles of an n-row batch, the chain kernels' grid for them (N = 512 -> 4 column tiles of 128; a multiple of 8 row-tile groups) and
+// the decode of that grid: blockIdx.x & 7 is the XCD the workgroup lands on, so the four column tiles of a row tile share an XCD and its
+// L2 (conv_tiles.h's tile_decode at 80 x 128, from the tile count: the group kernel decodes over its largest member's). False: a padding
+// workgroup of the last round.
+__host__ __device__ constexpr int row_tiles(int n) { return (n + 79) / 80; }
+inline dim3 chain_grid(int mtiles) { return dim3(8 * 4 * ((mtiles + 7) / 8)); }
+struct RowTile {
+  int mt, jx;   // row tile; workgroup index inside its XCD (the column tile is its two low bits)
+  __device__ __forceinline__ int nt() const { return jx & 3; }           // column tile
+  __device__ __forceinline__ int n0() const { return (jx & 3) * 128; }   // ... and its first column
+};
+__device__ __forceinline__ bool row_tile_decode(const int mtiles, RowTile& t) {
+  const int per_xcd = (mtiles + 7) >> 3;
+  t.jx = blockIdx.x >> 3;
+  t.mt = (blockIdx.x & 7) * per_xcd + (t.jx >> 2);
+  return t.mt < mtiles;
+}
+
+// Seams (hand-offs) a launch adds to the counter of each of its row tiles: one between two consecutive stages, a stage being a chain
+// layer or the loss stage. rowseq_kernel: n - 1; rowseq_loss_kernel: n; rowstep_kernel: n_fwd + n_bwd; rowseq_group_kernel: cnt - 1 per
+// member. The device adds 8 x this in a launch that returns at entry, the host advances its bases by it (seq_account).
+__host__ __device__ constexpr uint32_t seq_seams(int n_layers, int loss_stages = 0) { return (uint32_t)(n_layers + loss_stages - 1); }
+
+// The bounded poll of a hand-off counter. True: the budget expired.
+// Bounded: a sibling that never arrives (workgroups of one row tile on different XCDs -- every L2 then holds its own copy
+// of the counter and none of them ever reaches the target --, or a sibling that is never dispatched) must not hang the
+// stream. When the budget expires the wave raises the sticky fault word (seq_raise_fault) and goes on with whatever is in memory: the
+// results of this launch are garbage, the optimiser and schedule kernels of the step see the word and do nothing, and
+// the host switches the trainer to per-layer launches at its next state read (head_api.hip).
+// The whole poll is ONE asm statement: written as a C loop with a second exit, the compiler re-scheduled the K loops and
+// epilogues of the input-gradient instantiation (+3 us per chain, same instruction mix; found by diffing the ISA of a
+// build without the bound). sc1: past this CU's L1; the counter and the tiles live in the L2 all four workgroups share,
+// no L2 invalidate. Every lane loads the same word: the loop condition is scalar. The budget is counted in polls
+// (>= ~0.5 us each: an L2 round trip + the sleep).
+__device__ __forceinline__ bool seq_poll_expired(const uint32_t* flag, uint32_t target, uint32_t limit) {
+  uint32_t vseen, sseen, spins, timed;
+  asm volatile(
+      "s_mov_b32 %[spins], 0\n\t"
+      "s_mov_b32 %[timed], 0\n"
+      "1:\n\t"
+      "global_load_dword %[vseen], %[flag], off sc1\n\t"
+      "s_waitcnt vmcnt(0)\n\t"
+      "v_readfirstlane_b32 %[sseen], %[vseen]\n\t"
+      "s_sub_i32 %[sseen], %[sseen], %[target]\n\t"
+      "s_cmp_ge_i32 %[sseen], 0\n\t"
+      "s_cbranch_scc1 2f\n\t"
+      "s_sleep 1\n\t"   // 64 clocks between two polls
+      "s_add_u32 %[spins], %[spins], 1\n\t"
+      "s_cmp_lt_u32 %[spins], %[limit]\n\t"
+      "s_cbranch_scc1 1b\n\t"
+      "s_mov_b32 %[timed], 1\n"
+      "2:"
+      : [vseen] "=&v"(vseen), [sseen] "=&s"(sseen), [spins] "=&s"(spins), [timed] "=&s"(timed)
+      : [flag] "v"(flag), [target] "s"(target), [limit] "s"(limit)
+      : "memory", "scc");
+  return timed != 0;
+}
+
+// An expired poll (one lane of the wave): the fault word goes up and the step is switched off -- every later kernel of this trainer starts
+// with `if (!st->active) return`, the chain kernels with SEQ_DEAD.
+__device__ __forceinline__ void seq_raise_fault(uint32_t* fault_word, const TrainState* st) {
+  __hip_atomic_store(fault_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (st) __hip_atomic_store(const_cast<int*>(&st->active), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The bump of a hand-off counter (one lane of the wave, behind the acknowledgement of the wave's stores: ACEZ_VMCNT(0)): an L2-local
+// atomic without return, no fence.
+__device__ __forceinline__ void seq_bump(uint32_t* flag, const uint32_t inc) {
+  asm volatile("global_atomic_add %0, %1, off" ::"v"(flag), "v"(inc) : "memory");
+}
+
+// The entry test of a launch on a trainer's counters: training has ended on the device (after an expired poll the fault handler has
+// cleared `active` too), or a poll of this trainer has expired in an EARLIER launch -- the buffers of the faulted step are left alone
+// until the host has fallen back. Both words are wave-uniform loads. A dead launch does no work, but its counters keep step with the
+// host's bases (seq_catch_up, one lane of the workgroup: the same L2-local atomic as the hand-off itself).
+// A macro, not a function: as a function (by value or on the kernel arguments by reference) `flags` was fetched in front of the test of
+// `st` and the four chain kernels' registers were allocated anew -- the two loads keep the order they were measured with. Used here
+// and by rowseq_group_kernel (head_group.hip, which #undefs it behind that kernel).
+#define SEQ_DEAD(st, flags) (((st) && !(st)->active) || (flags)[SEQ_FAULT_WORD])
+__device__ __forceinline__ void seq_catch_up(const uint32_t seams, uint32_t* flags, const int mt) {
+  const uint32_t inc = 8u * seams;
+  seq_bump(flags + mt * 32, inc);
+}
+
+// The placement record of a chain kernel (xcc_dbg: RowSeqArgs; null: none), by thread 0 of the workgroup that owns tile t: which XCD ran
+// it. `a`: the kernel arguments by reference, RowSeqArgs or RowStepArgs. (A chain kernel's entry is row_tile_decode and its return --
+// a workgroup without a row tile touches no counter; inside a function that return became a predicate over the whole entry --, this
+// record, then SEQ_DEAD.)
+template <class A>
+__device__ __forceinline__ void seq_record_placement(const A& a, const RowTile& t) {
+  if (a.xcc_dbg && threadIdx.x == 0) {
+    const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;   // HW_REG_XCC_ID[3:0]
+    atomicOr(a.xcc_dbg + (blockIdx.x & 7), 1u << xcc);
+    a.xcc_dbg[8 + t.mt * 4 + t.nt()] = xcc;
+  }
+}
+
 // One layer of one workgroup. SEQ = false: the whole of rowgemm80_kernel. SEQ = true: one link of rowseq_kernel (below), where
 // the layers of a dependent chain run in ONE launch and the kernel boundary is replaced by a same-XCD hand-off (SeqLink).
 struct SeqLink {
@@ -129,7 +233,7 @@ struct SeqLink {
   bool first, wait;      // first layer of the launch (requests its own W stages) / In is produced inside this launch
   bool signal;           // another layer follows: bump *flag after the stores
   const uint16_t* next_W;  // weights of the layer after (null: none): its first four W stages are requested before the epilogue
-  uint32_t flag_index;   // flag = flags + flag_index; the trainer's sticky fault word is flags[64 * 32]: set when the bounded poll
+  uint32_t flag_index;   // flag = flags + flag_index; the trainer's sticky fault word is flags[SEQ_FAULT_WORD]: set when the bounded poll
                          // below expires (the host then falls back to per-layer launches, head_api.hip seq_fault_check)
   uint32_t limit;        // the poll budget (a number of polls), a kernel argument
 };
@@ -199,42 +303,7 @@ __device__ __forceinline__ void rowgemm80_body(const RowGemmArgs& a, uint16_t* s
       // W stages 0..3 first (requested by the layer before unless this is the first), then -- once the four column tiles
       // of the producing layer have landed in this XCD's L2 -- the In stages
       if (q.first) { issueW(0); issueW(1); issueW(2); issueW(3); }
-      if (q.wait) {
-        // Bounded: a sibling that never arrives (workgroups of one row tile on different XCDs -- every L2 then holds its own copy
-        // of the counter and none of them ever reaches the target --, or a sibling that is never dispatched) must not hang the
-        // stream. When the budget expires the wave raises the sticky fault word and goes on with whatever is in memory: the
-        // results of this launch are garbage, the optimiser and schedule kernels of the step see the word and do nothing, and
-        // the host switches the trainer to per-layer launches at its next state read (head_api.hip).
-        // The whole poll is ONE asm statement: written as a C loop with a second exit, the compiler re-scheduled the K loops and
-        // epilogues of the input-gradient instantiation (+3 us per chain, same instruction mix; found by diffing the ISA of a
-        // build without the bound). sc1: past this CU's L1; the counter and the tiles live in the L2 all four workgroups share,
-        // no L2 invalidate. Every lane loads the same word: the loop condition is scalar. The budget is counted in polls
-        // (>= ~0.5 us each: an L2 round trip + the sleep).
-        uint32_t vseen, sseen, spins, timed;
-        asm volatile(
-            "s_mov_b32 %[spins], 0\n\t"
-            "s_mov_b32 %[timed], 0\n"
-            "1:\n\t"
-            "global_load_dword %[vseen], %[flag], off sc1\n\t"
-            "s_waitcnt vmcnt(0)\n\t"
-            "v_readfirstlane_b32 %[sseen], %[vseen]\n\t"
-            "s_sub_i32 %[sseen], %[sseen], %[target]\n\t"
-            "s_cmp_ge_i32 %[sseen], 0\n\t"
-            "s_cbranch_scc1 2f\n\t"
-            "s_sleep 1\n\t"   // 64 clocks between two polls
-            "s_add_u32 %[spins], %[spins], 1\n\t"
-            "s_cmp_lt_u32 %[spins], %[limit]\n\t"
-            "s_cbranch_scc1 1b\n\t"
-            "s_mov_b32 %[timed], 1\n"
-            "2:"
-            : [vseen] "=&v"(vseen), [sseen] "=&s"(sseen), [spins] "=&s"(spins), [timed] "=&s"(timed)
-            : [flag] "v"(q.flag), [target] "s"(q.target), [limit] "s"(q.limit)
-            : "memory", "scc");
-        if (timed && l == 0) {   // the fault word, and the step is switched off: every later kernel of this trainer starts with `if (!st->active) return`
-          __hip_atomic_store(q.flag - q.flag_index + 64 * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (a.st) __hip_atomic_store(const_cast<int*>(&a.st->active), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
+      if (q.wait && seq_poll_expired(q.flag, q.target, q.limit) && l == 0) seq_raise_fault(q.flag - q.flag_index + SEQ_FAULT_WORD, a.st);
       issueI(0); issueI(1); issueI(2); issueI(3);
     }
 #pragma unroll
@@ -453,10 +522,7 @@ __device__ __forceinline__ void rowgemm80_body(const RowGemmArgs& a, uint16_t* s
     if (q2 < 1280 && r2 < M) *reinterpret_cast<uint4*>(first + o2) = f2v;
     if (SEQ && q.signal) {
       ACEZ_VMCNT(0);   // this wave's stores are acknowledged by the L2 = visible to the three sibling workgroups (same XCD)
-      if (l == 0) {
-        const uint32_t one = 1;
-        asm volatile("global_atomic_add %0, %1, off" ::"v"(q.flag), "v"(one) : "memory");
-      }
+      if (l == 0) seq_bump(q.flag, 1u);
     }
     if (AUX != AUX_NONE && second) {   // (null: a training forward does not keep the pre-residual activation -- only its mask bits are read again)
       if (r0 < M) *reinterpret_cast<uint4*>(second + o0) = s0;
@@ -527,12 +593,9 @@ template <bool BIAS_RELU, bool HAS_ADD, bool HAS_MASK, int AUX, class E = EltBf1
 __global__ __launch_bounds__(512) void rowgemm80_kernel(RowGemmArgs a) {
   const int active = a.st ? a.st->active : 1;
   __shared__ __attribute__((aligned(16))) uint16_t smem[RG80_SMEM];
-  const int mtiles = (a.M + 79) / 80;
-  const int per_xcd = (mtiles + 7) >> 3;
-  const int jx = blockIdx.x >> 3;
-  const int mt = (blockIdx.x & 7) * per_xcd + (jx >> 2);
-  if (mt >= mtiles) return;
-  rowgemm80_body<BIAS_RELU, HAS_ADD, HAS_MASK, AUX, false, E>(a, smem, active, mt, (jx & 3) * 128, SeqLink{});
+  RowTile t;
+  if (!row_tile_decode(row_tiles(a.M), t)) return;
+  rowgemm80_body<BIAS_RELU, HAS_ADD, HAS_MASK, AUX, false, E>(a, smem, active, t.mt, t.n0(), SeqLink{});
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -562,14 +625,14 @@ struct RowSeqArgs {
   SeqLayer layer[SEQ_MAX_LAYERS];
   int n_layers, M;
   const TrainState* st;
-  uint32_t* flags;     // [64 row tiles][32] hand-off counters + [64 * 32] the fault word
+  uint32_t* flags;     // [64 row tiles][32] hand-off counters + [SEQ_FAULT_WORD] the fault word
   uint32_t base[64];   // per row tile: seams completed by earlier launches (a launch only touches the row tiles of ITS batch)
   uint32_t spin_limit; // poll budget of a hand-off (polls of >= ~0.5 us); expired: fault word + st->active = 0
   uint32_t* xcc_dbg;   // null, or [8 + 256]: words 0..7 |= 1 << XCC_ID of the workgroups with blockIdx & 7 = word (sticky); word
                        // 8 + 4 mt + nt = XCC_ID of the workgroup that owned tile (mt, nt) in the last launch (tests: the four column
                        // tiles of a row tile must report the same XCD)
-                       // flags[64 * 32] = the sticky fault word (non-zero: a poll of this trainer has expired, every launch returns at
-                       // once), flags[64 * 32 + 1] = a copy of the poll budget (diagnostics)
+                       // flags[SEQ_FAULT_WORD] = the sticky fault word (non-zero: a poll of this trainer has expired, every launch returns at
+                       // once), flags[SEQ_FAULT_WORD + 1] = a copy of the poll budget (diagnostics)
 };
 
 // What the layers of a chain share: the batch, the trainer's state and counters, and where the chain stands among the launch's hand-offs
@@ -588,6 +651,8 @@ struct SeqCtx {
 template <bool BWD, class E, bool HEAD, bool TAIL = false>
 __device__ __forceinline__ void rowseq_layers(const SeqLayer* layers, const int n_layers, const SeqCtx& c, uint16_t* smem, const int mt, const int n0) {
   for (int layer = 0; layer < n_layers; ++layer) {
+    // (one table row -> RowGemmArgs, SeqLink, epilogue shape: written out here and in rowseq_group_kernel -- shared as a function, the
+    // fill or the dispatch alone, it changed the instruction order or the registers of the chain kernels)
     const SeqLayer& y = layers[layer];
     RowGemmArgs g;
     g.In = y.In; g.W = y.W; g.bias = y.bias; g.add = y.add; g.mask_out = y.mask_out; g.mask_in = y.mask_in; g.res = y.res; g.out_main = y.out_main; g.out_aux = y.out_aux;
@@ -612,27 +677,15 @@ __device__ __forceinline__ void rowseq_layers(const SeqLayer* layers, const int 
 template <bool BWD, class E = EltBf16>
 __global__ __launch_bounds__(512) void rowseq_kernel(RowSeqArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t smem[RG80_SMEM_SEQ];
-  const int mtiles = (a.M + 79) / 80;
-  const int per_xcd = (mtiles + 7) >> 3;
-  const int jx = blockIdx.x >> 3;
-  const int mt = (blockIdx.x & 7) * per_xcd + (jx >> 2);
-  if (mt >= mtiles) return;
-  if (a.xcc_dbg && threadIdx.x == 0) {
-    const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;   // HW_REG_XCC_ID[3:0]
-    atomicOr(a.xcc_dbg + (blockIdx.x & 7), 1u << xcc);
-    a.xcc_dbg[8 + mt * 4 + (jx & 3)] = xcc;
-  }
-  // (after an expired poll the fault handler has cleared `active`: nothing of this trainer runs until the host has fallen back)
-  // (... or a hand-off poll of this trainer has expired in an EARLIER launch -- the sticky fault word behind the counters: the buffers of
-  // the faulted step are left alone until the host has fallen back; both words are wave-uniform loads issued together)
-  if ((a.st && !a.st->active) || a.flags[64 * 32]) {   // training has ended on the device: no work, but the counters keep step with the host's bases
-    if (threadIdx.x == 0) {      // (the same L2-local atomic as the hand-off itself)
-      const uint32_t inc = 8u * (uint32_t)(a.n_layers - 1);
-      asm volatile("global_atomic_add %0, %1, off" ::"v"(a.flags + mt * 32), "v"(inc) : "memory");
-    }
+  RowTile t;
+  if (!row_tile_decode(row_tiles(a.M), t)) return;
+  const int mt = t.mt;
+  seq_record_placement(a, t);
+  if (SEQ_DEAD(a.st, a.flags)) {
+    if (threadIdx.x == 0) seq_catch_up(seq_seams(a.n_layers), a.flags, mt);
     return;
   }
-  rowseq_layers<BWD, E, false>(a.layer, a.n_layers, SeqCtx{a.M, a.st, a.flags, a.base[mt], 0u, a.spin_limit}, smem, mt, (jx & 3) * 128);
+  rowseq_layers<BWD, E, false>(a.layer, a.n_layers, SeqCtx{a.M, a.st, a.flags, a.base[mt], 0u, a.spin_limit}, smem, mt, t.n0());
 }
 
 // Placement probe (acez_trainer_create): a launch with rowseq_kernel's grid, block size and LDS footprint that only records
@@ -642,26 +695,27 @@ __global__ __launch_bounds__(512) void rowseq_kernel(RowSeqArgs a) {
 // the mapping does not hold from ever taking the fault path.)
 __global__ __launch_bounds__(512) void seq_probe_kernel(uint32_t* rec /*[256]*/, int mtiles) {
   __shared__ __attribute__((aligned(16))) uint16_t smem[RG80_SMEM_SEQ];
-  const int per_xcd = (mtiles + 7) >> 3;
-  const int jx = blockIdx.x >> 3;
-  const int mt = (blockIdx.x & 7) * per_xcd + (jx >> 2);
+  RowTile t;
+  const bool has_tile = row_tile_decode(mtiles, t);
   if (threadIdx.x == 0) smem[0] = (uint16_t)blockIdx.x;   // keeps the allocation
   __syncthreads();
-  if (mt >= mtiles || threadIdx.x != 0) return;
+  if (!has_tile || threadIdx.x != 0) return;
   const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;   // HW_REG_XCC_ID[3:0]
-  rec[mt * 4 + (jx & 3)] = (xcc << 16) | smem[0];
+  rec[t.mt * 4 + t.nt()] = (xcc << 16) | smem[0];
+}
+
+// the kernel instantiation of a context's 16-bit operand format: f(EltF16{}) or f(EltBf16{})
+template <class F>
+static inline void with_elt(bool f16, F f) {
+  if (f16) f(EltF16{});
+  else f(EltBf16{});
 }
 
 // host-side dispatch on the epilogue shape (the flags of RowGemmArgs select the instantiation)
 static inline void launch_rowgemm(const RowGemmArgs& g, hipStream_t s, bool f16 = false) {
   const bool br = g.bias != nullptr;
-  const int mtiles = (g.M + 79) / 80;
-  const dim3 grid(8 * 4 * ((mtiles + 7) / 8));  // N = 512 -> 4 column tiles; XCD-aware decode inside the kernels
-#define ACEZ_RG(...)                                                                                               \
-  do {                                                                                                             \
-    if (f16) hipLaunchKernelGGL((rowgemm80_kernel<__VA_ARGS__, EltF16>), grid, dim3(512), 0, s, g);                \
-    else hipLaunchKernelGGL((rowgemm80_kernel<__VA_ARGS__>), grid, dim3(512), 0, s, g);                            \
-  } while (0)
+  const dim3 grid = chain_grid(row_tiles(g.M));
+#define ACEZ_RG(...) with_elt(f16, [&](auto e) { hipLaunchKernelGGL((rowgemm80_kernel<__VA_ARGS__, decltype(e)>), grid, dim3(512), 0, s, g); })
   if (br && g.aux_mode == AUX_NONE) ACEZ_RG(true, false, false, AUX_NONE);
   else if (br && g.aux_mode == AUX_RESIDUAL) ACEZ_RG(true, false, false, AUX_RESIDUAL);
   else if (!br && g.mask_in && !g.add && g.aux_mode == AUX_NONE) ACEZ_RG(false, false, true, AUX_NONE);
@@ -1772,7 +1826,20 @@ __global__ __launch_bounds__(256) void recast_kernel(AdamArgs a) {
 // schedule (one thread): ace_schedule.py:72-101 before the step, :115-126 after it. The learning rate is
 // advanced with the same chainable recurrences torch.optim.lr_scheduler uses, in double.
 // ---------------------------------------------------------------------------------------------------
-__device__ double det_cos_pi(double x);  // cos(pi * x), x in [0, 1]
+// cos(pi x) for x in [0,1] with basic operations only (Taylor around the nearest multiple of 1/2).
+__device__ double det_cos_pi(double x) {
+  const double PI = 3.14159265358979323846;
+  // reduce: cos(pi x) = -sin(pi (x - 1/2))
+  const double y = (x - 0.5) * PI;  // in [-pi/2, pi/2]
+  const double y2 = y * y;
+  // sin(y), Taylor to y^21 (|y| <= pi/2: remainder < 1e-17)
+  double term = y, sum = y;
+  for (int k = 1; k <= 11; ++k) {
+    term = -term * y2 / (double)((2 * k) * (2 * k + 1));
+    sum += term;
+  }
+  return -sum;
+}
 
 __device__ double onecycle_lr(const SchedConfig& c, int step_num) {
   // torch OneCycleLR(max_lr, total_steps, pct_start=0.3, anneal='cos', div_factor=25, final_div_factor=1e4,
@@ -2127,45 +2194,10 @@ __global__ __launch_bounds__(256, 4) void adamw_next_kernel(AdamArgs a, int n_ad
   adamw_body(a, b - gblocks - 1, tileT);
 }
 
-// cos(pi x) for x in [0,1] with basic operations only (Taylor around the nearest multiple of 1/2).
-__device__ double det_cos_pi(double x) {
-  const double PI = 3.14159265358979323846;
-  // reduce: cos(pi x) = -sin(pi (x - 1/2))
-  const double y = (x - 0.5) * PI;  // in [-pi/2, pi/2]
-  const double y2 = y * y;
-  // sin(y), Taylor to y^21 (|y| <= pi/2: remainder < 1e-17)
-  double term = y, sum = y;
-  for (int k = 1; k <= 11; ++k) {
-    term = -term * y2 / (double)((2 * k) * (2 * k + 1));
-    sum += term;
-  }
-  return -sum;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// wgrad_opt: wgrad_kernel's product with the optimiser step of the wide layers as its epilogue (single-GPU fused step). wgrad + adamw
-// as two launches round-trip both split-K slabs through HBM (16.8 MB written, 16.8 MB read), start the optimiser's 25 MB of state
-// reads only when the gradients are complete, and pay a kernel boundary; here
-//  * both row slabs of a 128 x 128 tile are placed on ONE XCD (layer = XCD, 32 workgroups each for the default head). A workgroup
-//    finalises the 64 x 128 half tile of its slab index: its two multiplier waves of the OTHER half store their accumulators to the
-//    partner's exchange tile (this XCD's L2), wait for the acknowledgement and bump the partner's counter -- rowseq_kernel's hand-off:
-//    L2-local atomic, bounded sc1 poll on the other side, no fence, nothing read before it is produced;
-//  * the eight loader waves, idle once the last stage is requested, fetch p, m, v of the half tile a dozen stages before the K loop
-//    ends, then poll, add own (through LDS) + partner partial in slab order (slab 0 + slab 1: the additions of grad_reduce_kernel /
-//    adamw_body, so the parameters are bitwise those of backward + update), apply adamw_one and store p, m, v, W and -- through an
-//    LDS transpose -- W^T.
-// The guards are adamw_body's (schedule inactive, chain fault, NaN loss, fp16 overflow: nothing is stored); the exchange itself is
-// unconditional, so the two partners never disagree about it. A poll that expires raises the trainer's fault word exactly like a
-// rowseq hand-off (the host falls back to wgrad_kernel + adamw_kernel at its next state read); the stores of that wave are skipped.
-// Host: only when the grid fits the CUs (every workgroup resident) and the placement probe has passed (head_api.hip).
-// The four multiplier waves of a workgroup have nothing to do while its loader waves run the optimiser arithmetic (~3.5 us of VALU work
-// per CU): in the first `nsmall` workgroups they are the small-parameter workgroups of the optimiser launch (adamw_small_columns: biases,
-// fc3, statistics), and wave 0 of the last workgroup is the schedule wave that closes the step (do_post) -- with the next batch
-// gathered beside the loss kernel (loss_gather_kernel), a step without pose refinement has no optimiser launch left at all.
-// ---------------------------------------------------------------------------------------------------
-constexpr int WGO_PF = 17;   // prefetch loads per loader lane: 4 x (p, m, v) float4 + the first five rows of the loss partials
-// spin until an LDS counter of this workgroup reaches `target` (the waves of a workgroup meet through these after the K loop instead of
-// s_barrier: a barrier would make the loader waves' arithmetic wait for the multiplier waves' small-parameter work and vice versa)
+// LDS counters through which the waves of one workgroup meet without s_barrier (the wave quartets of rowseq_loss_stage; wgrad_opt_kernel's
+// multiplier and loader waves after the K loop: a barrier would make the loader waves' arithmetic wait for the multiplier waves'
+// small-parameter work and vice versa). Ahead of their first user, the loss stage.
+// spin until an LDS counter of this workgroup reaches `target`
 __device__ __forceinline__ void lds_wait_ge(uint32_t* f, uint32_t target) {
   while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < target) __builtin_amdgcn_s_sleep(1);
   asm volatile("" ::: "memory");
@@ -2204,32 +2236,6 @@ struct SeqLossArgs {
   GatherMeta meta;
 };
 
-// rowgemm80_body's hand-off poll for a consumer that is not a layer (the loss blocks of rowstep_kernel): the same bounded single asm
-// statement, sc1 past this CU's L1 (see there). True: the budget expired.
-__device__ __forceinline__ bool seq_poll_expired(const uint32_t* flag, uint32_t target, uint32_t limit) {
-  uint32_t vseen, sseen, spins, timed;
-  asm volatile(
-      "s_mov_b32 %[spins], 0\n\t"
-      "s_mov_b32 %[timed], 0\n"
-      "1:\n\t"
-      "global_load_dword %[vseen], %[flag], off sc1\n\t"
-      "s_waitcnt vmcnt(0)\n\t"
-      "v_readfirstlane_b32 %[sseen], %[vseen]\n\t"
-      "s_sub_i32 %[sseen], %[sseen], %[target]\n\t"
-      "s_cmp_ge_i32 %[sseen], 0\n\t"
-      "s_cbranch_scc1 2f\n\t"
-      "s_sleep 1\n\t"
-      "s_add_u32 %[spins], %[spins], 1\n\t"
-      "s_cmp_lt_u32 %[spins], %[limit]\n\t"
-      "s_cbranch_scc1 1b\n\t"
-      "s_mov_b32 %[timed], 1\n"
-      "2:"
-      : [vseen] "=&v"(vseen), [sseen] "=&s"(sseen), [spins] "=&s"(spins), [timed] "=&s"(timed)
-      : [flag] "v"(flag), [target] "s"(target), [limit] "s"(limit)
-      : "memory", "scc");
-  return timed != 0;
-}
-
 // Stage -1 for the workgroup of tile (mt, nt), all eight waves: the first layer's W stages, the next batch's gather, the tile's loss
 // blocks and their hand-off to layer 0 (`W0`: that layer's weights). `dead`: the launch's entry test -- only the gather runs.
 // FWD_SEAM (rowstep_kernel): the blocks' `act` rows are produced inside this launch, by the four workgroups of the row tile: every wave
@@ -2267,45 +2273,29 @@ __device__ __forceinline__ void rowseq_loss_stage(const uint16_t* W0, const SeqL
     uint32_t* const flag = c.flags + mt * 32;
     const int quartet = w >> 2;
     const int block = 5 * mt + (nt == 0 ? quartet : nt + 1);
-    if (FWD_SEAM && seq_poll_expired(flag, (c.base + c.seam0 - 1u) * 32u, c.limit) && l == 0) {   // rowgemm80_body's fault path
-      __hip_atomic_store(c.flags + 64 * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (c.st) __hip_atomic_store(const_cast<int*>(&c.st->active), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (FWD_SEAM && seq_poll_expired(flag, (c.base + c.seam0 - 1u) * 32u, c.limit) && l == 0) seq_raise_fault(c.flags + SEQ_FAULT_WORD, c.st);
     if (block < x.nblk) {
       float* scratch = reinterpret_cast<float*>(smem + 4 * RG80_STAGE) + quartet * (3 * 4 * 4 * 4);
       uint32_t* const f = qsync + quartet;
       loss_body<false, true, E, 4>(x.loss, block, w & 3, l, nullptr, scratch, LossPre{0, 0, 0, 0.f, 0.f}, [f] { lds_bump(f); lds_wait_ge(f, 4u); });
     }
     ACEZ_VMCNT(0);   // this wave's dZ stores are acknowledged by the L2 the four sibling workgroups share
-    if (l == 0) {
-      const uint32_t inc = nt == 0 ? 1u : 2u;   // 8 per workgroup: eight waves, or four
-      asm volatile("global_atomic_add %0, %1, off" ::"v"(flag), "v"(inc) : "memory");
-    }
+    if (l == 0) seq_bump(flag, nt == 0 ? 1u : 2u);   // 8 per workgroup: eight waves, or four
   }
 }
 
 template <class E = EltBf16>
 __global__ __launch_bounds__(512) void rowseq_loss_kernel(RowSeqArgs a, SeqLossArgs x) {
   __shared__ __attribute__((aligned(16))) uint16_t smem[RG80_SMEM_SEQ];
-  const int mtiles = (a.M + 79) / 80;
-  const int per_xcd = (mtiles + 7) >> 3;
-  const int jx = blockIdx.x >> 3;
-  const int mt = (blockIdx.x & 7) * per_xcd + (jx >> 2);
-  if (mt >= mtiles) return;
-  const int nt = jx & 3;
-  if (a.xcc_dbg && threadIdx.x == 0) {
-    const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;   // HW_REG_XCC_ID[3:0]
-    atomicOr(a.xcc_dbg + (blockIdx.x & 7), 1u << xcc);
-    a.xcc_dbg[8 + mt * 4 + nt] = xcc;
-  }
-  const bool dead = (a.st && !a.st->active) || a.flags[64 * 32];   // rowseq_kernel's entry test
+  RowTile t;
+  if (!row_tile_decode(row_tiles(a.M), t)) return;
+  const int mt = t.mt, nt = t.nt();
+  seq_record_placement(a, t);
+  const bool dead = SEQ_DEAD(a.st, a.flags);
   const SeqCtx c{a.M, a.st, a.flags, a.base[mt], 1u, a.spin_limit};
-  rowseq_loss_stage<E, false>(a.layer[0].W, x, c, dead, smem, mt, nt, mtiles);
-  if (dead) {   // no work, but the counters keep step with the host's bases (one seam more than rowseq_kernel's launch)
-    if (threadIdx.x == 0) {
-      const uint32_t inc = 8u * (uint32_t)a.n_layers;
-      asm volatile("global_atomic_add %0, %1, off" ::"v"(a.flags + mt * 32), "v"(inc) : "memory");
-    }
+  rowseq_loss_stage<E, false>(a.layer[0].W, x, c, dead, smem, mt, nt, row_tiles(a.M));
+  if (dead) {   // (one seam more than rowseq_kernel's launch)
+    if (threadIdx.x == 0) seq_catch_up(seq_seams(a.n_layers, 1), a.flags, mt);
     return;
   }
   rowseq_layers<true, E, true>(a.layer, a.n_layers, c, smem, mt, nt * 128);
@@ -2339,32 +2329,44 @@ static_assert(sizeof(RowStepArgs) <= 4096, "kernel-argument segment");
 template <class E = EltBf16>
 __global__ __launch_bounds__(512) void rowstep_kernel(RowStepArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t smem[RG80_SMEM_SEQ];
-  const int mtiles = (a.M + 79) / 80;
-  const int per_xcd = (mtiles + 7) >> 3;
-  const int jx = blockIdx.x >> 3;
-  const int mt = (blockIdx.x & 7) * per_xcd + (jx >> 2);
-  if (mt >= mtiles) return;   // (a workgroup without a row tile touches no counter)
-  const int nt = jx & 3;
-  if (a.xcc_dbg && threadIdx.x == 0) {
-    const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;   // HW_REG_XCC_ID[3:0]
-    atomicOr(a.xcc_dbg + (blockIdx.x & 7), 1u << xcc);
-    a.xcc_dbg[8 + mt * 4 + nt] = xcc;
-  }
-  const bool dead = (a.st && !a.st->active) || a.flags[64 * 32];   // rowseq_kernel's entry test
+  RowTile t;
+  if (!row_tile_decode(row_tiles(a.M), t)) return;
+  const int mt = t.mt, nt = t.nt();
+  seq_record_placement(a, t);
+  const bool dead = SEQ_DEAD(a.st, a.flags);
   const uint32_t base = a.base[mt];
   if (!dead) rowseq_layers<false, E, false, true>(a.fwd, a.n_fwd, SeqCtx{a.M, a.st, a.flags, base, 0u, a.spin_limit}, smem, mt, nt * 128);
   const SeqCtx c{a.M, a.st, a.flags, base, (uint32_t)a.n_fwd + 1u, a.spin_limit};
-  rowseq_loss_stage<E, true>(a.bwd[0].W, a.x, c, dead, smem, mt, nt, mtiles);
-  if (dead) {   // no work, but the counters keep step with the host's bases
-    if (threadIdx.x == 0) {
-      const uint32_t inc = 8u * (uint32_t)(a.n_fwd + a.n_bwd);
-      asm volatile("global_atomic_add %0, %1, off" ::"v"(a.flags + mt * 32), "v"(inc) : "memory");
-    }
+  rowseq_loss_stage<E, true>(a.bwd[0].W, a.x, c, dead, smem, mt, nt, row_tiles(a.M));
+  if (dead) {
+    if (threadIdx.x == 0) seq_catch_up(seq_seams(a.n_fwd + a.n_bwd, 1), a.flags, mt);
     return;
   }
   rowseq_layers<true, E, true>(a.bwd, a.n_bwd, c, smem, mt, nt * 128);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// wgrad_opt: wgrad_kernel's product with the optimiser step of the wide layers as its epilogue (single-GPU fused step). wgrad + adamw
+// as two launches round-trip both split-K slabs through HBM (16.8 MB written, 16.8 MB read), start the optimiser's 25 MB of state
+// reads only when the gradients are complete, and pay a kernel boundary; here
+//  * both row slabs of a 128 x 128 tile are placed on ONE XCD (layer = XCD, 32 workgroups each for the default head). A workgroup
+//    finalises the 64 x 128 half tile of its slab index: its two multiplier waves of the OTHER half store their accumulators to the
+//    partner's exchange tile (this XCD's L2), wait for the acknowledgement and bump the partner's counter -- rowseq_kernel's hand-off:
+//    L2-local atomic, bounded sc1 poll on the other side, no fence, nothing read before it is produced;
+//  * the eight loader waves, idle once the last stage is requested, fetch p, m, v of the half tile a dozen stages before the K loop
+//    ends, then poll, add own (through LDS) + partner partial in slab order (slab 0 + slab 1: the additions of grad_reduce_kernel /
+//    adamw_body, so the parameters are bitwise those of backward + update), apply adamw_one and store p, m, v, W and -- through an
+//    LDS transpose -- W^T.
+// The guards are adamw_body's (schedule inactive, chain fault, NaN loss, fp16 overflow: nothing is stored); the exchange itself is
+// unconditional, so the two partners never disagree about it. A poll that expires raises the trainer's fault word exactly like a
+// rowseq hand-off (the host falls back to wgrad_kernel + adamw_kernel at its next state read); the stores of that wave are skipped.
+// Host: only when the grid fits the CUs (every workgroup resident) and the placement probe has passed (head_api.hip).
+// The four multiplier waves of a workgroup have nothing to do while its loader waves run the optimiser arithmetic (~3.5 us of VALU work
+// per CU): in the first `nsmall` workgroups they are the small-parameter workgroups of the optimiser launch (adamw_small_columns: biases,
+// fc3, statistics), and wave 0 of the last workgroup is the schedule wave that closes the step (do_post) -- with the next batch
+// gathered beside the loss kernel (loss_gather_kernel), a step without pose refinement has no optimiser launch left at all.
+// ---------------------------------------------------------------------------------------------------
+constexpr int WGO_PF = 17;   // prefetch loads per loader lane: 4 x (p, m, v) float4 + the first five rows of the loss partials
 #ifdef ACEZ_DIAG   // timeline of the epilogue (tools/wgo_trace.py): stamp i of this wave
 #define WGO_STAMP(i) do { if (o.trace && (threadIdx.x & 63) == 0) o.trace[((size_t)blockIdx.x * 12 + (threadIdx.x >> 6)) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
@@ -2456,10 +2458,7 @@ __global__ __launch_bounds__(WGRAD_THREADS) void wgrad_opt_kernel(WgradArgs a, W
           for (int r = 0; r < 16; ++r)
             X[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 128 + wc * 64 + j * 32 + (l & 31)] = acc[i][j][r];
       ACEZ_VMCNT(0);   // acknowledged by the L2 both workgroups share
-      if (l == 0) {
-        const uint32_t one = 1;
-        asm volatile("global_atomic_add %0, %1, off" ::"v"(o.flags + (size_t)(pair * 2 + (1 - slab)) * 32), "v"(one) : "memory");
-      }
+      if (l == 0) seq_bump(o.flags + (size_t)(pair * 2 + (1 - slab)) * 32, 1u);
     } else {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -2500,32 +2499,12 @@ __global__ __launch_bounds__(WGRAD_THREADS) void wgrad_opt_kernel(WgradArgs a, W
   bool skip = !active || fault_now || lossv != lossv;   // adamw_body's guards
   if (E::is_f16) skip = skip || f16_overflow(absmax_reduce(amx));
   const bool skip_by_guard = skip;   // (uniform over the launch: every wave evaluates the same words)
-  uint32_t vseen, sseen, spins, timed;
   const uint32_t* flag = o.flags + (size_t)(pair * 2 + slab) * 32;
   uint32_t wgo_target = o.target;
 #ifdef ACEZ_DIAG   // fault injection in SOME workgroups (ACEZ_WGO_FAULT_MOD): a partially applied step
   if (o.fault_mod > 0 && b % o.fault_mod == 1) wgo_target += 1u << 20;
 #endif
-  asm volatile(
-      "s_mov_b32 %[spins], 0\n\t"
-      "s_mov_b32 %[timed], 0\n"
-      "1:\n\t"
-      "global_load_dword %[vseen], %[flag], off sc1\n\t"
-      "s_waitcnt vmcnt(0)\n\t"
-      "v_readfirstlane_b32 %[sseen], %[vseen]\n\t"
-      "s_sub_i32 %[sseen], %[sseen], %[target]\n\t"
-      "s_cmp_ge_i32 %[sseen], 0\n\t"
-      "s_cbranch_scc1 2f\n\t"
-      "s_sleep 1\n\t"
-      "s_add_u32 %[spins], %[spins], 1\n\t"
-      "s_cmp_lt_u32 %[spins], %[limit]\n\t"
-      "s_cbranch_scc1 1b\n\t"
-      "s_mov_b32 %[timed], 1\n"
-      "2:"
-      : [vseen] "=&v"(vseen), [sseen] "=&s"(sseen), [spins] "=&s"(spins), [timed] "=&s"(timed)
-      : [flag] "v"(flag), [target] "s"(wgo_target), [limit] "s"(o.spin_limit)
-      : "memory", "scc");
-  if (timed) {   // the partner never arrived (the two slabs of a tile are not on one XCD after all): fault word, step switched off
+  if (seq_poll_expired(flag, wgo_target, o.spin_limit)) {   // the partner never arrived (the two slabs of a tile are not on one XCD after all): fault word, step switched off
     skip = true;
     if (l == 0) {
       // What the host needs to finish this step (wgo_recover, head_api.hip): which rows were not updated, and with what they would have
@@ -2537,8 +2516,7 @@ __global__ __launch_bounds__(WGRAD_THREADS) void wgrad_opt_kernel(WgradArgs a, W
         o.rec->s = s; o.rec->inv_scale = inv_scale; o.rec->M = a.M; o.rec->in0 = a.In[0];
         __hip_atomic_store(&o.rec->epoch, o.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
-      __hip_atomic_store(ad.fault, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(const_cast<int*>(&st->active), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      seq_raise_fault(reinterpret_cast<uint32_t*>(ad.fault), st);
     }
   }
   WGO_STAMP(2);   // loaders: guards evaluated, partner's counter seen
