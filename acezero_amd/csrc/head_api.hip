@@ -1054,10 +1054,14 @@ static int launch_update(acez_trainer* tr, const StepPlan& p, hipStream_t s, int
     const int npb = (int)((tr->pb.n_pose_params + 255) / 256);
     const bool ahead = p.next_at == NextAt::Optimiser;
     const int gblocks = ahead ? std::max(64, std::min(gather_blocks(n_next), 4 * tr->n_cus - n_adam - npb)) : 0;
+    // Split flow: the optimiser workgroups of this very launch raise the local fault word from the all-reduced statistics slot 3, so the
+    // pose workgroups decide on the slot itself (a fused step's slot is still being written by this launch: the word alone is right there)
+    const float* reduced_fault = fused ? nullptr : (const float*)(tr->pb.d_grad + tr->n_params + 3);
     { ProfScope ps(tr, s, KC_ADAMW);
       hipLaunchKernelGGL(adamw_split_pose_kernel, dim3(npb + n_adam + gblocks), dim3(256), 0, s, a, npb, tr->pb.d_pose_params, tr->pb.d_pose_m,
                          tr->pb.d_pose_v, (const float*)(tr->pb.d_grad + tr->n_params + 4), (int64_t)tr->pb.n_pose_params,
-                         (const AdamScalars*)&tr->st->pose_adam, (const int*)&tr->st->pose_enable, (const int*)&tr->st->active, (const int*)tr->seq_err, wt,
+                         (const AdamScalars*)&tr->st->pose_adam, (const int*)&tr->st->pose_enable, (const int*)&tr->st->active, (const int*)tr->seq_err,
+                         reduced_fault, wt,
                          n_adam, (const uint16_t*)tr->buf.d_features, d_next, tr->R[0], ahead ? n_next : 0, gather_meta(tr)); }
     if (ahead) tr->carry.hold(d_next, n_next, false);
     if (!wt) tr->pose_wt_valid = false;   // no transposed copies kept here: the next folded forward rebuilds them

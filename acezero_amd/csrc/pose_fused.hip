@@ -104,9 +104,11 @@ __global__ __launch_bounds__(256, 3) void grad_reduce_pose_kernel(GradReduceArgs
 
 // blocks: the workgroups (if any) that gather the NEXT batch's rows (acez_train_update_next: the following backward's launch then carries
 // the pose forward and the schedule wave only), npb of 256 pose parameters each, n_adam = adamw_kernel's. Wt: the transposed copies
-// (null: none kept)
+// (null: none kept). reduced_fault: statistics slot 3 of the all-reduced bucket (split flow; null in a fused step, where sibling workgroups
+// of this launch are still writing the slot)
 __global__ __launch_bounds__(256, 4) void adamw_split_pose_kernel(AdamArgs a, int npb, float* p, float* m, float* v, const float* g, int64_t n,
-                                                               const AdamScalars* sc, const int* enable, const int* active, const int* fault, float* Wt,
+                                                               const AdamScalars* sc, const int* enable, const int* active, const int* fault,
+                                                               const float* reduced_fault, float* Wt,
                                                                int n_adam, const uint16_t* __restrict__ feat, const int64_t* __restrict__ idx_next,
                                                                uint16_t* __restrict__ out, int n_next, GatherMeta meta) {
   __shared__ uint16_t tileT[64][66];
@@ -114,6 +116,8 @@ __global__ __launch_bounds__(256, 4) void adamw_split_pose_kernel(AdamArgs a, in
   const int ngb = (int)gridDim.x - npb - n_adam;
   int b = (int)blockIdx.x;
   if (b < ngb) {
+    // (a step abandoned by ANOTHER rank: these rows may or may not be gathered, as the hold races with adamw_body raising the word below.
+    // Either is right: the next backward is a no-op under the fault word, and the fall-back drops the batch held ahead and gathers again)
     gather_rows(feat, idx_next, out, n_next, (b * (int)blockDim.x + (int)threadIdx.x) >> 6, (ngb * (int)blockDim.x) >> 6, threadIdx.x & 63, meta);
     return;
   }
@@ -122,9 +126,14 @@ __global__ __launch_bounds__(256, 4) void adamw_split_pose_kernel(AdamArgs a, in
     adamw_body(a, b - npb, tileT);
     return;
   }
-  if (active && !*active) return;
-  if (fault && *fault) return;   // abandoned step (rowseq fault, head_kernels.hip)
-  if (enable && !*enable) return;
+  // the four guard words are requested together, before any of them is looked at (one round trip in front of the workgroup, not four)
+  const int active_now = active ? *active : 1, fault_now = fault ? *fault : 0, enabled = enable ? *enable : 1;
+  const float reduced = reduced_fault ? *reduced_fault : 0.f;
+  if (!active_now || fault_now) return;   // schedule ended / abandoned step (rowseq fault, head_kernels.hip): the rank that already knows
+  // ... and the rank that learns of it from the bucket: adamw_body raises `fault` / clears `active` from the all-reduced slot in THIS
+  // launch, behind these workgroups in the grid, so the words are a race here and the statistic is not (as in sched_post_wave)
+  if (fmodf(reduced, 1024.f) != 0.f) return;
+  if (!enabled) return;
   const int64_t i = (int64_t)b * 256 + threadIdx.x;
   if (i >= n) return;
   const AdamScalars s = *sc;

@@ -301,6 +301,46 @@ def big_problem(n_images=24, patches_per_view=512):
     return prob
 
 
+# ---- everything a training step leaves behind in a HeadTrainer, as bit patterns (the bitwise flow-equivalence and abandoned-step tests) ----
+def trainer_snapshot(tr):
+    """Trained state of a HeadTrainer: head parameters and moments, the 16-bit weight copies, pose parameters and moments (where the
+    configuration has them), the refined poses, every field of state() and the log. The state read comes first: it runs a pending
+    schedule wave and performs a pending fall-back, so the tensors are read behind both."""
+    out = dict(tr.state())
+    for name, t in (("params", tr.params), ("m", tr.adam_m), ("v", tr.adam_v), ("pose_params", tr.pose_params), ("pose_m", tr.pose_m),
+                    ("pose_v", tr.pose_v)):
+        if t is not None:
+            out[name] = t.view(torch.int32).cpu().numpy().copy()
+    w16 = tr.new_weights16_buffer()
+    tr.export_weights16(0, tr.L, w16)
+    out["w16"] = w16.cpu().numpy()
+    out["poses"] = tr.current_poses().view(np.int32).copy()
+    loss, inl = tr.log(0, tr.iterations + 8)
+    out["log"] = (loss.view(np.int32).copy(), inl.view(np.int32).copy())
+    return out
+
+
+def same_bits(x, y):
+    if isinstance(x, tuple):
+        return len(x) == len(y) and all(np.array_equal(p, q) for p, q in zip(x, y))
+    if isinstance(x, np.ndarray):
+        return np.array_equal(x, y)
+    return x == y or (x != x and y != y)   # (scalars of state(): a NaN equals a NaN)
+
+
+def snapshot_differences(a, b):
+    """Keys of two snapshots whose values differ in any bit."""
+    assert a.keys() == b.keys()
+    return [k for k in a if not same_bits(a[k], b[k])]
+
+
+def assert_snapshots_equal(a, b, what):
+    for k in snapshot_differences(a, b):
+        if isinstance(a[k], np.ndarray):
+            raise AssertionError((what, k, int((a[k] != b[k]).sum())))
+        raise AssertionError((what, k) if isinstance(a[k], tuple) else (what, k, a[k], b[k]))
+
+
 # ---- the mesh tools' GPU tests (tests/test_mesh_gpu.py, tests/test_simplify_gpu.py, tests/test_mesh_args_gpu.py) ----
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 

@@ -11,6 +11,7 @@ import torch
 from acezero_amd import _native as N
 from acezero_amd import synth
 from acezero_amd.head import HeadGroup, HeadTrainer
+from tests import helpers
 
 pytestmark = pytest.mark.gpu
 
@@ -39,13 +40,7 @@ def _batches(k, n, steps):
 
 
 def _snapshot(tr, n):
-    st = tr.state()
-    out = {k: st[k] for k in ("iteration", "max_iterations", "lr", "in_cooldown", "grad_scale", "opt_steps", "loss", "batch_inliers")}
-    for name, t in (("params", tr.params), ("m", tr.adam_m), ("v", tr.adam_v)):
-        out[name] = t.view(torch.int32).cpu().numpy().copy()
-    w16 = tr.new_weights16_buffer()
-    tr.export_weights16(0, tr.L, w16)
-    out["w16"] = w16.cpu().numpy()
+    out = helpers.trainer_snapshot(tr)   # the trained state; below: what the last step left in the trainer's work buffers
     for l in range(tr.L):
         if l < 3 * (tr.nb + 1) and l % 3 == 2:
             continue    # (a block's last activation is not stored by a training forward, only its mask bits)
@@ -53,22 +48,11 @@ def _snapshot(tr, n):
         out[f"dZ{l}"] = tr.debug_read("dZ", l, n)
     for b in range(tr.nb + 2):
         out[f"R{b}"] = tr.debug_read("R", b, n)
-    loss, inl = tr.log(0, tr.iterations + 8)
-    out["log"] = (loss.view(np.int32).copy(), inl.view(np.int32).copy())
     out["xyz"] = tr.last_scene_coords(n).view(np.int32).copy()
     return out
 
 
-def _assert_same(a, b, what):
-    assert a.keys() == b.keys()
-    for k in a:
-        if isinstance(a[k], tuple):
-            for x, y in zip(a[k], b[k]):
-                assert np.array_equal(x, y), (what, k)
-        elif isinstance(a[k], np.ndarray):
-            assert np.array_equal(a[k], b[k]), (what, k, int((a[k] != b[k]).sum()))
-        else:
-            assert a[k] == b[k], (what, k, a[k], b[k])
+_assert_same = helpers.assert_snapshots_equal
 
 
 def _run(dtype, H, steps=40, announce=False, sizes=None, iters=None, mixed=False):

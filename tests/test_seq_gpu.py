@@ -229,21 +229,51 @@ def test_placement_probe_passes_on_this_gpu_and_gates_the_chains():
         os.environ.pop("ACEZ_SEQ", None)
 
 
-@pytest.mark.parametrize("fault_at", [2, 3])   # launch 2 = the forward chain of the second step, 3 = its input-gradient chain
-def test_expired_handoff_poll_abandons_the_step_and_falls_back_to_per_layer_launches(fault_at, diag_lib):
+# the trainers of the fault tests: the plainest one (_small_trainer), and the refinement step's -- pose network + calibration, naive poses
+FAULT_CONFIGS = ["plain", "head_tanh_posemlp", "head_tanh_posenaive"]
+
+
+def _fault_trainer(prob, config):
+    """'plain': _small_trainer. Else helpers.HEAD_CONFIGS[config] through tests/test_head_gpu.py::_trainer, the pose optimiser enabled from
+    the second step on (no wait), the network's configuration with calibration refinement (the step ace_zero.py's refinement rounds run)."""
+    if config == "plain":
+        return _small_trainer(prob)
+    from oracle import head_oracle
+    cfg = helpers.full_cfg(helpers.HEAD_CONFIGS[config], prob)
+    cfg.update(global_batch=2048, iterations=50, pose_refinement_wait=0, refine_calibration=config == "head_tanh_posemlp")
+    return _trainer(prob, head_oracle.init_params(helpers.SEED + 1), cfg, max_batch=2048)
+
+
+def _with_configs(values):
+    """Every value with every trainer; the plain trainer's cases keep the ids they had before the configurations were added."""
+    return [pytest.param(v, c, id=str(v) + ("" if c == "plain" else "-" + c)) for c in FAULT_CONFIGS for v in values]
+
+
+def _trained(tr):
+    """Clones of every trained tensor (no state read: the fall-back must not have happened yet where this is compared)."""
+    return [t.clone() for t in (tr.params, tr.adam_m, tr.adam_v, tr.pose_params, tr.pose_m, tr.pose_v) if t is not None]
+
+
+def _trained_equal(tr, saved):
+    return all(torch.equal(a, b) for a, b in zip(_trained(tr), saved))
+
+
+@pytest.mark.parametrize("fault_at,config", _with_configs([2, 3]))   # launch 2 = the forward chain of the second step, 3 = its input-gradient chain
+def test_expired_handoff_poll_abandons_the_step_and_falls_back_to_per_layer_launches(fault_at, config, diag_lib):
     """Fault injection (ACEZ_SEQ_FAULT_AT): one seam of one launch waits for a count that never comes -- what a sibling on a foreign
-    XCD looks like. The poll must expire (no hang), the step it happened in must leave parameters, optimiser state and iteration
-    count untouched, every later step before the next state read must be a no-op too, state() must switch the trainer to
+    XCD looks like. The poll must expire (no hang), the step it happened in must leave the whole trained state -- head and pose
+    parameters, all moments, 16-bit copies, refined poses, calibration scalar, schedule state, log (helpers.trainer_snapshot) --
+    untouched, every later step before the next state read must be a no-op too, state() must switch the trainer to
     per-layer launches, and from there on the trajectory must be bit-identical to a per-layer trainer fed the surviving batches."""
     prob = _big_problem(n_images=8, patches_per_view=256)
     os.environ.update(ACEZ_SEQ_FAULT_AT=str(fault_at), ACEZ_SEQ_SPIN_US="3000")
     try:
-        new = _small_trainer(prob)
+        new = _fault_trainer(prob, config)
     finally:
         os.environ.pop("ACEZ_SEQ_FAULT_AT"); os.environ.pop("ACEZ_SEQ_SPIN_US")
     os.environ["ACEZ_SEQ"] = "0"
     try:
-        ref = _small_trainer(prob)
+        ref = _fault_trainer(prob, config)
     finally:
         os.environ.pop("ACEZ_SEQ", None)
     rng = np.random.default_rng(4)
@@ -252,38 +282,55 @@ def test_expired_handoff_poll_abandons_the_step_and_falls_back_to_per_layer_laun
     ref.step(batches[0])
     torch.cuda.synchronize()
     assert torch.equal(new.params, ref.params)
-    before = (new.params.clone(), new.adam_m.clone(), new.adam_v.clone())
+    snap0 = helpers.trainer_snapshot(new)
+    helpers.assert_snapshots_equal(snap0, helpers.trainer_snapshot(ref), (config, "first step"))
+    before = _trained(new)
     new.step(batches[1])          # the faulting step
     new.step(batches[2])          # issued before the host knows: must be a no-op as well
     torch.cuda.synchronize()
-    assert torch.equal(new.params, before[0]) and torch.equal(new.adam_m, before[1]) and torch.equal(new.adam_v, before[2])
+    assert _trained_equal(new, before)
     st = new.state()              # the state read performs the fall-back
     assert st["iteration"] == 1 and not st["nan"], st
     assert new.seq_status() == {"enabled": False, "probe": 1, "faults": 1}
+    helpers.assert_snapshots_equal(helpers.trainer_snapshot(new), snap0, (config, "abandoned step"))
     for b in batches[3:]:
         new.step(b)
         ref.step(b)
     torch.cuda.synchronize()
     assert torch.equal(new.params, ref.params) and torch.equal(new.adam_m, ref.adam_m) and torch.equal(new.adam_v, ref.adam_v)
     assert new.state() == ref.state()
+    end = helpers.trainer_snapshot(new)
+    helpers.assert_snapshots_equal(end, helpers.trainer_snapshot(ref), (config, "behind the fall-back"))
+    assert {"params", "iteration"} <= set(helpers.snapshot_differences(end, snap0))
+    assert new.pose_params is None or "pose_params" in helpers.snapshot_differences(end, snap0)   # (the pose optimiser does step)
     f = torch.from_numpy(prob["features"][:777]).cuda()
     assert torch.equal(new.get_scene_coordinates(f), ref.get_scene_coordinates(f))
 
 
-@pytest.mark.parametrize("announce", [False, True])
-def test_fault_word_travels_in_the_gradient_bucket(announce, diag_lib):
+@pytest.mark.parametrize("announce,config", _with_configs([False, True]))
+def test_fault_word_travels_in_the_gradient_bucket(announce, config, diag_lib):
     """Data-parallel flow (backward / all-reduce / update): statistics slot 3 of the bucket carries the rank's fault word, so that
     after the all-reduce EVERY rank skips the optimiser step and the replicas stay identical. One process plays both ranks here:
-    rank A faults, rank B does not; B receives A's slot through the (emulated) sum and must skip its update and fall back too."""
+    rank A faults, rank B does not; B receives A's slot through the (emulated) sum and must skip its update and fall back too.
+    With pose refinement a healthy step comes first, so that the pose optimiser is enabled in the step that faults; on both ranks the
+    whole trained state (helpers.trainer_snapshot) stays what it was."""
     prob = _big_problem(n_images=8, patches_per_view=256)
-    os.environ.update(ACEZ_SEQ_FAULT_AT="0", ACEZ_SEQ_SPIN_US="3000")
+    warm = 0 if config == "plain" else 1
+    os.environ.update(ACEZ_SEQ_FAULT_AT=str(2 * warm), ACEZ_SEQ_SPIN_US="3000")   # (two chain launches per split step)
     try:
-        a = _small_trainer(prob)
+        a = _fault_trainer(prob, config)
     finally:
         os.environ.pop("ACEZ_SEQ_FAULT_AT"); os.environ.pop("ACEZ_SEQ_SPIN_US")
-    b = _small_trainer(prob)
+    b = _fault_trainer(prob, config)
     rng = np.random.default_rng(8)
     idx = torch.from_numpy(rng.permutation(prob["features"].shape[0])[:2048].astype(np.int64)).cuda()
+    for _ in range(warm):
+        w = torch.from_numpy(rng.permutation(prob["features"].shape[0])[:2048].astype(np.int64)).cuda()
+        for t in (a, b):
+            t.backward(w)
+            t.update()
+    snap0 = helpers.trainer_snapshot(b)
+    helpers.assert_snapshots_equal(helpers.trainer_snapshot(a), snap0, (config, "replicas in front of the step"))
     a.backward(idx)
     b.backward(idx)
     torch.cuda.synchronize()
@@ -292,6 +339,7 @@ def test_fault_word_travels_in_the_gradient_bucket(announce, diag_lib):
     a.grad.copy_(total)
     b.grad.copy_(total)
     p0 = b.params.clone()
+    trained0 = _trained(b)
     # announce: acez_train_update_next -- the schedule wave that closes the step sits in the SAME launch as the optimiser workgroup that
     # raises the local fault word from the all-reduced slot; it must decide on the slot itself (no iteration counted on either rank)
     nxt = torch.from_numpy(rng.permutation(prob["features"].shape[0])[:2048].astype(np.int64)).cuda() if announce else None
@@ -299,12 +347,16 @@ def test_fault_word_travels_in_the_gradient_bucket(announce, diag_lib):
     b.update(nxt)
     torch.cuda.synchronize()
     assert torch.equal(b.params, p0) and torch.equal(a.params, p0)
+    assert _trained_equal(a, trained0) and _trained_equal(b, trained0)
     if announce:     # a step issued before the host knows (with the announced rows): a no-op on both
         a.backward(nxt); b.backward(nxt)
         torch.cuda.synchronize()
         assert torch.equal(b.params, p0) and torch.equal(a.params, p0)
-    assert a.state()["iteration"] == 0 and b.state()["iteration"] == 0
+        assert _trained_equal(a, trained0) and _trained_equal(b, trained0)
+    assert a.state()["iteration"] == warm and b.state()["iteration"] == warm
     assert a.seq_status()["faults"] == 1 and b.seq_status()["faults"] == 1 and not b.seq_status()["enabled"]
+    helpers.assert_snapshots_equal(helpers.trainer_snapshot(a), snap0, (config, "the rank that abandoned"))
+    helpers.assert_snapshots_equal(helpers.trainer_snapshot(b), snap0, (config, "the rank that learnt of it from the bucket"))
 
 
 @pytest.mark.parametrize("mask", ["", "0:0-223", "0:0-7,16-255", "0:0-31,64-255"])

@@ -98,8 +98,12 @@ def test_product_library_fused_step_equals_backward_plus_update(name, n, dtype):
     assert torch.equal(fused.get_scene_coordinates(f), split.get_scene_coordinates(f))
 
 
-@pytest.mark.parametrize("fault_mod,dtype,announce", [(0, "bf16", True), (3, "bf16", True), (3, "fp16", True), (3, "bf16", False), (0, "fp16", False)])
-def test_expired_exchange_poll_finishes_the_step_in_the_fall_back(fault_mod, dtype, announce, diag_lib):
+# calib: with calibration refinement -- the one refinement this flow accepts (pose refinement takes the optimiser out of the weight-gradient
+# launch, wgrad_opt_usable). The cases without it keep the ids they had.
+@pytest.mark.parametrize("fault_mod,dtype,announce,calib", [
+    pytest.param(*c, False, id="-".join(str(x) for x in c)) for c in ((0, "bf16", True), (3, "bf16", True), (3, "fp16", True), (3, "bf16", False), (0, "fp16", False))
+] + [pytest.param(*c, True, id="-".join(str(x) for x in c) + "-calib") for c in ((0, "bf16", True), (3, "fp16", True), (3, "bf16", False))])
+def test_expired_exchange_poll_finishes_the_step_in_the_fall_back(fault_mod, dtype, announce, calib, diag_lib):
     """Fault injection (ACEZ_WGO_FAULT_AT, ACEZ_WGO_FAULT_MOD): in one launch every workgroup -- or every third -- waits for a partner
     count that never comes: what a tile whose two slabs sit on different XCDs looks like. No hang; no weight tile is stored from an
     incomplete sum. The small parameters and the schedule wave of that launch read the fault word long before it is raised, so the step
@@ -108,7 +112,9 @@ def test_expired_exchange_poll_finishes_the_step_in_the_fall_back(fault_mod, dty
     the step's own AdamW scalars to exactly the rows whose wave gave up. After the state read the trainer is, bit for bit, the two-launch
     flow's trainer after the same steps: a step is atomic again (ace_trainer.py:620-640).
     announce = False: the faulting step and the steps queued behind it do NOT announce their successors, so their gathers are
-    the plain gather launches into R[0] -- the faulted step's layer-0 operand -- which must hold while the fault word is up as well."""
+    the plain gather launches into R[0] -- the faulted step's layer-0 operand -- which must hold while the fault word is up as well.
+    Behind the fall-back and at the end the WHOLE trained state is compared (helpers.trainer_snapshot: 16-bit copies, calibration scalar,
+    every field of the schedule state, the log), not three tensors."""
     prob = _big_problem(n_images=8, patches_per_view=256)
     if dtype == "fp16":
         prob = dict(prob)
@@ -118,7 +124,8 @@ def test_expired_exchange_poll_finishes_the_step_in_the_fall_back(fault_mod, dty
         from acezero_amd.head import HeadTrainer
         from acezero_amd import synth
         tr = HeadTrainer(prob["mean"], num_head_blocks=1, use_homogeneous=True, max_batch=2048, loss_type="tanh", schedule="1cyclepoly",
-                         iterations=50, lr_min=1e-4, lr_max=6e-4, warmup_iterations=10, cooldown_iterations=10, dtype=dtype)
+                         iterations=50, lr_min=1e-4, lr_max=6e-4, warmup_iterations=10, cooldown_iterations=10, dtype=dtype,
+                         refine_calibration=calib, focal_init=float(prob["focal"]))
         tr.load_flat(torch.from_numpy(synth.init_head_params(11, num_head_blocks=1, use_homogeneous=True)))
         tr.set_buffer(prob["features"], prob["target_px"], prob["view_idx"], prob["view_aug_inv"], prob["view_K"], prob["view_Kinv"],
                       prob["view_image"], prob["image_pose_inv"])
@@ -169,6 +176,9 @@ def test_expired_exchange_poll_finishes_the_step_in_the_fall_back(fault_mod, dty
     torch.cuda.synchronize()
     assert st["iteration"] == 2 and st == ref.state()
     assert torch.equal(new.params, ref.params) and torch.equal(new.adam_m, ref.adam_m) and torch.equal(new.adam_v, ref.adam_v)
+    finished = helpers.trainer_snapshot(new)
+    helpers.assert_snapshots_equal(finished, helpers.trainer_snapshot(ref), "the step the fall-back finished")
+    assert not calib or st["focal_scale"] != 1.0   # (the calibration scalar is trained here)
     f = torch.from_numpy(prob["features"][:777]).cuda()
     assert torch.equal(new.get_scene_coordinates(f), ref.get_scene_coordinates(f))   # the 16-bit copies W / W^T of the finished rows too
     for b in batches[4:]:         # the abandoned batches 2 and 3 were not counted; training goes on, on the two-launch flow
@@ -176,3 +186,6 @@ def test_expired_exchange_poll_finishes_the_step_in_the_fall_back(fault_mod, dty
     torch.cuda.synchronize()
     assert torch.equal(new.params, ref.params) and torch.equal(new.adam_m, ref.adam_m) and torch.equal(new.adam_v, ref.adam_v)
     assert new.state() == ref.state() and new.state()["iteration"] == 5
+    end = helpers.trainer_snapshot(new)
+    helpers.assert_snapshots_equal(end, helpers.trainer_snapshot(ref), "behind the fall-back")
+    assert {"params", "w16", "iteration", "log"} | ({"focal_scale"} if calib else set()) <= set(helpers.snapshot_differences(end, finished))
