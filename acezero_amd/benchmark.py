@@ -255,7 +255,7 @@ def reproject_inputs(transforms_json, network, encoder_path, image_resolution=48
     numpy, targets [T,oh,ow,3] u8, info) with the train frames' point cloud of `network` (head checkpoint) as sources and the test
     frames' cell means as targets, poses and focals as the file states them."""
     import torch
-    from .cli import _default_encoder_path, load_frames
+    from .images import _default_encoder_path, load_frames
     from .session import ReconstructionSession, default_options
     with open(transforms_json) as f:
         tr = json.load(f)

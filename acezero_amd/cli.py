@@ -21,19 +21,24 @@ from pathlib import Path
 import numpy as np
 
 from . import DEFAULT_DTYPE
-from .formats import (match_poses, read_ace_pose_file, read_crop_file, read_depth_png, read_ply_mesh, read_ply_points, read_ply_vertices,
-                      write_depth_png, write_ply, write_pose_line)
+from .formats import (_strtobool, focal_at_height, read_ace_pose_file, read_crop_file, read_depth_png, read_ply_mesh,
+                      read_ply_points, read_ply_vertices, read_posed_images, write_depth_png, write_ply, write_pose_line)
+# the host loaders live in images.py; their names stay in this namespace (cli.load_frames, ...) for callers and tests
+from .images import (_default_encoder_path, check_calibration_focals, check_single_focal, depth_map_at_cells, focals_in_original_units,
+                     frame_shapes, frame_size_classes, initial_focals, load_depth_maps, load_frames, load_session_frames, session_frames)
 
 _logger = logging.getLogger("acezero_amd")
 
 
-def _strtobool(x):
-    v = str(x).lower()
-    if v in ("y", "yes", "t", "true", "on", "1"):
-        return True
-    if v in ("n", "no", "f", "false", "off", "0"):
-        return False
-    raise argparse.ArgumentTypeError(f"invalid truth value {x!r}")
+def _require_gpu(name, why):
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit(f"{name}.py needs a GPU: {why}, there is no CPU path")
+
+
+def _require_ply(path):
+    if not str(path).endswith(".ply"):
+        raise SystemExit("output file format not supported: use .ply")
 
 
 # (flags, type, default, choices, help) -- train_ace.py:21-228
@@ -287,10 +292,6 @@ def export_point_cloud_parser():
     return p
 
 
-def _default_encoder_path(path):
-    return Path(__file__).resolve().parent.parent / "ace_encoder_pretrained.pt" if str(path) == "<path>" else Path(path)
-
-
 # ------------------------------------------------------------------------------------------------------- feature buffer
 def save_feature_buffer(path, prob, image_files=None, with_depth_targets=False):
     """Write a training buffer (dict in the layout of acezero_amd.synth.make_training_problem) as .npz."""
@@ -422,13 +423,42 @@ def _train_visualizer(opt, frame_rgb=None):
                       existing_state=opt.use_existing_vis_buffer, frame_rgb=frame_rgb)
 
 
-def _register_visualizer(opt):
-    """register_mapping.py --render_visualization: continues from `<network stem>_mapping.pkl` in --render_target_path."""
+def _register_visualizer(opt, n):
+    """register_mapping.py --render_visualization (None without it): continues from `<network stem>_mapping.pkl` in
+    --render_target_path, set up for n registration frames."""
+    if not opt.render_visualization:
+        return None
     from .render import Visualizer
-    return Visualizer(opt.render_target_path, opt.render_flipped_portrait, opt.render_map_depth_filter,
-                      reloc_conf_threshold=opt.render_pose_conf_threshold, confidence_threshold=opt.confidence_threshold,
-                      state_file_name=Path(opt.network).stem + "_mapping.pkl", marker_size=opt.render_marker_size,
-                      camera_z_offset=opt.render_camera_z_offset)
+    vis = Visualizer(opt.render_target_path, opt.render_flipped_portrait, opt.render_map_depth_filter,
+                     reloc_conf_threshold=opt.render_pose_conf_threshold, confidence_threshold=opt.confidence_threshold,
+                     state_file_name=Path(opt.network).stem + "_mapping.pkl", marker_size=opt.render_marker_size,
+                     camera_z_offset=opt.render_camera_z_offset)
+    vis.setup_reloc(n)
+    return vis
+
+
+def _save_reloc_state(opt, vis):
+    if vis is not None:
+        vis.save_reloc_state(os.path.join(str(opt.render_target_path), Path(opt.network).stem + "_register.pkl"))
+
+
+def _session_pose_file(opt):
+    return Path(opt.network).parent / f"poses_{opt.session}.txt"
+
+
+def _register_session(opt, enc_sd, frames, fscale, depth_files=None):
+    """The session a registration from images runs in: frames of one size and their resize factor, register_mapping.py's flags as
+    session options (the external focal in resized pixels) and, for RGB-D registration, the frames' depth files read at the cells."""
+    import torch
+    from .session import ReconstructionSession
+    depth = None
+    if depth_files is not None:
+        H, W = frames.shape[2:]
+        depth = torch.from_numpy(np.stack([depth_map_at_cells(f, H, W) for f in depth_files]))
+    so = _session_options(opt, use_external_focal_length=opt.use_external_focal_length * fscale if opt.use_external_focal_length > 0 else -1.0,
+                          ransac_iterations=opt.hypotheses, ransac_threshold=opt.threshold, register_seed=opt.base_seed, use_aug=False,
+                          registration_confidence=opt.confidence_threshold)
+    return ReconstructionSession(enc_sd, frames, opt=so, depth=depth)
 
 
 def _finalize_mapping_visualization(opt, vis, tr, buf, n, max_points=1_000_000):
@@ -473,17 +503,14 @@ def _train_from_images(opt):
     import glob
     import torch
     from .session import ReconstructionSession
-    rgb = None
-    _, load_session_frames = _frame_loaders(opt)
+    focal_flags = dict(external=opt.use_external_focal_length, heuristic=opt.use_heuristic_focal_length, return_rgb=opt.render_visualization)
     if opt.use_ace_pose_file is not None:
         files, poses, focals = read_ace_pose_file(opt.use_ace_pose_file, opt.ace_pose_file_conf_threshold)
-        files, frames, fscale, *rgb = load_session_frames(None, opt.image_resolution, files=files, return_rgb=opt.render_visualization)
+        s = session_frames(_frame_loaders(opt)[1], None, opt.image_resolution, files=files, file_focals=focals, **focal_flags)
     else:
-        files, frames, fscale, *rgb = load_session_frames(opt.rgb_files, opt.image_resolution, return_rgb=opt.render_visualization)
-        focals = []
+        s = session_frames(_frame_loaders(opt)[1], opt.rgb_files, opt.image_resolution, **focal_flags)
         poses = np.stack([np.loadtxt(f) for f in sorted(glob.glob(opt.pose_files))]) if opt.pose_files is not None else None   # dataset_io.load_pose
-    rgb = rgb[0] if rgb else None
-    mixed = not torch.is_tensor(frames)                                  # a folder of several frame sizes: its size classes
+    files = s.files
     ids = list(range(len(files)))
     if opt.use_pose_seed >= 0:                                           # dataset.py:110-124
         ids, poses = [int(opt.use_pose_seed * len(files))], np.eye(4)[None]
@@ -491,36 +518,20 @@ def _train_from_images(opt):
             raise SystemExit("--use_pose_seed needs --depth_files here (the reference's ZoeDepth fallback is a network download)")
     elif poses is None or len(poses) != len(files):
         raise SystemExit("need one pose per image: --use_ace_pose_file, --pose_files or --use_pose_seed")
-    frame_focals = None
-    if mixed:                                                            # every frame's focal, converted with its own factor
-        frame_focals = initial_focals(frames, fscale, external=opt.use_external_focal_length, heuristic=opt.use_heuristic_focal_length,
-                                      file_focals=focals)
-        if opt.refine_calibration:
-            check_calibration_focals(frame_focals[ids])                  # before any frame is encoded
-        focal = float(frame_focals[0])
-    else:
-        H, W = frames.shape[2:]
-        if opt.use_external_focal_length is not None:
-            focal = opt.use_external_focal_length * fscale
-        elif opt.use_heuristic_focal_length or not focals:
-            focal = math.sqrt(W ** 2 + H ** 2) * 0.7
-        else:
-            assert np.allclose(focals, focals[0]), "a single focal length is supported"
-            focal = focals[0] * fscale
-    hw = frame_shapes(frames, len(files)) if mixed else frames.shape[2:]
-    depth = load_depth_maps(opt.depth_files, len(files), hw) if opt.depth_files is not None else None
-    so = _session_options(opt, cooldown_iterations=opt.learning_rate_cooldown_iterations, use_external_focal_length=focal,
+    if s.mixed and opt.refine_calibration:
+        check_calibration_focals(s.frame_focals[ids])                    # the frames that are mapped; before any frame is encoded
+    depth = load_depth_maps(opt.depth_files, len(files), s.hw) if opt.depth_files is not None else None
+    so = _session_options(opt, cooldown_iterations=opt.learning_rate_cooldown_iterations, use_external_focal_length=s.focal,
                           cooldown_threshold=opt.learning_rate_cooldown_trigger_percent_threshold)
-    ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, opt=so, depth=depth,
-                                focals=frame_focals)
-    m = ses.map(ids, torch.from_numpy(np.asarray(poses, np.float64)), ses.focal0 if mixed else focal, iterations=opt.iterations, loss_type=opt.repro_loss_type,
+    ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), s.frames, opt=so, depth=depth,
+                                focals=s.frame_focals)
+    m = ses.map(ids, torch.from_numpy(np.asarray(poses, np.float64)), ses.focal0 if s.mixed else s.focal, iterations=opt.iterations, loss_type=opt.repro_loss_type,
                 schedule=opt.learning_rate_schedule, lr_max=opt.learning_rate_max, refinement=opt.pose_refinement,
                 pose_wait=opt.pose_refinement_wait, refine_calibration=opt.refine_calibration,
                 load_weights=torch.load(opt.load_weights, map_location="cpu") if opt.load_weights is not None else None,
                 with_depth=opt.use_pose_seed >= 0 or opt.depth_files is not None, tag=opt.output_map_file.stem,
-                visualizer=_train_visualizer(opt, rgb) if opt.render_visualization else None)
-    # each frame's focal back in its own original units
-    f_out = focals_in_original_units(m["focal"], ses.frel, fscale) if mixed else np.full(len(files), m["focal"] / fscale)
+                visualizer=_train_visualizer(opt, s.rgb) if opt.render_visualization else None)
+    f_out = s.original_focals(m["focal"], ses.frel)                      # each frame's focal back in its own original units
     opt.output_map_file.parent.mkdir(parents=True, exist_ok=True)
     torch.save(m["head"], opt.output_map_file)                           # save_model (ace_trainer.py:681-694)
     pose_file = opt.output_map_file.parent / f"poses_{opt.output_map_file.stem}_preliminary.txt"
@@ -532,39 +543,16 @@ def _train_from_images(opt):
     return 0
 
 
-def frame_size_classes(rgb_glob):
-    """The sorted file list grouped by image size (header reads only): {(W, H): [positions in the sorted list]}. One size means
-    one resize factor and one resized shape for load_frames. The reference's batch-size-1 loaders take any mix (dataset.py:278-417)."""
-    import glob
-    from PIL import Image
-    files = sorted(glob.glob(rgb_glob))
-    if not files:
-        raise SystemExit(f"no files match {rgb_glob!r}")
-    classes = {}
-    for i, f in enumerate(files):
-        with Image.open(f) as im:
-            classes.setdefault(im.size, []).append(i)
-    return files, classes
-
-
 def _register_mixed_sizes(opt, files, classes, depth_files=None):
     """register_mapping.py on a folder whose frames have several sizes: registration is independent per frame, so every size class
     gets its own encoder / RANSAC context (one ReconstructionSession each); --max_estimates draws its seeded subset over the whole
     list, the random streams are keyed by the position in the whole list, the pose file keeps the list's order. depth_files (one per
     file, same order): RGB-D registration."""
     import torch
-    from .session import ReconstructionSession
-    n = len(files)
-    if opt.max_estimates <= 0 or opt.max_estimates >= n:
-        chosen = np.arange(n)
-    else:
-        chosen = np.sort(torch.randperm(n, generator=torch.Generator().manual_seed(int(opt.base_seed)))[:opt.max_estimates].numpy())
-    keep = set(int(i) for i in chosen)
+    from .session import estimate_subset
+    keep = set(int(i) for i in estimate_subset(len(files), opt.max_estimates, opt.base_seed))
     load_frames, _ = _frame_loaders(opt)
-    vis = None
-    if opt.render_visualization:                                         # one video over all size classes, in size-class order
-        vis = _register_visualizer(opt)
-        vis.setup_reloc(len(keep))
+    vis = _register_visualizer(opt, len(keep))                              # one video over all size classes, in size-class order
     enc_sd = torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu")
     head_sd = torch.load(opt.network, map_location="cpu")
     rows = {}
@@ -574,27 +562,19 @@ def _register_mixed_sizes(opt, files, classes, depth_files=None):
             continue
         sub_files, frames, fscale, *rgb = load_frames(None, opt.image_resolution, files=[files[i] for i in pos],
                                                       return_rgb=opt.render_visualization)
-        so = _session_options(opt, use_external_focal_length=opt.use_external_focal_length * fscale if opt.use_external_focal_length > 0 else -1.0,
-                              ransac_iterations=opt.hypotheses, ransac_threshold=opt.threshold, register_seed=opt.base_seed, use_aug=False,
-                              registration_confidence=opt.confidence_threshold)
-        depth = None
-        if depth_files is not None:
-            H, W = frames.shape[2:]
-            depth = torch.from_numpy(np.stack([depth_map_at_cells(depth_files[i], H, W) for i in pos]))
-        ses = ReconstructionSession(enc_sd, frames, opt=so, depth=depth)
+        ses = _register_session(opt, enc_sd, frames, fscale, None if depth_files is None else [depth_files[i] for i in pos])
         poses, inl = ses.register(head_sd, ses.focal0, max_tries=opt.hypotheses_max_tries, rng_ids=pos, tag=f"register {w}x{h}",
-                                  visualizer=vis, images=rgb[0] if rgb else None, use_depth=depth is not None)
+                                  visualizer=vis, images=rgb[0] if rgb else None, use_depth=depth_files is not None)
         for k, i in enumerate(pos):
             rows[i] = (poses[k], int(inl[k]), ses.focal0 / fscale)
         del ses
-    out = Path(opt.network).parent / f"poses_{opt.session}.txt"
+    out = _session_pose_file(opt)
     with open(out, "w") as f:
         for i in sorted(rows):
             p, c, focal = rows[i]
             write_pose_line(f, files[i], np.linalg.inv(np.asarray(p, np.float64)), c, float(focal))
     _logger.info(f"Registered {len(rows)} images of {len(classes)} sizes -> {out}")
-    if vis is not None:
-        vis.save_reloc_state(os.path.join(str(opt.render_target_path), Path(opt.network).stem + "_register.pkl"))
+    _save_reloc_state(opt, vis)
     return 0
 
 
@@ -602,31 +582,20 @@ def _register_from_images(opt, depth_files=None):
     """register_mapping.py on image files: encoder -> head -> RANSAC for every frame (register_mapping.py:201-276). depth_files (one
     per image, in the sorted order of the images): RGB-D registration."""
     import torch
-    from .session import ReconstructionSession, write_pose_file
+    from .session import write_pose_file
     all_files, classes = frame_size_classes(opt.rgb_files)
     if len(classes) > 1:
         return _register_mixed_sizes(opt, all_files, classes, depth_files)
     load_frames, _ = _frame_loaders(opt)
     files, frames, fscale, *rgb = load_frames(opt.rgb_files, opt.image_resolution, return_rgb=opt.render_visualization)
-    depth = None
-    if depth_files is not None:
-        H, W = frames.shape[2:]
-        depth = torch.from_numpy(np.stack([depth_map_at_cells(f, H, W) for f in depth_files]))
-    so = _session_options(opt, use_external_focal_length=opt.use_external_focal_length * fscale if opt.use_external_focal_length > 0 else -1.0,
-                          ransac_iterations=opt.hypotheses, ransac_threshold=opt.threshold, register_seed=opt.base_seed, use_aug=False,
-                          registration_confidence=opt.confidence_threshold)
-    ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, opt=so, depth=depth)
-    vis = None
-    if opt.render_visualization:
-        vis = _register_visualizer(opt)
-        vis.setup_reloc(len(files) if opt.max_estimates <= 0 else min(opt.max_estimates, len(files)))
+    ses = _register_session(opt, torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, fscale, depth_files)
+    vis = _register_visualizer(opt, len(files) if opt.max_estimates <= 0 else min(opt.max_estimates, len(files)))
     poses, inl = ses.register(torch.load(opt.network, map_location="cpu"), ses.focal0, max_estimates=opt.max_estimates, max_tries=opt.hypotheses_max_tries,
-                              visualizer=vis, images=rgb[0] if rgb else None, use_depth=depth is not None)
-    out = Path(opt.network).parent / f"poses_{opt.session}.txt"
+                              visualizer=vis, images=rgb[0] if rgb else None, use_depth=depth_files is not None)
+    out = _session_pose_file(opt)
     write_pose_file(out, [files[i] for i in ses.registered_ids], poses, inl, ses.focal0 / fscale)
     _logger.info(f"Registered {len(poses)} images -> {out}")
-    if vis is not None:
-        vis.save_reloc_state(os.path.join(str(opt.render_target_path), Path(opt.network).stem + "_register.pkl"))
+    _save_reloc_state(opt, vis)
     return 0
 
 
@@ -635,6 +604,7 @@ def register_main(argv=None):
     import torch
     from . import dsacstar
     from .head import HeadTrainer
+    from .session import estimate_subset
     opt = with_ingest_flag(register_parser()).parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     if opt.feature_file is None:
@@ -642,12 +612,7 @@ def register_main(argv=None):
     torch.manual_seed(opt.base_seed)
     data = np.load(opt.feature_file, allow_pickle=False)
     files = [str(x) for x in data["image_files"]]
-    # --max_estimates: a seeded random subset, as the reference's DataLoader(shuffle=True) under torch.manual_seed(base_seed) gives
-    # (register_mapping.py:122-147,256), in file order -- not the first n frames
-    if opt.max_estimates <= 0 or opt.max_estimates >= len(files):
-        ids = np.arange(len(files))
-    else:
-        ids = np.sort(torch.randperm(len(files), generator=torch.Generator().manual_seed(int(opt.base_seed)))[:opt.max_estimates].numpy())
+    ids = estimate_subset(len(files), opt.max_estimates, opt.base_seed)   # a seeded random subset in file order, not the first n frames
     n = len(ids)
     t0 = time.time()
     if "scene_coordinates" in data.files:
@@ -669,21 +634,19 @@ def register_main(argv=None):
     poses, inl, _ = dsacstar.register_batch(sc, [(focal[i], ppx[i], ppy[i]) for i in ids], prm, opt.base_seed, [int(i) for i in ids],
                                             want_masks=False)
     poses, inl = poses.cpu().numpy(), inl.cpu().numpy()
-    out_dir = Path(opt.network).parent
-    pose_log_file = out_dir / f"poses_{opt.session}.txt"
+    pose_log_file = _session_pose_file(opt)
     with open(pose_log_file, "w") as f:
         for k, i in enumerate(ids):
             _logger.info(f"Frame: {files[i]}, Confidence: {int(inl[k])}")
             write_pose_line(f, files[i], np.linalg.inv(poses[k].astype(np.float64)), int(inl[k]), float(focal[i]))   # :261-276
     dt = time.time() - t0
     _logger.info(f"Registered {n} images in {dt:.2f}s ({n / max(dt, 1e-9):.0f} images/s) -> {pose_log_file}")
-    if opt.render_visualization:
-        vis = _register_visualizer(opt)
-        vis.setup_reloc(n)
+    vis = _register_visualizer(opt, n)
+    if vis is not None:
         _logger.info("--feature_file holds no pixels: the registration frames show the frustums without their images")
         for k in range(n):
             vis.render_reloc_frame(poses[k].astype(np.float64), int(inl[k]))
-        vis.save_reloc_state(os.path.join(str(opt.render_target_path), Path(opt.network).stem + "_register.pkl"))
+        _save_reloc_state(opt, vis)
     return 0
 
 
@@ -708,142 +671,6 @@ def register_rgbd_main(argv=None):
 
 
 # --------------------------------------------------------------------------------------------------------- ace_zero
-def load_frames(rgb_glob, image_resolution=480, files=None, return_rgb=False, size_classes=False):
-    """Minimal stand-in for CamLocDataset's image path without augmentation (dataset.py:189-195,227-237,146-160): decode,
-    resize so that the short side is `image_resolution` (PIL bilinear, as torchvision does for PIL images), grey, normalise.
-    Focal lengths on the command line and in pose files refer to the ORIGINAL image size and are multiplied by the frame's resize
-    factor (dataset.py:289-290). Every size class (frames of one resized shape) passes check_frame_size before any of its frames
-    is decoded.
-
-    Default: all frames must have one size. Returns (files, float32 [n,1,H,W], resize factor[, uint8 rgb [n,H,W,3]]).
-    size_classes=True: any mix of sizes (the reference's batch-size-1 loaders take one, dataset.py:278-417). Returns (files,
-    classes, factors[, rgb]): classes = [(positions in the sorted file list, float32 [k,1,H_c,W_c]), ...] in the order of their
-    first frame, factors = float64 [n] resize factor of every frame, rgb = a list of n uint8 [H_i,W_i,3] arrays -- what
-    ReconstructionSession takes for a folder of mixed sizes."""
-    import glob
-    import torch
-    from PIL import Image
-    from .session import check_frame_size
-    if files is None:
-        files = sorted(glob.glob(rgb_glob))                             # dataset_io.get_files_from_glob sorts
-    if not files:
-        raise SystemExit(f"no files match {rgb_glob!r}")
-    frames, factors, rgbs, shapes = [], [], [], {}
-    for i, f in enumerate(files):
-        im = Image.open(f)
-        w, h = im.size
-        sc = image_resolution / min(w, h)
-        nw, nh = (image_resolution, int(h * sc)) if w <= h else (int(w * sc), image_resolution)
-        if (nh, nw) not in shapes:
-            if shapes and not size_classes:
-                size = next(iter(shapes))
-                raise SystemExit(f"{f}: resized frame is {(nh, nw)}, the first one {size}: frames of ONE size were expected (load_frames("
-                                 "size_classes=True) takes a mix; the entry points do)")
-            try:
-                check_frame_size(nh, nw)                                 # before the class's frames are decoded
-            except RuntimeError as e:
-                raise SystemExit(str(e))
-            shapes[(nh, nw)] = []
-        shapes[(nh, nw)].append(i)
-        small = im.convert("RGB").resize((nw, nh), Image.BILINEAR)
-        g = np.asarray(small.convert("L"), np.float32) / 255.0
-        if return_rgb:
-            rgbs.append(np.asarray(small, np.uint8))
-        frames.append((g - 0.4) / 0.25)
-        factors.append(sc)
-    if not size_classes:
-        out = (files, torch.from_numpy(np.stack(frames)[:, None]), factors[-1])
-        return out + (np.stack(rgbs),) if return_rgb else out
-    classes = [(np.array(pos, np.int64), torch.from_numpy(np.stack([frames[i] for i in pos])[:, None])) for pos in shapes.values()]
-    out = (files, classes, np.array(factors, np.float64))
-    return out + (rgbs,) if return_rgb else out
-
-
-def load_session_frames(rgb_glob, image_resolution=480, files=None, return_rgb=False):
-    """load_frames for the entry points: a folder of one size comes back exactly as load_frames returns it (files, [n,1,H,W],
-    resize factor[, rgb [n,H,W,3]]), a folder of mixed sizes as load_frames(size_classes=True) returns it (files, classes, per-frame
-    factors[, per-frame rgb list])."""
-    out = load_frames(rgb_glob, image_resolution, files=files, return_rgb=return_rgb, size_classes=True)
-    if len(out[1]) > 1:
-        return out
-    files, classes, factors = out[:3]
-    one = (files, classes[0][1], float(factors[-1]))
-    return one + (np.stack(out[3]),) if return_rgb else one
-
-
-def initial_focals(frames, factors, external=None, heuristic=False, file_focals=None):
-    """Per-frame initial focal lengths in resized pixels of a folder of size classes (`frames`, `factors` as load_frames(size_classes=True)
-    returns them): an external focal or the pose file's focals (original-image pixels) times the frame's factor (dataset.py:289-290),
-    else 70% of the resized frame's diagonal (dataset.py:269-274)."""
-    n = len(factors)
-    out = np.zeros(n, np.float64)
-    for pos, t in frames:
-        h, w = t.shape[2:]
-        for i in pos:
-            if external is not None and external > 0:
-                out[i] = external * factors[i]
-            elif heuristic or file_focals is None or not len(file_focals):
-                out[i] = math.sqrt(w ** 2 + h ** 2) * 0.7
-            else:
-                out[i] = file_focals[i] * factors[i]
-    return out
-
-
-def focals_in_original_units(focal, frel, factors):
-    """Per-frame focal lengths for pose files, in each frame's ORIGINAL-image pixels: the session's nominal focal x the frame's ratio
-    (ReconstructionSession.frel), divided by the frame's resize factor (dataset.py:289-290 the other way round)."""
-    return focal * np.asarray(frel, np.float64) / np.asarray(factors, np.float64)
-
-
-def check_single_focal(focals_original):
-    """ace_zero.py:301-302 hands ONE focal (original-image pixels) from round to round and asserts that every frame has it."""
-    if not np.allclose(focals_original, focals_original[0]):
-        raise SystemExit("ace_zero.py supports a single focal length (ace_zero.py:301-302): the frames' focal lengths differ in original-image "
-                         "pixels (pass --use_external_focal_length, or map the frames of each camera separately)")
-
-
-def check_calibration_focals(focals):
-    """refine_calibration.py:14-15: calibration refinement learns ONE focal; every frame must start from the same one."""
-    if not np.allclose(focals, focals[0]):
-        raise SystemExit("All images must have the same focal length for calibration refinement")
-
-
-def load_depth_maps(depth_glob, n, frame_hw):
-    """--depth_files (dataset.py:299-304,333,359): 16-bit millimetres -> metres, nearest resize to the frame, value at the
-    feature-map pixel centres (offset 4, stride 8). frame_hw = (H, W) of every frame: float32 [n, ceil(H/8), ceil(W/8)]; or a list
-    of n per-frame (H_i, W_i) (a folder of mixed sizes): a list of n float32 [ceil(H_i/8), ceil(W_i/8)] maps."""
-    import glob
-    import torch
-    files = sorted(glob.glob(depth_glob))
-    if len(files) != n:
-        raise SystemExit(f"{len(files)} depth files for {n} images")
-    one = depth_map_at_cells
-    if isinstance(frame_hw, list):
-        return [torch.from_numpy(one(f, int(h), int(w))) for f, (h, w) in zip(files, frame_hw)]
-    H, W = frame_hw
-    return torch.from_numpy(np.stack([one(f, H, W) for f in files]) if n else np.zeros((0, (H + 7) // 8, (W + 7) // 8), np.float32))
-
-
-def depth_map_at_cells(path, H, W):
-    """One depth file (16-bit millimetres) -> metres, nearest resize to the H x W frame, value at the feature-map pixel centres
-    (offset 4, stride 8): float32 [ceil(H/8), ceil(W/8)]."""
-    from PIL import Image
-    d = np.asarray(Image.open(path).resize((W, H), Image.NEAREST), np.float32) / 1000.0
-    sub = d[4::8, 4::8]
-    out = np.zeros(((H + 7) // 8, (W + 7) // 8), np.float32)
-    out[:sub.shape[0], :sub.shape[1]] = sub
-    return out
-
-
-def frame_shapes(frames, n):
-    """(H, W) of every frame of a folder of size classes."""
-    hw = [None] * n
-    for pos, t in frames:
-        for i in pos:
-            hw[i] = tuple(t.shape[2:])
-    return hw
-
-
 def ace_zero_main(argv=None):
     import torch
     from .session import ReconstructionSession, default_options, write_pose_file
@@ -867,29 +694,27 @@ def ace_zero_main(argv=None):
         raise SystemExit("--rgbd True needs --depth_files matching one depth map (16 bit, millimetres) per image")
     logging.basicConfig(level=logging.INFO if rank == 0 else logging.WARNING)
     opt.results_folder.mkdir(parents=True, exist_ok=True)
-    files, frames, fscale, rgb = _frame_loaders(opt)[1](opt.rgb_files, opt.image_resolution, return_rgb=True)
-    mixed = not torch.is_tensor(frames)                                  # a folder of several frame sizes: its size classes
-    frame_focals = None
-    if mixed:
-        frame_focals = initial_focals(frames, fscale, external=opt.use_external_focal_length)
+    external = opt.use_external_focal_length if opt.use_external_focal_length > 0 else None
+    s = session_frames(_frame_loaders(opt)[1], opt.rgb_files, opt.image_resolution, external=external, return_rgb=True)
+    files, rgb = s.files, s.rgb
+    if s.mixed:
         if opt.refine_calibration:
-            check_calibration_focals(frame_focals)                       # before any frame is encoded
-        check_single_focal(frame_focals / fscale)
-    hw = frame_shapes(frames, len(files)) if mixed else frames.shape[2:]
-    depth = load_depth_maps(opt.depth_files, len(files), hw) if opt.depth_files is not None else None
+            check_calibration_focals(s.frame_focals)                     # before any frame is encoded
+        check_single_focal(s.frame_focals / s.factors)
+    depth = load_depth_maps(opt.depth_files, len(files), s.hw) if opt.depth_files is not None else None
     if depth is None and opt.seed_network is None:
         raise SystemExit("ace_zero.py (MI355X): seeds need --depth_files (or --seed_network); the reference's ZoeDepth fallback is a "
                          "network download and not part of this package")
     known = vars(default_options())
     over = {k: v for k, v in vars(opt).items() if k in known and k != "seed_network"}
-    if opt.use_external_focal_length > 0:
-        over["use_external_focal_length"] = float(frame_focals[0]) if mixed else opt.use_external_focal_length * fscale
+    if external is not None:
+        over["use_external_focal_length"] = s.focal
     if opt.seed_network is not None:
         over["seed_network"] = torch.load(opt.seed_network, map_location="cpu")
-    ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, opt=default_options(**over), depth=depth,
-                                focals=frame_focals)
+    ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), s.frames, opt=default_options(**over), depth=depth,
+                                focals=s.frame_focals)
     # pose files: every frame's focal in its own original units (one focal, the session's nominal one, goes from round to round)
-    orig = (lambda f: focals_in_original_units(f, ses.frel, fscale)) if mixed else (lambda f: f / fscale)
+    orig = lambda f: s.original_focals(f, ses.frel)
     render_dir = opt.results_folder / "renderings"                       # ace_zero_util.get_render_path
     render = None
     if opt.render_visualization:
@@ -968,21 +793,14 @@ def export_point_cloud_main(argv=None):
         files, c2w, focals = read_ace_pose_file(opt.pose_file, opt.confidence_threshold)
         if not files:
             raise SystemExit("no pose above the confidence threshold")
-        files, frames, fscale, rgb = _frame_loaders(opt)[1](None, opt.image_resolution, files=files, return_rgb=True)
-        frame_focals = None
-        if torch.is_tensor(frames):
-            assert np.allclose(focals, focals[0]), "a single focal length is supported"
-            f0 = focals[0] * fscale
-        else:                                                            # mixed sizes: every frame's focal with its own factor
-            frame_focals = initial_focals(frames, fscale, file_focals=focals)
-            f0 = float(frame_focals[0])
-        so = default_options(use_external_focal_length=f0, use_aug=False, registration_confidence=opt.confidence_threshold,
+        s = session_frames(_frame_loaders(opt)[1], None, opt.image_resolution, files=files, file_focals=focals, return_rgb=True)
+        so = default_options(use_external_focal_length=s.focal, use_aug=False, registration_confidence=opt.confidence_threshold,
                              compute_dtype=opt.compute_dtype)
-        ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), frames, opt=so, focals=frame_focals)
-        conf = np.full(len(files), np.inf)
+        ses = ReconstructionSession(torch.load(_default_encoder_path(opt.encoder_path), map_location="cpu"), s.frames, opt=so, focals=s.frame_focals)
+        conf = np.full(len(s.files), np.inf)
         xyz, src, sel = ses.point_cloud(torch.load(opt.network, map_location="cpu"), c2w, conf, ses.focal0, dense=opt.dense_point_cloud,
                                         filter_depth=100, opengl=opt.convention == "opengl")
-        clr = point_colours(ses, rgb, src, sel)
+        clr = point_colours(ses, s.rgb, src, sel)
     write_point_cloud(opt.output_file, xyz, clr)
     _logger.info(f"Done. Wrote point cloud to: {opt.output_file}")
     return 0
@@ -1014,20 +832,18 @@ def eval_parser():
 
 def eval_poses_main(argv=None):
     """eval_poses.py: read the ACE pose file (every line) and the GT pose files, align, log per-frame errors, accuracy and medians."""
-    from .evaluate import evaluate_poses, load_gt_pose_files, log_lines, read_pose_file_with_confidence
+    import glob
+    from .evaluate import evaluate_poses, log_lines, read_pose_pairs
     logging.basicConfig(level=logging.INFO)
     opt = eval_parser().parse_args(argv)
     log = logging.getLogger("eval_poses")
     log.info("Reading ACE pose file.")
-    ace_estimates = read_pose_file_with_confidence(opt.ace_pose_file)
-    log.info(f"Read {len(ace_estimates)} poses from: {opt.ace_pose_file}")
-    sorted_ace_poses = [ace_estimates[key] for key in sorted(ace_estimates.keys())]
-    sorted_gt_poses = load_gt_pose_files(opt.gt_pose_files)
-    log.info(f"Loaded {len(sorted_gt_poses)} ground truth poses.")
-    pairs = list(zip(sorted_ace_poses, sorted_gt_poses))            # zip semantics: the shorter list decides
-    if not pairs:
+    estimates, ground_truth, confidences, n_estimates = read_pose_pairs(opt.ace_pose_file, opt.gt_pose_files)
+    log.info(f"Read {n_estimates} poses from: {opt.ace_pose_file}")
+    log.info(f"Loaded {len(glob.glob(opt.gt_pose_files))} ground truth poses.")
+    if not len(estimates):
         raise SystemExit("no (estimate, ground truth) pairs to evaluate")
-    res = evaluate_poses(np.stack([p[0][0] for p in pairs]), np.stack([p[1] for p in pairs]), np.array([p[0][1] for p in pairs]),
+    res = evaluate_poses(estimates, ground_truth, confidences,
                          estimate_alignment=opt.estimate_alignment, estimate_alignment_scale=opt.estimate_alignment_scale,
                          estimate_alignment_conf_threshold=opt.estimate_alignment_conf_threshold, pose_error_thresh_t=opt.pose_error_thresh_t,
                          pose_error_thresh_r=opt.pose_error_thresh_r, seed=opt.seed)
@@ -1036,7 +852,7 @@ def eval_poses_main(argv=None):
     for r_err, t_err in zip(res["r_err"], res["t_err"]):
         log.info(f"Rotation Error: {r_err:.2f}deg, Translation Error: {t_err * 100:.1f}cm")
     total_frames = len(res["t_err"])
-    assert total_frames == len(ace_estimates)
+    assert total_frames == n_estimates
     log.info("===================================================")
     log.info("Test complete.")
     for line in log_lines(res):
@@ -1185,8 +1001,7 @@ def fuse_depth_main(argv=None):
     opt = fuse_depth_parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     log = logging.getLogger("fuse_depth")
-    if not str(opt.output_file).endswith(".ply"):
-        raise SystemExit("output file format not supported: use .ply")
+    _require_ply(opt.output_file)
     if opt.voxel_size <= 0:
         raise SystemExit("--voxel_size must be positive")
     criteria = _component_criteria(opt)
@@ -1195,20 +1010,18 @@ def fuse_depth_main(argv=None):
     rgb_files, depth_files = sorted(glob.glob(opt.rgb_files)), sorted(glob.glob(opt.depth_files))
     if len(depth_files) != len(rgb_files):
         raise SystemExit(f"{len(depth_files)} depth files for {len(rgb_files)} images")
-    names, c2w_all, focals_all = read_ace_pose_file(opt.pose_file, opt.confidence_threshold)
-    if not names:
-        raise SystemExit("no pose above the confidence threshold")
+    try:
+        c2w_all, focals_all, pose_row = read_posed_images(opt.pose_file, rgb_files, opt.confidence_threshold)
+    except ValueError as e:
+        raise SystemExit(str(e))
     # (rgb file, depth file, row of the pose file), in the folder's order
-    pairs = [(r, d, k) for r, d, k in zip(rgb_files, depth_files, match_poses(names, rgb_files)) if k is not None]
-    if not pairs:
-        raise SystemExit("no image of the glob has a pose above the confidence threshold in the pose file")
+    pairs = [(r, d, k) for r, d, k in zip(rgb_files, depth_files, pose_row) if k is not None]
     t0 = time.perf_counter()
     with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
         depth = list(pool.map(read_depth_png, [p[1] for p in pairs]))
         image_h = [Image.open(p[0]).size[1] for p in pairs]
         c2w = np.stack([c2w_all[p[2]] for p in pairs])
-        # a pose file's focal is in pixels of the original image; the depth map is that image at another scale
-        focals = np.array([focals_all[p[2]] * d.shape[0] / ih for p, d, ih in zip(pairs, depth, image_h)])
+        focals = np.array([focal_at_height(focals_all[p[2]], d.shape[0], ih) for p, d, ih in zip(pairs, depth, image_h)])
         origin, dims = fusion.bounds_from_frames(depth, c2w, focals, opt.voxel_size, truncation, depth_unit=opt.depth_unit,
                                                  max_depth=opt.max_depth, max_voxels=MAX_GRID_VOXELS if opt.sparse else opt.max_voxels)
         if opt.sparse:
@@ -1223,9 +1036,7 @@ def fuse_depth_main(argv=None):
                 return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB").resize((w, h), Image.NEAREST), np.uint8))
             rgb = list(pool.map(read_rgb, [(p[0], d.shape) for p, d in zip(pairs, depth)]))
     t_decode = time.perf_counter() - t0
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("fuse_depth.py needs a GPU: TSDF fusion is a HIP kernel, there is no CPU path")
+    _require_gpu("fuse_depth", "TSDF fusion is a HIP kernel")
     t0 = time.perf_counter()
     if opt.sparse:
         vol = fusion.SparseTSDFVolume(origin, dims, opt.voxel_size, truncation, "cuda", max_blocks=opt.max_voxels // fusion.BLOCK_VOXELS)
@@ -1289,15 +1100,13 @@ def _mesh_command(name, opt, check, why, run):
     or refuses them; run(log, that, vertices, colours, faces) gives the new mesh on the device and the line that sums it up."""
     logging.basicConfig(level=logging.INFO)
     log = logging.getLogger(name)
-    if not str(opt.output_file).endswith(".ply"):
-        raise SystemExit("output file format not supported: use .ply")
+    _require_ply(opt.output_file)
     options = check(opt)
     if not opt.input_file.is_file():
         raise SystemExit(f"{opt.input_file}: no such file")
     vertices, colours, faces = read_ply_mesh(opt.input_file)
+    _require_gpu(name, why)
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit(f"{name}.py needs a GPU: {why}, there is no CPU path")
     device = lambda a: None if a is None else torch.from_numpy(a).cuda()
     out_v, out_c, out_f, summary = run(log, options, device(vertices), device(colours), device(np.ascontiguousarray(faces, np.int32)))
     log.info(summary)
@@ -1438,7 +1247,6 @@ def eval_geometry_main(argv=None):
     if opt.crop_file is not None and not os.path.isfile(opt.crop_file):
         raise SystemExit(f"{opt.crop_file}: no such file")
     crop_volume = None if opt.crop_file is None else read_crop_file(opt.crop_file)
-    surface = opt.sample_spacing is not None or opt.gt_sample_spacing is not None or crop_volume is not None
     rec_colours = rec_faces = gt_faces = None
     if opt.sample_spacing is not None:
         rec, rec_colours, rec_faces = read_ply_mesh(opt.reconstruction)
@@ -1453,9 +1261,8 @@ def eval_geometry_main(argv=None):
     else:
         gt = read_ply_points(opt.ground_truth)
     log.info(f"Read {len(rec)} points from {opt.reconstruction} and {len(gt)} from {opt.ground_truth}.")
+    _require_gpu("eval_geometry", "the cloud distances are HIP kernels")
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("eval_geometry.py needs a GPU: the cloud distances are HIP kernels, there is no CPU path")
     transform = None
     if opt.transform is not None:
         try:
@@ -1463,95 +1270,57 @@ def eval_geometry_main(argv=None):
         except ValueError:
             raise SystemExit(f"{opt.transform}: expected 16 numbers, a 4x4 matrix")
     elif opt.ace_pose_file is not None:
-        from .evaluate import evaluate_poses, load_gt_pose_files, read_pose_file_with_confidence
-        estimates = read_pose_file_with_confidence(opt.ace_pose_file)
-        pairs = list(zip([estimates[key] for key in sorted(estimates.keys())], load_gt_pose_files(opt.gt_pose_files)))
-        if not pairs:
+        from .evaluate import evaluate_poses, read_pose_pairs
+        estimates, ground_truth, confidences, _ = read_pose_pairs(opt.ace_pose_file, opt.gt_pose_files)
+        if not len(estimates):
             raise SystemExit("no (estimate, ground truth) pose pairs to align with")
-        res = evaluate_poses(np.stack([p[0][0] for p in pairs]), np.stack([p[1] for p in pairs]), np.array([p[0][1] for p in pairs]),
-                             estimate_alignment_conf_threshold=opt.estimate_alignment_conf_threshold, seed=opt.seed)
+        res = evaluate_poses(estimates, ground_truth, confidences, estimate_alignment_conf_threshold=opt.estimate_alignment_conf_threshold,
+                             seed=opt.seed)
         if res["T"] is None:
             raise SystemExit("the alignment of the estimated poses to the ground-truth poses failed: too few confident poses, or no "
                              "consistent similarity")
         transform = np.linalg.inv(res["T"])                       # T maps ground truth -> estimates (its rotation part carries the scale)
-        log.info(f"Aligned on {len(pairs)} pose pairs: scale {res['scale']:.6f} (ground truth -> reconstruction), median pose error "
+        log.info(f"Aligned on {len(estimates)} pose pairs: scale {res['scale']:.6f} (ground truth -> reconstruction), median pose error "
                  f"{res['median_r_deg']:.2f}deg, {res['median_t_cm']:.1f}cm.")
     t0 = time.perf_counter()
-    sampling = crop_info = colours_d = None
+    device = lambda a: None if a is None else torch.from_numpy(a).cuda()
     try:
-        rec_d, gt_d = torch.from_numpy(rec).cuda(), torch.from_numpy(gt).cuda()
-        if surface:
-            # the order of DESIGN 4n: read, move the vertices, sample, polygon crop, ICP (from the identity), voxel, box crop, search
-            transform_initial = transform
-            if transform is not None:
-                rec_d = geometry.apply_similarity(rec_d, transform)
-            transform = None
-            if opt.sample_spacing is not None or opt.gt_sample_spacing is not None:
-                sampling = {"seed": opt.sample_seed}
-            if opt.sample_spacing is not None:
-                colours_d = None if rec_colours is None else torch.from_numpy(rec_colours).cuda()
-                rec_d, _, colours_d, info = geometry.sample_mesh(rec_d, torch.from_numpy(rec_faces).cuda(), spacing=opt.sample_spacing,
-                                                                 seed=opt.sample_seed, colours=colours_d)
-                sampling.update(spacing=opt.sample_spacing, **info)
-                log.info(f"Sampled {info['samples']} points, {opt.sample_spacing} m apart, from the {info['faces']} faces of the "
-                         f"reconstruction ({info['area']:.4f} m^2; {info['faces_invalid']} faces invalid).")
-            if opt.gt_sample_spacing is not None:
-                gt_d, _, _, info = geometry.sample_mesh(gt_d, torch.from_numpy(gt_faces).cuda(), spacing=opt.gt_sample_spacing, seed=opt.sample_seed)
-                sampling.update(gt_spacing=opt.gt_sample_spacing, **{"gt_" + k: v for k, v in info.items()})
-                log.info(f"Sampled {info['samples']} points, {opt.gt_sample_spacing} m apart, from the {info['faces']} faces of the "
-                         f"ground truth ({info['area']:.4f} m^2; {info['faces_invalid']} faces invalid).")
-            if crop_volume is not None:
-                keep = geometry.polygon_mask(rec_d, crop_volume)
-                crop_info = {"file": str(opt.crop_file), "orthogonal_axis": "XYZ"[crop_volume.axis], "corners": int(len(crop_volume.polygon)),
-                             "axis_min": float(crop_volume.axis_min), "axis_max": float(crop_volume.axis_max),
-                             "dropped": int(rec_d.shape[0] - int(keep.sum().item()))}
-                rec_d = rec_d[keep].contiguous()
-                if opt.sample_spacing is not None and colours_d is not None:
-                    colours_d = colours_d[keep].contiguous()
-                if opt.crop_file_ground_truth:
-                    gt_d, crop_info["gt_dropped"] = geometry.crop_to_polygon(gt_d, crop_volume)
-                log.info(f"Crop file {opt.crop_file}: {crop_info['corners']} corners along {crop_info['orthogonal_axis']}, "
-                         f"{crop_info['dropped']} reconstruction points dropped, {rec_d.shape[0]} kept"
-                         + (f"; {crop_info['gt_dropped']} ground-truth points dropped" if opt.crop_file_ground_truth else "") + ".")
-                if rec_d.shape[0] == 0:
-                    raise ValueError(f"the reconstruction is empty after the crop file's polygon ({crop_info['dropped']} points dropped): "
-                                     "are the clouds in the same frame?")
-        if opt.icp:
-            if not surface:
-                transform_initial = transform
-            transform, stages = geometry.refine_alignment(rec_d, gt_d, transform, distances=icp_distances, voxels=opt.icp_voxel_sizes,
-                                                          max_iterations=opt.icp_max_iterations, with_scale=opt.icp_scale)
-            for stage in stages:
-                log.info(f"ICP stage at {stage['distance']} m: {stage['iterations']} iterations, {stage['status']}"
-                         + (", the alignment before it kept" if stage["kept_previous"] else "")
-                         + (f", fitness {stage['fitness'][-1] * 100:.2f}%, rmse {stage['rmse'][-1] * 1000:.3f} mm" if stage["iterations"] else ""))
-        res = geometry.evaluate_geometry(rec_d, gt_d, opt.thresholds, transform=transform, voxel=opt.voxel_size, crop=opt.crop,
-                                         max_distance=opt.max_distance)
-        if opt.write_samples is not None:                         # as they are scored: cropped by the polygon, under the final alignment
-            scored = rec_d if transform is None else geometry.apply_similarity(rec_d, transform)
-            write_ply(opt.write_samples, scored.cpu().numpy(), np.full((scored.shape[0], 3), 200, np.uint8) if colours_d is None
-                      else colours_d.cpu().numpy())
-            log.info(f"Wrote {scored.shape[0]} samples to {opt.write_samples}.")
+        res, scored, colours = geometry.score_reconstruction(
+            device(rec), device(gt), opt.thresholds, rec_faces=device(rec_faces), rec_colours=device(rec_colours), gt_faces=device(gt_faces),
+            transform=transform, sample_spacing=opt.sample_spacing, gt_sample_spacing=opt.gt_sample_spacing, sample_seed=opt.sample_seed,
+            crop_volume=crop_volume, crop_ground_truth=opt.crop_file_ground_truth, icp_distances=icp_distances,
+            icp_voxels=opt.icp_voxel_sizes, icp_max_iterations=opt.icp_max_iterations, icp_scale=opt.icp_scale, voxel=opt.voxel_size,
+            crop=opt.crop, max_distance=opt.max_distance)
     except ValueError as e:
-        raise SystemExit(str(e) + (f" (the crop file's polygon dropped {crop_info['dropped']} points before)"
-                                   if crop_info is not None and "crop file" not in str(e) and "is empty" in str(e) else ""))
-    if surface and transform_initial is not None:                  # what is reported maps the file's frame: T_icp T_initial
-        transform = transform_initial if transform is None else transform @ transform_initial
+        raise SystemExit(str(e))
+    for gt_, what in (("", "reconstruction"), ("gt_", "ground truth")):
+        info = res.get("sampling", {})
+        if gt_ + "spacing" in info:
+            log.info(f"Sampled {info[gt_ + 'samples']} points, {info[gt_ + 'spacing']} m apart, from the {info[gt_ + 'faces']} faces of the "
+                     f"{what} ({info[gt_ + 'area']:.4f} m^2; {info[gt_ + 'faces_invalid']} faces invalid).")
+    if crop_volume is not None:
+        info = res["crop_file"]
+        log.info(f"Crop file {opt.crop_file}: {info['corners']} corners along {info['orthogonal_axis']}, "
+                 f"{info['dropped']} reconstruction points dropped, {res['rec_points_read']} kept"
+                 + (f"; {info['gt_dropped']} ground-truth points dropped" if opt.crop_file_ground_truth else "") + ".")
+        res["crop_file"] = {"file": str(opt.crop_file), **info}
+    for stage in res.get("icp", []):
+        log.info(f"ICP stage at {stage['distance']} m: {stage['iterations']} iterations, {stage['status']}"
+                 + (", the alignment before it kept" if stage["kept_previous"] else "")
+                 + (f", fitness {stage['fitness'][-1] * 100:.2f}%, rmse {stage['rmse'][-1] * 1000:.3f} mm" if stage["iterations"] else ""))
+    if opt.write_samples is not None:                             # as they are scored: cropped by the polygon, under the final alignment
+        write_ply(opt.write_samples, scored.cpu().numpy(), np.full((scored.shape[0], 3), 200, np.uint8) if colours is None
+                  else colours.cpu().numpy())
+        log.info(f"Wrote {scored.shape[0]} samples to {opt.write_samples}.")
     t_device = time.perf_counter() - t0
     for line in geometry.log_lines(res):
         log.info(line)
     log.info(f"Upload + kernels + download {t_device:.2f} s.")
     if opt.output_json is not None:
-        res["transform"] = None if transform is None else [[float(x) for x in row] for row in transform]
-        if sampling is not None:
-            res["sampling"] = sampling
-        if crop_info is not None:
-            res["crop_file"] = crop_info
         if opt.icp:
-            res["transform_initial"] = None if transform_initial is None else [[float(x) for x in row] for row in transform_initial]
             # a stage without correspondences has rmse = sqrt(0 / 0): null in the file, which stays strict JSON
-            res["icp"] = [{k: [x if math.isfinite(x) else None for x in v] if isinstance(v, list) else v
-                           for k, v in stage.items() if k != "transforms"} for stage in stages]
+            res["icp"] = [{k: [x if math.isfinite(x) else None for x in v] if isinstance(v, list) else v for k, v in stage.items()}
+                          for stage in res["icp"]]
         with open(opt.output_json, "w") as f:
             json.dump(res, f, indent=1, sort_keys=True)
             f.write("\n")
@@ -1638,20 +1407,16 @@ def estimate_depth_main(argv=None):
     stems = [os.path.splitext(os.path.basename(f))[0] for f in rgb_files]
     if len(set(stems)) != len(stems):
         raise SystemExit("two images of the glob share a name: their depth maps would overwrite each other")
-    names, c2w_all, focals_all = read_ace_pose_file(opt.pose_file, opt.confidence_threshold)
-    if not names:
-        raise SystemExit("no pose above the confidence threshold")
-    pose_row = match_poses(names, rgb_files)
-    if all(k is None for k in pose_row):
-        raise SystemExit("no image of the glob has a pose above the confidence threshold in the pose file")
+    try:
+        c2w_all, focals_all, pose_row = read_posed_images(opt.pose_file, rgb_files, opt.confidence_threshold)
+    except ValueError as e:
+        raise SystemExit(str(e))
     cloud = None
     if opt.point_cloud is not None:
         cloud = read_ply_vertices(opt.point_cloud).astype(np.float64)
         if opt.cloud_convention == "opengl":
             cloud[:, 1], cloud[:, 2] = -cloud[:, 1], -cloud[:, 2]
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("estimate_depth.py needs a GPU: plane-sweep stereo is a HIP kernel, there is no CPU path")
+    _require_gpu("estimate_depth", "plane-sweep stereo is a HIP kernel")
     t0 = time.perf_counter()
     grey, image_h = mvs.load_grey_frames(rgb_files, opt.image_resolution)
     t_decode = time.perf_counter() - t0
@@ -1664,7 +1429,7 @@ def estimate_depth_main(argv=None):
             continue
         h, w = grey[f].shape
         c2w[f] = c2w_all[k]
-        focals[f] = focals_all[k] * h / image_h[f]               # the pose file's focal is in pixels of the original image
+        focals[f] = focal_at_height(focals_all[k], h, image_h[f])
         if cloud is None:
             ranges[f] = tuple(opt.depth_range)
         else:

@@ -132,10 +132,20 @@ def load_gt_pose_files(pattern):
     return [np.loadtxt(p).astype(np.float32).astype(np.float64) for p in sorted(glob.glob(pattern))]
 
 
+def read_pose_pairs(ace_pose_file, gt_glob):
+    """What eval_poses.py and eval_geometry.py align on: the pose file's estimates in the sorted order of their names, zipped with
+    the sorted ground-truth files (the shorter list decides). Returns (estimates [n,4,4], ground truth [n,4,4], confidences [n],
+    number of estimates read); n may be 0."""
+    estimates = read_pose_file_with_confidence(ace_pose_file)
+    pairs = list(zip([estimates[key] for key in sorted(estimates.keys())], load_gt_pose_files(gt_glob)))
+    stack = lambda rows: np.stack(rows) if rows else np.zeros((0, 4, 4))
+    return stack([p[0][0] for p in pairs]), stack([p[1] for p in pairs]), np.array([p[0][1] for p in pairs]), len(estimates)
+
+
 def log_lines(res):
     """The two summary lines eval_poses.py logs at the end."""
     return [f"Accuracy: {res['accuracy']:.1f}%", f"Median Error: {res['median_r_deg']:.1f}deg, {res['median_t_cm']:.1f}cm"]
 
 
 __all__ = ["TestEstimate", "estimate_alignment", "evaluate_poses", "median_of_sorted", "read_pose_file_with_confidence",
-           "load_gt_pose_files", "log_lines", "DEFAULT_SEED"]
+           "load_gt_pose_files", "read_pose_pairs", "log_lines", "DEFAULT_SEED"]

@@ -2,6 +2,7 @@
 (`file qw qx qy qz tx ty tz focal confidence`, world->camera), binary little-endian PLY (point clouds, fused meshes, camera
 meshes; read_ply_mesh also reads other tools' meshes), the Tanks and Temples crop file (JSON) and the 16-bit depth PNG that
 estimate_depth.py writes and fuse_depth.py reads. Host code only."""
+import argparse
 import os
 from collections import namedtuple
 
@@ -63,6 +64,34 @@ def match_poses(names, files):
     by_name = {n: k for k, n in enumerate(names)}
     by_base = {os.path.basename(n): k for k, n in enumerate(names)}
     return [by_name.get(f, by_base.get(os.path.basename(f))) for f in files]
+
+
+def read_posed_images(pose_file, files, confidence_threshold):
+    """The posed images of fuse_depth.py and estimate_depth.py: (cam->world [k,4,4], focals [k], for every file its row of the two or
+    None) from the pose file's entries that are not below the threshold. ValueError if no entry is left or no file has one."""
+    names, c2w, focals = read_ace_pose_file(pose_file, confidence_threshold)
+    if not names:
+        raise ValueError("no pose above the confidence threshold")
+    rows = match_poses(names, files)
+    if all(k is None for k in rows):
+        raise ValueError("no image of the glob has a pose above the confidence threshold in the pose file")
+    return c2w, focals, rows
+
+
+def focal_at_height(focal, h, image_h):
+    """A pose file's focal is in pixels of the original image (image_h rows); a depth map or working image of h rows is that image at
+    another scale."""
+    return focal * h / image_h
+
+
+# -------------------------------------------------------------------------------------------------------- flag values
+def _strtobool(x):
+    v = str(x).lower()
+    if v in ("y", "yes", "t", "true", "on", "1"):
+        return True
+    if v in ("n", "no", "f", "false", "off", "0"):
+        return False
+    raise argparse.ArgumentTypeError(f"invalid truth value {x!r}")
 
 
 # ------------------------------------------------------------------------------------------------------------------ PLY

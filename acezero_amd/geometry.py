@@ -416,6 +416,69 @@ def crop_to_polygon(points, crop):
     return points[keep].contiguous(), int(points.shape[0] - int(keep.sum().item()))
 
 
+def score_reconstruction(rec, gt, thresholds, *, rec_faces=None, rec_colours=None, gt_faces=None, transform=None, sample_spacing=None,
+                         gt_sample_spacing=None, sample_seed=0, crop_volume=None, crop_ground_truth=False, icp_distances=None,
+                         icp_voxels=None, icp_max_iterations=30, icp_scale=False, voxel=None, crop=True, max_distance=None):
+    """eval_geometry.py's pipeline on device tensors, in the order of DESIGN.md section 4n. Points (no spacing, no crop_volume): ICP
+    (icp_distances given) starts from `transform`, evaluate_geometry applies the result. A surface: move the vertices by `transform`,
+    sample the faces (rec_faces / gt_faces at their spacing), drop what lies outside crop_volume (a formats.CropVolume; with
+    crop_ground_truth the ground truth's points too), ICP from the identity, then voxel, box crop and search in evaluate_geometry.
+    Returns (res, points, colours): evaluate_geometry's dict with `transform` (file frame -> ground truth: T_icp T_initial; rows of
+    floats or None) and, where they apply, `sampling`, `crop_file`, `transform_initial` and `icp` (the stage infos without their
+    matrices), as eval_geometry.py --output_json holds them; the reconstruction's points as they are scored (sampled, cropped by the
+    polygon, under the final alignment) and their colours (None without rec_colours). ValueError if a cloud ends up empty."""
+    initial = None if transform is None else np.array(transform, np.float64).reshape(4, 4)
+    surface = sample_spacing is not None or gt_sample_spacing is not None or crop_volume is not None
+    T, colours = initial, rec_colours                                # T: what is still to be applied to rec
+    sampling = crop_info = stages = None
+    try:
+        if surface:
+            if T is not None:
+                rec = apply_similarity(rec, T)
+            T = None
+            if sample_spacing is not None or gt_sample_spacing is not None:
+                sampling = {"seed": sample_seed}
+            if sample_spacing is not None:
+                rec, _, colours, info = sample_mesh(rec, rec_faces, spacing=sample_spacing, seed=sample_seed, colours=colours)
+                sampling.update(spacing=sample_spacing, **info)
+            if gt_sample_spacing is not None:
+                gt, _, _, info = sample_mesh(gt, gt_faces, spacing=gt_sample_spacing, seed=sample_seed)
+                sampling.update(gt_spacing=gt_sample_spacing, **{"gt_" + k: v for k, v in info.items()})
+            if crop_volume is not None:
+                keep = polygon_mask(rec, crop_volume)
+                crop_info = {"orthogonal_axis": "XYZ"[crop_volume.axis], "corners": int(len(crop_volume.polygon)),
+                             "axis_min": float(crop_volume.axis_min), "axis_max": float(crop_volume.axis_max),
+                             "dropped": int(rec.shape[0] - int(keep.sum().item()))}
+                rec = rec[keep].contiguous()
+                if colours is not None:
+                    colours = colours[keep].contiguous()
+                if crop_ground_truth:
+                    gt, crop_info["gt_dropped"] = crop_to_polygon(gt, crop_volume)
+                if rec.shape[0] == 0:
+                    raise ValueError(f"the reconstruction is empty after the crop file's polygon ({crop_info['dropped']} points dropped): "
+                                     "are the clouds in the same frame?")
+        if icp_distances is not None:
+            T, stages = refine_alignment(rec, gt, T, distances=icp_distances, voxels=icp_voxels, max_iterations=icp_max_iterations,
+                                         with_scale=icp_scale)
+        res = evaluate_geometry(rec, gt, thresholds, transform=T, voxel=voxel, crop=crop, max_distance=max_distance)
+    except ValueError as e:
+        raise ValueError(str(e) + (f" (the crop file's polygon dropped {crop_info['dropped']} points before)"
+                                   if crop_info is not None and "crop file" not in str(e) and "is empty" in str(e) else ""))
+    points = rec if T is None else apply_similarity(rec, T)
+    if surface and initial is not None:                              # what is reported maps the file's frame: T_icp T_initial
+        T = initial if T is None else T @ initial
+    rows = lambda M: None if M is None else [[float(x) for x in row] for row in M]
+    res["transform"] = rows(T)
+    if sampling is not None:
+        res["sampling"] = sampling
+    if crop_info is not None:
+        res["crop_file"] = crop_info
+    if stages is not None:
+        res["transform_initial"] = rows(initial)
+        res["icp"] = [{k: v for k, v in stage.items() if k != "transforms"} for stage in stages]
+    return res, points, colours
+
+
 def log_lines(res):
     """The summary eval_geometry.py logs: the counts, then one line per threshold."""
     lines = [f"Reconstruction: {res['rec_points']} points ({res['rec_points_read']} read, {res['dropped']} dropped outside the ground "
@@ -431,4 +494,4 @@ def log_lines(res):
 
 __all__ = ["nearest_distances", "voxel_downsample", "evaluate_geometry", "apply_similarity", "crop_to_box", "scores", "fscore",
            "log_lines", "grid_dims", "point_cells", "build_grid", "order_by_cell", "icp_stage", "refine_alignment", "sample_mesh",
-           "sample_density", "crop_to_polygon", "polygon_mask"]
+           "sample_density", "crop_to_polygon", "polygon_mask", "score_reconstruction"]

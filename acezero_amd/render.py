@@ -795,7 +795,7 @@ def export_cameras_main(argv=None):
     """export_cameras.py: pose_file output_file [--frustum_scale] [--frustum_markers] [--draw_non_confident] [--confidence_threshold]."""
     import argparse
     from pathlib import Path
-    from .cli import _strtobool
+    from .formats import _strtobool
     p = argparse.ArgumentParser(description="Export the cameras of an ACE pose file as a mesh (PLY).",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("pose_file", type=Path, help="ACE pose file (file qw qx qy qz tx ty tz focal confidence)")

@@ -107,6 +107,15 @@ def ransac_params(opt, use_depth=False, max_tries=16):
                 sub=8, max_tries=int(max_tries), unit="cm" if use_depth else "px")
 
 
+def estimate_subset(n, max_estimates, seed):
+    """--max_estimates: the ids of a seeded random subset of n frames, in file order -- not the first max_estimates frames -- as the
+    reference's DataLoader(shuffle=True) under torch.manual_seed(base_seed) gives one (register_mapping.py:122-147,256; a different
+    stream, the same law). max_estimates <= 0 or >= n: all of them."""
+    if max_estimates <= 0 or max_estimates >= n:
+        return np.arange(n)
+    return np.sort(torch.randperm(n, generator=torch.Generator().manual_seed(int(seed)))[:max_estimates].numpy())
+
+
 def check_rgbd_mode(images, depth, world=1):
     """RGB-D mode (default_options(rgbd=True)) needs a depth map for EVERY frame, at the frame's own feature resolution, and runs in one
     process. images / depth as ReconstructionSession takes them. Raises before any frame is encoded."""
@@ -774,12 +783,7 @@ class ReconstructionSession:
         o = self.opt
         if use_depth and self.depth is None:
             raise RuntimeError("register(use_depth=True) needs the session's depth maps (depth=...)")
-        if max_estimates <= 0 or max_estimates >= self.n:
-            ids = np.arange(self.n)
-        else:
-            g = torch.Generator().manual_seed(int(o.register_seed))
-            ids = np.sort(torch.randperm(self.n, generator=g)[:max_estimates].numpy())
-        self.registered_ids = ids
+        ids = self.registered_ids = estimate_subset(self.n, max_estimates, o.register_seed)
         t0 = time.time()
         mine = ids[ids % self.world == self.rank]
         prm = ransac_params(o, use_depth, max_tries)

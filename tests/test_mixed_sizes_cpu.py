@@ -1,5 +1,6 @@
 """Folders of mixed frame sizes on the host side: size classes from load_frames, per-frame resize factors and focals, depth maps
 at every frame's own feature resolution, the calibration-refinement refusal, per-frame pose-file focals and point colours."""
+import math
 import os
 from types import SimpleNamespace
 
@@ -61,6 +62,57 @@ def test_per_frame_focals_and_depth(tmp_path):
     depth = cli.load_depth_maps(str(tmp_path / "d*.png"), 6, cli.frame_shapes(classes, 6))
     assert [tuple(d.shape) for d in depth] == [(6, 8), (8, 6), (6, 8), (8, 6), (6, 10), (6, 8)]
     assert all(np.allclose(d.numpy(), (1000 + i) / 1000.0) for i, d in enumerate(depth))
+
+
+def _saved_sizes(files):
+    from PIL import Image
+    return [Image.open(f).size for f in files]
+
+
+@pytest.mark.parametrize("folder", ["one size", "two sizes", "one size, originals of two sizes"])
+def test_session_frames_restates_the_commands_focal_rules(tmp_path, folder):
+    """images.session_frames against the rules of dataset.py:269-274,289-290 as train_ace.py, ace_zero.py and export_point_cloud.py
+    applied them, restated here: a focal in original-image pixels times the resize factor, else 70% of the resized diagonal; one size
+    converts with ONE factor, the last frame's, several sizes with every frame's own. Exact in float64."""
+    from PIL import Image
+    from acezero_amd import images
+    res = 48
+    glob_ = _folder(tmp_path, sizes=SIZES if folder == "two sizes" else [(64, 48)] * 3, scale=2)
+    if folder == "one size, originals of two sizes":                     # the LAST file at the plain size: factor 1.0, the others' 0.5
+        Image.fromarray(np.zeros((48, 64, 3), np.uint8)).save(tmp_path / "f2.png")
+    files = sorted(str(p) for p in tmp_path.glob("f*.png"))
+    n = len(files)
+    factors = np.array([res / min(w, h) for w, h in _saved_sizes(files)])
+    shapes = [(int(h * f), res) if w <= h else (res, int(w * f)) for (w, h), f in zip(_saved_sizes(files), factors)]   # resized (H, W)
+    diagonal = np.array([math.sqrt(w ** 2 + h ** 2) * 0.7 for h, w in shapes])
+    mixed = folder == "two sizes"
+    assert factors[-1] == (1.0 if folder == "one size, originals of two sizes" else 0.5)
+    file_focals = [300.0 + 7 * i for i in range(n)] if mixed else [300.0] * n
+    for kind, flags in (("external", dict(external=123.25)), ("heuristic", dict(heuristic=True, file_focals=file_focals)),
+                        ("none", {}), ("file", dict(file_focals=file_focals)), ("external first", dict(external=123.25, file_focals=file_focals))):
+        s = images.session_frames(cli.load_session_frames, glob_, res, **flags)
+        assert s.files == files and s.mixed == mixed and s.rgb is None
+        if kind.startswith("external"):
+            per_frame = 123.25 * factors
+        elif kind in ("heuristic", "none"):
+            per_frame = diagonal
+        else:
+            per_frame = np.array(file_focals) * factors
+        nominal = 1.1 * s.focal                                          # a refined nominal focal
+        if mixed:
+            assert s.frame_focals.dtype == np.float64 and np.array_equal(s.frame_focals, per_frame) and s.focal == per_frame[0]
+            assert s.hw == shapes and np.array_equal(s.factors, factors)
+            frel = per_frame / per_frame[0]                              # what ReconstructionSession keeps of focals=frame_focals
+            assert np.array_equal(s.original_focals(nominal, frel), nominal * frel / factors)
+        else:
+            one = 123.25 * factors[-1] if kind.startswith("external") else diagonal[0] if kind in ("heuristic", "none") else 300.0 * factors[-1]
+            assert s.frame_focals is None and s.focal == one and tuple(s.hw) == shapes[0] and s.factors == factors[-1]
+            assert np.array_equal(s.original_focals(nominal, None), np.full(n, nominal / factors[-1]))
+    rgb = images.session_frames(cli.load_session_frames, None, res, files=files, return_rgb=True).rgb
+    assert len(rgb) == n and all(tuple(a.shape) == hw + (3,) for a, hw in zip(rgb, shapes))
+    if not mixed:
+        with pytest.raises(AssertionError, match="a single focal length is supported"):
+            images.session_frames(cli.load_session_frames, glob_, res, file_focals=[300.0, 300.0, 301.0])
 
 
 def test_calibration_refinement_refuses_differing_focals(tmp_path):

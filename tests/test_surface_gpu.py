@@ -288,6 +288,38 @@ def test_a_crop_file_over_half_the_room(room, caplog):
         run_command([tmp / "rec.ply"] + room["common"] + [tmp / "none.json", "--crop_file", tmp / "elsewhere.json"])
 
 
+def test_score_reconstruction_is_the_commands_pipeline(room, tmp_path):
+    """geometry.score_reconstruction called directly -- surface samples, a crop volume, a --transform that is off by a centimetre and
+    two ICP stages -- returns the numbers eval_geometry.py writes to --output_json for the same inputs (all but the crop file's name)
+    and the points it writes to --write_samples, bit for bit."""
+    from acezero_amd import geometry
+    from acezero_amd.formats import read_crop_file, read_ply_mesh, read_ply_points, write_ply
+    tmp, spacing, distances = room["tmp"], 0.02, [0.08, 0.04]
+    S, off = GC.similarity(scale=1.3), np.eye(4)
+    off[:3, 3] = [0.01, -0.005, 0.008]
+    write_ply(tmp_path / "moved.ply", R.apply_similarity(room["v"], S), room["colours"], room["f"])
+    np.savetxt(tmp_path / "nearly_back.txt", off @ np.linalg.inv(S))
+    doc = {"orthogonal_axis": "Z", "axis_min": -1.0, "axis_max": 1.0, "bounding_polygon": [[0.0, -1.0, 0.0], [1.0, -1.0, 0.0], [1.0, 1.0, 0.0], [0.0, 1.0, 0.0]]}
+    (tmp_path / "half.json").write_text(json.dumps(doc))
+    written = run_command([tmp_path / "moved.ply", tmp / "gt.ply", "--thresholds", *THRESHOLDS, "--transform", tmp_path / "nearly_back.txt",
+                           "--sample_spacing", spacing, "--crop_file", tmp_path / "half.json", "--icp", "True", "--icp_distances", *distances,
+                           "--icp_max_iterations", 5, "--write_samples", tmp_path / "scored.ply", "--output_json", tmp_path / "scores.json"])
+    assert written["crop_file"].pop("file") == str(tmp_path / "half.json")
+    v, colours, f = read_ply_mesh(tmp_path / "moved.ply")
+    device = lambda a: torch.from_numpy(a).cuda()
+    res, points, point_colours = geometry.score_reconstruction(
+        device(v), device(read_ply_points(tmp / "gt.ply")), THRESHOLDS, rec_faces=device(f), rec_colours=device(colours),
+        transform=np.loadtxt(tmp_path / "nearly_back.txt"), sample_spacing=spacing, crop_volume=read_crop_file(tmp_path / "half.json"),
+        icp_distances=distances, icp_max_iterations=5)
+    assert json.loads(json.dumps(res)) == written                       # (the round trip turns tuples into lists, nothing else)
+    assert len(res["icp"]) == 2 and res["sampling"]["spacing"] == spacing and 0 < res["crop_file"]["dropped"] < res["sampling"]["samples"]
+    assert res["transform_initial"] == np.loadtxt(tmp_path / "nearly_back.txt").tolist() and res["transform"] != res["transform_initial"]
+    scored, scored_colours, _ = read_ply_mesh(tmp_path / "scored.ply")
+    assert len(scored) == res["rec_points_read"] == res["sampling"]["samples"] - res["crop_file"]["dropped"]
+    assert np.array_equal(points.cpu().numpy().view(np.uint32), scored.view(np.uint32))
+    assert np.array_equal(point_colours.cpu().numpy(), scored_colours)
+
+
 def test_the_fused_mesh_by_its_surface(room, tmp_path):
     """fuse_depth.py's surface-nets mesh of the room: eval_geometry.py samples it as the restatement does, and the recall below the
     voxel edge, which its vertices alone cannot reach, is there."""

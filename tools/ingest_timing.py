@@ -1,7 +1,7 @@
-"""Image ingest: the host path (cli.load_frames, one Python loop over Pillow) against the device path (acezero_amd.ingest: threaded
+"""Image ingest: the host path (images.load_frames, one Python loop over Pillow) against the device path (acezero_amd.ingest: threaded
 decode, HIP resize + grey + normalise) on N synthetic 1920 x 1080 JPEGs written to a temporary folder. Prints a table and one JSON
 line, all in milliseconds per frame:
-  host            cli.load_frames over the N files, wall clock (decode + resize + grey + normalise on one thread)
+  host            images.load_frames over the N files, wall clock (decode + resize + grey + normalise on one thread)
   device[w]       ingest.load_frames_device with w decode threads over the same files, wall clock to the final synchronise
   decode[w]       ingest.decode_frames with w threads alone, wall clock
   upload          one pinned chunk of 32 decoded frames host -> device, HIP events
@@ -71,19 +71,19 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ingest_timing.py measures on a GPU; there is nothing to time without one")
-    from acezero_amd import cli, ingest
+    from acezero_amd import images, ingest
     out = {"n": a.n, "source": [H, W], "image_resolution": RES, "cpus": len(os.sched_getaffinity(0)), "device": torch.cuda.get_device_name(0)}
     with tempfile.TemporaryDirectory() as folder:
         glob_ = write_jpegs(folder, a.n)
         files = sorted(os.path.join(folder, f) for f in os.listdir(folder))
         warm = files[:min(len(files), 2 * CHUNK)]
         # the same frames first (and the warm-up of both paths)
-        _, hf, _, hrgb = cli.load_frames(None, RES, files=warm, return_rgb=True)
+        _, hf, _, hrgb = images.load_frames(None, RES, files=warm, return_rgb=True)
         _, df, _, drgb = ingest.load_frames_device(None, RES, files=warm, return_rgb=True, workers=16)
         assert torch.equal(df.cpu(), hf) and np.array_equal(drgb, hrgb), "device frames differ from the host frames"
         nh, nw = hf.shape[2:]
         out["resized"] = [int(nh), int(nw)]
-        out["host_ms"], raw = wall_ms(lambda: cli.load_frames(glob_, RES), max(1, a.reps - 1))
+        out["host_ms"], raw = wall_ms(lambda: images.load_frames(glob_, RES), max(1, a.reps - 1))
         out["host_ms"] /= a.n
         out["host_ms_runs"] = [round(t / a.n, 3) for t in raw]
         out["device_ms"], out["decode_ms"], out["device_ms_runs"] = {}, {}, {}
