@@ -218,6 +218,15 @@ SYMBOLS = {
                                          C.c_void_p, C.c_int64, C.c_void_p]),
     "acez_tsdf_faces_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "acez_tsdf_track_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                             C.c_float, C.c_void_p, C.c_int64, C.POINTER(TsdfFrame), C.c_int, C.c_void_p, C.c_int, C.c_float,
+                                             C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "acez_tsdf_track_accumulate_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                    C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int64,
+                                                    C.POINTER(TsdfFrame), C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "acez_tsdf_track_update": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
     "acez_mvs_prefilter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(TsdfFrame), C.c_int, C.c_void_p, C.c_void_p]),
     "acez_mvs_relative": (C.c_int, [C.POINTER(TsdfFrame), C.POINTER(TsdfFrame), C.POINTER(C.c_float)]),
     "acez_mvs_sweep": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(TsdfFrame), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_float,

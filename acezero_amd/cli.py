@@ -22,7 +22,8 @@ import numpy as np
 
 from . import DEFAULT_DTYPE
 from .formats import (_strtobool, focal_at_height, read_ace_pose_file, read_crop_file, read_depth_png, read_ply_mesh,
-                      read_ply_points, read_ply_vertices, read_posed_images, write_depth_png, write_ply, write_pose_line)
+                      read_ply_points, read_ply_vertices, read_posed_images, write_depth_png, write_ply, write_pose_line,
+                      write_poses_like)
 # the host loaders live in images.py; their names stay in this namespace (cli.load_frames, ...) for callers and tests
 from .images import (_default_encoder_path, check_calibration_focals, check_single_focal, depth_map_at_cells, focals_in_original_units,
                      frame_shapes, frame_size_classes, initial_focals, load_depth_maps, load_frames, load_session_frames, session_frames)
@@ -950,6 +951,14 @@ def fuse_depth_parser():
                                                                      "this edge in metres (after the component filter)")
     p.add_argument("--simplify_placement", type=str, default="quadric", choices=["quadric", "mean"],
                    help="with --simplify_cell: a cell's vertex minimises the plane quadrics of the faces around it, or is the mean of its vertices")
+    p.add_argument("--refine_poses", type=int, default=0, metavar="ROUNDS",
+                   help="refine the poses against the fused volume this many times (fuse, track every frame on the volume's SDF, fuse again) "
+                        "before the mesh is extracted; 0: off")
+    p.add_argument("--refine_iterations", type=int, default=10, help="with --refine_poses: Gauss-Newton iterations per frame and round at most")
+    p.add_argument("--refine_min_weight", type=float, default=1.0, help="with --refine_poses: a depth pixel is used where all eight voxels "
+                                                                       "around its point have been observed this many times")
+    p.add_argument("--refined_pose_file", type=Path, default=None, help="with --refine_poses: write the refined poses here, in the pose "
+                                                                        "file's format (frames whose tracking was degenerate keep their pose)")
     return p
 
 
@@ -998,12 +1007,17 @@ def fuse_depth_main(argv=None):
     from concurrent.futures import ThreadPoolExecutor
     from PIL import Image
     from . import fusion
-    opt = fuse_depth_parser().parse_args(argv)
+    parser = fuse_depth_parser()
+    opt = parser.parse_args(argv)
+    if opt.refined_pose_file is not None and opt.refine_poses == 0:
+        parser.error("--refined_pose_file needs --refine_poses ROUNDS")
     logging.basicConfig(level=logging.INFO)
     log = logging.getLogger("fuse_depth")
     _require_ply(opt.output_file)
     if opt.voxel_size <= 0:
         raise SystemExit("--voxel_size must be positive")
+    if opt.refine_poses < 0 or opt.refine_iterations < 1 or not opt.refine_min_weight > 0:
+        raise SystemExit("--refine_poses must not be negative, --refine_iterations at least 1, --refine_min_weight positive")
     criteria = _component_criteria(opt)
     simplify_cell = None if opt.simplify_cell is None else _simplify_cell(opt.simplify_cell, "--simplify_cell")
     truncation = 4.0 * opt.voxel_size if opt.truncation is None else opt.truncation
@@ -1038,17 +1052,24 @@ def fuse_depth_main(argv=None):
     t_decode = time.perf_counter() - t0
     _require_gpu("fuse_depth", "TSDF fusion is a HIP kernel")
     t0 = time.perf_counter()
-    if opt.sparse:
-        vol = fusion.SparseTSDFVolume(origin, dims, opt.voxel_size, truncation, "cuda", max_blocks=opt.max_voxels // fusion.BLOCK_VOXELS)
-        vol.mark(depth, cam_to_world=c2w, focals=focals, depth_unit=opt.depth_unit, max_depth=opt.max_depth)
-        try:
-            n_blocks = vol.allocate()
-        except ValueError as e:
-            raise SystemExit(f"{e}: the volume would allocate more than --max_voxels {opt.max_voxels} voxels: raise --voxel_size, lower "
-                             f"--max_depth or raise --max_voxels")
-    else:
-        vol = fusion.TSDFVolume(origin, dims, opt.voxel_size, truncation, "cuda")
-    vol.integrate(depth, cam_to_world=c2w, focals=focals, rgb=rgb, depth_unit=opt.depth_unit, max_depth=opt.max_depth)   # 64 frames a call
+    def make_volume():
+        if opt.sparse:
+            return fusion.SparseTSDFVolume(origin, dims, opt.voxel_size, truncation, "cuda", max_blocks=opt.max_voxels // fusion.BLOCK_VOXELS)
+        return fusion.TSDFVolume(origin, dims, opt.voxel_size, truncation, "cuda")
+    rounds = []
+    try:                                                     # mark, allocate, integrate: 64 frames a call
+        if opt.refine_poses:
+            vol, c2w, rounds = fusion.refine_poses(make_volume, depth, c2w, focals, rgb=rgb, rounds=opt.refine_poses, depth_unit=opt.depth_unit,
+                                                   max_depth=opt.max_depth, min_weight=opt.refine_min_weight,
+                                                   max_iterations=opt.refine_iterations)
+        else:
+            vol = fusion.fuse(make_volume, depth, c2w, focals, rgb=rgb, depth_unit=opt.depth_unit, max_depth=opt.max_depth)
+    except fusion.TooManyBlocks as e:
+        raise SystemExit(f"{e}: the volume would allocate more than --max_voxels {opt.max_voxels} voxels: raise --voxel_size, lower "
+                         f"--max_depth or raise --max_voxels")
+    n_blocks = vol.allocated_blocks if opt.sparse else None
+    if opt.refined_pose_file is not None:
+        write_poses_like(opt.refined_pose_file, opt.pose_file, opt.confidence_threshold, [p[2] for p in pairs], c2w)
     vertices, colours, faces = vol.extract_mesh(opt.min_weight)
     known = vol.known_voxels(opt.min_weight)
     dropped = None
@@ -1073,6 +1094,12 @@ def fuse_depth_main(argv=None):
         n_grid, n_vox = grid[0] * grid[1] * grid[2], dims[0] * dims[1] * dims[2]
         log.info(f"Allocated blocks: {n_blocks} of {n_grid} ({100.0 * n_blocks / n_grid:.2f} % of the block grid), "
                  f"{n_blocks * fusion.BLOCK_VOXELS * 20 + n_grid * 5} bytes of volume storage where the dense volume would take {n_vox * 20}.")
+    for k, r in enumerate(rounds):
+        log.info(f"Pose refinement round {k + 1}: {r['converged']} frames converged, {r['degenerate']} degenerate, {r['out_of_iterations']} out "
+                 f"of iterations; mean rms residual {1000.0 * r['rms_before']:.3f} -> {1000.0 * r['rms_after']:.3f} mm, mean pixels used "
+                 f"{r['pixels']:.0f}.")
+    if opt.refined_pose_file is not None:
+        log.info(f"Wrote the refined poses to: {opt.refined_pose_file}")
     log.info(f"Known voxels: {known}. Mesh: {len(vertices)} vertices, {len(faces)} faces.")
     if dropped is not None:
         log.info(f"Extracted mesh: {_component_summary(dropped)}.")

@@ -1,5 +1,5 @@
-// fusion_api.hip -- TSDF fusion of depth maps and surface-net mesh extraction (include/acez.h section K: acez_tsdf_integrate,
-// acez_tsdf_cells, acez_tsdf_faces). fuse_depth.py.
+// fusion_api.hip -- TSDF fusion of depth maps, surface-net mesh extraction and frame-to-model tracking (include/acez.h sections K, K2,
+// K3: acez_tsdf_integrate, acez_tsdf_cells, acez_tsdf_faces, ...). fuse_depth.py.
 //
 // The header's section K is the definition: every float operation below is written in its order, the unit is built with
 // -ffp-contract=off, and tests/tsdf_restated.py restates it in numpy float32 for the bit-for-bit comparison.
@@ -22,6 +22,13 @@
 // cells_blocks,    one 512-thread workgroup per allocated block; the block and its one-voxel halo (a 10^3 tile of storage offsets,
 // faces_blocks     tsdf, weight and, for the faces, the active flags) go to LDS through the table, 13 KB.
 //
+// Section K3 (acez_tsdf_track_accumulate, acez_tsdf_track_accumulate_blocks, acez_tsdf_track_update) refines poses against the volume:
+// accumulate  grid (tiles of the call's largest frame, frames), one lane per depth pixel of a 256-pixel row segment: the pixel's world
+//             point under the frame's device-resident pose (fp64), the trilinear tsdf and its gradient from eight (tsdf, weight)
+//             pairs, the 29 Gauss-Newton terms, reduced by the xor butterfly and the wavefronts in order to one row per tile. The
+//             dense and the block kernel are one template over the function that finds a voxel's element.
+// update      one 256-thread workgroup per frame: the rows' sums in a fixed order, then track_solve.h on thread 0.
+//
 // The dense and the block kernels differ in where a voxel lies, not in what happens to it. The steps they share are device functions:
 // frustum_verdicts (the per-frame skip of a workgroup's box, with the barrier), update_voxel (load, fuse_frames over the call's frames,
 // store if touched), write_vertex and write_quad. The host's checks of the frame arguments are check_frame_call, the rows' own checks
@@ -31,6 +38,7 @@
 
 #include "acez_common.h"
 #include "frame_table.h"
+#include "track_solve.h"
 
 namespace {
 
@@ -522,6 +530,163 @@ __global__ void __launch_bounds__(SB_VOX) faces_blocks_kernel(const float* __res
   }
 }
 
+// ---------------------------------------------------------------------------------------------- section K3: tracking frames against the volume
+constexpr int TK_THREADS = 256, TK_WAVES = TK_THREADS / 64;
+using acez::TRACK_TERMS;
+using acez::TRACK_STATE;
+
+// xor butterfly 32, 16, .. 1: every lane ends with the wavefront's sum, the same bits in all of them (a + b == b + a)
+__device__ __forceinline__ double track_wave_sum(double v) {
+  for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_xor(v, s, 64);
+  return v;
+}
+
+// the TRACK_TERMS values of every lane of the workgroup -> their sums: the butterfly per wavefront, then the wavefronts in ascending
+// order. Threads 0 .. TRACK_TERMS - 1 return the sum of their own term, the others 0. One barrier, reached by every thread.
+__device__ __forceinline__ double track_block_sum(const double (&v)[TRACK_TERMS], double (*s_sum)[TRACK_TERMS]) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < TRACK_TERMS; ++i) {
+    const double w = track_wave_sum(v[i]);
+    if ((t & 63) == 0) s_sum[t >> 6][i] = w;
+  }
+  __syncthreads();
+  double r = 0.0;
+  if (t < TRACK_TERMS) {
+    r = s_sum[0][t];
+    for (int w = 1; w < TK_WAVES; ++w) r = r + s_sum[w][t];
+  }
+  return r;
+}
+
+// where a voxel lies: its element in d_tsdf / d_weight, or -1 for a voxel that has no storage (sparse: a block without a slot).
+// The caller has checked 0 <= i < nx (and alike), so every index formed here is inside the volume or the block table.
+struct DenseAt {
+  __device__ __forceinline__ int64_t operator()(const Volume& vol, int i, int j, int k) const { return ((int64_t)k * vol.ny + j) * vol.nx + i; }
+};
+struct BlocksAt {
+  const int32_t* __restrict__ table;
+  Blocks bl;
+  __device__ __forceinline__ int64_t operator()(const Volume&, int i, int j, int k) const {
+    const int32_t slot = table[((int64_t)(k >> 3) * bl.by + (j >> 3)) * bl.bx + (i >> 3)];
+    if (slot < 0 || slot >= bl.n_blocks) return -1;
+    return (int64_t)slot * SB_VOX + ((k & 7) * SB + (j & 7)) * SB + (i & 7);
+  }
+};
+
+// ACCUMULATE: workgroup (x, f) takes the pixels 256 x .. 256 x + 255 of frame f, one lane per pixel, and writes one row of sums.
+template <class At>
+__global__ void __launch_bounds__(TK_THREADS) track_accumulate_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight, At at,
+                                                                       Volume vol, float tau, const uint16_t* __restrict__ depth,
+                                                                       const acez_tsdf_frame* __restrict__ frames, float depth_unit,
+                                                                       float max_depth, float min_weight, const double* __restrict__ state,
+                                                                       double* __restrict__ partials) {
+  __shared__ double s_sum[TK_WAVES][TRACK_TERMS];
+  const int f = blockIdx.y;
+  const double* st = state + (int64_t)f * TRACK_STATE;          // uniform addresses: scalar loads
+  if (st[acez::TRACK_STATUS] != acez::TRACK_RUNNING) return;    // this frame's loop has stopped (uniform over the workgroup)
+  const acez_tsdf_frame& fr = frames[f];
+  const int64_t n_pix = (int64_t)fr.h * fr.w;
+  if ((int64_t)blockIdx.x * TK_THREADS >= n_pix) return;        // a tile past this frame's own count (uniform)
+  const int t = threadIdx.x;
+  const int64_t p = (int64_t)blockIdx.x * TK_THREADS + t;
+  double v[TRACK_TERMS];
+#pragma unroll
+  for (int i = 0; i < TRACK_TERMS; ++i) v[i] = 0.0;
+  const uint16_t raw = p < n_pix ? depth[fr.offset + p] : (uint16_t)0;   // in [offset, offset + h * w): the host checked that range
+  const float d32 = (float)raw * depth_unit;
+  if (raw != 0 && !(d32 > max_depth)) {
+    const int ix = (int)(p % fr.w), iy = (int)(p / fr.w);
+    const double z = d32;
+    const double x = (((double)ix - (double)fr.ppx) * z) / (double)fr.focal;
+    const double y = (((double)iy - (double)fr.ppy) * z) / (double)fr.focal;
+    const double tr[3] = {st[3], st[7], st[11]};
+    double pw[3], g[3], fl[3];
+    bool ok = true;
+    const double o3[3] = {vol.ox, vol.oy, vol.oz};
+    const int n3[3] = {vol.nx, vol.ny, vol.nz};
+    const double vs = vol.v;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      pw[a] = ((st[4 * a] * x + st[4 * a + 1] * y) + st[4 * a + 2] * z) + tr[a];
+      g[a] = (pw[a] - o3[a]) / vs;
+      fl[a] = floor(g[a]);
+      ok = ok && isfinite(g[a]) && fl[a] >= 0.0 && fl[a] <= (double)(n3[a] - 2);
+    }
+    if (ok) {
+      const int i0 = (int)fl[0], j0 = (int)fl[1], k0 = (int)fl[2];    // 0 <= i0 <= nx - 2 (and alike): all eight corners are voxels
+      double c[8];
+      bool known = true, cut = false;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int64_t el = at(vol, i0 + (e & 1), j0 + ((e >> 1) & 1), k0 + (e >> 2));
+        const float w = el >= 0 ? weight[el] : 0.0f;
+        const float tv = el >= 0 ? tsdf[el] : 1.0f;
+        known = known && (w >= min_weight);
+        cut = cut || !(tv >= 1.0f);
+        c[e] = tv;
+      }
+      if (known && cut) {
+        const double fx = g[0] - fl[0], fy = g[1] - fl[1], fz = g[2] - fl[2];
+        // along x: the four edges (dy, dz) = (0,0), (1,0), (0,1), (1,1); their differences are the x-derivative's corners
+        const double dx00 = c[1] - c[0], dx10 = c[3] - c[2], dx01 = c[5] - c[4], dx11 = c[7] - c[6];
+        const double c00 = c[0] + fx * dx00, c10 = c[2] + fx * dx10, c01 = c[4] + fx * dx01, c11 = c[6] + fx * dx11;
+        const double dy0 = c10 - c00, dy1 = c11 - c01;
+        const double c0 = c00 + fy * dy0, c1 = c01 + fy * dy1;
+        const double dz = c1 - c0;
+        const double value = c0 + fz * dz;
+        const double gx0 = dx00 + fy * (dx10 - dx00), gx1 = dx01 + fy * (dx11 - dx01);
+        const double gx = gx0 + fz * (gx1 - gx0);
+        const double gy = dy0 + fz * (dy1 - dy0);
+        const double td = tau, scale = td / vs;
+        const double r = td * value;
+        const double n[3] = {scale * gx, scale * gy, scale * dz};
+        const double a[3] = {pw[0] - tr[0], pw[1] - tr[1], pw[2] - tr[2]};
+        const double J[6] = {n[0], n[1], n[2], a[1] * n[2] - a[2] * n[1], a[2] * n[0] - a[0] * n[2], a[0] * n[1] - a[1] * n[0]};
+        v[0] = 1.0;
+        int o = acez::TRACK_H;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+          for (int j = i; j < 6; ++j) v[o++] = J[i] * J[j];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) v[acez::TRACK_B + i] = J[i] * r;
+        v[acez::TRACK_R2] = r * r;
+      }
+    }
+  }
+  const double total = track_block_sum(v, s_sum);
+  if (t < TRACK_TERMS) partials[((int64_t)f * gridDim.x + blockIdx.x) * TRACK_TERMS + t] = total;
+}
+
+// UPDATE: one workgroup per frame. Thread t sums the frame's partial rows t, t + 256, .. in ascending order, the workgroup's sums as in
+// ACCUMULATE, thread 0 runs track_update (track_solve.h) on the totals.
+__global__ void __launch_bounds__(TK_THREADS) track_update_kernel(const double* __restrict__ partials, int tiles,
+                                                                   const acez_tsdf_frame* __restrict__ frames, double rel_rms, double damping,
+                                                                   double min_count, int max_iterations, double* state, double* history) {
+  __shared__ double s_sum[TK_WAVES][TRACK_TERMS];
+  __shared__ double s_total[TRACK_TERMS];
+  const int f = blockIdx.x;
+  double* st = state + (int64_t)f * TRACK_STATE;
+  const double records = st[acez::TRACK_RECORDS];
+  if (st[acez::TRACK_STATUS] != acez::TRACK_RUNNING || !(records >= 0.0 && records < (double)max_iterations)) return;   // uniform
+  const acez_tsdf_frame& fr = frames[f];
+  int64_t rows = ((int64_t)fr.h * fr.w + TK_THREADS - 1) / TK_THREADS;     // the table is device data: bound what is formed from it
+  rows = rows < 0 ? 0 : (rows > tiles ? tiles : rows);
+  const int t = threadIdx.x;
+  const double* mine = partials + (int64_t)f * tiles * TRACK_TERMS;
+  double v[TRACK_TERMS];
+#pragma unroll
+  for (int i = 0; i < TRACK_TERMS; ++i) v[i] = 0.0;
+  for (int64_t r = t; r < rows; r += TK_THREADS)
+#pragma unroll
+    for (int i = 0; i < TRACK_TERMS; ++i) v[i] = v[i] + mine[r * TRACK_TERMS + i];
+  const double total = track_block_sum(v, s_sum);
+  if (t < TRACK_TERMS) s_total[t] = total;
+  __syncthreads();
+  if (t == 0) acez::track_update(st, s_total, rel_rms, damping, min_count, history + (int64_t)f * max_iterations * acez::TRACK_RECORD);
+}
+
 }  // namespace
 
 #define FU_REQUIRE_DIMS(limit)                                                                                        \
@@ -701,6 +866,88 @@ extern "C" int acez_tsdf_faces_blocks(const float* d_tsdf, const float* d_weight
   const Volume vol{nx, ny, nz, 0.0f, 0.0f, 0.0f, 1.0f};
   hipLaunchKernelGGL(faces_blocks_kernel, dim3((unsigned)n_blocks), dim3(SB_VOX), 0, (hipStream_t)stream, d_tsdf, d_weight, d_block_table,
                      d_slot_blocks, vol, bl, min_weight, d_active, d_edge_flags, d_vertex_rank, d_edge_rank, d_out_faces, n_faces);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- section K3: tracking frames against the volume
+// what the two ACCUMULATE entry points share; fills `tiles`, the rows per frame of d_partials = the grid's x extent
+static int check_track_call(const uint16_t* d_depth, const acez_tsdf_frame* h_frames, acez_tsdf_frame* d_frames, const double* d_state,
+                            const double* d_partials, float ox, float oy, float oz, float voxel_size, float truncation, float depth_unit,
+                            float max_depth, float min_weight, int64_t n_pixels, int n_frames, int* tiles) {
+  ACEZ_REQUIRE(d_depth && h_frames && d_frames && d_state && d_partials, "null pointer");
+  ACEZ_REQUIRE(isfinite(ox) && isfinite(oy) && isfinite(oz) && isfinite(voxel_size) && voxel_size > 0.0f, "voxel size must be positive, the origin finite");
+  if (int rc = check_frame_call(truncation, depth_unit, max_depth, nullptr, n_pixels, h_frames, n_frames)) return rc;
+  ACEZ_REQUIRE(isfinite(min_weight), "min_weight must be finite");
+  int64_t most = 0;
+  for (int f = 0; f < n_frames; ++f) most = most > (int64_t)h_frames[f].h * h_frames[f].w ? most : (int64_t)h_frames[f].h * h_frames[f].w;
+  *tiles = (int)((most + TK_THREADS - 1) / TK_THREADS);       // <= 2^30 / 256
+  return ACEZ_OK;
+}
+
+template <class At>
+static int launch_track_accumulate(const float* d_tsdf, const float* d_weight, At at, const Volume& vol, float truncation,
+                                   const uint16_t* d_depth, const acez_tsdf_frame* h_frames, int n_frames, acez_tsdf_frame* d_frames,
+                                   int upload, float depth_unit, float max_depth, float min_weight, const double* d_state,
+                                   double* d_partials, int tiles, hipStream_t s) {
+  if (n_frames == 0) return ACEZ_OK;
+  if (upload)
+    if (int rc = acez::upload_frames(d_frames, h_frames, n_frames, s)) return rc;
+  hipLaunchKernelGGL(track_accumulate_kernel<At>, dim3((unsigned)tiles, (unsigned)n_frames), dim3(TK_THREADS), 0, s, d_tsdf, d_weight, at, vol,
+                     truncation, d_depth, (const acez_tsdf_frame*)d_frames, depth_unit, max_depth, min_weight, d_state, d_partials);
+  ACEZ_HIP_CHECK(hipGetLastError());
+  return ACEZ_OK;
+}
+
+extern "C" int acez_tsdf_track_accumulate(const float* d_tsdf, const float* d_weight, int nx, int ny, int nz, float ox, float oy, float oz,
+                                          float voxel_size, float truncation, const uint16_t* d_depth, int64_t n_pixels,
+                                          const acez_tsdf_frame* h_frames, int n_frames, acez_tsdf_frame* d_frames, int upload,
+                                          float depth_unit, float max_depth, float min_weight, const double* d_state, double* d_partials,
+                                          void* stream) {
+  ACEZ_REQUIRE(d_tsdf && d_weight, "null pointer");
+  FU_REQUIRE_DIMS(((int64_t)1 << 31) - 1);
+  int tiles = 0;
+  if (int rc = check_track_call(d_depth, h_frames, d_frames, d_state, d_partials, ox, oy, oz, voxel_size, truncation, depth_unit, max_depth,
+                                min_weight, n_pixels, n_frames, &tiles))
+    return rc;
+  if (int rc = acez::require_device("tracking against the TSDF volume runs on a gfx950 GPU")) return rc;
+  const Volume vol{nx, ny, nz, ox, oy, oz, voxel_size};
+  return launch_track_accumulate(d_tsdf, d_weight, DenseAt{}, vol, truncation, d_depth, h_frames, n_frames, d_frames, upload, depth_unit,
+                                 max_depth, min_weight, d_state, d_partials, tiles, (hipStream_t)stream);
+}
+
+extern "C" int acez_tsdf_track_accumulate_blocks(const float* d_tsdf, const float* d_weight, const int32_t* d_block_table,
+                                                 const int32_t* d_slot_blocks, int n_blocks, int nx, int ny, int nz, float ox, float oy,
+                                                 float oz, float voxel_size, float truncation, const uint16_t* d_depth, int64_t n_pixels,
+                                                 const acez_tsdf_frame* h_frames, int n_frames, acez_tsdf_frame* d_frames, int upload,
+                                                 float depth_unit, float max_depth, float min_weight, const double* d_state,
+                                                 double* d_partials, void* stream) {
+  ACEZ_REQUIRE(d_block_table && (n_blocks <= 0 || (d_tsdf && d_weight && d_slot_blocks)), "null pointer");
+  Blocks bl;
+  if (int rc = check_block_grid(nx, ny, nz, ox, oy, oz, voxel_size, n_blocks, &bl)) return rc;
+  int tiles = 0;
+  if (int rc = check_track_call(d_depth, h_frames, d_frames, d_state, d_partials, ox, oy, oz, voxel_size, truncation, depth_unit, max_depth,
+                                min_weight, n_pixels, n_frames, &tiles))
+    return rc;
+  ACEZ_REQUIRE(min_weight > 0.0f, "min_weight must be positive (a voxel without a block has weight 0)");
+  if (int rc = acez::require_device("tracking against the TSDF volume runs on a gfx950 GPU")) return rc;
+  const Volume vol{nx, ny, nz, ox, oy, oz, voxel_size};
+  return launch_track_accumulate(d_tsdf, d_weight, BlocksAt{d_block_table, bl}, vol, truncation, d_depth, h_frames, n_frames, d_frames, upload,
+                                 depth_unit, max_depth, min_weight, d_state, d_partials, tiles, (hipStream_t)stream);
+}
+
+extern "C" int acez_tsdf_track_update(const double* d_partials, int tiles, const acez_tsdf_frame* d_frames, int n_frames, double rel_rms,
+                                      double damping, int min_count, int max_iterations, double* d_state, double* d_history, void* stream) {
+  ACEZ_REQUIRE(d_partials && d_frames && d_state && d_history, "null pointer");
+  ACEZ_REQUIRE(n_frames >= 0 && n_frames <= ACEZ_TSDF_MAX_FRAMES, "frame count out of range (0 .. 256 per call)");
+  ACEZ_REQUIRE(tiles >= 0, "negative tile count");
+  ACEZ_REQUIRE(max_iterations >= 1, "max_iterations must be at least 1");
+  ACEZ_REQUIRE(isfinite(rel_rms) && rel_rms >= 0.0 && isfinite(damping) && damping >= 0.0, "the tolerance and the damping must be finite and not negative");
+  ACEZ_REQUIRE(min_count >= 6, "min_count must be at least 6 (the unknowns of a pose)");
+  if (int rc = acez::require_device("the tracking update runs on a gfx950 GPU")) return rc;
+  if (n_frames == 0) return ACEZ_OK;
+  hipLaunchKernelGGL(track_update_kernel, dim3((unsigned)n_frames), dim3(TK_THREADS), 0, (hipStream_t)stream, d_partials, tiles, d_frames, rel_rms,
+                     damping, (double)min_count, max_iterations, d_state, d_history);
   ACEZ_HIP_CHECK(hipGetLastError());
   return ACEZ_OK;
 }

@@ -78,6 +78,16 @@ def read_posed_images(pose_file, files, confidence_threshold):
     return c2w, focals, rows
 
 
+def write_poses_like(path, pose_file, confidence_threshold, rows, cam_to_world):
+    """A pose file of the entries `rows` of pose_file (indices into what read_ace_pose_file keeps at this threshold, as
+    read_posed_images returns them), in the order given, with their poses replaced by cam_to_world [k,4,4]; file names, focal lengths
+    and confidences are the input's."""
+    kept = [e for e in read_pose_file(pose_file) if not e.confidence < confidence_threshold]
+    with open(path, "w") as f:
+        for k, T in zip(rows, cam_to_world):
+            write_pose_line(f, kept[k].file, np.linalg.inv(np.asarray(T, np.float64)), kept[k].confidence_text, kept[k].focal)
+
+
 def focal_at_height(focal, h, image_h):
     """A pose file's focal is in pixels of the original image (image_h rows); a depth map or working image of h rows is that image at
     another scale."""

@@ -8,6 +8,9 @@ section 4j; fuse_depth.py is the command line).
 
 The volume lives in HBM; integration and extraction are HIP kernels (acezero_amd/csrc/fusion_api.hip). There is no CPU fallback.
 SparseTSDFVolume is the same function on a block-sparse volume (section K2), for grids whose dense volume does not fit.
+
+    poses, info, _ = vol.track(depth_u16, cam_to_world=poses, focals=f)              # section K3: frame-to-model refinement
+    vol, poses, rounds = refine_poses(make_volume, depth_u16, poses, f, rounds=2)    # fuse, track, fuse again
 """
 import numpy as np
 import torch
@@ -19,8 +22,8 @@ from ._device import no_cpu, ptr as _ptr, stream as _stream
 
 class _Volume:
     """What the dense and the block-sparse volume share: the grid, integrate()'s loop over the calls and the two-pass extraction. A
-    subclass holds the storage (tsdf, weight, colour; None while it has none) and supplies _integrate_call, _elements, _cells and
-    _faces."""
+    subclass holds the storage (tsdf, weight, colour; None while it has none) and supplies _integrate_call, _track_accumulate,
+    _elements, _cells and _faces."""
 
     def __init__(self, origin, dims, voxel_size, truncation, device, max_weight):
         device = torch.device(device)
@@ -87,6 +90,58 @@ class _Volume:
             N.check(self._faces(float(min_weight), _ptr(active), _ptr(flags), _ptr(vrank), _ptr(erank), _ptr(faces), n_f, *tail))
         return vertices, colours, faces
 
+    def track(self, depth_u16, cam_to_world, focals, ppx=None, ppy=None, depth_unit=0.001, max_depth=4.0, min_weight=1.0,
+              max_iterations=10, rel_rms=1e-6, damping=1e-4, min_count=64, frames_per_call=64):
+        """Refine the frames' poses against this volume (include/acez.h section K3): per frame, damped
+        Gauss-Newton on the trilinear SDF at its back-projected depth pixels. Frame arguments as in integrate(); cam_to_world [n,4,4]
+        is taken in float64. Per call of frames_per_call frames the max_iterations ACCUMULATE + UPDATE launches are enqueued back to
+        back: every frame's loop lives on the device, launches after it has stopped pass over it, and the host reads all states and
+        histories back once at the end. Returns (cam_to_world float64 [n,4,4]; one dict per frame: status ("converged",
+        "max_iterations" or "degenerate": too few pixels on known voxels near the surface, or a system that determines no step),
+        iterations, count_first / count_last (pixels used) and rms_first / rms_last (metres) of its first and last record; the history
+        float64 [n,max_iterations,16]: per record the pose it was taken under (12), count, sum r^2, rms, the status after it). The
+        result does not depend on frames_per_call."""
+        self._check_ready("track", min_weight)
+        n, max_iterations = len(depth_u16), int(max_iterations)
+        c2w = np.asarray(cam_to_world.detach().cpu().numpy() if torch.is_tensor(cam_to_world) else cam_to_world, np.float64).reshape(n, -1, 4)
+        if max_iterations < 1:
+            raise ValueError("max_iterations must be at least 1")
+        states, histories = [], []
+        for d_depth, _, rows, d_rows, k in calls(depth_u16, None, c2w, focals, ppx, ppy, None, frames_per_call, self.device):
+            lo = sum(len(s) for s in states)
+            tiles = max((rows[f].h * rows[f].w + TRACK_TILE - 1) // TRACK_TILE for f in range(k))
+            state_h = np.zeros((k, TRACK_STATE))
+            state_h[:, :12] = c2w[lo:lo + k, :3].reshape(k, 12)
+            state = torch.from_numpy(state_h).to(self.device)
+            partials = torch.empty((k, tiles, TRACK_TERMS), dtype=torch.float64, device=self.device)
+            history = torch.zeros((k, max_iterations, TRACK_RECORD), dtype=torch.float64, device=self.device)
+            with torch.cuda.device(self.device):
+                lib, stream = N.lib(), _stream()
+                for it in range(max_iterations):                       # the table is uploaded once; no synchronisation after that
+                    self._track_accumulate(_ptr(d_depth), d_depth.numel(), rows, k, _ptr(d_rows), int(it == 0), float(depth_unit),
+                                           float(max_depth), float(min_weight), _ptr(state), _ptr(partials), stream)
+                    N.check(lib.acez_tsdf_track_update(_ptr(partials), tiles, _ptr(d_rows), k, float(rel_rms), float(damping), int(min_count),
+                                                       max_iterations, _ptr(state), _ptr(history), stream))
+            states.append(state)
+            histories.append(history)
+        if n == 0:
+            return np.zeros((0, 4, 4)), [], np.zeros((0, max_iterations, TRACK_RECORD))
+        both = torch.cat([torch.cat(states).reshape(-1), torch.cat(histories).reshape(-1)]).cpu().numpy()       # the one read-back
+        state_h, history_h = both[:n * TRACK_STATE].reshape(n, TRACK_STATE), both[n * TRACK_STATE:].reshape(n, max_iterations, TRACK_RECORD)
+        poses = np.tile(np.eye(4), (n, 1, 1))
+        poses[:, :3] = state_h[:, :12].reshape(n, 3, 4)
+        info = []
+        for f in range(n):
+            done = int(state_h[f, 13])
+            first, last = history_h[f, 0], history_h[f, max(done - 1, 0)]
+            info.append(dict(status=TRACK_STATUS[int(state_h[f, 12])], iterations=done, count_first=int(first[12]), count_last=int(last[12]),
+                             rms_first=float(first[14]), rms_last=float(last[14])))
+        return poses, info, history_h
+
+
+TRACK_TILE, TRACK_TERMS, TRACK_STATE, TRACK_RECORD = 256, 29, 45, 16      # include/acez.h section K3
+TRACK_STATUS = {0: "max_iterations", 1: "converged", 2: "degenerate"}
+
 
 class TSDFVolume(_Volume):
     """nx x ny x nz voxels of `voxel_size` metres, voxel (0,0,0)'s centre at `origin` (world, OpenCV convention). tsdf, weight
@@ -104,6 +159,9 @@ class TSDFVolume(_Volume):
                                             _ptr(d_depth), _ptr(d_rgb), d_depth.numel(), rows, n, _ptr(d_rows), depth_unit, max_depth,
                                             self.max_weight, frustum_skip, _stream()))
 
+    def _track_accumulate(self, *tail):
+        N.check(N.lib().acez_tsdf_track_accumulate(_ptr(self.tsdf), _ptr(self.weight), *self._grid_args(), self.truncation, *tail))
+
     def _elements(self):
         return self.dims[0] * self.dims[1] * self.dims[2]
 
@@ -112,6 +170,10 @@ class TSDFVolume(_Volume):
 
     def _faces(self, *tail):
         return N.lib().acez_tsdf_faces(_ptr(self.tsdf), _ptr(self.weight), *self.dims, *tail)
+
+
+class TooManyBlocks(ValueError):
+    """SparseTSDFVolume.allocate(): more blocks are marked than max_blocks allows."""
 
 
 BLOCK = 8                                # a block of the sparse volume is 8 x 8 x 8 voxels (include/acez.h section K2)
@@ -179,7 +241,7 @@ class SparseTSDFVolume(_Volume):
         rank = torch.cumsum(self.block_flags, 0, dtype=torch.int32)
         n = int(rank[-1].item())
         if self.max_blocks is not None and n > self.max_blocks:
-            raise ValueError(f"{n} blocks are marked, more than max_blocks {self.max_blocks}")
+            raise TooManyBlocks(f"{n} blocks are marked, more than max_blocks {self.max_blocks}")
         marked = self.block_flags != 0
         bx, by, bz = self.grid
         self.block_table = torch.where(marked, rank - 1, torch.full_like(rank, -1)).reshape(bz, by, bx)
@@ -198,6 +260,10 @@ class SparseTSDFVolume(_Volume):
                                                    self.allocated_blocks, *self._grid_args(), self.truncation, _ptr(d_depth), _ptr(d_rgb),
                                                    d_depth.numel(), rows, n, _ptr(d_rows), depth_unit, max_depth, self.max_weight,
                                                    frustum_skip, _stream()))
+
+    def _track_accumulate(self, *tail):
+        N.check(N.lib().acez_tsdf_track_accumulate_blocks(_ptr(self.tsdf), _ptr(self.weight), _ptr(self.block_table), _ptr(self.slot_blocks),
+                                                          self.allocated_blocks, *self._grid_args(), self.truncation, *tail))
 
     def _elements(self):
         return self.allocated_blocks * BLOCK_VOXELS
@@ -233,6 +299,40 @@ class SparseTSDFVolume(_Volume):
         weight = scatter(self.weight if n else None, 0.0)
         colour = torch.stack([scatter(self.colour[ch] if n else None, 0.0) for ch in range(3)])
         return tsdf, weight, colour
+
+
+def fuse(make_volume, depth, cam_to_world, focals, ppx=None, ppy=None, rgb=None, depth_unit=0.001, max_depth=4.0):
+    """A fresh volume from make_volume() with the frames fused into it; a sparse volume is marked and allocated first."""
+    vol = make_volume()
+    if isinstance(vol, SparseTSDFVolume):
+        vol.mark(depth, cam_to_world=cam_to_world, focals=focals, ppx=ppx, ppy=ppy, depth_unit=depth_unit, max_depth=max_depth)
+        vol.allocate()
+    return vol.integrate(depth, cam_to_world=cam_to_world, focals=focals, ppx=ppx, ppy=ppy, rgb=rgb, depth_unit=depth_unit, max_depth=max_depth)
+
+
+def refine_poses(make_volume, depth, cam_to_world, focals, ppx=None, ppy=None, rgb=None, rounds=1, depth_unit=0.001, max_depth=4.0,
+                 **track_args):
+    """Alternate fusion and tracking `rounds` times: fuse the frames under the current poses into a fresh volume
+    from make_volume() (without colour), track every frame against it (track_args: _Volume.track's keywords), take the tracked poses
+    except for the frames that ended degenerate, which keep the pose they entered the round with; then fuse once more, with colour,
+    under the final poses. Returns (that volume, cam_to_world float64 [n,4,4], per round a dict: info (track's list), poses, converged,
+    degenerate, out_of_iterations (frame counts), rms_before, rms_after (metres, means over the frames that are not degenerate, nan
+    if there is none) and pixels (mean pixels used))."""
+    n = len(depth)
+    poses = np.array(np.asarray(cam_to_world, np.float64).reshape(n, 4, 4))
+    frames = dict(focals=focals, ppx=ppx, ppy=ppy, depth_unit=depth_unit, max_depth=max_depth)
+    stats = []
+    for _ in range(int(rounds)):
+        vol = fuse(make_volume, depth, poses, rgb=None, **frames)
+        tracked, info, _ = vol.track(depth, poses, **frames, **track_args)
+        del vol
+        good = np.array([i["status"] != "degenerate" for i in info], bool)
+        poses[good] = tracked[good]
+        mean = lambda key: float(np.mean([i[key] for i, g in zip(info, good) if g])) if good.any() else float("nan")
+        stats.append(dict(info=info, poses=poses.copy(), converged=sum(i["status"] == "converged" for i in info), degenerate=int((~good).sum()),
+                          out_of_iterations=sum(i["status"] == "max_iterations" for i in info), rms_before=mean("rms_first"),
+                          rms_after=mean("rms_last"), pixels=mean("count_last")))
+    return fuse(make_volume, depth, poses, rgb=rgb, **frames), poses, stats
 
 
 def bounds_from_frames(depth, cam_to_world, focals, voxel_size, truncation, depth_unit=0.001, max_depth=4.0, percentile=0.0, stride=8,

@@ -931,6 +931,100 @@ int acez_tsdf_faces_blocks(const float* d_tsdf, const float* d_weight, const int
                            const int32_t* d_vertex_rank, const int32_t* d_edge_rank, int32_t* d_out_faces, int64_t n_faces, void* stream);
 
 /* =====================================================================================================
+ * K3. Tracking frames against the volume: frame-to-model pose refinement on the SDF (fuse_depth.py --refine_poses)
+ * =====================================================================================================
+ * The volume that all frames built is the model; a frame's pose is moved so that its back-projected depth pixels fall on the model's
+ * zero level (the tracking half of KinectFusion in the SDF form of Bylow et al.: no ray-cast, no correspondences). Gauss-Newton on
+ * the trilinear SDF, the loop resident on the device (acezero_amd.fusion's _Volume.track enqueues
+ * max_iterations ACCUMULATE + UPDATE pairs per call and reads the result back once; tests/track_restated.py restates both in numpy).
+ * The volume, the packed uint16 depth buffer and the frame table are section K's (K2's for the block-sparse twin). Of a row only
+ * focal, ppx, ppy, h, w and offset are used; m must be finite (the rows' checks are section K's) but is ignored: the poses live in
+ * the state. Every frame of a call runs its own loop; frames do not interact.
+ *
+ * STATE. d_state: n_frames records of 45 doubles owned by the caller, frame f at element 45 f. [0..11] the current camera -> world
+ * pose, rows 0..2 of the 4 x 4, row-major (R = columns 0..2, t = column 3); [12] status: 0 running, 1 converged, 2 degenerate;
+ * [13] the number of records written; [14], [15] count and rms of the previous record; [16..44] the 29 totals of the last UPDATE that
+ * ran. A loop starts from the pose, status 0, the rest 0.
+ *
+ * ACCUMULATE (acez_tsdf_track_accumulate; acez_tsdf_track_accumulate_blocks on section K2's storage). Grid (tiles, n_frames) with
+ * tiles = ceil(h w / 256) of the call's LARGEST frame; workgroup (x, f) takes the pixels i = 256 x .. 256 x + 255 of frame f, row-major,
+ * ix = i % w, iy = i / w. A workgroup of a frame whose status != 0 returns at once; so does one with 256 x >= h w of its own frame
+ * (its row of d_partials is never written and never read). Per pixel:
+ *   raw = d_depth[offset + i]. NO SAMPLE if raw == 0 or d32 = float(raw) * depth_unit (fp32, section K step 6) > max_depth.
+ *   From here everything is fp64, round to nearest, one rounding per operation in the order written (the unit is built without
+ *   contraction); floats (d32, ppx, ppy, focal, origin, v, tau, the voxels' tsdf) enter by exact conversion.
+ *   z = d32,  x = ((ix - ppx) * z) / focal,  y = ((iy - ppy) * z) / focal
+ *   pw_a = ((R_a0 x + R_a1 y) + R_a2 z) + t_a                                          (a = 0, 1, 2: the world point)
+ *   g_a = (pw_a - origin_a) / v,  i0_a = floor(g_a),  fr_a = g_a - i0_a
+ *   NO SAMPLE unless on every axis g_a is finite and 0 <= i0_a <= n_a - 2 (all eight corners i0 + (dx, dy, dz) are voxels).
+ *   NO SAMPLE unless all eight corners have weight >= min_weight (fp32 comparison). Sparse: a corner in a block without a slot (table
+ *   entry outside 0 .. n_blocks - 1) has weight 0 and tsdf 1; min_weight must be > 0 there. (d_slot_blocks belongs to the volume's
+ *   description as in K2; the look-up goes through the table alone and does not read it.)
+ *   NO SAMPLE if every corner's tsdf >= 1 (truncated free space: the interpolant is flat, there is no gradient).
+ *   With c_(dx dy dz) the corners' tsdf and (fx, fy, fz) = fr:
+ *     along x, the four edges:  e_(dy dz) = c_(1 dy dz) - c_(0 dy dz),   c_(dy dz) = c_(0 dy dz) + fx * e_(dy dz)
+ *     along y:                  h_dz = c_(1 dz) - c_(0 dz),               c_dz = c_(0 dz) + fy * h_dz
+ *     along z:                  gz = c_1 - c_0,                            value = c_0 + fz * gz
+ *     the analytic derivative of that interpolant in the same nesting:
+ *       gx_dz = e_(0 dz) + fy * (e_(1 dz) - e_(0 dz)),  gx = gx_0 + fz * (gx_1 - gx_0);     gy = h_0 + fz * (h_1 - h_0);     gz as above
+ *   r = tau * value (metres),  n = (tau / v) * (gx, gy, gz)  (the quotient once, then three products)
+ *   a = pw - t: the lever about the pivot, the frame's current camera centre
+ *   J = [n_x, n_y, n_z, a_y n_z - a_z n_y, a_z n_x - a_x n_z, a_x n_y - a_y n_x]           (each cross term: two products, one difference)
+ *   the 29 terms:  [0] 1   [1..21] J_i J_j, i <= j, row-major (the upper triangle of J J^T)   [22..27] J_i r   [28] r r
+ *   A pixel without a sample, and a lane past h w, contributes 29 zeros.
+ * Reduction, section N's: pixel i is lane i % 64 of wavefront (i / 64) % 4 of tile i / 256. Per term: within a wavefront the xor
+ * butterfly v = v + v[lane ^ s] for s = 32, 16, 8, 4, 2, 1, then the tile's four wavefronts added in ascending order,
+ * (((w0 + w1) + w2) + w3). d_partials double [n_frames][tiles][29]: one row per tile. No atomics: nothing depends on scheduling.
+ * The frame table: h_frames is checked on every call (that is what bounds every index the kernel forms) and sizes the grid; with
+ * upload != 0 it is copied into d_frames as in section K (the copy has completed when the call returns), with upload == 0 d_frames
+ * must hold these rows from an earlier call on the same stream, and the call is asynchronous: a loop uploads once.
+ * The voxel loads are the cost: eight fp32 pairs per sample. A tile is a segment of 256 pixels of one or two image rows, whose points
+ * run along a line through the volume, so neighbouring lanes read neighbouring voxels.
+ *
+ * UPDATE (acez_tsdf_track_update). One workgroup of 256 threads per frame; d_frames as ACCUMULATE left it, `tiles` the row stride of
+ * d_partials. If status != 0, or [13] is not in 0 .. max_iterations - 1, it returns at once. Totals: thread t adds the frame's rows
+ * t, t + 256, .. (below min(ceil(h w / 256), tiles)) in ascending order from 0.0, per term; the 256 threads' sums are reduced as above.
+ * Then, in this order (acezero_amd/csrc/track_solve.h is the text; only +, -, *, / and sqrt occur, so that the device, the host
+ * instantiation and numpy give the same bits):
+ *   count = total[0], rms = sqrt(total[28] / count), 0 if count is not > 0
+ *   record [13] of the frame's history (16 doubles each: pose (12), count, total[28], rms, and the status this update ends with) is
+ *   written, [13] += 1, [14], [15] = count, rms, the totals are kept
+ *   (a) from the second record on: |rms - previous| < rel_rms -> status 1, pose unchanged
+ *   (b) a total that is not finite, or count < min_count -> status 2, pose unchanged
+ *   (c) H = the symmetric matrix of [1..21], b = [22..27]; lambda = damping * (((((H00 + H11) + H22) + H33) + H44) + H55) / 6);
+ *       H' = H + lambda I. Cholesky H' = L L^T in place, column j = 0 .. 5: d = H'_jj - L_j0^2 - .. - L_j(j-1)^2 (subtracted in this
+ *       order); d <= 1e-12 * the largest diagonal entry of H' (or not a number) -> status 2, pose unchanged; L_jj = sqrt(d);
+ *       L_ij = (H'_ij - L_i0 L_j0 - .. - L_i(j-1) L_j(j-1)) / L_jj for i > j
+ *   (d) y_i = (b_i - L_i0 y_0 - .. - L_i(i-1) y_(i-1)) / L_ii, i = 0 .. 5;  x_i = (y_i - L_(i+1)i x_(i+1) - .. - L_5i x_5) / L_ii,
+ *       i = 5 .. 0;  (u, omega) = -x
+ *   (e) retraction (Cayley): q = (1, omega / 2) / sqrt(((1 + hx hx) + hy hy) + hz hz) with h = omega / 2, as (qw, qx, qy, qz);
+ *       D = [1 - 2 (qy qy + qz qz), 2 (qx qy - qw qz), 2 (qx qz + qw qy);  2 (qx qy + qw qz), 1 - 2 (qx qx + qz qz), 2 (qy qz - qw qx);
+ *            2 (qx qz - qw qy), 2 (qy qz + qw qx), 1 - 2 (qx qx + qy qy)]
+ *   (f) R <- D R with (D R)_rc = (D_r0 R_0c + D_r1 R_1c) + D_r2 R_2c;  t <- t + u. The pivot is t, so the rotation leaves it in place.
+ *       A new pose that is not finite -> status 2, pose unchanged.
+ * d_history double [n_frames][max_iterations][16].
+ * The damping keeps a direction the frame does not observe (a single wall: sliding in its plane) nearly still; with damping 0 such a
+ * frame ends degenerate. Gauss-Newton on a TSDF sees no further than tau: an error beyond it is not recovered.
+ *
+ * ACCUMULATE without upload and UPDATE are asynchronous on `stream`. ACEZ_ERR_INVALID, before anything is launched, for: what section K
+ * (K2) refuses for the same arguments (dimensions, v, tau, depth_unit, max_depth, the frame count and rows, the block grid and count);
+ * a null d_state, d_partials, d_history, d_frames or volume (the sparse twin takes null storage with n_blocks = 0: every corner is
+ * unknown); min_weight not finite (sparse: not > 0); tiles < 0; max_iterations < 1; rel_rms or damping negative or not finite;
+ * min_count < 6. */
+int acez_tsdf_track_accumulate(const float* d_tsdf, const float* d_weight, int nx, int ny, int nz, float ox, float oy, float oz,
+                               float voxel_size, float truncation, const uint16_t* d_depth, int64_t n_pixels,
+                               const acez_tsdf_frame* h_frames, int n_frames, acez_tsdf_frame* d_frames, int upload, float depth_unit,
+                               float max_depth, float min_weight, const double* d_state, double* d_partials, void* stream);
+int acez_tsdf_track_accumulate_blocks(const float* d_tsdf, const float* d_weight, const int32_t* d_block_table,
+                                      const int32_t* d_slot_blocks, int n_blocks, int nx, int ny, int nz, float ox, float oy, float oz,
+                                      float voxel_size, float truncation, const uint16_t* d_depth, int64_t n_pixels,
+                                      const acez_tsdf_frame* h_frames, int n_frames, acez_tsdf_frame* d_frames, int upload,
+                                      float depth_unit, float max_depth, float min_weight, const double* d_state, double* d_partials,
+                                      void* stream);
+int acez_tsdf_track_update(const double* d_partials, int tiles, const acez_tsdf_frame* d_frames, int n_frames, double rel_rms,
+                           double damping, int min_count, int max_iterations, double* d_state, double* d_history, void* stream);
+
+/* =====================================================================================================
  * L. Dense depth for RGB reconstructions: plane-sweep multi-view stereo (estimate_depth.py)
  * =====================================================================================================
  * Frames arrive as in section K: packed buffers of n_pixels elements and a HOST table of acez_mvs_frame rows (= acez_tsdf_frame:
