@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from tests import helpers
+from tests.head_stage_restated import decode_mask_bits as _decode_mask_bits
 from tests.helpers import big_problem as _big_problem
 from tests.test_head_gpu import _trainer
 
@@ -56,27 +57,6 @@ def test_one_launch_chains_equal_per_layer_launches(name, n):
         new.update()
         torch.cuda.synchronize()
         assert torch.equal(ref.params, new.params) and ref.state() == new.state()
-
-
-def _decode_mask_bits(words, n):
-    """[row tiles, 2048] uint32 words of a layer (RowGemmArgs::mask_out) -> bool [n, 512]: lane-private layout of rowgemm80's accumulators."""
-    mt_n = words.shape[0]
-    w4 = words.reshape(mt_n, 4, 4, 64, 2)                     # [row tile][column tile][wave][lane][x | y]
-    out = np.zeros((mt_n * 80, 512), bool)
-    lane = np.arange(64)
-    fr, fq = lane & 15, lane >> 4
-    for j in range(5):
-        for i in range(2):
-            f = 2 * j + i
-            for nt in range(4):
-                for w in range(4):
-                    rows = (np.arange(mt_n)[:, None] * 80 + j * 16 + fr[None, :])              # [mt, lane]
-                    col0 = nt * 128 + w * 32 + i * 16 + 4 * fq                                 # [lane]
-                    for word, cbase in ((0, 0), (1, 2)):
-                        v = w4[:, nt, w, :, word]
-                        out[rows, (col0 + cbase)[None, :]] = (v >> (9 - f)) & 1
-                        out[rows, (col0 + cbase + 1)[None, :]] = (v >> (25 - f)) & 1
-    return out[:n]
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
