@@ -5,6 +5,7 @@
 
 #include "../../include/acez.h"
 #include "acez_common.h"
+#include "ordered_sum.h"
 
 namespace acez {
 
@@ -38,8 +39,7 @@ __global__ __launch_bounds__(1024) void warp_mean_kernel(const float* __restrict
   const float br = jitter[2 * v];
   float acc = 0.f;
   for (int i = t; i < hw; i += 1024) acc += fminf(fmaxf((img[i] * 0.25f + 0.4f) * br, 0.f), 1.f);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+  acc = wave_sum(acc);
   if ((t & 63) == 0) part[t >> 6] = acc;
   __syncthreads();
   if (t == 0) {
@@ -97,14 +97,8 @@ __global__ __launch_bounds__(256) void warp_mask_kernel(const float* __restrict_
 // (torch's multinomial stream cannot be reproduced). One workgroup = one view x a slice of its samples:
 // inclusive prefix counts of the mask in LDS, one wave per sample (binary search, then a 1 KiB row copy).
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t smix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 __device__ __forceinline__ uint32_t sample_draw(uint64_t seed, uint64_t view_id, uint32_t s) {
-  return (uint32_t)(smix64(smix64(seed ^ (view_id * 0xD1342543DE82EF95ull)) + s) >> 32);
+  return (uint32_t)(mix64(mix64(seed ^ (view_id * 0xD1342543DE82EF95ull)) + s) >> 32);
 }
 
 constexpr int SAMPLE_MAX_HW = 24576;   // feature-map pixels per view the LDS prefix array holds (e.g. 128 x 192)

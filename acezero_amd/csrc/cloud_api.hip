@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "acez_common.h"
+#include "ordered_sum.h"
 
 namespace acez {
 
@@ -38,14 +39,8 @@ struct CloudArgs {
   int32_t* counts;      // [n]
 };
 
-__device__ __forceinline__ uint64_t cloud_smix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 __device__ __forceinline__ uint32_t cloud_draw(uint64_t seed, uint64_t frame, uint32_t j) {
-  return (uint32_t)(cloud_smix64(cloud_smix64(seed ^ (frame * 0xA0761D6478BD642Full)) + j) >> 32);
+  return (uint32_t)(mix64(mix64(seed ^ (frame * 0xA0761D6478BD642Full)) + j) >> 32);
 }
 
 // exclusive scan of one int per thread (256 threads); returns the exclusive prefix, *total = sum

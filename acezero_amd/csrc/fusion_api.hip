@@ -25,9 +25,9 @@
 // Section K3 (acez_tsdf_track_accumulate, acez_tsdf_track_accumulate_blocks, acez_tsdf_track_update) refines poses against the volume:
 // accumulate  grid (tiles of the call's largest frame, frames), one lane per depth pixel of a 256-pixel row segment: the pixel's world
 //             point under the frame's device-resident pose (fp64), the trilinear tsdf and its gradient from eight (tsdf, weight)
-//             pairs, the 29 Gauss-Newton terms, reduced by the xor butterfly and the wavefronts in order to one row per tile. The
-//             dense and the block kernel are one template over the function that finds a voxel's element.
-// update      one 256-thread workgroup per frame: the rows' sums in a fixed order, then track_solve.h on thread 0.
+//             pairs, the 29 Gauss-Newton terms, reduced in the order of ordered_sum.h to one row per tile. The dense and the block
+//             kernel are one template over the function that finds a voxel's element.
+// update      one 256-thread workgroup per frame: the rows' sums in that order, then track_solve.h on thread 0.
 //
 // The dense and the block kernels differ in where a voxel lies, not in what happens to it. The steps they share are device functions:
 // frustum_verdicts (the per-frame skip of a workgroup's box, with the barrier), update_voxel (load, fuse_frames over the call's frames,
@@ -38,6 +38,7 @@
 
 #include "acez_common.h"
 #include "frame_table.h"
+#include "ordered_sum.h"
 #include "track_solve.h"
 
 namespace {
@@ -535,30 +536,6 @@ constexpr int TK_THREADS = 256, TK_WAVES = TK_THREADS / 64;
 using acez::TRACK_TERMS;
 using acez::TRACK_STATE;
 
-// xor butterfly 32, 16, .. 1: every lane ends with the wavefront's sum, the same bits in all of them (a + b == b + a)
-__device__ __forceinline__ double track_wave_sum(double v) {
-  for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_xor(v, s, 64);
-  return v;
-}
-
-// the TRACK_TERMS values of every lane of the workgroup -> their sums: the butterfly per wavefront, then the wavefronts in ascending
-// order. Threads 0 .. TRACK_TERMS - 1 return the sum of their own term, the others 0. One barrier, reached by every thread.
-__device__ __forceinline__ double track_block_sum(const double (&v)[TRACK_TERMS], double (*s_sum)[TRACK_TERMS]) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < TRACK_TERMS; ++i) {
-    const double w = track_wave_sum(v[i]);
-    if ((t & 63) == 0) s_sum[t >> 6][i] = w;
-  }
-  __syncthreads();
-  double r = 0.0;
-  if (t < TRACK_TERMS) {
-    r = s_sum[0][t];
-    for (int w = 1; w < TK_WAVES; ++w) r = r + s_sum[w][t];
-  }
-  return r;
-}
-
 // where a voxel lies: its element in d_tsdf / d_weight, or -1 for a voxel that has no storage (sparse: a block without a slot).
 // The caller has checked 0 <= i < nx (and alike), so every index formed here is inside the volume or the block table.
 struct DenseAt {
@@ -584,7 +561,7 @@ __global__ void __launch_bounds__(TK_THREADS) track_accumulate_kernel(const floa
   __shared__ double s_sum[TK_WAVES][TRACK_TERMS];
   const int f = blockIdx.y;
   const double* st = state + (int64_t)f * TRACK_STATE;          // uniform addresses: scalar loads
-  if (st[acez::TRACK_STATUS] != acez::TRACK_RUNNING) return;    // this frame's loop has stopped (uniform over the workgroup)
+  if (st[acez::LOOP_STATUS] != acez::LOOP_RUNNING) return;      // this frame's loop has stopped (uniform over the workgroup)
   const acez_tsdf_frame& fr = frames[f];
   const int64_t n_pix = (int64_t)fr.h * fr.w;
   if ((int64_t)blockIdx.x * TK_THREADS >= n_pix) return;        // a tile past this frame's own count (uniform)
@@ -655,12 +632,12 @@ __global__ void __launch_bounds__(TK_THREADS) track_accumulate_kernel(const floa
       }
     }
   }
-  const double total = track_block_sum(v, s_sum);
+  const double total = acez::block_sum_terms<TRACK_TERMS, TK_WAVES>(v, s_sum);
   if (t < TRACK_TERMS) partials[((int64_t)f * gridDim.x + blockIdx.x) * TRACK_TERMS + t] = total;
 }
 
-// UPDATE: one workgroup per frame. Thread t sums the frame's partial rows t, t + 256, .. in ascending order, the workgroup's sums as in
-// ACCUMULATE, thread 0 runs track_update (track_solve.h) on the totals.
+// UPDATE: one workgroup per frame sums the frame's partial rows (sum_rows of ordered_sum.h), thread 0 runs track_update (track_solve.h)
+// on the totals.
 __global__ void __launch_bounds__(TK_THREADS) track_update_kernel(const double* __restrict__ partials, int tiles,
                                                                    const acez_tsdf_frame* __restrict__ frames, double rel_rms, double damping,
                                                                    double min_count, int max_iterations, double* state, double* history) {
@@ -668,23 +645,12 @@ __global__ void __launch_bounds__(TK_THREADS) track_update_kernel(const double* 
   __shared__ double s_total[TRACK_TERMS];
   const int f = blockIdx.x;
   double* st = state + (int64_t)f * TRACK_STATE;
-  const double records = st[acez::TRACK_RECORDS];
-  if (st[acez::TRACK_STATUS] != acez::TRACK_RUNNING || !(records >= 0.0 && records < (double)max_iterations)) return;   // uniform
+  if (!acez::loop_live(st, max_iterations)) return;                        // uniform
   const acez_tsdf_frame& fr = frames[f];
   int64_t rows = ((int64_t)fr.h * fr.w + TK_THREADS - 1) / TK_THREADS;     // the table is device data: bound what is formed from it
   rows = rows < 0 ? 0 : (rows > tiles ? tiles : rows);
-  const int t = threadIdx.x;
-  const double* mine = partials + (int64_t)f * tiles * TRACK_TERMS;
-  double v[TRACK_TERMS];
-#pragma unroll
-  for (int i = 0; i < TRACK_TERMS; ++i) v[i] = 0.0;
-  for (int64_t r = t; r < rows; r += TK_THREADS)
-#pragma unroll
-    for (int i = 0; i < TRACK_TERMS; ++i) v[i] = v[i] + mine[r * TRACK_TERMS + i];
-  const double total = track_block_sum(v, s_sum);
-  if (t < TRACK_TERMS) s_total[t] = total;
-  __syncthreads();
-  if (t == 0) acez::track_update(st, s_total, rel_rms, damping, min_count, history + (int64_t)f * max_iterations * acez::TRACK_RECORD);
+  acez::sum_rows<TRACK_TERMS, TK_THREADS>(partials + (int64_t)f * tiles * TRACK_TERMS, rows, s_sum, s_total);
+  if (threadIdx.x == 0) acez::track_update(st, s_total, rel_rms, damping, min_count, history + (int64_t)f * max_iterations * acez::TRACK_RECORD);
 }
 
 }  // namespace

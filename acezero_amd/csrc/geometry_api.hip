@@ -16,9 +16,9 @@
 //              own 3 x 3 x 3 cells through L2. Both forms give the same bits.
 // voxel_means  one lane per segment, a sequential sum in array order.
 // icp          ACCUMULATE is the nearest kernel with the query computed from the source point and the device-resident transform, and
-//              with the 18 fp64 moments of the lane's correspondence reduced per workgroup in a fixed order (one search_nearest for
-//              both kernels); UPDATE is one workgroup that sums the workgroups' rows and runs the solve of icp_solve.h. Both return at
-//              once when the state says the loop has stopped, so a whole stage is enqueued without a host round trip.
+//              with the 18 fp64 moments of the lane's correspondence reduced per workgroup in ordered_sum.h's order (one search_nearest
+//              for both kernels); UPDATE is one workgroup that sums the workgroups' rows and runs the solve of icp_solve.h. Both return
+//              at once when the state says the loop has stopped (device_loop.h): a whole stage is enqueued without a host round trip.
 // No atomics, no communication between workgroups, plain loads and stores. Every range read from the cell table is clamped to
 // [0, m], so every loop is bounded by m and a malformed table cannot cause a read out of bounds.
 #include <limits.h>
@@ -28,6 +28,7 @@
 #include "acez_common.h"
 #include "icp_solve.h"
 #include "launch1d.h"
+#include "ordered_sum.h"
 
 namespace {
 
@@ -185,29 +186,6 @@ __global__ void __launch_bounds__(GN_THREADS) geom_nearest_kernel(const float* _
   }
 }
 
-// xor butterfly 32, 16, .. 1: every lane ends with the wavefront's sum, the same bits in all of them (a + b == b + a)
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_xor(v, s, 64);
-  return v;
-}
-
-// the ICP_TERMS values of every lane of the workgroup -> their sums: the butterfly per wavefront, then the wavefronts in ascending
-// order. Threads 0 .. ICP_TERMS - 1 return the sum of their own term, the others 0.
-__device__ __forceinline__ double block_sum_terms(const double (&v)[ICP_TERMS], double (*s_sum)[ICP_TERMS]) {
-  const int t = threadIdx.x;
-  for (int i = 0; i < ICP_TERMS; ++i) {
-    const double w = wave_sum(v[i]);
-    if ((t & 63) == 0) s_sum[t >> 6][i] = w;
-  }
-  __syncthreads();
-  double r = 0.0;
-  if (t < ICP_TERMS) {
-    r = s_sum[0][t];
-    for (int w = 1; w < GN_WAVES; ++w) r = r + s_sum[w][t];
-  }
-  return r;
-}
-
 // ACCUMULATE: one lane per source point. x' = T x in fp64 rounded once, the search of NEAREST on x', the 18 terms of the lane's
 // correspondence (zeros without one), one row of sums per workgroup.
 __global__ void __launch_bounds__(GN_THREADS) geom_icp_accumulate_kernel(const float* __restrict__ ref, const int32_t* __restrict__ ref_index,
@@ -215,7 +193,7 @@ __global__ void __launch_bounds__(GN_THREADS) geom_icp_accumulate_kernel(const f
                                                                           const float* __restrict__ src, int64_t n, float r2, float px, float py,
                                                                           float pz, const double* state, double* __restrict__ partials, int plain) {
   __shared__ double s_sum[GN_WAVES][ICP_TERMS];
-  if (state[ICP_STATUS] != ICP_RUNNING) return;                   // the loop has stopped (uniform over the grid)
+  if (state[LOOP_STATUS] != LOOP_RUNNING) return;                 // the loop has stopped (uniform over the grid)
   const int t = threadIdx.x;
   const int64_t q = (int64_t)blockIdx.x * GN_THREADS + t;
   float qx = 0.0f, qy = 0.0f, qz = 0.0f;
@@ -243,28 +221,19 @@ __global__ void __launch_bounds__(GN_THREADS) geom_icp_accumulate_kernel(const f
     v[16] = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2];
     v[17] = (double)best.d2;
   }
-  const double total = block_sum_terms(v, s_sum);
+  const double total = block_sum_terms<ICP_TERMS, GN_WAVES>(v, s_sum);
   if (t < ICP_TERMS) partials[(int64_t)blockIdx.x * ICP_TERMS + t] = total;
 }
 
-// UPDATE: one workgroup. Thread t sums the partial rows t, t + 256, .. in ascending order, the workgroup's sums as in ACCUMULATE,
-// thread 0 runs icp_update (icp_solve.h) on the totals.
+// UPDATE: one workgroup sums the partial rows (sum_rows of ordered_sum.h), thread 0 runs icp_update (icp_solve.h) on the totals.
 __global__ void __launch_bounds__(GN_THREADS) geom_icp_update_kernel(const double* __restrict__ partials, int64_t rows, int64_t n, float px,
                                                                       float py, float pz, int with_scale, double rel_fitness, double rel_rmse,
                                                                       int max_iterations, double* state, double* history) {
   __shared__ double s_sum[GN_WAVES][ICP_TERMS];
   __shared__ double s_total[ICP_TERMS];
-  const double iteration = state[ICP_ITERATIONS];
-  if (state[ICP_STATUS] != ICP_RUNNING || !(iteration >= 0.0 && iteration < (double)max_iterations)) return;   // uniform
-  const int t = threadIdx.x;
-  double v[ICP_TERMS];
-  for (int i = 0; i < ICP_TERMS; ++i) v[i] = 0.0;
-  for (int64_t r = t; r < rows; r += GN_THREADS)
-    for (int i = 0; i < ICP_TERMS; ++i) v[i] = v[i] + partials[r * ICP_TERMS + i];
-  const double total = block_sum_terms(v, s_sum);
-  if (t < ICP_TERMS) s_total[t] = total;
-  __syncthreads();
-  if (t == 0) {
+  if (!loop_live(state, max_iterations)) return;                  // uniform
+  sum_rows<ICP_TERMS, GN_THREADS>(partials, rows, s_sum, s_total);
+  if (threadIdx.x == 0) {
     const double pivot[3] = {(double)px, (double)py, (double)pz};
     icp_update(state, s_total, n, pivot, with_scale, rel_fitness, rel_rmse, history);
   }

@@ -6,15 +6,15 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "device_loop.h"
 #include "svd3.h"
 
 namespace acez {
 
 constexpr int ICP_TERMS = 18;        // 1, a (3), b (3), b (x) a (9, row r of b, column c of a at 7 + 3 r + c), |a|^2, d2
-constexpr int ICP_STATE = 34;        // doubles: T rows 0..2 (12), status, iterations, previous fitness, previous rmse, last totals (18)
-constexpr int ICP_RECORD = 16;       // doubles per history record: T (12), count, sum d2, fitness, rmse
-constexpr int ICP_STATUS = 12, ICP_ITERATIONS = 13, ICP_PREV_FITNESS = 14, ICP_PREV_RMSE = 15, ICP_TOTALS = 16;
-constexpr double ICP_RUNNING = 0.0, ICP_CONVERGED = 1.0, ICP_DEGENERATE = 2.0;
+constexpr int ICP_STATE = 34;        // doubles: device_loop.h's 16 (T, status, iterations, previous fitness, previous rmse), last totals (18)
+constexpr int ICP_RECORD = LOOP_RECORD;   // T (12), count, sum d2, fitness, rmse
+constexpr int ICP_PREV_FITNESS = 14, ICP_PREV_RMSE = 15;
 
 // The Umeyama step on the totals s: T <- Delta * T with Delta(x') = scale R (x' - pivot - mean a) + mean b + pivot. false, and T
 // untouched, if the correspondences do not determine it: fewer than 3, a total that is not finite, the covariance's second singular
@@ -56,7 +56,7 @@ __host__ __device__ inline bool icp_solve(const double* s, const double* pivot, 
 // One UPDATE on a running state (the caller has checked status and iteration count): the record, rule (a), rule (b), the step.
 __host__ __device__ inline void icp_update(double* state, const double* totals, int64_t n, const double* pivot, int with_scale,
                                            double rel_fitness, double rel_rmse, double* history) {
-  const int64_t it = (int64_t)state[ICP_ITERATIONS];
+  const int64_t it = (int64_t)state[LOOP_COUNT];
   const double count = totals[0], sum_d2 = totals[17];
   const double fitness = count / (double)n, rmse = sqrt(sum_d2 / count);
   double* rec = history + it * ICP_RECORD;
@@ -66,15 +66,15 @@ __host__ __device__ inline void icp_update(double* state, const double* totals, 
   rec[14] = fitness;
   rec[15] = rmse;
   const double prev_fitness = state[ICP_PREV_FITNESS], prev_rmse = state[ICP_PREV_RMSE];
-  state[ICP_ITERATIONS] = (double)(it + 1);
+  state[LOOP_COUNT] = (double)(it + 1);
   state[ICP_PREV_FITNESS] = fitness;
   state[ICP_PREV_RMSE] = rmse;
-  for (int i = 0; i < ICP_TERMS; ++i) state[ICP_TOTALS + i] = totals[i];
+  for (int i = 0; i < ICP_TERMS; ++i) state[LOOP_TOTALS + i] = totals[i];
   if (it >= 1 && fabs(fitness - prev_fitness) < rel_fitness && fabs(rmse - prev_rmse) < rel_rmse) {
-    state[ICP_STATUS] = ICP_CONVERGED;
+    state[LOOP_STATUS] = LOOP_CONVERGED;
     return;
   }
-  if (!icp_solve(totals, pivot, with_scale, state)) state[ICP_STATUS] = ICP_DEGENERATE;
+  if (!icp_solve(totals, pivot, with_scale, state)) state[LOOP_STATUS] = LOOP_DEGENERATE;
 }
 
 }  // namespace acez

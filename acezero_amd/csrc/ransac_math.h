@@ -14,18 +14,14 @@
 #define ACEZ_HD __host__ __device__
 #endif
 #include "det_math.h"
+#include "ordered_sum.h"
 
 namespace rsm {
 
 // ----------------------------------------------------------------------------------------------------
 // D1: counter-based random stream
 // ----------------------------------------------------------------------------------------------------
-ACEZ_HD inline uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ULL;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-  return z ^ (z >> 31);
-}
+using acez::mix64;
 ACEZ_HD inline uint64_t try_key(uint64_t seed, uint64_t frame, uint32_t hyp, uint32_t tr) {
   return mix64(mix64(mix64(seed) ^ frame) ^ (((uint64_t)hyp << 32) | (uint64_t)tr));
 }

@@ -4,6 +4,7 @@
 // forward kernel's code, so both kernels draw, score and refine with the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "ordered_sum.h"
 #include "ransac_math.h"
 #include "ransac_ctx.h"
 #include "svd3.h"
@@ -57,12 +58,7 @@ struct Frame {
   int nv;
 };
 
-// butterfly v_l + v_(l ^ off), off = 32, 16, .., 1: every lane ends with the same bits
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);
-  return v;
-}
+using acez::wave_sum;   // ordered_sum.h
 
 // get3DDistErrs for one cell: transform() rounds R X + t to float (cv::Point3f), the difference is a float vector, cv::norm
 // its fp64 length; (float) length * 100, clamped (a NaN length takes the clamp value)

@@ -27,6 +27,7 @@
 
 #include "acez_common.h"
 #include "launch1d.h"
+#include "ordered_sum.h"
 #include "simplify_solve.h"
 
 namespace {
@@ -112,9 +113,9 @@ __device__ __forceinline__ void cell_centre(const int64_t* __restrict__ sorted_k
 }
 
 // One wavefront per cluster, the wavefronts striding over the clusters. Lane l adds the corners l, l + 64, .. of the cluster's segment
-// corner_seg[c] .. corner_seg[c + 1] - 1 to its nine sums, serially; then the xor butterfly 32, 16, .. 1 (a + b == b + a: every lane
-// ends with the same bits) and lane 0 stores. The clusters are 0 .. K - 1 without a gap, so the first empty vertex segment ends a
-// wavefront's walk: the loop is bounded by m / (the number of wavefronts).
+// corner_seg[c] .. corner_seg[c + 1] - 1 to its nine sums, serially; then wave_sum (ordered_sum.h) and lane 0 stores. The clusters
+// are 0 .. K - 1 without a gap, so the first empty vertex segment ends a wavefront's walk: the loop is bounded by m / (the number of
+// wavefronts).
 __global__ void __launch_bounds__(SQ_THREADS) quadrics_kernel(const float* __restrict__ vertices, int m, const int32_t* __restrict__ faces, int64_t k,
                                                               const int64_t* __restrict__ sorted_keys, const int64_t* __restrict__ seg,
                                                               const int64_t* __restrict__ corner_order, const int64_t* __restrict__ corner_seg,
@@ -143,8 +144,7 @@ __global__ void __launch_bounds__(SQ_THREADS) quadrics_kernel(const float* __res
       }
       simplify_add_corner(pa, pb, pc, q);
     }
-    for (int step = SQ_WAVE / 2; step >= 1; step /= 2)
-      for (int j = 0; j < SIMPLIFY_TERMS; ++j) q[j] = q[j] + __shfl_xor(q[j], step, SQ_WAVE);
+    wave_sum(q);
     if (lane == 0)
       for (int j = 0; j < SIMPLIFY_TERMS; ++j) out_quadrics[SIMPLIFY_TERMS * c + j] = q[j];
   }

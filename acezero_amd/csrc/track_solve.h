@@ -7,14 +7,15 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "device_loop.h"
+
 namespace acez {
 
 constexpr int TRACK_TERMS = 29;      // 1, the upper triangle of J J^T row-major (21), J r (6), r^2
-constexpr int TRACK_STATE = 45;      // doubles: pose rows 0..2 (12), status, records, previous count, previous rms, last totals (29)
-constexpr int TRACK_RECORD = 16;     // doubles per history record: pose (12), count, sum r^2, rms, the status after this update
-constexpr int TRACK_STATUS = 12, TRACK_RECORDS = 13, TRACK_PREV_COUNT = 14, TRACK_PREV_RMS = 15, TRACK_TOTALS = 16;
+constexpr int TRACK_STATE = 45;      // doubles: device_loop.h's 16 (pose, status, records, previous count, previous rms), last totals (29)
+constexpr int TRACK_RECORD = LOOP_RECORD;   // pose (12), count, sum r^2, rms, the status after this update
+constexpr int TRACK_PREV_COUNT = 14, TRACK_PREV_RMS = 15;
 constexpr int TRACK_H = 1, TRACK_B = 22, TRACK_R2 = 28;
-constexpr double TRACK_RUNNING = 0.0, TRACK_CONVERGED = 1.0, TRACK_DEGENERATE = 2.0;
 
 // The step on the totals s: pose <- (R_delta R, t + u) with (u, omega) = -(H + damping * (trace(H) / 6) * I)^-1 b. false, and the pose
 // untouched, if a pivot of the Cholesky factorisation is <= 1e-12 x the largest diagonal entry, or the new pose is not finite.
@@ -80,7 +81,7 @@ __host__ __device__ inline bool track_solve(const double* s, double damping, dou
 // One UPDATE on a running state (the caller has checked status and record count): the record, rule (a), rule (b), the step.
 __host__ __device__ inline void track_update(double* state, const double* totals, double rel_rms, double damping, double min_count,
                                              double* history) {
-  const int64_t it = (int64_t)state[TRACK_RECORDS];
+  const int64_t it = (int64_t)state[LOOP_COUNT];
   const double count = totals[0], sum_r2 = totals[TRACK_R2];
   const double rms = count > 0.0 ? sqrt(sum_r2 / count) : 0.0;
   double* rec = history + it * TRACK_RECORD;
@@ -89,18 +90,18 @@ __host__ __device__ inline void track_update(double* state, const double* totals
   rec[13] = sum_r2;
   rec[14] = rms;
   const double prev_rms = state[TRACK_PREV_RMS];
-  state[TRACK_RECORDS] = (double)(it + 1);
+  state[LOOP_COUNT] = (double)(it + 1);
   state[TRACK_PREV_COUNT] = count;
   state[TRACK_PREV_RMS] = rms;
-  for (int i = 0; i < TRACK_TERMS; ++i) state[TRACK_TOTALS + i] = totals[i];
-  double status = TRACK_RUNNING;
+  for (int i = 0; i < TRACK_TERMS; ++i) state[LOOP_TOTALS + i] = totals[i];
+  double status = LOOP_RUNNING;
   bool finite = true;
   for (int i = 0; i < TRACK_TERMS; ++i) finite = finite && isfinite(totals[i]);
   if (it >= 1 && fabs(rms - prev_rms) < rel_rms)
-    status = TRACK_CONVERGED;
+    status = LOOP_CONVERGED;
   else if (!finite || count < min_count || !track_solve(totals, damping, state))
-    status = TRACK_DEGENERATE;
-  state[TRACK_STATUS] = status;
+    status = LOOP_DEGENERATE;
+  state[LOOP_STATUS] = status;
   rec[15] = status;
 }
 

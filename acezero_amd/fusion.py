@@ -17,7 +17,7 @@ import torch
 
 from . import _native as N
 from .frames import _per_frame, _w2c34, calls  # noqa: F401  (_w2c34: the tests restate poses through fusion._w2c34)
-from ._device import no_cpu, ptr as _ptr, stream as _stream
+from ._device import no_cpu, ptr as _ptr, read_loops, stream as _stream
 
 
 class _Volume:
@@ -126,15 +126,13 @@ class _Volume:
             histories.append(history)
         if n == 0:
             return np.zeros((0, 4, 4)), [], np.zeros((0, max_iterations, TRACK_RECORD))
-        both = torch.cat([torch.cat(states).reshape(-1), torch.cat(histories).reshape(-1)]).cpu().numpy()       # the one read-back
-        state_h, history_h = both[:n * TRACK_STATE].reshape(n, TRACK_STATE), both[n * TRACK_STATE:].reshape(n, max_iterations, TRACK_RECORD)
+        state_h, history_h, status, done = read_loops(states, histories)                                        # the one read-back
         poses = np.tile(np.eye(4), (n, 1, 1))
         poses[:, :3] = state_h[:, :12].reshape(n, 3, 4)
         info = []
         for f in range(n):
-            done = int(state_h[f, 13])
-            first, last = history_h[f, 0], history_h[f, max(done - 1, 0)]
-            info.append(dict(status=TRACK_STATUS[int(state_h[f, 12])], iterations=done, count_first=int(first[12]), count_last=int(last[12]),
+            first, last = history_h[f, 0], history_h[f, max(done[f] - 1, 0)]
+            info.append(dict(status=TRACK_STATUS[status[f]], iterations=int(done[f]), count_first=int(first[12]), count_last=int(last[12]),
                              rms_first=float(first[14]), rms_last=float(last[14])))
         return poses, info, history_h
 

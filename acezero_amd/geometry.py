@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from ._device import no_cpu, ptr as _ptr, stream as _stream
+from ._device import no_cpu, ptr as _ptr, read_loops, stream as _stream
 
 MAX_DIM = 1024                      # cells per axis (section N)
 MAX_CELLS = 2 ** 24
@@ -146,7 +146,8 @@ def nearest_distances(query, ref, radius, cell=None):
     return d2, index
 
 
-ICP_STATUS = {0: "max_iterations", 1: "converged", 2: "degenerate"}     # state[12]; a loop still running after the last pair ran out
+ICP_TILE, ICP_TERMS, ICP_STATE, ICP_RECORD = 256, 18, 34, 16           # include/acez.h section N
+ICP_STATUS = {0: "max_iterations", 1: "converged", 2: "degenerate"}     # a loop still running after the last pair ran out
 
 
 def icp_stage(src, tgt, radius, *, max_iterations=30, with_scale=False, rel_fitness=1e-6, rel_rmse=1e-6, cell=None):
@@ -175,10 +176,10 @@ def icp_stage(src, tgt, radius, *, max_iterations=30, with_scale=False, rel_fitn
     pivot = (g.origin + g.hi) * np.float32(0.5)
     pivot = [float(v) if np.isfinite(v) else 0.0 for v in pivot]
     src_sorted = src[order_by_cell(src, g)].contiguous()
-    state = torch.zeros(34, dtype=torch.float64, device=dev)
+    state = torch.zeros(ICP_STATE, dtype=torch.float64, device=dev)
     state[[0, 5, 10]] = 1.0
-    partials = torch.empty(((n + 255) // 256, 18), dtype=torch.float64, device=dev)
-    history = torch.zeros((max_iterations, 16), dtype=torch.float64, device=dev)
+    partials = torch.empty(((n + ICP_TILE - 1) // ICP_TILE, ICP_TERMS), dtype=torch.float64, device=dev)
+    history = torch.zeros((max_iterations, ICP_RECORD), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         lib, stream = N.lib(), _stream()
         for _ in range(max_iterations):                            # no synchronisation in between
@@ -187,12 +188,10 @@ def icp_stage(src, tgt, radius, *, max_iterations=30, with_scale=False, rel_fitn
                                                  pivot[0], pivot[1], pivot[2], _ptr(state), _ptr(partials), stream))
             N.check(lib.acez_geom_icp_update(_ptr(partials), n, pivot[0], pivot[1], pivot[2], int(bool(with_scale)), float(rel_fitness),
                                              float(rel_rmse), max_iterations, _ptr(state), _ptr(history), stream))
-    both = torch.cat([state, history.reshape(-1)]).cpu().numpy()  # the one read-back
-    state_h, history_h = both[:34], both[34:].reshape(max_iterations, 16)
-    done = int(state_h[13])
+    (state_h,), (history_h,), (status,), (done,) = read_loops([state[None]], [history[None]])      # the one read-back
     T = np.eye(4)
     T[:3] = state_h[:12].reshape(3, 4)
-    info = {"status": ICP_STATUS[int(state_h[12])], "iterations": done, "fitness": [float(v) for v in history_h[:done, 14]],
+    info = {"status": ICP_STATUS[status], "iterations": int(done), "fitness": [float(v) for v in history_h[:done, 14]],
             "rmse": [float(v) for v in history_h[:done, 15]], "count": [int(v) for v in history_h[:done, 12]],
             "sum_d2": [float(v) for v in history_h[:done, 13]],
             "transforms": [np.vstack([history_h[k, :12].reshape(3, 4), [0.0, 0.0, 0.0, 1.0]]) for k in range(done)]}

@@ -7,12 +7,12 @@ import functools
 import numpy as np
 
 from tests import geometry_restated as R
+from tests.ordered_sums import block_sums, totals  # noqa: F401  (the header's summation order; the tests call I.block_sums, I.totals)
 
 F = np.float32
-BLOCK, WAVE, TERMS = 256, 64, 18
+TERMS = 18
 RUNNING, CONVERGED, DEGENERATE = 0, 1, 2
 STATUS = {RUNNING: "max_iterations", CONVERGED: "converged", DEGENERATE: "degenerate"}
-LANES = np.arange(WAVE)
 
 
 # ------------------------------------------------------------------------------------------------------------------ the cases
@@ -73,33 +73,6 @@ def terms(x, q, d2, found, pivot):
         t[:, 16] = (a[:, 0] * a[:, 0] + a[:, 1] * a[:, 1]) + a[:, 2] * a[:, 2]
         t[:, 17] = d2.astype(np.float64)
     return np.where(found[:, None], t, 0.0)
-
-
-def block_sums(t):
-    """float64 [ceil(n / 256), 18] from [n,18]: source i is lane i % 64 of wavefront (i / 64) % 4 of workgroup i / 256; per wavefront
-    the xor butterfly 32, 16, .. 1, then the wavefronts in ascending order."""
-    blocks = (len(t) + BLOCK - 1) // BLOCK
-    v = np.zeros((blocks * BLOCK, TERMS))
-    v[:len(t)] = t
-    v = v.reshape(blocks, BLOCK // WAVE, WAVE, TERMS)
-    for s in (32, 16, 8, 4, 2, 1):
-        v = v + v[:, :, LANES ^ s, :]
-    assert all(np.array_equal(v[:, :, 0].view(np.uint64), v[:, :, k].view(np.uint64)) for k in (1, 37, 63)), "a + b == b + a"
-    w = v[:, :, 0, :]
-    out = w[:, 0]
-    for k in range(1, BLOCK // WAVE):
-        out = out + w[:, k]
-    return out
-
-
-def totals(partials):
-    """float64 [18]: thread t adds rows t, t + 256, .. in ascending order from 0.0; then the threads' sums as a workgroup's."""
-    rows = len(partials)
-    v = np.zeros((BLOCK, TERMS))
-    for lo in range(0, rows, BLOCK):
-        part = partials[lo:lo + BLOCK]
-        v[:len(part)] = v[:len(part)] + part
-    return block_sums(v)[0]
 
 
 def accumulate(src, tgt, radius, T, pivot, nearest=R.nearest):

@@ -8,13 +8,13 @@ import math
 
 import numpy as np
 
+from tests.ordered_sums import WAVE, wave_sums
+
 F = np.float32
 AXIS_BITS = 21
 NO_CELL = 2 ** 63 - 1
 RANK_RATIO = 1e-3
 EPS = 2.220446049250313e-16
-WAVE = 64
-LANES = np.arange(WAVE)
 
 
 # ------------------------------------------------------------------------------------------------------------------- svd3.h
@@ -134,10 +134,7 @@ def wavefront_sums(rows, group, n_groups):
     for j in range(int(count.max()) if n_groups else 0):
         sel = np.flatnonzero(count > j)
         lanes[sel, j % WAVE] = lanes[sel, j % WAVE] + rows[start[sel] + j]
-    for s in (32, 16, 8, 4, 2, 1):
-        lanes = lanes + lanes[:, LANES ^ s]
-    assert all(np.array_equal(lanes[:, 0].view(np.uint64), lanes[:, l].view(np.uint64)) for l in (1, 37, 63)), "a + b == b + a"
-    return lanes[:, 0]
+    return wave_sums(lanes)
 
 
 def clusters(vertices, cell):

@@ -23,7 +23,7 @@ ROOT = os.path.dirname(HERE)
 def probe():
     so = os.path.join(HERE, "_build", "libicp_probe.so")
     src = os.path.join(HERE, "icp_probe.hip")
-    deps = [src] + [os.path.join(ROOT, "acezero_amd", "csrc", f) for f in ("icp_solve.h", "svd3.h")]
+    deps = [src] + [os.path.join(ROOT, "acezero_amd", "csrc", f) for f in ("icp_solve.h", "device_loop.h", "svd3.h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         os.makedirs(os.path.dirname(so), exist_ok=True)
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
@@ -88,6 +88,32 @@ def test_summation_order():
     assert np.array_equal(I.block_sums(ones)[:, 0], [256, 256, 256, 232]) and I.totals(I.block_sums(ones))[0] == 1000
     many = I.totals(np.ones((700, I.TERMS)))                       # more partial rows than UPDATE has threads
     assert (many == 700).all()
+
+
+def test_summation_order_at_both_widths():
+    """The one restatement (tests/ordered_sums.py) at the 18 terms of ICP and the 29 of tracking: 1000 rows, workgroups of 256, 256,
+    256 and 232, against the definition lane by lane; the totals of those four rows likewise."""
+    rng = np.random.default_rng(1)
+
+    def by_lanes(rows, terms):                                     # one workgroup: butterfly per wavefront, wavefronts ascending
+        waves = []
+        for w in range(4):
+            v = np.zeros((64, terms))
+            mine = rows[w * 64:(w + 1) * 64]
+            v[:len(mine)] = mine
+            for s in (32, 16, 8, 4, 2, 1):
+                v = np.stack([v[lane] + v[lane ^ s] for lane in range(64)])
+            waves.append(v[0])
+        return ((waves[0] + waves[1]) + waves[2]) + waves[3]
+
+    for terms in (18, 29):
+        t = rng.normal(size=(1000, terms)) * 10.0 ** rng.integers(-6, 6, (1000, 1))
+        part = I.block_sums(t)
+        assert part.shape == (4, terms)
+        for blk in range(4):
+            assert np.array_equal(part[blk].view(np.uint64), by_lanes(t[blk * 256:(blk + 1) * 256], terms).view(np.uint64))
+        # UPDATE: thread r < 4 holds 0.0 + row r, the other threads 0.0
+        assert np.array_equal(I.totals(part).view(np.uint64), by_lanes(0.0 + part, terms).view(np.uint64))
 
 
 @pytest.mark.parametrize("with_scale", [False, True], ids=["rigid", "with_scale"])

@@ -20,7 +20,7 @@ ROOT = os.path.dirname(HERE)
 def probe():
     so = os.path.join(HERE, "_build", "libtrack_probe.so")
     src = os.path.join(HERE, "track_probe.hip")
-    deps = [src, os.path.join(ROOT, "acezero_amd", "csrc", "track_solve.h")]
+    deps = [src] + [os.path.join(ROOT, "acezero_amd", "csrc", f) for f in ("track_solve.h", "device_loop.h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         os.makedirs(os.path.dirname(so), exist_ok=True)
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",

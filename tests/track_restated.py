@@ -8,12 +8,12 @@ import math
 import numpy as np
 
 from tests import tsdf_restated as TR
+from tests.ordered_sums import block_sums, totals  # noqa: F401  (the header's summation order; the tests call T.block_sums, T.totals)
 
 F = np.float32
-TILE, WAVE, TERMS, STATE, RECORD = 256, 64, 29, 45, 16
+TERMS, STATE, RECORD = 29, 45, 16
 RUNNING, CONVERGED, DEGENERATE = 0, 1, 2
 STATUS = {RUNNING: "max_iterations", CONVERGED: "converged", DEGENERATE: "degenerate"}
-LANES = np.arange(WAVE)
 PAIRS = [(i, j) for i in range(6) for j in range(i, 6)]          # the upper triangle, row-major
 
 
@@ -73,31 +73,6 @@ def terms(tsdf, weight, origin, voxel_size, truncation, depth, pose, focal, ppx,
             out[:, 22 + k] = J[k] * r
         out[:, 28] = r * r
     return np.where(ok[:, None], out, 0.0)
-
-
-def block_sums(t):
-    """float64 [ceil(n / 256), 29] from [n, 29]: pixel i is lane i % 64 of wavefront (i / 64) % 4 of tile i / 256; per wavefront the
-    xor butterfly 32, 16, .. 1, then the wavefronts in ascending order."""
-    blocks = (len(t) + TILE - 1) // TILE
-    v = np.zeros((blocks * TILE, t.shape[1]))
-    v[:len(t)] = t
-    v = v.reshape(blocks, TILE // WAVE, WAVE, t.shape[1])
-    for s in (32, 16, 8, 4, 2, 1):
-        v = v + v[:, :, LANES ^ s, :]
-    w = v[:, :, 0, :]
-    out = w[:, 0]
-    for k in range(1, TILE // WAVE):
-        out = out + w[:, k]
-    return out
-
-
-def totals(partials):
-    """float64 [29]: thread t adds rows t, t + 256, .. in ascending order from 0.0; then the threads' sums as a tile's."""
-    v = np.zeros((TILE, partials.shape[1]))
-    for lo in range(0, len(partials), TILE):
-        part = partials[lo:lo + TILE]
-        v[:len(part)] = v[:len(part)] + part
-    return block_sums(v)[0]
 
 
 def to_dense(tsdf_blocks, weight_blocks, block_table, dims):

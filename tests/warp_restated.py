@@ -8,6 +8,8 @@ torch's float64 affine_grid / grid_sample to 1e-12); np.float32 evaluates the sa
 number format, which is how the tests' error bounds are measured (tests/warp_cases.py)."""
 import numpy as np
 
+from tests.ordered_sums import wave_sums
+
 EPS32 = float(np.finfo(np.float32).eps)
 
 
@@ -63,10 +65,7 @@ def jitter_mean(image, br, dt=np.float64):
     acc = np.zeros(1024, dt)
     for r in rows.reshape(-1, 1024):
         acc = acc + r
-    acc = acc.reshape(16, 64)
-    lane = np.arange(64)
-    for off in (32, 16, 8, 4, 2, 1):
-        acc = acc + acc[:, lane ^ off]
+    acc = wave_sums(acc.reshape(16, 64, 1))
     s = dt(0)
     for i in range(16):
         s = s + acc[i, 0]
