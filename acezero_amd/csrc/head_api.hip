@@ -102,12 +102,12 @@ struct acez_trainer {
   bool f16 = false;
   int last_nblk = 0;   // loss workgroups of the last backward (the schedule wave scans their |ds| maxima in fp16 mode)
   int n_cus = 0;
-  uint32_t* seq_flags = nullptr;  // [64 row tiles][32] hand-off counters, monotonically increasing
+  uint32_t* seq_flags = nullptr;  // [64 row tiles][32] progress words (one per wave of the tile's four workgroups), monotonically increasing
   uint32_t seq_base[64] = {};     // seams completed so far, per row tile
   uint32_t* seq_xcc = nullptr;    // ACEZ_SEQ_XCC=1: placement record of rowseq_kernel (acez_trainer_debug_read kind 6)
   // Safety net of the hand-off (the workgroup -> XCD mapping is not an API contract): a placement probe at creation decides whether
   // the one-launch chains are used at all; every poll is bounded and raises `seq_err` (device), which turns the optimiser /
-  // schedule kernels of that step into no-ops; the next state read (seq_fault_check) resets the counters and switches this
+  // schedule kernels of that step into no-ops; the next state read (seq_fault_check) resets the progress words and switches this
   // trainer to per-layer launches for good. The abandoned iterations are not counted, so the training loop simply runs them again.
   int* seq_err = nullptr;              // = (int*)(seq_flags + SEQ_FAULT_WORD): one allocation, so that the kernel needs no second pointer
   uint32_t seq_spin_limit = 40000;     // polls (>= ~0.5 us each: at least ~20 ms); ACEZ_SEQ_SPIN_US overrides (2 polls per us)
@@ -288,7 +288,7 @@ static int seq_fault_check(acez_trainer* tr, hipStream_t s) {
   if (!err) return 0;
   wgo_recover(tr, s);   // (before the fault word comes down: nothing else may run on this trainer's buffers in between)
   tr->carry.drop_batch();   // batches "gathered ahead" since the fault were held back
-  (void)hipMemsetAsync(tr->seq_flags, 0, (SEQ_FAULT_WORD + 1) * sizeof(uint32_t), s);   // counters + fault word (the poll budget behind them stays)
+  (void)hipMemsetAsync(tr->seq_flags, 0, (SEQ_FAULT_WORD + 1) * sizeof(uint32_t), s);   // whole lines + fault word (the poll budget behind them stays)
   hipLaunchKernelGGL(sched_reactivate_kernel, dim3(1), dim3(64), 0, s, tr->st);
   const int one = 1;
   (void)hipMemcpyAsync(&tr->st_infer->active, &one, sizeof(int), hipMemcpyHostToDevice, s);
@@ -547,19 +547,22 @@ static bool wgrad_opt_usable(const acez_trainer* tr) {
          tr->cfg.pose_refinement == 0 && 256 * ((tr->L + 7) / 8) <= tr->n_cus;
 }
 
-// The host's side of the hand-off protocol (head_kernels.hip) for one launch on a trainer's counters, in front of the launch: `base`
-// (the launch's argument) = the seams completed so far per row tile; the trainer's own bases move on by the `seams` the launch adds to
-// the row tiles of ITS n-row batch (seq_seams: the device adds as much when the launch returns at entry). `stands_for`: the launches of
-// the per-chain flow this one counts as in seq_launches; `layers`: the layer GEMMs it is accounted as in a profiling scope, so that the
-// per-layer average stays comparable.
-// tests (ACEZ_SEQ_FAULT_AT): the launch that the n-th launch falls in is told that a million seams have completed before it -- every
-// hand-off then waits for a count that never comes, which is what a sibling on a foreign XCD looks like (a launch without a seam: not)
-static void seq_account(acez_trainer* tr, uint32_t (&base)[64], int n, uint32_t seams, int layers, int stands_for = 1) {
+// The host's side of the hand-off protocol (head_kernels.hip) for one launch on a trainer's progress words, in front of the launch: `base`
+// (the launch's argument) = the seams completed so far per row tile -- the launch's waves post base + 1, base + 2, ... and poll for
+// them --; the trainer's own bases move on by the `seams` the launch completes on the row tiles of ITS n-row batch (seq_seams: a launch
+// that returns at entry leaves base + seams in its words). `stands_for`: the launches of the per-chain flow this one counts as in
+// seq_launches; `layers`: the layer GEMMs it is accounted as in a profiling scope, so that the per-layer average stays comparable.
+// Returns the launch's poll_bias, 0.
+// tests (ACEZ_SEQ_FAULT_AT): the launch that the n-th launch falls in polls as if a million seams had completed before it (the bias;
+// what it posts is unchanged) -- every hand-off then waits for a seam that never comes, which is what a sibling on a foreign XCD looks
+// like (a launch without a seam: not)
+static uint32_t seq_account(acez_trainer* tr, uint32_t (&base)[64], int n, uint32_t seams, int layers, int stands_for = 1) {
   const bool fault = seams > 0 && tr->seq_fault_at >= tr->seq_launches && tr->seq_fault_at < tr->seq_launches + stands_for;
-  for (int mt = 0; mt < 64; ++mt) base[mt] = tr->seq_base[mt] + (fault ? 1u << 20 : 0u);
+  for (int mt = 0; mt < 64; ++mt) base[mt] = tr->seq_base[mt];
   tr->seq_launches += stands_for;
   for (int mt = 0; mt < row_tiles(n); ++mt) tr->seq_base[mt] += seams;
   tr->prof_launches += layers;
+  return fault ? 1u << 20 : 0u;
 }
 
 // head != null (input gradients only): the chain's first launch is rowseq_loss_kernel -- the loss of the batch as its stage -1, one
@@ -574,7 +577,7 @@ static void launch_rowseq(acez_trainer* tr, const std::vector<SeqLayer>& layers,
     const int cnt = (int)std::min<size_t>(SEQ_MAX_LAYERS, layers.size() - i0);
     for (int i = 0; i < cnt; ++i) a.layer[i] = layers[i0 + i];
     a.n_layers = cnt; a.M = n; a.st = st ? st : tr->st_infer; a.flags = tr->seq_flags; a.xcc_dbg = tr->seq_xcc; a.spin_limit = tr->seq_spin_limit;
-    seq_account(tr, a.base, n, seq_seams(cnt, with_loss ? 1 : 0), cnt);
+    a.poll_bias = seq_account(tr, a.base, n, seq_seams(cnt, with_loss ? 1 : 0), cnt);
     with_elt(tr->f16, [&](auto e) {
       if (with_loss) hipLaunchKernelGGL(rowseq_loss_kernel<decltype(e)>, grid, dim3(512), 0, s, a, *head);
       else hipLaunchKernelGGL((rowseq_kernel<BWD, decltype(e)>), grid, dim3(512), 0, s, a);
@@ -940,7 +943,7 @@ static void launch_rowstep(const StepRun& r) {
   a.n_fwd = (int)fwd.size(); a.n_bwd = (int)bwd.size(); a.M = r.n;
   a.st = r.st ? r.st : tr->st_infer; a.flags = tr->seq_flags; a.xcc_dbg = tr->seq_xcc; a.spin_limit = tr->seq_spin_limit;
   // (the launch stands for two of the three-launch flow's, the forward chain's and the input-gradient chain's)
-  seq_account(tr, a.base, r.n, seq_seams(a.n_fwd + a.n_bwd, 1), a.n_fwd + a.n_bwd, 2);
+  a.poll_bias = seq_account(tr, a.base, r.n, seq_seams(a.n_fwd + a.n_bwd, 1), a.n_fwd + a.n_bwd, 2);
   a.x = train_loss_in_chain(r);
   with_elt(tr->f16, [&](auto e) { hipLaunchKernelGGL(rowstep_kernel<decltype(e)>, chain_grid(row_tiles(r.n)), dim3(512), 0, r.s, a); });
   ++tr->step_chain_steps;
@@ -1175,7 +1178,7 @@ static int train_step_impl(acez_trainer* tr, Flow flow, const int64_t* d_indices
   return run_steps(&r, 1, [&](bool bwd) { launch_chain(r, bwd); });
 }
 
-// The steps of the two flows are bitwise equal and share the counter bases: the switch is safe between any two steps
+// The steps of the two flows are bitwise equal and share the seam bases: the switch is safe between any two steps
 extern "C" int acez_trainer_set_step_chain(acez_trainer* tr, int enable) {
   ACEZ_REQUIRE(tr, "null trainer");
   tr->step_chain = enable != 0;
@@ -1433,7 +1436,8 @@ extern "C" int acez_trainer_get_profile(acez_trainer* tr, float* h_ms8, int32_t*
 // Diagnostics for the tests: copy one of the trainer's intermediate device buffers to the host. kind 0: post-ReLU output of wide
 // layer `index` [n][512] bf16 (training: not kept for the last layer of a block, whose mask bits are); 1: dZ of layer `index` [n][512] bf16;
 // 2: residual stream `index` [n][512] bf16 (0 = the gathered batch); 3: weight-gradient slab `index` [n_wide] fp32; 4: bias-gradient partial
-// rows of layer `index` [max_blocks][512] fp32; 9: ReLU mask bits of layer `index` (RowGemmArgs::mask_out), 8 KiB per 80-row tile.
+// rows of layer `index` [max_blocks][512] fp32; 9: ReLU mask bits of layer `index` (RowGemmArgs::mask_out), 8 KiB per 80-row tile;
+// 10: the hand-off state, u32 [64][32] progress words + [32] the fault word's line + [64] the host's bases (seq_base).
 extern "C" int acez_trainer_debug_read(acez_trainer* tr, int kind, int index, void* h_out, int64_t bytes, void* stream) {
   ACEZ_REQUIRE(tr && h_out && bytes > 0, "null pointer");
   ACEZ_HIP_CHECK(hipSetDevice(tr->device));
@@ -1449,6 +1453,12 @@ extern "C" int acez_trainer_debug_read(acez_trainer* tr, int kind, int index, vo
   else if (kind == 9 && index >= 0 && index < tr->L && tr->maskbits) { src = tr->maskbits + (size_t)index * tr->mask_stride; cap = (int64_t)tr->mask_stride * 8; }
   else if (kind == 7 && tr->wgo_trace) { src = tr->wgo_trace; cap = 256 * 12 * 8 * 8; }
   else if (kind == 8 && tr->pose_trace) { src = tr->pose_trace; cap = 3 * 1024 * 16 * 8; }
+  else if (kind == 10 && tr->seq_flags && bytes == (int64_t)(SEQ_FAULT_WORD + 32 + 64) * 4) {   // the 64 lines, the fault word's line, then the host's bases
+    ACEZ_HIP_CHECK(hipMemcpyAsync(h_out, tr->seq_flags, (SEQ_FAULT_WORD + 32) * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    ACEZ_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    memcpy(static_cast<uint32_t*>(h_out) + SEQ_FAULT_WORD + 32, tr->seq_base, 64 * sizeof(uint32_t));
+    return ACEZ_OK;
+  }
   ACEZ_REQUIRE(src && bytes <= cap, "unknown buffer or size out of range");
   ACEZ_HIP_CHECK(hipMemcpyAsync(h_out, src, (size_t)bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
   ACEZ_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));

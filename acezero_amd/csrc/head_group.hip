@@ -16,7 +16,7 @@ constexpr int GROUP_MAX = 8;
 struct GroupHead {
   SeqLayer fwd[2][MAX_LAYERS];   // [which of the trainer's two input buffers is R[0] this step][layer] (acez_train_step_next swaps them)
   SeqLayer bwd[MAX_LAYERS];
-  uint32_t* flags;               // the trainer's hand-off counters + sticky fault word (RowSeqArgs::flags)
+  uint32_t* flags;               // the trainer's progress words + sticky fault word (RowSeqArgs::flags)
   uint32_t spin_limit;
   int pad;
 };
@@ -28,6 +28,7 @@ struct RowSeqGroupArgs {
   int M[GROUP_MAX];
   int variant[GROUP_MAX];              // GroupHead::fwd index
   uint32_t base[GROUP_MAX][64];        // per member and row tile: seams completed by earlier launches (RowSeqArgs::base)
+  uint32_t poll_bias[GROUP_MAX];       // RowSeqArgs::poll_bias
   int H, layer0, n_layers, mtiles;     // layers [layer0, layer0 + n_layers) of every member's table; mtiles = the largest member's
 };
 
@@ -41,14 +42,14 @@ __global__ __launch_bounds__(512) void rowseq_group_kernel(RowSeqGroupArgs a) {
   const int mt = t.mt, n0 = t.n0();
   if (threadIdx.x == 0) {
     // which members this workgroup runs, decided once for the whole workgroup: row tile mt inside the member's batch, its schedule
-    // active and its fault word down (rowseq_kernel's entry test, per member). A member that does not run keeps its counters in step with
+    // active and its fault word down (rowseq_kernel's entry test, per member). A member that does not run keeps its words in step with
     // the host's bases exactly as rowseq_kernel's early return does; row tiles past a member's batch are not counted (seq_account).
     uint32_t run = 0;
     for (int h = 0; h < a.H; ++h) {
       if (mt >= row_tiles(a.M[h])) continue;
       uint32_t* flags = a.heads[h].flags;
       if (SEQ_DEAD(a.st[h], flags)) {
-        seq_catch_up(seq_seams(a.n_layers), flags, mt);
+        seq_catch_up(a.base[h][mt] + seq_seams(a.n_layers), flags, mt, t.nt());
         continue;
       }
       run |= 1u << h;
@@ -79,8 +80,12 @@ __global__ __launch_bounds__(512) void rowseq_group_kernel(RowSeqGroupArgs a) {
       g.absmax = (BWD && st) ? const_cast<uint32_t*>(st->dz_absmax_slots) : nullptr;
       SeqLink q;
       // (target and budget are scalar operands of the poll: the table lives in global memory, so say that they are uniform)
-      q.flag = a.heads[h].flags + mt * 32;
-      q.target = (uint32_t)__builtin_amdgcn_readfirstlane((int)((a.base[h][mt] + (uint32_t)layer) * 32u));
+      // (... and the line's address, the scalar base of the poll's load)
+      const uint64_t line = reinterpret_cast<uint64_t>(a.heads[h].flags + mt * 32);
+      q.flag = reinterpret_cast<uint32_t*>((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)line) |
+                                           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(line >> 32)) << 32));
+      q.post = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.base[h][mt] + (uint32_t)layer + 1u));
+      q.target = q.post - 1u + (uint32_t)__builtin_amdgcn_readfirstlane((int)a.poll_bias[h]);
       q.first = first; q.wait = layer > 0; q.signal = layer + 1 < a.n_layers;
       q.next_W = next_W;
       q.flag_index = (uint32_t)(mt * 32); q.limit = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.heads[h].spin_limit);
@@ -175,7 +180,7 @@ static void launch_rowseq_group(acez_train_group* g, const std::vector<int>& idx
       acez_trainer* tr = g->m[i];
       a.st[i] = runs[i].st; a.M[i] = runs[i].n; a.variant[i] = tr->R[0] == g->in0[i] ? 0 : 1;
       a.mtiles = std::max(a.mtiles, row_tiles(runs[i].n));
-      seq_account(tr, a.base[i], runs[i].n, seq_seams(cnt), 0);   // (layers = 0: the group's chain launches open no profiling scope)
+      a.poll_bias[i] = seq_account(tr, a.base[i], runs[i].n, seq_seams(cnt), 0);   // (layers = 0: the group's chain launches open no profiling scope)
     }
     with_elt(f16, [&](auto e) { hipLaunchKernelGGL((rowseq_group_kernel<BWD, decltype(e)>), chain_grid(a.mtiles), dim3(512), 0, s, a); });
   }

@@ -126,7 +126,7 @@ __device__ __forceinline__ uint32_t absmax_all(const TrainState* st, int lane) {
 // rowseq_loss_kernel, rowstep_kernel, head_group.hip's rowseq_group_kernel) through rowgemm80_body<..., SEQ> and rowseq_loss_stage, and
 // wgrad_opt_kernel's exchange. The host's side is seq_account (head_api.hip).
 // ---------------------------------------------------------------------------------------------------
-constexpr int SEQ_FAULT_WORD = 64 * 32;   // flags[SEQ_FAULT_WORD]: the trainer's sticky fault word, behind its 64 row-tile counters (one 128-byte line each)
+constexpr int SEQ_FAULT_WORD = 64 * 32;   // flags[SEQ_FAULT_WORD]: the trainer's sticky fault word, behind its 64 row-tile lines (128 bytes = 32 progress words each)
 
 // Row tiles of an n-row batch, the chain kernels' grid for them (N = 512 -> 4 column tiles of 128; a multiple of 8 row-tile groups) and
 // the decode of that grid: blockIdx.x & 7 is the XCD the workgroup lands on, so the four column tiles of a row tile share an XCD and its
@@ -146,23 +146,58 @@ __device__ __forceinline__ bool row_tile_decode(const int mtiles, RowTile& t) {
   return t.mt < mtiles;
 }
 
-// Seams (hand-offs) a launch adds to the counter of each of its row tiles: one between two consecutive stages, a stage being a chain
-// layer or the loss stage. rowseq_kernel: n - 1; rowseq_loss_kernel: n; rowstep_kernel: n_fwd + n_bwd; rowseq_group_kernel: cnt - 1 per
-// member. The device adds 8 x this in a launch that returns at entry, the host advances its bases by it (seq_account).
+// Seams (hand-offs) a launch adds to each of its row tiles: one between two consecutive stages, a stage being a chain layer or the loss
+// stage. rowseq_kernel: n - 1; rowseq_loss_kernel: n; rowstep_kernel: n_fwd + n_bwd; rowseq_group_kernel: cnt - 1 per member. Seams are
+// numbered absolutely per row tile: a launch whose base is b completes seams b + 1 .. b + seq_seams, the host advances its bases by as
+// much (seq_account), and a launch that returns at entry leaves b + seq_seams in its words (seq_catch_up).
+// Progress words: word nt * 8 + w of a row tile's line belongs to wave w of column tile nt -- 4 workgroups x 8 waves, the 32 words of the
+// line. A wave stores the number of the seam it has completed into ITS word (seq_post); a consumer reads the whole line and passes when
+// none of the 32 is behind its seam (seq_poll_expired). One writer per word, absolute values: no read-modify-write, and nothing queues on
+// the line the way the 32 same-line atomics of a shared counter did (11-13 ns each in the L2).
 __host__ __device__ constexpr uint32_t seq_seams(int n_layers, int loss_stages = 0) { return (uint32_t)(n_layers + loss_stages - 1); }
+__device__ __forceinline__ int seq_word(const int nt, const int w) { return nt * 8 + w; }
 
-// The bounded poll of a hand-off counter. True: the budget expired.
+// The bounded poll of a row tile's line. True: the budget expired.
 // Bounded: a sibling that never arrives (workgroups of one row tile on different XCDs -- every L2 then holds its own copy
-// of the counter and none of them ever reaches the target --, or a sibling that is never dispatched) must not hang the
+// of the line and none of them ever shows all 32 words --, or a sibling that is never dispatched) must not hang the
 // stream. When the budget expires the wave raises the sticky fault word (seq_raise_fault) and goes on with whatever is in memory: the
 // results of this launch are garbage, the optimiser and schedule kernels of the step see the word and do nothing, and
 // the host switches the trainer to per-layer launches at its next state read (head_api.hip).
 // The whole poll is ONE asm statement: written as a C loop with a second exit, the compiler re-scheduled the K loops and
 // epilogues of the input-gradient instantiation (+3 us per chain, same instruction mix; found by diffing the ISA of a
-// build without the bound). sc1: past this CU's L1; the counter and the tiles live in the L2 all four workgroups share,
-// no L2 invalidate. Every lane loads the same word: the loop condition is scalar. The budget is counted in polls
+// build without the bound). sc1: past this CU's L1; the line and the tiles live in the L2 all four workgroups share,
+// no L2 invalidate. Lane l loads word l & 31 (one request for the line; the byte offset 4 (l & 31) is formed from `tid`, the thread's index in
+// the workgroup, INSIDE the statement: formed outside, it was hoisted out of the layer loop into a register of its own); a lane is behind while
+// word - target < 0 as a signed number (a sibling that is a seam AHEAD does not hold anybody up, and the 32-bit seam number may wrap); the
+// wave passes when no lane is behind: one compare into vcc, one scalar test of it. The budget is counted in polls
 // (>= ~0.5 us each: an L2 round trip + the sleep).
-__device__ __forceinline__ bool seq_poll_expired(const uint32_t* flag, uint32_t target, uint32_t limit) {
+__device__ __forceinline__ bool seq_poll_expired(const uint32_t* line, uint32_t tid, uint32_t target, uint32_t limit) {
+  uint32_t vseen, voff, spins, timed;
+  asm volatile(
+      "v_lshlrev_b32 %[voff], 2, %[tid]\n\t"
+      "v_and_b32 %[voff], 0x7c, %[voff]\n\t"
+      "s_mov_b32 %[spins], 0\n\t"
+      "s_mov_b32 %[timed], 0\n"
+      "1:\n\t"
+      "global_load_dword %[vseen], %[voff], %[line] sc1\n\t"
+      "s_waitcnt vmcnt(0)\n\t"
+      "v_subrev_u32 %[vseen], %[target], %[vseen]\n\t"
+      "v_cmp_gt_i32 vcc, 0, %[vseen]\n\t"
+      "s_cbranch_vccz 2f\n\t"
+      "s_sleep 1\n\t"   // 64 clocks between two polls
+      "s_add_u32 %[spins], %[spins], 1\n\t"
+      "s_cmp_lt_u32 %[spins], %[limit]\n\t"
+      "s_cbranch_scc1 1b\n\t"
+      "s_mov_b32 %[timed], 1\n"
+      "2:"
+      : [vseen] "=&v"(vseen), [voff] "=&v"(voff), [spins] "=&s"(spins), [timed] "=&s"(timed)
+      : [line] "s"(line), [tid] "v"(tid), [target] "s"(target), [limit] "s"(limit)
+      : "memory", "scc", "vcc");
+  return timed != 0;
+}
+// ... and of ONE counter word with several senders (wgrad_opt_kernel's exchange: two waves bump a pair's word, seq_bump): every lane
+// loads the same word, the loop condition is scalar.
+__device__ __forceinline__ bool seq_poll_word_expired(const uint32_t* flag, uint32_t target, uint32_t limit) {
   uint32_t vseen, sseen, spins, timed;
   asm volatile(
       "s_mov_b32 %[spins], 0\n\t"
@@ -193,23 +228,29 @@ __device__ __forceinline__ void seq_raise_fault(uint32_t* fault_word, const Trai
   if (st) __hip_atomic_store(const_cast<int*>(&st->active), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The bump of a hand-off counter (one lane of the wave, behind the acknowledgement of the wave's stores: ACEZ_VMCNT(0)): an L2-local
-// atomic without return, no fence.
+// A wave's progress word (one lane of the wave, behind the acknowledgement of the wave's stores: ACEZ_VMCNT(0)): a plain vector store of
+// the seam number the wave has completed -- the value a consumer of that seam polls for --, no atomic, no fence.
+__device__ __forceinline__ void seq_post(uint32_t* word, const uint32_t seam) {
+  asm volatile("global_store_dword %0, %1, off" ::"v"(word), "v"(seam) : "memory");
+}
+// The bump of a counter word that has several senders (wgrad_opt_kernel's exchange; one lane of the wave, behind ACEZ_VMCNT(0)): an
+// L2-local atomic without return, no fence.
 __device__ __forceinline__ void seq_bump(uint32_t* flag, const uint32_t inc) {
   asm volatile("global_atomic_add %0, %1, off" ::"v"(flag), "v"(inc) : "memory");
 }
 
-// The entry test of a launch on a trainer's counters: training has ended on the device (after an expired poll the fault handler has
+// The entry test of a launch on a trainer's lines: training has ended on the device (after an expired poll the fault handler has
 // cleared `active` too), or a poll of this trainer has expired in an EARLIER launch -- the buffers of the faulted step are left alone
-// until the host has fallen back. Both words are wave-uniform loads. A dead launch does no work, but its counters keep step with the
-// host's bases (seq_catch_up, one lane of the workgroup: the same L2-local atomic as the hand-off itself).
+// until the host has fallen back. Both words are wave-uniform loads. A dead launch does no work, but its words keep step with the
+// host's bases (seq_catch_up, one lane of the workgroup: the launch's last seam number `last` = base + seq_seams into the workgroup's eight
+// words -- the words are absolute, so this is a live launch's end state by construction).
 // A macro, not a function: as a function (by value or on the kernel arguments by reference) `flags` was fetched in front of the test of
 // `st` and the four chain kernels' registers were allocated anew -- the two loads keep the order they were measured with. Used here
 // and by rowseq_group_kernel (head_group.hip, which #undefs it behind that kernel).
 #define SEQ_DEAD(st, flags) (((st) && !(st)->active) || (flags)[SEQ_FAULT_WORD])
-__device__ __forceinline__ void seq_catch_up(const uint32_t seams, uint32_t* flags, const int mt) {
-  const uint32_t inc = 8u * seams;
-  seq_bump(flags + mt * 32, inc);
+__device__ __forceinline__ void seq_catch_up(const uint32_t last, uint32_t* flags, const int mt, const int nt) {
+  uint4* const w8 = reinterpret_cast<uint4*>(flags + mt * 32 + seq_word(nt, 0));
+  w8[0] = w8[1] = make_uint4(last, last, last, last);
 }
 
 // The placement record of a chain kernel (xcc_dbg: RowSeqArgs; null: none), by thread 0 of the workgroup that owns tile t: which XCD ran
@@ -228,10 +269,11 @@ __device__ __forceinline__ void seq_record_placement(const A& a, const RowTile& 
 // One layer of one workgroup. SEQ = false: the whole of rowgemm80_kernel. SEQ = true: one link of rowseq_kernel (below), where
 // the layers of a dependent chain run in ONE launch and the kernel boundary is replaced by a same-XCD hand-off (SeqLink).
 struct SeqLink {
-  uint32_t* flag;        // per-row-tile counter in this XCD's L2 (one 128-byte line each), monotonically increasing
-  uint32_t target;       // value of *flag when the four column tiles of the layer before have stored their outputs
+  uint32_t* flag;        // the row tile's line of 32 progress words in this XCD's L2, each monotonically increasing
+  uint32_t target;       // the seam in front of this layer: in every word once the four column tiles of the layer before have stored their outputs
+  uint32_t post;         // the seam behind this layer: what its waves store into their words
   bool first, wait;      // first layer of the launch (requests its own W stages) / In is produced inside this launch
-  bool signal;           // another layer follows: bump *flag after the stores
+  bool signal;           // another layer follows: post the wave's word after the stores
   const uint16_t* next_W;  // weights of the layer after (null: none): its first four W stages are requested before the epilogue
   uint32_t flag_index;   // flag = flags + flag_index; the trainer's sticky fault word is flags[SEQ_FAULT_WORD]: set when the bounded poll
                          // below expires (the host then falls back to per-layer launches, head_api.hip seq_fault_check)
@@ -303,7 +345,7 @@ __device__ __forceinline__ void rowgemm80_body(const RowGemmArgs& a, uint16_t* s
       // W stages 0..3 first (requested by the layer before unless this is the first), then -- once the four column tiles
       // of the producing layer have landed in this XCD's L2 -- the In stages
       if (q.first) { issueW(0); issueW(1); issueW(2); issueW(3); }
-      if (q.wait && seq_poll_expired(q.flag, q.target, q.limit) && l == 0) seq_raise_fault(q.flag - q.flag_index + SEQ_FAULT_WORD, a.st);
+      if (q.wait && seq_poll_expired(q.flag, t, q.target, q.limit) && l == 0) seq_raise_fault(q.flag - q.flag_index + SEQ_FAULT_WORD, a.st);
       issueI(0); issueI(1); issueI(2); issueI(3);
     }
 #pragma unroll
@@ -522,7 +564,7 @@ __device__ __forceinline__ void rowgemm80_body(const RowGemmArgs& a, uint16_t* s
     if (q2 < 1280 && r2 < M) *reinterpret_cast<uint4*>(first + o2) = f2v;
     if (SEQ && q.signal) {
       ACEZ_VMCNT(0);   // this wave's stores are acknowledged by the L2 = visible to the three sibling workgroups (same XCD)
-      if (l == 0) seq_bump(q.flag, 1u);
+      if (l == 0) seq_post(q.flag + seq_word(n0 >> 7, w), q.post);
     }
     if (AUX != AUX_NONE && second) {   // (null: a training forward does not keep the pre-residual activation -- only its mask bits are read again)
       if (r0 < M) *reinterpret_cast<uint4*>(second + o0) = s0;
@@ -602,8 +644,8 @@ __global__ __launch_bounds__(512) void rowgemm80_kernel(RowGemmArgs a) {
 // rowseq: the layers of a dependent GEMM chain (the 8 forward layers, or the 7 input-gradient layers) in ONE launch with
 // rowgemm80's tiling, roles, ring, K order and epilogues -- bit-identical outputs. Layer l + 1 of row tile mt reads layer l's
 // 80 x 512 output = the four column tiles of mt, which the grid decode places on ONE XCD, so the hand-off stays inside that
-// XCD's L2: every wave bumps the row tile's counter once its stores are acknowledged, the next layer's loader waves poll it
-// past their L1. No agent-scope fence (a buffer_inv sc1 / buffer_wbl2 sc1 pair per seam costs 5 - 40 us: measured with
+// XCD's L2: every wave posts its progress word in the row tile's line once its stores are acknowledged, the next layer's loader waves
+// poll the line past their L1. No agent-scope fence (a buffer_inv sc1 / buffer_wbl2 sc1 pair per seam costs 5 - 40 us: measured with
 // tools/seam_proto.hip). Tile-local epilogue inputs (`add`, `res`) were written by the same CU or before the launch; `In` is
 // never read before it is produced, so no stale L1 line can exist. What the seam saves over a kernel boundary: the launch
 // ramp, and the next layer's first four W stages are in flight while the epilogue runs (tools/seam_proto.hip: 6.13 -> 4.88 us
@@ -625,9 +667,10 @@ struct RowSeqArgs {
   SeqLayer layer[SEQ_MAX_LAYERS];
   int n_layers, M;
   const TrainState* st;
-  uint32_t* flags;     // [64 row tiles][32] hand-off counters + [SEQ_FAULT_WORD] the fault word
+  uint32_t* flags;     // [64 row tiles][32] progress words + [SEQ_FAULT_WORD] the fault word
   uint32_t base[64];   // per row tile: seams completed by earlier launches (a launch only touches the row tiles of ITS batch)
   uint32_t spin_limit; // poll budget of a hand-off (polls of >= ~0.5 us); expired: fault word + st->active = 0
+  uint32_t poll_bias;  // 0; tests (seq_account): added to every seam this launch POLLS for, not to what it posts -- a seam that never comes
   uint32_t* xcc_dbg;   // null, or [8 + 256]: words 0..7 |= 1 << XCC_ID of the workgroups with blockIdx & 7 = word (sticky); word
                        // 8 + 4 mt + nt = XCC_ID of the workgroup that owned tile (mt, nt) in the last launch (tests: the four column
                        // tiles of a row tile must report the same XCD)
@@ -643,6 +686,7 @@ struct SeqCtx {
   uint32_t base;         // seams of this row tile completed by earlier launches (RowSeqArgs::base[mt])
   uint32_t seam0;        // hand-offs of THIS launch in front of the chain's layer 0
   uint32_t limit;        // RowSeqArgs::spin_limit
+  uint32_t bias;         // RowSeqArgs::poll_bias
 };
 
 // The layers of a chain for the workgroup of tile (mt, n0). HEAD (rowseq_loss_kernel, rowstep_kernel's second chain): c.seam0 hand-offs of
@@ -659,7 +703,7 @@ __device__ __forceinline__ void rowseq_layers(const SeqLayer* layers, const int 
     g.bias_partials = y.bias_partials; g.M = c.M; g.N = 512; g.K = 512; g.relu = BWD ? 0 : 1; g.aux_mode = y.aux_mode; g.st = c.st;
     g.absmax = (BWD && c.st) ? const_cast<uint32_t*>(c.st->dz_absmax_slots) : nullptr;
     SeqLink q;
-    q.flag = c.flags + mt * 32; q.target = (c.base + c.seam0 + (uint32_t)layer) * 32u;   // 4 workgroups x 8 waves per seam
+    q.flag = c.flags + mt * 32; q.post = c.base + c.seam0 + (uint32_t)layer + 1u; q.target = q.post - 1u + c.bias;
     q.first = !HEAD && layer == 0; q.wait = HEAD || layer > 0; q.signal = TAIL || layer + 1 < n_layers;
     q.next_W = layer + 1 < n_layers ? layers[layer + 1].W : nullptr;
     q.flag_index = (uint32_t)(mt * 32); q.limit = c.limit;
@@ -682,10 +726,10 @@ __global__ __launch_bounds__(512) void rowseq_kernel(RowSeqArgs a) {
   const int mt = t.mt;
   seq_record_placement(a, t);
   if (SEQ_DEAD(a.st, a.flags)) {
-    if (threadIdx.x == 0) seq_catch_up(seq_seams(a.n_layers), a.flags, mt);
+    if (threadIdx.x == 0) seq_catch_up(a.base[mt] + seq_seams(a.n_layers), a.flags, mt, t.nt());
     return;
   }
-  rowseq_layers<BWD, E, false>(a.layer, a.n_layers, SeqCtx{a.M, a.st, a.flags, a.base[mt], 0u, a.spin_limit}, smem, mt, t.n0());
+  rowseq_layers<BWD, E, false>(a.layer, a.n_layers, SeqCtx{a.M, a.st, a.flags, a.base[mt], 0u, a.spin_limit, a.poll_bias}, smem, mt, t.n0());
 }
 
 // Placement probe (acez_trainer_create): a launch with rowseq_kernel's grid, block size and LDS footprint that only records
@@ -2217,9 +2261,10 @@ __device__ __forceinline__ void lds_bump(uint32_t* f) {   // after this wave's e
 //             tiles 1..3 run block 5 mt + 1 + nt on their multiplier waves. loss_body as loss_kernel instantiates it; the four waves of a
 //             quartet meet through an LDS counter of their own (a barrier would tie the two quartets together), the scratch lies in the
 //             staging tiles, which layer 0 does not touch before its K stage 4.
-//   hand-off  dZ of fc2 is the In of the first layer: every wave of a loss block bumps the row tile's counter behind the acknowledgement
-//             of its stores, 8 per workgroup, exactly as a layer epilogue does; layer 0 then waits for 32 like any later layer. A block
-//             past the batch's last row stores nothing (and owns no partial slot) and still bumps.
+//   hand-off  dZ of fc2 is the In of the first layer: every wave of a loss block posts its progress word behind the acknowledgement of
+//             its stores, exactly as a layer epilogue does -- and in column tiles 1..3, whose loader waves run no block, the word of its
+//             loader partner w + 4 with it (lanes 0 and 1 of one store) --; layer 0 then waits for the 32 words like any later layer. A
+//             block past the batch's last row stores nothing (and owns no partial slot) and still posts.
 //   W stages  the loader waves request the first layer's first four W stages before anything else, as the seam prefetch does.
 //   gather    the loader waves of column tiles 1..3 have only a hand-off to wait for: they copy the NEXT batch's rows (gather_rows, three
 //             dependent load levels -- shorter than a loss block's chain) into the trainer's other input buffer. Under the fault word
@@ -2239,7 +2284,7 @@ struct SeqLossArgs {
 // Stage -1 for the workgroup of tile (mt, nt), all eight waves: the first layer's W stages, the next batch's gather, the tile's loss
 // blocks and their hand-off to layer 0 (`W0`: that layer's weights). `dead`: the launch's entry test -- only the gather runs.
 // FWD_SEAM (rowstep_kernel): the blocks' `act` rows are produced inside this launch, by the four workgroups of the row tile: every wave
-// that runs a block first waits for the tile's counter to reach `c.base + c.seam0 - 1` seams, as a layer's loader waves would. Nothing
+// that runs a block first waits for the tile's 32 words to reach seam `c.base + c.seam0 - 1`, as a layer's loader waves would. Nothing
 // is requested in front of that poll: the four workgroups of a tile run in step, so the poll is usually passed at its first look, and
 // whatever sits in front of its vmcnt(0) is a round trip added to the chain, not hidden by it (W3, b3 and the rows' indices and metadata
 // touched there, to warm this CU's L1 for loss_body: +0.8 us per step, DESIGN_HISTORY).
@@ -2273,14 +2318,14 @@ __device__ __forceinline__ void rowseq_loss_stage(const uint16_t* W0, const SeqL
     uint32_t* const flag = c.flags + mt * 32;
     const int quartet = w >> 2;
     const int block = 5 * mt + (nt == 0 ? quartet : nt + 1);
-    if (FWD_SEAM && seq_poll_expired(flag, (c.base + c.seam0 - 1u) * 32u, c.limit) && l == 0) seq_raise_fault(c.flags + SEQ_FAULT_WORD, c.st);
+    if (FWD_SEAM && seq_poll_expired(flag, t, c.base + c.seam0 - 1u + c.bias, c.limit) && l == 0) seq_raise_fault(c.flags + SEQ_FAULT_WORD, c.st);
     if (block < x.nblk) {
       float* scratch = reinterpret_cast<float*>(smem + 4 * RG80_STAGE) + quartet * (3 * 4 * 4 * 4);
       uint32_t* const f = qsync + quartet;
       loss_body<false, true, E, 4>(x.loss, block, w & 3, l, nullptr, scratch, LossPre{0, 0, 0, 0.f, 0.f}, [f] { lds_bump(f); lds_wait_ge(f, 4u); });
     }
     ACEZ_VMCNT(0);   // this wave's dZ stores are acknowledged by the L2 the four sibling workgroups share
-    if (l == 0) seq_bump(flag, nt == 0 ? 1u : 2u);   // 8 per workgroup: eight waves, or four
+    if (l < (nt == 0 ? 1 : 2)) seq_post(flag + seq_word(nt, w) + 4 * l, c.base + c.seam0);   // the workgroup's eight words: eight waves, or four with their partners'
   }
 }
 
@@ -2292,10 +2337,10 @@ __global__ __launch_bounds__(512) void rowseq_loss_kernel(RowSeqArgs a, SeqLossA
   const int mt = t.mt, nt = t.nt();
   seq_record_placement(a, t);
   const bool dead = SEQ_DEAD(a.st, a.flags);
-  const SeqCtx c{a.M, a.st, a.flags, a.base[mt], 1u, a.spin_limit};
+  const SeqCtx c{a.M, a.st, a.flags, a.base[mt], 1u, a.spin_limit, a.poll_bias};
   rowseq_loss_stage<E, false>(a.layer[0].W, x, c, dead, smem, mt, nt, row_tiles(a.M));
   if (dead) {   // (one seam more than rowseq_kernel's launch)
-    if (threadIdx.x == 0) seq_catch_up(seq_seams(a.n_layers, 1), a.flags, mt);
+    if (threadIdx.x == 0) seq_catch_up(a.base[mt] + seq_seams(a.n_layers, 1), a.flags, mt, nt);
     return;
   }
   rowseq_layers<true, E, true>(a.layer, a.n_layers, c, smem, mt, nt * 128);
@@ -2309,7 +2354,7 @@ __global__ __launch_bounds__(512) void rowseq_loss_kernel(RowSeqArgs a, SeqLossA
 // dirty lines (which now leave the L2 by eviction, under the input-gradient layers).
 //   seams     per launch and row tile: n_fwd - 1 between the forward layers, one from the last forward layer (which signals: TAIL) to the
 //             loss blocks, one from the loss blocks to the first input-gradient layer, n_bwd - 1 between those: n_fwd + n_bwd (15 for the
-//             default head). One counter array, one base per row tile; a dead launch adds the same amount.
+//             default head). One array of lines, one base per row tile; a dead launch leaves the same words.
 //   L1        nothing is read through a CU's L1 before it is produced: `act` (fc2's output) has no reader inside the forward chain, the
 //             buffers the input-gradient chain and the loss write are none of the forward chain's inputs, the mask bits are written and
 //             read by the same lane. No fence, no cache write-back or invalidate anywhere in the launch.
@@ -2321,6 +2366,7 @@ struct RowStepArgs {
   uint32_t* flags;       // as RowSeqArgs: flags, base, spin_limit, xcc_dbg -- once for both chains
   uint32_t base[64];
   uint32_t spin_limit;
+  uint32_t poll_bias;
   uint32_t* xcc_dbg;
   SeqLossArgs x;
 };
@@ -2335,11 +2381,11 @@ __global__ __launch_bounds__(512) void rowstep_kernel(RowStepArgs a) {
   seq_record_placement(a, t);
   const bool dead = SEQ_DEAD(a.st, a.flags);
   const uint32_t base = a.base[mt];
-  if (!dead) rowseq_layers<false, E, false, true>(a.fwd, a.n_fwd, SeqCtx{a.M, a.st, a.flags, base, 0u, a.spin_limit}, smem, mt, nt * 128);
-  const SeqCtx c{a.M, a.st, a.flags, base, (uint32_t)a.n_fwd + 1u, a.spin_limit};
+  if (!dead) rowseq_layers<false, E, false, true>(a.fwd, a.n_fwd, SeqCtx{a.M, a.st, a.flags, base, 0u, a.spin_limit, a.poll_bias}, smem, mt, nt * 128);
+  const SeqCtx c{a.M, a.st, a.flags, base, (uint32_t)a.n_fwd + 1u, a.spin_limit, a.poll_bias};
   rowseq_loss_stage<E, true>(a.bwd[0].W, a.x, c, dead, smem, mt, nt, row_tiles(a.M));
   if (dead) {
-    if (threadIdx.x == 0) seq_catch_up(seq_seams(a.n_fwd + a.n_bwd, 1), a.flags, mt);
+    if (threadIdx.x == 0) seq_catch_up(base + seq_seams(a.n_fwd + a.n_bwd, 1), a.flags, mt, nt);
     return;
   }
   rowseq_layers<true, E, true>(a.bwd, a.n_bwd, c, smem, mt, nt * 128);
@@ -2351,7 +2397,8 @@ __global__ __launch_bounds__(512) void rowstep_kernel(RowStepArgs a) {
 // reads only when the gradients are complete, and pay a kernel boundary; here
 //  * both row slabs of a 128 x 128 tile are placed on ONE XCD (layer = XCD, 32 workgroups each for the default head). A workgroup
 //    finalises the 64 x 128 half tile of its slab index: its two multiplier waves of the OTHER half store their accumulators to the
-//    partner's exchange tile (this XCD's L2), wait for the acknowledgement and bump the partner's counter -- rowseq_kernel's hand-off:
+//    partner's exchange tile (this XCD's L2), wait for the acknowledgement and bump the partner's counter (two senders per word, so a
+//    counter and not rowseq_kernel's progress words: seq_bump, seq_poll_word_expired) --
 //    L2-local atomic, bounded sc1 poll on the other side, no fence, nothing read before it is produced;
 //  * the eight loader waves, idle once the last stage is requested, fetch p, m, v of the half tile a dozen stages before the K loop
 //    ends, then poll, add own (through LDS) + partner partial in slab order (slab 0 + slab 1: the additions of grad_reduce_kernel /
@@ -2504,7 +2551,7 @@ __global__ __launch_bounds__(WGRAD_THREADS) void wgrad_opt_kernel(WgradArgs a, W
 #ifdef ACEZ_DIAG   // fault injection in SOME workgroups (ACEZ_WGO_FAULT_MOD): a partially applied step
   if (o.fault_mod > 0 && b % o.fault_mod == 1) wgo_target += 1u << 20;
 #endif
-  if (seq_poll_expired(flag, wgo_target, o.spin_limit)) {   // the partner never arrived (the two slabs of a tile are not on one XCD after all): fault word, step switched off
+  if (seq_poll_word_expired(flag, wgo_target, o.spin_limit)) {   // the partner never arrived (the two slabs of a tile are not on one XCD after all): fault word, step switched off
     skip = true;
     if (l == 0) {
       // What the host needs to finish this step (wgo_recover, head_api.hip): which rows were not updated, and with what they would have

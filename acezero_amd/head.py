@@ -403,6 +403,13 @@ class HeadTrainer:
                                                  out.nbytes, _stream()))
         return out
 
+    def seq_words(self):
+        """Hand-off state of the one-launch chains (tests): (words uint32 [64, 32] -- word 8 nt + w of row tile mt's line is the last seam
+        wave w of column tile nt has completed --, the sticky fault word, the host's seam bases uint32 [64])."""
+        out = np.zeros(64 * 32 + 32 + 64, np.uint32)
+        N.check(self.lib.acez_trainer_debug_read(self._h, 10, 0, out.ctypes.data_as(C.c_void_p), out.nbytes, _stream()))
+        return out[:2048].reshape(64, 32).copy(), int(out[2048]), out[2080:].copy()
+
     def current_poses(self):
         """Refined world->cam poses [n_images,3,4] (PoseRefiner.get_all_current_poses, refine_poses.py:184-210)."""
         n = int(self._buf["image_pose_inv"].shape[0])

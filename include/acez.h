@@ -461,7 +461,9 @@ int acez_trainer_set_step_chain(acez_trainer* tr, int enable);   /* default 1; m
  * 4: bias-gradient partial rows of layer `index`, f32 [max_batch/32][512];  5: s_memtime stamps of the chain kernel
  * (ACEZ_CHAIN_TRACE=1), u64 [2][256];  6: XCD placement record of the one-launch GEMM chains (ACEZ_SEQ_XCC=1), u32 [8 + 256]:
  * words 0..7 = OR of 1 << XCC_ID over the workgroups with blockIdx & 7 = word, word 8 + 4 mt + nt = XCC_ID that ran tile
- * (mt, nt) in the last launch.  No reference counterpart (autograd internals). */
+ * (mt, nt) in the last launch;  10: the hand-off state of the one-launch chains, u32 [64][32] progress words (word 8 nt + w of row
+ * tile mt's line: the last seam wave w of column tile nt has completed) + [32] the line of the sticky fault word (word 0) + [64] the
+ * host's seam bases per row tile; `bytes` must be exactly (64 * 32 + 32 + 64) * 4.  No reference counterpart (autograd internals). */
 int acez_trainer_debug_read(acez_trainer* tr, int kind, int index, void* h_out, int64_t bytes, void* stream);
 
 /* Current refined world->cam poses of all images, f32 [n_images][3][4] (PoseRefiner.get_all_current_poses,
