@@ -23,7 +23,10 @@ STAMP_DIAG = os.path.join(HERE, ".libacez_diag.stamp")
 # The mesh unit is all integers; it carries the flag like its neighbours, so that a float added to it later starts out exact.
 UNITS = {
     "acez_common.hip": [],
-    "head_api.hip": [],
+    "head_api.hip": [],      # the head's host side; its kernels are the next three units
+    "head_kernels.hip": [],  # the chain unit: its kernels' code depends on which siblings share the module (DESIGN_HISTORY.md), keep it whole
+    "head_optim.hip": [],
+    "head_maps.hip": [],
     "encoder_api.hip": [],
     "conv_kernels.hip": [],
     "buffer_api.hip": [],

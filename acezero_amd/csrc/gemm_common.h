@@ -1,4 +1,4 @@
-// gemm_common.h -- device helpers shared by the GEMM-shaped kernels (head_kernels.hip, conv_kernels.hip, head_maps.hip):
+// gemm_common.h -- device helpers shared by the GEMM-shaped kernels (head_kernels.hip, head_optim.hip, conv_kernels.hip, head_maps.hip):
 // bf16 packing, LDS swizzles, LDS-DMA address-space typedefs, counted waits.
 #pragma once
 #include <hip/hip_runtime.h>

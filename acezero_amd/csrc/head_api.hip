@@ -1,8 +1,10 @@
 // head_api.hip -- C-ABI entry points of the head training / inference path (include/acez.h, group T).
-// Host-side orchestration only: every entry point enqueues kernels of head_kernels.hip on the caller's stream.
-#include "head_kernels.hip"
-#include "pose_fused.hip"
-#include "head_maps.hip"
+// Host-side orchestration only: every entry point enqueues kernels of the chain unit (head_kernels.hip), the optimiser unit
+// (head_optim.hip, with the pose network's launches) or the whole-frame unit (head_maps.hip) on the caller's stream. Their declarations and
+// argument structs are in head_kernels.h; the host's side of the chains' hand-off protocol uses head_seq.h.
+#include <hip/hip_runtime.h>
+#include "head_kernels.h"
+#include "head_seq.h"
 #include "acez_common.h"
 #include "conv_launch.h"
 #include <stdlib.h>
@@ -123,7 +125,7 @@ struct acez_trainer {
   bool step_chain = true;
   long step_chain_steps = 0;   // steps run through the merged launch (acez_trainer_step_chain_status)
   long seq_launches = 0, seq_fault_at = -1;   // tests: ACEZ_SEQ_FAULT_AT=<n> makes the n-th launch time out
-  // wgrad_opt_kernel (head_kernels.hip): the optimiser step of the wide layers inside the weight-gradient launch of the single-GPU fused
+  // wgrad_opt_kernel (head_optim.hip): the optimiser step of the wide layers inside the weight-gradient launch of the single-GPU fused
   // step. Same placement contract and safety net as the one-launch chains (tr->seq, the probe, the bounded poll, seq_err): usable only
   // while they are, and only when every workgroup of the launch is resident (wgrad_opt_usable).
   bool wgrad_opt = true;          // ACEZ_WGRAD_OPT=0 (diagnostics build): wgrad_kernel + the optimiser's tile workgroups, as before
@@ -151,6 +153,28 @@ enum { KC_SCHED = 0, KC_GATHER, KC_GEMM_FWD, KC_LOSS, KC_GEMM_DGRAD, KC_WGRAD, K
 // loss_kernel's workgroups for n rows (4 waves of 4 rows); the gather's for n rows (4 rows per workgroup and pass, at most 1024)
 static int loss_blocks(int n) { return (n + 15) / 16; }
 static int gather_blocks(int n) { return (n + 3) / 4 < 1024 ? (n + 3) / 4 : 1024; }
+
+// the kernel instantiation of a context's 16-bit operand format: f(EltF16{}) or f(EltBf16{})
+template <class F>
+static inline void with_elt(bool f16, F f) {
+  if (f16) f(EltF16{});
+  else f(EltBf16{});
+}
+
+// host-side dispatch on the epilogue shape (the flags of RowGemmArgs select the instantiation)
+static inline void launch_rowgemm(const RowGemmArgs& g, hipStream_t s, bool f16 = false) {
+  const bool br = g.bias != nullptr;
+  const dim3 grid = chain_grid(row_tiles(g.M));
+#define ACEZ_RG(...) with_elt(f16, [&](auto e) { hipLaunchKernelGGL((rowgemm80_kernel<__VA_ARGS__, decltype(e)>), grid, dim3(512), 0, s, g); })
+  if (br && g.aux_mode == AUX_NONE) ACEZ_RG(true, false, false, AUX_NONE);
+  else if (br && g.aux_mode == AUX_RESIDUAL) ACEZ_RG(true, false, false, AUX_RESIDUAL);
+  else if (!br && g.mask_in && !g.add && g.aux_mode == AUX_NONE) ACEZ_RG(false, false, true, AUX_NONE);
+  else if (!br && g.mask_in && !g.add && g.aux_mode == AUX_UNMASKED) ACEZ_RG(false, false, true, AUX_UNMASKED);
+  else if (!br && g.mask_in && g.add && g.aux_mode == AUX_UNMASKED) ACEZ_RG(false, true, true, AUX_UNMASKED);
+  else if (!br && g.mask_in && g.add && g.aux_mode == AUX_NONE) ACEZ_RG(false, true, true, AUX_NONE);
+  else abort();  // no other epilogue shape exists in the head
+#undef ACEZ_RG
+}
 
 // the pose tile (images per workgroup) as a template argument: f(std::integral_constant<int, T>, workgroups for n_images)
 template <class F>
@@ -530,7 +554,6 @@ extern "C" int acez_trainer_sync_weights(acez_trainer* tr, void* stream) {
   return ACEZ_OK;
 }
 
-// forward chain on n rows whose input features are in `in0`; returns the fc2 output buffer
 // rowseq_kernel is usable when its workgroups wait for each other safely: all of them resident at once
 static bool seq_usable(const acez_trainer* tr, int n) {
   const int mtiles = row_tiles(n);
@@ -547,7 +570,7 @@ static bool wgrad_opt_usable(const acez_trainer* tr) {
          tr->cfg.pose_refinement == 0 && 256 * ((tr->L + 7) / 8) <= tr->n_cus;
 }
 
-// The host's side of the hand-off protocol (head_kernels.hip) for one launch on a trainer's progress words, in front of the launch: `base`
+// The host's side of the hand-off protocol (head_seq.h) for one launch on a trainer's progress words, in front of the launch: `base`
 // (the launch's argument) = the seams completed so far per row tile -- the launch's waves post base + 1, base + 2, ... and poll for
 // them --; the trainer's own bases move on by the `seams` the launch completes on the row tiles of ITS n-row batch (seq_seams: a launch
 // that returns at entry leaves base + seams in its words). `stands_for`: the launches of the per-chain flow this one counts as in
@@ -585,30 +608,20 @@ static void launch_rowseq(acez_trainer* tr, const std::vector<SeqLayer>& layers,
   }
 }
 
-// collect != null: nothing is launched; the layer table of the one-launch chain goes to *collect (head_group.hip builds its tables so)
-static uint16_t* launch_forward(acez_trainer* tr, const uint16_t* in0, int n, const TrainState* st, hipStream_t s,
-                                std::vector<SeqLayer>* collect = nullptr) {
-  ProfScope chain_scope(tr, s, collect ? -1 : KC_GEMM_FWD);  // one event pair around the whole chain of dependent GEMM launches
+// A trainer's two GEMM chains as layer tables, one row per layer in launch order. Every flow reads them: the per-layer launches
+// (rowgemm_args), the one-launch chains (launch_rowseq), the merged step launch (launch_rowstep) and the group's device tables (head_group.hip).
+// The forward chain on input rows in0; its last row's out_main is the fc2 output. training: every layer leaves its ReLU mask as bits for
+// the input-gradient chain (fc2's mask is applied by the loss kernel).
+static std::vector<SeqLayer> forward_layers(const acez_trainer* tr, const uint16_t* in0, bool training) {
   const float* P = tr->pb.d_params;
-  const bool seq = collect || seq_usable(tr, n);
   std::vector<SeqLayer> sq;
-  // a training forward (st != null) leaves every layer's ReLU mask as bits for the input-gradient chain; fc2's mask is applied by the loss kernel
-  auto mask_out = [&](int l) -> uint2* { return (st && tr->maskbits && l != 3 * (tr->nb + 1) + 1) ? tr->maskbits + (size_t)l * tr->mask_stride : nullptr; };
+  auto mask_out = [&](int l) -> uint2* { return (training && tr->maskbits && l != 3 * (tr->nb + 1) + 1) ? tr->maskbits + (size_t)l * tr->mask_stride : nullptr; };
   auto gemm = [&](int l, const uint16_t* in, uint16_t* out_main, const uint16_t* res, uint16_t* out_aux) {
-    if (seq) {
-      SeqLayer y{};
-      y.In = in; y.W = tr->Wb + (size_t)l * 262144; y.bias = P + (int64_t)l * 262656 + 262144; y.res = res; y.out_main = out_main;
-      y.out_aux = out_aux; y.aux_mode = res ? AUX_RESIDUAL : AUX_NONE;
-      y.mask_out = mask_out(l);
-      sq.push_back(y);
-      return;
-    }
-    RowGemmArgs g{};
-    g.In = in; g.W = tr->Wb + (size_t)l * 262144; g.bias = P + (int64_t)l * 262656 + 262144;
-    g.add = nullptr; g.mask_out = mask_out(l); g.mask_in = nullptr; g.res = res; g.out_main = out_main; g.out_aux = out_aux;
-    g.M = n; g.N = 512; g.K = 512; g.relu = 1; g.aux_mode = res ? AUX_RESIDUAL : AUX_NONE; g.st = st; g.bias_partials = nullptr;
-    launch_rowgemm(g, s, tr->f16);
-    ++tr->prof_launches;
+    SeqLayer y{};
+    y.In = in; y.W = tr->Wb + (size_t)l * 262144; y.bias = P + (int64_t)l * 262656 + 262144; y.res = res; y.out_main = out_main;
+    y.out_aux = out_aux; y.aux_mode = res ? AUX_RESIDUAL : AUX_NONE;
+    y.mask_out = mask_out(l);
+    sq.push_back(y);
   };
   const uint16_t* r = in0;
   for (int b = 0; b <= tr->nb; ++b) {
@@ -622,9 +635,59 @@ static uint16_t* launch_forward(acez_trainer* tr, const uint16_t* in0, int n, co
   const int f1 = 3 * (tr->nb + 1), f2 = f1 + 1;
   gemm(f1, r, tr->out[f1], nullptr, nullptr);
   gemm(f2, tr->out[f1], tr->out[f2], nullptr, nullptr);
-  if (collect) *collect = sq;
-  else if (seq) launch_rowseq<false>(tr, sq, n, st, s);
-  return tr->out[f2];
+  return sq;
+}
+
+// The input-gradient chain of a training step, from dZ of fc2 (written by the loss) down to the first layer
+static std::vector<SeqLayer> dgrad_layers(const acez_trainer* tr) {
+  const int f1 = 3 * (tr->nb + 1), f2 = f1 + 1;
+  std::vector<SeqLayer> sq;
+  auto dgrad = [&](int l, int l_out, const uint16_t* add, uint16_t* out_main, uint16_t* out_aux) {
+    if (add && !out_aux) abort();   // rowseq_kernel<true> has the three epilogue shapes of this chain only (an `add` comes with a residual-gradient output)
+    SeqLayer y{};
+    y.In = tr->dZ[l]; y.W = tr->WbT + (size_t)l * 262144; y.add = add; y.out_main = out_main; y.out_aux = out_aux;
+    y.mask_in = tr->maskbits + (size_t)l_out * tr->mask_stride;   // the bits forward layer l_out left (RowGemmArgs::mask_in)
+    y.bias_partials = tr->bias_partials + (size_t)l_out * tr->bias_layer_stride; y.aux_mode = out_aux ? AUX_UNMASKED : AUX_NONE;
+    sq.push_back(y);
+  };
+  dgrad(f2, f1, nullptr, tr->dZ[f1], nullptr);
+  int cur = 0;
+  dgrad(f1, 3 * tr->nb + 2, nullptr, tr->dZ[3 * tr->nb + 2], tr->dR[cur]);
+  for (int b = tr->nb; b >= 0; --b) {
+    dgrad(3 * b + 2, 3 * b + 1, nullptr, tr->dZ[3 * b + 1], nullptr);
+    dgrad(3 * b + 1, 3 * b, nullptr, tr->dZ[3 * b], nullptr);
+    if (b > 0) {
+      dgrad(3 * b, 3 * (b - 1) + 2, tr->dR[cur], tr->dZ[3 * (b - 1) + 2], tr->dR[cur ^ 1]);
+      cur ^= 1;
+    }
+  }
+  return sq;
+}
+
+// A table row as the arguments of its per-layer launch (rowgemm80_kernel) on M rows: what rowseq_layers fills in on the device
+static RowGemmArgs rowgemm_args(const SeqLayer& y, int M, bool relu, const TrainState* st, uint32_t* absmax) {
+  RowGemmArgs g{};
+  g.In = y.In; g.W = y.W; g.bias = y.bias; g.add = y.add; g.mask_out = y.mask_out; g.mask_in = y.mask_in; g.res = y.res;
+  g.out_main = y.out_main; g.out_aux = y.out_aux; g.bias_partials = y.bias_partials; g.aux_mode = y.aux_mode;
+  g.M = M; g.N = 512; g.K = 512; g.relu = relu ? 1 : 0; g.st = st; g.absmax = absmax;
+  return g;
+}
+
+// one chain on per-layer launches
+static void launch_layers(acez_trainer* tr, const std::vector<SeqLayer>& layers, int n, bool relu, const TrainState* st, uint32_t* absmax, hipStream_t s) {
+  for (const SeqLayer& y : layers) {
+    launch_rowgemm(rowgemm_args(y, n, relu, st, absmax), s, tr->f16);
+    ++tr->prof_launches;
+  }
+}
+
+// forward chain on n rows whose input features are in `in0` (st != null: a training forward); returns the fc2 output buffer
+static uint16_t* launch_forward(acez_trainer* tr, const uint16_t* in0, int n, const TrainState* st, hipStream_t s) {
+  ProfScope chain_scope(tr, s, KC_GEMM_FWD);  // one event pair around the whole chain of dependent GEMM launches
+  const std::vector<SeqLayer> layers = forward_layers(tr, in0, st != nullptr);
+  if (seq_usable(tr, n)) launch_rowseq<false>(tr, layers, n, st, s);
+  else launch_layers(tr, layers, n, true, st, nullptr, s);
+  return layers.back().out_main;
 }
 
 static void fill_loss_head(acez_trainer* tr, LossArgs& a) {
@@ -882,60 +945,24 @@ static SeqLossArgs train_loss_in_chain(const StepRun& r) {
   return x;
 }
 
-// The input-gradient chain of a training step (collect != null: nothing is launched, the one-launch chain's layer table goes to *collect;
-// inchain != null: the step's loss and the next batch's gather ride in the chain's launch)
-static void launch_dgrad(acez_trainer* tr, int n, const TrainState* st, hipStream_t s, std::vector<SeqLayer>* collect = nullptr,
-                         const StepRun* inchain = nullptr) {
-  const int f1 = 3 * (tr->nb + 1), f2 = f1 + 1;
-  const bool seq = collect || seq_usable(tr, n);
-  std::vector<SeqLayer> sq;
-  auto dgrad = [&](int l, int l_out, const uint16_t* add, uint16_t* out_main, uint16_t* out_aux) {
-    const uint2* mask = tr->maskbits + (size_t)l_out * tr->mask_stride;   // the bits forward layer l_out left (RowGemmArgs::mask_in)
-    if (seq) {
-      if (add && !out_aux) abort();   // rowseq_kernel<true> has the three epilogue shapes of this chain only (an `add` comes with a residual-gradient output)
-      SeqLayer y{};
-      y.In = tr->dZ[l]; y.W = tr->WbT + (size_t)l * 262144; y.add = add; y.mask_in = mask; y.out_main = out_main; y.out_aux = out_aux;
-      y.bias_partials = tr->bias_partials + (size_t)l_out * tr->bias_layer_stride; y.aux_mode = out_aux ? AUX_UNMASKED : AUX_NONE;
-      sq.push_back(y);
-      return;
-    }
-    RowGemmArgs g{};
-    g.bias_partials = tr->bias_partials + (size_t)l_out * tr->bias_layer_stride;
-    g.In = tr->dZ[l]; g.W = tr->WbT + (size_t)l * 262144; g.bias = nullptr; g.add = add; g.mask_in = mask; g.mask_out = nullptr; g.res = nullptr;
-    g.out_main = out_main; g.out_aux = out_aux; g.M = n; g.N = 512; g.K = 512; g.relu = 0;
-    g.aux_mode = out_aux ? AUX_UNMASKED : AUX_NONE; g.st = st;
-    g.absmax = tr->f16 ? tr->st->dz_absmax_slots : nullptr;
-    launch_rowgemm(g, s, tr->f16);
-    ++tr->prof_launches;
-  };
-  ProfScope dchain(tr, s, collect ? -1 : KC_GEMM_DGRAD);
-  dgrad(f2, f1, nullptr, tr->dZ[f1], nullptr);
-  int cur = 0;
-  dgrad(f1, 3 * tr->nb + 2, nullptr, tr->dZ[3 * tr->nb + 2], tr->dR[cur]);
-  for (int b = tr->nb; b >= 0; --b) {
-    dgrad(3 * b + 2, 3 * b + 1, nullptr, tr->dZ[3 * b + 1], nullptr);
-    dgrad(3 * b + 1, 3 * b, nullptr, tr->dZ[3 * b], nullptr);
-    if (b > 0) {
-      dgrad(3 * b, 3 * (b - 1) + 2, tr->dR[cur], tr->dZ[3 * (b - 1) + 2], tr->dR[cur ^ 1]);
-      cur ^= 1;
-    }
-  }
-  if (collect) *collect = sq;
-  else if (seq && inchain) {
+// The input-gradient chain of a training step. inchain != null (train_step_impl: only where the one-launch chain runs): the step's loss and
+// the next batch's gather ride in the chain's launch
+static void launch_dgrad(acez_trainer* tr, int n, const TrainState* st, hipStream_t s, const StepRun* inchain = nullptr) {
+  ProfScope dchain(tr, s, KC_GEMM_DGRAD);
+  const std::vector<SeqLayer> layers = dgrad_layers(tr);
+  if (inchain) {
     const SeqLossArgs x = train_loss_in_chain(*inchain);
-    launch_rowseq<true>(tr, sq, n, st, s, &x);
+    launch_rowseq<true>(tr, layers, n, st, s, &x);
   }
-  else if (seq) launch_rowseq<true>(tr, sq, n, st, s);
-  else if (inchain) abort();   // (train_step_impl only asks for it where the one-launch chain runs)
+  else if (seq_usable(tr, n)) launch_rowseq<true>(tr, layers, n, st, s);
+  else launch_layers(tr, layers, n, false, st, tr->f16 ? tr->st->dz_absmax_slots : nullptr, s);
 }
 
-// Both chains of a fused step and its loss as ONE launch (rowstep_kernel): the layer tables of launch_forward and launch_dgrad, the loss
-// arguments of the three-launch flow, seq_account for n_fwd + n_bwd hand-offs per row tile
+// Both chains of a fused step and its loss as ONE launch (rowstep_kernel): the two layer tables, the loss arguments of the three-launch
+// flow, seq_account for n_fwd + n_bwd hand-offs per row tile
 static void launch_rowstep(const StepRun& r) {
   acez_trainer* tr = r.tr;
-  std::vector<SeqLayer> fwd, bwd;
-  launch_forward(tr, tr->R[0], r.n, r.st, r.s, &fwd);
-  launch_dgrad(tr, r.n, r.st, r.s, &bwd);
+  const std::vector<SeqLayer> fwd = forward_layers(tr, tr->R[0], r.st != nullptr), bwd = dgrad_layers(tr);
   if (fwd.size() > SEQ_MAX_LAYERS || bwd.size() > SEQ_MAX_LAYERS || bwd.empty()) abort();   // (train_step_impl only asks for it where both tables fit)
   RowStepArgs a{};
   for (size_t i = 0; i < fwd.size(); ++i) a.fwd[i] = fwd[i];
@@ -1112,7 +1139,7 @@ static void launch_chain(const StepRun& r, bool bwd) {
   if (r.step_chain) {   // one launch for both chains, made where the input-gradient chain's would be
     if (bwd) launch_rowstep(r);
   }
-  else if (bwd) launch_dgrad(r.tr, r.n, r.st, r.s, nullptr, r.loss_in_chain ? &r : nullptr);
+  else if (bwd) launch_dgrad(r.tr, r.n, r.st, r.s, r.loss_in_chain ? &r : nullptr);
   else launch_forward(r.tr, r.tr->R[0], r.n, r.st, r.s);
 }
 

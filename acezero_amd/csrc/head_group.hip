@@ -9,99 +9,7 @@
 // seam it waits on was closed while it worked on the other heads' tiles, and the next body's first W stages are requested behind the
 // current epilogue exactly as between two layers of one head. Measured: 0.96 x the members' own steps at H = 3 --
 // the members' activations together no longer fit the Infinity Cache -- so the session does not use it by default.
-
-constexpr int GROUP_MAX = 8;
-
-// one member's chain layer tables (device memory, written once by acez_train_group_create)
-struct GroupHead {
-  SeqLayer fwd[2][MAX_LAYERS];   // [which of the trainer's two input buffers is R[0] this step][layer] (acez_train_step_next swaps them)
-  SeqLayer bwd[MAX_LAYERS];
-  uint32_t* flags;               // the trainer's progress words + sticky fault word (RowSeqArgs::flags)
-  uint32_t spin_limit;
-  int pad;
-};
-
-// per-step arguments (kernel argument block: no host-to-device copy per step)
-struct RowSeqGroupArgs {
-  const GroupHead* heads;
-  const TrainState* st[GROUP_MAX];
-  int M[GROUP_MAX];
-  int variant[GROUP_MAX];              // GroupHead::fwd index
-  uint32_t base[GROUP_MAX][64];        // per member and row tile: seams completed by earlier launches (RowSeqArgs::base)
-  uint32_t poll_bias[GROUP_MAX];       // RowSeqArgs::poll_bias
-  int H, layer0, n_layers, mtiles;     // layers [layer0, layer0 + n_layers) of every member's table; mtiles = the largest member's
-};
-
-template <bool BWD, class E = EltBf16>
-__global__ __launch_bounds__(512) void rowseq_group_kernel(RowSeqGroupArgs a) {
-  __shared__ __attribute__((aligned(16))) uint16_t smem[RG80_SMEM_SEQ];
-  __shared__ uint32_t run_mask;
-  // rowseq_kernel's decode over the largest member's row tiles: the four column tiles of row tile mt of EVERY member share one XCD
-  RowTile t;
-  if (!row_tile_decode(a.mtiles, t)) return;
-  const int mt = t.mt, n0 = t.n0();
-  if (threadIdx.x == 0) {
-    // which members this workgroup runs, decided once for the whole workgroup: row tile mt inside the member's batch, its schedule
-    // active and its fault word down (rowseq_kernel's entry test, per member). A member that does not run keeps its words in step with
-    // the host's bases exactly as rowseq_kernel's early return does; row tiles past a member's batch are not counted (seq_account).
-    uint32_t run = 0;
-    for (int h = 0; h < a.H; ++h) {
-      if (mt >= row_tiles(a.M[h])) continue;
-      uint32_t* flags = a.heads[h].flags;
-      if (SEQ_DEAD(a.st[h], flags)) {
-        seq_catch_up(a.base[h][mt] + seq_seams(a.n_layers), flags, mt, t.nt());
-        continue;
-      }
-      run |= 1u << h;
-    }
-    run_mask = run;
-  }
-  __syncthreads();
-  const uint32_t run = __builtin_amdgcn_readfirstlane(run_mask);
-  if (!run) return;
-  auto table = [&](int h, int layer) -> const SeqLayer& {
-    const GroupHead& g = a.heads[h];
-    return BWD ? g.bwd[a.layer0 + layer] : g.fwd[a.variant[h]][a.layer0 + layer];
-  };
-  bool first = true;
-  for (int layer = 0; layer < a.n_layers; ++layer) {
-    for (int h = 0; h < a.H; ++h) {
-      if (!((run >> h) & 1u)) continue;
-      const SeqLayer& y = table(h, layer);
-      // the body this workgroup runs next: the next member of this layer, else the first member of the next layer
-      const uint32_t later = run & ~((2u << h) - 1u);
-      const uint16_t* next_W = nullptr;
-      if (later) next_W = table(__builtin_ctz(later), layer).W;
-      else if (layer + 1 < a.n_layers) next_W = table(__builtin_ctz(run), layer + 1).W;
-      const TrainState* st = a.st[h];
-      RowGemmArgs g;   // (rowseq_layers' row -> RowGemmArgs, SeqLink and epilogue shape, written out: see there)
-      g.In = y.In; g.W = y.W; g.bias = y.bias; g.add = y.add; g.mask_out = y.mask_out; g.mask_in = y.mask_in; g.res = y.res; g.out_main = y.out_main; g.out_aux = y.out_aux;
-      g.bias_partials = y.bias_partials; g.M = a.M[h]; g.N = 512; g.K = 512; g.relu = BWD ? 0 : 1; g.aux_mode = y.aux_mode; g.st = st;
-      g.absmax = (BWD && st) ? const_cast<uint32_t*>(st->dz_absmax_slots) : nullptr;
-      SeqLink q;
-      // (target and budget are scalar operands of the poll: the table lives in global memory, so say that they are uniform)
-      // (... and the line's address, the scalar base of the poll's load)
-      const uint64_t line = reinterpret_cast<uint64_t>(a.heads[h].flags + mt * 32);
-      q.flag = reinterpret_cast<uint32_t*>((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)line) |
-                                           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(line >> 32)) << 32));
-      q.post = (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.base[h][mt] + (uint32_t)layer + 1u));
-      q.target = q.post - 1u + (uint32_t)__builtin_amdgcn_readfirstlane((int)a.poll_bias[h]);
-      q.first = first; q.wait = layer > 0; q.signal = layer + 1 < a.n_layers;
-      q.next_W = next_W;
-      q.flag_index = (uint32_t)(mt * 32); q.limit = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.heads[h].spin_limit);
-      first = false;
-      if (!BWD) {
-        if (y.aux_mode == AUX_RESIDUAL) rowgemm80_body<true, false, false, AUX_RESIDUAL, true, E>(g, smem, 1, mt, n0, q);
-        else rowgemm80_body<true, false, false, AUX_NONE, true, E>(g, smem, 1, mt, n0, q);
-      } else {
-        if (y.add) rowgemm80_body<false, true, true, AUX_UNMASKED, true, E>(g, smem, 1, mt, n0, q);
-        else if (y.aux_mode == AUX_UNMASKED) rowgemm80_body<false, false, true, AUX_UNMASKED, true, E>(g, smem, 1, mt, n0, q);
-        else rowgemm80_body<false, false, true, AUX_NONE, true, E>(g, smem, 1, mt, n0, q);
-      }
-    }
-  }
-}
-#undef SEQ_DEAD
+// The kernel is in the chain unit (head_kernels.hip), its argument structs in head_kernels.h; this is the host's half.
 
 struct acez_train_group {
   std::vector<acez_trainer*> m;
@@ -140,11 +48,8 @@ extern "C" int acez_train_group_create(acez_train_group** out, acez_trainer* con
     acez_trainer* t = members[i];
     GroupHead& gh = heads[i];
     memset(&gh, 0, sizeof(gh));
-    // the members' own chain tables: what launch_forward / launch_dgrad hand to rowseq_kernel (a training forward: st != null)
-    std::vector<SeqLayer> f0, f1, b;
-    launch_forward(t, t->R[0], t->max_batch, t->st, nullptr, &f0);
-    launch_forward(t, t->R0_alt, t->max_batch, t->st, nullptr, &f1);
-    launch_dgrad(t, t->max_batch, t->st, nullptr, &b);
+    // the members' own chain tables: what launch_forward / launch_dgrad hand to rowseq_kernel (a training forward)
+    const std::vector<SeqLayer> f0 = forward_layers(t, t->R[0], true), f1 = forward_layers(t, t->R0_alt, true), b = dgrad_layers(t);
     for (size_t l = 0; l < f0.size(); ++l) { gh.fwd[0][l] = f0[l]; gh.fwd[1][l] = f1[l]; }
     for (size_t l = 0; l < b.size(); ++l) gh.bwd[l] = b[l];
     gh.flags = t->seq_flags; gh.spin_limit = t->seq_spin_limit;

@@ -217,4 +217,302 @@ struct WgradOptArgs {
   int fault_mod;         // diagnostics build: workgroups with b % fault_mod == 1 wait for a count that never comes (a partial fault); 0: none
 };
 
+// ---- the one-launch chains (head_kernels.hip): a chain's layer table and the launches' arguments
+struct SeqLayer {
+  const uint16_t *In, *W;
+  const float* bias;
+  const uint16_t *add, *res;
+  uint2* mask_out;          // RowGemmArgs::mask_out / mask_in
+  const uint2* mask_in;
+  uint16_t *out_main, *out_aux;
+  float* bias_partials;
+  int aux_mode, pad;
+};
+constexpr int SEQ_MAX_LAYERS = 8;
+struct RowSeqArgs {
+  SeqLayer layer[SEQ_MAX_LAYERS];
+  int n_layers, M;
+  const TrainState* st;
+  uint32_t* flags;     // [64 row tiles][32] progress words + [SEQ_FAULT_WORD] the fault word
+  uint32_t base[64];   // per row tile: seams completed by earlier launches (a launch only touches the row tiles of ITS batch)
+  uint32_t spin_limit; // poll budget of a hand-off (polls of >= ~0.5 us); expired: fault word + st->active = 0
+  uint32_t poll_bias;  // 0; tests (seq_account): added to every seam this launch POLLS for, not to what it posts -- a seam that never comes
+  uint32_t* xcc_dbg;   // null, or [8 + 256]: words 0..7 |= 1 << XCC_ID of the workgroups with blockIdx & 7 = word (sticky); word
+                       // 8 + 4 mt + nt = XCC_ID of the workgroup that owned tile (mt, nt) in the last launch (tests: the four column
+                       // tiles of a row tile must report the same XCD)
+                       // flags[SEQ_FAULT_WORD] = the sticky fault word (non-zero: a poll of this trainer has expired, every launch returns at
+                       // once), flags[SEQ_FAULT_WORD + 1] = a copy of the poll budget (diagnostics)
+};
+
+// rowseq_loss_kernel / rowstep_kernel: the loss launch as a stage of the chain's launch (head_kernels.hip, "rowseq_loss")
+struct SeqLossArgs {
+  LossArgs loss;
+  int nblk;                  // loss blocks of the batch (loss_kernel's grid)
+  const uint16_t* feat;      // the next batch: gather_rows' arguments (n_next = 0: none)
+  const int64_t* idx_next;
+  uint16_t* out_next;
+  int n_next;
+  GatherMeta meta;
+};
+
+// rowstep_kernel: both chains and the loss stage of a fused step in one launch (head_kernels.hip, "rowstep")
+struct RowStepArgs {
+  SeqLayer fwd[SEQ_MAX_LAYERS], bwd[SEQ_MAX_LAYERS];
+  int n_fwd, n_bwd, M;
+  const TrainState* st;
+  uint32_t* flags;       // as RowSeqArgs: flags, base, spin_limit, xcc_dbg -- once for both chains
+  uint32_t base[64];
+  uint32_t spin_limit;
+  uint32_t poll_bias;
+  uint32_t* xcc_dbg;
+  SeqLossArgs x;
+};
+static_assert(sizeof(RowStepArgs) <= 4096, "kernel-argument segment");
+
+// ---- the schedule wave's arguments in the launches that carry it (step_begin_kernel, adamw_next_kernel, wgrad_opt_kernel, step_begin_pose_kernel)
+struct PostArgs {
+  const TrainState* src;   // the slot the closing step's kernels read
+  TrainState* st;          // the slot the bookkeeping writes (the other one; == src: in place)
+  SchedConfig c;
+  const float* grad_stats;
+  float inv_global_batch;
+  float* log_loss;
+  float* log_inl;
+  int log_cap;
+  const int* fault;
+  const float* stat_partials;   // the loss kernel's per-workgroup statistics of the step being closed (slot 3: largest |ds|) and their count
+  int n_loss_blocks;
+};
+
+// ---- grids and workgroup shapes the host and the kernels agree on
+constexpr int WGRAD_RING = 4;                       // slots of the [dZ | In] stage ring, 32 KiB each (RING - 1 stages in flight per CU)
+constexpr int WGRAD_LOADERS = 8;                    // loader waves per workgroup (beside the 4 multiplier waves)
+constexpr int WGRAD_THREADS = 256 + 64 * WGRAD_LOADERS;
+// Workgroups of the optimiser's part of a launch: the first adamw_small_blocks() handle the small parameters (biases, fc3) and, in
+// the fused step, the statistics; then one workgroup per 64 x 64 weight tile. (Small first: each of them is a chain of dependent
+// round trips -- partials -> butterfly -> p, m, v -> store -- that should run under the streaming tile blocks, not after them.)
+__host__ __device__ inline int adamw_small_blocks(int n_layers, int64_t n_fc3, bool fused) {
+  const int64_t n_small = (int64_t)n_layers * 512 + n_fc3;
+  return fused ? (int)((n_small + 4 + 63) / 64)   // fused: 64 outputs per workgroup, four lanes each (adamw_small_columns)
+               : (int)((n_small + 255) / 256);
+}
+// small-parameter workgroups of a fused optimiser launch (wgrad_opt_kernel: one per 32 outputs, in the multiplier waves of the first ones)
+__host__ __device__ inline int small_cols_blocks(int n_layers, int64_t n_fc3, int lanes_per_output) {
+  const int64_t per = 256 / lanes_per_output;
+  return (int)(((int64_t)n_layers * 512 + n_fc3 + 4 + per - 1) / per);
+}
+constexpr int GR_TAIL_LANES = 8;   // lanes per output of grad_reduce_kernel's tail (4: 97 workgroups with 80 loads per lane in flight; 8: 193 with 40)
+__host__ __device__ inline int grad_reduce_tail_blocks(int n_layers, int64_t n_fc3) { return small_cols_blocks(n_layers, n_fc3, GR_TAIL_LANES); }
+
+// ---- whole-frame inference (head_maps.hip)
+struct HeadMapsArgs {
+  const uint16_t* In;       // [n][512] feature rows
+  const uint16_t* Wf;       // fragment-ordered weights of the L wide layers
+  const float* params;      // the flat fp32 parameter vector (bias of layer l at l * 262656 + 262144)
+  uint16_t* R[8];           // R[b], b = 1 .. nb: [n][512] scratch of the residual stream after block b - 1 (unused entries null)
+  uint16_t* Out;            // [n][512]: the output of the last wide layer (fc2), what loss_kernel's fc3 reads -- or null with `fc3` below
+  int n, nb;
+  // fc3 + de-homogenisation on the finished tile (ace_network.py:135-149): the arithmetic of loss_body's phases A / B (same per-lane FMA
+  // chains, the same DPP wave sum, the same expressions: the same function of the activations as loss_kernel's); the
+  // [n][512] activation map is then neither written nor read (315 MB each way per 64 frames) and the separate launch (117 us) is gone.
+  int fc3;                  // 1: write scene coordinates to out_xyz instead of activations to Out
+  const uint16_t* W3;       // [no][512] 16-bit
+  const float* b3;          // [no]
+  int no, use_homogeneous;
+  float mean[3], max_inv_scale, min_inv_scale, h_beta;
+  float* out_xyz;           // [n][3], or with planar_hw > 0 [frames][3][planar_hw] (row m = frame * planar_hw + pixel), rows offset by row_offset
+  int planar_hw, row_offset;
+};
+
+// ---- pose refinement (pose_kernels.hip, pose_small.hip, pose_fused.hip)
+struct PoseNetArgs {
+  const float* P;          // flat parameters
+  const float* Wt;         // [4][128][128] transposed copies of conv2, conv3, fc1, fc2 (pose_transpose_kernel), forward only
+  const float* T0;         // [I][16] original world->cam poses
+  int I;
+  float w;                 // update weight (refine_poses.py:165)
+  float *a1, *a2, *a3, *r, *f1, *f2;   // [I][128] activations
+  float* delta;            // [I][12]
+  float* pose_cur;         // [I][16] refined poses (forward) 
+  const float* dT;         // [I][12] gradient wrt the refined pose (backward)
+  float *ddelta, *dz2, *dz1, *dr, *dzc3, *dzc2, *dzc1;   // backward: gradients wrt each layer's pre-activation output
+  const int* active;
+  int ortho;               // 0 gram-schmidt, 1 procrustes (--refinement_ortho)
+  unsigned long long* trace;   // diagnostics build (ACEZ_POSE_TRACE=1, tools/pose_trace.py): [tiles][16] s_memtime stamps of thread 0; else null
+};
+constexpr int64_t PN_SKIP_W = 0, PN_SKIP_B = 1536, PN_C1_W = 1664, PN_C1_B = 3200, PN_C2_W = 3328, PN_C2_B = 19712, PN_C3_W = 19840,
+                  PN_C3_B = 36224, PN_F1_W = 36352, PN_F1_B = 52736, PN_F2_W = 52864, PN_F2_B = 69248, PN_F3_W = 69376, PN_F3_B = 70912;
+constexpr int PN_IMG = 16;     // images per workgroup
+struct PoseWgradArgs {
+  const float* dY[7]; const float* X[7];
+  int O[7], K[7], xpitch[7];
+  int64_t offW[7], offB[7];
+  int I;
+  float* grad;            // pose gradient vector (d_grad + n_params + 4)
+  const int* active;
+  int job_start[8];       // prefix sums of ceil(O / 16) * ceil(K / 16) over the layers
+  // Fused optimiser (single-GPU step: the tile's gradient is final inside this workgroup, so AdamW -- adamw_small_kernel's arithmetic --
+  // is applied on the spot and the transposed forward copies Wt[wt_slot] of the four 128 x 128 layers are refreshed): fuse = 0 in
+  // the backward / all-reduce / update flow, where adamw_small_kernel and pose_transpose_kernel do this after the all-reduce.
+  int fuse;
+  float *p, *m, *v, *Wt;
+  int wt_slot[7];         // index into Wt[4][128][128] of the layer, -1: none
+  const AdamScalars* sc;
+  const int* enable;      // st->pose_enable (ace_trainer.py:634-636)
+  const int* fault;       // rowseq fault word: an abandoned step updates nothing
+  unsigned long long* trace;   // diagnostics build (ACEZ_POSE_TRACE=1): [jobs][16] s_memtime stamps of thread 0; else null
+};
+// W = waves of the workgroup (template parameter of pose_small.hip's bodies): W / 2 reduction slices, 64 W threads. The forward (S3) runs with
+// 8 waves, the reduce + backward chain (S1) with 4: its launch is shared with the optimiser's 256-thread workgroups (twice the waves to
+// dispatch cost more than the shorter layers gave back), and its gradients keep the two-slice summation order.
+constexpr int PN4_W_FWD = 8, PN4_W_BWD = 4;
+// T = images per pose workgroup: 16 = the v_mfma_f32_16x16x4_f32 bodies of pose_kernels.hip (256 threads), 4 = the small tiles of
+// pose_small.hip (a quarter of the matrix time per layer, four times as many CUs, 512 threads; the default). A launch's workgroups
+// all have pose_threads<T>() threads: in the launches shared with the optimiser its workgroups use the first 256 (the other waves
+// return at once), the gather's rows are spread over the waves there are.
+template <int T>
+constexpr int pose_threads() { return 256; }              // the launches that hold S1 (PN4_W_BWD = 4 waves)
+template <int T>
+constexpr int pose_fwd_threads() { return T == 16 ? 256 : 64 * PN4_W_FWD; }
+
+// ---------------------------------------------------------------------------------------------------
+// Every kernel the host launches (head_api.hip, head_group.hip), declared with the launch bounds of its definition. Templates: the product's
+// instantiations, once -- ACEZ_*_KERNELS(extern template __global__, E) here, ACEZ_*_KERNELS(template __global__, E) in the defining unit.
+// ---------------------------------------------------------------------------------------------------
+// head_kernels.hip (the chain unit)
+template <bool BIAS_RELU, bool HAS_ADD, bool HAS_MASK, int AUX, class E>
+__global__ __launch_bounds__(512) void rowgemm80_kernel(RowGemmArgs a);
+template <bool BWD, class E>
+__global__ __launch_bounds__(512) void rowseq_kernel(RowSeqArgs a);
+__global__ __launch_bounds__(512) void seq_probe_kernel(uint32_t* rec /*[256]*/, int mtiles);
+template <class E, int LR>
+__global__ __launch_bounds__(256) void loss_kernel(LossArgs a);
+template <class E, int LR>
+__global__ __launch_bounds__(256) void loss_gather_kernel(LossArgs a, int nblk, const uint16_t* __restrict__ feat, const int64_t* __restrict__ idx_next,
+                                                          uint16_t* __restrict__ out, int n_next, GatherMeta meta);
+template <class E>
+__global__ __launch_bounds__(512) void rowseq_loss_kernel(RowSeqArgs a, SeqLossArgs x);
+template <class E>
+__global__ __launch_bounds__(512) void rowstep_kernel(RowStepArgs a);
+#define ACEZ_CHAIN_KERNELS(X, E)                                                                                                       \
+  X void rowgemm80_kernel<true, false, false, AUX_NONE, E>(RowGemmArgs);                                                               \
+  X void rowgemm80_kernel<true, false, false, AUX_RESIDUAL, E>(RowGemmArgs);                                                           \
+  X void rowgemm80_kernel<false, false, true, AUX_NONE, E>(RowGemmArgs);                                                               \
+  X void rowgemm80_kernel<false, false, true, AUX_UNMASKED, E>(RowGemmArgs);                                                           \
+  X void rowgemm80_kernel<false, true, true, AUX_UNMASKED, E>(RowGemmArgs);                                                            \
+  X void rowgemm80_kernel<false, true, true, AUX_NONE, E>(RowGemmArgs);                                                                \
+  X void rowseq_kernel<false, E>(RowSeqArgs);                                                                                          \
+  X void rowseq_kernel<true, E>(RowSeqArgs);                                                                                           \
+  X void rowseq_loss_kernel<E>(RowSeqArgs, SeqLossArgs);                                                                               \
+  X void rowstep_kernel<E>(RowStepArgs);                                                                                               \
+  X void loss_kernel<E, 4>(LossArgs);                                                                                                  \
+  X void loss_gather_kernel<E, 4>(LossArgs, int, const uint16_t*, const int64_t*, uint16_t*, int, GatherMeta);
+ACEZ_CHAIN_KERNELS(extern template __global__, EltBf16)
+ACEZ_CHAIN_KERNELS(extern template __global__, EltF16)
+
+// head_optim.hip (the optimiser unit)
+__global__ __launch_bounds__(256) void gather_kernel(const uint16_t* __restrict__ feat, const int64_t* __restrict__ idx, uint16_t* __restrict__ out, int n,
+                                                     const TrainState* st, GatherMeta meta);
+__global__ __launch_bounds__(256) void step_begin_kernel(const uint16_t* __restrict__ feat, const int64_t* __restrict__ idx, uint16_t* __restrict__ out, int n,
+                                                         PostArgs p, GatherMeta meta);
+template <class E>
+__global__ __launch_bounds__(WGRAD_THREADS) void wgrad_kernel(WgradArgs a);
+template <class E>
+__global__ __launch_bounds__(WGRAD_THREADS) void wgrad_opt_kernel(WgradArgs a, WgradOptArgs o, PostArgs post);
+template <class E>
+__global__ __launch_bounds__(512) void wgo_recover_kernel(AdamArgs ad, const float* __restrict__ slabs, int64_t slab_stride, const uint32_t* __restrict__ status,
+                                                          const WgoFaultRec* __restrict__ rec, int n_layers);
+__global__ __launch_bounds__(256) void grad_reduce_kernel(GradReduceArgs a);
+__global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a);
+__global__ __launch_bounds__(256, 4) void adamw_next_kernel(AdamArgs a, int n_adam, const uint16_t* __restrict__ feat, const int64_t* __restrict__ idx_next,
+                                                            uint16_t* __restrict__ out, int n_next, PostArgs p, GatherMeta meta);
+__global__ __launch_bounds__(256) void transpose16_kernel(const uint16_t* __restrict__ Wb, uint16_t* __restrict__ WbT, int layer_lo);
+__global__ __launch_bounds__(256) void import16_kernel(const uint16_t* __restrict__ src, uint16_t* __restrict__ Wb, uint16_t* __restrict__ WbT, int own_lo,
+                                                       int own_hi);
+__global__ __launch_bounds__(256) void recast_kernel(AdamArgs a);
+__global__ void sched_reactivate_kernel(TrainState* st);
+__global__ void sched_init_kernel(TrainState* st, SchedConfig c);
+__global__ __launch_bounds__(64) void sched_post_kernel(const TrainState* src, TrainState* st, SchedConfig c, const float* grad_stats, float inv_global_batch,
+                                                        float* log_loss, float* log_inl, int log_cap, const int* fault, const float* stat_partials,
+                                                        int n_loss_blocks);
+#define ACEZ_OPTIM_KERNELS(X, E)                                                                                                       \
+  X void wgrad_kernel<E>(WgradArgs);                                                                                                   \
+  X void wgrad_opt_kernel<E>(WgradArgs, WgradOptArgs, PostArgs);                                                                       \
+  X void wgo_recover_kernel<E>(AdamArgs, const float*, int64_t, const uint32_t*, const WgoFaultRec*, int);
+ACEZ_OPTIM_KERNELS(extern template __global__, EltBf16)
+ACEZ_OPTIM_KERNELS(extern template __global__, EltF16)
+
+// ... and the pose chain it includes (pose_kernels.hip -> pose_small.hip -> pose_fused.hip)
+__global__ __launch_bounds__(256) void pose_compose_kernel(const float* T0 /*[I][16]*/, const float* delta /*[I][12]*/, float w, float* out /*[I][16]*/,
+                                                           int n_images, const int* active, int ortho);
+__global__ __launch_bounds__(256) void pose_compose_bwd_kernel(const float* T0, const float* delta, float w, const float* dT /*[I][12]*/,
+                                                               float* ddelta /*[I][12]*/, int n_images, const int* active, int ortho);
+__global__ __launch_bounds__(256) void pose_mlp_fwd_kernel(PoseNetArgs a);
+__global__ __launch_bounds__(256) void pose_transpose_kernel(const float* P, float* Wt, const int* active);
+__global__ __launch_bounds__(256) void pose_mlp_bwd_kernel(PoseNetArgs a);
+template <int PW_BATCH, int PW_WAVES>
+__global__ __launch_bounds__(64 * PW_WAVES, PW_BATCH <= 32 ? PW_WAVES / 2 : 2) void pose_mlp_wgrad_kernel(PoseWgradArgs a);
+__global__ __launch_bounds__(256) void pose_grad_reduce2_kernel(const float* row_dT /*[n][12]*/, const int* row_image /*[n]*/, int n, float* dT /*[I][12]*/,
+                                                                int n_images, const int* active);
+template <int T>
+__global__ __launch_bounds__(pose_fwd_threads<T>(), T == 16 ? 2 : 1) void step_begin_pose_kernel(const uint16_t* __restrict__ feat, const int64_t* __restrict__ idx,
+                                                                 uint16_t* __restrict__ out, int n, PostArgs p, int do_post, PoseNetArgs a, int np,
+                                                                 GatherMeta meta);
+template <int T>
+__global__ __launch_bounds__(pose_fwd_threads<T>()) void pose_fwd_t_kernel(PoseNetArgs a);
+template <int T>
+__global__ __launch_bounds__(256, 3) void adamw_pose_kernel(AdamArgs a, PoseNetArgs pn, const float* row_dT, const int* row_image, int n, int np);
+template <int T>
+__global__ __launch_bounds__(256, 3) void grad_reduce_pose_kernel(GradReduceArgs a, PoseNetArgs pn, const float* row_dT, const int* row_image, int n, int np);
+__global__ __launch_bounds__(256, 4) void adamw_split_pose_kernel(AdamArgs a, int npb, float* p, float* m, float* v, const float* g, int64_t n,
+                                                                  const AdamScalars* sc, const int* enable, const int* active, const int* fault,
+                                                                  const float* reduced_fault, float* Wt, int n_adam, const uint16_t* __restrict__ feat,
+                                                                  const int64_t* __restrict__ idx_next, uint16_t* __restrict__ out, int n_next, GatherMeta meta);
+#define ACEZ_POSE_KERNELS(X, T)                                                                                                        \
+  X void step_begin_pose_kernel<T>(const uint16_t*, const int64_t*, uint16_t*, int, PostArgs, int, PoseNetArgs, int, GatherMeta);       \
+  X void adamw_pose_kernel<T>(AdamArgs, PoseNetArgs, const float*, const int*, int, int);                                              \
+  X void grad_reduce_pose_kernel<T>(GradReduceArgs, PoseNetArgs, const float*, const int*, int, int);
+ACEZ_POSE_KERNELS(extern template __global__, 4)
+ACEZ_POSE_KERNELS(extern template __global__, 16)
+extern template __global__ void pose_fwd_t_kernel<4>(PoseNetArgs);
+extern template __global__ void pose_mlp_wgrad_kernel<16, 8>(PoseWgradArgs);
+
+// head_maps.hip
+__global__ __launch_bounds__(256) void wfrag_pack_kernel(const uint16_t* __restrict__ Wb, uint16_t* __restrict__ Wf, int n_frags);
+template <class E>
+__global__ __launch_bounds__(512) void head_maps_kernel(HeadMapsArgs a);
+extern template __global__ void head_maps_kernel<EltBf16>(HeadMapsArgs);
+extern template __global__ void head_maps_kernel<EltF16>(HeadMapsArgs);
+
 }  // namespace acez
+
+// ---- the head group's chain launch (rowseq_group_kernel, head_kernels.hip; host: head_group.hip). These three names live in the global
+// namespace, where the group's file has always declared them: the kernel's symbol is part of the stored profiles.
+constexpr int GROUP_MAX = 8;
+
+// one member's chain layer tables (device memory, written once by acez_train_group_create)
+struct GroupHead {
+  acez::SeqLayer fwd[2][acez::MAX_LAYERS];   // [which of the trainer's two input buffers is R[0] this step][layer] (acez_train_step_next swaps them)
+  acez::SeqLayer bwd[acez::MAX_LAYERS];
+  uint32_t* flags;               // the trainer's progress words + sticky fault word (RowSeqArgs::flags)
+  uint32_t spin_limit;
+  int pad;
+};
+
+// per-step arguments (kernel argument block: no host-to-device copy per step)
+struct RowSeqGroupArgs {
+  const GroupHead* heads;
+  const acez::TrainState* st[GROUP_MAX];
+  int M[GROUP_MAX];
+  int variant[GROUP_MAX];              // GroupHead::fwd index
+  uint32_t base[GROUP_MAX][64];        // per member and row tile: seams completed by earlier launches (RowSeqArgs::base)
+  uint32_t poll_bias[GROUP_MAX];       // RowSeqArgs::poll_bias
+  int H, layer0, n_layers, mtiles;     // layers [layer0, layer0 + n_layers) of every member's table; mtiles = the largest member's
+};
+template <bool BWD, class E>
+__global__ __launch_bounds__(512) void rowseq_group_kernel(RowSeqGroupArgs a);
+#define ACEZ_GROUP_KERNELS(X, E) \
+  X void rowseq_group_kernel<false, E>(RowSeqGroupArgs); \
+  X void rowseq_group_kernel<true, E>(RowSeqGroupArgs);
+ACEZ_GROUP_KERNELS(extern template __global__, acez::EltBf16)
+ACEZ_GROUP_KERNELS(extern template __global__, acez::EltF16)

@@ -1,5 +1,5 @@
 // head_maps.hip -- the head's wide layers on whole frames (acez_head_forward_maps / acez_head_forward with >= 32 768 rows per pass:
-// Regressor.forward at registration time, register_mapping.py:201-242 -> ace_network.py:120-149) as ONE launch. Included by head_api.hip.
+// Regressor.forward at registration time, register_mapping.py:201-242 -> ace_network.py:120-149) as ONE launch. A unit of its own (HeadMapsArgs: head_kernels.h).
 //
 // Until round 6 these passes ran the eight 512 -> 512 layers as eight launches of the encoder's large-tile kernel (convgemm512_kernel:
 // 266-342 us per layer and 307 200 rows, 0.19-0.23 of the MFMA peak, every layer's activations written to and read back from HBM).
@@ -20,29 +20,12 @@
 //     coalesced pass over the tile: the block input is re-read from global memory (block 0: the features themselves; later blocks: the
 //     tile is copied out to R[b] when it is produced) -- a residual kept in registers would be 64 VGPRs next to 128 accumulators.
 // tools/chain128_proto.hip is the timing prototype (8 layers on 307 200 rows: 1277 us against 2430 for the eight launches).
-#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "head_kernels.h"
 #include "gemm_common.h"
 
 namespace acez {
-
-struct HeadMapsArgs {
-  const uint16_t* In;       // [n][512] feature rows
-  const uint16_t* Wf;       // fragment-ordered weights of the L wide layers
-  const float* params;      // the flat fp32 parameter vector (bias of layer l at l * 262656 + 262144)
-  uint16_t* R[8];           // R[b], b = 1 .. nb: [n][512] scratch of the residual stream after block b - 1 (unused entries null)
-  uint16_t* Out;            // [n][512]: the output of the last wide layer (fc2), what loss_kernel's fc3 reads -- or null with `fc3` below
-  int n, nb;
-  // fc3 + de-homogenisation on the finished tile (ace_network.py:135-149): the arithmetic of loss_body's phases A / B (same per-lane FMA
-  // chains, the same DPP wave sum, the same expressions: the same function of the activations as loss_kernel's); the
-  // [n][512] activation map is then neither written nor read (315 MB each way per 64 frames) and the separate launch (117 us) is gone.
-  int fc3;                  // 1: write scene coordinates to out_xyz instead of activations to Out
-  const uint16_t* W3;       // [no][512] 16-bit
-  const float* b3;          // [no]
-  int no, use_homogeneous;
-  float mean[3], max_inv_scale, min_inv_scale, h_beta;
-  float* out_xyz;           // [n][3], or with planar_hw > 0 [frames][3][planar_hw] (row m = frame * planar_hw + pixel), rows offset by row_offset
-  int planar_hw, row_offset;
-};
 
 // Wf[((l * 16 + cb) * 32 + kk) * 512 + lane * 8 + e] = Wb[l][cb * 32 + (lane & 31)][kk * 16 + (lane >> 5) * 8 + e]
 __global__ __launch_bounds__(256) void wfrag_pack_kernel(const uint16_t* __restrict__ Wb, uint16_t* __restrict__ Wf, int n_frags) {
@@ -264,5 +247,8 @@ __global__ __launch_bounds__(512) void head_maps_kernel(HeadMapsArgs a) {
     }
   }
 }
+
+template __global__ void head_maps_kernel<EltBf16>(HeadMapsArgs);
+template __global__ void head_maps_kernel<EltF16>(HeadMapsArgs);
 
 }  // namespace acez

@@ -14,18 +14,15 @@
 // long pole). Only launches whose own workgroups are small qualify -- the gather (no LDS) and the optimiser (8 KiB, HBM-bound): a
 // kernel's LDS and register allocation is the same for all of its workgroups, so the GEMM launches (112-154 KiB) cannot host them.
 // The pose workgroups are unchanged bodies of pose_kernels.hip; the per-image results are the same sums in the same order.
+// Included by head_optim.hip: its launches carry the gather (head_gather.h), the optimiser bodies (head_opt.h) and the schedule wave
+// (head_sched.h). pose_threads / pose_fwd_threads, which the host sizes these launches with, are in head_kernels.h.
 #include "pose_small.hip"
+#include "head_gather.h"
+#include "head_opt.h"
+#include "head_sched.h"
 
 namespace acez {
 
-// T = images per pose workgroup: 16 = the v_mfma_f32_16x16x4_f32 bodies of pose_kernels.hip (256 threads), 4 = the small tiles of
-// pose_small.hip (a quarter of the matrix time per layer, four times as many CUs, 512 threads; the default). A launch's workgroups
-// all have pose_threads<T>() threads: in the launches shared with the optimiser its workgroups use the first 256 (the other waves
-// return at once), the gather's rows are spread over the waves there are.
-template <int T>
-constexpr int pose_threads() { return 256; }              // the launches that hold S1 (PN4_W_BWD = 4 waves)
-template <int T>
-constexpr int pose_fwd_threads() { return T == 16 ? 256 : 64 * PN4_W_FWD; }
 template <int T>
 constexpr int pose_fwd_smem_floats() { return T == 16 ? 4 : pose4_fwd_smem_floats<(T == 16 ? 8 : T)>(); }
 template <int T>
@@ -129,7 +126,7 @@ __global__ __launch_bounds__(256, 4) void adamw_split_pose_kernel(AdamArgs a, in
   // the four guard words are requested together, before any of them is looked at (one round trip in front of the workgroup, not four)
   const int active_now = active ? *active : 1, fault_now = fault ? *fault : 0, enabled = enable ? *enable : 1;
   const float reduced = reduced_fault ? *reduced_fault : 0.f;
-  if (!active_now || fault_now) return;   // schedule ended / abandoned step (rowseq fault, head_kernels.hip): the rank that already knows
+  if (!active_now || fault_now) return;   // schedule ended / abandoned step (rowseq fault, head_seq.h): the rank that already knows
   // ... and the rank that learns of it from the bucket: adamw_body raises `fault` / clears `active` from the all-reduced slot in THIS
   // launch, behind these workgroups in the grid, so the words are a race here and the statistic is not (as in sched_post_wave)
   if (fmodf(reduced, 1024.f) != 0.f) return;
@@ -153,5 +150,11 @@ __global__ __launch_bounds__(256, 4) void adamw_split_pose_kernel(AdamArgs a, in
     }
   }
 }
+
+// the product's instantiations (head_kernels.h)
+ACEZ_POSE_KERNELS(template __global__, 4)
+ACEZ_POSE_KERNELS(template __global__, 16)
+template __global__ void pose_fwd_t_kernel<4>(PoseNetArgs);
+template __global__ void pose_mlp_wgrad_kernel<16, 8>(PoseWgradArgs);
 
 }  // namespace acez

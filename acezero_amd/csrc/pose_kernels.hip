@@ -225,29 +225,11 @@ __global__ __launch_bounds__(256) void pose_compose_bwd_kernel(const float* T0, 
 // fp32 throughout (the reference keeps this network outside autocast). Parameter order = named_parameters():
 // head_skip, conv1, conv2, conv3, fc1, fc2, fc3 (weight, bias each).
 // ---------------------------------------------------------------------------------------------------
-struct PoseNetArgs {
-  const float* P;          // flat parameters
-  const float* Wt;         // [4][128][128] transposed copies of conv2, conv3, fc1, fc2 (pose_transpose_kernel), forward only
-  const float* T0;         // [I][16] original world->cam poses
-  int I;
-  float w;                 // update weight (refine_poses.py:165)
-  float *a1, *a2, *a3, *r, *f1, *f2;   // [I][128] activations
-  float* delta;            // [I][12]
-  float* pose_cur;         // [I][16] refined poses (forward) 
-  const float* dT;         // [I][12] gradient wrt the refined pose (backward)
-  float *ddelta, *dz2, *dz1, *dr, *dzc3, *dzc2, *dzc1;   // backward: gradients wrt each layer's pre-activation output
-  const int* active;
-  int ortho;               // 0 gram-schmidt, 1 procrustes (--refinement_ortho)
-  unsigned long long* trace;   // diagnostics build (ACEZ_POSE_TRACE=1, tools/pose_trace.py): [tiles][16] s_memtime stamps of thread 0; else null
-};
 #ifdef ACEZ_DIAG
 #define PN_STAMP(a, tile, i) do { __builtin_amdgcn_sched_barrier(0); if ((a).trace && threadIdx.x == 0) (a).trace[(size_t)(tile) * 16 + (i)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
 #define PN_STAMP(a, tile, i) do { } while (0)
 #endif
-constexpr int64_t PN_SKIP_W = 0, PN_SKIP_B = 1536, PN_C1_W = 1664, PN_C1_B = 3200, PN_C2_W = 3328, PN_C2_B = 19712, PN_C3_W = 19840,
-                  PN_C3_B = 36224, PN_F1_W = 36352, PN_F1_B = 52736, PN_F2_W = 52864, PN_F2_B = 69248, PN_F3_W = 69376, PN_F3_B = 70912;
-constexpr int PN_IMG = 16;     // images per workgroup
 
 typedef __attribute__((ext_vector_type(4))) float pn_f4;
 
@@ -453,25 +435,6 @@ __device__ __forceinline__ float adamw_small_one(float p, float gv, float& mv, f
   return pv - s.step_size * (mv / denom);
 }
 
-struct PoseWgradArgs {
-  const float* dY[7]; const float* X[7];
-  int O[7], K[7], xpitch[7];
-  int64_t offW[7], offB[7];
-  int I;
-  float* grad;            // pose gradient vector (d_grad + n_params + 4)
-  const int* active;
-  int job_start[8];       // prefix sums of ceil(O / 16) * ceil(K / 16) over the layers
-  // Fused optimiser (single-GPU step: the tile's gradient is final inside this workgroup, so AdamW -- adamw_small_kernel's arithmetic --
-  // is applied on the spot and the transposed forward copies Wt[wt_slot] of the four 128 x 128 layers are refreshed): fuse = 0 in
-  // the backward / all-reduce / update flow, where adamw_small_kernel and pose_transpose_kernel do this after the all-reduce.
-  int fuse;
-  float *p, *m, *v, *Wt;
-  int wt_slot[7];         // index into Wt[4][128][128] of the layer, -1: none
-  const AdamScalars* sc;
-  const int* enable;      // st->pose_enable (ace_trainer.py:634-636)
-  const int* fault;       // rowseq fault word: an abandoned step updates nothing
-  unsigned long long* trace;   // diagnostics build (ACEZ_POSE_TRACE=1): [jobs][16] s_memtime stamps of thread 0; else null
-};
 // PW_WAVES waves per workgroup: each takes 1 / PW_WAVES of the images (8 waves at 1000 images: 32 MFMA steps = two batches of 16 loads;
 // ten waves with ONE batch of 26 -- measured in round 5 -- shortened the slowest workgroup from 10.7 to 8.5 us and still lengthened the
 // launch by 18 %: 640-thread workgroups take longer to place than the round trip they save)
@@ -761,7 +724,7 @@ __device__ __forceinline__ void pose_s1_body(const PoseNetArgs& a, const float* 
 __global__ __launch_bounds__(256) void adamw_small_kernel(float* p, float* m, float* v, const float* gpart, int64_t gstride, int nz, int64_t n,
                                                           const AdamScalars* sc, const int* enable, const int* active, const int* fault) {
   if (active && !*active) return;
-  if (fault && *fault) return;   // abandoned step (rowseq fault, head_kernels.hip)
+  if (fault && *fault) return;   // abandoned step (rowseq fault, head_seq.h)
   if (enable && !*enable) return;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;

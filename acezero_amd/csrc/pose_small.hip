@@ -26,10 +26,7 @@
 
 namespace acez {
 
-// W = waves of the workgroup (template parameter of everything below): W / 2 reduction slices, 64 W threads. The forward (S3) runs with
-// 8 waves, the reduce + backward chain (S1) with 4: its launch is shared with the optimiser's 256-thread workgroups (twice the waves to
-// dispatch cost more than the shorter layers gave back), and its gradients keep the two-slice summation order.
-constexpr int PN4_W_FWD = 8, PN4_W_BWD = 4;
+// (PN4_W_FWD / PN4_W_BWD, the waves of the forward and of the backward workgroups, are in head_kernels.h: the host sizes launches with them)
 
 // Row pitch of the 128-wide LDS tiles: 132 floats. A lane's B operands are 16-byte reads of image j = lane & 3: at a pitch of 128 floats
 // the four images start in the same bank (4-way conflict on every read of the product loop), at 132 they are 16 bytes apart.

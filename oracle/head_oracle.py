@@ -37,7 +37,7 @@ def fp16_round(x):
 
 
 GRAD_SCALE_FP16 = 64.0     # a factor the HIP kernels put on the gradient chain in fp16 mode: a power of two chosen per step from the
-                           # largest |d loss / d fc3 output| (head_kernels.hip sched_post_wave); scaling by a power of two commutes with fp16
+                           # largest |d loss / d fc3 output| (head_sched.h sched_post_wave); scaling by a power of two commutes with fp16
                            # rounding wherever nothing under- or overflows, so ANY in-range power of two gives the same result
 
 
@@ -247,7 +247,7 @@ class HeadOracle:
         return self.r(g * self.gs) / self.gs
 
     def next_grad_scale(self):
-        """head_kernels.hip sched_post_wave: the power of two that would have put the step's largest propagated gradient near 4096"""
+        """head_sched.h sched_post_wave: the power of two that would have put the step's largest propagated gradient near 4096"""
         if self.mode == "fp16" and self.absmax > 0:
             e = math.floor(math.log2(4096.0 / (self.absmax / self.gs)))
             self.gs = 2.0 ** min(16, max(-8, e))

@@ -1,8 +1,8 @@
 """The optimiser stage of the head's training step, restated in plain numpy (no import from the package or the oracle).
 
 What is restated, and where it lives in the kernels:
-  scalars()      sched_prepare_hot (head_kernels.hip): the seven AdamScalars of a step, computed in double and cast to float32
-  step32()       adamw_one / adamw_small_one (head_kernels.hip, pose_kernels.hip): five un-contracted float32 lines
+  scalars()      sched_prepare_hot (head_sched.h): the seven AdamScalars of a step, computed in double and cast to float32
+  step32()       adamw_one / adamw_small_one (head_opt.h, pose_kernels.hip): five un-contracted float32 lines
   step64()       the same formula in float64 from the same float32 inputs: the yardstick of the rounding bound
   bounds()       the per-element distance a correct float32 evaluation may keep from step64 (derived below)
   rne_bf16/fp16  the recast of the fp32 masters into the 16-bit compute copies (round to nearest, ties to even)

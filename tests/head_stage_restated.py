@@ -3,7 +3,7 @@
 Every stage is restated from the operands the kernel itself read: the trainer's 16-bit weight copies, the fp32 biases, and the buffers
 HeadTrainer.debug_read returns ('out', 'R', 'mask', 'dZ', 'slab', 'bias_partials') plus tr.grad after backward(). Nothing comes from
 the oracle's forward pass, so a rounding flip in one stage cannot leak into the judgement of the next. Which buffer feeds which layer is
-oracle/head_oracle.py's forward() / backward() (the same tables as head_api.hip launch_forward, launch_dgrad, fill_wgrad_args).
+oracle/head_oracle.py's forward() / backward() (the same tables as head_api.hip forward_layers, dgrad_layers, fill_wgrad_args).
 
 The criterion. For one output element let v be the fp64 value of the sum the kernel forms (K products, plus the bias, plus the residual
 gradient where there is one) and A the sum of the absolute values of the same terms. An fp32 accumulation of T terms in ANY order is off
@@ -128,7 +128,7 @@ def unkept(l, L):
 
 
 def slab_rows(n, nslabs, slab):
-    """Rows [mb, me) of a split-K slab (head_kernels.hip wgrad_kloop: rows_per_slab is rounded up to whole 64-row stages)."""
+    """Rows [mb, me) of a split-K slab (head_wgrad.h wgrad_kloop: rows_per_slab is rounded up to whole 64-row stages)."""
     rps = (n + nslabs * 64 - 1) // (nslabs * 64) * 64
     mb = slab * rps
     return mb, max(mb, min(n, mb + rps))

@@ -1,5 +1,5 @@
-"""CPU: an executable model of rowseq_kernel's hand-off protocol (acezero_amd/csrc/head_kernels.hip: the protocol section --
-row_tile_decode, seq_seams, seq_bump, seq_catch_up, SEQ_DEAD --, rowseq_kernel, SeqLink; head_api.hip: seq_account, launch_rowseq,
+"""CPU: an executable model of rowseq_kernel's hand-off protocol (acezero_amd/csrc/head_seq.h: row_tile_decode, seq_seams,
+seq_bump, seq_catch_up, SEQ_DEAD, SeqLink; head_kernels.hip: rowseq_kernel; head_api.hip: seq_account, launch_rowseq,
 seq_usable). It restates, in a few lines each, the grid decode (workgroup -> XCD, row tile, column
 tile), the per-row-tile counters (8 increments per workgroup and seam, target (base[mt] + layer) * 32), the host's base accounting
 (a launch advances the bases of ITS row tiles only; chains longer than 8 layers are split; a launch on an ended schedule does no

@@ -1,4 +1,4 @@
-"""GPU: the progress words of the same-XCD hand-off (head_kernels.hip, the protocol section: seq_post, seq_poll_expired, seq_catch_up;
+"""GPU: the progress words of the same-XCD hand-off (head_seq.h: seq_post, seq_poll_expired, seq_catch_up;
 rowstep_kernel, rowseq_kernel, rowseq_loss_kernel). Word 8 nt + w of a row tile's 128-byte line belongs to wave w of column tile nt and
 holds the last seam that wave has completed, as an absolute number; the host keeps the number of seams completed per row tile
 (head_api.hip seq_account). So after EVERY step, live or dead, all 32 words of every row tile of the batch must equal the host's base of

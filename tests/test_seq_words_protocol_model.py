@@ -1,5 +1,5 @@
-"""CPU: an executable model of the hand-off protocol's progress words (acezero_amd/csrc/head_kernels.hip, the protocol section:
-seq_word, seq_post, seq_poll_expired, seq_catch_up, SEQ_DEAD; rowgemm80_body's post and poll sites, rowseq_loss_stage; head_api.hip:
+"""CPU: an executable model of the hand-off protocol's progress words (acezero_amd/csrc/head_seq.h:
+seq_word, seq_post, seq_poll_expired, seq_catch_up, SEQ_DEAD; head_kernels.hip: rowgemm80_body's post and poll sites, rowseq_loss_stage; head_api.hip:
 seq_account). It shares no code with the device.
 
 A row tile owns one 128-byte line of 32 words; word 8 nt + w belongs to wave w of column tile nt (4 workgroups x 8 waves). Seams are

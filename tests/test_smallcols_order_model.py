@@ -1,4 +1,4 @@
-"""CPU: the summation ORDER of the column-parallel small-parameter reduction (acezero_amd/csrc/head_kernels.hip: SmallCols<4> / <8>,
+"""CPU: the summation ORDER of the column-parallel small-parameter reduction (acezero_amd/csrc/head_opt.h: SmallCols<4> / <8>,
 used by adamw_small_columns, grad_reduce_kernel's tail and the multiplier waves of wgrad_opt_kernel) is the order of tail_output (one
 wavefront per output: lane j adds the partial rows j, j + 64, ... in that order, then the xor butterfly 32, 16, ..., 1), so the two
 produce the same float32 bits. The kernels are compared on the GPU (tests/test_head_gpu.py, tests/test_wgrad_opt_gpu.py); this file

@@ -1,5 +1,5 @@
 """CPU: an executable model of rowstep_kernel's hand-off protocol (acezero_amd/csrc/head_kernels.hip: rowstep_kernel,
-rowseq_loss_stage, rowseq_layers on the protocol section's seq_seams, seq_bump, seq_catch_up and SEQ_DEAD; head_api.hip: launch_rowstep,
+rowseq_loss_stage, rowseq_layers on head_seq.h's seq_seams, seq_bump, seq_catch_up and SEQ_DEAD; head_api.hip: launch_rowstep,
 seq_account), in the style of tests/test_seq_protocol_model.py. One launch runs, per
 row tile, the forward layers, the loss blocks and the input-gradient layers on the tile's four workgroups; every stage but the last
 bumps the tile's counter 8 times per workgroup (a layer: eight waves, one each; the loss stage: eight waves x 1 in column tile 0, four

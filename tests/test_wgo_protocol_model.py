@@ -1,4 +1,4 @@
-"""CPU: an executable model of wgrad_opt_kernel's exchange protocol (acezero_amd/csrc/head_kernels.hip: wgrad_opt_kernel; head_api.hip:
+"""CPU: an executable model of wgrad_opt_kernel's exchange protocol (acezero_amd/csrc/head_optim.hip: wgrad_opt_kernel; head_api.hip:
 wgrad_opt_usable, the launch in train_backward_impl). It restates the grid decode (workgroup -> XCD, layer, slab, tile), the two
 counters of a tile (one per receiving workgroup, bumped once by each of the partner's two sending waves, never reset; a launch waits
 for 2 x the number of launches so far) and a dispatcher with a limited number of CU slots per XCD, and checks that

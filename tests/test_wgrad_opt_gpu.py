@@ -1,4 +1,4 @@
-"""GPU: wgrad_opt_kernel (head_kernels.hip) -- the optimiser step of the wide layers, the small parameters and the schedule wave inside
+"""GPU: wgrad_opt_kernel (head_optim.hip) -- the optimiser step of the wide layers, the small parameters and the schedule wave inside
 the weight-gradient launch, the next batch gathered beside the loss kernel -- against the flow it replaces (ACEZ_WGRAD_OPT=0 in the
 diagnostics build: wgrad_kernel + the optimiser launch). The two slabs of a tile are added in the same order, the small parameters are
 reduced in tail_output's order and every element goes through the same adamw_one: EVERYTHING must agree bit for bit, step after step

@@ -18,11 +18,17 @@ OUT = "/tmp/acez_isa"
 P_LGKM0 = r"s_waitcnt.*lgkmcnt\(0\)"
 
 
-def compile_units():
-    os.makedirs(OUT, exist_ok=True)
-    for unit, extra in B.UNITS.items():
-        cmd = [B._hipcc()] + B.COMMON + extra + ["-save-temps=obj", "-c", os.path.join(B.CSRC, unit), "-o", os.path.join(OUT, unit.replace(".hip", ".o"))]
-        subprocess.run(cmd, cwd=OUT, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
+def compile_units(build=B, out=OUT, prefix="", flags=()):
+    """Compile the units of `build` (an acezero_amd.build module; tools/isa_diff.py passes another checkout's) whose names start with
+    `prefix` into `out`, keeping the assembly. Returns the paths of the gfx950 .s files."""
+    os.makedirs(out, exist_ok=True)
+    units = {u: x for u, x in build.UNITS.items() if u.startswith(prefix)}
+    procs = [subprocess.Popen([build._hipcc()] + build.COMMON + extra + list(flags) + ["-save-temps=obj", "-c", os.path.join(build.CSRC, unit), "-o",
+                               os.path.join(out, unit.replace(".hip", ".o"))], cwd=out, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+             for unit, extra in units.items()]
+    if any(p.wait() for p in procs):
+        raise RuntimeError("hipcc failed on a unit of %s" % build.CSRC)
+    return [os.path.join(out, unit.replace(".hip", "") + "-hip-amdgcn-amd-amdhsa-gfx950.s") for unit in units]
 
 
 def scan(path):

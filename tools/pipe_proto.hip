@@ -12,7 +12,7 @@
 //     16 K-steps of [ds_read_b128 B-fragments] x [register A-fragments], bias + ReLU, store, and bump their own progress word.
 // L2 -> CU traffic per chain and CU: 128 KiB of weights once + 640 KiB of activations, against 8 x 208 KiB = 1664 KiB.
 // Same MFMA (16x16x32), same K order per output element as rowgemm80 => bit-identical outputs (checked first).
-#include "head_kernels.hip"
+#include "head_kernels.hip"   // the chain unit: rowgemm80_kernel is the bit-equality reference
 #include <cstdio>
 #include <vector>
 #include <cstring>
@@ -640,7 +640,7 @@ int main(int argc, char** argv) {
       RowGemmArgs g{};
       g.In = i ? outA[i - 1] : In; g.W = W + (size_t)i * 512 * 512; g.bias = bias + i * 512; g.out_main = outA[i]; g.M = M; g.N = 512; g.K = 512;
       g.relu = 1; g.aux_mode = AUX_NONE;
-      launch_rowgemm(g, 0);
+      hipLaunchKernelGGL((rowgemm80_kernel<true, false, false, AUX_NONE, EltBf16>), chain_grid(row_tiles(g.M)), dim3(512), 0, 0, g);
     }
   };
   if (M % 256) { printf("this experiment wants M %% 256 == 0 (uniform micro-batch count per XCD)\n"); return 1; }

@@ -10,7 +10,7 @@
 // layer) are requested BEFORE the wait, while the epilogue runs.
 // MODE bit 0: release AND acquire with agent-scope fences (buffer_wbl2 / buffer_inv sc1); bit 1: only the acquire fence;
 // 0: no fence at all -- the stores' acknowledgements and an L1-bypassing poll, valid because producer and consumers share one L2.
-#include "head_kernels.hip"
+#include "head_kernels.hip"   // the chain unit: rowgemm80_kernel is the bit-equality reference
 #include <cstdio>
 #include <vector>
 #include <cstring>
@@ -647,7 +647,7 @@ int main() {
       RowGemmArgs g{};
       g.In = i ? outA[i - 1] : In; g.W = W + (size_t)i * 512 * 512; g.bias = bias + i * 512; g.out_main = outA[i]; g.M = M; g.N = 512; g.K = 512;
       g.relu = 1; g.aux_mode = AUX_NONE;
-      launch_rowgemm(g, 0);
+      hipLaunchKernelGGL((rowgemm80_kernel<true, false, false, AUX_NONE, EltBf16>), chain_grid(row_tiles(g.M)), dim3(512), 0, 0, g);
     }
   };
   // bit equality of the last layer's output

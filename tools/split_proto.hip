@@ -219,7 +219,7 @@ int main() {
       RowGemmArgs g{};
       g.In = i ? outA[i - 1] : In; g.W = W + (size_t)i * 512 * 512; g.bias = bias + i * 512; g.out_main = outA[i]; g.M = M; g.N = 512; g.K = 512;
       g.relu = 1; g.aux_mode = AUX_NONE;
-      launch_rowgemm(g, 0);
+      hipLaunchKernelGGL((rowgemm80_kernel<true, false, false, AUX_NONE, EltBf16>), chain_grid(row_tiles(g.M)), dim3(512), 0, 0, g);
     }
   };
   const char* names[3] = {"rowseq 80x128, 1 per CU", "split A 40x128, 2 per CU", "split B 80x64,  2 per CU"};
