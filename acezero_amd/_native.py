@@ -92,6 +92,7 @@ class TsdfFrame(C.Structure):
                 ("reserved", C.c_int32), ("offset", C.c_int64)]
 
 
+MESHRENDER_SMALL, MESHRENDER_LARGE = 16, 1024      # ACEZ_MESHRENDER_SMALL, ACEZ_MESHRENDER_LARGE: the routes' thresholds (samples in a box)
 MVS_MAX_SOURCES = 8             # ACEZ_MVS_MAX_SOURCES; a row of the stereo entry points' table (acez_mvs_frame) is a TsdfFrame
 
 
@@ -269,6 +270,10 @@ SYMBOLS = {
     "acez_simplify_place": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                       C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "acez_simplify_unique": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "acez_meshrender_check_faces": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
+    "acez_meshrender": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(TsdfFrame), C.c_int, C.c_void_p, C.c_float,
+                                  C.c_float, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -18,7 +18,7 @@ STAMP = os.path.join(HERE, ".libacez.stamp")
 LIB_DIAG = os.path.join(HERE, "libacez_diag.so")
 STAMP_DIAG = os.path.join(HERE, ".libacez_diag.stamp")
 
-# translation unit -> extra flags.  The RANSAC (RGB and RGB-D), point-cloud, pose-evaluation, rendering, ingest, reprojection, fusion, stereo, cloud-distance, surface and simplification units must not contract a*b+c into fma: their
+# translation unit -> extra flags.  The RANSAC (RGB and RGB-D), point-cloud, pose-evaluation, rendering, mesh-rendering, ingest, reprojection, fusion, stereo, cloud-distance, surface and simplification units must not contract a*b+c into fma: their
 # arithmetic is compared bit-for-bit with the CPU oracle (DESIGN.md "Determinism"); the ingest unit's host-side tables with Pillow's.
 # The mesh unit is all integers; it carries the flag like its neighbours, so that a float added to it later starts out exact.
 UNITS = {
@@ -36,6 +36,7 @@ UNITS = {
     "cloud_api.hip": ["-ffp-contract=off"],
     "align_api.hip": ["-ffp-contract=off"],
     "render_api.hip": ["-ffp-contract=off"],
+    "meshrender_api.hip": ["-ffp-contract=off"],
     "ingest_api.hip": ["-ffp-contract=off"],
     "reproject_api.hip": ["-ffp-contract=off"],
     "fusion_api.hip": ["-ffp-contract=off"],

@@ -959,6 +959,13 @@ def fuse_depth_parser():
                                                                        "around its point have been observed this many times")
     p.add_argument("--refined_pose_file", type=Path, default=None, help="with --refine_poses: write the refined poses here, in the pose "
                                                                         "file's format (frames whose tracking was degenerate keep their pose)")
+    p.add_argument("--model_depth_dir", type=Path, default=None,
+                   help="render the mesh that is written into every fused frame's camera (after the component filter and the "
+                        "simplification, under the refined poses if --refine_poses ran) and write one 16-bit depth PNG per frame here, "
+                        "named after the image, at the depth map's own size and --depth_unit")
+    p.add_argument("--model_depth_compare", type=_strtobool, default=False,
+                   help="with --model_depth_dir: log how the rendered depth agrees with the input depth, per frame and for the folder")
+    p.add_argument("--model_depth_tolerance", type=float, default=0.01, help="with --model_depth_compare: metres up to which two depths agree")
     return p
 
 
@@ -1011,6 +1018,8 @@ def fuse_depth_main(argv=None):
     opt = parser.parse_args(argv)
     if opt.refined_pose_file is not None and opt.refine_poses == 0:
         parser.error("--refined_pose_file needs --refine_poses ROUNDS")
+    if opt.model_depth_compare and opt.model_depth_dir is None:
+        parser.error("--model_depth_compare needs --model_depth_dir DIR")
     logging.basicConfig(level=logging.INFO)
     log = logging.getLogger("fuse_depth")
     _require_ply(opt.output_file)
@@ -1080,6 +1089,16 @@ def fuse_depth_main(argv=None):
     if simplify_cell is not None:
         from . import simplify
         vertices, colours, faces, simplified = simplify.simplify_mesh(vertices, colours, faces, simplify_cell, opt.simplify_placement)
+    model_lines = None
+    if opt.model_depth_dir is not None:                      # the mesh as it is written, still on the device
+        from . import meshrender
+        stems = [os.path.splitext(os.path.basename(p[0]))[0] for p in pairs]
+        if len(set(stems)) != len(stems):
+            raise SystemExit("two images of the glob share a name: their model depth maps would overwrite each other")
+        model_lines = meshrender.render_to_folder(vertices, faces, None, c2w, focals, [d.shape for d in depth], stems, opt.model_depth_dir,
+                                                  min_depth=MODEL_MIN_DEPTH, max_depth=opt.max_depth, depth_unit=opt.depth_unit,
+                                                  compare=depth if opt.model_depth_compare else None,
+                                                  tolerance=opt.model_depth_tolerance)
     vertices, colours, faces = vertices.cpu(), colours.cpu(), faces.cpu()
     t_device = time.perf_counter() - t0
     t0 = time.perf_counter()
@@ -1105,8 +1124,123 @@ def fuse_depth_main(argv=None):
         log.info(f"Extracted mesh: {_component_summary(dropped)}.")
     if simplified is not None:
         log.info(_simplify_line(simplify_cell, opt.simplify_placement, simplified))
+    if model_lines is not None:
+        for line in model_lines:
+            log.info(line)
+        log.info(f"Wrote {len(pairs)} model depth maps to: {opt.model_depth_dir}")
     log.info(f"Decode {t_decode:.2f} s, upload + kernels + download {t_device:.2f} s, write {t_write:.2f} s.")
     log.info(f"Done. Wrote mesh to: {opt.output_file}")
+    return 0
+
+
+# ---------------------------------------------------------------------------------------------------------- render_mesh
+MODEL_MIN_DEPTH = 0.05                   # the near plane of the model depth maps, metres
+
+
+def render_mesh_parser():
+    p = argparse.ArgumentParser(description="Render a triangle mesh into the cameras of a reconstruction on the GPU: one 16-bit depth PNG "
+                                            "per image, seen from that image's pose (and, on request, normal and colour images).",
+                                formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("mesh_file", type=Path, help="mesh to render (.ply, binary little-endian or ASCII; world coordinates, OpenCV convention)")
+    p.add_argument("pose_file", type=Path, help="ACE pose file of the reconstruction (file qw qx qy qz tx ty tz f conf)")
+    p.add_argument("rgb_files", type=str, help="glob of the images, e.g. 'scene/*.jpg'")
+    p.add_argument("output_dir", type=Path, help="folder for the maps: depth/NAME.png (and normals/, colour/) per image of the glob with a pose")
+    p.add_argument("--image_resolution", type=int, default=None, help="short side of the rendered maps; default: the image's own size")
+    p.add_argument("--depth_files", type=str, default=None, help="glob of depth maps, one per image in sorted order: every frame is rendered "
+                                                                 "at its depth map's size (instead of --image_resolution)")
+    p.add_argument("--depth_unit", type=float, default=0.001, help="metres per unit of the written depth maps (0.001: millimetres)")
+    p.add_argument("--min_depth", type=float, default=MODEL_MIN_DEPTH, help="near plane in metres: triangles are clipped against it")
+    p.add_argument("--max_depth", type=float, default=65.0, help="depth beyond this many metres is not written")
+    p.add_argument("--confidence_threshold", type=float, default=1000, help="ignore pose-file entries below this confidence")
+    p.add_argument("--write_normals", type=_strtobool, default=False, help="also write normals/NAME.png: 128 + 127 n of the camera-space normal")
+    p.add_argument("--write_colour", type=_strtobool, default=False, help="also write colour/NAME.png: the mesh's vertex colours")
+    p.add_argument("--compare_depth_files", type=str, default=None, help="glob of measured depth maps (one per image, sorted, of the rendered "
+                                                                         "size and --depth_unit): log the agreement per frame and for the folder")
+    p.add_argument("--compare_tolerance", type=float, default=0.01, help="with --compare_depth_files: metres up to which two depths agree")
+    p.add_argument("--output_json", type=Path, default=None, help="with --compare_depth_files: write the agreement here")
+    return p
+
+
+def render_mesh_main(argv=None):
+    """render_mesh.py: .ply + pose file -> rasterisation into every posed image's camera (HIP) -> 16-bit depth PNGs."""
+    import glob
+    import json
+    from PIL import Image
+    from . import meshrender
+    parser = render_mesh_parser()
+    opt = parser.parse_args(argv)
+    logging.basicConfig(level=logging.INFO)
+    log = logging.getLogger("render_mesh")
+    if opt.image_resolution is not None and opt.depth_files is not None:
+        parser.error("give at most one of --image_resolution and --depth_files")
+    if opt.image_resolution is not None and opt.image_resolution < 1:
+        raise SystemExit("--image_resolution must be positive")
+    for name in ("depth_unit", "min_depth", "max_depth", "compare_tolerance"):
+        if not 0 < getattr(opt, name) < math.inf:
+            raise SystemExit(f"--{name} must be positive and finite")
+    if opt.output_json is not None and opt.compare_depth_files is None:
+        parser.error("--output_json needs --compare_depth_files")
+    if not opt.mesh_file.is_file():
+        raise SystemExit(f"{opt.mesh_file}: no such file")
+    rgb_files = sorted(glob.glob(opt.rgb_files))
+    if not rgb_files:
+        raise SystemExit(f"no files match {opt.rgb_files!r}")
+    per_image = {}
+    for flag in ("depth_files", "compare_depth_files"):
+        if getattr(opt, flag) is not None:
+            per_image[flag] = sorted(glob.glob(getattr(opt, flag)))
+            if len(per_image[flag]) != len(rgb_files):
+                raise SystemExit(f"--{flag}: {len(per_image[flag])} depth files for {len(rgb_files)} images")
+    try:
+        c2w_all, focals_all, pose_row = read_posed_images(opt.pose_file, rgb_files, opt.confidence_threshold)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    keep = [f for f, k in enumerate(pose_row) if k is not None]
+    stems = [os.path.splitext(os.path.basename(rgb_files[f]))[0] for f in keep]
+    if len(set(stems)) != len(stems):
+        raise SystemExit("two images of the glob share a name: their maps would overwrite each other")
+    vertices, colours, faces = read_ply_mesh(opt.mesh_file)
+    if opt.write_colour and colours is None:
+        raise SystemExit(f"--write_colour: {opt.mesh_file} has no vertex colours")
+    from .ingest import resized_size
+    sizes, focals = [], []
+    for f in keep:
+        iw, ih = Image.open(rgb_files[f]).size
+        if opt.depth_files is not None:
+            w, h = Image.open(per_image["depth_files"][f]).size
+        elif opt.image_resolution is not None:
+            _, h, w = resized_size(iw, ih, opt.image_resolution)
+        else:
+            h, w = ih, iw
+        sizes.append((h, w))
+        focals.append(focal_at_height(focals_all[pose_row[f]], h, ih))
+    measured = None
+    if opt.compare_depth_files is not None:
+        measured = [read_depth_png(per_image["compare_depth_files"][f]) for f in keep]
+        for d, size, f in zip(measured, sizes, keep):
+            if d.shape != size:
+                raise SystemExit(f"{per_image['compare_depth_files'][f]}: {d.shape[1]} x {d.shape[0]} px, but the frame is rendered at "
+                                 f"{size[1]} x {size[0]}: give the same files as --depth_files")
+    _require_gpu("render_mesh", "the rasterisation is a HIP kernel")
+    import torch
+    t0 = time.perf_counter()
+    device = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    report = {}
+    lines = meshrender.render_to_folder(device(vertices), device(np.ascontiguousarray(faces, np.int32)), device(colours),
+                                        np.stack([c2w_all[pose_row[f]] for f in keep]), np.array(focals), sizes, stems, opt.output_dir / "depth",
+                                        min_depth=opt.min_depth, max_depth=opt.max_depth, depth_unit=opt.depth_unit,
+                                        normals_dir=opt.output_dir / "normals" if opt.write_normals else None,
+                                        colour_dir=opt.output_dir / "colour" if opt.write_colour else None, compare=measured,
+                                        tolerance=opt.compare_tolerance, report=report)
+    log.info(f"Rendered {len(faces)} faces into {len(keep)} of {len(rgb_files)} images in {time.perf_counter() - t0:.2f} s "
+             f"(upload, kernels, download, write).")
+    for line in lines:
+        log.info(line)
+    if opt.output_json is not None:
+        with open(opt.output_json, "w") as fh:
+            json.dump(report, fh, indent=1)
+        log.info(f"Wrote the agreement to: {opt.output_json}")
+    log.info(f"Done. Wrote the maps to: {opt.output_dir}")
     return 0
 
 

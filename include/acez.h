@@ -1444,6 +1444,78 @@ int acez_simplify_place(const float* d_vertices, const uint8_t* d_colours, int64
 int acez_simplify_unique(const int32_t* d_triples, const uint8_t* d_face_class, const int64_t* d_perm, int64_t k, int64_t m,
                          uint8_t* d_face_keep, uint8_t* d_cluster_used, void* stream);
 
+/* =====================================================================================================
+ * R. A mesh seen from the frames' cameras: model depth, face ids, normals and colours per pixel (render_mesh.py, fuse_depth.py --model_depth_dir)
+ * =====================================================================================================
+ * A triangle mesh is rasterised into every frame of a table: d_vertices float32 [n_vertices][3] (world, OpenCV convention), d_faces
+ * int32 [n_faces][3], d_colours uint8 [n_vertices][3] (optional), and a HOST table of n_frames acez_tsdf_frame rows as in section K
+ * (m[12] = the 3 x 4 world -> camera rows, focal, ppx, ppy in pixels of THIS frame, h, w, and `offset`: the element index of the
+ * frame's pixel (0, 0) in every per-pixel buffer of the call). Frames of different sizes share a call. Camera and pixel convention
+ * are section K's: the pixel index is the image coordinate, so the sample of pixel (ix, iy) is the point (ix, iy) (not + 1/2), and a
+ * map rendered here and integrated by acez_tsdf_integrate under the same row is read, for a point of the surface, at the pixel it was
+ * rendered into. Coverage and depth are section H's rules in this camera. All float arithmetic is fp32, round to nearest, one
+ * rounding per operation in the order written (the unit is built without contraction), division is IEEE division.
+ * tests/meshrender_restated.py restates all of it in numpy.
+ *
+ * Per frame and face t (its id) with the vertices P0, P1, P2 in the face's order:
+ *   1. c_k = (xc, yc, zc):  xc = ((m0 * px + m1 * py) + m2 * pz) + m3      (yc from m4..m7, zc from m8..m11). A c_k with a component
+ *      that is not finite drops the triangle.
+ *   2. near plane: vertex k is IN if zc >= min_depth. None in: dropped. All in: the triangle (c_0, c_1, c_2). Else Sutherland-Hodgman
+ *      over the edges (0,1), (1,2), (2,0): an IN vertex is emitted, and an edge whose ends differ emits, with a the IN end and b the other,
+ *      t = (min_depth - a.z) / (b.z - a.z), (a.x + t * (b.x - a.x), a.y + t * (b.y - a.y), min_depth). The 3 or 4 points q_0 .. are
+ *      drawn as the triangles (q_0, q_1, q_2) and (q_0, q_2, q_3), both under the id t.
+ *   3. per triangle and vertex: a = (focal * x) / z, b = (focal * y) / z; unless |a| < 2^21 and |b| < 2^21 for all three the triangle
+ *      is dropped BY THE GUARD. u = a + ppx, v = b + ppy, iz = 1 / z; X = int64(rintf(u * 256)), Y alike (ties to even).
+ *   4. area = E(0, 1; 2) with E(a, b; p) = (X_p - X_a) * (Y_b - Y_a) - (Y_p - Y_a) * (X_b - X_a). Zero: dropped. Negative: vertices 1
+ *      and 2 change places (X, Y and iz) and area = -area: both windings are drawn.
+ *   5. box: x from max(0, ceil(min X / 256)) to min(w - 1, floor(max X / 256)), y alike with h; empty: dropped.
+ *   6. per pixel (ix, iy) of the box, S = (256 ix, 256 iy): w0 = E(1, 2; S), w1 = E(2, 0; S), w2 = E(0, 1; S). Covered if none is
+ *      negative and every zero one belongs to an OWNED edge (a, b): Y_b - Y_a > 0, or Y_b == Y_a and X_b - X_a < 0 (top-left rule).
+ *   7. invd = ((float(w0) * iz_0 + float(w1) * iz_1) + float(w2) * iz_2) / float(area), d = 1 / invd; dropped unless d <= max_depth.
+ *   8. key = (bits of d) << 32 | t; the pixel keeps the smallest key: the nearest face, and of equal depths the lower id.
+ * The image is a function of the mesh and the table alone: no ordering of the atomics enters it.
+ *
+ * Outputs, each packed by the rows' offsets, each but d_depth optional (NULL). With the winning key's d and t:
+ *   d_depth      float32   d; 0 where no face was hit
+ *   d_face       int32     t; -1 where no face was hit
+ *   d_depth_u16  uint16    q = rintf(d / depth_unit) if q <= 65535, else 0; 0 where no face was hit (the project's depth PNG)
+ *   d_normal     uint8 x 3 with c_0, c_1, c_2 of step 1 (the unclipped face), A = c_1 - c_0, B = c_2 - c_0, n = A x B (each component
+ *                two products and one difference: Ay * Bz - Az * By, Az * Bx - Ax * Bz, Ax * By - Ay * Bx), the pixel's ray
+ *                r = (float(ix) - ppx, float(iy) - ppy, focal): n is negated if (n.x * r.x + n.y * r.y) + n.z * r.z > 0 (it then faces
+ *                the camera); len = float(sqrt(double((n.x * n.x + n.y * n.y) + n.z * n.z))); component c -> 128 + rintf((c / len) * 127),
+ *                clamped to 1 .. 255. (128, 128, 128) if len is 0 or infinite; (0, 0, 0) where no face was hit
+ *   d_colour     uint8 x 3 C_k = c_(k+1) x c_(k+2) (indices mod 3, components as above), e_k = (r.x * C_k.x + r.y * C_k.y) + r.z * C_k.z,
+ *                D = (e_0 + e_1) + e_2; per channel m = ((e_0 * float(col_0) + e_1 * float(col_1)) + e_2 * float(col_2)) / D, then
+ *                min(floorf(m + 0.5), 255), 0 if that is negative or not a number. The barycentrics come from the unclipped vertices
+ *                (section H's textured path), so near-plane clipping does not change them. (0, 0, 0) where no face was hit
+ *   d_status     int32 [1] the triangle-frames dropped by the guard of step 3 (a clipped triangle counts once). Not zero: the image
+ *                may have a hole there; callers log a warning. Guard-band clipping against the side planes is not done.
+ *
+ * Work distribution (acezero_amd/csrc/meshrender_api.hip). One lane per face keeps the face's world vertices in
+ * registers over the frames its block walks. Per frame the largest box (step 5) of the face's one or two triangles picks the route:
+ * at most ACEZ_MESHRENDER_SMALL samples and not clipped: the lane walks the box itself; at most ACEZ_MESHRENDER_LARGE samples, or
+ * clipped: the lane's wavefront walks it with 64 lanes; more: the workgroup walks it with 256 threads. All routes run the same
+ * steps 2-8, so the route changes no key.
+ *
+ * acez_meshrender: d_keys uint64 [n_keys] scratch (one key per pixel of the call), the planes of n_pixels elements (x 3 for normal and
+ * colour), d_frames device scratch of n_frames rows: all the caller's; nothing is allocated. The table is checked here and copied into
+ * d_frames on `stream`; the copy has completed when the call returns, everything else is asynchronous. n_frames = 0 does nothing;
+ * n_faces = 0 clears the planes. A face with an index outside 0 .. n_vertices - 1 is passed over by the kernels, which therefore form
+ * no index outside their buffers whatever d_faces holds; since the faces live in device memory, refusing such a mesh is
+ * acez_meshrender_check_faces' part, on a host copy of the faces (host only, no device needed): acezero_amd.meshrender calls it, or
+ * the same test on the device, before it renders.
+ * ACEZ_ERR_INVALID, before anything is launched, for: a null d_keys, d_depth, d_status, frame table or (with faces) d_faces or
+ * d_vertices; a colour plane without vertex colours; counts outside 0 .. 2^31 - 1; min_depth, max_depth or depth_unit not positive and
+ * finite; n_frames outside 0 .. 256; a row section K refuses, with offset + h * w beyond n_pixels or n_keys; |ppx| or |ppy| > 2^20
+ * (with the guard that keeps the int64 edge functions below 2^63). */
+#define ACEZ_MESHRENDER_SMALL 16      /* samples in the box up to which a lane walks it alone */
+#define ACEZ_MESHRENDER_LARGE 1024    /* samples in the box above which the workgroup walks it */
+int acez_meshrender_check_faces(const int32_t* h_faces, int64_t n_faces, int64_t n_vertices);
+int acez_meshrender(const float* d_vertices, const uint8_t* d_colours, int64_t n_vertices, const int32_t* d_faces, int64_t n_faces,
+                    const acez_tsdf_frame* h_frames, int n_frames, acez_tsdf_frame* d_frames, float min_depth, float max_depth,
+                    float depth_unit, unsigned long long* d_keys, int64_t n_keys, float* d_depth, int32_t* d_face, uint16_t* d_depth_u16,
+                    uint8_t* d_normal, uint8_t* d_colour, int64_t n_pixels, int32_t* d_status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
