@@ -1464,7 +1464,10 @@ extern "C" int acez_trainer_get_profile(acez_trainer* tr, float* h_ms8, int32_t*
 // layer `index` [n][512] bf16 (training: not kept for the last layer of a block, whose mask bits are); 1: dZ of layer `index` [n][512] bf16;
 // 2: residual stream `index` [n][512] bf16 (0 = the gathered batch); 3: weight-gradient slab `index` [n_wide] fp32; 4: bias-gradient partial
 // rows of layer `index` [max_blocks][512] fp32; 9: ReLU mask bits of layer `index` (RowGemmArgs::mask_out), 8 KiB per 80-row tile;
-// 10: the hand-off state, u32 [64][32] progress words + [32] the fault word's line + [64] the host's bases (seq_base).
+// 10: the hand-off state, u32 [64][32] progress words + [32] the fault word's line + [64] the host's bases (seq_base);
+// what the loss stage leaves behind or read (`index` must be 0): 11: its fc3 partials [16-row blocks][fc3_stride] fp32; 12: its statistics
+// partials [blocks][4] fp32; 13: the 16-bit copy of W3 [no][512]; 14: the per-row pose gradients row_dT [n][12] fp32; 15: row_image [n] i32;
+// 16: the refined poses the loss read, pose_cur [n_images][16] fp32 (14 - 16: pose refinement only).
 extern "C" int acez_trainer_debug_read(acez_trainer* tr, int kind, int index, void* h_out, int64_t bytes, void* stream) {
   ACEZ_REQUIRE(tr && h_out && bytes > 0, "null pointer");
   ACEZ_HIP_CHECK(hipSetDevice(tr->device));
@@ -1476,6 +1479,12 @@ extern "C" int acez_trainer_debug_read(acez_trainer* tr, int kind, int index, vo
   else if (kind == 2 && index >= 0 && index < tr->nb + 2) { src = tr->R[index]; cap = act_bytes; }
   else if (kind == 3 && index >= 0 && index < tr->nslabs && tr->slabs) { src = tr->slabs + (size_t)index * tr->n_wide; cap = tr->n_wide * 4; }
   else if (kind == 4 && index >= 0 && index < tr->L && tr->bias_partials) { src = tr->bias_partials + (size_t)index * tr->bias_layer_stride; cap = tr->bias_layer_stride * 4; }
+  else if (kind == 11 && index == 0 && tr->fc3_partials) { src = tr->fc3_partials; cap = (int64_t)loss_blocks(tr->max_batch) * tr->fc3_stride * 4; }
+  else if (kind == 12 && index == 0 && tr->stat_partials) { src = tr->stat_partials; cap = (int64_t)loss_blocks(tr->max_batch) * 4 * 4; }
+  else if (kind == 13 && index == 0 && tr->W3b) { src = tr->W3b; cap = (int64_t)tr->no * 512 * 2; }
+  else if (kind == 14 && index == 0 && tr->row_dT) { src = tr->row_dT; cap = (int64_t)tr->max_batch * 12 * 4; }
+  else if (kind == 15 && index == 0 && tr->row_image) { src = tr->row_image; cap = (int64_t)tr->max_batch * 4; }
+  else if (kind == 16 && index == 0 && tr->pose_cur && tr->have_buf) { src = tr->pose_cur; cap = (int64_t)tr->buf.n_images * 16 * 4; }
   else if (kind == 6 && tr->seq_xcc) { src = tr->seq_xcc; cap = (8 + 256) * 4; }
   else if (kind == 9 && index >= 0 && index < tr->L && tr->maskbits) { src = tr->maskbits + (size_t)index * tr->mask_stride; cap = (int64_t)tr->mask_stride * 8; }
   else if (kind == 7 && tr->wgo_trace) { src = tr->wgo_trace; cap = 256 * 12 * 8 * 8; }

@@ -385,18 +385,34 @@ class HeadTrainer:
         N.check(self.lib.acez_trainer_get_profile(self._h, ms.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(self.KERNEL_CLASSES)}
 
-    DEBUG_KINDS = {"out": 0, "dZ": 1, "R": 2, "slab": 3, "bias_partials": 4, "mask": 9}
+    DEBUG_KINDS = {"out": 0, "dZ": 1, "R": 2, "slab": 3, "bias_partials": 4, "mask": 9, "fc3_partials": 11, "stat_partials": 12, "W3": 13, "row_dT": 14, "row_image": 15,
+                   "pose_cur": 16}
 
     def debug_read(self, kind, index, rows):
         """Intermediate buffer of the last backward call (tests): 'out' / 'dZ' / 'R' -> uint16 [rows,512] (bf16 bit patterns),
         'slab' -> float32 [n_wide], 'bias_partials' -> float32 [rows,512], 'mask' -> uint32 [80-row tiles, 2048] (the lane-private ReLU
-        mask bits a training forward leaves per layer; the pre-residual activation of a block's last layer is not kept in training)."""
+        mask bits a training forward leaves per layer; the pre-residual activation of a block's last layer is not kept in training),
+        'fc3_partials' / 'stat_partials' -> float32 [rows = 16-row loss blocks, ...] (the loss kernel's partial sums), 'W3' -> uint16
+        [no,512] (the 16-bit compute copy of the fc3 weights), with pose refinement 'row_dT' -> float32 [rows,12], 'row_image' -> int32
+        [rows], 'pose_cur' -> float32 [rows = images,16]."""
         if kind in ("out", "dZ", "R"):
             out = np.zeros((rows, 512), np.uint16)
         elif kind == "mask":
             out = np.zeros(((rows + 79) // 80, 2048), np.uint32)
         elif kind == "slab":
             out = np.zeros(self.L * 262656, np.float32)
+        elif kind == "fc3_partials":     # rows = 16-row blocks of the loss kernel: [no][512] weight sums, then the no bias sums
+            out = np.zeros((rows, (self.no * 513 + 3) & ~3), np.float32)
+        elif kind == "stat_partials":    # rows = 16-row blocks: loss, inliers, focal gradient, unused
+            out = np.zeros((rows, 4), np.float32)
+        elif kind == "W3":               # the 16-bit compute copy of the fc3 weights (rows is ignored)
+            out = np.zeros((self.no, 512), np.uint16)
+        elif kind == "row_dT":           # pose refinement: the loss kernel's per-row pose gradients
+            out = np.zeros((rows, 12), np.float32)
+        elif kind == "row_image":
+            out = np.zeros(rows, np.int32)
+        elif kind == "pose_cur":         # rows = images: the refined world -> camera matrices the loss read
+            out = np.zeros((rows, 16), np.float32)
         else:
             out = np.zeros((rows, 512), np.float32)
         N.check(self.lib.acez_trainer_debug_read(self._h, self.DEBUG_KINDS[kind], int(index), out.ctypes.data_as(C.c_void_p),

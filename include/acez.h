@@ -463,7 +463,11 @@ int acez_trainer_set_step_chain(acez_trainer* tr, int enable);   /* default 1; m
  * words 0..7 = OR of 1 << XCC_ID over the workgroups with blockIdx & 7 = word, word 8 + 4 mt + nt = XCC_ID that ran tile
  * (mt, nt) in the last launch;  10: the hand-off state of the one-launch chains, u32 [64][32] progress words (word 8 nt + w of row
  * tile mt's line: the last seam wave w of column tile nt has completed) + [32] the line of the sticky fault word (word 0) + [64] the
- * host's seam bases per row tile; `bytes` must be exactly (64 * 32 + 32 + 64) * 4.  No reference counterpart (autograd internals). */
+ * host's seam bases per row tile; `bytes` must be exactly (64 * 32 + 32 + 64) * 4;  11: the loss kernel's fc3 partials, f32
+ * [16-row blocks][(513 no + 3) & ~3] (per block: no weight rows of 512, then no bias sums);  12: its statistics partials, f32
+ * [16-row blocks][4] (loss, inliers, focal gradient, unused);  13: the 16-bit compute copy of the fc3 weights, [no][512];  with pose
+ * refinement, 14: the loss kernel's per-row pose gradients, f32 [n][12];  15: the image of each row, i32 [n];  16: the refined poses
+ * the loss read, f32 [n_images][16]  (`index` must be 0 for 11 - 16).  No reference counterpart (autograd internals). */
 int acez_trainer_debug_read(acez_trainer* tr, int kind, int index, void* h_out, int64_t bytes, void* stream);
 
 /* Current refined world->cam poses of all images, f32 [n_images][3][4] (PoseRefiner.get_all_current_poses,

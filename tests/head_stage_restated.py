@@ -42,9 +42,10 @@ the factor 2 above is needed.
   * the unmasked residual gradient dR has no debug_read kind: where the mask bit is 1 it IS the stored dZ, elsewhere it is carried as
     the interval [round16(v_lo - s), round16(v_hi + s)] of the stage that produced it, and the consuming stage's v becomes an interval.
 
-Out of scope (they stay on the vector-norm bounds of tests/test_head_gpu.py): fc3 and the production of dZ[L - 1], which need the loss
-gradient dS; the loss; the pose network; the optimiser. dZ[L - 1] is an OPERAND here (of dZ[L - 2], of the last layer's weight and
-bias gradients), never an output.
+Out of scope here: fc3, the loss with all its branches and the production of dZ[L - 1] with the fc3 / bias / statistics partials, which
+tests/loss_stage_restated.py judges per row and per element (tests/test_loss_stage_gpu.py); the optimiser, pinned bit for bit by
+tests/test_adamw_exact_gpu.py; the pose network behind the loss kernel's pose gradient rows, which stays on the vector-norm bounds of
+tests/test_head_gpu.py. dZ[L - 1] is an OPERAND here (of dZ[L - 2], of the last layer's weight and bias gradients), never an output.
 """
 import numpy as np
 import torch

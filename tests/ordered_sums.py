@@ -40,3 +40,18 @@ def totals(partials, tile=256):
         part = partials[lo:lo + tile]
         v[:len(part)] = v[:len(part)] + part
     return block_sums(v, tile)[0]
+
+
+def lane_strided_totals(partials, nblk, inv_scale=None, swap=None, extra=0):
+    """head_opt.h tail_output in float32, bit for bit: lane j adds rows j, j + 64, .. of `partials` [>= nblk, k] in order from 0, then
+    the xor butterfly 32 .. 1 (wave_sums, which keeps the dtype of its input), then x inv_grad_scale where one is given. swap = (a, b):
+    those two rows exchanged; extra: rows past nblk included (the mutants of tests/test_loss_stage_cpu.py)."""
+    p = np.asarray(partials, np.float32)[:nblk + extra].copy()
+    if swap:
+        p[[swap[0], swap[1]]] = p[[swap[1], swap[0]]]
+    acc = np.zeros((WAVE, p.shape[1]), np.float32)
+    for b in range(p.shape[0]):
+        acc[b % WAVE] = acc[b % WAVE] + p[b]
+    tot = wave_sums(acc)
+    assert tot.dtype == np.float32
+    return tot if inv_scale is None else tot * np.float32(inv_scale)
